@@ -13,7 +13,7 @@ sites, inputs resident in HBM.  With N GPUs every rank holds its own shard of an
 (weak scaling; shards are flush-group aligned and carry the job offset, so the job's results do not
 depend on N) and each step ends with ONE gather of site_prob + mod_ratio to rank 0 over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload uniform|ragged] [--sites S] [--iters T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload uniform|ragged] [--sites S] [--iters T] [--dump-outputs DIR]
 
 `--gpus N` without a launcher starts its own N ranks (re-executes under torch.distributed.run on
 127.0.0.1); under torch.distributed.run (RANK/WORLD_SIZE set) it runs as one rank.  The 8-GPU run is
@@ -49,6 +49,11 @@ PEAK_LDS_GATHERS = 256 * 2.4e9 * 32
 
 # one multiply per draw; packed f32: 2 per lane per 4-cycle issue slot = the 157.3 TFLOP/s vector peak / 2 flops per FMA
 PEAK_VALU_MULS = PEAK_F32_TFLOPS * 1e12 / 2
+
+# --dump-outputs: at most 4 M read probabilities (16 MB) and 3 M sites (12 MB site_prob + 24 MB mod_ratio) are written
+DUMP_READS_MAX = 4_000_000
+DUMP_SITES_MAX = 3_000_000
+DUMP_SEEDS = {"read_prob": 1, "site_prob": 2, "mod_ratio": 2}
 
 
 def pool_roofline(variant, draws, avg_ms, launches):
@@ -590,9 +595,10 @@ class Bench:
         self.gather = mdist.SiteGather(self.cuts, self.dev, dst=0)
         self.gather_kind = "RCCL (torch.distributed)" + ("; native m6a_gather unavailable -- %s" % why if why else "")
 
-    def run(self, steps, warmup, min_seconds=0.0):
+    def run(self, steps, warmup, min_seconds=0.0, want_outputs=False):
         """Cold call, warm-up, the timed region (HIP events around the encoder launches inside it), extra steps with
-        events around the pooling launches; optionally a sustained leg of at least `min_seconds`."""
+        events around the pooling launches; optionally a sustained leg of at least `min_seconds`.  want_outputs: the results
+        of the timed region's last step are copied out right after it (Bench.outputs)."""
         eng = self.eng
         # the cold call: whatever the context did not set up at creation (flush-group offsets, output staging, tables of
         # bag sizes it could not know) is built inside
@@ -617,6 +623,7 @@ class Bench:
             self.gather.timing = True
         dt = self.timed(steps)
         own_dt = getattr(self, "own_dt", dt)
+        outputs = self.outputs() if want_outputs else None
         gather_ms = None
         if timing_gather:
             gather_ms, _ = self.gather.exchange_ms()
@@ -651,7 +658,29 @@ class Bench:
         dt, first_call_ms = self.max_over_ranks(dt, first_call_ms)
         return {"dt": dt, "first_call_ms": first_call_ms, "second_call_ms": second_call_ms, "enc_ms": enc_ms, "enc_n": enc_n, "pool_ms": pool_ms, "pool_n": pool_n,
                 "enc_clk": enc_clk, "pool_clk": pool_clk,
-                "sustained": sustained, "own_ms_per_step": own_dt / steps * 1e3, "gather_ms_per_step": gather_ms}
+                "sustained": sustained, "own_ms_per_step": own_dt / steps * 1e3, "gather_ms_per_step": gather_ms, "outputs": outputs}
+
+    def outputs(self):
+        """What the timed region's last step handed its caller, copied to the host (rank 0; None elsewhere): read_prob (this
+        rank's reads), site_prob and mod_ratio (the whole job's, gathered, when there is an exchange).  An array longer than
+        its cap is cut to a fixed seeded sample of positions, so the dump stays under 64 MB.
+        Returns {name: (host array, length of the full array, sorted sample positions or None)}."""
+        torch = self.torch
+        site, mod = self.gather.finish() if self.gather is not None else (self.site, self.mod)
+        if self.rank != 0:
+            return None
+
+        def take(t, cap, seed, idx=None):
+            n = int(t.numel())
+            if n <= cap:
+                return t.cpu().numpy(), n, None
+            if idx is None:
+                idx = np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+            return t[torch.from_numpy(idx).to(t.device)].cpu().numpy(), n, idx
+        out = {"read_prob": take(self.rp, DUMP_READS_MAX, DUMP_SEEDS["read_prob"])}
+        out["site_prob"] = take(site, DUMP_SITES_MAX, DUMP_SEEDS["site_prob"])
+        out["mod_ratio"] = take(mod, DUMP_SITES_MAX, DUMP_SEEDS["mod_ratio"], out["site_prob"][2])     # the same sites as site_prob
+        return out
 
     def certify(self, r, local_ms):
         """What makes an N-rank line checkable from the line alone (collective; returns the keys on rank 0): the communicator's
@@ -845,7 +874,12 @@ def main():
     ap.add_argument("--verify", action="store_true",
                     help="after the timed steps rank 0 recomputes the WHOLE job unsharded on its GPU and checks that the gathered "
                          "site_prob / mod_ratio equal it bit for bit (small --sites only: rank 0 holds the whole job)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their last step computed to DIR/<name>.npy: read_prob (float32), site_prob "
+                         "(float32), mod_ratio (float64); arrays above 4 M reads / 3 M sites are a fixed seeded sample of positions")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_main(args.workload, args.iters, budget_s=20.0)))
@@ -935,6 +969,18 @@ def main():
     emit()
 
 
+def dump_outputs(out_dir, outputs):
+    """Writes Bench.outputs() as <out_dir>/<name>.npy; returns what the bench line says about them."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, (a, n, idx) in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        arrays[name] = {"dtype": str(a.dtype), "shape": list(a.shape), "length": n,
+                        "sample": None if idx is None else "%d sorted positions drawn without replacement by numpy default_rng(%d)"
+                                                          % (len(idx), DUMP_SEEDS[name])}
+    return {"dir": os.path.abspath(out_dir), "step": "last timed step", "arrays": arrays}
+
+
 def run(args, line, rank, world, local_rank, S, bag, T):
     import torch
     from m6anet_amd import dist as mdist
@@ -970,7 +1016,9 @@ def run(args, line, rank, world, local_rank, S, bag, T):
 
     if os.environ.get("M6A_BENCH_TEST_KILL_RANK") == str(rank):   # test hook: this rank dies before the timed region
         os._exit(9)
-    r = b.run(args.steps, args.warmup, args.min_seconds)
+    r = b.run(args.steps, args.warmup, args.min_seconds, want_outputs=args.dump_outputs is not None)
+    if r["outputs"] is not None:
+        line["dump_outputs"] = dump_outputs(args.dump_outputs, r.pop("outputs"))
     cert = None
     if multi:
         # every rank made its cold call alone above; what run() timed first was only the first call WITH the exchange

@@ -51,7 +51,7 @@ def form(eng, rank, world, xdir, tag):
 
 
 def ragged_cuts(world):
-    sizes = [7, 0, 1233, 1, 0, 64, 3, 4097, 0, 31, 2, 500][:world]
+    sizes = [7, 0, 1, 1233, 0, 64, 3, 4097, 0, 31, 2, 500][:world]     # four ranks: an odd, an empty and a one-site shard + the last
     if world >= 2:
         sizes[-1] = 129                                  # the last rank never empty: it is a destination below
     return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)

@@ -188,7 +188,8 @@ int m6a_bag_forward(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, int
  * i.e. the legacy shuffle of arange(n), the stream seeded once with `seed` -- and predicts
  * y_pred[t][s] = 1 - prod_k (1 - p[read k of the sample]) (MILModel.forward, model.py:155-164).
  * y_pred [n_iters][n_sites]; y_pred_avg [n_sites] = np.mean(y_pred, axis=0) (training_utils.py:253)
- * or NULL.  Every bag needs >= n_samples reads (NumPy raises otherwise: M6A_EINVAL).  The sampler
+ * or NULL.  As in NumPy, the mean adds pass after pass when n_sites >= 2, and a single site takes NumPy's
+ * pairwise mean of its n_iters values.  Every bag needs >= n_samples reads (NumPy raises otherwise: M6A_EINVAL).  The sampler
  * is a sequential walk over one random stream and runs on the host; gathers, products and the
  * mean run on the GPU.  m6a_validate_pool starts from read probabilities, m6a_validate encodes
  * first (read_prob [R] or NULL).  Pointers: all host or all device, as everywhere. */

@@ -124,6 +124,7 @@ __global__ void iota_off_kernel(int64_t *off, int64_t n_plus_1, int64_t step);
 __global__ void rebase_off_kernel(const int64_t *off, int64_t count, int64_t *out);
 __global__ void sampled_noisy_or_kernel(const float *read_prob, const int32_t *gidx, int64_t n_bags, int k, float *y);
 __global__ void mean_over_passes_kernel(const float *y, int n_iters, int64_t n_sites, float *avg);
+__global__ void pairwise_mean_kernel(const float *y, int n_iters, float *avg);
 __global__ void bag_minmax_kernel(const int64_t *off, int64_t n_sites, unsigned long long *out, uint32_t *hist);
 __global__ void bag_verify_kernel(const unsigned long long *got, const uint32_t *hist, unsigned long long mn, unsigned long long mx,
                                   unsigned long long reads, unsigned long long hash, int *err);

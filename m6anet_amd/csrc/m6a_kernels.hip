@@ -17,7 +17,7 @@
 //                      sequence is then identical in every flush group, so it is a precomputed table
 //                      and the kernel is a pure LDS gather, 8 sites per pass.  (The default for uniform
 //                      bags is pool_reg_kernel in m6a_pool_reg.hip: bags in registers, no LDS at all.)
-//   sampled_noisy_or_kernel, mean_over_passes_kernel: the validation-style forward.
+//   sampled_noisy_or_kernel, mean_over_passes_kernel, pairwise_mean_kernel: the validation-style forward.
 //   bag_noisy_or_kernel, iota_off_kernel, bag_minmax_kernel: small helpers.
 //
 // Reference lines each kernel restates are cited at the kernel.  Wave = 64 lanes throughout.
@@ -1708,6 +1708,59 @@ __global__ void mean_over_passes_kernel(const float *y, int n_iters, int64_t n_s
     float acc = 0.0f;
     for (int t = 0; t < n_iters; t++) acc += y[(int64_t)t * n_sites + s];
     avg[s] = acc / (float)n_iters;
+}
+
+// np.mean(y, axis=0) of a float32 [n_iters][1]: NumPy drops the size-1 axis and reduces the contiguous column with its
+// pairwise sum (block 128, 8 accumulators, split at n/2 rounded down to a multiple of 8), then one divide.  ONE lane walks
+// the tree with an explicit stack (depth <= 25 for n < 2^31): ~n dependent loads and adds, a few microseconds per 1 000
+// passes.  Launched only for single-site validation calls; mean_over_passes_kernel takes every S >= 2.
+__device__ static float pairwise_leaf(const float *a, int64_t n)
+{
+    if (n < 8) {
+        float res = 0.0f;
+        for (int64_t i = 0; i < n; i++) res += a[i];
+        return res;
+    }
+    float r[8];
+    for (int k = 0; k < 8; k++) r[k] = a[k];
+    int64_t i = 8;
+    for (; i < n - (n % 8); i += 8)
+        for (int k = 0; k < 8; k++) r[k] += a[i + k];
+    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res += a[i];
+    return res;
+}
+
+__global__ void pairwise_mean_kernel(const float *y, int n_iters, float *avg)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    struct Frame { int64_t off, n; float left; bool right; };
+    Frame st[32];
+    int sp = 0;
+    st[0] = {0, n_iters, 0.0f, false};
+    float sum;
+    for (;;) {
+        Frame &f = st[sp];
+        if (f.n > 128) {                                  // descend into the left half first
+            const int64_t n2 = (f.n / 2) - (f.n / 2) % 8;
+            st[++sp] = {f.off, n2, 0.0f, false};
+            continue;
+        }
+        sum = pairwise_leaf(y + f.off, f.n);
+        // climb: a parent that has only its left half stores it and descends right; one with both returns left + right
+        for (;;) {
+            if (sp == 0) { avg[0] = sum / (float)n_iters; return; }
+            Frame &p = st[--sp];
+            const int64_t n2 = (p.n / 2) - (p.n / 2) % 8;
+            if (!p.right) {
+                p.left = sum;
+                p.right = true;
+                st[++sp] = {p.off + n2, p.n - n2, 0.0f, false};
+                break;
+            }
+            sum = p.left + sum;
+        }
+    }
 }
 
 // out[i] = off[i] - off[0]: the CSR row of a chunk of sites, rebased to the chunk's first read

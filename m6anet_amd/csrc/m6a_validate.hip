@@ -277,7 +277,10 @@ int launch_validate_pool(m6a_ctx *c, const float *d_rp, const int64_t *h_off, in
     prof_begin(c, 1);
     hipLaunchKernelGGL(sampled_noisy_or_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream,
                        d_rp, (const int32_t *)c->val_idx.p, nb, K, d_y);
-    if (d_avg)
+    // np.mean(y_pred, axis=0): pass after pass for S >= 2; a single site's column is reduced with NumPy's pairwise sum
+    if (d_avg && S == 1)
+        hipLaunchKernelGGL(pairwise_mean_kernel, dim3(1), dim3(64), 0, c->stream, (const float *)d_y, T, d_avg);
+    else if (d_avg)
         hipLaunchKernelGGL(mean_over_passes_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream,
                            (const float *)d_y, T, S, d_avg);
     prof_end(c, 1);

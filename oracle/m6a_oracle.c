@@ -474,9 +474,13 @@ int m6a_or_validate(const float *read_prob, const int64_t *off, int64_t n_sites,
                 for (int j = 0; j < k; j++) prod *= (1.0f - read_prob[off[s] + row[j]]);
                 y_pred[(int64_t)t * n_sites + s] = 1.0f - prod;
             }
-        if (y_pred_avg)
+        if (y_pred_avg && n_sites == 1) {
+            /* np.mean(axis=0) of a (T,1) array: NumPy drops the size-1 axis and reduces the contiguous column with its
+             * pairwise sum */
+            y_pred_avg[0] = m6a_or_pairwise_sum_f32(y_pred, n_iters) / (float)n_iters;
+        } else if (y_pred_avg)
             for (int64_t s = 0; s < n_sites; s++) {
-                float acc = 0.0f;                 /* np.mean(axis=0) of a C-contiguous (T,S) array: row by row */
+                float acc = 0.0f;                 /* np.mean(axis=0) of a C-contiguous (T,S) array, S >= 2: row by row */
                 for (int t = 0; t < n_iters; t++) acc += y_pred[(int64_t)t * n_sites + s];
                 y_pred_avg[s] = acc / (float)n_iters;
             }

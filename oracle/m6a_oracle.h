@@ -90,7 +90,8 @@ int m6a_or_validation_indices(uint32_t seed, const int64_t *off, int64_t n_sites
 
 /* validate()'s predictions (training_utils.py:233-250): y_pred[t][s] = 1 - prod_k (1 - p[off[s]+idx[t][s][k]])
  * (float32, left to right: MILModel.forward -> SigmoidProdPooling, pooling_blocks.py:127-129), and
- * y_pred_avg = np.mean(y_pred, axis=0): float32, pass after pass, then one divide. */
+ * y_pred_avg = np.mean(y_pred, axis=0): float32, pass after pass, then one divide; a single site (NumPy drops the
+ * size-1 axis) takes the pairwise sum of its n_iters values, then one divide. */
 int m6a_or_validate(const float *read_prob, const int64_t *off, int64_t n_sites, int n_iters, int k,
                     uint32_t seed, float *y_pred, float *y_pred_avg);
 

@@ -178,7 +178,7 @@ def test_validation_sampler_and_predictions_vs_reference_validate(golden, key, s
         # batch_size 1: torch's sgemm on 20-row batches rounds a few read probabilities differently (1 ulp)
         assert np.abs(y - g[key + "_y_pred"]).max() <= 2.4e-7
         assert np.abs(avg - g[key + "_y_pred_avg"]).max() <= 2.4e-7
-    # the mean is float32, pass after pass (np.mean over axis 0 of a C-contiguous array)
+    # the mean is float32, pass after pass for S >= 2 (np.mean over axis 0 of a C-contiguous array)
     acc = np.zeros(y.shape[1], np.float32)
     for row in g[key + "_y_pred"]:
         acc = acc + row
@@ -199,3 +199,119 @@ def test_validation_metrics_mirror(golden, key, seed, T, same_batching):
     assert abs(tu.get_roc_auc(y, avg) - float(g[key + "_roc_auc"])) < 1e-12
     assert abs(tu.get_pr_auc(y, avg) - float(g[key + "_pr_auc"])) < 1e-12
     assert abs(tu.binary_cross_entropy(avg, y) - float(g[key + "_avg_loss"])) < 1e-6
+
+
+# ------------------------------------------------------------------ plain NumPy statements, and the oracle held to them -----
+# The evaluation half and single-group pooling written from their documented semantics (include/m6a.h: m6a_validate,
+# m6a_site_pool) with NumPy doing the arithmetic, so NumPy's own reduction rules apply.  tests/test_gpu_eval_and_edges.py
+# holds the HIP kernels to the same statements.
+def np_validate(rp, off, T, seed, k=20):
+    """(y_pred [T][S], y_pred_avg [S]): one RandomState for the call; pass after pass, site after site,
+    choice(n, k, replace=False); 1 - the float32 product of 1 - p, left to right; np.mean(y_pred, axis=0)."""
+    rp = np.asarray(rp, np.float32)
+    off = np.asarray(off, np.int64)
+    S = len(off) - 1
+    rs = np.random.RandomState(seed)
+    vals = np.empty((T, S, k), np.float32)
+    for t in range(T):
+        for s in range(S):
+            vals[t, s] = rp[off[s] + rs.choice(int(off[s + 1] - off[s]), k, replace=False)]
+    prod = np.ones((T, S), np.float32)
+    for j in range(k):
+        prod = prod * (np.float32(1) - vals[:, :, j])
+    y = np.float32(1) - prod
+    return y, np.mean(y, axis=0)
+
+
+def np_pool_one_group(rp, off, T, thr, seed, K=20):
+    """(site [S], mod_ratio [S]) of one flush group (save_per_batch = 1): one RandomState; per site
+    mod = np.mean(x >= thr), then choice(x, T*K) reshaped (T, K), 1 - prod along axis 1, mean."""
+    rp = np.asarray(rp, np.float32)
+    off = np.asarray(off, np.int64)
+    S = len(off) - 1
+    rs = np.random.RandomState(seed)
+    site, mod = np.empty(S, np.float32), np.empty(S, np.float64)
+    for s in range(S):
+        x = rp[off[s]:off[s + 1]]
+        mod[s] = np.mean(x >= thr)
+        v = rs.choice(x, T * K, replace=True).reshape(T, K)
+        site[s] = (1 - np.prod(1 - v, axis=1)).mean()
+    return site, mod
+
+
+# read probabilities a kernel can get wrong without random inputs noticing: NaN (the encoder turns a NaN feature into
+# one), the threshold and its float neighbours (mod_ratio counts p >= thr), both zeros, one, subnormals
+THR_EDGE = np.array([THR, np.nextafter(THR, np.float32(1)), np.nextafter(THR, np.float32(0))], np.float32)
+SPECIALS = np.array([0.0, -0.0, 1.0, 1e-45, 1.1754942e-38, np.finfo(np.float32).tiny, THR,
+                     np.nextafter(THR, np.float32(1)), np.nextafter(THR, np.float32(0))], np.float32)
+
+
+def edge_probs(bags, seed):
+    """(read_prob, off): skewed random probabilities; site s is, by s % 4,
+    0: only thr and its two neighbours;  1: NaN at one random read plus the specials;  2: the specials, no NaN;
+    3: random reads with thr at one of them."""
+    bags = np.asarray(bags, np.int64)
+    off = np.concatenate([[0], np.cumsum(bags)]).astype(np.int64)
+    g = np.random.Generator(np.random.PCG64(seed))
+    p = (g.random(int(off[-1]), dtype=np.float32) ** 4).astype(np.float32)
+    for s, n in enumerate(bags.tolist()):
+        if n == 0:
+            continue
+        x = p[off[s]:off[s + 1]]
+        pos = g.permutation(n)
+        kind = s % 4
+        if kind == 0:
+            x[:] = THR_EDGE[(np.arange(n) + s // 4) % 3]
+        elif kind == 1:
+            x[pos[0]] = np.nan
+            m = min(n - 1, SPECIALS.size)
+            x[pos[1:1 + m]] = SPECIALS[(np.arange(m) + s) % SPECIALS.size]
+        elif kind == 2:
+            m = min(n, SPECIALS.size)
+            x[pos[:m]] = SPECIALS[(np.arange(m) + s) % SPECIALS.size]
+        else:
+            x[pos[0]] = THR
+    return p, off
+
+
+@pytest.mark.parametrize("T", [1, 7, 8, 9, 24, 129, 1000, 4099])
+@pytest.mark.parametrize("n", [25, 64])
+def test_validate_single_site_is_numpy_mean(T, n):
+    """One site: np.mean(y_pred, axis=0) of a (T, 1) array drops the size-1 axis and takes NumPy's pairwise mean of the
+    column, not the pass-after-pass sum of S >= 2."""
+    p = (np.random.Generator(np.random.PCG64(T * 100 + n)).random(n, dtype=np.float32) ** 4).astype(np.float32)
+    off = np.array([0, n], np.int64)
+    y, avg = orc.validate(p, off, T, seed=T)
+    want_y, want_avg = np_validate(p, off, T, T)
+    assert np.array_equal(y, want_y)
+    assert np.array_equal(avg, want_avg), (avg, want_avg)
+
+
+MASK_BAGS = [31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097]
+# (bags, T, k, seed): bag sizes at the sampler's mask boundaries, a bag above 2^16, k = 1 .. 64 and k equal to the bag size
+VAL_NUMPY_CASES = [(MASK_BAGS, 5, 20, 0), (MASK_BAGS, 3, 1, 2**31), (MASK_BAGS, 3, 7, 2**32 - 1), (MASK_BAGS, 4, 21, 0),
+                   (MASK_BAGS[4:], 3, 64, 2**31), ([70000, 20, 65536, 21], 2, 20, 2**32 - 1), ([20] * 50, 7, 20, 0),
+                   ([7, 9, 7, 30], 5, 7, 2**31), ([64, 64, 100], 3, 64, 2**32 - 1), ([1, 1, 3], 4, 1, 0), ([21, 40] * 30, 9, 21, 0)]
+
+
+@pytest.mark.parametrize("bags,T,k,seed", VAL_NUMPY_CASES)
+def test_validate_vs_numpy(bags, T, k, seed):
+    p, off = edge_probs(bags, len(bags) + k)
+    y, avg = orc.validate(p, off, T, seed=seed, k=k)
+    want_y, want_avg = np_validate(p, off, T, seed, k)
+    assert np.array_equal(y, want_y, equal_nan=True)
+    assert np.array_equal(avg, want_avg, equal_nan=True)
+
+
+@pytest.mark.parametrize("T", [1, 3, 50, 1000])
+def test_pool_special_values_vs_numpy(T):
+    """One flush group (save_per_batch = 1): site probabilities (which sites come out NaN included) and mod_ratio of
+    bags holding NaN, the threshold and its neighbours, zeros, one and subnormals, against the NumPy statement."""
+    bags = np.repeat([1, 2, 20, 33, 64, 200], 4)            # every bag size with every kind of edge_probs
+    p, off = edge_probs(bags, T)
+    assert np.isnan(p[off[1]])                              # a one-read site holding NaN
+    site, mod = orc.site_pool(p, off, T, THR, seed=T, save_per_batch=1)
+    want_site, want_mod = np_pool_one_group(p, off, T, THR, T)
+    assert np.array_equal(site, want_site, equal_nan=True)
+    assert np.array_equal(mod, want_mod)
+    assert np.isnan(site[1]) and not np.isnan(site).all()

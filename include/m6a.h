@@ -37,7 +37,9 @@ enum {
     M6A_EHIP = -3,       /* HIP runtime error (text in m6a_last_error) */
     M6A_ESTREAM = -4,    /* a flush group needs more MT19937 words than the stream cap allows */
     M6A_ENODEV = -5,     /* no usable gfx950 device */
-    M6A_EUNSUPPORTED = -6
+    M6A_EUNSUPPORTED = -6,
+    M6A_EFORMAT = -7,    /* malformed input file (m6a_prep_eventalign) */
+    M6A_EIO = -8         /* a file cannot be opened or read (m6a_prep_eventalign) */
 };
 
 /* rng_mode of m6a_site_pool / m6a_infer / m6a_job_begin.  M6A_RNG_NUMPY is the ONLY value: exact replay of the reference's
@@ -315,6 +317,26 @@ int m6a_set_table_variant(m6a_ctx *ctx, int mode);
 const char *m6a_last_pool_variant(const m6a_ctx *ctx);
 
 const char *m6a_version(void);
+
+/* `dataprep --device gpu` (m6anet/scripts/dataprep.py:54-70; include/m6a_io.h for the host half).  Streams eventalign.txt into HBM
+ * on device device_id and computes what m6a_io_dataprep_rows computes on the host: the index runs (or, with index_path non-NULL,
+ * the rows of that eventalign.index) and every run's candidate rows, as an m6a_io_prep_table that m6a_io_dataprep_write turns
+ * into eventalign.index, data.json, data.info and data.log, byte-identical to m6a_io_dataprep.  Needs no weights and no ctx.
+ * The whole file stays resident: device memory is capped at free memory minus a margin (M6A_PREP_BUDGET_MB lowers it), and a file
+ * that does not fit is M6A_ENOMEM, with text that names --device cpu.  M6A_PREP_CHUNK_KB (default 65536, rounded up to 4 KB)
+ * sets the size of the pinned upload chunks.  Runs the device declines (numbers outside the fast paths, events out of key order,
+ * malformed lines) are marked M6A_PREP_RUN_HOST; the writer combines them on the host.  Errors: M6A_EFORMAT for a file without a
+ * header line or a line with fewer than three tabs (the host's M6A_IO_EFORMAT), M6A_EIO for a missing file or index; the text is
+ * in m6a_prep_last_error() (thread-local). */
+typedef struct m6a_prep m6a_prep;
+struct m6a_io_prep_table;
+int m6a_prep_eventalign(int device_id, const char *path, int n_neighbors, const char *index_path, m6a_prep **out);
+const struct m6a_io_prep_table *m6a_prep_table(const m6a_prep *p);    /* owned by p */
+/* milliseconds of the phases: [0] upload + newline count, [1] newline offsets, [2] lines, runs, combine and windows, [3] results to
+ * the host, [4] the host's run table; [5] = the upload's rate in GB/s (file bytes / [0]) */
+int m6a_prep_times(const m6a_prep *p, double *ms6);
+void m6a_prep_free(m6a_prep *p);
+const char *m6a_prep_last_error(void);
 
 #ifdef __cplusplus
 }

@@ -127,6 +127,47 @@ int m6a_io_dataprep(const char *eventalign_path, const char *out_dir, int n_thre
                     int readcount_min, int readcount_max, int min_segment_count, int n_neighbors,
                     int compress, int skip_index);
 
+/* The two halves of m6a_io_dataprep, for producers other than the host (`dataprep --device gpu`: m6a_prep_eventalign in
+ * m6a.h returns the same table).  A table of plain arrays, owned by whoever made it:
+ *   transcripts  name t = tx_blob[tx_off[t], tx_off[t + 1]), ids in order of first appearance;
+ *   runs         the rows of eventalign.index in file order: run_tx, run_read, byte range [run_start, run_end);
+ *                run_npos = number of combined (position, k-mer) groups; run_status M6A_PREP_RUN_OK, or M6A_PREP_RUN_HOST
+ *                where the producer declined the run (a number outside the fast paths, events out of key order, a
+ *                malformed line): m6a_io_dataprep_write combines it on the host, and its npos and rows are not read;
+ *   rows         candidate windows, CSR by run (row_off[n_runs + 1]), in position order inside a run: row_pos = centre
+ *                position (position + 2), row_kmer (5 + 2 n_neighbors) characters without terminator, row_feat
+ *                3 (2 n_neighbors + 1) doubles, [dwell, sd, mean] per position from the first to the last of the window.
+ * The candidate rows of a run are everything preprocess_tx derives from that run alone; the readcount cut, one run per
+ * read (the last), n_pos > 1, the sort by position, min_segment_count and the text are m6a_io_dataprep_write's. */
+enum { M6A_PREP_RUN_OK = 0, M6A_PREP_RUN_HOST = 1 };
+typedef struct m6a_io_prep_table {
+    int n_neighbors;
+    int64_t n_tx;
+    const char *tx_blob;
+    const int64_t *tx_off;          /* [n_tx + 1] */
+    int64_t n_runs;
+    const uint32_t *run_tx;
+    const int64_t *run_read, *run_start, *run_end, *run_npos;
+    const int32_t *run_status;
+    const int64_t *row_off;         /* [n_runs + 1] */
+    int64_t n_rows;
+    const int64_t *row_pos;
+    const char *row_kmer;           /* [n_rows][5 + 2 n_neighbors] */
+    const double *row_feat;         /* [n_rows][3 (2 n_neighbors + 1)] */
+} m6a_io_prep_table;
+
+typedef struct m6a_io_rows m6a_io_rows;
+/* The table on the host: the index (or, with index_path non-NULL, the rows of that eventalign.index) and every run's
+ * candidate rows (no run is declined).  Errors are those of m6a_io_dataprep's index phase. */
+int m6a_io_dataprep_rows(const char *eventalign_path, const char *index_path, int n_threads, int n_neighbors, m6a_io_rows **out);
+const m6a_io_prep_table *m6a_io_rows_table(const m6a_io_rows *r);
+void m6a_io_rows_free(m6a_io_rows *r);
+/* The four files of m6a_io_dataprep from a table, whoever made it: eventalign.index from the runs (write_index != 0; with
+ * skip_index the file is left as it is), data.json / data.info / data.log through the same per-transcript code.  Reads
+ * eventalign_path only for the runs marked M6A_PREP_RUN_HOST. */
+int m6a_io_dataprep_write(const char *eventalign_path, const char *out_dir, const m6a_io_prep_table *table, int n_threads,
+                          int readcount_min, int readcount_max, int min_segment_count, int compress, int write_index);
+
 #ifdef __cplusplus
 }
 #endif

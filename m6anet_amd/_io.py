@@ -9,8 +9,32 @@ LIB_PATH = os.environ.get("M6A_IO_LIB") or os.path.join(_PKG, "libm6a_io.so")   
 SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_sites", "m6a_io_n_reads",
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
-           "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep"]
+           "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
+           "m6a_io_rows_free", "m6a_io_dataprep_write"]
 _lib = None
+
+
+class PrepTable(C.Structure):
+    """m6a_io_prep_table (include/m6a_io.h): the runs and candidate rows of a dataprep, as plain arrays."""
+    _fields_ = [("n_neighbors", C.c_int), ("n_tx", C.c_int64), ("tx_blob", C.c_void_p), ("tx_off", C.c_void_p),
+                ("n_runs", C.c_int64), ("run_tx", C.c_void_p), ("run_read", C.c_void_p), ("run_start", C.c_void_p),
+                ("run_end", C.c_void_p), ("run_npos", C.c_void_p), ("run_status", C.c_void_p), ("row_off", C.c_void_p),
+                ("n_rows", C.c_int64), ("row_pos", C.c_void_p), ("row_kmer", C.c_void_p), ("row_feat", C.c_void_p)]
+
+
+def table_arrays(t):
+    """Copies of a PrepTable's arrays as numpy: names, runs (tx, read, start, end, npos, status), row_off, rows (pos, kmer, feat)."""
+    def arr(ptr, ctype, n):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, np.dtype(ctype))
+    nt, nr, nrow = t.n_tx, t.n_runs, t.n_rows
+    K, NF = 5 + 2 * t.n_neighbors, 3 * (2 * t.n_neighbors + 1)
+    tx_off = arr(t.tx_off, C.c_int64, nt + 1)
+    blob = C.string_at(t.tx_blob, int(tx_off[-1])) if nt else b""
+    return dict(names=[blob[tx_off[i]:tx_off[i + 1]].decode() for i in range(nt)],
+                run_tx=arr(t.run_tx, C.c_uint32, nr), run_read=arr(t.run_read, C.c_int64, nr), run_start=arr(t.run_start, C.c_int64, nr),
+                run_end=arr(t.run_end, C.c_int64, nr), run_npos=arr(t.run_npos, C.c_int64, nr), run_status=arr(t.run_status, C.c_int32, nr),
+                row_off=arr(t.row_off, C.c_int64, nr + 1) if nr else np.zeros(1, np.int64), row_pos=arr(t.row_pos, C.c_int64, nrow),
+                row_kmer=arr(t.row_kmer, C.c_uint8, nrow * K).reshape(nrow, K), row_feat=arr(t.row_feat, C.c_double, nrow * NF).reshape(nrow, NF))
 
 
 class M6AIOError(RuntimeError):
@@ -59,6 +83,12 @@ def load():
     L.m6a_io_store_tag.argtypes = [vp]
     L.m6a_io_store_tag.restype = C.c_char_p
     L.m6a_io_dataprep.argtypes = [C.c_char_p, C.c_char_p, i32, i32, i32, i32, i32, i32, i32]
+    L.m6a_io_dataprep_rows.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
+    L.m6a_io_rows_table.argtypes = [vp]
+    L.m6a_io_rows_table.restype = C.POINTER(PrepTable)
+    L.m6a_io_rows_free.argtypes = [vp]
+    L.m6a_io_rows_free.restype = None
+    L.m6a_io_dataprep_write.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PrepTable), i32, i32, i32, i32, i32, i32]
     _lib = L
     return L
 
@@ -84,12 +114,70 @@ def _chk(rc):
 
 
 def dataprep(eventalign, out_dir, n_threads=0, readcount_min=1, readcount_max=1000, min_segment_count=20,
-             n_neighbors=1, compress=False, skip_index=False):
-    """Native `m6anet dataprep` (m6anet/scripts/dataprep.py:54-70)."""
+             n_neighbors=1, compress=False, skip_index=False, device="cpu", device_id=0):
+    """Native `m6anet dataprep` (m6anet/scripts/dataprep.py:54-70).  device="gpu": the line scan, parse, combine and windows run
+    in HIP (m6a_prep_eventalign, include/m6a.h) and the host writes the same four files from their table
+    (m6a_io_dataprep_write); a file larger than the device budget is an error, never a silent host run."""
+    if device not in ("cpu", "gpu"):
+        raise ValueError("device must be 'cpu' or 'gpu', not %r" % (device,))
     os.makedirs(out_dir, exist_ok=True)
-    _chk(load().m6a_io_dataprep(os.fsencode(eventalign), os.fsencode(out_dir), int(n_threads), int(readcount_min),
-                                int(readcount_max), int(min_segment_count), int(n_neighbors), 1 if compress else 0,
-                                1 if skip_index else 0))
+    if device == "cpu":
+        _chk(load().m6a_io_dataprep(os.fsencode(eventalign), os.fsencode(out_dir), int(n_threads), int(readcount_min),
+                                    int(readcount_max), int(min_segment_count), int(n_neighbors), 1 if compress else 0,
+                                    1 if skip_index else 0))
+        return
+    with prep_on_device(eventalign, n_neighbors, os.path.join(out_dir, "eventalign.index") if skip_index else None, device_id) as table:
+        write_table(eventalign, out_dir, table, n_threads, readcount_min, readcount_max, min_segment_count, compress, not skip_index)
+
+
+def write_table(eventalign, out_dir, table, n_threads=0, readcount_min=1, readcount_max=1000, min_segment_count=20, compress=False,
+                write_index=True):
+    """m6a_io_dataprep_write: the four files from a PrepTable (a pointer to one, or the structure)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ptr = table if isinstance(table, C._Pointer) else C.pointer(table)
+    _chk(load().m6a_io_dataprep_write(os.fsencode(eventalign), os.fsencode(out_dir), ptr, int(n_threads), int(readcount_min),
+                                      int(readcount_max), int(min_segment_count), 1 if compress else 0, 1 if write_index else 0))
+
+
+class host_rows:
+    """m6a_io_dataprep_rows as a context manager: yields the table (a pointer to PrepTable), freed on exit."""
+
+    def __init__(self, eventalign, n_neighbors=1, index_path=None, n_threads=0):
+        L = load()
+        self._h = C.c_void_p()
+        _chk(L.m6a_io_dataprep_rows(os.fsencode(eventalign), None if index_path is None else os.fsencode(index_path), int(n_threads),
+                                    int(n_neighbors), C.byref(self._h)))
+        self.table = L.m6a_io_rows_table(self._h)
+
+    def __enter__(self):
+        return self.table
+
+    def __exit__(self, *exc):
+        load().m6a_io_rows_free(self._h)
+        self._h = None
+
+
+class prep_on_device:
+    """m6a_prep_eventalign (libm6a_hip.so) as a context manager: yields the device-made table, freed on exit.  Errors are
+    M6AIOError with the m6a_io code of the same failure on the host path (EFORMAT for a short line, EIO for a missing index)."""
+    _CODES = {-1: -1, -2: -2, -7: -4, -8: -3}       # M6A_EFORMAT -> M6A_IO_EFORMAT, M6A_EIO -> M6A_IO_EIO
+
+    def __init__(self, eventalign, n_neighbors=1, index_path=None, device_id=0):
+        from . import _lib
+        L = _lib.load()
+        self._L, self._h = L, C.c_void_p()
+        rc = L.m6a_prep_eventalign(int(device_id), os.fsencode(eventalign), int(n_neighbors),
+                                   None if index_path is None else os.fsencode(index_path), C.byref(self._h))
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        self.table = C.cast(L.m6a_prep_table(self._h), C.POINTER(PrepTable))
+
+    def __enter__(self):
+        return self.table
+
+    def __exit__(self, *exc):
+        self._L.m6a_prep_free(self._h)
+        self._h = None
 
 
 def _weakrefable(x):

@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("M6A_HIP_LIB") or os.path.join(_PKG, "libm6a_hip.so") 
 
 M6A_OK = 0
 ERRORS = {-1: "M6A_EINVAL", -2: "M6A_ENOMEM", -3: "M6A_EHIP", -4: "M6A_ESTREAM", -5: "M6A_ENODEV",
-          -6: "M6A_EUNSUPPORTED"}
+          -6: "M6A_EUNSUPPORTED", -7: "M6A_EFORMAT", -8: "M6A_EIO"}
 RNG_NUMPY = 0
 
 # every symbol include/m6a.h declares (tests check the .so exports exactly these)
@@ -16,7 +16,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_encode_reads", "m6a_site_pool", "m6a_infer", "m6a_job_begin", "m6a_job_feed", "m6a_job_feed_collated", "m6a_job_size", "m6a_job_end", "m6a_job_abort", "m6a_bag_forward", "m6a_validate_pool", "m6a_validate", "m6a_flush_groups",
            "m6a_reference_written_sites",
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
-           "m6a_version"]
+           "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error"]
 
 _lib = None
 
@@ -117,6 +117,14 @@ def load():
     L.m6a_last_pool_variant.argtypes = [vp]
     L.m6a_last_pool_variant.restype = C.c_char_p
     L.m6a_version.restype = C.c_char_p
+    L.m6a_prep_eventalign.argtypes = [i32, C.c_char_p, i32, C.c_char_p, C.POINTER(vp)]
+    L.m6a_prep_table.argtypes = [vp]
+    L.m6a_prep_table.restype = vp
+    L.m6a_prep_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.m6a_prep_free.argtypes = [vp]
+    L.m6a_prep_free.restype = None
+    L.m6a_prep_last_error.argtypes = []
+    L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("m6a_flush_groups", "m6a_reference_written_sites"):

@@ -1293,6 +1293,10 @@ struct TxOut {
     std::string err;
 };
 
+void window_rows(const std::vector<Pos> &ps, int w, long long rd, std::vector<SiteRow> &sites, std::vector<double> &feat);
+void emit_transcript(const std::string &tx, std::vector<SiteRow> &sites, const std::vector<double> &feat, int min_segment_count,
+                     int w, int compress, TxOut &o);
+
 // One transcript: combine -> runs of consecutive positions -> +-w window -> DRACH centre -> group by position
 // (parallel_preprocess_tx :328-396 + preprocess_tx :399-488 + filter_events :51-168)
 void preprocess_transcript(const char *base, size_t file_size, const std::string &tx, const std::vector<IdxRun> &idx,
@@ -1317,33 +1321,46 @@ void preprocess_transcript(const char *base, size_t file_size, const std::string
     }
     if (readcount < readcount_min) return;
     o.wanted = true;
-    const size_t W = (size_t)w, NF = 3 * (2 * W + 1);
     std::vector<SiteRow> sites;
     std::vector<double> feat;
-    for (long long rd : read_order) {
-        const std::vector<Pos> &ps = by_read[rd];     // sorted by position already
-        size_t a = 0;
-        while (a < ps.size()) {                       // runs of consecutive positions (partition_into_continuous_positions)
-            size_t b = a + 1;
-            while (b < ps.size() && ps[b].position == ps[b - 1].position + 1) ++b;
-            if (b - a >= 2 * W + 1) {
-                for (size_t i = a + W; i + W < b; i++) {
-                    if (!is_drach(ps[i].kmer)) continue;
-                    SiteRow sr;
-                    sr.pos = ps[i].position + 2;      // centre of the 5-mer
-                    sr.kmer.assign(ps[i - W].kmer);   // combine_sequence: first 5-mer + the last base of every later one
-                    for (size_t k = i - W + 1; k <= i + W; k++) sr.kmer += ps[k].kmer.back();
-                    sr.f = feat.size();
-                    for (size_t k = i - W; k <= i + W; k++) {      // roll(): previous ..., centre, next ...; [dwell, sd, mean] each
-                        feat.push_back(ps[k].dwell); feat.push_back(ps[k].sd); feat.push_back(ps[k].mean);
-                    }
-                    sr.read = rd;
-                    sites.push_back(std::move(sr));
+    for (long long rd : read_order) window_rows(by_read[rd], w, rd, sites, feat);
+    emit_transcript(tx, sites, feat, min_segment_count, w, compress, o);
+}
+
+// The front half of a transcript, per read: one run's combined positions (sorted by position) -> its candidate rows
+// (partition_into_continuous_positions, roll, combine_sequence and the DRACH test: dataprep_utils.py:51-67,117-183)
+void window_rows(const std::vector<Pos> &ps, int w, long long rd, std::vector<SiteRow> &sites, std::vector<double> &feat)
+{
+    const size_t W = (size_t)w;
+    size_t a = 0;
+    while (a < ps.size()) {                           // runs of consecutive positions (partition_into_continuous_positions)
+        size_t b = a + 1;
+        while (b < ps.size() && ps[b].position == ps[b - 1].position + 1) ++b;
+        if (b - a >= 2 * W + 1) {
+            for (size_t i = a + W; i + W < b; i++) {
+                if (!is_drach(ps[i].kmer)) continue;
+                SiteRow sr;
+                sr.pos = ps[i].position + 2;          // centre of the 5-mer
+                sr.kmer.assign(ps[i - W].kmer);       // combine_sequence: first 5-mer + the last base of every later one
+                for (size_t k = i - W + 1; k <= i + W; k++) sr.kmer += ps[k].kmer.back();
+                sr.f = feat.size();
+                for (size_t k = i - W; k <= i + W; k++) {          // roll(): previous ..., centre, next ...; [dwell, sd, mean] each
+                    feat.push_back(ps[k].dwell); feat.push_back(ps[k].sd); feat.push_back(ps[k].mean);
                 }
+                sr.read = rd;
+                sites.push_back(std::move(sr));
             }
-            a = b;
         }
+        a = b;
     }
+}
+
+// The back half of a transcript: its candidate rows (reads in data_dict order, positions ascending inside a read) -> the
+// records of data.json and data.info (preprocess_tx :415-488)
+void emit_transcript(const std::string &tx, std::vector<SiteRow> &sites, const std::vector<double> &feat, int min_segment_count,
+                     int w, int compress, TxOut &o)
+{
+    const size_t NF = 3 * (2 * (size_t)w + 1);
     if (sites.empty()) return;                        // preprocess_tx returns before its log line (dataprep_utils.py:415,431)
     o.logged = true;
     // reference: np.argsort(positions) (unstable, machine-dependent order inside a position);
@@ -1385,6 +1402,55 @@ void preprocess_transcript(const char *base, size_t file_size, const std::string
         }
         i = j;
     }
+}
+
+// preprocess_transcript over a table (m6a_io_dataprep_write): the same cut, de-duplication and back half, with the front half's
+// rows taken from the table -- or, for a run its producer declined, computed here as preprocess_transcript computes them
+void preprocess_transcript_rows(const char *base, size_t file_size, const std::string &tx, const std::vector<IdxRun> &idx,
+                                const std::vector<uint32_t> &rows, const m6a_io_prep_table &T, int readcount_min, int readcount_max,
+                                int min_segment_count, int compress, TxOut &o)
+{
+    struct Src { uint32_t run; std::vector<Pos> ps; };   // ps: the host's combine of a declined run
+    std::vector<long long> read_order;
+    std::unordered_map<long long, Src> by_read;
+    int readcount = 0;
+    for (uint32_t ri : rows) {
+        const IdxRun &r = idx[ri];
+        if (r.start < 0 || r.end > (int64_t)file_size || r.start > r.end) { o.rc = M6A_IO_EFORMAT; o.err = "index row outside eventalign.txt"; return; }
+        Src src{ri, {}};
+        int64_t npos;
+        if (T.run_status[ri] == M6A_PREP_RUN_OK) {
+            npos = T.run_npos[ri];
+        } else {
+            if (!combine_read(base + r.start, base + r.end, base + file_size, src.ps)) { o.rc = M6A_IO_EFORMAT; o.err = "malformed eventalign line for " + tx; return; }
+            npos = (int64_t)src.ps.size();
+        }
+        if (npos > 1) {                               // `if data.size > 1`
+            if (!by_read.count(r.read)) read_order.push_back(r.read);
+            by_read[r.read] = std::move(src);
+        }
+        if (++readcount > readcount_max) break;      // (sic) up to readcount_max + 1 reads
+    }
+    if (readcount < readcount_min) return;
+    o.wanted = true;
+    const int w = T.n_neighbors;
+    const size_t K = 5 + 2 * (size_t)w, NF = 3 * (2 * (size_t)w + 1);
+    std::vector<SiteRow> sites;
+    std::vector<double> feat;
+    for (long long rd : read_order) {
+        const Src &src = by_read[rd];
+        if (T.run_status[src.run] != M6A_PREP_RUN_OK) { window_rows(src.ps, w, rd, sites, feat); continue; }
+        for (int64_t k = T.row_off[src.run]; k < T.row_off[src.run + 1]; k++) {
+            SiteRow sr;
+            sr.pos = T.row_pos[k];
+            sr.kmer.assign(T.row_kmer + (size_t)k * K, K);
+            sr.read = rd;
+            sr.f = feat.size();
+            feat.insert(feat.end(), T.row_feat + (size_t)k * NF, T.row_feat + (size_t)(k + 1) * NF);
+            sites.push_back(std::move(sr));
+        }
+    }
+    emit_transcript(tx, sites, feat, min_segment_count, w, compress, o);
 }
 
 // One byte range of eventalign.txt (whole lines): its contiguous (contig, read_index) runs; contig names are interned per
@@ -1482,7 +1548,7 @@ extern "C" int m6a_io_repr_rounded(double v, int digits, char *buf40)
 
 static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n_threads,
                          int readcount_min, int readcount_max, int min_segment_count, int n_neighbors,
-                         int compress, int skip_index);
+                         int compress, int skip_index, const m6a_io_prep_table *T);
 
 // Test hook (tests/test_dataprep.py): M6A_IO_TEST_THROW=index|transcript|index_file|bookkeeping makes that phase run out of memory
 // once, on whichever thread gets there first -- what the try/catch blocks below are for cannot be provoked reliably otherwise.
@@ -1533,7 +1599,7 @@ extern "C" int m6a_io_dataprep(const char *eventalign_path, const char *out_dir,
 {
     try {
         return dataprep_impl(eventalign_path, out_dir, n_threads, readcount_min, readcount_max, min_segment_count, n_neighbors,
-                             compress, skip_index);
+                             compress, skip_index, nullptr);
     } catch (const std::bad_alloc &) {
         return fail(M6A_IO_ENOMEM, "dataprep: out of memory");
     } catch (const std::exception &e) {
@@ -1543,25 +1609,90 @@ extern "C" int m6a_io_dataprep(const char *eventalign_path, const char *out_dir,
     }
 }
 
-static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n_threads,
-                         int readcount_min, int readcount_max, int min_segment_count, int n_neighbors,
-                         int compress, int skip_index)
+// ---- index (parallel_index, dataprep_utils.py:187-266): one row per contiguous (contig, read_index) run.
+// Byte ranges of whole lines on all threads; the runs that meet at a range boundary are stitched afterwards.  bounds = where
+// every range's rows start (the index file is formatted a batch of ranges at a time), nw = the workers it ran on.
+static int build_index(const char *eventalign_path, const char *base, const char *end, int n_threads, PhaseTrace &trace,
+                       std::vector<IdxRun> &idx, std::vector<std::string> &tx_names, std::vector<size_t> &bounds, int &nw_out)
 {
-    if (!eventalign_path || !out_dir) return fail(M6A_IO_EINVAL, "null argument");
-    if (n_neighbors < 1 || n_neighbors > 16) return fail(M6A_IO_EINVAL, "n_neighbors must be 1..16");
-    PhaseTrace trace;
-    Mapped ev;
-    const char *pm = getenv("M6A_IO_POPULATE_MAX_MB");
-    int rc = ev.open(eventalign_path, (size_t)(pm ? atoll(pm) : 2048) << 20);
-    if (rc) return rc;
-    const char *base = ev.p, *end = ev.p + ev.n;
-    const std::string dir(out_dir);
-    trace.mark("dataprep: map");
+    const char *body = (const char *)memchr(base, '\n', (size_t)(end - base));
+    if (!body) return fail(M6A_IO_EFORMAT, "%s: no header line", eventalign_path);
+    ++body;
+    const size_t n_body = (size_t)(end - body);
+    const char *rk = getenv("M6A_IO_INDEX_RANGE_KB");                                      // tests: small ranges on small files
+    const size_t min_range = std::max<size_t>(1, (size_t)(rk ? atoll(rk) : 8192)) << 10;  // a range is at least 8 MB
+    const int nw = n_workers(n_threads, (int64_t)std::max<size_t>(1, n_body / min_range));
+    const int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)nw * 4, n_body / min_range + 1));
+    std::vector<const char *> cut((size_t)NC + 1, end);
+    cut[0] = body;
+    for (int k = 1; k < NC; k++) {
+        const char *p = body + n_body / (size_t)NC * (size_t)k;
+        if (p < cut[(size_t)k - 1]) p = cut[(size_t)k - 1];
+        const char *nl = p < end ? (const char *)memchr(p, '\n', (size_t)(end - p)) : nullptr;
+        cut[(size_t)k] = nl ? nl + 1 : end;
+    }
+    std::vector<IndexChunk> chunks((size_t)NC);
+    on_threads(nw, NC, [&](int k) { if (k == NC / 2) test_throw("index"); index_range(base, cut[(size_t)k], cut[(size_t)k + 1], chunks[(size_t)k]); });
+    trace.mark("dataprep: index ranges");
+    for (const auto &c : chunks)
+        if (c.rc) return fail(c.rc, "%s: short line at byte %lld", eventalign_path, (long long)c.bad_at);
+    // sequential, per RANGE (not per run): contig names into the file-wide table in order of first appearance; a first
+    // run that continues the previous range's last one (same contig, same read, adjacent bytes) is folded into it
+    size_t total = 0, n_local = 0;
+    for (const auto &c : chunks) n_local += c.names.size();
+    std::unordered_map<std::string_view, uint32_t> view_ids;      // keys are views into the mapping: nothing is copied to look a name up
+    view_ids.reserve(n_local);
+    tx_names.reserve(n_local);
+    IndexChunk *open_c = nullptr;                                  // the range holding the file's last run so far
+    for (auto &c : chunks) {
+        c.global.resize(c.names.size());
+        for (size_t i = 0; i < c.names.size(); i++) {
+            auto it = view_ids.find(c.names[i]);
+            if (it == view_ids.end()) {
+                const uint32_t id = (uint32_t)tx_names.size();
+                tx_names.emplace_back(c.names[i]);
+                view_ids.emplace(c.names[i], id);
+                c.global[i] = id;
+            } else c.global[i] = it->second;
+        }
+        if (!c.runs.empty() && open_c) {
+            LocalRun &last = open_c->runs.back();
+            const LocalRun &first = c.runs.front();
+            if (last.end == first.start && last.read == first.read && open_c->global[last.tx] == c.global[first.tx]) {
+                last.end = first.end;
+                c.drop_first = true;
+            }
+        }
+        c.out = total;
+        total += c.runs.size() - (c.drop_first ? 1 : 0);
+        if (c.runs.size() > (c.drop_first ? 1u : 0u)) open_c = &c;
+    }
+    if (total > 0xffffffffull) return fail(M6A_IO_EINVAL, "more than 2^32 index rows");
+    trace.mark("dataprep: index names merged");
+    idx.resize(total);
+    // every range fills its rows of the index; their text is formatted and written a batch of ranges at a time, so the
+    // index file (a tenth of the eventalign.txt) never sits in memory as a whole
+    on_threads(nw, NC, [&](int k) {
+        IndexChunk &c = chunks[(size_t)k];
+        size_t o = c.out;
+        for (size_t i = c.drop_first ? 1 : 0; i < c.runs.size(); i++) {
+            const LocalRun &r = c.runs[i];
+            idx[o++] = IdxRun{c.global[r.tx], r.read, r.start, r.end};
+        }
+        std::vector<LocalRun>().swap(c.runs);
+    });
+    trace.mark("dataprep: index rows filled");
+    // the index file: on a background thread (see idx_writer above) -- a batch of row ranges is formatted on a quarter of
+    // the workers, then every range pwrite()s its own text at its offset, while the transcript pass runs on all of them
+    bounds.assign((size_t)NC + 1, total);
+    for (int k = 0; k < NC; k++) bounds[(size_t)k] = chunks[(size_t)k].out;
+    nw_out = nw;
+    return M6A_IO_OK;
+}
 
-    // ---- index (parallel_index, dataprep_utils.py:187-266): one row per contiguous (contig, read_index) run.
-    // Byte ranges of whole lines on all threads; the runs that meet at a range boundary are stitched afterwards.
-    std::vector<IdxRun> idx;
-    std::vector<std::string> tx_names;                 // id -> name, ids in order of first appearance
+// --skip_index: the rows of an existing eventalign.index
+static int read_index_file(const std::string &idx_path, std::vector<IdxRun> &idx, std::vector<std::string> &tx_names)
+{
     std::unordered_map<std::string, uint32_t> tx_ids;
     auto intern = [&](const char *p, size_t n) -> uint32_t {
         if (!idx.empty() && tx_names[idx.back().tx].size() == n && memcmp(tx_names[idx.back().tx].data(), p, n) == 0) return idx.back().tx;
@@ -1573,6 +1704,63 @@ static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n
         tx_names.push_back(std::move(key));
         return id;
     };
+    FILE *f = fopen(idx_path.c_str(), "r");
+    if (!f) return fail(M6A_IO_EIO, "--skip_index but %s does not exist", idx_path.c_str());
+    FileCloser fc(f);                                  // idx.push_back / intern can throw
+    char line[4096];
+    bool first = true;
+    while (fgets(line, sizeof line, f)) {
+        if (first) { first = false; continue; }
+        char *c = strrchr(line, ',');
+        if (!c) continue;
+        IdxRun r;
+        r.end = atoll(c + 1); *c = 0;
+        c = strrchr(line, ','); if (!c) continue; r.start = atoll(c + 1); *c = 0;
+        c = strrchr(line, ','); if (!c) continue; r.read = atoll(c + 1); *c = 0;
+        r.tx = intern(line, strlen(line));
+        idx.push_back(r);
+    }
+    (void)fc.close();
+    return M6A_IO_OK;
+}
+
+// the runs and names of a table (m6a_io_dataprep_write)
+static int table_index(const m6a_io_prep_table &T, std::vector<IdxRun> &idx, std::vector<std::string> &tx_names)
+{
+    if (T.n_tx < 0 || T.n_runs < 0 || T.n_runs > 0xffffffffll || (T.n_runs && (!T.run_tx || !T.run_read || !T.run_start || !T.run_end || !T.run_npos ||
+        !T.run_status || !T.row_off)) || (T.n_tx && (!T.tx_off || !T.tx_blob)))
+        return fail(M6A_IO_EINVAL, "dataprep table: bad sizes or null arrays");
+    if (T.n_runs && (T.row_off[0] != 0 || T.row_off[T.n_runs] != T.n_rows || (T.n_rows && (!T.row_pos || !T.row_kmer || !T.row_feat))))
+        return fail(M6A_IO_EINVAL, "dataprep table: row offsets do not match n_rows");
+    tx_names.resize((size_t)T.n_tx);
+    for (int64_t t = 0; t < T.n_tx; t++) tx_names[(size_t)t].assign(T.tx_blob + T.tx_off[t], (size_t)(T.tx_off[t + 1] - T.tx_off[t]));
+    idx.resize((size_t)T.n_runs);
+    for (int64_t i = 0; i < T.n_runs; i++) {
+        if ((int64_t)T.run_tx[i] >= T.n_tx || T.row_off[i] > T.row_off[i + 1]) return fail(M6A_IO_EINVAL, "dataprep table: bad run %lld", (long long)i);
+        idx[(size_t)i] = IdxRun{T.run_tx[i], T.run_read[i], T.run_start[i], T.run_end[i]};
+    }
+    return M6A_IO_OK;
+}
+
+static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n_threads,
+                         int readcount_min, int readcount_max, int min_segment_count, int n_neighbors,
+                         int compress, int skip_index, const m6a_io_prep_table *T)
+{
+    if (!eventalign_path || !out_dir) return fail(M6A_IO_EINVAL, "null argument");
+    if (T) n_neighbors = T->n_neighbors;
+    if (n_neighbors < 1 || n_neighbors > 16) return fail(M6A_IO_EINVAL, "n_neighbors must be 1..16");
+    PhaseTrace trace;
+    Mapped ev;
+    const char *pm = getenv("M6A_IO_POPULATE_MAX_MB");
+    // from a table, the file is read only for the runs its producer declined: mapped lazily
+    int rc = ev.open(eventalign_path, T ? 0 : (size_t)(pm ? atoll(pm) : 2048) << 20);
+    if (rc) return rc;
+    const char *base = ev.p, *end = ev.p + ev.n;
+    const std::string dir(out_dir);
+    trace.mark("dataprep: map");
+
+    std::vector<IdxRun> idx;
+    std::vector<std::string> tx_names;                 // id -> name, ids in order of first appearance
     const std::string idx_path = dir + "/eventalign.index";
     // declared before the index writer and the stream guards: destroyed after them, i.e. after the writer thread has been joined
     // and every stream closed -- then, unless the run succeeded, the files this call created are removed
@@ -1586,101 +1774,14 @@ static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n
         void wait() { if (th.joinable()) th.join(); }
         ~IndexFileWriter() { wait(); }
     } idx_writer;
-    if (skip_index) {
-        FILE *f = fopen(idx_path.c_str(), "r");
-        if (!f) return fail(M6A_IO_EIO, "--skip_index but %s does not exist", idx_path.c_str());
-        FileCloser fc(f);                                  // idx.push_back / intern can throw
-        char line[4096];
-        bool first = true;
-        while (fgets(line, sizeof line, f)) {
-            if (first) { first = false; continue; }
-            char *c = strrchr(line, ',');
-            if (!c) continue;
-            IdxRun r;
-            r.end = atoll(c + 1); *c = 0;
-            c = strrchr(line, ','); if (!c) continue; r.start = atoll(c + 1); *c = 0;
-            c = strrchr(line, ','); if (!c) continue; r.read = atoll(c + 1); *c = 0;
-            r.tx = intern(line, strlen(line));
-            idx.push_back(r);
-        }
-        (void)fc.close();
-    } else {
-        const char *body = (const char *)memchr(base, '\n', ev.n);
-        if (!body) return fail(M6A_IO_EFORMAT, "%s: no header line", eventalign_path);
-        ++body;
-        const size_t n_body = (size_t)(end - body);
-        const char *rk = getenv("M6A_IO_INDEX_RANGE_KB");                                      // tests: small ranges on small files
-        const size_t min_range = std::max<size_t>(1, (size_t)(rk ? atoll(rk) : 8192)) << 10;  // a range is at least 8 MB
-        const int nw = n_workers(n_threads, (int64_t)std::max<size_t>(1, n_body / min_range));
-        const int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)nw * 4, n_body / min_range + 1));
-        std::vector<const char *> cut((size_t)NC + 1, end);
-        cut[0] = body;
-        for (int k = 1; k < NC; k++) {
-            const char *p = body + n_body / (size_t)NC * (size_t)k;
-            if (p < cut[(size_t)k - 1]) p = cut[(size_t)k - 1];
-            const char *nl = p < end ? (const char *)memchr(p, '\n', (size_t)(end - p)) : nullptr;
-            cut[(size_t)k] = nl ? nl + 1 : end;
-        }
-        std::vector<IndexChunk> chunks((size_t)NC);
-        on_threads(nw, NC, [&](int k) { if (k == NC / 2) test_throw("index"); index_range(base, cut[(size_t)k], cut[(size_t)k + 1], chunks[(size_t)k]); });
-        trace.mark("dataprep: index ranges");
-        for (const auto &c : chunks)
-            if (c.rc) return fail(c.rc, "%s: short line at byte %lld", eventalign_path, (long long)c.bad_at);
-        // sequential, per RANGE (not per run): contig names into the file-wide table in order of first appearance; a first
-        // run that continues the previous range's last one (same contig, same read, adjacent bytes) is folded into it
-        size_t total = 0, n_local = 0;
-        for (const auto &c : chunks) n_local += c.names.size();
-        std::unordered_map<std::string_view, uint32_t> view_ids;      // keys are views into the mapping: nothing is copied to look a name up
-        view_ids.reserve(n_local);
-        tx_names.reserve(n_local);
-        IndexChunk *open_c = nullptr;                                  // the range holding the file's last run so far
-        for (auto &c : chunks) {
-            c.global.resize(c.names.size());
-            for (size_t i = 0; i < c.names.size(); i++) {
-                auto it = view_ids.find(c.names[i]);
-                if (it == view_ids.end()) {
-                    const uint32_t id = (uint32_t)tx_names.size();
-                    tx_names.emplace_back(c.names[i]);
-                    view_ids.emplace(c.names[i], id);
-                    c.global[i] = id;
-                } else c.global[i] = it->second;
-            }
-            if (!c.runs.empty() && open_c) {
-                LocalRun &last = open_c->runs.back();
-                const LocalRun &first = c.runs.front();
-                if (last.end == first.start && last.read == first.read && open_c->global[last.tx] == c.global[first.tx]) {
-                    last.end = first.end;
-                    c.drop_first = true;
-                }
-            }
-            c.out = total;
-            total += c.runs.size() - (c.drop_first ? 1 : 0);
-            if (c.runs.size() > (c.drop_first ? 1u : 0u)) open_c = &c;
-        }
-        if (total > 0xffffffffull) return fail(M6A_IO_EINVAL, "more than 2^32 index rows");
-        trace.mark("dataprep: index names merged");
-        idx.resize(total);
-        // every range fills its rows of the index; their text is formatted and written a batch of ranges at a time, so the
-        // index file (a tenth of the eventalign.txt) never sits in memory as a whole
-        on_threads(nw, NC, [&](int k) {
-            IndexChunk &c = chunks[(size_t)k];
-            size_t o = c.out;
-            for (size_t i = c.drop_first ? 1 : 0; i < c.runs.size(); i++) {
-                const LocalRun &r = c.runs[i];
-                idx[o++] = IdxRun{c.global[r.tx], r.read, r.start, r.end};
-            }
-            std::vector<LocalRun>().swap(c.runs);
-        });
-        trace.mark("dataprep: index rows filled");
-        // the index file: on a background thread (see idx_writer above) -- a batch of row ranges is formatted on a quarter of
-        // the workers, then every range pwrite()s its own text at its offset, while the transcript pass runs on all of them
+    // the index file: on a background thread (see idx_writer above) -- a batch of row ranges is formatted on a quarter of
+    // the workers, then every range pwrite()s its own text at its offset, while the transcript pass runs on all of them
+    auto start_index_writer = [&](std::vector<size_t> bounds, int nw) -> int {
         const int fd = ::open(idx_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) return fail(M6A_IO_EIO, "cannot write %s", idx_path.c_str());
         FdCloser fd_guard(fd);                             // until the writer thread exists and owns it (std::thread's constructor can throw)
         partial.add(idx_path);
         test_throw("bookkeeping");
-        std::vector<size_t> bounds((size_t)NC + 1, total);
-        for (int k = 0; k < NC; k++) bounds[(size_t)k] = chunks[(size_t)k].out;
         const int nbg = std::max(1, nw / 4);
         idx_writer.th = std::thread([&idx, &tx_names, &idx_writer, fd, nbg, bounds = std::move(bounds)]() {
           try {
@@ -1733,6 +1834,24 @@ static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n
           }
         });
         (void)fd_guard.release();                          // the thread closes it
+        return M6A_IO_OK;
+    };
+    if (T) {
+        if ((rc = table_index(*T, idx, tx_names))) return rc;
+        if (!skip_index) {                                 // ranges of 64 k rows
+            std::vector<size_t> bounds;
+            for (size_t o = 0; o < idx.size(); o += 65536) bounds.push_back(o);
+            bounds.push_back(idx.size());
+            const int nw = n_workers(n_threads, (int64_t)bounds.size() - 1);
+            if ((rc = start_index_writer(std::move(bounds), nw))) return rc;
+        }
+    } else if (skip_index) {
+        if ((rc = read_index_file(idx_path, idx, tx_names))) return rc;
+    } else {
+        std::vector<size_t> bounds;
+        int nw = 1;
+        if ((rc = build_index(eventalign_path, base, end, n_threads, trace, idx, tx_names, bounds, nw))) return rc;
+        if ((rc = start_index_writer(std::move(bounds), nw))) return rc;
     }
     trace.mark("dataprep: index file handed to its writer");
     if (ev.p && ev.n) (void)madvise((void *)ev.p, ev.n, MADV_NORMAL);       // the transcript pass jumps between a read's runs
@@ -1799,8 +1918,12 @@ static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n
             }
             std::unique_ptr<TxOut> o(new TxOut);
             if (t == NT / 2) test_throw("transcript");
-            preprocess_transcript(base, ev.n, tx_names[(size_t)t], idx, tx_rows[(size_t)t], readcount_min, readcount_max,
-                                  min_segment_count, n_neighbors, compress, *o);
+            if (T)
+                preprocess_transcript_rows(base, ev.n, tx_names[(size_t)t], idx, tx_rows[(size_t)t], *T, readcount_min, readcount_max,
+                                           min_segment_count, compress, *o);
+            else
+                preprocess_transcript(base, ev.n, tx_names[(size_t)t], idx, tx_rows[(size_t)t], readcount_min, readcount_max,
+                                      min_segment_count, n_neighbors, compress, *o);
             std::vector<uint32_t>().swap(tx_rows[(size_t)t]);
             std::unique_lock<std::mutex> lk(mu);
             if (o->rc && !failed) { failed = true; fail_rc = o->rc; fail_msg = o->err; cv.notify_all(); }
@@ -1861,4 +1984,121 @@ static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n
     if (trace.on) fprintf(stderr, "m6a_io: dataprep peak of finished-but-unwritten json: %.1f MB (budget %.0f MB, window %lld transcripts)\n", peak_pending / 1e6, pending_budget / 1e6, (long long)window);
     partial.keep = true;
     return M6A_IO_OK;
+}
+
+// ---- the two halves of dataprep (include/m6a_io.h): a table of runs and candidate rows, and the files written from one
+struct m6a_io_rows {
+    m6a_io_prep_table t{};
+    std::string blob;
+    std::vector<int64_t> tx_off, run_read, run_start, run_end, run_npos, row_off, row_pos;
+    std::vector<uint32_t> run_tx;
+    std::vector<int32_t> run_status;
+    std::string kmer;
+    std::vector<double> feat;
+};
+
+static int dataprep_rows_impl(const char *eventalign_path, const char *index_path, int n_threads, int n_neighbors, m6a_io_rows &R)
+{
+    if (n_neighbors < 1 || n_neighbors > 16) return fail(M6A_IO_EINVAL, "n_neighbors must be 1..16");
+    PhaseTrace trace;
+    Mapped ev;
+    const char *pm = getenv("M6A_IO_POPULATE_MAX_MB");
+    int rc = ev.open(eventalign_path, (size_t)(pm ? atoll(pm) : 2048) << 20);
+    if (rc) return rc;
+    std::vector<IdxRun> idx;
+    std::vector<std::string> tx_names;
+    if (index_path) {
+        if ((rc = read_index_file(index_path, idx, tx_names))) return rc;
+    } else {
+        std::vector<size_t> bounds;
+        int nw = 1;
+        if ((rc = build_index(eventalign_path, ev.p, ev.p + ev.n, n_threads, trace, idx, tx_names, bounds, nw))) return rc;
+    }
+    if (ev.p && ev.n) (void)madvise((void *)ev.p, ev.n, MADV_NORMAL);
+    const size_t NR = idx.size(), K = 5 + 2 * (size_t)n_neighbors, NF = 3 * (2 * (size_t)n_neighbors + 1);
+    for (const std::string &n : tx_names) { R.tx_off.push_back((int64_t)R.blob.size()); R.blob += n; }
+    R.tx_off.push_back((int64_t)R.blob.size());
+    R.run_tx.resize(NR); R.run_read.resize(NR); R.run_start.resize(NR); R.run_end.resize(NR); R.run_npos.resize(NR); R.run_status.resize(NR);
+    R.row_off.assign(NR + 1, 0);
+    // every run on its own (what a device producer does), a block of runs per work item; blocks are joined in order
+    struct Block { std::vector<SiteRow> sites; std::vector<double> feat; };
+    const int64_t per = 4096, NB = (int64_t)((NR + per - 1) / per);
+    std::vector<Block> blocks((size_t)NB);
+    on_threads(n_workers(n_threads, NB), (int)NB, [&](int b) {
+        Block &B = blocks[(size_t)b];
+        std::vector<Pos> ps;
+        for (size_t i = (size_t)b * per; i < std::min(NR, (size_t)(b + 1) * per); i++) {
+            const IdxRun &r = idx[i];
+            R.run_tx[i] = r.tx; R.run_read[i] = r.read; R.run_start[i] = r.start; R.run_end[i] = r.end;
+            ps.clear();
+            const bool ok = r.start >= 0 && r.end <= (int64_t)ev.n && r.start <= r.end &&
+                            combine_read(ev.p + r.start, ev.p + r.end, ev.p + ev.n, ps);
+            R.run_status[i] = ok ? M6A_PREP_RUN_OK : M6A_PREP_RUN_HOST;           // malformed: the writer reports it if it is reached
+            R.run_npos[i] = ok ? (int64_t)ps.size() : 0;
+            const size_t before = B.sites.size();
+            if (ok) window_rows(ps, n_neighbors, r.read, B.sites, B.feat);
+            R.row_off[i + 1] = (int64_t)(B.sites.size() - before);
+        }
+    });
+    for (size_t i = 0; i < NR; i++) R.row_off[i + 1] += R.row_off[i];
+    const size_t NROWS = (size_t)R.row_off[NR];
+    R.row_pos.resize(NROWS);
+    R.kmer.resize(NROWS * K);
+    R.feat.resize(NROWS * NF);
+    on_threads(n_workers(n_threads, NB), (int)NB, [&](int b) {
+        Block &B = blocks[(size_t)b];
+        size_t o = (size_t)R.row_off[std::min(NR, (size_t)b * per)];
+        for (const SiteRow &sr : B.sites) {
+            R.row_pos[o] = sr.pos;
+            std::memcpy(&R.kmer[o * K], sr.kmer.data(), K);
+            std::memcpy(&R.feat[o * NF], &B.feat[sr.f], NF * sizeof(double));
+            ++o;
+        }
+        std::vector<SiteRow>().swap(B.sites);
+        std::vector<double>().swap(B.feat);
+    });
+    trace.mark("dataprep rows: runs combined");
+    m6a_io_prep_table &t = R.t;
+    t.n_neighbors = n_neighbors;
+    t.n_tx = (int64_t)tx_names.size(); t.tx_blob = R.blob.data(); t.tx_off = R.tx_off.data();
+    t.n_runs = (int64_t)NR; t.run_tx = R.run_tx.data(); t.run_read = R.run_read.data(); t.run_start = R.run_start.data();
+    t.run_end = R.run_end.data(); t.run_npos = R.run_npos.data(); t.run_status = R.run_status.data(); t.row_off = R.row_off.data();
+    t.n_rows = (int64_t)NROWS; t.row_pos = R.row_pos.data(); t.row_kmer = R.kmer.data(); t.row_feat = R.feat.data();
+    return M6A_IO_OK;
+}
+
+extern "C" int m6a_io_dataprep_rows(const char *eventalign_path, const char *index_path, int n_threads, int n_neighbors, m6a_io_rows **out)
+{
+    if (!eventalign_path || !out) return fail(M6A_IO_EINVAL, "null argument");
+    *out = nullptr;
+    try {
+        std::unique_ptr<m6a_io_rows> r(new m6a_io_rows);
+        const int rc = dataprep_rows_impl(eventalign_path, index_path, n_threads, n_neighbors, *r);
+        if (rc) return rc;
+        *out = r.release();
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "dataprep rows: out of memory");
+    } catch (const std::exception &e) {
+        return fail(M6A_IO_EIO, "dataprep rows: %s", e.what());
+    }
+}
+
+extern "C" const m6a_io_prep_table *m6a_io_rows_table(const m6a_io_rows *r) { return r ? &r->t : nullptr; }
+extern "C" void m6a_io_rows_free(m6a_io_rows *r) { delete r; }
+
+extern "C" int m6a_io_dataprep_write(const char *eventalign_path, const char *out_dir, const m6a_io_prep_table *table, int n_threads,
+                                     int readcount_min, int readcount_max, int min_segment_count, int compress, int write_index)
+{
+    if (!table) return fail(M6A_IO_EINVAL, "null argument");
+    try {
+        return dataprep_impl(eventalign_path, out_dir, n_threads, readcount_min, readcount_max, min_segment_count, table->n_neighbors,
+                             compress, write_index ? 0 : 1, table);
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "dataprep: out of memory");
+    } catch (const std::exception &e) {
+        return fail(M6A_IO_EIO, "dataprep: %s", e.what());
+    } catch (...) {
+        return fail(M6A_IO_EIO, "dataprep: unexpected exception");
+    }
 }

@@ -1,5 +1,6 @@
 """`dataprep` sub-command: same flags as `m6anet dataprep` (m6anet/scripts/dataprep.py:14-51),
-running the native implementation in libm6a_io.so (host-only)."""
+running the native implementation in libm6a_io.so (host-only), or with --device gpu the HIP scan of libm6a_hip.so
+followed by the same host writer."""
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -23,6 +24,9 @@ def argparser():
                         help="number of neighboring features to extract (1..16; the shipped models take 1).")
     parser.add_argument("--compress", default=False, action="store_true",
                         help="round down the features to 3 decimal places.")
+    parser.add_argument("--device", default="cpu", choices=("cpu", "gpu"),
+                        help="gpu: scan, parse and combine the eventalign file in HIP on GPU 0 (the same four files, byte for byte; "
+                             "the file must fit in device memory).")
     return parser
 
 
@@ -32,4 +36,4 @@ def main(args):
         os.makedirs(args.out_dir)
     _io.dataprep(args.eventalign, args.out_dir, n_threads=args.n_processes, readcount_min=args.readcount_min,
                  readcount_max=args.readcount_max, min_segment_count=args.min_segment_count,
-                 n_neighbors=args.n_neighbors, compress=args.compress, skip_index=args.skip_index)
+                 n_neighbors=args.n_neighbors, compress=args.compress, skip_index=args.skip_index, device=args.device)

@@ -13,7 +13,14 @@ sites, inputs resident in HBM.  With N GPUs every rank holds its own shard of an
 (weak scaling; shards are flush-group aligned and carry the job offset, so the job's results do not
 depend on N) and each step ends with ONE gather of site_prob + mod_ratio to rank 0 over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload uniform|ragged] [--sites S] [--iters T] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload uniform|ragged] [--sites S] [--iters T] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing more: it sets up, makes the cold call, warms up, times the K steps (HIP
+events around the encoder launches inside them give `roofline`), writes --dump-outputs, and prints the line.  --full adds
+everything else the line can carry, each in runs of its own after the timed steps: the pooling kernel's roofline with its
+measured ceiling, live rocprofv3 PMC traffic, the sustained leg (--min-seconds, 3 s by default), on the default shape the opt-in
+12-slot encoder, host inputs and the `ragged` shape, and the CPU baseline; --no-* options leave parts of it out.  An N-rank run
+keeps, either way, what certifies its line: each rank's compute-only steps before the process group, `rccl`, `per_rank`, `efficiency`.
 
 `--gpus N` without a launcher starts its own N ranks (re-executes under torch.distributed.run on
 127.0.0.1); under torch.distributed.run (RANK/WORLD_SIZE set) it runs as one rank.  The 8-GPU run is
@@ -141,8 +148,7 @@ def live_traffic(workload, kernel_name, pool_kernel_name=None, timeout_s=240, en
         d = tempfile.mkdtemp(prefix="m6a_pmc_")
         try:
             cmd = ["rocprofv3", "--pmc", ctr, "--kernel-trace", "-d", d, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
-                   "--workload", workload, "--steps", "3", "--warmup", "1", "--min-seconds", "0", "--no-cpu-baseline", "--no-live-traffic", "--no-ragged-extra",
-                   "--enc-variant", str(enc_variant)]
+                   "--workload", workload, "--steps", "3", "--warmup", "1", "--enc-variant", str(enc_variant)]     # a plain run
             subprocess.run(cmd, capture_output=True, timeout=timeout_s, env=dict(os.environ, TMPDIR=os.environ.get("TMPDIR", "/tmp")))
             dbs = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
             if not dbs:
@@ -596,9 +602,9 @@ class Bench:
         self.gather_kind = "RCCL (torch.distributed)" + ("; native m6a_gather unavailable -- %s" % why if why else "")
 
     def run(self, steps, warmup, min_seconds=0.0, want_outputs=False):
-        """Cold call, warm-up, the timed region (HIP events around the encoder launches inside it), extra steps with
-        events around the pooling launches; optionally a sustained leg of at least `min_seconds`.  want_outputs: the results
-        of the timed region's last step are copied out right after it (Bench.outputs)."""
+        """Cold call, warm-up, the timed region (HIP events around the encoder launches inside it); with --full extra steps
+        with events around the pooling launches; optionally a sustained leg of at least `min_seconds`.  want_outputs: the
+        results of the timed region's last step are copied out right after it (Bench.outputs)."""
         eng = self.eng
         # the cold call: whatever the context did not set up at creation (flush-group offsets, output staging, tables of
         # bag sizes it could not know) is built inside
@@ -630,10 +636,12 @@ class Bench:
             self.gather.timing = False
         enc_ms, enc_n = eng.profile_read(0)
         enc_clk = eng.profile_clock(0)                       # in-kernel stamps of the region's last encoder launch
-        eng.profile("pooling")
-        self.timed(min(steps, 10))
-        pool_ms, pool_n = eng.profile_read(1)
-        pool_clk = eng.profile_clock(1)
+        pool_ms, pool_n, pool_clk = 0.0, 0, None
+        if self.args.full:
+            eng.profile("pooling")
+            self.timed(min(steps, 10))
+            pool_ms, pool_n = eng.profile_read(1)
+            pool_clk = eng.profile_clock(1)
         eng.profile(False)
         eng.sync()
         sustained = None
@@ -760,7 +768,7 @@ class Bench:
         tr = None
         if world == 1 and traffic:
             default_shape = S == spec["sites"] and T == 1000 and (self.workload == "ragged" or bag == spec["bag"])
-            if default_shape and not args.no_live_traffic:
+            if args.full and default_shape and not args.no_live_traffic:
                 tr = live_traffic(self.workload, enc_kernel, pool_kernel, enc_variant=args.enc_variant)
             if tr is None:
                 tr = measured_traffic(S, bag)
@@ -818,6 +826,9 @@ class Bench:
                                       "Gdraws_per_s": draws / (pool_avg_ms * 1e-3) / 1e9 if pool_avg_ms else None}},
         }
         at_measured_clock(out["roofline"], r.get("enc_clk"))
+        if not r["pool_n"]:
+            # only --full times the pooling launches (extra steps in Bench.run): without them there is no pooling figure
+            del out["pool_roofline"], out["kernels"][pool_kernel]
         if r["sustained"]:
             su = r["sustained"]
             out["value_sustained"] = total_sites * su["steps"] / su["seconds"]
@@ -848,7 +859,7 @@ class Bench:
                             "over %s" % self.gather_kind if self.gather is not None else "none"}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -857,15 +868,20 @@ def main():
     ap.add_argument("--sites", type=int, default=None, help="sites per GPU (default: the workload's)")
     ap.add_argument("--reads", type=int, default=None, help="uniform workload: reads per site (default 20)")
     ap.add_argument("--iters", type=int, default=1000, help="num_iterations")
-    ap.add_argument("--min-seconds", type=float, default=3.0,
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry (runs of their own): the pooling roofline and "
+                         "its measured ceiling, live PMC traffic, the sustained leg, the extra legs of the default shape, the CPU baseline")
+    ap.add_argument("--min-seconds", type=float, default=None,
                     help="after the timed region (which alone defines `value`) keep stepping for at least this long and report "
                          "value_sustained plus rocm-smi's clock / power under load -- the K-step region is tens of milliseconds, inside "
-                         "one DVFS window; 0 skips the leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "one DVFS window; default 3 with --full, otherwise 0 (no leg)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-ragged-extra", action="store_true",
-                    help="default run only: skip the extra `ragged` key (configs[4]'s per-GPU shape, ~10 steps after the headline)")
+                    help="with --full, default run only: skip the extra legs (the opt-in 12-slot encoder, host inputs, and the `ragged` "
+                         "key: configs[4]'s per-GPU shape, ~10 steps after the headline)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not re-run under rocprofv3 for roofline.traffic; quote the committed profiles/*_enc_traffic.json instead")
+                    help="with --full: do not re-run under rocprofv3 for roofline.traffic; quote the committed "
+                         "profiles/*_enc_traffic.json instead (what a plain run does)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--enc-variant", type=int, default=0,
                     help="m6a_set_encoder_variant: 0 auto = the 16-slot kernels (the reference's bits; what the CLI runs), 1 the same, "
@@ -877,10 +893,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what their last step computed to DIR/<name>.npy: read_prob (float32), site_prob "
                          "(float32), mod_ratio (float64); arrays above 4 M reads / 3 M sites are a fixed seeded sample of positions")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.min_seconds is None:
+        args.min_seconds = 3.0 if args.full else 0.0
+    return args
 
+
+def main():
+    args = parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_main(args.workload, args.iters, budget_s=20.0)))
         return
@@ -1037,7 +1059,7 @@ def run(args, line, rank, world, local_rank, S, bag, T):
             line["efficiency"] = line["value"] / (world * line["rank0_local"]["sites_per_s"])
         default_run = (world == 1 and args.workload == "uniform" and S == WORKLOADS["uniform"]["sites"] and T == 1000 and
                        bag == WORKLOADS["uniform"]["bag"])
-        if default_run and not args.no_ragged_extra:
+        if args.full and default_run and not args.no_ragged_extra:
             # three EXTRA legs after the headline; each is optional: a failure is recorded under "<leg>_error" and the line goes out
             def optional(name, leg):
                 try:
@@ -1105,7 +1127,7 @@ def run(args, line, rank, world, local_rank, S, bag, T):
             b.eng.set_encoder_variant(args.enc_variant)
             line["with_h2d"] = with_h2d(b, T)
             optional("ragged", leg_ragged)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = run_cpu_baseline_subprocess(args.workload, T)
     if multi:
         import torch.distributed as dist

@@ -288,6 +288,15 @@ def test_early_rank_start_helpers(tmp_path, monkeypatch):
     assert not _early.ranks_may_share_a_gpu()
 
 
+def test_bench_measures_beyond_the_headline_only_with_full():
+    """bench.py's plain run keeps no sustained leg unless asked for one; --full brings the 3 s default back."""
+    import bench
+    a = bench.parse_args(["--steps", "5", "--warmup", "2"])
+    assert not a.full and a.min_seconds == 0 and (a.steps, a.warmup) == (5, 2)
+    assert bench.parse_args(["--full"]).min_seconds == 3.0
+    assert bench.parse_args(["--min-seconds", "1.5"]).min_seconds == 1.5 and bench.parse_args(["--full", "--min-seconds", "0"]).min_seconds == 0
+
+
 def test_cpu_baseline_reports_what_the_process_may_use():
     """bench.py's cpu_baseline states its CPUs honestly: effective_cores = affinity mask cut by the cgroup quota (the GPU boxes
     lease 16 of 256 logical CPUs), never more than the host has; the product's own thread counts use the same figure."""

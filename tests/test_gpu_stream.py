@@ -648,7 +648,7 @@ def test_bench_world_4_rehearsal_on_one_gpu(workload, sites):
 
 
 def test_bench_default_line_has_the_contract_and_one_encoder_for_product_and_headline(eng):
-    """The line the driver reads (default shape, no flags but shorter legs): the contract's keys, and VERDICT r5 item 1 -- ONE
+    """The line the driver reads (default shape, --full with shorter legs): the contract's keys, and VERDICT r5 item 1 -- ONE
     encoder kernel for the product and the headline: the kernel the timed region ran (`config.encoder_kernel_function`, the one
     `roofline` prices) is the library's automatic choice AND what the CLI selects by default (asserted against the CLI's own code,
     not a string in bench.py).  The opt-in 12-slot kernel, the host-input leg and the ragged shape are extra keys -- every extra
@@ -656,7 +656,7 @@ def test_bench_default_line_has_the_contract_and_one_encoder_for_product_and_hea
     from m6anet_amd.scripts import inference as cli
     # 10 steps behind 5 warm-up steps: a 3-step region right after the cold call sits on the clock ramp (one box in round 6 gave the
     # encoder 0.64 of peak there against 0.81 in the same build's bench run); the bounds below are sanity bounds, not measurements
-    out, lines = run_bench(["--steps", "10", "--warmup", "5", "--min-seconds", "0", "--no-cpu-baseline", "--no-live-traffic"], {}, timeout=600)
+    out, lines = run_bench(["--steps", "10", "--warmup", "5", "--full", "--min-seconds", "0", "--no-cpu-baseline", "--no-live-traffic"], {}, timeout=600)
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
     d = lines[0]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
@@ -703,6 +703,24 @@ def test_bench_default_line_has_the_contract_and_one_encoder_for_product_and_hea
     g = d["ragged"]
     assert g["value"] > 1e7 and g["config"]["pool_kernel"] == "ragged-table" and 0.6 < g["roofline"]["frac"] < 1.0
     assert g["config"]["encoder_kernel_function"] == "enc_site16_kernel" and g["pool_roofline"]["clock_ghz_measured"] is not None
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """A plain run (no --full) on the default shape sets up, warms up, times its steps and prints the line: the contract's keys
+    and the encoder roofline from the events inside the timed region, and nothing that takes a run of its own -- no pooling
+    figures, no live PMC pass, no sustained leg, none of the default shape's extra legs, no CPU baseline."""
+    out, lines = run_bench(["--steps", "3", "--warmup", "1"], {}, timeout=600)
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    d = lines[0]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True and "error" not in d
+    assert d["value"] > 0 and abs(d["value"] - 1e6 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    for k in ("fast_encoder_optin", "with_h2d", "ragged", "cpu_baseline", "pool_roofline", "value_sustained", "sustained"):
+        assert k not in d, k
+    r = d["roofline"]
+    assert r["launches"] == 3 and list(d["kernels"]) == [d["config"]["encoder_kernel_function"]]
+    assert r["traffic_source"] is None or "not measured by this run" in r["traffic_source"]
 
 
 def test_bench_sustained_leg_with_two_ranks():

@@ -5,11 +5,11 @@ export TMPDIR=/tmp
 O=gpurun_out
 T=$1
 mkdir -p $O
-# the bench lines: default (configs[2] + the `ragged` key), --workload ragged, and both sustained for >= 10 s
-python bench.py > $O/${T}_bench_uniform.json 2> $O/${T}_bench_uniform.err
-python bench.py --workload ragged > $O/${T}_bench_ragged.json 2> $O/${T}_bench_ragged.err
-python bench.py --min-seconds 10 --no-cpu-baseline --no-live-traffic --no-ragged-extra > $O/${T}_bench_uniform_sustained.json 2> $O/${T}_sustained.err
-python bench.py --workload ragged --min-seconds 10 --no-cpu-baseline --no-live-traffic > $O/${T}_bench_ragged_sustained.json 2>> $O/${T}_sustained.err
+# the bench lines with --full: default (configs[2] + the `ragged` key), --workload ragged, and both sustained for >= 10 s
+python bench.py --full > $O/${T}_bench_uniform.json 2> $O/${T}_bench_uniform.err
+python bench.py --full --workload ragged > $O/${T}_bench_ragged.json 2> $O/${T}_bench_ragged.err
+python bench.py --full --min-seconds 10 --no-cpu-baseline --no-live-traffic --no-ragged-extra > $O/${T}_bench_uniform_sustained.json 2> $O/${T}_sustained.err
+python bench.py --full --workload ragged --min-seconds 10 --no-cpu-baseline --no-live-traffic > $O/${T}_bench_ragged_sustained.json 2>> $O/${T}_sustained.err
 # kernel trace + PMC passes (counters in their own runs, --kernel-trace only)
 CMD="python bench.py --min-seconds 0 --no-cpu-baseline --no-live-traffic --no-ragged-extra"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_trace -o bench -- $CMD > $O/${T}_trace.json 2> $O/${T}_trace.err

@@ -18,7 +18,8 @@
  *                     read back a few bytes first (off[S]; min/max bag size to choose the
  *                     sampling kernel) and so block on the stream once or twice per call;
  *   - one ctx per (process, GPU, stream); calls on one ctx are not thread-safe;
- *   - no exceptions, no callbacks, no torch types cross this boundary.
+ *   - no exceptions, no callbacks, no torch types cross this boundary (one exception, stated there: m6a_prep_sites_build calls
+ *     the plain C functions of libm6a_io.so it is given for the runs its device front half declines).
  */
 #ifndef M6A_H
 #define M6A_H
@@ -337,6 +338,60 @@ const struct m6a_io_prep_table *m6a_prep_table(const m6a_prep *p);    /* owned b
 int m6a_prep_times(const m6a_prep *p, double *ms6);
 void m6a_prep_free(m6a_prep *p);
 const char *m6a_prep_last_error(void);
+
+/* `eventalign_inference`: eventalign.txt -> the arrays m6a_io_load_sites makes of `dataprep` + data.json (n_neighbors = 1, no
+ * --compress), without the JSON and with X left in HBM for m6a_infer.  The front half is m6a_prep_eventalign's; the back half does on
+ * the device what m6a_io_dataprep_write and then the loader do with its candidate rows: per transcript (ids in order of first
+ * appearance) its runs in file order, counting stopped after readcount_max + 1 runs, transcripts with fewer than readcount_min runs
+ * dropped, a read index seen again keeping its first place and taking the later run's rows; rows sorted by (transcript, position,
+ * place); reads of one site must agree on the 7-mer; a site is kept with >= min_segment_count and >= 20 reads (DEFAULT_MIN_READS);
+ * X = (float)((v - mean) / std) in f64 with the norm table in m6a_io_load_sites' form (n_norm = 0: no normalisation).  The arrays
+ * equal m6a_io_load_sites' on the two-step output, X bit for bit.  Runs the front half declines go to `host` (m6a_io_runs_rows,
+ * m6a_io_rows_table, m6a_io_rows_free, m6a_io_last_error of libm6a_io.so), and their rows join the device's before the runs are
+ * selected; a failure there is returned with the host half's own text (`error` may be NULL).
+ * Only ids come back: per segment of equal contig bytes 24 B and its name, per site off / transcript / position / 7-mer, per read
+ * its read id; d2h_bytes counts every device-to-host byte of the call (m6a_prep_sites_fetch adds its own).  X, site_kmers and off
+ * are device pointers owned by the handle; so are read_prob [R], site_prob [S] and mod_ratio [S], the outputs to give m6a_infer
+ * (after m6a_set_host_offsets(off_host)), which m6a_prep_sites_fetch copies to host memory.  Errors as m6a_prep_eventalign's, plus
+ * M6A_EFORMAT with the host's text for disagreeing 7-mers, a missing 5-mer in the norm table or a site outside the vocabulary; a
+ * job over the device budget is M6A_ENOMEM and its text names the two-step path.  ms: [0] upload, [1] newline offsets, [2] lines,
+ * runs, combine and windows, [3] back half on the device (its small copies of segments and per-site arrays included), [4] host
+ * (names, declined runs), [5] the copy of the read ids (m6a_prep_sites_fetch adds the time of its own copies), [6] the upload's GB/s,
+ * [7] the whole call. */
+typedef struct m6a_prep_sites m6a_prep_sites;
+struct m6a_io_rows;
+typedef struct m6a_prep_host_half {
+    int (*rows)(const char *eventalign_path, int64_t n_runs, const int64_t *start, const int64_t *end, const int64_t *read,
+                int n_neighbors, int n_threads, struct m6a_io_rows **out);
+    const struct m6a_io_prep_table *(*table)(const struct m6a_io_rows *r);
+    void (*free)(struct m6a_io_rows *r);
+    const char *(*error)(void);
+} m6a_prep_host_half;
+typedef struct m6a_prep_sites_info {
+    int64_t n_sites, n_reads, n_tx;
+    const float *X;                 /* device [R][9] */
+    const uint8_t *site_kmers;      /* device [S][3] vocabulary ids */
+    const int64_t *off;             /* device [S+1] */
+    float *read_prob, *site_prob;   /* device [R], [S]: m6a_infer's outputs */
+    double *mod_ratio;              /* device [S] */
+    const int64_t *off_host;        /* [S+1] */
+    const uint32_t *site_tx;        /* [S] transcript of each site: tx_blob[tx_off[t], tx_off[t + 1]) */
+    const int64_t *site_pos;        /* [S] */
+    const char *site_kmer7;         /* [S][7], no terminators */
+    const char *tx_blob;
+    const int64_t *tx_off;          /* [n_tx + 1] */
+    const double *read_ids;         /* [R] */
+    double ms[8];
+    int64_t d2h_bytes;
+} m6a_prep_sites_info;
+int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
+                         const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                         const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out);
+const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p);     /* owned by p */
+int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio);
+/* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */
+int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_kmers, int64_t *off);
+void m6a_prep_sites_free(m6a_prep_sites *p);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,12 @@ const double *m6a_io_read_ids(const m6a_sites *s);         /* [R] numeric read i
 const int32_t *m6a_io_read_rep(const m6a_sites *s);        /* [R] replicate of each read */
 const char *m6a_io_tx_id(const m6a_sites *s, int64_t site);    /* NUL-terminated */
 const char *m6a_io_kmer5(const m6a_sites *s, int64_t site);    /* centre 5-mer, NUL-terminated */
+/* Sites for the writers only, from host arrays (`eventalign_inference`: m6a_prep_sites_build in include/m6a.h leaves X on the
+ * device): off [S+1], tx_pos [S], site_tx [S] indexing the names tx_blob[tx_off[t], tx_off[t + 1]) (n_tx of them), kmer5 [S][5]
+ * without terminators, read_ids [R]; one replicate.  m6a_io_X and m6a_io_site_kmers return NULL; m6a_io_write_csv / _n and the
+ * shard writers print the rows m6a_io_load_sites' sites would print; m6a_io_save_store refuses them (M6A_IO_EINVAL: no features). */
+int m6a_io_sites_from_arrays(int64_t n_sites, const int64_t *off, const int64_t *tx_pos, const char *tx_blob, const int64_t *tx_off,
+                             int64_t n_tx, const uint32_t *site_tx, const char *kmer5, const double *read_ids, m6a_sites **out);
 
 /* Binary site store: everything m6a_io_load_sites produces -- normalised features,
  * k-mer ids, CSR offsets, ids -- in one file, so a dataset is parsed from data.json ONCE and every later run maps it
@@ -160,6 +166,11 @@ typedef struct m6a_io_rows m6a_io_rows;
 /* The table on the host: the index (or, with index_path non-NULL, the rows of that eventalign.index) and every run's
  * candidate rows (no run is declined).  Errors are those of m6a_io_dataprep's index phase. */
 int m6a_io_dataprep_rows(const char *eventalign_path, const char *index_path, int n_threads, int n_neighbors, m6a_io_rows **out);
+/* The rows of the given runs alone (byte ranges of eventalign_path, their read indices), as m6a_io_dataprep_rows makes them for its
+ * own: a table of n_runs runs without transcripts, run_status M6A_PREP_RUN_HOST where a line is malformed.  The host half of
+ * m6a_prep_sites_build (include/m6a.h: m6a_prep_host_half) for the runs its device front half declines. */
+int m6a_io_runs_rows(const char *eventalign_path, int64_t n_runs, const int64_t *start, const int64_t *end, const int64_t *read,
+                     int n_neighbors, int n_threads, m6a_io_rows **out);
 const m6a_io_prep_table *m6a_io_rows_table(const m6a_io_rows *r);
 void m6a_io_rows_free(m6a_io_rows *r);
 /* The four files of m6a_io_dataprep from a table, whoever made it: eventalign.index from the runs (write_index != 0; with

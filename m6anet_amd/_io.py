@@ -10,7 +10,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write"]
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays"]
 _lib = None
 
 
@@ -89,6 +89,8 @@ def load():
     L.m6a_io_rows_free.argtypes = [vp]
     L.m6a_io_rows_free.restype = None
     L.m6a_io_dataprep_write.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PrepTable), i32, i32, i32, i32, i32, i32]
+    L.m6a_io_runs_rows.argtypes = [C.c_char_p, i64, vp, vp, vp, i32, i32, C.POINTER(vp)]
+    L.m6a_io_sites_from_arrays.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -180,6 +182,99 @@ class prep_on_device:
         self._h = None
 
 
+def norm_arrays(norm):
+    """Normalisation factors (dict kmer -> (mean[3], std[3]), or None) in m6a_io_load_sites' form: (kmers blob, mean, std, n)."""
+    if not norm:
+        return None, None, None, 0
+    kmers = sorted(norm)
+    mean = np.ascontiguousarray([norm[k][0] for k in kmers], np.float64)
+    std = np.ascontiguousarray([norm[k][1] for k in kmers], np.float64)
+    return "".join(kmers).encode(), mean, std, len(kmers)
+
+
+class prep_sites:
+    """m6a_prep_sites_build (libm6a_hip.so): eventalign.txt -> the loader's arrays with X, site_kmers and off left on the device.
+    `info` is the m6a_prep_sites_info; host copies are numpy arrays (off, site_tx, tx_pos, kmer7, read_ids) and `names` (per
+    transcript).  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
+    _CODES = prep_on_device._CODES
+
+    def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0):
+        from . import _lib
+        L, io = _lib.load(), load()
+        self._L, self._h = L, C.c_void_p()
+        blob, mean, std, n = norm_arrays(norm)
+        host = _lib.HostHalf(C.cast(io.m6a_io_runs_rows, C.c_void_p), C.cast(io.m6a_io_rows_table, C.c_void_p),
+                             C.cast(io.m6a_io_rows_free, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
+        rc = L.m6a_prep_sites_build(int(device_id), os.fsencode(eventalign), int(readcount_min), int(readcount_max), int(min_segment_count),
+                                    blob, None if mean is None else mean.ctypes.data, None if std is None else std.ctypes.data, n,
+                                    C.byref(host), int(n_threads), C.byref(self._h))
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        i = self.info = L.m6a_prep_sites_get(self._h).contents
+        S, R, T = i.n_sites, i.n_reads, i.n_tx
+
+        def arr(ptr, ctype, n):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy() if n else np.zeros(0, np.dtype(ctype))
+        self.n_sites, self.n_reads = S, R
+        self.off = arr(i.off_host, C.c_int64, S + 1)
+        self.site_tx = arr(i.site_tx, C.c_uint32, S)
+        self.tx_pos = arr(i.site_pos, C.c_int64, S)
+        self.kmer7 = arr(i.site_kmer7, C.c_uint8, 7 * S).reshape(S, 7)
+        self.read_ids = arr(i.read_ids, C.c_double, R)
+        tx_off = arr(i.tx_off, C.c_int64, T + 1)
+        self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
+        self.tx_off = tx_off
+        self.names = [self.tx_blob[tx_off[t]:tx_off[t + 1]].decode() for t in range(T)]
+
+    def times(self):
+        """Phase milliseconds (include/m6a.h) and the device-to-host bytes so far."""
+        keys = ("upload", "newlines", "parse_combine_windows", "back_half", "host", "read_ids_and_fetch_d2h", "upload_GBps", "total")
+        return dict(zip(keys, list(self.info.ms))), int(self.info.d2h_bytes)
+
+    def fetch(self):
+        """(read_prob, site_prob, mod_ratio) from the device outputs m6a_infer wrote."""
+        rp = np.empty(self.n_reads, np.float32)
+        sp = np.empty(self.n_sites, np.float32)
+        mr = np.empty(self.n_sites, np.float64)
+        rc = self._L.m6a_prep_sites_fetch(self._h, rp.ctypes.data, sp.ctypes.data, mr.ctypes.data)
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        return rp, sp, mr
+
+    def inputs(self):
+        """Host copies of the device arrays (X [R, 9], site_kmers [S, 3], off [S + 1]), for inspection."""
+        X = np.empty((self.n_reads, 9), np.float32)
+        km = np.empty((self.n_sites, 3), np.uint8)
+        off = np.empty(self.n_sites + 1, np.int64)
+        rc = self._L.m6a_prep_sites_inputs(self._h, X.ctypes.data, km.ctypes.data, off.ctypes.data)
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        return X, km, off
+
+    def writer(self):
+        """The sites as an m6a_sites for the CSV writers (NativeSites.from_arrays)."""
+        k5 = np.ascontiguousarray(self.kmer7[:, 1:6])
+        return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.m6a_prep_sites_free(self._h)
+            self._h = None
+            self.info = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _weakrefable(x):
     try:
         import weakref
@@ -192,11 +287,15 @@ def _weakrefable(x):
 class NativeSites:
     """Owns an m6a_sites handle; exposes its arrays as zero-copy numpy views."""
 
-    def __init__(self, input_dirs=None, min_reads=20, norm=None, n_threads=0, store=None):
+    def __init__(self, input_dirs=None, min_reads=20, norm=None, n_threads=0, store=None, _arrays=None):
         """Either parses `input_dirs` (data.info + data.json per directory) or maps a binary site `store` file."""
         L = load()
         h = C.c_void_p()
-        if store is not None:
+        if _arrays is not None:
+            off, tx_pos, blob, tx_off, site_tx, k5, ids = _arrays
+            _chk(L.m6a_io_sites_from_arrays(len(tx_pos), off.ctypes.data, tx_pos.ctypes.data, blob, tx_off.ctypes.data, len(tx_off) - 1,
+                                            site_tx.ctypes.data, k5.tobytes(), ids.ctypes.data, C.byref(h)))
+        elif store is not None:
             _chk(L.m6a_io_open_store(os.fsencode(store), C.byref(h)))
         else:
             dirs = (C.c_char_p * len(input_dirs))(*[os.fsencode(d) for d in input_dirs])
@@ -216,15 +315,26 @@ class NativeSites:
 
         def view(fn, ctype, shape):
             n = int(np.prod(shape))
+            if n == 0:                                   # an empty array may have no address (sites from arrays, S = 0)
+                return np.zeros(shape, np.dtype(ctype))
             arr = np.ctypeslib.as_array(C.cast(fn(h), C.POINTER(ctype)), shape=(n,)).reshape(shape)
             arr.flags.writeable = False
             return arr
-        self.X = view(L.m6a_io_X, C.c_float, (R, 9))
-        self.site_kmers = view(L.m6a_io_site_kmers, C.c_uint8, (S, 3))
+        self.X = view(L.m6a_io_X, C.c_float, (R, 9)) if _arrays is None else None         # from_arrays: sites for the writers only
+        self.site_kmers = view(L.m6a_io_site_kmers, C.c_uint8, (S, 3)) if _arrays is None else None
         self.off = view(L.m6a_io_off, C.c_int64, (S + 1,))
         self.tx_pos = view(L.m6a_io_tx_pos, C.c_int64, (S,))
         self.read_id_values = view(L.m6a_io_read_ids, C.c_double, (R,))
-        self.read_rep = view(L.m6a_io_read_rep, C.c_int32, (R,))
+        self.read_rep = view(L.m6a_io_read_rep, C.c_int32, (R,)) if _arrays is None else None
+
+    @classmethod
+    def from_arrays(cls, off, tx_pos, tx_blob, tx_off, site_tx, kmer5, read_ids):
+        """m6a_io_sites_from_arrays: sites without X for the writers.  tx_blob / tx_off: the transcript names; site_tx [S] indexes them;
+        kmer5 [S][5] uint8 (or bytes-like rows); read_ids [R] float64."""
+        k5 = np.ascontiguousarray(np.frombuffer(b"".join(kmer5), np.uint8) if isinstance(kmer5, (list, tuple)) else kmer5, np.uint8)
+        arrays = (np.ascontiguousarray(off, np.int64), np.ascontiguousarray(tx_pos, np.int64), bytes(tx_blob), np.ascontiguousarray(tx_off, np.int64),
+                  np.ascontiguousarray(site_tx, np.uint32), k5, np.ascontiguousarray(read_ids, np.float64))
+        return cls(_arrays=arrays)
 
     def tx_id(self, i):
         return self._L.m6a_io_tx_id(self._h, i).decode()
@@ -241,7 +351,7 @@ class NativeSites:
         rp = np.ascontiguousarray(read_prob, np.float32)
         sp = np.ascontiguousarray(site_prob, np.float32)
         mr = np.ascontiguousarray(mod_ratio, np.float64)
-        assert rp.size == self.X.shape[0] and sp.size == self.tx_pos.size == mr.size
+        assert rp.size == int(self.off[-1]) and sp.size == self.tx_pos.size == mr.size
         _chk(self._L.m6a_io_write_csv_n(self._h, os.fsencode(out_dir), rp.ctypes.data, sp.ctypes.data, mr.ctypes.data,
                                         1 if write_header else 0, int(n_threads), -1 if n_sites is None else int(n_sites)))
 

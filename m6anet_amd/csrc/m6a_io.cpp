@@ -626,6 +626,8 @@ int m6a_io_save_store(const m6a_sites *s, const char *path, const char *tag)
 {
     if (!s || !path) return fail(M6A_IO_EINVAL, "null argument");
     const int64_t S = s->nS, R = s->nR;
+    if ((R && (!s->vX || !s->vRep)) || (S && !s->vK))      // m6a_io_sites_from_arrays: sites for the writers, no features
+        return fail(M6A_IO_EINVAL, "these sites hold no features (m6a_io_sites_from_arrays): nothing to store");
     std::vector<int64_t> txo((size_t)S + 1, 0);
     for (int64_t i = 0; i < S; i++) txo[(size_t)i + 1] = txo[(size_t)i] + (int64_t)s->tx_ids[(size_t)i].size();
     StoreHeader h;
@@ -709,6 +711,44 @@ int m6a_io_open_store(const char *path, m6a_sites **out)
 }
 const char *m6a_io_tx_id(const m6a_sites *s, int64_t i) { return s->tx_ids[(size_t)i].c_str(); }
 const char *m6a_io_kmer5(const m6a_sites *s, int64_t i) { return s->kmer5[(size_t)i].c_str(); }
+
+int m6a_io_sites_from_arrays(int64_t n_sites, const int64_t *off, const int64_t *tx_pos, const char *tx_blob, const int64_t *tx_off, int64_t n_tx,
+                             const uint32_t *site_tx, const char *kmer5, const double *read_ids, m6a_sites **out)
+{
+    if (!out) return M6A_IO_EINVAL;
+    *out = nullptr;
+    if (n_sites < 0 || n_tx < 0 || !off || (n_sites && (!tx_pos || !site_tx || !kmer5 || !tx_off || !tx_blob)) || (n_tx && !tx_off))
+        return fail(M6A_IO_EINVAL, "null argument");
+    if (off[0] != 0) return fail(M6A_IO_EINVAL, "off[0] must be 0");
+    for (int64_t i = 0; i < n_sites; i++) {
+        if (off[i + 1] < off[i]) return fail(M6A_IO_EINVAL, "off[] must be non-decreasing");
+        if ((int64_t)site_tx[i] >= n_tx) return fail(M6A_IO_EINVAL, "site %lld: transcript %u of %lld", (long long)i, site_tx[i], (long long)n_tx);
+    }
+    const int64_t R = off[n_sites];
+    if (R && !read_ids) return fail(M6A_IO_EINVAL, "null argument");
+    try {
+        std::unique_ptr<m6a_sites> s(new m6a_sites);
+        s->off.assign(off, off + n_sites + 1);
+        s->tx_pos.assign(tx_pos, tx_pos + n_sites);
+        s->read_ids.resize((size_t)R);
+        std::copy(read_ids, read_ids + R, s->read_ids.data());
+        s->tx_ids.resize((size_t)n_sites);
+        s->kmer5.resize((size_t)n_sites);
+        for (int64_t i = 0; i < n_sites; i++) {
+            const uint32_t t = site_tx[i];
+            s->tx_ids[(size_t)i].assign(tx_blob + tx_off[t], (size_t)(tx_off[t + 1] - tx_off[t]));
+            s->kmer5[(size_t)i].assign(kmer5 + 5 * i, 5);
+        }
+        s->view_owned();
+        s->vX = nullptr;                                    // no features: the rows are for the writers
+        s->vK = nullptr;
+        s->vRep = nullptr;
+        *out = s.release();
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory for %lld reads", (long long)R);
+    }
+}
 
 int m6a_io_format_f16(double v, char *buf336) { const int k = format_f16(v, buf336); buf336[k] = 0; return k; }
 
@@ -1997,6 +2037,9 @@ struct m6a_io_rows {
     std::vector<double> feat;
 };
 
+static void rows_of_runs(const Mapped &ev, const std::vector<IdxRun> &idx, const std::vector<std::string> &tx_names, int n_threads,
+                         int n_neighbors, m6a_io_rows &R);
+
 static int dataprep_rows_impl(const char *eventalign_path, const char *index_path, int n_threads, int n_neighbors, m6a_io_rows &R)
 {
     if (n_neighbors < 1 || n_neighbors > 16) return fail(M6A_IO_EINVAL, "n_neighbors must be 1..16");
@@ -2015,6 +2058,15 @@ static int dataprep_rows_impl(const char *eventalign_path, const char *index_pat
         if ((rc = build_index(eventalign_path, ev.p, ev.p + ev.n, n_threads, trace, idx, tx_names, bounds, nw))) return rc;
     }
     if (ev.p && ev.n) (void)madvise((void *)ev.p, ev.n, MADV_NORMAL);
+    rows_of_runs(ev, idx, tx_names, n_threads, n_neighbors, R);
+    trace.mark("dataprep rows: runs combined");
+    return M6A_IO_OK;
+}
+
+// every run on its own: its combined positions and candidate rows (status M6A_PREP_RUN_HOST where combine_read fails)
+static void rows_of_runs(const Mapped &ev, const std::vector<IdxRun> &idx, const std::vector<std::string> &tx_names, int n_threads,
+                         int n_neighbors, m6a_io_rows &R)
+{
     const size_t NR = idx.size(), K = 5 + 2 * (size_t)n_neighbors, NF = 3 * (2 * (size_t)n_neighbors + 1);
     for (const std::string &n : tx_names) { R.tx_off.push_back((int64_t)R.blob.size()); R.blob += n; }
     R.tx_off.push_back((int64_t)R.blob.size());
@@ -2057,14 +2109,12 @@ static int dataprep_rows_impl(const char *eventalign_path, const char *index_pat
         std::vector<SiteRow>().swap(B.sites);
         std::vector<double>().swap(B.feat);
     });
-    trace.mark("dataprep rows: runs combined");
     m6a_io_prep_table &t = R.t;
     t.n_neighbors = n_neighbors;
     t.n_tx = (int64_t)tx_names.size(); t.tx_blob = R.blob.data(); t.tx_off = R.tx_off.data();
     t.n_runs = (int64_t)NR; t.run_tx = R.run_tx.data(); t.run_read = R.run_read.data(); t.run_start = R.run_start.data();
     t.run_end = R.run_end.data(); t.run_npos = R.run_npos.data(); t.run_status = R.run_status.data(); t.row_off = R.row_off.data();
     t.n_rows = (int64_t)NROWS; t.row_pos = R.row_pos.data(); t.row_kmer = R.kmer.data(); t.row_feat = R.feat.data();
-    return M6A_IO_OK;
 }
 
 extern "C" int m6a_io_dataprep_rows(const char *eventalign_path, const char *index_path, int n_threads, int n_neighbors, m6a_io_rows **out)
@@ -2075,6 +2125,30 @@ extern "C" int m6a_io_dataprep_rows(const char *eventalign_path, const char *ind
         std::unique_ptr<m6a_io_rows> r(new m6a_io_rows);
         const int rc = dataprep_rows_impl(eventalign_path, index_path, n_threads, n_neighbors, *r);
         if (rc) return rc;
+        *out = r.release();
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "dataprep rows: out of memory");
+    } catch (const std::exception &e) {
+        return fail(M6A_IO_EIO, "dataprep rows: %s", e.what());
+    }
+}
+
+extern "C" int m6a_io_runs_rows(const char *eventalign_path, int64_t n_runs, const int64_t *start, const int64_t *end, const int64_t *read,
+                                int n_neighbors, int n_threads, m6a_io_rows **out)
+{
+    if (!eventalign_path || !out || n_runs < 0 || (n_runs && (!start || !end || !read))) return fail(M6A_IO_EINVAL, "null argument");
+    *out = nullptr;
+    if (n_neighbors < 1 || n_neighbors > 16) return fail(M6A_IO_EINVAL, "n_neighbors must be 1..16");
+    if (n_runs > 0xffffffffll) return fail(M6A_IO_EINVAL, "more than 2^32 runs");
+    try {
+        Mapped ev;
+        int rc = ev.open(eventalign_path, 0);               // only the given runs are read: mapped lazily
+        if (rc) return rc;
+        std::vector<IdxRun> idx((size_t)n_runs);
+        for (int64_t i = 0; i < n_runs; i++) idx[(size_t)i] = IdxRun{0, read[i], start[i], end[i]};
+        std::unique_ptr<m6a_io_rows> r(new m6a_io_rows);
+        rows_of_runs(ev, idx, {}, n_threads, n_neighbors, *r);
         *out = r.release();
         return M6A_IO_OK;
     } catch (const std::bad_alloc &) {

@@ -34,6 +34,7 @@
 namespace {
 
 thread_local std::string g_prep_err;
+thread_local int64_t g_d2h = 0;          // bytes copied device -> host by this thread's current call (m6a_prep_sites reports them)
 
 int prep_fail(int code, const char *fmt, ...)
 {
@@ -473,22 +474,35 @@ namespace {
 
 // device memory of one call, every allocation counted against the budget (free memory minus a margin, or M6A_PREP_BUDGET_MB)
 struct DevMem {
-    std::vector<void *> ptrs;
+    std::vector<std::pair<void *, size_t>> ptrs;
     size_t used = 0, budget = 0;
-    ~DevMem() { for (void *p : ptrs) (void)hipFree(p); }
+    const char *advice = "use --device cpu";     // what the budget error tells the user to do instead
+    ~DevMem() { for (auto &p : ptrs) (void)hipFree(p.first); }
     template <class T> int alloc(T *&p, size_t count, const char *what)
     {
         const size_t bytes = std::max<size_t>(16, count * sizeof(T));
         if (used + bytes > budget)
             return prep_fail(M6A_ENOMEM, "dataprep on the device needs more than its budget of %zu MB (%s: %zu MB used, %zu MB more); "
-                             "this file does not fit: use --device cpu", budget >> 20, what, used >> 20, bytes >> 20);
+                             "this file does not fit: %s", budget >> 20, what, used >> 20, bytes >> 20, advice);
         void *q = nullptr;
-        if (hipMalloc(&q, bytes) != hipSuccess) return prep_fail(M6A_ENOMEM, "hipMalloc of %zu MB failed (%s); use --device cpu", bytes >> 20, what);
-        ptrs.push_back(q);
+        if (hipMalloc(&q, bytes) != hipSuccess) return prep_fail(M6A_ENOMEM, "hipMalloc of %zu MB failed (%s); %s", bytes >> 20, what, advice);
+        ptrs.emplace_back(q, bytes);
         used += bytes;
         p = (T *)q;
         return M6A_OK;
     }
+    // hipFree now (release) or never (detach: the caller owns it from here on)
+    void drop(const void *p, bool free_it)
+    {
+        for (size_t i = 0; i < ptrs.size(); i++)
+            if (ptrs[i].first == p) {
+                if (free_it) { (void)hipFree(ptrs[i].first); used -= ptrs[i].second; }
+                ptrs.erase(ptrs.begin() + (ptrdiff_t)i);
+                return;
+            }
+    }
+    void release(const void *p) { drop(p, true); }
+    void detach(const void *p) { drop(p, false); }
 };
 
 struct Streams {
@@ -537,6 +551,7 @@ int scan_total(DevMem &m, int64_t *a, int64_t n, hipStream_t s, int64_t &total)
     int rc = scan_excl(m, a, n + 1, s);
     if (rc) return rc;
     PCHK(hipMemcpyAsync(&total, a + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    g_d2h += (int64_t)sizeof(int64_t);
     PCHK(hipStreamSynchronize(s));
     return M6A_OK;
 }
@@ -573,30 +588,31 @@ int read_index(const char *path, std::vector<std::string> &names, std::vector<ui
     return M6A_OK;
 }
 
-int prep_impl(int device_id, const char *path, int w, const char *index_path, m6a_prep &P)
+// The device results of the front half (upload, newline scan, lines, runs, combine, windows); all of them live in `m`.
+struct Front {
+    int64_t n = 0, NR = 0, NROW = 0;
+    RunDev *runs = nullptr;
+    int64_t *row_off = nullptr, *row_pos = nullptr;
+    uint8_t *row_kmer = nullptr;
+    double *row_feat = nullptr;
+    std::vector<const void *> scratch;      // the file, its newlines, lines and combined positions: nothing after the windows reads them
+};
+
+// istart / iend: the runs of an eventalign.index (--skip_index), or null.  ms[0..2], ms[5] as m6a_prep_times reports them.
+int front_half(int device_id, const char *path, int w, const std::vector<int64_t> *istart, const std::vector<int64_t> *iend,
+               DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
 {
-    if (w < 1 || w > 16) return prep_fail(M6A_EINVAL, "n_neighbors must be 1..16");
+    const bool index_path = istart != nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
     if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
     PCHK(hipSetDevice(device_id));
-    Fd fd;
     fd.fd = ::open(path, O_RDONLY);
     if (fd.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", path);
     struct stat st;
     if (fstat(fd.fd, &st) != 0) return prep_fail(M6A_EIO, "cannot stat %s", path);
     const int64_t n = (int64_t)st.st_size;
-
-    // --skip_index: the runs come from the file (read before anything touches the device, as the host path does)
-    std::vector<std::string> names;
-    std::vector<uint32_t> itx;
-    std::vector<int64_t> iread, istart, iend;
-    if (index_path) {
-        int rc = read_index(index_path, names, itx, iread, istart, iend);
-        if (rc) return rc;
-    }
-
-    DevMem m;
+    F.n = n;
     {
         size_t fr = 0, tot = 0;
         PCHK(hipMemGetInfo(&fr, &tot));
@@ -612,7 +628,6 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
     if (!rc) rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts");
     if (rc) return rc;
 
-    Streams S;
     for (int i = 0; i < 2; i++) {
         PCHK(hipStreamCreateWithFlags(&S.s[i], hipStreamNonBlocking));
         PCHK(hipEventCreateWithFlags(&S.copied[i], hipEventDisableTiming));
@@ -647,8 +662,8 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
     if (n == 0) PCHK(hipMemsetAsync(bcnt, 0, sizeof(int64_t), s));
     PCHK(hipStreamSynchronize(S.s[1]));
     PCHK(hipStreamSynchronize(s));
-    P.ms[0] = now_ms() - t_up;
-    P.ms[5] = P.ms[0] > 0 ? (double)n / (P.ms[0] * 1e6) : 0;
+    ms[0] = now_ms() - t_up;
+    ms[5] = ms[0] > 0 ? (double)n / (ms[0] * 1e6) : 0;
 
     // ---- newline offsets
     double t1 = now_ms();
@@ -660,10 +675,10 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
     nl_write_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)df, nb, bcnt, nl);
     PCHK(hipGetLastError());
     uint8_t last = '\n';
-    if (n > 0) PCHK(hipMemcpyAsync(&last, df + n - 1, 1, hipMemcpyDeviceToHost, s));
+    if (n > 0) { PCHK(hipMemcpyAsync(&last, df + n - 1, 1, hipMemcpyDeviceToHost, s)); g_d2h += 1; }
     PCHK(hipStreamSynchronize(s));
     const int64_t nlines = NL + (last != '\n' ? 1 : 0);
-    P.ms[1] = now_ms() - t1;
+    ms[1] = now_ms() - t1;
 
     // ---- lines, runs, combine, windows
     t1 = now_ms();
@@ -679,6 +694,7 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
     }
     unsigned long long bad_at = none;
     PCHK(hipMemcpyAsync(&bad_at, bad, sizeof bad_at, hipMemcpyDeviceToHost, s));
+    g_d2h += (int64_t)sizeof bad_at;
     PCHK(hipStreamSynchronize(s));
     if (!index_path && bad_at != none) return prep_fail(M6A_EFORMAT, "%s: short line at byte %lld", path, (long long)bad_at);
 
@@ -693,6 +709,7 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
         int64_t *vline, *nr;
         if ((rc = m.alloc(vline, (size_t)NV + 1, "valid lines"))) return rc;
         if ((rc = m.alloc(nr, (size_t)NV + 1, "run starts"))) return rc;
+        F.scratch.insert(F.scratch.end(), {vflag, vline, nr});
         compact_kernel<<<grid(nlines), kBlk, 0, s>>>(vflag, nlines, ev, vline);
         PCHK(hipGetLastError());
         if (NV > 0) {
@@ -707,10 +724,10 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
             PCHK(hipGetLastError());
         }
     } else {
-        NR = (int64_t)istart.size();
+        NR = (int64_t)istart->size();
         if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
         std::vector<RunDev> h((size_t)NR);
-        for (int64_t r = 0; r < NR; r++) { h[(size_t)r].start = istart[(size_t)r]; h[(size_t)r].end = iend[(size_t)r]; }
+        for (int64_t r = 0; r < NR; r++) { h[(size_t)r].start = (*istart)[(size_t)r]; h[(size_t)r].end = (*iend)[(size_t)r]; }
         if (NR) PCHK(hipMemcpyAsync(runs, h.data(), (size_t)NR * sizeof(RunDev), hipMemcpyHostToDevice, s));
         if (NR) {
             runs_from_index_kernel<<<grid(NR), kBlk, 0, s>>>(n, nl, NL, nlines, runs, NR);
@@ -750,7 +767,36 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
         PCHK(hipGetLastError());
     }
     PCHK(hipStreamSynchronize(s));
-    P.ms[2] = now_ms() - t1;
+    ms[2] = now_ms() - t1;
+    F.NR = NR; F.NROW = NROW; F.runs = runs; F.row_off = row_off; F.row_pos = drow_pos; F.row_kmer = drow_kmer; F.row_feat = drow_feat;
+    F.scratch.insert(F.scratch.end(), {df, bcnt, nl, ev, bad, pos_off, ps});
+    return M6A_OK;
+}
+
+int prep_impl(int device_id, const char *path, int w, const char *index_path, m6a_prep &P)
+{
+    if (w < 1 || w > 16) return prep_fail(M6A_EINVAL, "n_neighbors must be 1..16");
+    // --skip_index: the runs come from the file (read before anything touches the device, as the host path does)
+    std::vector<std::string> names;
+    std::vector<uint32_t> itx;
+    std::vector<int64_t> iread, istart, iend;
+    if (index_path) {
+        int rc = read_index(index_path, names, itx, iread, istart, iend);
+        if (rc) return rc;
+    }
+    DevMem m;
+    Streams S;
+    Fd fd;
+    Front F;
+    int rc = front_half(device_id, path, w, index_path ? &istart : nullptr, index_path ? &iend : nullptr, m, S, fd, F, P.ms);
+    if (rc) return rc;
+    hipStream_t s = S.s[0];
+    const int64_t NR = F.NR, NROW = F.NROW, K = 5 + 2 * w, NF = 3 * (2 * w + 1);
+    RunDev *runs = F.runs;
+    const int64_t *row_off = F.row_off, *drow_pos = F.row_pos;
+    const uint8_t *drow_kmer = F.row_kmer;
+    const double *drow_feat = F.row_feat;
+    double t1;
 
     // ---- to the host
     t1 = now_ms();
@@ -823,6 +869,811 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
 
 }  // namespace
 
+// ---- the back half (m6a_prep_sites): the candidate rows, still in HBM, -> the arrays m6a_io_load_sites makes of data.json -------
+// What m6a_io_dataprep_write's preprocess_transcript_rows / emit_transcript and then the loader do, on the device:
+//   segments   runs where the contig bytes change; the host interns their names (transcript ids in order of first appearance)
+//              and gives every segment its transcript, the rank of its first run inside the transcript and the readcount verdict
+//   runs       a run is used when its rank <= readcount_max, its transcript has >= readcount_min counted runs and npos > 1; of
+//              the runs of one (transcript, read) the last supplies the rows and the first the place (a Python dict's overwrite)
+//   rows       the used runs' rows sorted by (transcript, position, place) -- LSD radix sort, 4-bit digits, stable
+//   sites      cut where (transcript, position) changes; 7-mers must agree; kept with >= min_segment_count and >= 20 reads
+//   X          (float)((v - mean) / std) in f64 per feature, as m6a_io_load_sites computes it
+namespace {
+
+constexpr int kRadixItems = 16, kRadixTile = kBlk * kRadixItems;     // 4096 keys per block
+static_assert(kBlk == 256, "radix_scatter_kernel scans 16 digits x 16 chunks of 16 lanes: one lane per (digit, chunk)");
+
+__global__ void radix_hist_kernel(const uint64_t *__restrict__ key, int64_t n, int shift, int64_t nblk, int64_t *__restrict__ hist)
+{
+    __shared__ int c[16];
+    if (threadIdx.x < 16) c[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * kRadixTile;
+    for (int k = 0; k < kRadixItems; k++) {
+        const int64_t i = base + (int64_t)k * kBlk + threadIdx.x;
+        if (i < n) atomicAdd(&c[(key[i] >> shift) & 15], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) hist[threadIdx.x * nblk + blockIdx.x] = c[threadIdx.x];
+}
+
+// stable: lane t owns keys [16 t, 16 t + 16) of the block's tile, in order; hist = exclusive scan, digit-major then block
+__global__ void radix_scatter_kernel(const uint64_t *__restrict__ key, const uint32_t *__restrict__ val, int64_t n, int shift, int64_t nblk,
+                                     const int64_t *__restrict__ hist, uint64_t *__restrict__ key2, uint32_t *__restrict__ val2)
+{
+    __shared__ int cnt[16][kBlk];
+    __shared__ int part[16][16];
+    const int t = threadIdx.x;
+    for (int d = 0; d < 16; d++) cnt[d][t] = 0;
+    const int64_t i0 = (int64_t)blockIdx.x * kRadixTile + (int64_t)t * kRadixItems;
+    for (int k = 0; k < kRadixItems; k++)
+        if (i0 + k < n) cnt[(key[i0 + k] >> shift) & 15][t]++;
+    __syncthreads();
+    const int d = t >> 4, c = t & 15;                  // per digit, the exclusive scan over the lanes: 16 chunks of 16 lanes
+    int sum = 0;
+    for (int k = 0; k < 16; k++) sum += cnt[d][c * 16 + k];
+    part[d][c] = sum;
+    __syncthreads();
+    if (t < 16) {
+        int run = 0;
+        for (int k = 0; k < 16; k++) { const int v = part[t][k]; part[t][k] = run; run += v; }
+    }
+    __syncthreads();
+    int run = part[d][c];
+    for (int k = 0; k < 16; k++) { const int v = cnt[d][c * 16 + k]; cnt[d][c * 16 + k] = run; run += v; }
+    __syncthreads();
+    for (int k = 0; k < kRadixItems && i0 + k < n; k++) {
+        const uint64_t x = key[i0 + k];
+        const int g = (int)((x >> shift) & 15);
+        const int64_t o = hist[g * nblk + blockIdx.x] + cnt[g][t]++;
+        key2[o] = x;
+        val2[o] = val[i0 + k];
+    }
+}
+
+// flag[i] -> list of the flagged i (after the exclusive scan of the flags: ex[i + 1] != ex[i])
+__global__ void compact_u32_kernel(const int64_t *__restrict__ ex, int64_t n, uint32_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i < n && ex[i + 1] != ex[i]) out[ex[i]] = (uint32_t)i;
+}
+
+struct SegDev { int64_t first, contig; int32_t len, pad; };        // a segment: runs from `first` on with the same contig bytes
+struct SegUp { int64_t rank0; uint32_t tx, keep; };                  // from the host: its transcript and the rank of its first run
+struct DeclDev { int64_t run, start, end, read; };                   // a run the front half declined
+struct DeclUp { int64_t run, npos; };
+
+__global__ void run_flags_kernel(const RunDev *__restrict__ runs, int64_t NR, int64_t *__restrict__ seg, int64_t *__restrict__ decl)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r >= NR) return;
+    seg[r] = r == 0 || !runs[r].same_contig;
+    decl[r] = runs[r].status != M6A_PREP_RUN_OK;
+}
+
+__global__ void run_lists_kernel(const RunDev *__restrict__ runs, int64_t NR, const int64_t *__restrict__ sx, const int64_t *__restrict__ dx,
+                                 SegDev *__restrict__ seg, DeclDev *__restrict__ decl)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r >= NR) return;
+    const RunDev &R = runs[r];
+    if (sx[r + 1] != sx[r]) seg[sx[r]] = SegDev{r, R.contig, R.contig_len, 0};
+    if (dx[r + 1] != dx[r]) decl[dx[r]] = DeclDev{r, R.start, R.end, R.read};
+}
+
+__global__ void decl_patch_kernel(RunDev *__restrict__ runs, const DeclUp *__restrict__ up, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    runs[up[i].run].npos = up[i].npos;
+    runs[up[i].run].status = M6A_PREP_RUN_OK;
+}
+
+// preprocess_transcript_rows' loop: counted (rank <= lim), transcript kept, `if data.size > 1`
+__global__ void run_select_kernel(const RunDev *__restrict__ runs, int64_t NR, const int64_t *__restrict__ sx, const SegDev *__restrict__ seg,
+                                  const SegUp *__restrict__ up, int64_t lim, uint32_t *__restrict__ run_tx, int64_t *__restrict__ run_rank,
+                                  int64_t *__restrict__ elig)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r >= NR) return;
+    const int64_t g = sx[r + 1] - 1;
+    const int64_t rank = up[g].rank0 + (r - seg[g].first);
+    run_tx[r] = up[g].tx;
+    run_rank[r] = rank;
+    elig[r] = up[g].keep && rank <= lim && runs[r].status == M6A_PREP_RUN_OK && runs[r].npos > 1;
+}
+
+struct RowSrc {                            // rows [0, n0) are the front half's, the rest the host half's (declined runs)
+    const int64_t *pos0, *pos1;
+    const uint8_t *kmer0, *kmer1;
+    const double *feat0, *feat1;
+    int64_t n0;
+    __device__ int64_t pos(int64_t k) const { return k < n0 ? pos0[k] : pos1[k - n0]; }
+    __device__ const uint8_t *kmer(int64_t k) const { return k < n0 ? kmer0 + k * 7 : kmer1 + (k - n0) * 7; }
+    __device__ const double *feat(int64_t k) const { return k < n0 ? feat0 + k * 9 : feat1 + (k - n0) * 9; }
+};
+
+__device__ inline uint64_t bias(int64_t v) { return (uint64_t)v ^ (1ull << 63); }   // order-preserving int64 -> uint64
+
+// min / max of runs[idx[i]].read (what == 0) or rs.pos(idx[i]) (what == 1), biased: mm[0] = min, mm[1] = max
+__global__ void minmax_kernel(const uint32_t *__restrict__ idx, int64_t n, int what, const RunDev *__restrict__ runs, RowSrc rs,
+                              unsigned long long *__restrict__ mm)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    unsigned long long lo = ~0ull, hi = 0;
+    if (i < n) lo = hi = bias(what == 0 ? runs[idx[i]].read : rs.pos(idx[i]));
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    if ((threadIdx.x & 63) == 0 && lo <= hi) { atomicMin(&mm[0], lo); atomicMax(&mm[1], hi); }
+}
+
+// the key of run E[i]: transcript << read_bits | (read - read_min); use: 1 = the read part, 2 = the transcript part
+__global__ void run_key_kernel(const uint32_t *__restrict__ E, int64_t n, const RunDev *__restrict__ runs, const uint32_t *__restrict__ run_tx,
+                               uint64_t read_min, int tx_shift, unsigned use, uint64_t *__restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = E[i];
+    uint64_t v = 0;
+    if (use & 1) v |= bias(runs[r].read) - read_min;
+    if (use & 2) v |= (uint64_t)run_tx[r] << tx_shift;
+    key[i] = v;
+}
+
+// E sorted by (transcript, read, rank): the last run of a group supplies the rows, the first its place
+__global__ void dup_head_kernel(const uint32_t *__restrict__ E, int64_t n, const RunDev *__restrict__ runs, const uint32_t *__restrict__ run_tx,
+                                int64_t *__restrict__ head)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    head[i] = i == 0 || run_tx[E[i]] != run_tx[E[i - 1]] || runs[E[i]].read != runs[E[i - 1]].read;
+}
+
+__global__ void dup_first_kernel(const uint32_t *__restrict__ E, int64_t n, const int64_t *__restrict__ gx, const int64_t *__restrict__ run_rank,
+                                 int64_t *__restrict__ gfirst)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i < n && gx[i + 1] != gx[i]) gfirst[gx[i]] = run_rank[E[i]];
+}
+
+__global__ void dup_last_kernel(const uint32_t *__restrict__ E, int64_t n, const int64_t *__restrict__ gx, const int64_t *__restrict__ gfirst,
+                                uint8_t *__restrict__ used, int64_t *__restrict__ run_place)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    if (i == n - 1 || gx[i + 2] != gx[i + 1]) {
+        used[E[i]] = 1;
+        run_place[E[i]] = gfirst[gx[i + 1] - 1];
+    }
+}
+
+__global__ void used_rows_count_kernel(const uint8_t *__restrict__ used, const int64_t *__restrict__ row_off, int64_t NR, int64_t *__restrict__ cnt)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r < NR) cnt[r] = used[r] ? row_off[r + 1] - row_off[r] : 0;
+}
+
+__global__ void used_rows_write_kernel(const uint8_t *__restrict__ used, const int64_t *__restrict__ row_off, int64_t NR, const int64_t *__restrict__ ex,
+                                       uint32_t *__restrict__ L, uint32_t *__restrict__ row_run)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r >= NR || !used[r]) return;
+    for (int64_t k = row_off[r], o = ex[r]; k < row_off[r + 1]; k++, o++) {
+        L[o] = (uint32_t)k;
+        row_run[k] = (uint32_t)r;
+    }
+}
+
+// the host half's rows: appended behind the front half's
+__global__ void host_flag_kernel(const uint8_t *__restrict__ used, const int64_t *__restrict__ hrun, int64_t NH, int64_t *__restrict__ flag)
+{
+    const int64_t h = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (h < NH) flag[h] = used[hrun[h]];
+}
+
+__global__ void host_rows_kernel(const int64_t *__restrict__ hrun, int64_t NH, int64_t n0, int64_t L0, const int64_t *__restrict__ ex,
+                                 uint32_t *__restrict__ L, uint32_t *__restrict__ row_run)
+{
+    const int64_t h = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (h >= NH) return;
+    row_run[n0 + h] = (uint32_t)hrun[h];
+    if (ex[h + 1] != ex[h]) L[L0 + ex[h]] = (uint32_t)(n0 + h);
+}
+
+struct RowKey { uint64_t pos_min; int sh_tx, sh_pos, sh_place; unsigned use; };   // use: 1 transcript, 2 position, 4 place
+
+__global__ void row_key_kernel(const uint32_t *__restrict__ L, int64_t n, RowSrc rs, const uint32_t *__restrict__ row_run,
+                               const uint32_t *__restrict__ run_tx, const int64_t *__restrict__ run_place, RowKey k, uint64_t *__restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t row = L[i], r = row_run[row];
+    uint64_t v = 0;
+    if (k.use & 1) v |= (uint64_t)run_tx[r] << k.sh_tx;
+    if (k.use & 2) v |= (bias(rs.pos(row)) - k.pos_min) << k.sh_pos;
+    if (k.use & 4) v |= (uint64_t)run_place[r] << k.sh_place;
+    key[i] = v;
+}
+
+__global__ void site_head_kernel(const uint32_t *__restrict__ L, int64_t n, RowSrc rs, const uint32_t *__restrict__ row_run,
+                                 const uint32_t *__restrict__ run_tx, int64_t *__restrict__ head)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    head[i] = i == 0 || run_tx[row_run[L[i]]] != run_tx[row_run[L[i - 1]]] || rs.pos(L[i]) != rs.pos(L[i - 1]);
+}
+
+__global__ void site_start_kernel(const int64_t *__restrict__ hx, int64_t n, int64_t *__restrict__ start)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    if (hx[i + 1] != hx[i]) start[hx[i]] = i;
+    if (i == n - 1) start[hx[n]] = n;
+}
+
+// emit_transcript: every read of a site carries the site's 7-mer (else M6A_IO_EFORMAT at the first such site)
+__global__ void site_check_kernel(const uint32_t *__restrict__ L, int64_t n, RowSrc rs, const int64_t *__restrict__ hx,
+                                  const int64_t *__restrict__ start, unsigned long long *__restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    const int64_t s = hx[i + 1] - 1;
+    const uint8_t *a = rs.kmer(L[i]), *b = rs.kmer(L[start[s]]);
+    for (int k = 0; k < 7; k++)
+        if (a[k] != b[k]) { atomicMin(bad, (unsigned long long)s); return; }
+}
+
+__global__ void probe_kernel(const uint32_t *__restrict__ L, const int64_t *__restrict__ start, int64_t s, RowSrc rs,
+                             const uint32_t *__restrict__ row_run, const uint32_t *__restrict__ run_tx, int64_t *__restrict__ out)
+{
+    const uint32_t k = L[start[s]];
+    out[0] = run_tx[row_run[k]];
+    out[1] = rs.pos(k);
+}
+
+__global__ void site_keep_kernel(const int64_t *__restrict__ start, int64_t NS, int64_t need, int64_t *__restrict__ flag)
+{
+    const int64_t s = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (s < NS) flag[s] = start[s + 1] - start[s] >= need;
+}
+
+__global__ void site_emit_kernel(const int64_t *__restrict__ start, int64_t NS, const int64_t *__restrict__ kx, int64_t *__restrict__ src,
+                                 int64_t *__restrict__ cnt)
+{
+    const int64_t s = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (s >= NS || kx[s + 1] == kx[s]) return;
+    src[kx[s]] = start[s];
+    cnt[kx[s]] = start[s + 1] - start[s];
+}
+
+__device__ inline uint64_t pack5(const uint8_t *k)
+{
+    return ((uint64_t)k[0] << 32) | ((uint64_t)k[1] << 24) | ((uint64_t)k[2] << 16) | ((uint64_t)k[3] << 8) | (uint64_t)k[4];
+}
+
+__device__ inline int find5(const uint64_t *keys, int n, uint64_t v)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int m = (lo + hi) >> 1; if (keys[m] < v) lo = m + 1; else hi = m; }
+    return lo < n && keys[lo] == v ? lo : -1;
+}
+
+// per kept site: transcript, position, 7-mer; the norm rows and the vocabulary ids of its three 5-mers (m6a_io_load_sites' order
+// of checks: the normalisation factors of the three 5-mers, then the vocabulary); bad = 8 site + what
+__global__ void site_info_kernel(const uint32_t *__restrict__ L, const int64_t *__restrict__ src, int64_t S, RowSrc rs,
+                                 const uint32_t *__restrict__ row_run, const uint32_t *__restrict__ run_tx, const uint64_t *__restrict__ nkeys,
+                                 const int32_t *__restrict__ nix, int n_norm, const uint64_t *__restrict__ vocab, int n_vocab,
+                                 int32_t *__restrict__ site_norm,
+                                 uint8_t *__restrict__ site_kmers, uint32_t *__restrict__ site_tx, int64_t *__restrict__ site_pos,
+                                 uint8_t *__restrict__ site_k7, unsigned long long *__restrict__ bad)
+{
+    const int64_t s = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (s >= S) return;
+    const uint32_t k = L[src[s]];
+    const uint8_t *km = rs.kmer(k);
+    site_tx[s] = run_tx[row_run[k]];
+    site_pos[s] = rs.pos(k);
+    for (int c = 0; c < 7; c++) site_k7[s * 7 + c] = km[c];
+    for (int c = 0; c < 3; c++) {
+        site_norm[s * 3 + c] = 0;
+        if (!n_norm) continue;
+        const int j = find5(nkeys, n_norm, pack5(km + c));
+        if (j < 0) { atomicMin(bad, (unsigned long long)(s * 8 + c)); return; }
+        site_norm[s * 3 + c] = nix[j];
+    }
+    for (int c = 0; c < 3; c++) {
+        const int v = find5(vocab, n_vocab, pack5(km + c));
+        if (v < 0) { atomicMin(bad, (unsigned long long)(s * 8 + 3 + c)); return; }
+        site_kmers[s * 3 + c] = (uint8_t)v;
+    }
+}
+
+// one lane per read of the kept sites: X[i][9] and the read id
+__global__ void x_kernel(const uint32_t *__restrict__ L, const int64_t *__restrict__ src, const int64_t *__restrict__ off, int64_t S, int64_t R,
+                         RowSrc rs, const uint32_t *__restrict__ row_run, const RunDev *__restrict__ runs, const int32_t *__restrict__ site_norm,
+                         const double *__restrict__ nmean, const double *__restrict__ nstd, int n_norm, float *__restrict__ X,
+                         double *__restrict__ read_ids)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= R) return;
+    int64_t lo = 0, hi = S - 1;                          // the site s with off[s] <= i < off[s + 1]
+    while (lo < hi) { const int64_t m = (lo + hi + 1) >> 1; if (off[m] <= i) lo = m; else hi = m - 1; }
+    const int64_t s = lo;
+    const uint32_t k = L[src[s] + (i - off[s])];
+    const double *f = rs.feat(k);
+    for (int c = 0; c < 3; c++) {
+        const int64_t nr = 3 * (int64_t)site_norm[s * 3 + c];
+        for (int q = 0; q < 3; q++) {
+            double v = f[3 * c + q];
+            if (v != v) v = __longlong_as_double(0x7ff8000000000000ll);      // the NaN json.loads / the loader make of "NaN"
+            X[i * 9 + 3 * c + q] = n_norm ? (float)((v - nmean[nr + q]) / nstd[nr + q]) : (float)v;
+        }
+    }
+    read_ids[i] = (double)runs[row_run[k]].read;
+}
+
+const unsigned long long kMinMax0[2] = {~0ull, 0}, kNone = ~0ull;
+
+int bits_for(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+// stable sort of (key, val) by the low `bits` bits of key; key / val end up pointing at the sorted pair (swapped with key2 / val2)
+int radix_sort(DevMem &m, uint64_t *&key, uint32_t *&val, uint64_t *&key2, uint32_t *&val2, int64_t n, int bits, hipStream_t s)
+{
+    if (n <= 1 || bits <= 0) return M6A_OK;
+    const int64_t nblk = (n + kRadixTile - 1) / kRadixTile;
+    int64_t *hist;
+    int rc = m.alloc(hist, (size_t)(16 * nblk) + 1, "sort");
+    if (rc) return rc;
+    for (int sh = 0; sh < bits; sh += 4) {
+        radix_hist_kernel<<<(unsigned)nblk, kBlk, 0, s>>>(key, n, sh, nblk, hist);
+        PCHK(hipGetLastError());
+        if ((rc = scan_excl(m, hist, 16 * nblk, s))) return rc;
+        radix_scatter_kernel<<<(unsigned)nblk, kBlk, 0, s>>>(key, val, n, sh, nblk, hist, key2, val2);
+        PCHK(hipGetLastError());
+        std::swap(key, key2);
+        std::swap(val, val2);
+    }
+    PCHK(hipStreamSynchronize(s));
+    m.release(hist);
+    return M6A_OK;
+}
+
+template <class T> int d2h(T *dst, const T *src, size_t count, hipStream_t s)
+{
+    if (!count) return M6A_OK;
+    PCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, s));
+    g_d2h += (int64_t)(count * sizeof(T));
+    return M6A_OK;
+}
+
+template <class T> int h2d(T *dst, const T *src, size_t count, hipStream_t s)
+{
+    if (!count) return M6A_OK;
+    PCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, s));
+    return M6A_OK;
+}
+
+// the 66-word vocabulary of m6a_io.cpp (sorted unique 5-mers of all N-DRACH-N 7-mers), packed like pack5
+std::vector<uint64_t> vocab_keys()
+{
+    std::vector<uint64_t> v;
+    const std::string N = "ACGT", D = "AGT", R = "GA", H = "ACT";
+    for (char a : N) for (char d : D) for (char r : R) for (char h : H) for (char b : N) {
+        const char k7[7] = {a, d, r, 'A', 'C', h, b};
+        for (int i = 0; i < 3; i++) {
+            uint64_t x = 0;
+            for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)k7[i + j];
+            v.push_back(x);
+        }
+    }
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return v;
+}
+
+}  // namespace
+
+struct m6a_prep_sites {
+    m6a_prep_sites_info info{};
+    int device = 0;
+    std::vector<void *> dev;                 // X, site_kmers, off, read_prob, site_prob, mod_ratio
+    std::vector<int64_t> off, pos, tx_off;
+    std::vector<uint32_t> tx;
+    std::vector<char> k7;
+    std::string blob;
+    std::vector<double> ids;
+    ~m6a_prep_sites() { for (void *p : dev) (void)hipFree(p); }
+};
+
+namespace {
+
+int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
+               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites &P)
+{
+    if (n_norm < 0 || (n_norm > 0 && (!norm_kmers || !norm_mean || !norm_std))) return prep_fail(M6A_EINVAL, "bad normalisation arguments");
+    const double t_all = now_ms();
+    g_d2h = 0;
+    double *ms = P.info.ms, fms[6] = {0, 0, 0, 0, 0, 0};
+    DevMem m;
+    m.advice = "run `dataprep` and then `inference` instead (the two-step path)";
+    Streams S;
+    Fd fd;
+    Front F;
+    int rc = front_half(device_id, path, 1, nullptr, nullptr, m, S, fd, F, fms);
+    if (rc) return rc;
+    ms[0] = fms[0]; ms[1] = fms[1]; ms[2] = fms[2]; ms[6] = fms[5];
+    hipStream_t s = S.s[0];
+    PCHK(hipStreamSynchronize(s));
+    for (const void *p : F.scratch) m.release(p);          // the file and its line records: X needs the room
+    double t1 = now_ms(), dev_ms = 0, host_ms = 0;
+    const int64_t NR = F.NR, NROW = F.NROW;
+    if (NR > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 runs");
+
+    // ---- segments and declined runs, to the host
+    int64_t *sx, *dx, NSEG = 0, ND = 0;
+    if ((rc = m.alloc(sx, (size_t)NR + 1, "segments")) || (rc = m.alloc(dx, (size_t)NR + 1, "declined runs"))) return rc;
+    if (NR) {
+        run_flags_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, dx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, sx, NR, s, NSEG)) || (rc = scan_total(m, dx, NR, s, ND))) return rc;
+    SegDev *seg;
+    DeclDev *decl;
+    if ((rc = m.alloc(seg, (size_t)NSEG + 1, "segments")) || (rc = m.alloc(decl, (size_t)ND + 1, "declined runs"))) return rc;
+    if (NR) {
+        run_lists_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, dx, seg, decl);
+        PCHK(hipGetLastError());
+    }
+    std::vector<SegDev> hseg((size_t)NSEG);
+    std::vector<DeclDev> hdecl((size_t)ND);
+    if ((rc = d2h(hseg.data(), seg, (size_t)NSEG, s)) || (rc = d2h(hdecl.data(), decl, (size_t)ND, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    dev_ms += now_ms() - t1;
+
+    // ---- the host: transcript names (read from the file where the contig changes), ranks, the readcount verdict, declined runs
+    t1 = now_ms();
+    std::unordered_map<std::string, uint32_t> ids;
+    std::vector<SegUp> up((size_t)NSEG);
+    std::vector<int64_t> tx_runs;
+    std::string nm;
+    for (int64_t g = 0; g < NSEG; g++) {
+        const SegDev &G = hseg[(size_t)g];
+        nm.resize((size_t)G.len);
+        for (int64_t got = 0; got < G.len;) {
+            const ssize_t k = ::pread(fd.fd, &nm[(size_t)got], (size_t)(G.len - got), (off_t)(G.contig + got));
+            if (k < 0 && errno == EINTR) continue;
+            if (k <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
+            got += k;
+        }
+        auto it = ids.find(nm);
+        uint32_t t;
+        if (it != ids.end()) t = it->second;
+        else {
+            t = (uint32_t)ids.size();
+            ids.emplace(nm, t);
+            P.tx_off.push_back((int64_t)P.blob.size());
+            P.blob += nm;
+            tx_runs.push_back(0);
+        }
+        const int64_t len = (g + 1 < NSEG ? hseg[(size_t)g + 1].first : NR) - G.first;
+        up[(size_t)g].rank0 = tx_runs[t];
+        up[(size_t)g].tx = t;
+        tx_runs[t] += len;
+    }
+    P.tx_off.push_back((int64_t)P.blob.size());
+    const int64_t lim = std::max(0, rmax);                  // `if ++readcount > readcount_max: break` after the first run
+    for (SegUp &u : up) u.keep = std::min(tx_runs[u.tx], lim + 1) >= rmin;
+    // declined runs the host loop reaches: combined and windowed by the host half
+    std::vector<int64_t> cstart, cend, cread, crun;
+    for (const DeclDev &d : hdecl) {
+        const int64_t g = (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), d.run, [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
+        if (up[(size_t)g].rank0 + (d.run - hseg[(size_t)g].first) > lim) continue;
+        cstart.push_back(d.start); cend.push_back(d.end); cread.push_back(d.read); crun.push_back(d.run);
+    }
+    std::vector<DeclUp> dup;
+    std::vector<int64_t> hpos, hrun;
+    std::vector<uint8_t> hkmer;
+    std::vector<double> hfeat;
+    if (!crun.empty()) {
+        if (!host || !host->rows || !host->table || !host->free)
+            return prep_fail(M6A_EINVAL, "%zu runs need the host half and none was given", crun.size());
+        struct m6a_io_rows *hr = nullptr;
+        const int hrc = host->rows(path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, n_threads, &hr);
+        if (hrc != 0 || !hr) {                              // its own code and text (m6a_io's -1..-4 -> M6A_EINVAL, ENOMEM, EIO, EFORMAT)
+            const int code = hrc == -2 ? M6A_ENOMEM : hrc == -3 ? M6A_EIO : hrc == -4 ? M6A_EFORMAT : hrc == -1 ? M6A_EINVAL : M6A_EIO;
+            return prep_fail(code, "%s", host->error ? host->error() : "the host half failed on the declined runs");
+        }
+        struct Guard { const m6a_prep_host_half *h; struct m6a_io_rows *r; ~Guard() { h->free(r); } } guard{host, hr};
+        const m6a_io_prep_table *T = host->table(hr);
+        if (!T || T->n_runs != (int64_t)crun.size() || T->n_neighbors != 1) return prep_fail(M6A_EINVAL, "the host half returned a bad table");
+        for (size_t i = 0; i < crun.size(); i++) {
+            if (T->run_status[i] != M6A_PREP_RUN_OK) {
+                const int64_t g = (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), crun[i], [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
+                const uint32_t t = up[(size_t)g].tx;
+                return prep_fail(M6A_EFORMAT, "malformed eventalign line for %.*s", (int)(P.tx_off[t + 1] - P.tx_off[t]), P.blob.data() + P.tx_off[t]);
+            }
+            dup.push_back(DeclUp{crun[i], T->run_npos[i]});
+            for (int64_t k = T->row_off[i]; k < T->row_off[i + 1]; k++) {
+                hpos.push_back(T->row_pos[k]);
+                hkmer.insert(hkmer.end(), T->row_kmer + k * 7, T->row_kmer + k * 7 + 7);
+                hfeat.insert(hfeat.end(), T->row_feat + k * 9, T->row_feat + k * 9 + 9);
+                hrun.push_back(crun[i]);
+            }
+        }
+    }
+    const int64_t NH = (int64_t)hpos.size(), NT = (int64_t)tx_runs.size();
+    if (NROW + NH > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate rows");
+    host_ms += now_ms() - t1;
+
+    // ---- runs: used or not, and their place
+    t1 = now_ms();
+    SegUp *dup_seg;
+    DeclUp *ddecl;
+    int64_t *dhpos, *dhrun;
+    uint8_t *dhkmer;
+    double *dhfeat;
+    if ((rc = m.alloc(dup_seg, (size_t)NSEG + 1, "segments")) || (rc = m.alloc(ddecl, dup.size() + 1, "declined runs")) ||
+        (rc = m.alloc(dhpos, (size_t)NH + 1, "host rows")) || (rc = m.alloc(dhrun, (size_t)NH + 1, "host rows")) ||
+        (rc = m.alloc(dhkmer, (size_t)NH * 7 + 1, "host rows")) || (rc = m.alloc(dhfeat, (size_t)NH * 9 + 1, "host rows")))
+        return rc;
+    if ((rc = h2d(dup_seg, up.data(), up.size(), s)) || (rc = h2d(ddecl, dup.data(), dup.size(), s)) || (rc = h2d(dhpos, hpos.data(), hpos.size(), s)) ||
+        (rc = h2d(dhrun, hrun.data(), hrun.size(), s)) || (rc = h2d(dhkmer, hkmer.data(), hkmer.size(), s)) ||
+        (rc = h2d(dhfeat, hfeat.data(), hfeat.size(), s)))
+        return rc;
+    if (!dup.empty()) {
+        decl_patch_kernel<<<grid((int64_t)dup.size()), kBlk, 0, s>>>(F.runs, ddecl, (int64_t)dup.size());
+        PCHK(hipGetLastError());
+    }
+    const RowSrc rs{F.row_pos, dhpos, F.row_kmer, dhkmer, F.row_feat, dhfeat, NROW};
+    uint32_t *run_tx;
+    int64_t *run_rank, *elig, NE = 0;
+    if ((rc = m.alloc(run_tx, (size_t)NR + 1, "runs")) || (rc = m.alloc(run_rank, (size_t)NR + 1, "runs")) || (rc = m.alloc(elig, (size_t)NR + 1, "runs")))
+        return rc;
+    if (NR) {
+        run_select_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, seg, dup_seg, lim, run_tx, run_rank, elig);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, elig, NR, s, NE))) return rc;
+    uint64_t *k1, *k2;
+    uint32_t *E, *E2;
+    if ((rc = m.alloc(k1, (size_t)NE + 1, "runs")) || (rc = m.alloc(k2, (size_t)NE + 1, "runs")) || (rc = m.alloc(E, (size_t)NE + 1, "runs")) ||
+        (rc = m.alloc(E2, (size_t)NE + 1, "runs")))
+        return rc;
+    unsigned long long *mm, hmm[2] = {kNone, 0};
+    if ((rc = m.alloc(mm, 2, "flags"))) return rc;
+    if (NR) {
+        compact_u32_kernel<<<grid(NR), kBlk, 0, s>>>(elig, NR, E);
+        PCHK(hipGetLastError());
+    }
+    if (NE) {
+        PCHK(hipMemcpyAsync(mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
+        minmax_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, 0, F.runs, rs, mm);
+        PCHK(hipGetLastError());
+        if ((rc = d2h(hmm, mm, 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        const int rb = bits_for(hmm[1] - hmm[0]), tb = bits_for((uint64_t)std::max<int64_t>(NT - 1, 0));
+        // (transcript, read) in one key when it fits, else the read first and the transcript after it (LSD, stable)
+        const unsigned both = (rb ? 1u : 0u) | (tb ? 2u : 0u);
+        const unsigned passes[2] = {rb + tb <= 64 ? both : 1u, rb + tb <= 64 ? 0u : 2u};
+        for (unsigned use : passes) {
+            if (!use) continue;
+            const int bits = (use & 1 ? rb : 0) + (use & 2 ? tb : 0);
+            run_key_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, F.runs, run_tx, hmm[0], use & 1 ? rb : 0, use, k1);
+            PCHK(hipGetLastError());
+            if ((rc = radix_sort(m, k1, E, k2, E2, NE, bits, s))) return rc;
+        }
+    }
+    uint8_t *used;
+    int64_t *run_place, *gx, *gfirst, NG = 0;
+    if ((rc = m.alloc(used, (size_t)NR + 1, "runs")) || (rc = m.alloc(run_place, (size_t)NR + 1, "runs")) || (rc = m.alloc(gx, (size_t)NE + 2, "runs")))
+        return rc;
+    PCHK(hipMemsetAsync(used, 0, (size_t)NR + 1, s));
+    if (NE) {
+        dup_head_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, F.runs, run_tx, gx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, gx, NE, s, NG))) return rc;
+    if ((rc = m.alloc(gfirst, (size_t)NG + 1, "runs"))) return rc;
+    if (NE) {
+        dup_first_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, gx, run_rank, gfirst);
+        PCHK(hipGetLastError());
+        dup_last_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, gx, gfirst, used, run_place);
+        PCHK(hipGetLastError());
+    }
+    PCHK(hipStreamSynchronize(s));
+    for (const void *p : {(const void *)k1, (const void *)k2, (const void *)E, (const void *)E2, (const void *)gx, (const void *)gfirst,
+                          (const void *)elig, (const void *)sx, (const void *)dx})
+        m.release(p);
+
+    // ---- rows of the used runs, sorted by (transcript, position, place)
+    int64_t *rx, NL0 = 0, *hx, NLH = 0;
+    if ((rc = m.alloc(rx, (size_t)NR + 1, "rows")) || (rc = m.alloc(hx, (size_t)NH + 1, "rows"))) return rc;
+    if (NR) {
+        used_rows_count_kernel<<<grid(NR), kBlk, 0, s>>>(used, F.row_off, NR, rx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, rx, NR, s, NL0))) return rc;
+    if (NH) {
+        host_flag_kernel<<<grid(NH), kBlk, 0, s>>>(used, dhrun, NH, hx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, hx, NH, s, NLH))) return rc;
+    const int64_t NL = NL0 + NLH;
+    uint32_t *L, *L2, *row_run;
+    if ((rc = m.alloc(L, (size_t)NL + 1, "rows")) || (rc = m.alloc(L2, (size_t)NL + 1, "rows")) || (rc = m.alloc(row_run, (size_t)(NROW + NH) + 1, "rows")) ||
+        (rc = m.alloc(k1, (size_t)NL + 1, "rows")) || (rc = m.alloc(k2, (size_t)NL + 1, "rows")))
+        return rc;
+    if (NR) {
+        used_rows_write_kernel<<<grid(NR), kBlk, 0, s>>>(used, F.row_off, NR, rx, L, row_run);
+        PCHK(hipGetLastError());
+    }
+    if (NH) {
+        host_rows_kernel<<<grid(NH), kBlk, 0, s>>>(dhrun, NH, NROW, NL0, hx, L, row_run);
+        PCHK(hipGetLastError());
+    }
+    if (NL) {
+        PCHK(hipMemcpyAsync(mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
+        minmax_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, 1, F.runs, rs, mm);
+        PCHK(hipGetLastError());
+        if ((rc = d2h(hmm, mm, 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        RowKey key{hmm[0], 0, 0, 0, 0};
+        const int fb[3] = {bits_for((uint64_t)lim), bits_for(hmm[1] - hmm[0]), bits_for((uint64_t)std::max<int64_t>(NT - 1, 0))};
+        const unsigned fu[3] = {4, 2, 1};                  // place, position, transcript: least significant first
+        int at = 0;
+        for (int f = 0; f <= 3; f++) {
+            if (f == 3 || (fb[f] && at + fb[f] > 64)) {   // sort by what is packed so far
+                if (key.use) {
+                    row_key_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, rs, row_run, run_tx, run_place, key, k1);
+                    PCHK(hipGetLastError());
+                    if ((rc = radix_sort(m, k1, L, k2, L2, NL, at, s))) return rc;
+                }
+                key.use = 0;
+                at = 0;
+            }
+            if (f == 3 || !fb[f]) continue;
+            if (f == 0) key.sh_place = at;
+            if (f == 1) key.sh_pos = at;
+            if (f == 2) key.sh_tx = at;
+            key.use |= fu[f];
+            at += fb[f];
+        }
+    }
+
+    // ---- sites: cut, checked, filtered
+    int64_t *shx, NS0 = 0;
+    if ((rc = m.alloc(shx, (size_t)NL + 1, "sites"))) return rc;
+    if (NL) {
+        site_head_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, rs, row_run, run_tx, shx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, shx, NL, s, NS0))) return rc;
+    int64_t *start, *kx, NS = 0;
+    unsigned long long *bad, hbad = kNone;
+    if ((rc = m.alloc(start, (size_t)NS0 + 1, "sites")) || (rc = m.alloc(kx, (size_t)NS0 + 1, "sites")) || (rc = m.alloc(bad, 1, "flags"))) return rc;
+    PCHK(hipMemcpyAsync(bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
+    if (NL) {
+        site_start_kernel<<<grid(NL), kBlk, 0, s>>>(shx, NL, start);
+        PCHK(hipGetLastError());
+        site_check_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, rs, shx, start, bad);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = d2h(&hbad, bad, 1, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    if (hbad != ~0ull) {
+        int64_t *probe, hp[2] = {0, 0};
+        if ((rc = m.alloc(probe, 2, "flags"))) return rc;
+        probe_kernel<<<1, 1, 0, s>>>(L, start, (int64_t)hbad, rs, row_run, run_tx, probe);
+        PCHK(hipGetLastError());
+        if ((rc = d2h(hp, probe, 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        const int64_t t = hp[0];
+        return prep_fail(M6A_EFORMAT, "reads disagree on the sequence at %.*s:%lld", (int)(P.tx_off[t + 1] - P.tx_off[t]), P.blob.data() + P.tx_off[t],
+                         (long long)hp[1]);
+    }
+    if (NS0) {
+        site_keep_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, std::max<int64_t>(min_seg, 20), kx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, kx, NS0, s, NS))) return rc;
+    int64_t *src, *doff;
+    if ((rc = m.alloc(src, (size_t)NS + 1, "sites")) || (rc = m.alloc(doff, (size_t)NS + 1, "the offsets"))) return rc;
+    PCHK(hipMemsetAsync(doff + NS, 0, sizeof(int64_t), s));
+    if (NS0) {
+        site_emit_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, kx, src, doff);
+        PCHK(hipGetLastError());
+    }
+    int64_t R = 0;
+    if ((rc = scan_total(m, doff, NS, s, R))) return rc;
+
+    // ---- normalisation, vocabulary, X
+    std::vector<uint64_t> nk, voc = vocab_keys();
+    std::vector<std::pair<uint64_t, int32_t>> norm;
+    for (int i = 0; i < n_norm; i++) {
+        uint64_t x = 0;
+        for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)norm_kmers[5 * i + j];
+        norm.emplace_back(x, i);
+    }
+    std::sort(norm.begin(), norm.end());                   // a repeated 5-mer: the loader's map keeps the first
+    std::vector<int32_t> nix;
+    for (size_t i = 0; i < norm.size(); i++)
+        if (i == 0 || norm[i].first != norm[i - 1].first) { nk.push_back(norm[i].first); nix.push_back(norm[i].second); }
+    uint64_t *dnk, *dvoc;
+    int32_t *dnix, *site_norm;
+    double *dmean, *dstd;
+    uint32_t *site_tx;
+    int64_t *site_pos;
+    uint8_t *site_k7, *site_kmers;
+    if ((rc = m.alloc(dnk, nk.size() + 1, "norm")) || (rc = m.alloc(dnix, nix.size() + 1, "norm")) || (rc = m.alloc(dvoc, voc.size(), "norm")) ||
+        (rc = m.alloc(dmean, (size_t)n_norm * 3 + 1, "norm")) || (rc = m.alloc(dstd, (size_t)n_norm * 3 + 1, "norm")) ||
+        (rc = m.alloc(site_norm, (size_t)NS * 3 + 1, "sites")) || (rc = m.alloc(site_tx, (size_t)NS + 1, "sites")) ||
+        (rc = m.alloc(site_pos, (size_t)NS + 1, "sites")) || (rc = m.alloc(site_k7, (size_t)NS * 7 + 1, "sites")) ||
+        (rc = m.alloc(site_kmers, (size_t)NS * 3 + 1, "site k-mers")))
+        return rc;
+    if ((rc = h2d(dnk, nk.data(), nk.size(), s)) || (rc = h2d(dnix, nix.data(), nix.size(), s)) || (rc = h2d(dvoc, voc.data(), voc.size(), s)) ||
+        (rc = h2d(dmean, norm_mean, (size_t)n_norm * 3, s)) || (rc = h2d(dstd, norm_std, (size_t)n_norm * 3, s)))
+        return rc;
+    PCHK(hipMemcpyAsync(bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
+    if (NS) {
+        site_info_kernel<<<grid(NS), kBlk, 0, s>>>(L, src, NS, rs, row_run, run_tx, dnk, dnix, (int)nk.size(), dvoc, (int)voc.size(), site_norm,
+                                                   site_kmers, site_tx, site_pos, site_k7, bad);
+        PCHK(hipGetLastError());
+    }
+    P.off.resize((size_t)NS + 1);
+    P.tx.resize((size_t)NS);
+    P.pos.resize((size_t)NS);
+    P.k7.resize((size_t)NS * 7);
+    unsigned long long hb2 = kNone;
+    if ((rc = d2h(&hb2, bad, 1, s)) || (rc = d2h(P.off.data(), doff, (size_t)NS + 1, s)) || (rc = d2h(P.tx.data(), site_tx, (size_t)NS, s)) ||
+        (rc = d2h(P.pos.data(), site_pos, (size_t)NS, s)) || (rc = d2h((uint8_t *)P.k7.data(), site_k7, (size_t)NS * 7, s)))
+        return rc;
+    PCHK(hipStreamSynchronize(s));
+    if (hb2 != ~0ull) {
+        const int64_t bs = (int64_t)(hb2 >> 3), what = (int64_t)(hb2 & 7);
+        const char *k = P.k7.data() + bs * 7;
+        if (what < 3) return prep_fail(M6A_EFORMAT, "no normalisation factors for %.5s", k + what);
+        const uint32_t t = P.tx[(size_t)bs];
+        return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", (int)(P.tx_off[t + 1] - P.tx_off[t]), P.blob.data() + P.tx_off[t],
+                         (long long)P.pos[(size_t)bs], k);
+    }
+    float *X;
+    double *dids;
+    if ((rc = m.alloc(X, (size_t)R * 9, "X")) || (rc = m.alloc(dids, (size_t)R + 1, "read ids"))) return rc;
+    if (R) {
+        x_kernel<<<grid(R), kBlk, 0, s>>>(L, src, doff, NS, R, rs, row_run, F.runs, site_norm, dmean, dstd, n_norm, X, dids);
+        PCHK(hipGetLastError());
+    }
+    P.ids.resize((size_t)R);
+    PCHK(hipStreamSynchronize(s));
+    dev_ms += now_ms() - t1;
+    t1 = now_ms();
+    if ((rc = d2h(P.ids.data(), dids, (size_t)R, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    ms[5] = now_ms() - t1;
+    float *rp, *sp;
+    double *mr;
+    if ((rc = m.alloc(rp, (size_t)R, "read probabilities")) || (rc = m.alloc(sp, (size_t)NS, "site probabilities")) ||
+        (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
+        return rc;
+    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr}) {
+        m.detach(p);
+        P.dev.push_back((void *)p);
+    }
+    m6a_prep_sites_info &I = P.info;
+    I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
+    I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
+    I.off_host = P.off.data(); I.site_tx = P.tx.data(); I.site_pos = P.pos.data(); I.site_kmer7 = P.k7.data();
+    I.tx_blob = P.blob.data(); I.tx_off = P.tx_off.data(); I.read_ids = P.ids.data();
+    ms[3] = dev_ms; ms[4] = host_ms; ms[7] = now_ms() - t_all;
+    I.d2h_bytes = g_d2h;
+    return M6A_OK;
+}
+
+}  // namespace
+
 extern "C" int m6a_prep_eventalign(int device_id, const char *path, int n_neighbors, const char *index_path, m6a_prep **out)
 {
     if (!path || !out) return prep_fail(M6A_EINVAL, "null argument");
@@ -851,3 +1702,57 @@ extern "C" int m6a_prep_times(const m6a_prep *p, double *ms6)
 }
 extern "C" void m6a_prep_free(m6a_prep *p) { delete p; }
 extern "C" const char *m6a_prep_last_error(void) { return g_prep_err.c_str(); }
+
+extern "C" int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
+                                    const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                                    const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out)
+{
+    if (!path || !out) return prep_fail(M6A_EINVAL, "null argument");
+    *out = nullptr;
+    m6a_prep_sites *p = new (std::nothrow) m6a_prep_sites;
+    if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
+    p->device = device_id;
+    int rc;
+    try {
+        rc = sites_impl(device_id, path, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm, host,
+                        n_threads, *p);
+    } catch (const std::bad_alloc &) {
+        rc = prep_fail(M6A_ENOMEM, "out of host memory");
+    } catch (...) {
+        rc = prep_fail(M6A_EIO, "unexpected exception");
+    }
+    if (rc) { delete p; return rc; }
+    *out = p;
+    return M6A_OK;
+}
+
+extern "C" const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p) { return p ? &p->info : nullptr; }
+
+extern "C" int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio)
+{
+    if (!p) return prep_fail(M6A_EINVAL, "null argument");
+    const int64_t R = p->info.n_reads, S = p->info.n_sites;
+    if ((R && !read_prob) || (S && (!site_prob || !mod_ratio))) return prep_fail(M6A_EINVAL, "null argument");
+    const double t = now_ms();
+    PCHK(hipSetDevice(p->device));
+    if (R) PCHK(hipMemcpy(read_prob, p->info.read_prob, (size_t)R * sizeof(float), hipMemcpyDeviceToHost));
+    if (S) PCHK(hipMemcpy(site_prob, p->info.site_prob, (size_t)S * sizeof(float), hipMemcpyDeviceToHost));
+    if (S) PCHK(hipMemcpy(mod_ratio, p->info.mod_ratio, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    p->info.d2h_bytes += R * (int64_t)sizeof(float) + S * (int64_t)(sizeof(float) + sizeof(double));
+    p->info.ms[5] += now_ms() - t;
+    return M6A_OK;
+}
+
+extern "C" int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_kmers, int64_t *off)
+{
+    if (!p || !X || !site_kmers || !off) return prep_fail(M6A_EINVAL, "null argument");
+    const int64_t R = p->info.n_reads, S = p->info.n_sites;
+    PCHK(hipSetDevice(p->device));
+    if (R) PCHK(hipMemcpy(X, p->info.X, (size_t)R * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    if (S) PCHK(hipMemcpy(site_kmers, p->info.site_kmers, (size_t)S * 3, hipMemcpyDeviceToHost));
+    PCHK(hipMemcpy(off, p->info.off, (size_t)(S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    p->info.d2h_bytes += R * 36 + S * 3 + (S + 1) * 8;
+    return M6A_OK;
+}
+
+extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }

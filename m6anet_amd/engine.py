@@ -332,11 +332,18 @@ class M6ANetEngine:
             mod = self._out(aX.is_dev, S, np.float64, "float64")
         aP = _Arg(rp, np.float32, "float32") if rp is not None else None
         aS, aM = _Arg(site, np.float32, "float32"), _Arg(mod, np.float64, "float64")
-        self._chk(self._L.m6a_infer(self._h, aX.ptr, aK.ptr, aO.ptr, S, int(n_iters), int(n_samples),
-                                    float(np.float32(read_proba_threshold)), int(seed) & 0xffffffff,
-                                    _lib.RNG_NUMPY, int(batch_size), int(save_per_batch),
-                                    aP.ptr if aP else None, aS.ptr, aM.ptr))
+        self.infer_ptrs(aX.ptr, aK.ptr, aO.ptr, S, n_iters, n_samples, read_proba_threshold, seed, batch_size, save_per_batch,
+                        aP.ptr if aP else None, aS.ptr, aM.ptr)
         return rp, site, mod
+
+    def infer_ptrs(self, X, site_kmers, off, n_sites, n_iters, n_samples=N_SAMPLES, read_proba_threshold=DEFAULT_READ_THRESHOLD,
+                   seed=0, batch_size=16, save_per_batch=2, read_prob=None, site_prob=None, mod_ratio=None):
+        """m6a_infer on raw addresses (ints) the caller owns -- e.g. the device arrays of m6a_prep_sites_build: all host or all
+        device, as include/m6a.h says.  With device pointers the call is queued on the context's stream: `sync()` before the
+        outputs are read; `set_host_offsets` first spares the read-back of off."""
+        self._chk(self._L.m6a_infer(self._h, X, site_kmers, off, int(n_sites), int(n_iters), int(n_samples),
+                                    float(np.float32(read_proba_threshold)), int(seed) & 0xffffffff,
+                                    _lib.RNG_NUMPY, int(batch_size), int(save_per_batch), read_prob, site_prob, mod_ratio))
 
     # -- the same job, streamed: run_inference's batch loop (inference_utils.py:33-54) feeds as the loader produces --------
     def job_begin(self, n_iters, n_samples=N_SAMPLES, read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16,

@@ -1,0 +1,88 @@
+"""`eventalign_inference` sub-command: eventalign.txt -> data.site_proba.csv / data.indiv_proba.csv in one process, byte-identical
+to `dataprep --device cpu` followed by `inference` with the same flags.  The file is parsed, combined and windowed in HBM
+(m6a_prep_sites_build, include/m6a.h), the sites' features go from there to X without leaving the device, and only ids and
+probabilities come back to the host; no data.json is written or parsed."""
+import os
+import pathlib
+import time
+from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
+
+from . import dataprep, inference
+
+# the flags of `dataprep` that shape the sites, and every flag of `inference` but its input and --gpus (same defaults and meaning)
+DATAPREP_FLAGS = ("--readcount_min", "--readcount_max", "--min_segment_count", "--n_processes")
+INFERENCE_FLAGS = ("--pretrained_model", "--model_config", "--model_state_dict", "--norm_path", "--batch_size", "--save_per_batch",
+                   "--num_iterations", "--device", "--seed", "--read_proba_threshold", "--encoder", "--drop_unflushed_tail")
+
+
+def _copy(src, dst, flags):
+    for a in src._actions:
+        if any(o in flags for o in a.option_strings):
+            dst._add_action(a)
+
+
+def argparser():
+    parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter, add_help=False)
+    parser.add_argument("--eventalign", required=True, help="eventalign filepath, the output from nanopolish.")
+    parser.add_argument("--out_dir", required=True, help="directory to output inference results.")
+    _copy(dataprep.argparser(), parser, DATAPREP_FLAGS)
+    _copy(inference.argparser(), parser, INFERENCE_FLAGS)
+    return parser
+
+
+def main(args):
+    import threading
+
+    from .. import _io
+    from ..constants import DEFAULT_MIN_READS, N_SAMPLES
+    from ..data_utils import load_norm_factors
+    from ..engine import reference_written_sites
+
+    weights = inference.resolve_model(args)
+    device = inference._device_index(args.device)
+    made = {}
+
+    def make_engine():                       # the GPU context comes up while the file is parsed
+        try:
+            made["engine"] = inference.make_engine_for(args, weights, device)
+        except BaseException as exc:        # re-raised on the main thread below
+            made["error"] = exc
+
+    starter = threading.Thread(target=make_engine)
+    starter.start()
+    try:
+        sites = _io.prep_sites(args.eventalign, args.readcount_min, args.readcount_max, args.min_segment_count,
+                               load_norm_factors(args.norm_path), args.n_processes, device)
+    finally:
+        starter.join()
+    if "error" in made:
+        sites.close()
+        raise made["error"]
+    engine = made["engine"]
+    try:
+        pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
+        writer = sites.writer()
+        if sites.n_sites == 0:               # what `inference` leaves behind: the two header lines, then the loader's error
+            writer.write_csv(args.out_dir, [], [], [], write_header=True, n_threads=args.n_processes)
+            raise _io.M6AIOError("m6a_io error -4: no site with at least %d reads" % DEFAULT_MIN_READS, -4)
+        i = sites.info
+        t0 = time.perf_counter()
+        engine.set_host_offsets(sites.off)   # the kernels are chosen from this copy: nothing is read back
+        engine.infer_ptrs(i.X, i.site_kmers, i.off, sites.n_sites, args.num_iterations, N_SAMPLES, args.read_proba_threshold, args.seed,
+                          args.batch_size, args.save_per_batch, i.read_prob, i.site_prob, i.mod_ratio)
+        engine.sync()
+        t1 = time.perf_counter()
+        read_prob, site_prob, mod_ratio = sites.fetch()
+        t2 = time.perf_counter()
+        n_write = None
+        if args.drop_unflushed_tail:         # the reference's row set (inference_utils.py:47)
+            n_write = reference_written_sites(sites.n_sites, args.batch_size, args.save_per_batch)
+        writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes, n_sites=n_write)
+        if os.environ.get("M6A_EVENTALIGN_TIMES"):      # phases for tools/measure_eventalign_inference.py
+            import json
+            ms, d2h = sites.times()
+            ms.update(infer=(t1 - t0) * 1e3, fetch=(t2 - t1) * 1e3, csv_write=(time.perf_counter() - t2) * 1e3)
+            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads}), flush=True)
+    finally:
+        sites.close()
+        engine.close()

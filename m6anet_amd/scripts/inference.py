@@ -97,7 +97,8 @@ def _check_model_config(path):
         raise ValueError("--model_config %s is not the m6anet.toml topology (blocks %s): not supported" % (path, got))
 
 
-def main(args):
+def resolve_model(args):
+    """The weights of this run; a pretrained model also sets args.read_proba_threshold and args.norm_path (the reference's rule)."""
     if not 0 <= int(args.seed) <= 0xffffffff:
         raise ValueError("Seed must be between 0 and 2**32 - 1")        # what np.random.seed raises
     if args.model_config is not None:
@@ -120,7 +121,11 @@ def main(args):
         weights = load_weights(args.pretrained_model)
         args.read_proba_threshold = PRETRAINED_CONFIGS[args.pretrained_model][1]
         args.norm_path = PRETRAINED_CONFIGS[args.pretrained_model][2]
+    return weights
 
+
+def main(args):
+    weights = resolve_model(args)
     if args.gpus < 1:
         raise ValueError("--gpus must be >= 1")
     if "M6A_RANK" in os.environ:                         # one rank of a --gpus N job (started by multi_gpu.launch)

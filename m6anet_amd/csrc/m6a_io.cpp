@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <charconv>
 #include <chrono>
+#include <climits>
 #include <clocale>
 #include <cstdlib>
 #include <locale.h>
@@ -1186,6 +1187,7 @@ inline int scan_line(const char *p, const char *e, const char *safe, const char 
             return n;
         }
         while (mt) { if (n < 16) fe[n++] = q + __builtin_ctz(mt); mt &= mt - 1; }
+        if (q + 16 > e) { q = e; break; }                  // no newline before the run's end (an index row that ends mid-line): le = e
         q += 16;
     }
 #else
@@ -1210,16 +1212,18 @@ bool combine_read(const char *p, const char *e, const char *safe, std::vector<Po
     static thread_local std::vector<Ev> evs;
     static thread_local std::vector<uint32_t> order;
     evs.clear();
-    // position, start_idx, end_idx are integers in every eventalign.txt (pandas reads them as int64): plain digits
-    // take the integer path, anything else (a sign, a dot, an exponent) the general number parser
+    // position, start_idx, end_idx are integers in every eventalign.txt (pandas reads them as int64): plain digits up to
+    // INT64_MAX take the integer path (19 digits included: through a double they would lose their last digits), anything else
+    // (a sign, a dot, an exponent) the general number parser
     auto int_field = [](const char *p, const char *e, long long &out) {
-        if (p >= e || e - p > 18) return false;
-        long long v = 0;
+        if (p >= e || e - p > 19) return false;
+        unsigned long long v = 0;                          // 19 digits stay below 10^19 < 2^64
         for (const char *q = p; q < e; ++q) {
             if (*q < '0' || *q > '9') return false;
-            v = v * 10 + (*q - '0');
+            v = v * 10 + (unsigned long long)(*q - '0');
         }
-        out = v;
+        if (v > (unsigned long long)LLONG_MAX) return false;   // past int64: the general parser, as before
+        out = (long long)v;
         return true;
     };
     auto any_field = [&](const char *p, const char *e, long long &out) {

@@ -1,8 +1,13 @@
 // m6a_prep.hip -- `dataprep --device gpu` (include/m6a.h: m6a_prep_eventalign): eventalign.txt -> the table of runs and candidate
 // rows that m6a_io_dataprep_write (include/m6a_io.h) turns into the four files.  The device restates, line for line, what the
-// host's index_range, combine_read and window_rows (m6a_io.cpp) do; whatever its fast paths decline (a number with a sign or
-// an exponent, more than 15 / 18 digits, a short or empty line inside a run, events out of (position, k-mer) order, a model
-// k-mer that is not 5 characters) marks the run M6A_PREP_RUN_HOST and the host combines it.
+// host's index_range, combine_read and window_rows (m6a_io.cpp) do; whatever its fast paths decline marks the run
+// M6A_PREP_RUN_HOST and the host combines it.  A run is declined exactly when (tests/eventalign_statement.py: declines)
+//   - one of its lines has no tab (an empty line, too) or fewer than 15 fields, or its contig name is longer than an int32 holds;
+//   - on a line whose reference_kmer equals model_kmer: a float field that is not digits [. digits] with 1..15 digit characters
+//     (a sign, an exponent, a name, 16 digits), position / start_idx / end_idx that is not 1..18 plain digits, or a k-mer that
+//     is not 5 characters -- the fields of lines whose k-mers differ are never read, so nothing in them declines a run;
+//   - two such lines follow each other out of (position, k-mer) order;
+//   - with --skip_index, its byte range is not whole body lines.
 //
 //   upload      the file streams into HBM through two pinned staging buffers (pread into one while the other is copied);
 //               nl_count_kernel counts the newlines of every 4 KB block of chunk k while chunk k + 1 is in flight

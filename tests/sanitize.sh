@@ -19,7 +19,8 @@ gcc $SAN -Wall -Iinclude tools/feed_probe.c -ldl -o $B/feed_probe || exit 1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -fPIC -shared -fsanitize=address,undefined -fno-gpu-sanitize -fno-omit-frame-pointer \
     -shared-libsan -DM6A_MT_JUMP_PATH="\"$PWD/m6anet_amd/assets/mt19937_jump.bin\"" -Iinclude -Im6anet_amd/csrc \
     m6anet_amd/csrc/m6a_kernels.hip m6anet_amd/csrc/m6a_pool_reg.hip m6anet_amd/csrc/m6a_pool_rtab.hip m6anet_amd/csrc/m6a_api.hip \
-    m6anet_amd/csrc/m6a_host_ring.hip m6anet_amd/csrc/m6a_job.hip m6anet_amd/csrc/m6a_comm.hip m6anet_amd/csrc/m6a_validate.hip -o $B/libm6a_hip.so
+    m6anet_amd/csrc/m6a_host_ring.hip m6anet_amd/csrc/m6a_job.hip m6anet_amd/csrc/m6a_comm.hip m6anet_amd/csrc/m6a_validate.hip m6anet_amd/csrc/m6a_prep.hip \
+    -o $B/libm6a_hip.so
 HIP_SAN=$?
 set +x
 echo "libm6a_hip.so host-side sanitizer build: rc=$HIP_SAN"

@@ -357,7 +357,21 @@ const char *m6a_prep_last_error(void);
  * job over the device budget is M6A_ENOMEM and its text names the two-step path.  ms: [0] upload, [1] newline offsets, [2] lines,
  * runs, combine and windows, [3] back half on the device (its small copies of segments and per-site arrays included), [4] host
  * (names, declined runs), [5] the copy of the read ids (m6a_prep_sites_fetch adds the time of its own copies), [6] the upload's GB/s,
- * [7] the whole call. */
+ * [7] the whole call.
+ *
+ * m6a_prep_sites_build_multi: several files are replicates, pooled as m6a_io_load_sites pools several input directories, and the
+ * arrays equal the loader's on `dataprep` of every file (same readcount_min / readcount_max / min_segment_count) -- X bit for bit.
+ * Every file goes through both halves on its own, without the 20-read floor and without the per-site checks; its text, line records
+ * and candidate rows are released before the next file is uploaded, and what stays is X and the read id of the reads of its sites
+ * with >= min_segment_count reads.  Sites are keyed by (transcript name, position); the pooled sites are the union in order of first
+ * appearance (file 0's in file 0's order, then what file 1 adds, ...), a site's reads are its parts in file order, and it is kept
+ * when the SUM of its reads is >= 20.  Kept sites only are checked, lowest first: the normalisation factors of the first part's
+ * 7-mer, then every later part's 7-mer against it ("replicates disagree on the sequence of <tx>:<pos>"), then the vocabulary.
+ * read_rep [R] is the position of each read's file in `paths` (a file without sites still takes its number), filled on the host from
+ * the 4 n_paths bytes per kept site that come back; nothing comes back per dropped site, and per read only its id.  tx_blob /
+ * tx_off name the transcripts of all files in order of first appearance.  ms sums the files' phases; the union and the pooled copy
+ * are counted in [3].  m6a_prep_sites_build is the n_paths = 1 case (n_rep = 1, read_rep all 0).  peak_bytes is the high-water mark
+ * of the call's device allocations, the handle's own arrays included. */
 typedef struct m6a_prep_sites m6a_prep_sites;
 struct m6a_io_rows;
 typedef struct m6a_prep_host_half {
@@ -383,10 +397,16 @@ typedef struct m6a_prep_sites_info {
     const double *read_ids;         /* [R] */
     double ms[8];
     int64_t d2h_bytes;
+    int n_rep;                      /* files pooled */
+    const int32_t *read_rep;        /* [R] replicate of each read */
+    int64_t peak_bytes;
 } m6a_prep_sites_info;
 int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
                          const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
                          const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out);
+int m6a_prep_sites_build_multi(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
+                               int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                               const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out);
 const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p);     /* owned by p */
 int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio);
 /* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */

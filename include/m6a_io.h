@@ -53,6 +53,12 @@ const char *m6a_io_kmer5(const m6a_sites *s, int64_t site);    /* centre 5-mer, 
  * shard writers print the rows m6a_io_load_sites' sites would print; m6a_io_save_store refuses them (M6A_IO_EINVAL: no features). */
 int m6a_io_sites_from_arrays(int64_t n_sites, const int64_t *off, const int64_t *tx_pos, const char *tx_blob, const int64_t *tx_off,
                              int64_t n_tx, const uint32_t *site_tx, const char *kmer5, const double *read_ids, m6a_sites **out);
+/* The same for n_rep pooled replicates (m6a_prep_sites_build_multi): read_rep [R] is each read's replicate, 0 <= read_rep[r] < n_rep.
+ * With n_rep > 1 the writers print read ids as `<id>_<replicate>`, as for sites loaded from several input directories; m6a_io_read_rep
+ * returns the copy; X and the k-mer ids are still absent and m6a_io_save_store still refuses. */
+int m6a_io_sites_from_arrays_rep(int64_t n_sites, const int64_t *off, const int64_t *tx_pos, const char *tx_blob, const int64_t *tx_off,
+                                 int64_t n_tx, const uint32_t *site_tx, const char *kmer5, const double *read_ids, const int32_t *read_rep,
+                                 int n_rep, m6a_sites **out);
 
 /* Binary site store: everything m6a_io_load_sites produces -- normalised features,
  * k-mer ids, CSR offsets, ids -- in one file, so a dataset is parsed from data.json ONCE and every later run maps it

@@ -10,7 +10,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays"]
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep"]
 _lib = None
 
 
@@ -91,6 +91,7 @@ def load():
     L.m6a_io_dataprep_write.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PrepTable), i32, i32, i32, i32, i32, i32]
     L.m6a_io_runs_rows.argtypes = [C.c_char_p, i64, vp, vp, vp, i32, i32, C.POINTER(vp)]
     L.m6a_io_sites_from_arrays.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, C.POINTER(vp)]
+    L.m6a_io_sites_from_arrays_rep.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, vp, i32, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -194,8 +195,9 @@ def norm_arrays(norm):
 
 class prep_sites:
     """m6a_prep_sites_build (libm6a_hip.so): eventalign.txt -> the loader's arrays with X, site_kmers and off left on the device.
-    `info` is the m6a_prep_sites_info; host copies are numpy arrays (off, site_tx, tx_pos, kmer7, read_ids) and `names` (per
-    transcript).  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
+    `eventalign` is one path, or a list of paths that are replicates (m6a_prep_sites_build_multi: pooled on the device as the loader
+    pools several input directories; a list of one is a list -- `<id>_0`).  `info` is the m6a_prep_sites_info; host copies are numpy
+    arrays (off, site_tx, tx_pos, kmer7, read_ids, read_rep) and `names` (per transcript); n_replicates and peak_bytes as reported.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
     _CODES = prep_on_device._CODES
 
     def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0):
@@ -205,9 +207,13 @@ class prep_sites:
         blob, mean, std, n = norm_arrays(norm)
         host = _lib.HostHalf(C.cast(io.m6a_io_runs_rows, C.c_void_p), C.cast(io.m6a_io_rows_table, C.c_void_p),
                              C.cast(io.m6a_io_rows_free, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
-        rc = L.m6a_prep_sites_build(int(device_id), os.fsencode(eventalign), int(readcount_min), int(readcount_max), int(min_segment_count),
-                                    blob, None if mean is None else mean.ctypes.data, None if std is None else std.ctypes.data, n,
-                                    C.byref(host), int(n_threads), C.byref(self._h))
+        tail = (int(readcount_min), int(readcount_max), int(min_segment_count), blob, None if mean is None else mean.ctypes.data,
+                None if std is None else std.ctypes.data, n, C.byref(host), int(n_threads), C.byref(self._h))
+        if isinstance(eventalign, (str, bytes, os.PathLike)):
+            rc = L.m6a_prep_sites_build(int(device_id), os.fsencode(eventalign), *tail)
+        else:
+            paths = [os.fsencode(e) for e in eventalign]
+            rc = L.m6a_prep_sites_build_multi(int(device_id), (C.c_char_p * len(paths))(*paths), len(paths), *tail)
         if rc != 0:
             raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
         i = self.info = L.m6a_prep_sites_get(self._h).contents
@@ -221,6 +227,8 @@ class prep_sites:
         self.tx_pos = arr(i.site_pos, C.c_int64, S)
         self.kmer7 = arr(i.site_kmer7, C.c_uint8, 7 * S).reshape(S, 7)
         self.read_ids = arr(i.read_ids, C.c_double, R)
+        self.read_rep = arr(i.read_rep, C.c_int32, R)
+        self.n_replicates, self.peak_bytes = int(i.n_rep), int(i.peak_bytes)
         tx_off = arr(i.tx_off, C.c_int64, T + 1)
         self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
         self.tx_off = tx_off
@@ -254,7 +262,8 @@ class prep_sites:
     def writer(self):
         """The sites as an m6a_sites for the CSV writers (NativeSites.from_arrays)."""
         k5 = np.ascontiguousarray(self.kmer7[:, 1:6])
-        return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids)
+        rep = (self.read_rep, self.n_replicates) if self.n_replicates > 1 else (None, 1)
+        return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids, *rep)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -292,9 +301,13 @@ class NativeSites:
         L = load()
         h = C.c_void_p()
         if _arrays is not None:
-            off, tx_pos, blob, tx_off, site_tx, k5, ids = _arrays
-            _chk(L.m6a_io_sites_from_arrays(len(tx_pos), off.ctypes.data, tx_pos.ctypes.data, blob, tx_off.ctypes.data, len(tx_off) - 1,
-                                            site_tx.ctypes.data, k5.tobytes(), ids.ctypes.data, C.byref(h)))
+            off, tx_pos, blob, tx_off, site_tx, k5, ids, rep, n_rep = _arrays
+            head = (len(tx_pos), off.ctypes.data, tx_pos.ctypes.data, blob, tx_off.ctypes.data, len(tx_off) - 1, site_tx.ctypes.data,
+                    k5.tobytes(), ids.ctypes.data)
+            if rep is None:
+                _chk(L.m6a_io_sites_from_arrays(*head, C.byref(h)))
+            else:
+                _chk(L.m6a_io_sites_from_arrays_rep(*head, rep.ctypes.data, int(n_rep), C.byref(h)))
         elif store is not None:
             _chk(L.m6a_io_open_store(os.fsencode(store), C.byref(h)))
         else:
@@ -325,15 +338,17 @@ class NativeSites:
         self.off = view(L.m6a_io_off, C.c_int64, (S + 1,))
         self.tx_pos = view(L.m6a_io_tx_pos, C.c_int64, (S,))
         self.read_id_values = view(L.m6a_io_read_ids, C.c_double, (R,))
-        self.read_rep = view(L.m6a_io_read_rep, C.c_int32, (R,)) if _arrays is None else None
+        self.read_rep = view(L.m6a_io_read_rep, C.c_int32, (R,)) if _arrays is None or _arrays[7] is not None else None
 
     @classmethod
-    def from_arrays(cls, off, tx_pos, tx_blob, tx_off, site_tx, kmer5, read_ids):
+    def from_arrays(cls, off, tx_pos, tx_blob, tx_off, site_tx, kmer5, read_ids, read_rep=None, n_rep=1):
         """m6a_io_sites_from_arrays: sites without X for the writers.  tx_blob / tx_off: the transcript names; site_tx [S] indexes them;
-        kmer5 [S][5] uint8 (or bytes-like rows); read_ids [R] float64."""
+        kmer5 [S][5] uint8 (or bytes-like rows); read_ids [R] float64.  read_rep [R] int32 with n_rep: pooled replicates
+        (m6a_io_sites_from_arrays_rep), read ids printed `<id>_<replicate>` when n_rep > 1."""
         k5 = np.ascontiguousarray(np.frombuffer(b"".join(kmer5), np.uint8) if isinstance(kmer5, (list, tuple)) else kmer5, np.uint8)
         arrays = (np.ascontiguousarray(off, np.int64), np.ascontiguousarray(tx_pos, np.int64), bytes(tx_blob), np.ascontiguousarray(tx_off, np.int64),
-                  np.ascontiguousarray(site_tx, np.uint32), k5, np.ascontiguousarray(read_ids, np.float64))
+                  np.ascontiguousarray(site_tx, np.uint32), k5, np.ascontiguousarray(read_ids, np.float64),
+                  None if read_rep is None else np.ascontiguousarray(read_rep, np.int32), n_rep)
         return cls(_arrays=arrays)
 
     def tx_id(self, i):

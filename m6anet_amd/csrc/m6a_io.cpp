@@ -751,6 +751,37 @@ int m6a_io_sites_from_arrays(int64_t n_sites, const int64_t *off, const int64_t 
     }
 }
 
+int m6a_io_sites_from_arrays_rep(int64_t n_sites, const int64_t *off, const int64_t *tx_pos, const char *tx_blob, const int64_t *tx_off, int64_t n_tx,
+                                 const uint32_t *site_tx, const char *kmer5, const double *read_ids, const int32_t *read_rep, int n_rep,
+                                 m6a_sites **out)
+{
+    if (!out) return M6A_IO_EINVAL;
+    *out = nullptr;
+    if (n_rep < 1) return fail(M6A_IO_EINVAL, "n_rep must be at least 1");
+    m6a_sites *s = nullptr;
+    const int rc = m6a_io_sites_from_arrays(n_sites, off, tx_pos, tx_blob, tx_off, n_tx, site_tx, kmer5, read_ids, &s);
+    if (rc) return rc;
+    const int64_t R = s->nR;
+    if (R && !read_rep) { delete s; return fail(M6A_IO_EINVAL, "null argument"); }
+    for (int64_t r = 0; r < R; r++)
+        if (read_rep[r] < 0 || read_rep[r] >= n_rep) {
+            const int32_t v = read_rep[r];
+            delete s;
+            return fail(M6A_IO_EINVAL, "read %lld: replicate %d of %d", (long long)r, (int)v, n_rep);
+        }
+    try {
+        s->read_rep.resize((size_t)R);
+    } catch (const std::bad_alloc &) {
+        delete s;
+        return fail(M6A_IO_ENOMEM, "out of memory for %lld reads", (long long)R);
+    }
+    std::copy(read_rep, read_rep + R, s->read_rep.data());
+    s->n_rep = n_rep;
+    s->vRep = s->read_rep.data();
+    *out = s;
+    return M6A_IO_OK;
+}
+
 int m6a_io_format_f16(double v, char *buf336) { const int k = format_f16(v, buf336); buf336[k] = 0; return k; }
 
 int m6a_io_write_csv(const m6a_sites *s, const char *out_dir, const float *read_prob, const float *site_prob,

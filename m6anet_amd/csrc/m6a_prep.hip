@@ -480,7 +480,8 @@ namespace {
 // device memory of one call, every allocation counted against the budget (free memory minus a margin, or M6A_PREP_BUDGET_MB)
 struct DevMem {
     std::vector<std::pair<void *, size_t>> ptrs;
-    size_t used = 0, budget = 0;
+    size_t used = 0, budget = 0, peak = 0;
+    bool budget_set = false;                     // the first file of a job sets it; what stays of earlier files counts against it
     const char *advice = "use --device cpu";     // what the budget error tells the user to do instead
     ~DevMem() { for (auto &p : ptrs) (void)hipFree(p.first); }
     template <class T> int alloc(T *&p, size_t count, const char *what)
@@ -493,8 +494,20 @@ struct DevMem {
         if (hipMalloc(&q, bytes) != hipSuccess) return prep_fail(M6A_ENOMEM, "hipMalloc of %zu MB failed (%s); %s", bytes >> 20, what, advice);
         ptrs.emplace_back(q, bytes);
         used += bytes;
+        peak = std::max(peak, used);
         p = (T *)q;
         return M6A_OK;
+    }
+    // hipFree everything allocated from entry `mark` of ptrs on, but `keep`
+    void release_since(size_t mark, std::initializer_list<const void *> keep)
+    {
+        std::vector<std::pair<void *, size_t>> left(ptrs.begin(), ptrs.begin() + (ptrdiff_t)std::min(mark, ptrs.size()));
+        for (size_t i = mark; i < ptrs.size(); i++) {
+            if (std::find(keep.begin(), keep.end(), (const void *)ptrs[i].first) != keep.end()) { left.push_back(ptrs[i]); continue; }
+            (void)hipFree(ptrs[i].first);
+            used -= ptrs[i].second;
+        }
+        ptrs.swap(left);
     }
     // hipFree now (release) or never (detach: the caller owns it from here on)
     void drop(const void *p, bool free_it)
@@ -618,7 +631,8 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     if (fstat(fd.fd, &st) != 0) return prep_fail(M6A_EIO, "cannot stat %s", path);
     const int64_t n = (int64_t)st.st_size;
     F.n = n;
-    {
+    if (!m.budget_set) {
+        m.budget_set = true;
         size_t fr = 0, tot = 0;
         PCHK(hipMemGetInfo(&fr, &tot));
         const size_t margin = std::min<size_t>(fr / 16, (size_t)4 << 30);
@@ -1167,28 +1181,32 @@ __device__ inline int find5(const uint64_t *keys, int n, uint64_t v)
 }
 
 // per kept site: transcript, position, 7-mer; the norm rows and the vocabulary ids of its three 5-mers (m6a_io_load_sites' order
-// of checks: the normalisation factors of the three 5-mers, then the vocabulary); bad = 8 site + what
+// of checks: the normalisation factors of the three 5-mers, then the vocabulary); bad = 8 site + what.  Pooling replicates
+// (tx_map: this file's transcript ids -> the job's; defer): nothing is an error yet -- a site may still be dropped by the pooled
+// filter -- so a 5-mer without factors takes row 0 (pool_site_kernel refuses the site before its X is read) and no vocabulary id is made
 __global__ void site_info_kernel(const uint32_t *__restrict__ L, const int64_t *__restrict__ src, int64_t S, RowSrc rs,
                                  const uint32_t *__restrict__ row_run, const uint32_t *__restrict__ run_tx, const uint64_t *__restrict__ nkeys,
                                  const int32_t *__restrict__ nix, int n_norm, const uint64_t *__restrict__ vocab, int n_vocab,
                                  int32_t *__restrict__ site_norm,
                                  uint8_t *__restrict__ site_kmers, uint32_t *__restrict__ site_tx, int64_t *__restrict__ site_pos,
-                                 uint8_t *__restrict__ site_k7, unsigned long long *__restrict__ bad)
+                                 uint8_t *__restrict__ site_k7, unsigned long long *__restrict__ bad, const uint32_t *__restrict__ tx_map, int defer)
 {
     const int64_t s = (int64_t)blockIdx.x * kBlk + threadIdx.x;
     if (s >= S) return;
     const uint32_t k = L[src[s]];
     const uint8_t *km = rs.kmer(k);
-    site_tx[s] = run_tx[row_run[k]];
+    site_tx[s] = tx_map ? tx_map[run_tx[row_run[k]]] : run_tx[row_run[k]];
     site_pos[s] = rs.pos(k);
     for (int c = 0; c < 7; c++) site_k7[s * 7 + c] = km[c];
     for (int c = 0; c < 3; c++) {
         site_norm[s * 3 + c] = 0;
         if (!n_norm) continue;
         const int j = find5(nkeys, n_norm, pack5(km + c));
+        if (j < 0 && defer) continue;
         if (j < 0) { atomicMin(bad, (unsigned long long)(s * 8 + c)); return; }
         site_norm[s * 3 + c] = nix[j];
     }
+    if (defer) return;
     for (int c = 0; c < 3; c++) {
         const int v = find5(vocab, n_vocab, pack5(km + c));
         if (v < 0) { atomicMin(bad, (unsigned long long)(s * 8 + 3 + c)); return; }
@@ -1281,6 +1299,29 @@ std::vector<uint64_t> vocab_keys()
 
 }  // namespace
 
+struct m6a_prep_sites;
+
+namespace {
+
+// what stays of one replicate until the replicates are pooled: its sites with >= min_segment_count reads (transcript ids are the
+// job's), and X and the read id of their reads in site order -- 44 B per read, 31 B per site
+struct FilePart {
+    int64_t NC = 0, RC = 0;
+    float *X = nullptr;            // [RC][9]
+    double *ids = nullptr;         // [RC]
+    uint32_t *tx = nullptr;        // [NC]
+    int64_t *pos = nullptr, *off = nullptr;   // [NC], [NC + 1]
+    uint8_t *k7 = nullptr;         // [NC][7]
+};
+
+struct Pool {
+    std::unordered_map<std::string, uint32_t> ids;         // transcript names of all files, in order of first appearance
+    std::vector<FilePart> parts;
+    uint32_t global_tx(const std::string &nm, m6a_prep_sites &P);
+};
+
+}  // namespace
+
 struct m6a_prep_sites {
     m6a_prep_sites_info info{};
     int device = 0;
@@ -1290,20 +1331,38 @@ struct m6a_prep_sites {
     std::vector<char> k7;
     std::string blob;
     std::vector<double> ids;
+    std::vector<int32_t> rep;                // [R] replicate of each read (several files)
     ~m6a_prep_sites() { for (void *p : dev) (void)hipFree(p); }
 };
 
 namespace {
 
-int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
-               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites &P)
+uint32_t Pool::global_tx(const std::string &nm, m6a_prep_sites &P)
 {
-    if (n_norm < 0 || (n_norm > 0 && (!norm_kmers || !norm_mean || !norm_std))) return prep_fail(M6A_EINVAL, "bad normalisation arguments");
+    auto it = ids.find(nm);
+    if (it != ids.end()) return it->second;
+    const uint32_t t = (uint32_t)ids.size();
+    ids.emplace(nm, t);
+    P.tx_off.push_back((int64_t)P.blob.size());
+    P.blob += nm;
+    return t;
+}
+
+// One file.  pool == nullptr: the whole job (m6a_prep_sites_build), P filled.  Else the file is one replicate of several: its sites
+// with >= min_seg reads (the 20-read floor and the per-site checks wait for the pooled sites, pool_impl), their X and read ids stay
+// on the device as a FilePart, and everything else the file needed -- its text, line records, candidate rows -- is released.
+int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
+               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites &P, DevMem &m, double *ms,
+               Pool *pool)
+{
     const double t_all = now_ms();
-    g_d2h = 0;
-    double *ms = P.info.ms, fms[6] = {0, 0, 0, 0, 0, 0};
-    DevMem m;
-    m.advice = "run `dataprep` and then `inference` instead (the two-step path)";
+    double fms[6] = {0, 0, 0, 0, 0, 0};
+    const size_t mark = m.ptrs.size();
+    std::string own_blob;                                   // pooled: this file's names, for its own error texts; P's are the job's
+    std::vector<int64_t> own_tx_off;
+    std::string &blob = pool ? own_blob : P.blob;
+    std::vector<int64_t> &tx_off = pool ? own_tx_off : P.tx_off;
+    std::vector<uint32_t> l2g;                              // this file's transcript ids -> the job's
     Streams S;
     Fd fd;
     Front F;
@@ -1359,16 +1418,17 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         else {
             t = (uint32_t)ids.size();
             ids.emplace(nm, t);
-            P.tx_off.push_back((int64_t)P.blob.size());
-            P.blob += nm;
+            tx_off.push_back((int64_t)blob.size());
+            blob += nm;
             tx_runs.push_back(0);
+            if (pool) l2g.push_back(pool->global_tx(nm, P));
         }
         const int64_t len = (g + 1 < NSEG ? hseg[(size_t)g + 1].first : NR) - G.first;
         up[(size_t)g].rank0 = tx_runs[t];
         up[(size_t)g].tx = t;
         tx_runs[t] += len;
     }
-    P.tx_off.push_back((int64_t)P.blob.size());
+    tx_off.push_back((int64_t)blob.size());
     const int64_t lim = std::max(0, rmax);                  // `if ++readcount > readcount_max: break` after the first run
     for (SegUp &u : up) u.keep = std::min(tx_runs[u.tx], lim + 1) >= rmin;
     // declined runs the host loop reaches: combined and windowed by the host half
@@ -1398,7 +1458,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
             if (T->run_status[i] != M6A_PREP_RUN_OK) {
                 const int64_t g = (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), crun[i], [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
                 const uint32_t t = up[(size_t)g].tx;
-                return prep_fail(M6A_EFORMAT, "malformed eventalign line for %.*s", (int)(P.tx_off[t + 1] - P.tx_off[t]), P.blob.data() + P.tx_off[t]);
+                return prep_fail(M6A_EFORMAT, "malformed eventalign line for %.*s", (int)(tx_off[t + 1] - tx_off[t]), blob.data() + tx_off[t]);
             }
             dup.push_back(DeclUp{crun[i], T->run_npos[i]});
             for (int64_t k = T->row_off[i]; k < T->row_off[i + 1]; k++) {
@@ -1576,11 +1636,11 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         if ((rc = d2h(hp, probe, 2, s))) return rc;
         PCHK(hipStreamSynchronize(s));
         const int64_t t = hp[0];
-        return prep_fail(M6A_EFORMAT, "reads disagree on the sequence at %.*s:%lld", (int)(P.tx_off[t + 1] - P.tx_off[t]), P.blob.data() + P.tx_off[t],
+        return prep_fail(M6A_EFORMAT, "reads disagree on the sequence at %.*s:%lld", (int)(tx_off[t + 1] - tx_off[t]), blob.data() + tx_off[t],
                          (long long)hp[1]);
     }
     if (NS0) {
-        site_keep_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, std::max<int64_t>(min_seg, 20), kx);
+        site_keep_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, pool ? (int64_t)min_seg : std::max<int64_t>(min_seg, 20), kx);
         PCHK(hipGetLastError());
     }
     if ((rc = scan_total(m, kx, NS0, s, NS))) return rc;
@@ -1618,14 +1678,32 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         (rc = m.alloc(site_pos, (size_t)NS + 1, "sites")) || (rc = m.alloc(site_k7, (size_t)NS * 7 + 1, "sites")) ||
         (rc = m.alloc(site_kmers, (size_t)NS * 3 + 1, "site k-mers")))
         return rc;
+    uint32_t *dl2g = nullptr;
+    if (pool && ((rc = m.alloc(dl2g, l2g.size() + 1, "transcripts")) || (rc = h2d(dl2g, l2g.data(), l2g.size(), s)))) return rc;
     if ((rc = h2d(dnk, nk.data(), nk.size(), s)) || (rc = h2d(dnix, nix.data(), nix.size(), s)) || (rc = h2d(dvoc, voc.data(), voc.size(), s)) ||
         (rc = h2d(dmean, norm_mean, (size_t)n_norm * 3, s)) || (rc = h2d(dstd, norm_std, (size_t)n_norm * 3, s)))
         return rc;
     PCHK(hipMemcpyAsync(bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
     if (NS) {
         site_info_kernel<<<grid(NS), kBlk, 0, s>>>(L, src, NS, rs, row_run, run_tx, dnk, dnix, (int)nk.size(), dvoc, (int)voc.size(), site_norm,
-                                                   site_kmers, site_tx, site_pos, site_k7, bad);
+                                                   site_kmers, site_tx, site_pos, site_k7, bad, dl2g, pool ? 1 : 0);
         PCHK(hipGetLastError());
+    }
+    if (pool) {                                             // one replicate of several: X per candidate read, and what pool_impl needs of the sites
+        if (R > 0x7fffffffll) return prep_fail(M6A_EINVAL, "more than 2^31 candidate reads in %s", path);
+        FilePart fp;
+        if ((rc = m.alloc(fp.X, (size_t)R * 9, "X")) || (rc = m.alloc(fp.ids, (size_t)R + 1, "read ids"))) return rc;
+        if (R) {
+            x_kernel<<<grid(R), kBlk, 0, s>>>(L, src, doff, NS, R, rs, row_run, F.runs, site_norm, dmean, dstd, n_norm, fp.X, fp.ids);
+            PCHK(hipGetLastError());
+        }
+        PCHK(hipStreamSynchronize(s));
+        fp.NC = NS; fp.RC = R; fp.tx = site_tx; fp.pos = site_pos; fp.k7 = site_k7; fp.off = doff;
+        m.release_since(mark, {fp.X, fp.ids, fp.tx, fp.pos, fp.k7, fp.off});
+        pool->parts.push_back(fp);
+        dev_ms += now_ms() - t1;
+        ms[3] = dev_ms; ms[4] = host_ms; ms[5] = 0; ms[7] = now_ms() - t_all;
+        return M6A_OK;
     }
     P.off.resize((size_t)NS + 1);
     P.tx.resize((size_t)NS);
@@ -1641,7 +1719,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         const char *k = P.k7.data() + bs * 7;
         if (what < 3) return prep_fail(M6A_EFORMAT, "no normalisation factors for %.5s", k + what);
         const uint32_t t = P.tx[(size_t)bs];
-        return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", (int)(P.tx_off[t + 1] - P.tx_off[t]), P.blob.data() + P.tx_off[t],
+        return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", (int)(tx_off[t + 1] - tx_off[t]), blob.data() + tx_off[t],
                          (long long)P.pos[(size_t)bs], k);
     }
     float *X;
@@ -1671,9 +1749,385 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
     I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
     I.off_host = P.off.data(); I.site_tx = P.tx.data(); I.site_pos = P.pos.data(); I.site_kmer7 = P.k7.data();
-    I.tx_blob = P.blob.data(); I.tx_off = P.tx_off.data(); I.read_ids = P.ids.data();
+    I.tx_blob = blob.data(); I.tx_off = tx_off.data(); I.read_ids = P.ids.data();
+    P.rep.assign((size_t)R, 0);
+    I.n_rep = 1; I.read_rep = P.rep.data();
     ms[3] = dev_ms; ms[4] = host_ms; ms[7] = now_ms() - t_all;
-    I.d2h_bytes = g_d2h;
+    return M6A_OK;
+}
+
+
+// ---- replicates (m6a_prep_sites_build_multi): the union of the files' sites, formed where the features are ------------------------
+// Every file leaves a FilePart.  Their sites, numbered file after file ("candidates"), are keyed by (transcript, position):
+//   groups     one stable sort of the candidate numbers by the key: a group = the parts of one pooled site, in file order
+//   order      a group's first member is where the site first appears; an exclusive scan of those flags over the candidates, in
+//              their own order, numbers the pooled sites -- file 0's sites in file 0's order, then what file 1 adds, ...
+//   filter     reads summed over the parts; kept with >= 20; scan -> off; per (kept site, file) the block of rows it supplies
+//   checks     kept sites only, lowest first (atomicMin): the first part's normalisation factors, later parts' 7-mers against the
+//              first, the vocabulary -- m6a_io_load_sites' order
+//   copy       a wave per (kept site, file): the block's 9 n dwords of X and n read ids, lane after lane
+constexpr int64_t kMinReads = 20;          // DEFAULT_MIN_READS: the loader's floor on the pooled count
+
+__global__ void cand_fill_kernel(const int64_t *__restrict__ off, int64_t n, int64_t base, int32_t file, int64_t *__restrict__ c_src,
+                                 int32_t *__restrict__ c_cnt, int32_t *__restrict__ c_file, uint32_t *__restrict__ val)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    c_src[base + i] = off[i];
+    c_cnt[base + i] = (int32_t)(off[i + 1] - off[i]);
+    c_file[base + i] = file;
+    val[base + i] = (uint32_t)(base + i);
+}
+
+__global__ void cand_minmax_kernel(const int64_t *__restrict__ pos, int64_t n, unsigned long long *__restrict__ mm)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    unsigned long long lo = ~0ull, hi = 0;
+    if (i < n) lo = hi = bias(pos[i]);
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    if ((threadIdx.x & 63) == 0 && lo <= hi) { atomicMin(&mm[0], lo); atomicMax(&mm[1], hi); }
+}
+
+// use: 1 = the position part, 2 = the transcript part (shifted by tx_shift)
+__global__ void cand_key_kernel(const uint32_t *__restrict__ val, int64_t n, const uint32_t *__restrict__ c_tx, const int64_t *__restrict__ c_pos,
+                                uint64_t pos_min, int tx_shift, unsigned use, uint64_t *__restrict__ key)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = val[j];
+    uint64_t v = 0;
+    if (use & 1) v |= bias(c_pos[i]) - pos_min;
+    if (use & 2) v |= (uint64_t)c_tx[i] << tx_shift;
+    key[j] = v;
+}
+
+__global__ void cand_head_kernel(const uint32_t *__restrict__ val, int64_t n, const uint32_t *__restrict__ c_tx, const int64_t *__restrict__ c_pos,
+                                 int64_t *__restrict__ head)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (j >= n) return;
+    head[j] = j == 0 || c_tx[val[j]] != c_tx[val[j - 1]] || c_pos[val[j]] != c_pos[val[j - 1]];
+}
+
+__global__ void group_first_kernel(const uint32_t *__restrict__ val, const int64_t *__restrict__ gstart, int64_t NG, int64_t *__restrict__ first)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (g < NG) first[val[gstart[g]]] = 1;
+}
+
+// per group: its pooled number u (before the filter), its reads summed, kept or not
+__global__ void group_sum_kernel(const uint32_t *__restrict__ val, const int64_t *__restrict__ gstart, int64_t NG, const int32_t *__restrict__ c_cnt,
+                                 const int64_t *__restrict__ ux, int64_t *__restrict__ usum, int64_t *__restrict__ ugrp, int64_t *__restrict__ keep)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (g >= NG) return;
+    int64_t sum = 0;
+    for (int64_t j = gstart[g]; j < gstart[g + 1]; j++) sum += c_cnt[val[j]];
+    const int64_t u = ux[val[gstart[g]]];
+    usum[u] = sum;
+    ugrp[u] = g;
+    keep[u] = sum >= kMinReads;
+}
+
+__global__ void pool_emit_kernel(const int64_t *__restrict__ kx, int64_t NG, const int64_t *__restrict__ usum, const int64_t *__restrict__ ugrp,
+                                 int64_t *__restrict__ off, int64_t *__restrict__ kgrp)
+{
+    const int64_t u = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (u >= NG || kx[u + 1] == kx[u]) return;
+    off[kx[u]] = usum[u];
+    kgrp[kx[u]] = ugrp[u];
+}
+
+// per kept site: transcript, position and 7-mer of its first part; per part the block it supplies (blk_* [S][K], by file; a file
+// holds a (transcript, position) once, so a group has at most one member per file); then the checks; bad = 8 site + what
+// (0..2 a 5-mer without normalisation factors, 3 a later part's 7-mer differs, 4..6 a 5-mer outside the vocabulary)
+__global__ void pool_site_kernel(const uint32_t *__restrict__ val, const int64_t *__restrict__ gstart, const int64_t *__restrict__ kgrp, int64_t S, int K,
+                                 const int64_t *__restrict__ off, const uint32_t *__restrict__ c_tx, const int64_t *__restrict__ c_pos,
+                                 const uint8_t *__restrict__ c_k7, const int64_t *__restrict__ c_src, const int32_t *__restrict__ c_cnt,
+                                 const int32_t *__restrict__ c_file, const uint64_t *__restrict__ nkeys, int n_norm, const uint64_t *__restrict__ vocab,
+                                 int n_vocab, uint32_t *__restrict__ site_tx, int64_t *__restrict__ site_pos, uint8_t *__restrict__ site_k7,
+                                 uint8_t *__restrict__ site_kmers, int64_t *__restrict__ blk_src, int64_t *__restrict__ blk_dst,
+                                 int32_t *__restrict__ blk_cnt, unsigned long long *__restrict__ bad)
+{
+    const int64_t s = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (s >= S) return;
+    const int64_t g = kgrp[s], j0 = gstart[g], j1 = gstart[g + 1];
+    const uint32_t i0 = val[j0];
+    const uint8_t *km = c_k7 + (int64_t)i0 * 7;
+    site_tx[s] = c_tx[i0];
+    site_pos[s] = c_pos[i0];
+    for (int c = 0; c < 7; c++) site_k7[s * 7 + c] = km[c];
+    int64_t row = off[s];
+    bool differ = false;
+    for (int64_t j = j0; j < j1; j++) {
+        const uint32_t i = val[j];
+        const int64_t b = s * K + c_file[i];
+        blk_src[b] = c_src[i];
+        blk_dst[b] = row;
+        blk_cnt[b] = c_cnt[i];
+        row += c_cnt[i];
+        for (int c = 0; c < 7; c++) differ |= c_k7[(int64_t)i * 7 + c] != km[c];
+    }
+    for (int c = 0; c < 3 && n_norm; c++)
+        if (find5(nkeys, n_norm, pack5(km + c)) < 0) { atomicMin(bad, (unsigned long long)(s * 8 + c)); return; }
+    if (differ) { atomicMin(bad, (unsigned long long)(s * 8 + 3)); return; }
+    for (int c = 0; c < 3; c++) {
+        const int v = find5(vocab, n_vocab, pack5(km + c));
+        if (v < 0) { atomicMin(bad, (unsigned long long)(s * 8 + 4 + c)); return; }
+        site_kmers[s * 3 + c] = (uint8_t)v;
+    }
+}
+
+// a wave per (kept site, file): its block of n rows is 36 n bytes of X and 8 n of read ids, contiguous on both sides and 4-byte
+// aligned (rows are 36 B), so consecutive lanes move consecutive dwords; an empty block ends at once
+__global__ void pool_copy_kernel(int64_t n_blocks, int K, const int64_t *__restrict__ blk_src, const int64_t *__restrict__ blk_dst,
+                                 const int32_t *__restrict__ blk_cnt, const float *const *__restrict__ Xs, const double *const *__restrict__ ids_s,
+                                 float *__restrict__ X, double *__restrict__ ids)
+{
+    const int64_t b = (int64_t)blockIdx.x * (kBlk / 64) + (threadIdx.x >> 6);
+    if (b >= n_blocks) return;
+    const int64_t n = blk_cnt[b];
+    if (n == 0) return;
+    const int f = (int)(b % K), lane = threadIdx.x & 63;
+    const uint32_t *src = (const uint32_t *)Xs[f] + blk_src[b] * 9;
+    uint32_t *dst = (uint32_t *)X + blk_dst[b] * 9;
+    for (int64_t d = lane; d < n * 9; d += 64) dst[d] = src[d];
+    const double *isrc = ids_s[f] + blk_src[b];
+    double *idst = ids + blk_dst[b];
+    for (int64_t d = lane; d < n; d += 64) idst[d] = isrc[d];
+}
+
+int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_prep_sites &P, double *ms)
+{
+    double t1 = now_ms();
+    Streams S;
+    PCHK(hipStreamCreateWithFlags(&S.s[0], hipStreamNonBlocking));
+    hipStream_t s = S.s[0];
+    const int K = (int)pool.parts.size();
+    int64_t NC = 0;
+    for (const FilePart &fp : pool.parts) NC += fp.NC;
+    if (NC > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate sites");
+    const int64_t NT = (int64_t)pool.ids.size();
+    P.tx_off.push_back((int64_t)P.blob.size());
+    int rc;
+
+    // ---- the candidates of all files, file after file
+    uint32_t *c_tx, *val, *val2;
+    int64_t *c_pos, *c_src;
+    int32_t *c_cnt, *c_file;
+    uint8_t *c_k7;
+    uint64_t *k1, *k2;
+    if ((rc = m.alloc(c_tx, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(c_pos, (size_t)NC + 1, "pooled sites")) ||
+        (rc = m.alloc(c_src, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(c_cnt, (size_t)NC + 1, "pooled sites")) ||
+        (rc = m.alloc(c_file, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(c_k7, (size_t)NC * 7 + 1, "pooled sites")) ||
+        (rc = m.alloc(val, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(val2, (size_t)NC + 1, "pooled sites")) ||
+        (rc = m.alloc(k1, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(k2, (size_t)NC + 1, "pooled sites")))
+        return rc;
+    int64_t base = 0;
+    for (int f = 0; f < K; f++) {
+        const FilePart &fp = pool.parts[(size_t)f];
+        if (!fp.NC) continue;
+        PCHK(hipMemcpyAsync(c_tx + base, fp.tx, (size_t)fp.NC * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        PCHK(hipMemcpyAsync(c_pos + base, fp.pos, (size_t)fp.NC * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        PCHK(hipMemcpyAsync(c_k7 + base * 7, fp.k7, (size_t)fp.NC * 7, hipMemcpyDeviceToDevice, s));
+        cand_fill_kernel<<<grid(fp.NC), kBlk, 0, s>>>(fp.off, fp.NC, base, f, c_src, c_cnt, c_file, val);
+        PCHK(hipGetLastError());
+        base += fp.NC;
+    }
+    PCHK(hipStreamSynchronize(s));
+    for (FilePart &fp : pool.parts) {
+        for (const void *p : {(const void *)fp.tx, (const void *)fp.pos, (const void *)fp.k7, (const void *)fp.off}) m.release(p);
+        fp.tx = nullptr; fp.pos = fp.off = nullptr; fp.k7 = nullptr;
+    }
+
+    // ---- groups: the candidates sorted by (transcript, position), stable, so that a group's members are in file order
+    unsigned long long *mm, hmm[2] = {kNone, 0};
+    if ((rc = m.alloc(mm, 2, "flags"))) return rc;
+    if (NC) {
+        PCHK(hipMemcpyAsync(mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
+        cand_minmax_kernel<<<grid(NC), kBlk, 0, s>>>(c_pos, NC, mm);
+        PCHK(hipGetLastError());
+        if ((rc = d2h(hmm, mm, 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        const int pb = bits_for(hmm[1] - hmm[0]), tb = bits_for((uint64_t)std::max<int64_t>(NT - 1, 0));
+        // (transcript, position) in one key when it fits, else the position first and the transcript after it (LSD, stable)
+        const unsigned both = (pb ? 1u : 0u) | (tb ? 2u : 0u);
+        const unsigned passes[2] = {pb + tb <= 64 ? both : 1u, pb + tb <= 64 ? 0u : 2u};
+        for (unsigned use : passes) {
+            if (!use) continue;
+            const int bits = (use & 1 ? pb : 0) + (use & 2 ? tb : 0);
+            cand_key_kernel<<<grid(NC), kBlk, 0, s>>>(val, NC, c_tx, c_pos, hmm[0], use & 1 ? pb : 0, use, k1);
+            PCHK(hipGetLastError());
+            if ((rc = radix_sort(m, k1, val, k2, val2, NC, bits, s))) return rc;
+        }
+    }
+    int64_t *gx, *gstart, *ux, NG = 0, NU = 0;
+    if ((rc = m.alloc(gx, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(ux, (size_t)NC + 1, "pooled sites"))) return rc;
+    if (NC) {
+        cand_head_kernel<<<grid(NC), kBlk, 0, s>>>(val, NC, c_tx, c_pos, gx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, gx, NC, s, NG))) return rc;
+    if ((rc = m.alloc(gstart, (size_t)NG + 1, "pooled sites"))) return rc;
+    PCHK(hipMemsetAsync(ux, 0, (size_t)(NC + 1) * sizeof(int64_t), s));
+    if (NC) {
+        site_start_kernel<<<grid(NC), kBlk, 0, s>>>(gx, NC, gstart);
+        PCHK(hipGetLastError());
+        group_first_kernel<<<grid(NG), kBlk, 0, s>>>(val, gstart, NG, ux);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, ux, NC, s, NU))) return rc;
+    if (NU != NG) return prep_fail(M6A_EINVAL, "pooled sites: %lld groups, %lld first members", (long long)NG, (long long)NU);
+
+    // ---- the pooled filter and the offsets
+    int64_t *usum, *ugrp, *kx, *kgrp, *doff, NS = 0, R = 0;
+    if ((rc = m.alloc(usum, (size_t)NG + 1, "pooled sites")) || (rc = m.alloc(ugrp, (size_t)NG + 1, "pooled sites")) ||
+        (rc = m.alloc(kx, (size_t)NG + 1, "pooled sites")))
+        return rc;
+    if (NG) {
+        group_sum_kernel<<<grid(NG), kBlk, 0, s>>>(val, gstart, NG, c_cnt, ux, usum, ugrp, kx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, kx, NG, s, NS))) return rc;
+    if ((rc = m.alloc(kgrp, (size_t)NS + 1, "pooled sites")) || (rc = m.alloc(doff, (size_t)NS + 1, "the offsets"))) return rc;
+    if (NG) {
+        pool_emit_kernel<<<grid(NG), kBlk, 0, s>>>(kx, NG, usum, ugrp, doff, kgrp);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, doff, NS, s, R))) return rc;
+
+    // ---- per kept site: its arrays, its blocks, its checks
+    std::vector<uint64_t> nk, voc = vocab_keys();
+    for (int i = 0; i < n_norm; i++) {
+        uint64_t x = 0;
+        for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)norm_kmers[5 * i + j];
+        nk.push_back(x);
+    }
+    std::sort(nk.begin(), nk.end());
+    nk.erase(std::unique(nk.begin(), nk.end()), nk.end());
+    uint64_t *dnk, *dvoc;
+    uint32_t *site_tx;
+    int64_t *site_pos, *blk_src, *blk_dst;
+    int32_t *blk_cnt;
+    uint8_t *site_k7, *site_kmers;
+    unsigned long long *bad, hbad = kNone;
+    const size_t NB = (size_t)NS * (size_t)K;
+    if ((rc = m.alloc(dnk, nk.size() + 1, "norm")) || (rc = m.alloc(dvoc, voc.size(), "norm")) || (rc = m.alloc(site_tx, (size_t)NS + 1, "sites")) ||
+        (rc = m.alloc(site_pos, (size_t)NS + 1, "sites")) || (rc = m.alloc(site_k7, (size_t)NS * 7 + 1, "sites")) ||
+        (rc = m.alloc(site_kmers, (size_t)NS * 3 + 1, "site k-mers")) || (rc = m.alloc(blk_src, NB + 1, "blocks")) ||
+        (rc = m.alloc(blk_dst, NB + 1, "blocks")) || (rc = m.alloc(blk_cnt, NB + 1, "blocks")) || (rc = m.alloc(bad, 1, "flags")))
+        return rc;
+    if ((rc = h2d(dnk, nk.data(), nk.size(), s)) || (rc = h2d(dvoc, voc.data(), voc.size(), s))) return rc;
+    PCHK(hipMemcpyAsync(bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
+    PCHK(hipMemsetAsync(blk_cnt, 0, (NB + 1) * sizeof(int32_t), s));
+    PCHK(hipMemsetAsync(blk_src, 0, (NB + 1) * sizeof(int64_t), s));
+    PCHK(hipMemsetAsync(blk_dst, 0, (NB + 1) * sizeof(int64_t), s));
+    if (NS) {
+        pool_site_kernel<<<grid(NS), kBlk, 0, s>>>(val, gstart, kgrp, NS, K, doff, c_tx, c_pos, c_k7, c_src, c_cnt, c_file, dnk, (int)nk.size(), dvoc,
+                                                   (int)voc.size(), site_tx, site_pos, site_k7, site_kmers, blk_src, blk_dst, blk_cnt, bad);
+        PCHK(hipGetLastError());
+    }
+    P.off.resize((size_t)NS + 1);
+    P.tx.resize((size_t)NS);
+    P.pos.resize((size_t)NS);
+    P.k7.resize((size_t)NS * 7);
+    std::vector<int32_t> cnt(NB);
+    if ((rc = d2h(&hbad, bad, 1, s)) || (rc = d2h(P.off.data(), doff, (size_t)NS + 1, s)) || (rc = d2h(P.tx.data(), site_tx, (size_t)NS, s)) ||
+        (rc = d2h(P.pos.data(), site_pos, (size_t)NS, s)) || (rc = d2h((uint8_t *)P.k7.data(), site_k7, (size_t)NS * 7, s)) ||
+        (rc = d2h(cnt.data(), blk_cnt, NB, s)))
+        return rc;
+    PCHK(hipStreamSynchronize(s));
+    if (hbad != ~0ull) {
+        const int64_t bs = (int64_t)(hbad >> 3), what = (int64_t)(hbad & 7);
+        const char *k = P.k7.data() + bs * 7;
+        if (what < 3) return prep_fail(M6A_EFORMAT, "no normalisation factors for %.5s", k + what);
+        const uint32_t t = P.tx[(size_t)bs];
+        const int len = (int)(P.tx_off[t + 1] - P.tx_off[t]);
+        if (what == 3)
+            return prep_fail(M6A_EFORMAT, "replicates disagree on the sequence of %.*s:%lld", len, P.blob.data() + P.tx_off[t], (long long)P.pos[(size_t)bs]);
+        return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", len, P.blob.data() + P.tx_off[t], (long long)P.pos[(size_t)bs], k);
+    }
+
+    // ---- the pooled X and read ids
+    float *X;
+    double *dids;
+    const float **dXs;
+    const double **dis;
+    if ((rc = m.alloc(X, (size_t)R * 9, "X")) || (rc = m.alloc(dids, (size_t)R + 1, "read ids")) || (rc = m.alloc(dXs, (size_t)K, "blocks")) ||
+        (rc = m.alloc(dis, (size_t)K, "blocks")))
+        return rc;
+    std::vector<const float *> hXs;
+    std::vector<const double *> his;
+    for (const FilePart &fp : pool.parts) { hXs.push_back(fp.X); his.push_back(fp.ids); }
+    if ((rc = h2d(dXs, hXs.data(), hXs.size(), s)) || (rc = h2d(dis, his.data(), his.size(), s))) return rc;
+    if (NB && R) {
+        const int64_t nblk = ((int64_t)NB + kBlk / 64 - 1) / (kBlk / 64);
+        if (nblk > 0x7fffffffll) return prep_fail(M6A_EINVAL, "more than 2^33 (site, replicate) blocks");
+        pool_copy_kernel<<<(unsigned)nblk, kBlk, 0, s>>>((int64_t)NB, K, blk_src, blk_dst, blk_cnt, dXs, dis, X, dids);
+        PCHK(hipGetLastError());
+    }
+    P.rep.resize((size_t)R);
+    for (int64_t i = 0, r = 0; i < NS; i++)
+        for (int f = 0; f < K; f++)
+            for (int32_t k = 0; k < cnt[(size_t)(i * K + f)]; k++) P.rep[(size_t)r++] = f;
+    P.ids.resize((size_t)R);
+    PCHK(hipStreamSynchronize(s));
+    ms[3] += now_ms() - t1;
+    t1 = now_ms();
+    if ((rc = d2h(P.ids.data(), dids, (size_t)R, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    ms[5] += now_ms() - t1;
+    float *rp, *sp;
+    double *mr;
+    if ((rc = m.alloc(rp, (size_t)R, "read probabilities")) || (rc = m.alloc(sp, (size_t)NS, "site probabilities")) ||
+        (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
+        return rc;
+    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr}) {
+        m.detach(p);
+        P.dev.push_back((void *)p);
+    }
+    m6a_prep_sites_info &I = P.info;
+    I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
+    I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
+    I.off_host = P.off.data(); I.site_tx = P.tx.data(); I.site_pos = P.pos.data(); I.site_kmer7 = P.k7.data();
+    I.tx_blob = P.blob.data(); I.tx_off = P.tx_off.data(); I.read_ids = P.ids.data();
+    I.n_rep = K; I.read_rep = P.rep.data();
+    return M6A_OK;
+}
+
+int sites_multi(int device_id, const char *const *paths, int n_paths, int rmin, int rmax, int min_seg, const char *norm_kmers,
+                const double *norm_mean, const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites &P)
+{
+    if (n_norm < 0 || (n_norm > 0 && (!norm_kmers || !norm_mean || !norm_std))) return prep_fail(M6A_EINVAL, "bad normalisation arguments");
+    const double t_all = now_ms();
+    g_d2h = 0;
+    DevMem m;
+    m.advice = "run `dataprep` and then `inference` instead (the two-step path)";
+    double *ms = P.info.ms;
+    int rc;
+    if (n_paths == 1) {
+        if ((rc = sites_impl(device_id, paths[0], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, P, m, ms, nullptr)))
+            return rc;
+    } else {
+        Pool pool;
+        double bytes = 0;
+        for (int f = 0; f < n_paths; f++) {
+            double fm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            if ((rc = sites_impl(device_id, paths[f], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, P, m, fm, &pool)))
+                return rc;
+            for (int k = 0; k < 6; k++) ms[k] += fm[k];
+            bytes += fm[6] * fm[0] * 1e6;
+        }
+        ms[6] = ms[0] > 0 ? bytes / (ms[0] * 1e6) : 0;
+        if ((rc = pool_impl(pool, norm_kmers, n_norm, m, P, ms))) return rc;
+    }
+    ms[7] = now_ms() - t_all;
+    P.info.d2h_bytes = g_d2h;
+    P.info.peak_bytes = (int64_t)m.peak;
     return M6A_OK;
 }
 
@@ -1712,15 +2166,26 @@ extern "C" int m6a_prep_sites_build(int device_id, const char *path, int readcou
                                     const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
                                     const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out)
 {
-    if (!path || !out) return prep_fail(M6A_EINVAL, "null argument");
+    if (!path) return prep_fail(M6A_EINVAL, "null argument");
+    return m6a_prep_sites_build_multi(device_id, &path, 1, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std,
+                                      n_norm, host, n_threads, out);
+}
+
+extern "C" int m6a_prep_sites_build_multi(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
+                                          int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std,
+                                          int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out)
+{
+    if (!paths || !out || n_paths < 1) return prep_fail(M6A_EINVAL, "null argument");
+    for (int f = 0; f < n_paths; f++)
+        if (!paths[f]) return prep_fail(M6A_EINVAL, "null argument");
     *out = nullptr;
     m6a_prep_sites *p = new (std::nothrow) m6a_prep_sites;
     if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
     p->device = device_id;
     int rc;
     try {
-        rc = sites_impl(device_id, path, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm, host,
-                        n_threads, *p);
+        rc = sites_multi(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm,
+                         host, n_threads, *p);
     } catch (const std::bad_alloc &) {
         rc = prep_fail(M6A_ENOMEM, "out of host memory");
     } catch (...) {

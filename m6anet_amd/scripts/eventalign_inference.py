@@ -5,7 +5,7 @@ probabilities come back to the host; no data.json is written or parsed."""
 import os
 import pathlib
 import time
-from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
+from argparse import Action, ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from . import dataprep, inference
 
@@ -21,9 +21,19 @@ def _copy(src, dst, flags):
             dst._add_action(a)
 
 
+class OneOrSeveral(Action):
+    """--eventalign a.txt -> "a.txt" (one file, as ever); --eventalign a.txt b.txt -> ["a.txt", "b.txt"] (replicates)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values[0] if len(values) == 1 else list(values))
+
+
 def argparser():
     parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter, add_help=False)
-    parser.add_argument("--eventalign", required=True, help="eventalign filepath, the output from nanopolish.")
+    parser.add_argument("--eventalign", required=True, nargs="+", action=OneOrSeveral,
+                        help="eventalign filepath, the output from nanopolish.  Several files are replicates: their sites are pooled "
+                             "as `inference` pools several --input_dir (a site is kept when its reads summed over the files reach 20), "
+                             "and read ids are written <id>_<position of the file>.")
     parser.add_argument("--out_dir", required=True, help="directory to output inference results.")
     _copy(dataprep.argparser(), parser, DATAPREP_FLAGS)
     _copy(inference.argparser(), parser, INFERENCE_FLAGS)
@@ -82,7 +92,9 @@ def main(args):
             import json
             ms, d2h = sites.times()
             ms.update(infer=(t1 - t0) * 1e3, fetch=(t2 - t1) * 1e3, csv_write=(time.perf_counter() - t2) * 1e3)
-            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads}), flush=True)
+            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads,
+                                                **({"n_replicates": sites.n_replicates, "peak_bytes": sites.peak_bytes}
+                                                   if sites.n_replicates > 1 else {})}), flush=True)
     finally:
         sites.close()
         engine.close()

@@ -8,7 +8,16 @@ tools/measure_pipeline.py build it), page-cache warm.
 A shape is a number of copies (1400: tools/measure_pipeline.py's shape) or a size in GB.  Every command runs in a child process of
 its own under `timeout -k` (one that hangs ends there and nothing more is started), with --n_processes 16 for all three.  Records
 both wall times, the fused path's phases (M6A_EVENTALIGN_TIMES: upload, newline offsets, parse + combine + windows, back half,
-host, device-to-host copies and bytes, infer, CSV write) and whether the two CSVs are byte-identical."""
+host, device-to-host copies and bytes, infer, CSV write) and whether the two CSVs are byte-identical.
+
+    python tools/measure_eventalign_inference.py --replicates 3 [--shapes 3.1GB] [--legs 3] [--parent_tree DIR] [--copy_rate]
+                                                 [--out profiles/r08_eventalign_replicates.json]
+
+The shape's file K times as K replicates.  Legs are interleaved and the medians reported: (a) the fused command on the K files
+against K `dataprep`s and one `inference` over their K directories; (b) with --parent_tree (a built checkout of the parent commit)
+the ONE-file fused command of this tree against that tree's, the bar being the parent's median plus its own spread (max - min of its
+legs); (c) with --copy_rate one more fused run under `rocprofv3 --kernel-trace --stats`, a run of its own: pool_copy_kernel's bytes
+read + written over its time, next to a device-to-device copy of the same bytes (torch) on the same device."""
 import filecmp
 import gzip
 import json
@@ -24,14 +33,14 @@ CSVS = ("data.site_proba.csv", "data.indiv_proba.csv")
 THREADS = ["--n_processes", "16"]
 
 
-def timed(cmd, limit, env=None):
+def timed(cmd, limit, env=None, tree=REPO, wrap=()):
     t0 = time.perf_counter()
-    p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, "-m", "m6anet_amd"] + cmd, capture_output=True, text=True,
-                       cwd=REPO, env=env)
+    p = subprocess.run(["timeout", "-k", "10", str(limit)] + list(wrap) + [sys.executable, "-m", "m6anet_amd"] + cmd, capture_output=True,
+                       text=True, cwd=tree, env=env)
     return time.perf_counter() - t0, p
 
 
-def shape(tag, ev_dir, limit):
+def write_shape(tag, ev_dir):
     text = gzip.open(SRC, "rt").read()
     header, body = text.split("\n", 1)
     n = int(float(tag[:-2]) * 1e9 / len(body)) if tag.endswith("GB") else int(tag)
@@ -41,6 +50,105 @@ def shape(tag, ev_dir, limit):
         for k in range(n):
             f.write(body.replace("ENST", "C%dENST" % k) if k else body)
     subprocess.run(["cat", path], stdout=subprocess.DEVNULL, check=True)          # page-cache warm
+    return path, n
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+class StepFailed(Exception):
+    pass
+
+
+def must(s, p, what):
+    if p.returncode != 0:
+        raise StepFailed({"step": what, "rc": p.returncode, "stderr_tail": p.stderr[-2000:]})
+    return s
+
+
+def copy_rate(path, K, ev_dir, limit):
+    """(c): pool_copy_kernel under the kernel trace, and a device-to-device copy of as many bytes"""
+    import glob
+    out = os.path.join(ev_dir, "trace")
+    s, p = timed(["eventalign_inference", "--eventalign"] + [path] * K + ["--out_dir", os.path.join(ev_dir, "trace_out")] + THREADS, limit,
+                 env=dict(os.environ, M6A_EVENTALIGN_TIMES="1"), wrap=["rocprofv3", "--kernel-trace", "--stats", "-d", out, "--"])
+    must(s, p, "fused under rocprofv3")
+    t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+    import sqlite3
+    ns = None
+    for fn in glob.glob(os.path.join(out, "**", "*_results.db"), recursive=True):      # the rocpd database, as tools/rocpd_summary.py reads it
+        con = sqlite3.connect(fn)
+        cols = [r[1] for r in con.execute("pragma table_info(kernels)")]
+        name = "name" if "name" in cols else "kernel_name"
+        row = con.execute("select sum(end - start), count(*) from kernels where %s like '%%pool_copy_kernel%%'" % name).fetchone()
+        con.close()
+        if row and row[1] == 1:
+            ns = float(row[0])
+    if ns is None:
+        raise StepFailed({"step": "kernel trace", "error": "no single pool_copy_kernel launch in the trace under %s" % out})
+    moved = 2 * 44 * t["n_reads"]                          # X (36 B) and the read id (8 B) of every pooled read, read and written
+    import torch
+    a = torch.empty(moved // 2, dtype=torch.uint8, device="cuda")
+    b = torch.empty_like(a)
+    times = []
+    for _ in range(12):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        b.copy_(a)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e6)
+    d2d = median(times[2:])
+    return {"n_reads": t["n_reads"], "n_sites": t["n_sites"], "bytes_read_and_written": moved, "pool_copy_kernel_ns": ns,
+            "pool_copy_GBps": moved / ns, "d2d_copy_ns": d2d, "d2d_copy_GBps": moved / d2d, "ratio": d2d / ns}
+
+
+def replicates(tag, K, legs, parent, with_copy_rate, ev_dir, limit):
+    path, n = write_shape(tag, ev_dir)
+    res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "replicates": K, "legs": legs}
+    two, fused, one, par = [], [], [], []
+    times_env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    try:
+        for leg in range(legs):
+            dirs = [os.path.join(ev_dir, "prep_%d" % k) for k in range(K)]
+            s = sum(must(*timed(["dataprep", "--eventalign", path, "--out_dir", d] + THREADS, limit), "dataprep") for d in dirs)
+            s2 = must(*timed(["inference", "--input_dir"] + dirs + ["--out_dir", os.path.join(ev_dir, "two")] + THREADS, limit), "inference")
+            two.append({"s": s + s2, "dataprep_s": s, "inference_s": s2})
+            s3, p3 = timed(["eventalign_inference", "--eventalign"] + [path] * K + ["--out_dir", os.path.join(ev_dir, "fused")] + THREADS, limit,
+                           env=times_env)
+            must(s3, p3, "fused")
+            t = json.loads(p3.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+            t["s"] = s3
+            fused.append(t)
+            res["csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "two", f), os.path.join(ev_dir, "fused", f), shallow=False) for f in CSVS)
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit), "one file, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, tree=parent), "one file, parent tree"))
+                res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
+                                                                 shallow=False) for f in CSVS)
+            for d in dirs + [os.path.join(ev_dir, x) for x in ("two", "fused", "one", "one_parent")]:
+                subprocess.run(["rm", "-rf", d], check=False)
+        res["two_step"] = {"median_s": median([x["s"] for x in two]), "legs": two}
+        res["fused"] = {"median_s": median([x["s"] for x in fused]), "legs": fused}
+        res["fused_over_two_step_speed"] = res["two_step"]["median_s"] / res["fused"]["median_s"]
+        if parent:
+            res["one_file"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                               "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                               "within_bar": median(one) <= median(par) + max(par) - min(par)}
+        if with_copy_rate:
+            res["pooled_copy"] = copy_rate(path, K, ev_dir, limit)
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+    os.remove(path)
+    return res
+
+
+def shape(tag, ev_dir, limit):
+    path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9}
     prep, two, fused = (os.path.join(ev_dir, tag + s) for s in ("_prep", "_two", "_fused"))
     s1, p1 = timed(["dataprep", "--eventalign", path, "--out_dir", prep] + THREADS, limit)
@@ -74,6 +182,22 @@ def main():
     dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r07_eventalign_inference.json")
     limit = int(sys.argv[sys.argv.index("--timeout") + 1]) if "--timeout" in sys.argv else 900
     res = {}
+    if "--replicates" in sys.argv:
+        K = int(sys.argv[sys.argv.index("--replicates") + 1])
+        shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB"]
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r08_eventalign_replicates.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 3
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                res[tag] = replicates(tag, K, legs, parent, "--copy_rate" in sys.argv, d, limit)
+                print(json.dumps({tag: res[tag]}), flush=True)
+                if "failed" in res[tag]:
+                    break                                   # a failed step: nothing more is started
+        os.makedirs(os.path.dirname(dest), exist_ok=True)
+        with open(dest, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
         for tag in shapes:
             res[tag] = shape(tag, d, limit)

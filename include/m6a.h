@@ -40,7 +40,8 @@ enum {
     M6A_ENODEV = -5,     /* no usable gfx950 device */
     M6A_EUNSUPPORTED = -6,
     M6A_EFORMAT = -7,    /* malformed input file (m6a_prep_eventalign) */
-    M6A_EIO = -8         /* a file cannot be opened or read (m6a_prep_eventalign) */
+    M6A_EIO = -8,        /* a file cannot be opened, read or written (m6a_prep_*) */
+    M6A_EDECLINED = -9   /* the device CSV writer met a value it does not format; nothing was written (m6a_csv_format) */
 };
 
 /* rng_mode of m6a_site_pool / m6a_infer / m6a_job_begin.  M6A_RNG_NUMPY is the ONLY value: exact replay of the reference's
@@ -412,6 +413,54 @@ int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, 
 /* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */
 int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_kmers, int64_t *off);
 void m6a_prep_sites_free(m6a_prep_sites *p);
+
+/* data.site_proba.csv and data.indiv_proba.csv formatted on the device: the bytes m6a_io_write_csv_n writes (include/m6a_io.h),
+ *   site row   <tx>,<pos>,<n_reads>,<%.16f of (double)site_prob>,<5-mer>,<%.16f of mod_ratio>\n
+ *   read row   <tx>,<pos>,<id>,<%.16f of (double)read_prob>\n     <id> = <int>.0 when n_rep = 1, <int>_<replicate> when n_rep > 1
+ * from arrays in device memory (the lengths of all rows, two exclusive 64-bit scans, then the text).  NaN and the infinities print as
+ * glibc prints them (nan, -nan, inf, -inf).  The kernels DECLINE, and count, exactly: a finite probability or ratio that is negative
+ * (-0.0 included) or >= 2; a read id that is not integral, is negative (-0.0 included) or is >= 10^15.  None of these comes out of
+ * m6a_infer on an eventalign.txt whose read indices are below 10^15.  With anything declined a call returns M6A_EDECLINED, has written
+ * no text and has opened no file; the caller writes through the host (m6a_io_write_csv_n).  Errors as the m6a_prep_* family: text in
+ * m6a_prep_last_error(), M6A_EIO with the path for a file that cannot be opened or written, M6A_ENOMEM over the device budget.
+ *
+ * m6a_csv_format: HOST arrays in (the set m6a_io_sites_from_arrays_rep and m6a_io_write_csv_n take: kmer5 [S][5] without
+ * terminators, read_rep [R] in [0, n_rep), read only when n_rep > 1), uploaded, the rows of sites [site_begin, site_end) formatted
+ * on device device_id, the two texts out.  *site_bytes, *indiv_bytes and *n_declined are always set; with site_text = indiv_text =
+ * NULL that is all (the sizing call), else both buffers must hold the texts.  Needs no weights and no m6a_ctx.
+ *
+ * m6a_prep_sites_write_csv: the same kernels on the handle's own device arrays after m6a_infer has filled read_prob / site_prob /
+ * mod_ratio: the handle keeps the per-site transcript, position and 7-mer, the read ids and, for replicates, the per-site part
+ * sizes on the device, and only the transcript names are uploaded.  Lengths and offsets are computed for the whole job first, so
+ * both file sizes and the declined count are known before a file is opened or truncated.  Then the sites go in rounds of whole
+ * sites bounded by M6A_CSV_ROUND_KB of text (default 32768; a site with more text than that is a round of its own), double-buffered
+ * in pinned memory: round k + 1 is formatted and copied while round k is pwrite()n at its offsets by n_threads threads (0: the CPUs
+ * this process may use).  write_header and n_sites_limit (< 0: all sites) as in m6a_io_write_csv_n.  stats (may be NULL) is filled
+ * on every return; the handle's d2h_bytes grows by stats->d2h_bytes and its peak_bytes rises to the handle's arrays plus the writer's
+ * buffers if that is higher. */
+typedef struct m6a_csv_arrays {
+    int64_t n_sites, n_tx;
+    const int64_t *off;             /* [n_sites + 1], off[0] = 0 */
+    const uint32_t *site_tx;        /* [n_sites] */
+    const int64_t *site_pos;        /* [n_sites] */
+    const char *kmer5;              /* [n_sites][5] */
+    const char *tx_blob;
+    const int64_t *tx_off;          /* [n_tx + 1] */
+    const double *read_ids;         /* [R], R = off[n_sites] */
+    const int32_t *read_rep;        /* [R], or NULL when n_rep = 1 */
+    int n_rep;
+    const float *read_prob, *site_prob;
+    const double *mod_ratio;
+} m6a_csv_arrays;
+typedef struct m6a_csv_stats {
+    double ms_format, ms_copy, ms_write;    /* lengths + scans + the write kernels; device -> pinned copies; pwrite */
+    int64_t site_bytes, indiv_bytes;        /* text of either file, headers not counted */
+    int64_t n_declined, d2h_bytes, n_rounds;
+} m6a_csv_stats;
+int m6a_csv_format(int device_id, const m6a_csv_arrays *a, int64_t site_begin, int64_t site_end, char *site_text, int64_t site_cap,
+                   char *indiv_text, int64_t indiv_cap, int64_t *site_bytes, int64_t *indiv_bytes, int64_t *n_declined);
+int m6a_prep_sites_write_csv(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
+                             m6a_csv_stats *stats);
 
 #ifdef __cplusplus
 }

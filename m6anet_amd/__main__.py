@@ -18,7 +18,7 @@ def main(argv=None):
     sub.add_parser("inference", parents=[inference.argparser()], help="run the MI355X inference hot path")
     sub.add_parser("dataprep", parents=[dataprep.argparser()], help="eventalign.txt -> data.json / data.info (native, host-only)")
     sub.add_parser("pack", parents=[pack.argparser()], help="data.json / data.info -> one binary site store that later runs map")
-    sub.add_parser("eventalign_inference", parents=[eventalign_inference.argparser()],
+    sub.add_parser("eventalign_inference", parents=[eventalign_inference.cli_parser()],
                    help="eventalign.txt -> the two CSVs in one process, the features kept in HBM (= dataprep, then inference)")
     args = parser.parse_args(argv)
     {"inference": inference, "dataprep": dataprep, "pack": pack, "eventalign_inference": eventalign_inference}[args.command].main(args)

@@ -265,6 +265,22 @@ class prep_sites:
         rep = (self.read_rep, self.n_replicates) if self.n_replicates > 1 else (None, 1)
         return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids, *rep)
 
+    def write_csv(self, out_dir, write_header=True, n_threads=0, n_sites=None):
+        """m6a_prep_sites_write_csv: both CSV files formatted on the device from the handle's arrays (after the engine has filled
+        read_prob / site_prob / mod_ratio) and pwritten from pinned rounds.  Returns the statistics as a dict.  Raises CsvDeclined
+        (nothing opened, nothing written) when a value is outside what the kernels format: write through writer() then."""
+        from . import _lib
+        st = _lib.CsvStats()
+        rc = self._L.m6a_prep_sites_write_csv(self._h, os.fsencode(out_dir), 1 if write_header else 0, -1 if n_sites is None else int(n_sites),
+                                              int(n_threads), C.byref(st))
+        self.peak_bytes = int(self.info.peak_bytes)
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+        if rc == _lib.M6A_EDECLINED:
+            raise CsvDeclined("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), rc, stats["n_declined"])
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        return stats
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.m6a_prep_sites_free(self._h)
@@ -282,6 +298,49 @@ class prep_sites:
             self.close()
         except Exception:
             pass
+
+
+class CsvDeclined(M6AIOError):
+    """The device CSV writer met `n_declined` values it does not format (M6A_EDECLINED, include/m6a.h); nothing was written."""
+
+    def __init__(self, msg, code, n_declined):
+        super().__init__(msg, code)
+        self.n_declined = int(n_declined)
+
+
+def csv_format(off, tx_pos, tx_blob, tx_off, site_tx, kmer5, read_ids, read_prob, site_prob, mod_ratio, read_rep=None, n_rep=1,
+               site_begin=0, site_end=None, device_id=0):
+    """m6a_csv_format (libm6a_hip.so): the rows of sites [site_begin, site_end) of data.site_proba.csv and data.indiv_proba.csv,
+    formatted on the device from host arrays (NativeSites.from_arrays' set plus the three outputs).  Returns
+    (site_bytes, indiv_bytes, n_declined); with n_declined > 0 both texts are None (the device wrote none)."""
+    from . import _lib
+    L = _lib.load()
+    S = len(tx_pos)
+    k5 = np.ascontiguousarray(np.frombuffer(b"".join(kmer5), np.uint8) if isinstance(kmer5, (list, tuple)) else kmer5, np.uint8)
+    keep = [np.ascontiguousarray(off, np.int64), np.ascontiguousarray(site_tx, np.uint32), np.ascontiguousarray(tx_pos, np.int64), k5,
+            np.ascontiguousarray(tx_off, np.int64), np.ascontiguousarray(read_ids, np.float64),
+            None if read_rep is None else np.ascontiguousarray(read_rep, np.int32), np.ascontiguousarray(read_prob, np.float32),
+            np.ascontiguousarray(site_prob, np.float32), np.ascontiguousarray(mod_ratio, np.float64)]
+    o, tx, pos, k5, txo, ids, rep, rp, sp, mr = keep
+    assert o.size == S + 1 and tx.size == S and k5.size == 5 * S and sp.size == S and mr.size == S
+    assert ids.size == rp.size == int(o[-1]) and (rep is None or rep.size == ids.size)
+    blob = bytes(tx_blob)
+    a = _lib.CsvArrays(S, len(txo) - 1, o.ctypes.data, tx.ctypes.data, pos.ctypes.data, k5.ctypes.data, blob, txo.ctypes.data, ids.ctypes.data,
+                       None if rep is None else rep.ctypes.data, int(n_rep), rp.ctypes.data, sp.ctypes.data, mr.ctypes.data)
+    b, e = int(site_begin), S if site_end is None else int(site_end)
+    ns, ni, nd = C.c_int64(), C.c_int64(), C.c_int64()
+
+    def call(site_buf, indiv_buf):
+        rc = L.m6a_csv_format(int(device_id), C.byref(a), b, e, site_buf, ns.value if site_buf else 0, indiv_buf, ni.value if indiv_buf else 0,
+                              C.byref(ns), C.byref(ni), C.byref(nd))
+        if rc not in (0, _lib.M6A_EDECLINED):
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), prep_on_device._CODES.get(rc, rc))
+        return rc
+    if call(None, None) == _lib.M6A_EDECLINED:
+        return None, None, nd.value
+    site_buf, indiv_buf = C.create_string_buffer(max(1, ns.value)), C.create_string_buffer(max(1, ni.value))
+    call(site_buf, indiv_buf)
+    return site_buf.raw[:ns.value], indiv_buf.raw[:ni.value], nd.value
 
 
 def _weakrefable(x):

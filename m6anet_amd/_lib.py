@@ -8,7 +8,8 @@ LIB_PATH = os.environ.get("M6A_HIP_LIB") or os.path.join(_PKG, "libm6a_hip.so") 
 
 M6A_OK = 0
 ERRORS = {-1: "M6A_EINVAL", -2: "M6A_ENOMEM", -3: "M6A_EHIP", -4: "M6A_ESTREAM", -5: "M6A_ENODEV",
-          -6: "M6A_EUNSUPPORTED", -7: "M6A_EFORMAT", -8: "M6A_EIO"}
+          -6: "M6A_EUNSUPPORTED", -7: "M6A_EFORMAT", -8: "M6A_EIO", -9: "M6A_EDECLINED"}
+M6A_EDECLINED = -9
 RNG_NUMPY = 0
 
 # every symbol include/m6a.h declares (tests check the .so exports exactly these)
@@ -17,7 +18,8 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_reference_written_sites",
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
-           "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free"]
+           "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
+           "m6a_csv_format", "m6a_prep_sites_write_csv"]
 
 _lib = None
 
@@ -34,6 +36,19 @@ class PrepSitesInfo(C.Structure):
                 ("off_host", C.c_void_p), ("site_tx", C.c_void_p), ("site_pos", C.c_void_p), ("site_kmer7", C.c_void_p),
                 ("tx_blob", C.c_void_p), ("tx_off", C.c_void_p), ("read_ids", C.c_void_p), ("ms", C.c_double * 8),
                 ("d2h_bytes", C.c_int64), ("n_rep", C.c_int), ("read_rep", C.c_void_p), ("peak_bytes", C.c_int64)]
+
+
+class CsvArrays(C.Structure):
+    """m6a_csv_arrays (include/m6a.h): host arrays for m6a_csv_format."""
+    _fields_ = [("n_sites", C.c_int64), ("n_tx", C.c_int64), ("off", C.c_void_p), ("site_tx", C.c_void_p), ("site_pos", C.c_void_p),
+                ("kmer5", C.c_void_p), ("tx_blob", C.c_char_p), ("tx_off", C.c_void_p), ("read_ids", C.c_void_p), ("read_rep", C.c_void_p),
+                ("n_rep", C.c_int), ("read_prob", C.c_void_p), ("site_prob", C.c_void_p), ("mod_ratio", C.c_void_p)]
+
+
+class CsvStats(C.Structure):
+    """m6a_csv_stats (include/m6a.h)."""
+    _fields_ = [("ms_format", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double), ("site_bytes", C.c_int64),
+                ("indiv_bytes", C.c_int64), ("n_declined", C.c_int64), ("d2h_bytes", C.c_int64), ("n_rounds", C.c_int64)]
 
 
 class M6AError(RuntimeError):
@@ -147,6 +162,9 @@ def load():
     L.m6a_prep_sites_inputs.argtypes = [vp, vp, vp, vp]
     L.m6a_prep_sites_free.argtypes = [vp]
     L.m6a_prep_sites_free.restype = None
+    pl = C.POINTER(i64)
+    L.m6a_csv_format.argtypes = [i32, C.POINTER(CsvArrays), i64, i64, vp, i64, vp, i64, pl, pl, pl]
+    L.m6a_prep_sites_write_csv.argtypes = [vp, C.c_char_p, i32, i64, i32, C.POINTER(CsvStats)]
     L.m6a_prep_last_error.argtypes = []
     L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:

@@ -24,6 +24,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -521,6 +522,12 @@ struct DevMem {
     }
     void release(const void *p) { drop(p, true); }
     void detach(const void *p) { drop(p, false); }
+    size_t size_of(const void *p) const
+    {
+        for (const auto &q : ptrs)
+            if (q.first == p) return q.second;
+        return 0;
+    }
 };
 
 struct Streams {
@@ -1325,7 +1332,13 @@ struct Pool {
 struct m6a_prep_sites {
     m6a_prep_sites_info info{};
     int device = 0;
-    std::vector<void *> dev;                 // X, site_kmers, off, read_prob, site_prob, mod_ratio
+    std::vector<void *> dev;                 // X, site_kmers, off, read_prob, site_prob, mod_ratio, and what the CSV writer reads:
+    const uint32_t *csv_tx = nullptr;        // [S] transcript of each site      } as the build left them on the device
+    const int64_t *csv_pos = nullptr;        // [S] position                     } (m6a_prep_sites_write_csv, m6a_csv.h)
+    const uint8_t *csv_k7 = nullptr;         // [S][7] 7-mer
+    const double *csv_ids = nullptr;         // [R] read ids
+    const int32_t *csv_parts = nullptr;      // [S][n_rep] reads of each site by replicate (several files)
+    size_t held = 0;                         // bytes of `dev`
     std::vector<int64_t> off, pos, tx_off;
     std::vector<uint32_t> tx;
     std::vector<char> k7;
@@ -1741,10 +1754,13 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     if ((rc = m.alloc(rp, (size_t)R, "read probabilities")) || (rc = m.alloc(sp, (size_t)NS, "site probabilities")) ||
         (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
         return rc;
-    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr}) {
+    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr,
+                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids}) {
+        P.held += m.size_of(p);
         m.detach(p);
         P.dev.push_back((void *)p);
     }
+    P.csv_tx = site_tx; P.csv_pos = site_pos; P.csv_k7 = site_k7; P.csv_ids = dids;
     m6a_prep_sites_info &I = P.info;
     I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
     I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
@@ -2086,10 +2102,13 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
     if ((rc = m.alloc(rp, (size_t)R, "read probabilities")) || (rc = m.alloc(sp, (size_t)NS, "site probabilities")) ||
         (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
         return rc;
-    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr}) {
+    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr,
+                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids, (const void *)blk_cnt}) {
+        P.held += m.size_of(p);
         m.detach(p);
         P.dev.push_back((void *)p);
     }
+    P.csv_tx = site_tx; P.csv_pos = site_pos; P.csv_k7 = site_k7; P.csv_ids = dids; P.csv_parts = blk_cnt;
     m6a_prep_sites_info &I = P.info;
     I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
     I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
@@ -2226,3 +2245,5 @@ extern "C" int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_
 }
 
 extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }
+
+#include "m6a_csv.h"

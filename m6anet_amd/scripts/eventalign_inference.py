@@ -40,6 +40,30 @@ def argparser():
     return parser
 
 
+def cli_parser():
+    """argparser() -- the flags this command shares with `dataprep` and `inference` -- and the flag that is its own"""
+    parser = argparser()
+    parser.add_argument("--csv", choices=("host", "device"), default="host",
+                        help="who formats the rows of the two CSV files: the host's threads from the probabilities copied back, or HIP "
+                             "kernels from the arrays in device memory, the text coming back in pinned rounds (about 50 B per read "
+                             "cross the link instead of 13).  The bytes are the same; values the kernels decline go through the host.")
+    return parser
+
+
+def write_on_device(sites, out_dir, n_threads, n_sites):
+    """--csv device: prep_sites.write_csv's statistics, or None after one line on stderr when the kernels declined a value --
+    nothing has been opened or written then, and the caller writes the same bytes through the host."""
+    import sys
+
+    from .. import _io
+    try:
+        return sites.write_csv(out_dir, write_header=True, n_threads=n_threads, n_sites=n_sites)
+    except _io.CsvDeclined as e:
+        print("eventalign_inference: --csv device declined %d values (%s); writing the CSV files on the host"
+              % (e.n_declined, str(e).split(": ", 1)[1]), file=sys.stderr, flush=True)
+        return None
+
+
 def main(args):
     import threading
 
@@ -50,6 +74,7 @@ def main(args):
 
     weights = inference.resolve_model(args)
     device = inference._device_index(args.device)
+    csv_on = getattr(args, "csv", "host")    # argparser() alone (no --csv): the host writer
     made = {}
 
     def make_engine():                       # the GPU context comes up while the file is parsed
@@ -71,7 +96,7 @@ def main(args):
     engine = made["engine"]
     try:
         pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
-        writer = sites.writer()
+        writer = sites.writer() if csv_on == "host" or sites.n_sites == 0 else None       # --csv device needs it only to fall back
         if sites.n_sites == 0:               # what `inference` leaves behind: the two header lines, then the loader's error
             writer.write_csv(args.out_dir, [], [], [], write_header=True, n_threads=args.n_processes)
             raise _io.M6AIOError("m6a_io error -4: no site with at least %d reads" % DEFAULT_MIN_READS, -4)
@@ -82,17 +107,26 @@ def main(args):
                           args.batch_size, args.save_per_batch, i.read_prob, i.site_prob, i.mod_ratio)
         engine.sync()
         t1 = time.perf_counter()
-        read_prob, site_prob, mod_ratio = sites.fetch()
-        t2 = time.perf_counter()
         n_write = None
         if args.drop_unflushed_tail:         # the reference's row set (inference_utils.py:47)
             n_write = reference_written_sites(sites.n_sites, args.batch_size, args.save_per_batch)
-        writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes, n_sites=n_write)
+        csv = write_on_device(sites, args.out_dir, args.n_processes, n_write) if csv_on == "device" else None
+        t2 = time.perf_counter()
+        if csv is None:
+            read_prob, site_prob, mod_ratio = sites.fetch()
+            t2 = time.perf_counter()
+            writer = writer or sites.writer()
+            writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes, n_sites=n_write)
         if os.environ.get("M6A_EVENTALIGN_TIMES"):      # phases for tools/measure_eventalign_inference.py
             import json
             ms, d2h = sites.times()
-            ms.update(infer=(t1 - t0) * 1e3, fetch=(t2 - t1) * 1e3, csv_write=(time.perf_counter() - t2) * 1e3)
-            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads,
+            ms.update(infer=(t1 - t0) * 1e3, fetch=(t2 - t1) * 1e3 if csv is None else 0.0,
+                      csv_write=(time.perf_counter() - (t2 if csv is None else t1)) * 1e3)        # csv_write: the writer's wall time
+            extra = {"csv_writer": "host"}
+            if csv is not None:              # the device writer's own phases; they overlap, so they need not add up to csv_write
+                ms.update(csv_format=csv["ms_format"], csv_copy=csv["ms_copy"], csv_pwrite=csv["ms_write"])
+                extra = {"csv_writer": "device", "csv_text_bytes": csv["site_bytes"] + csv["indiv_bytes"], "csv_rounds": csv["n_rounds"]}
+            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads, **extra,
                                                 **({"n_replicates": sites.n_replicates, "peak_bytes": sites.peak_bytes}
                                                    if sites.n_replicates > 1 else {})}), flush=True)
     finally:

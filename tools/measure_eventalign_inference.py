@@ -17,7 +17,16 @@ The shape's file K times as K replicates.  Legs are interleaved and the medians 
 against K `dataprep`s and one `inference` over their K directories; (b) with --parent_tree (a built checkout of the parent commit)
 the ONE-file fused command of this tree against that tree's, the bar being the parent's median plus its own spread (max - min of its
 legs); (c) with --copy_rate one more fused run under `rocprofv3 --kernel-trace --stats`, a run of its own: pool_copy_kernel's bytes
-read + written over its time, next to a device-to-device copy of the same bytes (torch) on the same device."""
+read + written over its time, next to a device-to-device copy of the same bytes (torch) on the same device.
+
+    python tools/measure_eventalign_inference.py --csv host,device [--shapes 1400,23.1GB] [--replicates 3] [--legs 5] [--parent_tree DIR]
+                                                 [--copy_rate] [--out profiles/r09_csv_device.json]
+
+The two CSV writers of this tree as interleaved legs of the same command (one file, or the shape's file K times with --replicates K):
+medians, the phase table of every leg, and the bar -- the --csv device median below the --csv host median by more than the host legs'
+spread (max - min).  With --parent_tree the default command (one file) against the parent's, the bar of mode (b).  With --copy_rate
+one more --csv device run under `rocprofv3 --kernel-trace --stats`, a run of its own: csv_indiv_kernel's bytes read + written over
+its time next to a device-to-device copy of as many bytes."""
 import filecmp
 import gzip
 import json
@@ -105,6 +114,101 @@ def copy_rate(path, K, ev_dir, limit):
             "pool_copy_GBps": moved / ns, "d2d_copy_ns": d2d, "d2d_copy_GBps": moved / d2d, "ratio": d2d / ns}
 
 
+def kernel_ns(trace_dir, like):
+    """(summed duration in ns, launches) of the kernels whose name contains `like`, from the rocpd database under trace_dir"""
+    import glob
+    import sqlite3
+    for fn in glob.glob(os.path.join(trace_dir, "**", "*_results.db"), recursive=True):
+        con = sqlite3.connect(fn)
+        cols = [r[1] for r in con.execute("pragma table_info(kernels)")]
+        name = "name" if "name" in cols else "kernel_name"
+        row = con.execute("select sum(end - start), count(*) from kernels where %s like '%%%s%%'" % (name, like)).fetchone()
+        con.close()
+        if row and row[1]:
+            return float(row[0]), int(row[1])
+    return None, 0
+
+
+def csv_copy_rate(paths, ev_dir, limit):
+    """csv_indiv_kernel under the kernel trace: per read it reads the id (8 B) and the probability (4 B) and writes the row's text"""
+    out = os.path.join(ev_dir, "trace")
+    s, p = timed(["eventalign_inference", "--eventalign"] + paths + ["--out_dir", os.path.join(ev_dir, "trace_out"), "--csv", "device"] + THREADS,
+                 limit, env=dict(os.environ, M6A_EVENTALIGN_TIMES="1"), wrap=["rocprofv3", "--kernel-trace", "--stats", "-d", out, "--"])
+    must(s, p, "--csv device under rocprofv3")
+    t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+    ns, n = kernel_ns(out, "csv_indiv_kernel")
+    if ns is None:
+        raise StepFailed({"step": "kernel trace", "error": "no csv_indiv_kernel launch in the trace under %s" % out})
+    len_ns, _ = kernel_ns(out, "csv_len_kernel")
+    indiv = os.path.getsize(os.path.join(ev_dir, "trace_out", CSVS[1]))
+    moved = indiv + 12 * t["n_reads"]
+    import torch
+    a = torch.empty(moved // 2, dtype=torch.uint8, device="cuda")
+    b = torch.empty_like(a)
+    times = []
+    for _ in range(12):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        b.copy_(a)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e6)
+    d2d = median(times[2:])
+    subprocess.run(["rm", "-rf", out, os.path.join(ev_dir, "trace_out")], check=False)
+    return {"n_reads": t["n_reads"], "n_sites": t["n_sites"], "indiv_text_bytes": indiv, "bytes_read_and_written": moved, "csv_indiv_kernel_ns": ns,
+            "csv_indiv_kernel_launches": n, "csv_len_kernel_ns": len_ns, "csv_indiv_GBps": moved / ns, "d2d_copy_ns": d2d,
+            "d2d_copy_GBps": moved / d2d, "ratio": d2d / ns}
+
+
+def csv_writers(tag, K, legs, parent, with_copy_rate, ev_dir, limit):
+    path, n = write_shape(tag, ev_dir)
+    paths = [path] * K
+    res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "replicates": K, "legs": legs}
+    runs = {"host": [], "device": []}
+    one, par = [], []
+    env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    try:
+        for leg in range(legs):
+            for mode in ("host", "device"):
+                out = os.path.join(ev_dir, "csv_" + mode)
+                s, p = timed(["eventalign_inference", "--eventalign"] + paths + ["--out_dir", out, "--csv", mode] + THREADS, limit, env=env)
+                must(s, p, "--csv " + mode)
+                t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+                t["s"] = s
+                runs[mode].append(t)
+            res["csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "csv_host", f), os.path.join(ev_dir, "csv_device", f), shallow=False)
+                                        for f in CSVS)
+            res["csv_bytes"] = [os.path.getsize(os.path.join(ev_dir, "csv_device", f)) for f in CSVS]
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit), "default command, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, tree=parent), "default command, parent tree"))
+                res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
+                                                                 shallow=False) for f in CSVS)
+            for d in ("csv_host", "csv_device", "one", "one_parent"):
+                subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+            print("%s: leg %d of %d: --csv host %.2f s, --csv device %.2f s" % (tag, leg + 1, legs, runs["host"][-1]["s"], runs["device"][-1]["s"]),
+                  file=sys.stderr, flush=True)
+        for mode in runs:
+            res[mode] = {"median_s": median([x["s"] for x in runs[mode]]), "legs": runs[mode]}
+        hs = [x["s"] for x in runs["host"]]
+        res["host_spread_s"] = max(hs) - min(hs)
+        res["device_below_host_by_s"] = res["host"]["median_s"] - res["device"]["median_s"]
+        res["device_beats_host_by_more_than_the_spread"] = res["device_below_host_by_s"] > res["host_spread_s"]
+        if parent:
+            res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                                      "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                                      "within_bar": median(one) <= median(par) + max(par) - min(par)}
+        if with_copy_rate:
+            res["csv_kernel"] = csv_copy_rate(paths, ev_dir, limit)
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+        res["legs_done"] = runs
+    os.remove(path)
+    return res
+
+
 def replicates(tag, K, legs, parent, with_copy_rate, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "replicates": K, "legs": legs}
@@ -182,6 +286,25 @@ def main():
     dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r07_eventalign_inference.json")
     limit = int(sys.argv[sys.argv.index("--timeout") + 1]) if "--timeout" in sys.argv else 900
     res = {}
+    if "--csv" in sys.argv:
+        if sorted(sys.argv[sys.argv.index("--csv") + 1].split(",")) != ["device", "host"]:
+            raise SystemExit("--csv host,device: both writers are measured against each other")
+        K = int(sys.argv[sys.argv.index("--replicates") + 1]) if "--replicates" in sys.argv else 1
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r09_csv_device.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        if os.path.exists(dest):                            # the one-file and the replicate run share the file
+            res = json.load(open(dest))
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                key = tag if K == 1 else "%s x %d replicates" % (tag, K)
+                res[key] = csv_writers(tag, K, legs, parent, "--copy_rate" in sys.argv, d, limit)
+                print(json.dumps({key: res[key]}), flush=True)
+                with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured
+                    json.dump(res, f, indent=1)
+                if "failed" in res[key]:
+                    break                                   # a failed step: nothing more is started
+        return
     if "--replicates" in sys.argv:
         K = int(sys.argv[sys.argv.index("--replicates") + 1])
         shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB"]

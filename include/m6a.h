@@ -325,7 +325,9 @@ const char *m6a_version(void);
  * the rows of that eventalign.index) and every run's candidate rows, as an m6a_io_prep_table that m6a_io_dataprep_write turns
  * into eventalign.index, data.json, data.info and data.log, byte-identical to m6a_io_dataprep.  Needs no weights and no ctx.
  * The whole file stays resident: device memory is capped at free memory minus a margin (M6A_PREP_BUDGET_MB lowers it), and a file
- * that does not fit is M6A_ENOMEM, with text that names --device cpu.  M6A_PREP_CHUNK_KB (default 65536, rounded up to 4 KB)
+ * that does not fit is M6A_ENOMEM, with text that names --device cpu.  M6A_PREP_WINDOW_KB > 0 parses the file in windows of that
+ * size instead (the cut rule is stated at m6a_prep_sites_build_windows; the front half is shared) and the table is the same; it
+ * is ignored when index_path is given, because the rows of an index are arbitrary byte ranges.  M6A_PREP_CHUNK_KB (default 65536, rounded up to 4 KB)
  * sets the size of the pinned upload chunks.  Runs the device declines (numbers outside the fast paths, events out of key order,
  * malformed lines) are marked M6A_PREP_RUN_HOST; the writer combines them on the host.  Errors: M6A_EFORMAT for a file without a
  * header line or a line with fewer than three tabs (the host's M6A_IO_EFORMAT), M6A_EIO for a missing file or index; the text is
@@ -372,7 +374,29 @@ const char *m6a_prep_last_error(void);
  * the 4 n_paths bytes per kept site that come back; nothing comes back per dropped site, and per read only its id.  tx_blob /
  * tx_off name the transcripts of all files in order of first appearance.  ms sums the files' phases; the union and the pooled copy
  * are counted in [3].  m6a_prep_sites_build is the n_paths = 1 case (n_rep = 1, read_rep all 0).  peak_bytes is the high-water mark
- * of the call's device allocations, the handle's own arrays included. */
+ * of the call's device allocations, the handle's own arrays included.
+ *
+ * m6a_prep_sites_build_windows: m6a_prep_sites_build_multi with a window size.  window_bytes = 0 keeps every file resident while it
+ * is parsed (about 3 bytes of device memory per byte of text at the peak); < 0 takes M6A_PREP_WINDOW_KB from the environment (unset or
+ * 0: resident), which is what the two entry points without the argument do.  W = window_bytes > 0, rounded up to a multiple of
+ * 4096, parses each file as consecutive windows, and the arrays are the same bit for bit:
+ *   range    window k is file bytes [b_k, e_k), b_0 = 0; e_k is the byte after the last '\n' among the W bytes from b_k, or the
+ *            file's end n when b_k + W >= n.  Only that last window may end without a newline, and in every other one the read
+ *            index is atoll of the text up to e_k.  Line 0 of window 0 is the header; later windows have none.
+ *   cut      runs are formed over the window's lines as over a file's.  When e_k < n the last run may go on behind e_k: it is not
+ *            of this window, and b_{k+1} is its first byte; a window without a line that has a tab gives b_{k+1} = e_k.  A window
+ *            whose only run starts at b_k, or that holds no newline, is done again with 2 W, 4 W, ... bytes from b_k until a second
+ *            run starts in it or it reaches n.  Lines without a tab between two runs belong to neither.
+ *   errors   "no header line" is window 0's; "short line at byte" names the file offset whole-file mode names, since windows go in
+ *            order and the first that holds such a line ends the call.
+ *   across   the first run of a window starts a segment; both halves intern contig names by their bytes, so a contig cut by a
+ *            window is one transcript and the ranks of its runs go on.
+ * What stays on the device while the windows pass is two windows of text, the scratch of one, and the runs (72 B each) and
+ * candidate rows found so far; the budget is checked against that, not against the file's size, and the back half still needs the
+ * rows of the whole file at once.  Per window only totals come back (counts, the last newline, the dropped run's start).
+ * n_windows is the number of windows summed over the files (1 per resident file) and window_bytes the largest window used,
+ * growth included (0 when every file was resident).  ms[0] is then the time the call waited for uploads, most of which run under
+ * the previous window's kernels, and ms[6] the copy thread's own rate. */
 typedef struct m6a_prep_sites m6a_prep_sites;
 struct m6a_io_rows;
 typedef struct m6a_prep_host_half {
@@ -401,6 +425,7 @@ typedef struct m6a_prep_sites_info {
     int n_rep;                      /* files pooled */
     const int32_t *read_rep;        /* [R] replicate of each read */
     int64_t peak_bytes;
+    int64_t n_windows, window_bytes;
 } m6a_prep_sites_info;
 int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
                          const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
@@ -408,6 +433,9 @@ int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int
 int m6a_prep_sites_build_multi(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
                                int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
                                const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out);
+int m6a_prep_sites_build_windows(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
+                                 int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                                 const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, m6a_prep_sites **out);
 const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p);     /* owned by p */
 int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio);
 /* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */

@@ -197,10 +197,15 @@ class prep_sites:
     """m6a_prep_sites_build (libm6a_hip.so): eventalign.txt -> the loader's arrays with X, site_kmers and off left on the device.
     `eventalign` is one path, or a list of paths that are replicates (m6a_prep_sites_build_multi: pooled on the device as the loader
     pools several input directories; a list of one is a list -- `<id>_0`).  `info` is the m6a_prep_sites_info; host copies are numpy
-    arrays (off, site_tx, tx_pos, kmer7, read_ids, read_rep) and `names` (per transcript); n_replicates and peak_bytes as reported.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
+    arrays (off, site_tx, tx_pos, kmer7, read_ids, read_rep) and `names` (per transcript); n_replicates and peak_bytes as reported.
+    window_kb: parse each file in windows of that many KB instead of keeping it resident (m6a_prep_sites_build_windows; the arrays
+    are the same), 0 for resident, None for what M6A_PREP_WINDOW_KB says; n_windows and window_bytes say what was done.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
     _CODES = prep_on_device._CODES
 
-    def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0):
+    def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0,
+                 window_kb=None):
+        if window_kb is not None and window_kb < 0:
+            raise ValueError("window_kb must be 0 or more, not %r" % (window_kb,))
         from . import _lib
         L, io = _lib.load(), load()
         self._L, self._h = L, C.c_void_p()
@@ -208,12 +213,14 @@ class prep_sites:
         host = _lib.HostHalf(C.cast(io.m6a_io_runs_rows, C.c_void_p), C.cast(io.m6a_io_rows_table, C.c_void_p),
                              C.cast(io.m6a_io_rows_free, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
         tail = (int(readcount_min), int(readcount_max), int(min_segment_count), blob, None if mean is None else mean.ctypes.data,
-                None if std is None else std.ctypes.data, n, C.byref(host), int(n_threads), C.byref(self._h))
-        if isinstance(eventalign, (str, bytes, os.PathLike)):
-            rc = L.m6a_prep_sites_build(int(device_id), os.fsencode(eventalign), *tail)
-        else:
-            paths = [os.fsencode(e) for e in eventalign]
-            rc = L.m6a_prep_sites_build_multi(int(device_id), (C.c_char_p * len(paths))(*paths), len(paths), *tail)
+                None if std is None else std.ctypes.data, n, C.byref(host), int(n_threads))
+        if isinstance(eventalign, (str, bytes, os.PathLike)) and window_kb is None:
+            rc = L.m6a_prep_sites_build(int(device_id), os.fsencode(eventalign), *tail, C.byref(self._h))
+        else:                                # one path with a window size: the one-file job, asked through the list's entry point
+            one = isinstance(eventalign, (str, bytes, os.PathLike))
+            paths = [os.fsencode(e) for e in ([eventalign] if one else eventalign)]
+            rc = L.m6a_prep_sites_build_windows(int(device_id), (C.c_char_p * len(paths))(*paths), len(paths), *tail,
+                                                -1 if window_kb is None else int(window_kb) << 10, C.byref(self._h))
         if rc != 0:
             raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
         i = self.info = L.m6a_prep_sites_get(self._h).contents
@@ -229,6 +236,7 @@ class prep_sites:
         self.read_ids = arr(i.read_ids, C.c_double, R)
         self.read_rep = arr(i.read_rep, C.c_int32, R)
         self.n_replicates, self.peak_bytes = int(i.n_rep), int(i.peak_bytes)
+        self.n_windows, self.window_bytes = int(i.n_windows), int(i.window_bytes)
         tx_off = arr(i.tx_off, C.c_int64, T + 1)
         self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
         self.tx_off = tx_off

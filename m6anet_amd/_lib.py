@@ -18,7 +18,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_reference_written_sites",
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
-           "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
+           "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv"]
 
 _lib = None
@@ -35,7 +35,8 @@ class PrepSitesInfo(C.Structure):
                 ("off", C.c_void_p), ("read_prob", C.c_void_p), ("site_prob", C.c_void_p), ("mod_ratio", C.c_void_p),
                 ("off_host", C.c_void_p), ("site_tx", C.c_void_p), ("site_pos", C.c_void_p), ("site_kmer7", C.c_void_p),
                 ("tx_blob", C.c_void_p), ("tx_off", C.c_void_p), ("read_ids", C.c_void_p), ("ms", C.c_double * 8),
-                ("d2h_bytes", C.c_int64), ("n_rep", C.c_int), ("read_rep", C.c_void_p), ("peak_bytes", C.c_int64)]
+                ("d2h_bytes", C.c_int64), ("n_rep", C.c_int), ("read_rep", C.c_void_p), ("peak_bytes", C.c_int64),
+                ("n_windows", C.c_int64), ("window_bytes", C.c_int64)]
 
 
 class CsvArrays(C.Structure):
@@ -156,6 +157,8 @@ def load():
     L.m6a_prep_sites_build.argtypes = [i32, C.c_char_p, i32, i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(HostHalf), i32, C.POINTER(vp)]
     L.m6a_prep_sites_build_multi.argtypes = [i32, C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(HostHalf), i32,
                                              C.POINTER(vp)]
+    L.m6a_prep_sites_build_windows.argtypes = [i32, C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(HostHalf), i32,
+                                               i64, C.POINTER(vp)]
     L.m6a_prep_sites_get.argtypes = [vp]
     L.m6a_prep_sites_get.restype = C.POINTER(PrepSitesInfo)
     L.m6a_prep_sites_fetch.argtypes = [vp, vp, vp, vp]

@@ -16,6 +16,8 @@
 //   runs        valid lines compacted, a run starts where the contig bytes or the read index change (index_range)
 //   combine     one lane per run: Kahan sums per (position, k-mer) group, count then write
 //   windows     one lane per run: runs of 2w + 1 consecutive positions with a DRACH centre, count then write
+// With a window size (M6A_PREP_WINDOW_KB, m6a_prep_sites_build_windows) the same kernels run on one window of the file after the other
+// and only runs and rows stay on the device: front_windows, below.
 // Everything is built with -ffp-contract=off (build.py): no multiply-add is fused, and the f64 divisions are IEEE `/`.
 #include <hip/hip_runtime.h>
 
@@ -31,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -206,11 +209,11 @@ __device__ inline bool dev_float(const uint8_t *f, int64_t p, int64_t e, double 
     return true;
 }
 
-// one lane per body line i = 1 .. nlines - 1 (line 0 is the header)
-__global__ void line_kernel(const uint8_t *__restrict__ f, int64_t n, const int64_t *__restrict__ nl, int64_t NL, int64_t nlines,
+// one lane per body line i = first .. nlines - 1 (first = 1: line 0 is the header; 0 in a window behind the first, which has none)
+__global__ void line_kernel(const uint8_t *__restrict__ f, int64_t n, const int64_t *__restrict__ nl, int64_t NL, int64_t nlines, int64_t first,
                             LineEv *__restrict__ ev, unsigned long long *__restrict__ bad_at)
 {
-    const int64_t i = 1 + (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    const int64_t i = first + (int64_t)blockIdx.x * kBlk + threadIdx.x;
     if (i >= nlines) return;
     const int64_t p = line_start(nl, i), le = line_end(nl, NL, n, i);
     LineEv r;
@@ -252,16 +255,17 @@ __global__ void line_kernel(const uint8_t *__restrict__ f, int64_t n, const int6
     ev[i] = r;
 }
 
-__global__ void flag_kernel(const LineEv *__restrict__ ev, int64_t nlines, int64_t *__restrict__ out)
+__global__ void flag_kernel(const LineEv *__restrict__ ev, int64_t nlines, int64_t first, int64_t *__restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
-    if (i < nlines) out[i] = i >= 1 && (ev[i].flags & L_TAB) ? 1 : 0;
+    if (i < nlines) out[i] = i >= first && (ev[i].flags & L_TAB) ? 1 : 0;
 }
 
-__global__ void compact_kernel(const int64_t *__restrict__ flag_scan, int64_t nlines, const LineEv *__restrict__ ev, int64_t *__restrict__ vline)
+__global__ void compact_kernel(const int64_t *__restrict__ flag_scan, int64_t nlines, int64_t first, const LineEv *__restrict__ ev,
+                               int64_t *__restrict__ vline)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
-    if (i >= 1 && i < nlines && (ev[i].flags & L_TAB)) vline[flag_scan[i]] = i;
+    if (i >= first && i < nlines && (ev[i].flags & L_TAB)) vline[flag_scan[i]] = i;
 }
 
 __device__ inline bool same_bytes(const uint8_t *f, int64_t a, int64_t b, int64_t len)
@@ -443,6 +447,19 @@ __global__ void window_kernel(const uint8_t *__restrict__ f, const RunDev *__res
     if (!row_pos) row_cnt[r] = nrow;
 }
 
+// a window's kept runs to the job's run list: start / end / contig become file offsets (the window's text starts at file byte b);
+// l0, l1 and the k-mer offsets of the line and position records stay the window's own, and nothing reads them after the window
+__global__ void keep_runs_kernel(const RunDev *__restrict__ runs, int64_t NR, int64_t b, const int64_t *__restrict__ row_off,
+                                 RunDev *__restrict__ kept, int64_t *__restrict__ row_cnt)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r >= NR) return;
+    RunDev R = runs[r];
+    R.start += b; R.end += b; R.contig += b;
+    kept[r] = R;
+    row_cnt[r] = row_off[r + 1] - row_off[r];
+}
+
 __global__ void run_cols_kernel(const RunDev *__restrict__ runs, int64_t NR, int64_t *__restrict__ npos)
 {
     const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
@@ -478,16 +495,32 @@ namespace {
         if (e_ != hipSuccess) return prep_fail(M6A_EHIP, "%s: %s", #x, hipGetErrorString(e_));                             \
     } while (0)
 
+// scratch of the window loop: one allocation (counted like any other) that every window bump-allocates from the start, so that no
+// hipMalloc or hipFree runs between the kernels of a window; a window that needs more says how much and is done again
+struct Arena {
+    uint8_t *base = nullptr;
+    size_t cap = 0, off = 0, need = 0;
+};
+constexpr int kArenaFull = 1;               // DevMem::alloc's answer then; never leaves front_windows
+
 // device memory of one call, every allocation counted against the budget (free memory minus a margin, or M6A_PREP_BUDGET_MB)
 struct DevMem {
     std::vector<std::pair<void *, size_t>> ptrs;
     size_t used = 0, budget = 0, peak = 0;
     bool budget_set = false;                     // the first file of a job sets it; what stays of earlier files counts against it
     const char *advice = "use --device cpu";     // what the budget error tells the user to do instead
+    Arena *arena = nullptr;                      // set: alloc() takes from it (release() of such a pointer does nothing)
     ~DevMem() { for (auto &p : ptrs) (void)hipFree(p.first); }
     template <class T> int alloc(T *&p, size_t count, const char *what)
     {
         const size_t bytes = std::max<size_t>(16, count * sizeof(T));
+        if (arena) {
+            const size_t a = (bytes + 255) & ~(size_t)255;
+            if (arena->off + a > arena->cap) { arena->need = std::max(arena->need, arena->off + a); return kArenaFull; }
+            p = (T *)(arena->base + arena->off);
+            arena->off += a;
+            return M6A_OK;
+        }
         if (used + bytes > budget)
             return prep_fail(M6A_ENOMEM, "dataprep on the device needs more than its budget of %zu MB (%s: %zu MB used, %zu MB more); "
                              "this file does not fit: %s", budget >> 20, what, used >> 20, bytes >> 20, advice);
@@ -613,9 +646,65 @@ int read_index(const char *path, std::vector<std::string> &names, std::vector<ui
     return M6A_OK;
 }
 
+// runs of the valid lines from line `first` on (index_range): runs[NR + 1], in `m`; the three work arrays are noted in `scratch`
+int find_runs(DevMem &m, hipStream_t s, const uint8_t *df, int64_t n, const int64_t *nl, int64_t NL, int64_t nlines, int64_t first,
+              const LineEv *ev, RunDev *&runs, int64_t &NR, std::vector<const void *> *scratch)
+{
+    int rc;
+    int64_t *vflag, NV = 0;
+    if ((rc = m.alloc(vflag, (size_t)nlines + 1, "valid lines"))) return rc;
+    flag_kernel<<<grid(nlines), kBlk, 0, s>>>(ev, nlines, first, vflag);
+    PCHK(hipGetLastError());
+    if ((rc = scan_total(m, vflag, nlines, s, NV))) return rc;
+    int64_t *vline, *nr;
+    if ((rc = m.alloc(vline, (size_t)NV + 1, "valid lines"))) return rc;
+    if ((rc = m.alloc(nr, (size_t)NV + 1, "run starts"))) return rc;
+    if (scratch) scratch->insert(scratch->end(), {vflag, vline, nr});
+    compact_kernel<<<grid(nlines), kBlk, 0, s>>>(vflag, nlines, first, ev, vline);
+    PCHK(hipGetLastError());
+    if (NV > 0) {
+        newrun_kernel<<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, nr, NV, s, NR))) return rc;     // nr[j] = run of valid line j (exclusive scan of the starts) ...
+    // ... so valid line j's run is nr[j + 1] - 1: shift by one with an inclusive view
+    if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
+    if (NV > 0) {
+        runs_kernel<<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs);
+        PCHK(hipGetLastError());
+    }
+    return M6A_OK;
+}
+
+// combine of runs[0, NR) (count, then write ps at pos_off) and the count of their candidate rows: row_off is the exclusive scan
+int count_rows(DevMem &m, hipStream_t s, const uint8_t *df, const LineEv *ev, RunDev *runs, int64_t NR, int w, int64_t *&pos_off, PosRec *&ps,
+               int64_t *&row_off, int64_t &NROW)
+{
+    int rc;
+    int64_t NP = 0;
+    if ((rc = m.alloc(pos_off, (size_t)NR + 1, "positions"))) return rc;
+    if (NR) {
+        combine_kernel<<<grid(NR), kBlk, 0, s>>>(df, ev, runs, NR, nullptr, nullptr);
+        PCHK(hipGetLastError());
+        run_cols_kernel<<<grid(NR), kBlk, 0, s>>>(runs, NR, pos_off);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, pos_off, NR, s, NP))) return rc;
+    if ((rc = m.alloc(ps, (size_t)NP + 1, "combined positions"))) return rc;
+    if ((rc = m.alloc(row_off, (size_t)NR + 1, "rows"))) return rc;
+    if (NR) {
+        combine_kernel<<<grid(NR), kBlk, 0, s>>>(df, ev, runs, NR, pos_off, ps);
+        PCHK(hipGetLastError());
+        window_kernel<<<grid(NR), kBlk, 0, s>>>(df, runs, NR, pos_off, ps, w, row_off, nullptr, nullptr, nullptr, nullptr);
+        PCHK(hipGetLastError());
+    }
+    return scan_total(m, row_off, NR, s, NROW);
+}
+
 // The device results of the front half (upload, newline scan, lines, runs, combine, windows); all of them live in `m`.
 struct Front {
     int64_t n = 0, NR = 0, NROW = 0;
+    int64_t n_windows = 1, window_bytes = 0; // whole file: one window, of no set size
     RunDev *runs = nullptr;
     int64_t *row_off = nullptr, *row_pos = nullptr;
     uint8_t *row_kmer = nullptr;
@@ -623,8 +712,18 @@ struct Front {
     std::vector<const void *> scratch;      // the file, its newlines, lines and combined positions: nothing after the windows reads them
 };
 
+int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
+
+// M6A_PREP_WINDOW_KB as a window size in bytes (unset, 0 or not a number: the whole file)
+int64_t window_from_env()
+{
+    const char *e = getenv("M6A_PREP_WINDOW_KB");
+    return e && atoll(e) > 0 ? atoll(e) << 10 : 0;
+}
+
 // istart / iend: the runs of an eventalign.index (--skip_index), or null.  ms[0..2], ms[5] as m6a_prep_times reports them.
-int front_half(int device_id, const char *path, int w, const std::vector<int64_t> *istart, const std::vector<int64_t> *iend,
+// window > 0 (rounded up to whole 4 KB blocks) and no index: the file goes through in windows (front_windows); else it is resident.
+int front_half(int device_id, const char *path, int w, const std::vector<int64_t> *istart, const std::vector<int64_t> *iend, int64_t window,
                DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
 {
     const bool index_path = istart != nullptr;
@@ -648,11 +747,15 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
     }
     const int64_t nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);       // 4 KB scan blocks; the buffer is padded to them
-    uint8_t *df;
-    int64_t *bcnt;
-    int rc = m.alloc(df, (size_t)(nb * kScanBytes), "the file");
-    if (!rc) rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts");
-    if (rc) return rc;
+    const int64_t W = index_path || window <= 0 ? 0 : (window + kScanBytes - 1) / kScanBytes * kScanBytes;
+    uint8_t *df = nullptr;
+    int64_t *bcnt = nullptr;
+    int rc = M6A_OK;
+    if (!W) {
+        rc = m.alloc(df, (size_t)(nb * kScanBytes), "the file");
+        if (!rc) rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts");
+        if (rc) return rc;
+    }
 
     for (int i = 0; i < 2; i++) {
         PCHK(hipStreamCreateWithFlags(&S.s[i], hipStreamNonBlocking));
@@ -662,8 +765,9 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     const char *ck = getenv("M6A_PREP_CHUNK_KB");
     int64_t chunk = (ck && atoll(ck) > 0 ? atoll(ck) : 65536) << 10;
     chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
-    chunk = std::min<int64_t>(chunk, nb * kScanBytes);
+    chunk = std::min<int64_t>(chunk, W ? W : nb * kScanBytes);
     for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&S.pin[i], (size_t)chunk, hipHostMallocDefault));
+    if (W) return front_windows(device_id, path, w, W, chunk, m, S, fd, F, ms);
     PCHK(hipMemsetAsync(df + (nb - 1) * kScanBytes, 0, (size_t)kScanBytes, S.s[1]));        // the zero padding of the last block
 
     // ---- upload: pread chunk k into one pinned buffer while chunk k - 1 is copied and counted
@@ -715,7 +819,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     const unsigned long long none = ~0ull;
     PCHK(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, s));
     if (nlines > 1) {
-        line_kernel<<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, ev, bad);
+        line_kernel<<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, 1, ev, bad);
         PCHK(hipGetLastError());
     }
     unsigned long long bad_at = none;
@@ -727,28 +831,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     int64_t NR = 0;
     RunDev *runs = nullptr;
     if (!index_path) {
-        int64_t *vflag, NV = 0;
-        if ((rc = m.alloc(vflag, (size_t)nlines + 1, "valid lines"))) return rc;
-        flag_kernel<<<grid(nlines), kBlk, 0, s>>>(ev, nlines, vflag);
-        PCHK(hipGetLastError());
-        if ((rc = scan_total(m, vflag, nlines, s, NV))) return rc;
-        int64_t *vline, *nr;
-        if ((rc = m.alloc(vline, (size_t)NV + 1, "valid lines"))) return rc;
-        if ((rc = m.alloc(nr, (size_t)NV + 1, "run starts"))) return rc;
-        F.scratch.insert(F.scratch.end(), {vflag, vline, nr});
-        compact_kernel<<<grid(nlines), kBlk, 0, s>>>(vflag, nlines, ev, vline);
-        PCHK(hipGetLastError());
-        if (NV > 0) {
-            newrun_kernel<<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr);
-            PCHK(hipGetLastError());
-        }
-        if ((rc = scan_total(m, nr, NV, s, NR))) return rc;     // nr[j] = run of valid line j (exclusive scan of the starts) ...
-        // ... so valid line j's run is nr[j + 1] - 1: shift by one with an inclusive view
-        if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
-        if (NV > 0) {
-            runs_kernel<<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs);
-            PCHK(hipGetLastError());
-        }
+        if ((rc = find_runs(m, s, df, n, nl, NL, nlines, 1, ev, runs, NR, &F.scratch))) return rc;
     } else {
         NR = (int64_t)istart->size();
         if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
@@ -761,26 +844,9 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         }
         PCHK(hipStreamSynchronize(s));                        // h goes out of scope
     }
-    int64_t *pos_off, NP = 0;
-    if ((rc = m.alloc(pos_off, (size_t)NR + 1, "positions"))) return rc;
-    if (NR) {
-        combine_kernel<<<grid(NR), kBlk, 0, s>>>(df, ev, runs, NR, nullptr, nullptr);
-        PCHK(hipGetLastError());
-        run_cols_kernel<<<grid(NR), kBlk, 0, s>>>(runs, NR, pos_off);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, pos_off, NR, s, NP))) return rc;
+    int64_t *pos_off, *row_off, NROW = 0;
     PosRec *ps;
-    if ((rc = m.alloc(ps, (size_t)NP + 1, "combined positions"))) return rc;
-    int64_t *row_off, NROW = 0;
-    if ((rc = m.alloc(row_off, (size_t)NR + 1, "rows"))) return rc;
-    if (NR) {
-        combine_kernel<<<grid(NR), kBlk, 0, s>>>(df, ev, runs, NR, pos_off, ps);
-        PCHK(hipGetLastError());
-        window_kernel<<<grid(NR), kBlk, 0, s>>>(df, runs, NR, pos_off, ps, w, row_off, nullptr, nullptr, nullptr, nullptr);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, row_off, NR, s, NROW))) return rc;
+    if ((rc = count_rows(m, s, df, ev, runs, NR, w, pos_off, ps, row_off, NROW))) return rc;
     const int64_t K = 5 + 2 * w, NF = 3 * (2 * w + 1);
     int64_t *drow_pos;
     uint8_t *drow_kmer;
@@ -799,6 +865,327 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     return M6A_OK;
 }
 
+// ---- the front half in windows ---------------------------------------------------------------------------------------------------
+// The file goes through HBM W bytes at a time and only runs and candidate rows stay (include/m6a.h states the cut).  Window k is file
+// bytes [b, e): e is the byte after the last '\n' among the W bytes from b, or the file's end in the last window; lines, runs,
+// combine and windows are the whole-file kernels on that text (line 0 is the header in window 0 only).  The last run of a window that
+// is not the last may go on behind e: it is left out, and the next window starts at its first byte -- so every kept run was seen
+// whole, and a window whose only run starts at b is done again at twice the size.  The first run of a window has same_contig = 0:
+// a contig cut by a window becomes two segments, which both consumers intern under one name, and sites_impl's rank0 of the second
+// is the number of runs the transcript had before it (tx_runs) -- run_select_kernel's rank0 + (r - first) is then the rank the run
+// has in the one segment of whole-file mode, because the two segments are consecutive runs.
+// Two text buffers: while the kernel stream combines and windows window k, a thread preads window k + 1 through the pinned pair and
+// copies it on the copy stream.  It starts when window k's cut is known and reads from b of k + 1, so the bytes between that and
+// window k's end are read again (not copied from window k's buffer: the next text then starts 16-byte aligned at its buffer's
+// start, which the newline scan needs).  One arena serves both: the kernels of two windows never overlap.
+// What stays is appended in place: kept runs, their row counts and the three row arrays grow as device vectors whose capacity is
+// projected from the rows per byte so far, so the usual peak is the rows plus a margin.  (Result blocks per window, flattened at the
+// end with each block released as it is copied, would hold the rows twice at the moment the flat arrays are allocated.)  A vector
+// that outgrows its capacity is copied into a new one and both exist during the copy: a wrong projection costs up to twice that
+// array for that moment, and where the budget cannot take the projection the vector grows by half, not window by window.
+struct Upload {
+    int rc = M6A_OK;
+    std::string err;
+    double ms = 0;
+    std::thread t;
+    void wait() { if (t.joinable()) t.join(); }
+    ~Upload() { wait(); }
+};
+
+// file bytes [off, off + len) -> dst on the copy stream, zeros behind them to a whole scan block; returns when they have arrived
+int upload_range(int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk)
+{
+    PCHK(hipSetDevice(device_id));
+    for (int64_t k = 0, done = 0; done < len; k++, done += chunk) {
+        const int slot = (int)(k & 1);
+        PCHK(hipEventSynchronize(S.copied[slot]));
+        const int64_t part = std::min(chunk, len - done);
+        for (int64_t got = 0; got < part;) {
+            const ssize_t r = ::pread(fd, (char *)S.pin[slot] + got, (size_t)(part - got), (off_t)(off + done + got));
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
+            got += r;
+        }
+        PCHK(hipMemcpyAsync(dst + done, S.pin[slot], (size_t)part, hipMemcpyHostToDevice, S.s[1]));
+        PCHK(hipEventRecord(S.copied[slot], S.s[1]));
+    }
+    const int64_t padded = std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes;
+    if (padded > len) PCHK(hipMemsetAsync(dst + len, 0, (size_t)(padded - len), S.s[1]));
+    PCHK(hipStreamSynchronize(S.s[1]));
+    return M6A_OK;
+}
+
+void upload_start(Upload &u, int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk)
+{
+    u.t = std::thread([&u, device_id, fd, path, &S, dst, off, len, chunk]() {
+        const double t0 = now_ms();
+        u.rc = upload_range(device_id, fd, path, S, dst, off, len, chunk);
+        if (u.rc) u.err = g_prep_err;                       // the text is this thread's; the caller takes it over
+        u.ms = now_ms() - t0;
+    });
+}
+
+// a device array that grows at its end; everything in it is counted in `m`
+struct DevVec {
+    uint8_t *p = nullptr;
+    size_t cap = 0, used = 0;                               // bytes
+    // room for `need` bytes: `hope` (the projection) if the budget allows it, else half as much again as there is, else just `need`.
+    // What is there stays (s is idle); while it is copied the old and the new array both count against the budget.
+    int fit(DevMem &m, size_t need, size_t hope, hipStream_t s, const char *what)
+    {
+        if (p && need <= cap) return M6A_OK;
+        Arena *const a = m.arena;
+        m.arena = nullptr;
+        uint8_t *q = nullptr;
+        int rc = M6A_OK;
+        const size_t tries[3] = {hope, cap + cap / 2, need};
+        for (size_t t : tries) {
+            if (t < need || (t > need && m.used + t > m.budget)) continue;
+            hope = t;
+            rc = m.alloc(q, t, what);
+            break;
+        }
+        m.arena = a;
+        if (rc) return rc;
+        if (used) {
+            PCHK(hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, s));
+            PCHK(hipStreamSynchronize(s));
+        }
+        if (p) m.release(p);
+        p = q;
+        cap = std::max<size_t>(16, hope);
+        return M6A_OK;
+    }
+};
+
+struct Win {                                // one window: file bytes [b, b + n); `len` bytes from b are in df, zeros behind them
+    const uint8_t *df = nullptr;
+    int64_t b = 0, len = 0, n = 0, first = 0;
+    bool last = false, grow = false;
+    int64_t NL = 0, nlines = 0, NR = 0, keep = 0, next = 0;
+    int64_t *nl = nullptr;
+    LineEv *ev = nullptr;
+    RunDev *runs = nullptr;
+};
+
+// newline scan, lines and runs of a window, and its cut: n, keep (the runs that stay) and next (b of the window after) -- or grow
+int window_cut(DevMem &m, hipStream_t s, const char *path, Win &V, double *ms)
+{
+    double t1 = now_ms();
+    int rc;
+    const int64_t nb = std::max<int64_t>(1, (V.len + kScanBytes - 1) / kScanBytes);
+    int64_t *bcnt;
+    if ((rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts"))) return rc;
+    nl_count_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)V.df, 0, bcnt);
+    PCHK(hipGetLastError());
+    if ((rc = scan_total(m, bcnt, nb, s, V.NL))) return rc;
+    if (V.last && V.b == 0 && V.NL == 0) return prep_fail(M6A_EFORMAT, "%s: no header line", path);
+    V.grow = !V.last && V.NL == 0;                           // a line longer than the window
+    if (V.grow) return M6A_OK;
+    if ((rc = m.alloc(V.nl, (size_t)V.NL + 1, "newline offsets"))) return rc;
+    nl_write_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)V.df, nb, bcnt, V.nl);
+    PCHK(hipGetLastError());
+    if (V.last) {                                            // the only window that may end without a newline
+        uint8_t end = '\n';
+        if (V.len > 0) { PCHK(hipMemcpyAsync(&end, V.df + V.len - 1, 1, hipMemcpyDeviceToHost, s)); g_d2h += 1; }
+        PCHK(hipStreamSynchronize(s));
+        V.n = V.len;
+        V.nlines = V.NL + (end != '\n' ? 1 : 0);
+    } else {                                                 // it ends behind its last newline; what follows is the next window's
+        int64_t at = 0;
+        PCHK(hipMemcpyAsync(&at, V.nl + V.NL - 1, sizeof at, hipMemcpyDeviceToHost, s));
+        g_d2h += (int64_t)sizeof at;
+        PCHK(hipStreamSynchronize(s));
+        V.n = at + 1;
+        V.nlines = V.NL;
+    }
+    ms[1] += now_ms() - t1;
+
+    t1 = now_ms();
+    unsigned long long *bad;
+    if ((rc = m.alloc(V.ev, (size_t)std::max<int64_t>(V.nlines, 1), "line records"))) return rc;
+    if ((rc = m.alloc(bad, 1, "flags"))) return rc;
+    const unsigned long long none = ~0ull;
+    PCHK(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, s));
+    if (V.nlines > V.first) {
+        line_kernel<<<grid(V.nlines - V.first), kBlk, 0, s>>>(V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, bad);
+        PCHK(hipGetLastError());
+    }
+    unsigned long long bad_at = none;
+    PCHK(hipMemcpyAsync(&bad_at, bad, sizeof bad_at, hipMemcpyDeviceToHost, s));
+    g_d2h += (int64_t)sizeof bad_at;
+    PCHK(hipStreamSynchronize(s));
+    // every line in front of this window has been seen, so this is the file's first short line, as whole-file mode reports it
+    if (bad_at != none) return prep_fail(M6A_EFORMAT, "%s: short line at byte %lld", path, (long long)(V.b + (int64_t)bad_at));
+    if ((rc = find_runs(m, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.runs, V.NR, nullptr))) return rc;
+    V.keep = V.NR;
+    V.next = V.b + V.n;
+    if (!V.last && V.NR > 0) {                               // the last run may go on in the next window: that one starts with it
+        int64_t start = 0;
+        PCHK(hipMemcpyAsync(&start, &V.runs[V.NR - 1].start, sizeof start, hipMemcpyDeviceToHost, s));
+        g_d2h += (int64_t)sizeof start;
+        PCHK(hipStreamSynchronize(s));
+        V.keep = V.NR - 1;
+        V.next = V.b + start;
+        V.grow = V.next == V.b;                              // its only run, from its first byte: no cut in here
+    }
+    ms[2] += now_ms() - t1;
+    return M6A_OK;
+}
+
+// what stays of the windows: the job's runs, their row counts and the three row arrays, each grown at its end
+struct Kept {
+    DevVec runs, cnt, pos, kmer, feat;
+    int64_t NR = 0, NROW = 0;
+    // window V's kept runs and their `nrow` rows behind what is there; `ahead` = what the whole file is expected to hold over what is held now
+    int append(DevMem &m, hipStream_t s, const Win &V, int w, double ahead, const int64_t *pos_off, const PosRec *ps, const int64_t *row_off,
+               int64_t nrow)
+    {
+        const int64_t K = 5 + 2 * w, NF = 3 * (2 * w + 1);
+        const size_t nr = (size_t)(NR + V.keep) + 1, nw = (size_t)(NROW + nrow) + 1;
+        int rc;
+        if ((rc = runs.fit(m, nr * sizeof(RunDev), (size_t)((double)nr * ahead) * sizeof(RunDev), s, "runs")) ||
+            (rc = cnt.fit(m, nr * 8, (size_t)((double)nr * ahead) * 8, s, "rows")) ||
+            (rc = pos.fit(m, nw * 8, (size_t)((double)nw * ahead) * 8, s, "rows")) ||
+            (rc = kmer.fit(m, nw * (size_t)K, (size_t)((double)nw * ahead) * (size_t)K, s, "rows")) ||
+            (rc = feat.fit(m, nw * (size_t)NF * 8, (size_t)((double)nw * ahead) * (size_t)NF * 8, s, "rows")))
+            return rc;
+        if (V.keep) {
+            if (nrow) {
+                window_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.df, V.runs, V.keep, pos_off, ps, w, nullptr, row_off, (int64_t *)pos.p + NROW,
+                                                            kmer.p + NROW * K, (double *)feat.p + NROW * NF);
+                PCHK(hipGetLastError());
+            }
+            keep_runs_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.runs, V.keep, V.b, row_off, (RunDev *)runs.p + NR, (int64_t *)cnt.p + NR);
+            PCHK(hipGetLastError());
+        }
+        PCHK(hipStreamSynchronize(s));
+        NR += V.keep; NROW += nrow;
+        runs.used = (size_t)NR * sizeof(RunDev); cnt.used = (size_t)NR * 8;
+        pos.used = (size_t)NROW * 8; kmer.used = (size_t)(NROW * K); feat.used = (size_t)(NROW * NF) * 8;
+        return M6A_OK;
+    }
+};
+
+int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
+{
+    const int64_t n = F.n;
+    hipStream_t s = S.s[0];
+    int rc;
+    struct Text { uint8_t *p = nullptr; int64_t cap = 0; } text[2];
+    auto text_fit = [&](Text &T, int64_t len) -> int {      // what was in it is gone
+        const int64_t cap = std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes;
+        if (cap <= T.cap) return M6A_OK;
+        if (T.p) m.release(T.p);
+        T.p = nullptr; T.cap = 0;
+        const int e = m.alloc(T.p, (size_t)cap, "a window of the file");
+        if (!e) T.cap = cap;
+        return e;
+    };
+    Arena arena;
+    auto arena_grow = [&]() -> int {
+        PCHK(hipStreamSynchronize(s));
+        if (arena.base) m.release(arena.base);
+        arena.base = nullptr;
+        const size_t cap = std::max(arena.cap * 2, (arena.need + 4095) & ~(size_t)4095);
+        arena.cap = arena.off = 0;
+        const int e = m.alloc(arena.base, cap, "the scratch of a window");
+        if (!e) arena.cap = cap;
+        return e;
+    };
+    arena.need = (size_t)std::min(W, std::max(n, kScanBytes)) * 2;    // newline offsets and line records: about 1.5 bytes per byte of text
+    if ((rc = arena_grow())) return rc;
+    Kept kept;
+    int64_t b = 0, n_windows = 0, w_max = 0;
+    double wait_ms = 0, copy_ms = 0, copied = 0;
+
+    // window 0 arrives before anything can run; from then on window k + 1 arrives under window k's combine and windows
+    {
+        const int64_t len = std::min(W, n);
+        if ((rc = text_fit(text[0], len))) return rc;
+        const double t0 = now_ms();
+        if ((rc = upload_range(device_id, fd.fd, path, S, text[0].p, 0, len, chunk))) return rc;
+        wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)len;
+    }
+    for (int64_t k = 0;; k++) {
+        Text &T = text[k & 1], &T2 = text[(k + 1) & 1];
+        Upload up;                                           // of window k + 1; joined where it goes out of scope
+        bool started = false;
+        int64_t Wk = W;
+        Win V;
+        for (;;) {                                           // until the arena holds the window and the window holds a cut
+            V = Win();
+            V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
+            V.last = b + Wk >= n;
+            V.len = std::min(Wk, n - b);
+            arena.off = 0;
+            m.arena = &arena;
+            rc = window_cut(m, s, path, V, ms);
+            int64_t *pos_off = nullptr, *row_off = nullptr, nrow = 0;
+            PosRec *ps = nullptr;
+            if (!rc && !V.grow) {
+                if (!V.last && !started) {                   // the cut is known: the next window sets out
+                    m.arena = nullptr;
+                    if ((rc = text_fit(T2, std::min(W, n - V.next)))) return rc;
+                    m.arena = &arena;
+                    upload_start(up, device_id, fd.fd, path, S, T2.p, V.next, std::min(W, n - V.next), chunk);
+                    started = true;
+                }
+                const double t1 = now_ms();
+                rc = count_rows(m, s, V.df, V.ev, V.runs, V.keep, w, pos_off, ps, row_off, nrow);
+                ms[2] += now_ms() - t1;
+            }
+            m.arena = nullptr;
+            if (rc == kArenaFull) {
+                if ((rc = arena_grow())) return rc;
+                continue;
+            }
+            if (rc) return rc;
+            if (V.grow) {                                    // twice the window, read again from b
+                Wk *= 2;
+                const int64_t len = std::min(Wk, n - b);
+                PCHK(hipStreamSynchronize(s));
+                if ((rc = text_fit(T, len))) return rc;
+                const double t0 = now_ms();
+                if ((rc = upload_range(device_id, fd.fd, path, S, T.p, b, len, chunk))) return rc;
+                wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)len;
+                continue;
+            }
+            const double t1 = now_ms();
+            // rows per byte so far, carried over the whole file, and 5 % more
+            if ((rc = kept.append(m, s, V, w, (double)n / (double)std::max<int64_t>(V.next, 1) * 1.05, pos_off, ps, row_off, nrow))) return rc;
+            ms[2] += now_ms() - t1;
+            break;
+        }
+        ++n_windows;
+        w_max = std::max(w_max, Wk);
+        if (started) {
+            const double t0 = now_ms();
+            up.wait();
+            wait_ms += now_ms() - t0; copy_ms += up.ms; copied += (double)std::min(W, n - V.next);
+            if (up.rc) { g_prep_err = up.err; return up.rc; }
+        }
+        if (V.last) break;
+        b = V.next;
+    }
+    // the scratch goes before the back half: X needs the room
+    for (Text &T : text)
+        if (T.p) m.release(T.p);
+    m.release(arena.base);
+    // row_off: one exclusive scan of the row counts of all runs
+    const double t1 = now_ms();
+    int64_t total = 0;
+    if ((rc = scan_total(m, (int64_t *)kept.cnt.p, kept.NR, s, total))) return rc;
+    if (total != kept.NROW) return prep_fail(M6A_EHIP, "the windows' rows do not add up");
+    ms[2] += now_ms() - t1;
+    ms[0] = wait_ms;
+    ms[5] = copy_ms > 0 ? copied / (copy_ms * 1e6) : 0;
+    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
+    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p;
+    F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
+    return M6A_OK;
+}
+
 int prep_impl(int device_id, const char *path, int w, const char *index_path, m6a_prep &P)
 {
     if (w < 1 || w > 16) return prep_fail(M6A_EINVAL, "n_neighbors must be 1..16");
@@ -814,7 +1201,9 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
     Streams S;
     Fd fd;
     Front F;
-    int rc = front_half(device_id, path, w, index_path ? &istart : nullptr, index_path ? &iend : nullptr, m, S, fd, F, P.ms);
+    // an index's rows are arbitrary byte ranges, so --skip_index keeps the file resident whatever M6A_PREP_WINDOW_KB says
+    int rc = front_half(device_id, path, w, index_path ? &istart : nullptr, index_path ? &iend : nullptr, index_path ? 0 : window_from_env(),
+                        m, S, fd, F, P.ms);
     if (rc) return rc;
     hipStream_t s = S.s[0];
     const int64_t NR = F.NR, NROW = F.NROW, K = 5 + 2 * w, NF = 3 * (2 * w + 1);
@@ -1365,8 +1754,8 @@ uint32_t Pool::global_tx(const std::string &nm, m6a_prep_sites &P)
 // with >= min_seg reads (the 20-read floor and the per-site checks wait for the pooled sites, pool_impl), their X and read ids stay
 // on the device as a FilePart, and everything else the file needed -- its text, line records, candidate rows -- is released.
 int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
-               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites &P, DevMem &m, double *ms,
-               Pool *pool)
+               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window, m6a_prep_sites &P, DevMem &m,
+               double *ms, Pool *pool)
 {
     const double t_all = now_ms();
     double fms[6] = {0, 0, 0, 0, 0, 0};
@@ -1379,8 +1768,10 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     Streams S;
     Fd fd;
     Front F;
-    int rc = front_half(device_id, path, 1, nullptr, nullptr, m, S, fd, F, fms);
+    int rc = front_half(device_id, path, 1, nullptr, nullptr, window, m, S, fd, F, fms);
     if (rc) return rc;
+    P.info.n_windows += F.n_windows;
+    P.info.window_bytes = std::max(P.info.window_bytes, F.window_bytes);
     ms[0] = fms[0]; ms[1] = fms[1]; ms[2] = fms[2]; ms[6] = fms[5];
     hipStream_t s = S.s[0];
     PCHK(hipStreamSynchronize(s));
@@ -2119,24 +2510,26 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
 }
 
 int sites_multi(int device_id, const char *const *paths, int n_paths, int rmin, int rmax, int min_seg, const char *norm_kmers,
-                const double *norm_mean, const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites &P)
+                const double *norm_mean, const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window,
+                m6a_prep_sites &P)
 {
     if (n_norm < 0 || (n_norm > 0 && (!norm_kmers || !norm_mean || !norm_std))) return prep_fail(M6A_EINVAL, "bad normalisation arguments");
     const double t_all = now_ms();
     g_d2h = 0;
     DevMem m;
-    m.advice = "run `dataprep` and then `inference` instead (the two-step path)";
+    m.advice = "run `dataprep` and then `inference` instead (the two-step path), or let --window_mb parse the file in windows";
+    if (window < 0) window = window_from_env();
     double *ms = P.info.ms;
     int rc;
     if (n_paths == 1) {
-        if ((rc = sites_impl(device_id, paths[0], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, P, m, ms, nullptr)))
+        if ((rc = sites_impl(device_id, paths[0], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, window, P, m, ms, nullptr)))
             return rc;
     } else {
         Pool pool;
         double bytes = 0;
         for (int f = 0; f < n_paths; f++) {
             double fm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if ((rc = sites_impl(device_id, paths[f], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, P, m, fm, &pool)))
+            if ((rc = sites_impl(device_id, paths[f], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, window, P, m, fm, &pool)))
                 return rc;
             for (int k = 0; k < 6; k++) ms[k] += fm[k];
             bytes += fm[6] * fm[0] * 1e6;
@@ -2186,13 +2579,22 @@ extern "C" int m6a_prep_sites_build(int device_id, const char *path, int readcou
                                     const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out)
 {
     if (!path) return prep_fail(M6A_EINVAL, "null argument");
-    return m6a_prep_sites_build_multi(device_id, &path, 1, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std,
-                                      n_norm, host, n_threads, out);
+    return m6a_prep_sites_build_windows(device_id, &path, 1, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std,
+                                        n_norm, host, n_threads, -1, out);
 }
 
 extern "C" int m6a_prep_sites_build_multi(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
                                           int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std,
                                           int n_norm, const m6a_prep_host_half *host, int n_threads, m6a_prep_sites **out)
+{
+    return m6a_prep_sites_build_windows(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean,
+                                        norm_std, n_norm, host, n_threads, -1, out);
+}
+
+extern "C" int m6a_prep_sites_build_windows(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
+                                            int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std,
+                                            int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window_bytes,
+                                            m6a_prep_sites **out)
 {
     if (!paths || !out || n_paths < 1) return prep_fail(M6A_EINVAL, "null argument");
     for (int f = 0; f < n_paths; f++)
@@ -2204,7 +2606,7 @@ extern "C" int m6a_prep_sites_build_multi(int device_id, const char *const *path
     int rc;
     try {
         rc = sites_multi(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm,
-                         host, n_threads, *p);
+                         host, n_threads, window_bytes, *p);
     } catch (const std::bad_alloc &) {
         rc = prep_fail(M6A_ENOMEM, "out of host memory");
     } catch (...) {

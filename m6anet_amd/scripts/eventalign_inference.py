@@ -47,6 +47,11 @@ def cli_parser():
                         help="who formats the rows of the two CSV files: the host's threads from the probabilities copied back, or HIP "
                              "kernels from the arrays in device memory, the text coming back in pinned rounds (about 50 B per read "
                              "cross the link instead of 13).  The bytes are the same; values the kernels decline go through the host.")
+    parser.add_argument("--window_mb", type=int, default=0,
+                        help="parse each eventalign file in windows of this many MB instead of keeping all of it in device memory "
+                             "(0: the whole file, about 3 bytes of device memory per byte of text -- unless M6A_PREP_WINDOW_KB is set, which 0 leaves in force).  With windows the device "
+                             "holds two windows and the candidate rows, so a file larger than device memory goes through; the bytes "
+                             "written are the same.")
     return parser
 
 
@@ -75,6 +80,9 @@ def main(args):
     weights = inference.resolve_model(args)
     device = inference._device_index(args.device)
     csv_on = getattr(args, "csv", "host")    # argparser() alone (no --csv): the host writer
+    window_mb = getattr(args, "window_mb", 0)
+    if window_mb < 0:
+        raise ValueError("--window_mb must be 0 or more, not %d" % window_mb)
     made = {}
 
     def make_engine():                       # the GPU context comes up while the file is parsed
@@ -87,7 +95,8 @@ def main(args):
     starter.start()
     try:
         sites = _io.prep_sites(args.eventalign, args.readcount_min, args.readcount_max, args.min_segment_count,
-                               load_norm_factors(args.norm_path), args.n_processes, device)
+                               load_norm_factors(args.norm_path), args.n_processes, device,
+                               window_kb=window_mb * 1024 if window_mb else None)
     finally:
         starter.join()
     if "error" in made:
@@ -127,8 +136,9 @@ def main(args):
                 ms.update(csv_format=csv["ms_format"], csv_copy=csv["ms_copy"], csv_pwrite=csv["ms_write"])
                 extra = {"csv_writer": "device", "csv_text_bytes": csv["site_bytes"] + csv["indiv_bytes"], "csv_rounds": csv["n_rounds"]}
             print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads, **extra,
-                                                **({"n_replicates": sites.n_replicates, "peak_bytes": sites.peak_bytes}
-                                                   if sites.n_replicates > 1 else {})}), flush=True)
+                                                "n_windows": sites.n_windows, "window_bytes": sites.window_bytes,
+                                                "peak_bytes": sites.peak_bytes,
+                                                **({"n_replicates": sites.n_replicates} if sites.n_replicates > 1 else {})}), flush=True)
     finally:
         sites.close()
         engine.close()

@@ -26,7 +26,17 @@ The two CSV writers of this tree as interleaved legs of the same command (one fi
 medians, the phase table of every leg, and the bar -- the --csv device median below the --csv host median by more than the host legs'
 spread (max - min).  With --parent_tree the default command (one file) against the parent's, the bar of mode (b).  With --copy_rate
 one more --csv device run under `rocprofv3 --kernel-trace --stats`, a run of its own: csv_indiv_kernel's bytes read + written over
-its time next to a device-to-device copy of as many bytes."""
+its time next to a device-to-device copy of as many bytes.
+
+    python tools/measure_eventalign_inference.py --window_mb 0,256,1024,4096 [--shapes 3.1GB,24.3GB] [--legs 5] [--parent_tree DIR]
+                                                 [--budget_mb 16384[,22528]] [--out profiles/r10_eventalign_windows.json]
+
+The one-file command with each --window_mb (0: the whole file, the flag left out) as interleaved legs: medians, the phase table of
+every leg with n_windows and peak_bytes, every windowed leg's CSVs compared with the whole-file leg's, the ratio of each windowed
+median to the whole-file median and the best window.  No bar is set for that ratio.  With --parent_tree the default command against
+the parent's, the bar of mode (b).  With --budget_mb B[,B...], on shapes larger than B: one more leg per B with M6A_PREP_BUDGET_MB=B and
+the window with the lowest peak_bytes -- CSVs compared again, peak_bytes recorded, or the refusal's text: the rows of the whole file must
+still fit -- and the whole-file command under the same budget, which must refuse the file."""
 import filecmp
 import gzip
 import json
@@ -209,6 +219,82 @@ def csv_writers(tag, K, legs, parent, with_copy_rate, ev_dir, limit):
     return res
 
 
+def windows(tag, sizes, legs, parent, budget_mb, ev_dir, limit):
+    path, n = write_shape(tag, ev_dir)
+    res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs, "window_mb": sizes}
+    runs = {mb: [] for mb in sizes}
+    one, par = [], []
+    env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    env.pop("M6A_PREP_WINDOW_KB", None)
+    env.pop("M6A_PREP_BUDGET_MB", None)
+
+    def command(mb, out, env, check=True):
+        cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, out)] + THREADS
+        s, p = timed(cmd + (["--window_mb", str(mb)] if mb else []), limit, env=env)
+        if not check:
+            return s, p
+        must(s, p, "--window_mb %d" % mb)
+        t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+        t["s"] = s
+        return t
+
+    def same(a, b):
+        return all(filecmp.cmp(os.path.join(ev_dir, a, f), os.path.join(ev_dir, b, f), shallow=False) for f in CSVS)
+    try:
+        identical = True
+        for leg in range(legs):
+            for mb in sizes:
+                runs[mb].append(command(mb, "w%d" % mb, env))
+            identical = identical and all(same("w0", "w%d" % mb) for mb in sizes if mb)
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit, env=env), "default command, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, env=env, tree=parent), "default command, parent tree"))
+                res["one_file_csvs_identical"] = same("one", "one_parent")
+            print("%s: leg %d of %d: %s" % (tag, leg + 1, legs, ", ".join("%d MB %.2f s" % (mb, runs[mb][-1]["s"]) for mb in sizes)),
+                  file=sys.stderr, flush=True)
+        res["csvs_identical"] = identical
+        res["csv_bytes"] = [os.path.getsize(os.path.join(ev_dir, "w0", f)) for f in CSVS]
+        for mb in sizes:
+            res["%d" % mb] = {"median_s": median([x["s"] for x in runs[mb]]), "n_windows": runs[mb][-1]["n_windows"],
+                              "peak_bytes": runs[mb][-1]["peak_bytes"], "legs": runs[mb]}
+        whole = res["0"]["median_s"]
+        ws = [x["s"] for x in runs[0]]
+        res["whole_file_spread_s"] = max(ws) - min(ws)
+        res["windowed_over_whole_file_time"] = {"%d" % mb: res["%d" % mb]["median_s"] / whole for mb in sizes if mb}
+        best = min((mb for mb in sizes if mb), key=lambda mb: res["%d" % mb]["median_s"])
+        res["best_window_mb"] = best
+        if parent:
+            res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                                      "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                                      "within_bar": median(one) <= median(par) + max(par) - min(par)}
+        lean = min((mb for mb in sizes if mb), key=lambda mb: res["%d" % mb]["peak_bytes"])
+        res["under_budget"] = []
+        for mb in budget_mb:
+            if os.path.getsize(path) <= mb << 20:          # only a file larger than the memory allowed
+                continue
+            tight = dict(env, M6A_PREP_BUDGET_MB=str(mb))
+            s, p = command(lean, "tight", tight, check=False)
+            leg = {"budget_mb": mb, "window_mb": lean, "s": s}
+            if p.returncode != 0:                          # the rows of the whole file must still fit: a finding, not a failed step
+                leg["refused"] = p.stderr.strip().splitlines()[-1][-400:]
+            else:
+                t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+                leg.update(peak_bytes=t["peak_bytes"], n_windows=t["n_windows"], ms=t["ms"], csvs_identical=same("w0", "tight"),
+                           peak_under_budget=t["peak_bytes"] <= mb << 20)
+            s, p = command(0, "tight_whole", tight, check=False)
+            leg["whole_file_refused"] = p.returncode != 0 and "two-step path" in p.stderr
+            res["under_budget"].append(leg)
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+        res["legs_done"] = {"%d" % mb: v for mb, v in runs.items()}
+    for d in ["w%d" % mb for mb in sizes] + ["one", "one_parent", "tight", "tight_whole"]:
+        subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+    os.remove(path)
+    return res
+
+
 def replicates(tag, K, legs, parent, with_copy_rate, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "replicates": K, "legs": legs}
@@ -286,6 +372,27 @@ def main():
     dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r07_eventalign_inference.json")
     limit = int(sys.argv[sys.argv.index("--timeout") + 1]) if "--timeout" in sys.argv else 900
     res = {}
+    if "--window_mb" in sys.argv:
+        sizes = [int(x) for x in sys.argv[sys.argv.index("--window_mb") + 1].split(",")]
+        if 0 not in sizes or len(sizes) < 2 or min(sizes) < 0:
+            raise SystemExit("--window_mb 0,N[,N...]: windows are measured against the whole file")
+        shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB", "24.3GB"]
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r10_eventalign_windows.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        budget = [int(x) for x in sys.argv[sys.argv.index("--budget_mb") + 1].split(",")] if "--budget_mb" in sys.argv else []
+        if os.path.exists(dest):                            # one shape per call is allowed: the shapes share the file
+            res = json.load(open(dest))
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                res[tag] = windows(tag, sorted(sizes), legs, parent, budget, d, limit)
+                print(json.dumps({tag: res[tag]}), flush=True)
+                os.makedirs(os.path.dirname(dest), exist_ok=True)
+                with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured
+                    json.dump(res, f, indent=1)
+                if "failed" in res[tag]:
+                    break                                   # a failed step: nothing more is started
+        return
     if "--csv" in sys.argv:
         if sorted(sys.argv[sys.argv.index("--csv") + 1].split(",")) != ["device", "host"]:
             raise SystemExit("--csv host,device: both writers are measured against each other")

@@ -426,6 +426,8 @@ typedef struct m6a_prep_sites_info {
     const int32_t *read_rep;        /* [R] replicate of each read */
     int64_t peak_bytes;
     int64_t n_windows, window_bytes;
+    int64_t n_bgzf_blocks, compressed_bytes;    /* BGZF inputs (below): blocks and file bytes, summed over the files; 0 for plain text */
+    double ms_inflate;                          /* their inflate and CRC kernels and the newline count over the inflated text */
 } m6a_prep_sites_info;
 int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
                          const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
@@ -489,6 +491,48 @@ int m6a_csv_format(int device_id, const m6a_csv_arrays *a, int64_t site_begin, i
                    char *indiv_text, int64_t indiv_cap, int64_t *site_bytes, int64_t *indiv_bytes, int64_t *n_declined);
 int m6a_prep_sites_write_csv(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
                              m6a_csv_stats *stats);
+
+/* BGZF input (htslib's bgzip; SAM specification section 4.1).  m6a_prep_sites_build, _multi and _windows take a file of either kind,
+ * and replicates may mix them; tests/bgzf_statement.py states the same in plain Python.
+ *   detection    by content, never by name: a file whose first bytes are not 1f 8b is text and takes the path above untouched.  A file
+ *                that starts 1f 8b but whose first member does not meet the header rules is refused, M6A_EFORMAT, with a text that says
+ *                it is gzip but not BGZF and names `bgzip`.
+ *   header       1f 8b 08 04, MTIME (4), XFL, OS, XLEN (2), then XLEN bytes of extra subfields SI1 SI2 SLEN (2) data, walked in order;
+ *                the first with SI1 = 'B', SI2 = 'C', SLEN = 2 holds BSIZE = the block's total size - 1; others may stand before or
+ *                after it.  The subfields must fill XLEN exactly and the block must have room for its footer.
+ *   body         one raw DEFLATE stream (RFC 1951) of any number of stored, fixed and dynamic deflate blocks, then CRC32 (4) and
+ *                ISIZE (4) <= 65536.  Blocks are independent: a distance never reaches before the first byte of its own block's
+ *                output.  Empty blocks (ISIZE 0, such as the 28-byte end-of-file marker) may stand anywhere; a file without the
+ *                marker is accepted, as htslib accepts it.
+ *   text         the concatenation of the blocks' outputs; every byte offset in messages, runs and errors is an offset in it.
+ *   errors       a bad header; a BSIZE that runs past the end of the file; ISIZE over 65536; deflate block type 3; a stored LEN/NLEN
+ *                mismatch; a code-length set zlib refuses (over-subscribed; incomplete unless it is one code of one bit, never for the
+ *                code-length code; no end-of-block code; more than 286 / 30 symbols; a repeat without a length before it or past the
+ *                end); literal/length symbols 286-287, distance symbols 30-31 and codes no symbol has; a distance larger than the
+ *                bytes produced so far in this block; output beyond ISIZE; input exhausted before the end-of-block code; a stream that
+ *                does not end exactly at the footer; a length that is not ISIZE; a CRC-32 mismatch.  The first bad block in file
+ *                order is reported, M6A_EFORMAT, `<path>: BGZF block at byte <file offset of the block>: <reason>`; nothing is
+ *                parsed and no output file is touched.
+ * The compressed bytes go up through the pinned chunks while the host walks the chain in them (BSIZE gives the next block), the text
+ * buffer is allocated at the sum of ISIZE, one kernel inflates every block to its place and a second checks its CRC-32
+ * (m6anet_amd/csrc/m6a_bgzf.h); one 8-byte status comes back, not a byte per block.  The compressed buffer counts against the budget
+ * while it lives and is released before the line records are allocated.  What the host reads by path from a text file -- contig
+ * names, the byte ranges of declined runs -- comes from the inflated text on the device in one gathered copy each (counted in
+ * d2h_bytes); the host half gets the declined runs laid end to end in a temporary file, with offsets to match, which is removed.
+ * Refused: windows over a BGZF file (window_bytes > 0 or M6A_PREP_WINDOW_KB > 0), M6A_EINVAL -- the file must fit resident; and
+ * m6a_prep_eventalign on a BGZF file, M6A_EFORMAT naming eventalign_inference -- its eventalign.index would hold offsets into a
+ * file that does not exist.
+ *
+ * m6a_bgzf_inflate: the text of a BGZF file, inflated on device device_id, into text[0, cap); *n_bytes is its length.  text == NULL
+ * is the sizing call (the chain is walked on the host; nothing is uploaded).  Needs no weights and no m6a_ctx.  stats (may be NULL):
+ * blocks, file bytes, the upload, the inflate kernel, the CRC kernel, the copy of the text to the host in ms, and d2h_bytes.  Errors
+ * as the m6a_prep_* family, text in m6a_prep_last_error(). */
+typedef struct m6a_bgzf_stats {
+    int64_t n_blocks, compressed_bytes;
+    double ms_upload, ms_inflate, ms_crc, ms_copy;
+    int64_t d2h_bytes;
+} m6a_bgzf_stats;
+int m6a_bgzf_inflate(int device_id, const char *path, char *text, int64_t cap, int64_t *n_bytes, m6a_bgzf_stats *stats);
 
 #ifdef __cplusplus
 }

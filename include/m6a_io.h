@@ -185,6 +185,13 @@ void m6a_io_rows_free(m6a_io_rows *r);
 int m6a_io_dataprep_write(const char *eventalign_path, const char *out_dir, const m6a_io_prep_table *table, int n_threads,
                           int readcount_min, int readcount_max, int min_segment_count, int compress, int write_index);
 
+/* A BGZF file (include/m6a.h states the format) inflated on the host by the decode core the HIP kernels compile
+ * (m6anet_amd/csrc/m6a_bgzf.h): the text of all blocks into text[0, cap), its length in *n_bytes.  text == NULL is the sizing call:
+ * *n_bytes is the sum of ISIZE over the chain as far as its headers can be walked, and nothing is inflated.  M6A_IO_EFORMAT with
+ * `<path>: BGZF block at byte <offset>: <reason>` for the first bad block in file order (a bad header counts where it stands), with
+ * its own text for a file that is not gzip, or is gzip but not BGZF. */
+int m6a_io_bgzf_inflate(const char *path, char *text, int64_t cap, int64_t *n_bytes);
+
 #ifdef __cplusplus
 }
 #endif

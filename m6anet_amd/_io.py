@@ -10,7 +10,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep"]
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate"]
 _lib = None
 
 
@@ -92,6 +92,7 @@ def load():
     L.m6a_io_runs_rows.argtypes = [C.c_char_p, i64, vp, vp, vp, i32, i32, C.POINTER(vp)]
     L.m6a_io_sites_from_arrays.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, C.POINTER(vp)]
     L.m6a_io_sites_from_arrays_rep.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, vp, i32, C.POINTER(vp)]
+    L.m6a_io_bgzf_inflate.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     _lib = L
     return L
 
@@ -183,6 +184,41 @@ class prep_on_device:
         self._h = None
 
 
+def is_bgzf(path):
+    """True when the file's first bytes are a BGZF block header (by content, never by name); `eventalign_inference` inflates such a
+    file on the device."""
+    from . import bgzf
+    return bgzf.is_bgzf(path)
+
+
+def bgzf_inflate_host(path):
+    """m6a_io_bgzf_inflate: the text of a BGZF file, inflated on the host by the decode core the HIP kernels compile.  M6AIOError
+    (EFORMAT) names the first bad block in file order: `<path>: BGZF block at byte <offset>: <reason>`."""
+    L, n = load(), C.c_int64()
+    _chk(L.m6a_io_bgzf_inflate(os.fsencode(path), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(1, n.value))
+    _chk(L.m6a_io_bgzf_inflate(os.fsencode(path), buf, n.value, C.byref(n)))
+    return buf.raw[:n.value]
+
+
+def bgzf_inflate(path, device_id=0, stats=None):
+    """m6a_bgzf_inflate (libm6a_hip.so): the text of a BGZF file, inflated and CRC-checked by the HIP kernels.  Errors as
+    bgzf_inflate_host's.  `stats`: a dict that receives the m6a_bgzf_stats fields."""
+    from . import _lib
+    L, n, st = _lib.load(), C.c_int64(), _lib.BgzfStats()
+
+    def call(buf, cap):
+        rc = L.m6a_bgzf_inflate(int(device_id), os.fsencode(path), buf, cap, C.byref(n), C.byref(st))
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), prep_on_device._CODES.get(rc, rc))
+    call(None, 0)
+    buf = C.create_string_buffer(max(1, n.value))
+    call(buf, n.value)
+    if stats is not None:
+        stats.update({k: getattr(st, k) for k, _ in st._fields_})
+    return buf.raw[:n.value]
+
+
 def norm_arrays(norm):
     """Normalisation factors (dict kmer -> (mean[3], std[3]), or None) in m6a_io_load_sites' form: (kmers blob, mean, std, n)."""
     if not norm:
@@ -199,7 +235,9 @@ class prep_sites:
     pools several input directories; a list of one is a list -- `<id>_0`).  `info` is the m6a_prep_sites_info; host copies are numpy
     arrays (off, site_tx, tx_pos, kmer7, read_ids, read_rep) and `names` (per transcript); n_replicates and peak_bytes as reported.
     window_kb: parse each file in windows of that many KB instead of keeping it resident (m6a_prep_sites_build_windows; the arrays
-    are the same), 0 for resident, None for what M6A_PREP_WINDOW_KB says; n_windows and window_bytes say what was done.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
+    are the same), 0 for resident, None for what M6A_PREP_WINDOW_KB says; n_windows and window_bytes say what was done.  A file that
+    is BGZF (by content) is inflated on the device and gives the arrays of its text; n_bgzf_blocks, compressed_bytes and ms_inflate
+    say so (0 for plain files), and windows over such a file are refused.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
     _CODES = prep_on_device._CODES
 
     def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0,
@@ -237,6 +275,7 @@ class prep_sites:
         self.read_rep = arr(i.read_rep, C.c_int32, R)
         self.n_replicates, self.peak_bytes = int(i.n_rep), int(i.peak_bytes)
         self.n_windows, self.window_bytes = int(i.n_windows), int(i.window_bytes)
+        self.n_bgzf_blocks, self.compressed_bytes, self.ms_inflate = int(i.n_bgzf_blocks), int(i.compressed_bytes), float(i.ms_inflate)
         tx_off = arr(i.tx_off, C.c_int64, T + 1)
         self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
         self.tx_off = tx_off

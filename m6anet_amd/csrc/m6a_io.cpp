@@ -2211,3 +2211,56 @@ extern "C" int m6a_io_dataprep_write(const char *eventalign_path, const char *ou
         return fail(M6A_IO_EIO, "dataprep: unexpected exception");
     }
 }
+
+// ---- BGZF on the host: the decode core of m6a_bgzf.h (the one the HIP kernels compile), block after block -----------------------
+#include "m6a_bgzf.h"
+
+extern "C" int m6a_io_bgzf_inflate(const char *path, char *text, int64_t cap, int64_t *n_bytes)
+{
+    if (!path || !n_bytes) return fail(M6A_IO_EINVAL, "null argument");
+    *n_bytes = 0;
+    try {
+        FILE *f = fopen(path, "rb");
+        if (!f) return fail(M6A_IO_EIO, "cannot open %s", path);
+        std::vector<uint8_t> d;
+        uint8_t buf[1 << 16];
+        for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) d.insert(d.end(), buf, buf + k);
+        fclose(f);
+        if (d.size() < 2 || d[0] != 0x1f || d[1] != 0x8b) return fail(M6A_IO_EFORMAT, "%s is not a gzip file", path);
+        struct Blk { int64_t at; int32_t hdr, total, isize; uint32_t crc; };
+        std::vector<Blk> blocks;
+        int64_t total = 0;
+        auto on_block = [&](int64_t off, int32_t hdr, int32_t tot, uint32_t crc, int32_t isize) {
+            blocks.push_back(Blk{off, hdr, tot, isize, crc});
+            total += isize;
+        };
+        std::unique_ptr<m6a_bgzf::Walker<decltype(on_block)>> W(new m6a_bgzf::Walker<decltype(on_block)>(on_block));
+        W->feed(d.data(), (int64_t)d.size());
+        W->finish();
+        if (W->bad && W->bad_at == 0 && W->bad == m6a_bgzf::BR_HEADER)
+            return fail(M6A_IO_EFORMAT, "%s is gzip but not BGZF: its first member has no BGZF header (compress it with `bgzip`, or "
+                                        "`python -m m6anet_amd bgzip`)", path);
+        *n_bytes = total;
+        if (!text) return M6A_IO_OK;                        // the sizing call: the blocks of the chain as far as it can be walked
+        if (cap < total) return fail(M6A_IO_EINVAL, "the text needs %lld bytes, the buffer holds %lld", (long long)total, (long long)cap);
+        uint32_t tab[256];
+        for (uint32_t i = 0; i < 256; i++) tab[i] = m6a_bgzf::crc_entry(i);
+        std::unique_ptr<m6a_bgzf::Tables> T(new m6a_bgzf::Tables);
+        int64_t at = 0;
+        for (const Blk &b : blocks) {
+            m6a_bgzf::HostOut o{(uint8_t *)text + at};
+            int r = m6a_bgzf::inflate(d.data() + b.at + b.hdr, b.total - b.hdr - 8, o, b.isize, *T);
+            if (!r) {                                       // the CRC as the kernel forms it: 64 parts, each advanced to the end
+                uint32_t c = 0;
+                for (int lane = 0; lane < 64; lane++) c ^= m6a_bgzf::crc_lane(tab, (const uint8_t *)text + at, b.isize, lane);
+                if (c != b.crc) r = m6a_bgzf::BR_CRC;
+            }
+            if (r) return fail(M6A_IO_EFORMAT, "%s: BGZF block at byte %lld: %s", path, (long long)b.at, m6a_bgzf::reason_text(r));
+            at += b.isize;
+        }
+        if (W->bad) return fail(M6A_IO_EFORMAT, "%s: BGZF block at byte %lld: %s", path, (long long)W->bad_at, m6a_bgzf::reason_text(W->bad));
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "bgzf: out of memory");
+    }
+}

@@ -32,6 +32,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -710,7 +711,18 @@ struct Front {
     uint8_t *row_kmer = nullptr;
     double *row_feat = nullptr;
     std::vector<const void *> scratch;      // the file, its newlines, lines and combined positions: nothing after the windows reads them
+    bool bgzf_ok = false;                   // in: the caller takes BGZF input (sites_impl)
+    const uint8_t *text = nullptr;          // out, BGZF input: the inflated text, NOT in scratch -- the caller reads names and runs from it
+    int64_t n_blocks = 0, comp_bytes = 0;   // out, BGZF input
+    double ms_inflate = 0;
 };
+
+// m6a_bgzf.h, included at the end of this file
+struct BgzfUp;
+bool bgzf_is_gzip(int fd, int64_t n);
+int bgzf_front(const char *path, int fd, int64_t n_file, DevMem &m, Streams &S, int64_t chunk, uint8_t *&text, int64_t &n_text, Front &F, double *ms);
+int bgzf_gather(DevMem &m, hipStream_t s, const uint8_t *text, int64_t n_text, const std::vector<int64_t> &src, const std::vector<int64_t> &len,
+                std::vector<uint8_t> &out);
 
 int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
 
@@ -735,7 +747,14 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     if (fd.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", path);
     struct stat st;
     if (fstat(fd.fd, &st) != 0) return prep_fail(M6A_EIO, "cannot stat %s", path);
-    const int64_t n = (int64_t)st.st_size;
+    int64_t n = (int64_t)st.st_size;
+    const bool gz = bgzf_is_gzip(fd.fd, n);              // by content: 1f 8b.  Text takes the path below untouched.
+    if (gz && !F.bgzf_ok)
+        return prep_fail(M6A_EFORMAT, "%s is gzip-compressed: `dataprep --device gpu` writes an eventalign.index of offsets into the text, "
+                         "which is not there; `eventalign_inference` reads BGZF directly", path);
+    if (gz && !index_path && window > 0)
+        return prep_fail(M6A_EINVAL, "%s: windows over compressed input are not implemented (--window_mb, M6A_PREP_WINDOW_KB); a BGZF file "
+                         "must fit resident: run it without a window", path);
     F.n = n;
     if (!m.budget_set) {
         m.budget_set = true;
@@ -746,12 +765,12 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         const char *b = getenv("M6A_PREP_BUDGET_MB");
         if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
     }
-    const int64_t nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);       // 4 KB scan blocks; the buffer is padded to them
+    int64_t nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);       // 4 KB scan blocks; the buffer is padded to them
     const int64_t W = index_path || window <= 0 ? 0 : (window + kScanBytes - 1) / kScanBytes * kScanBytes;
     uint8_t *df = nullptr;
     int64_t *bcnt = nullptr;
     int rc = M6A_OK;
-    if (!W) {
+    if (!W && !gz) {
         rc = m.alloc(df, (size_t)(nb * kScanBytes), "the file");
         if (!rc) rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts");
         if (rc) return rc;
@@ -768,11 +787,22 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     chunk = std::min<int64_t>(chunk, W ? W : nb * kScanBytes);
     for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&S.pin[i], (size_t)chunk, hipHostMallocDefault));
     if (W) return front_windows(device_id, path, w, W, chunk, m, S, fd, F, ms);
-    PCHK(hipMemsetAsync(df + (nb - 1) * kScanBytes, 0, (size_t)kScanBytes, S.s[1]));        // the zero padding of the last block
+    if (gz) {                                                // the compressed bytes go up, the text is inflated where the upload would have put it
+        if ((rc = bgzf_front(path, fd.fd, n, m, S, chunk, df, n, F, ms))) return rc;
+        F.n = n;
+        nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);
+        const double t_nl = now_ms();
+        if ((rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts"))) return rc;
+        nl_count_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)df, 0, bcnt);
+        PCHK(hipGetLastError());
+        PCHK(hipStreamSynchronize(s));
+        F.ms_inflate += now_ms() - t_nl;
+    } else
+        PCHK(hipMemsetAsync(df + (nb - 1) * kScanBytes, 0, (size_t)kScanBytes, S.s[1]));        // the zero padding of the last block
 
     // ---- upload: pread chunk k into one pinned buffer while chunk k - 1 is copied and counted
     const double t_up = now_ms();
-    for (int64_t k = 0, off = 0; off < n; k++, off += chunk) {
+    for (int64_t k = 0, off = 0; !gz && off < n; k++, off += chunk) {
         const int slot = (int)(k & 1);
         PCHK(hipEventSynchronize(S.copied[slot]));          // the copy that last used this buffer is done
         const int64_t len = std::min(chunk, n - off);
@@ -792,8 +822,10 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     if (n == 0) PCHK(hipMemsetAsync(bcnt, 0, sizeof(int64_t), s));
     PCHK(hipStreamSynchronize(S.s[1]));
     PCHK(hipStreamSynchronize(s));
-    ms[0] = now_ms() - t_up;
-    ms[5] = ms[0] > 0 ? (double)n / (ms[0] * 1e6) : 0;
+    if (!gz) {
+        ms[0] = now_ms() - t_up;
+        ms[5] = ms[0] > 0 ? (double)n / (ms[0] * 1e6) : 0;
+    }
 
     // ---- newline offsets
     double t1 = now_ms();
@@ -861,7 +893,9 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     PCHK(hipStreamSynchronize(s));
     ms[2] = now_ms() - t1;
     F.NR = NR; F.NROW = NROW; F.runs = runs; F.row_off = row_off; F.row_pos = drow_pos; F.row_kmer = drow_kmer; F.row_feat = drow_feat;
-    F.scratch.insert(F.scratch.end(), {df, bcnt, nl, ev, bad, pos_off, ps});
+    F.scratch.insert(F.scratch.end(), {bcnt, nl, ev, bad, pos_off, ps});
+    if (gz) F.text = df;
+    else F.scratch.push_back(df);
     return M6A_OK;
 }
 
@@ -1768,8 +1802,12 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     Streams S;
     Fd fd;
     Front F;
+    F.bgzf_ok = true;
     int rc = front_half(device_id, path, 1, nullptr, nullptr, window, m, S, fd, F, fms);
     if (rc) return rc;
+    P.info.n_bgzf_blocks += F.n_blocks;
+    P.info.compressed_bytes += F.comp_bytes;
+    P.info.ms_inflate += F.ms_inflate;
     P.info.n_windows += F.n_windows;
     P.info.window_bytes = std::max(P.info.window_bytes, F.window_bytes);
     ms[0] = fms[0]; ms[1] = fms[1]; ms[2] = fms[2]; ms[6] = fms[5];
@@ -1807,10 +1845,20 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     std::vector<SegUp> up((size_t)NSEG);
     std::vector<int64_t> tx_runs;
     std::string nm;
-    for (int64_t g = 0; g < NSEG; g++) {
+    std::vector<uint8_t> packed;                            // BGZF input: the contig bytes of all segments, from the text on the device
+    if (F.text) {
+        std::vector<int64_t> src((size_t)NSEG), len((size_t)NSEG);
+        for (int64_t g = 0; g < NSEG; g++) { src[(size_t)g] = hseg[(size_t)g].contig; len[(size_t)g] = hseg[(size_t)g].len; }
+        if ((rc = bgzf_gather(m, s, F.text, F.n, src, len, packed))) return rc;
+    }
+    for (int64_t g = 0, at = 0; g < NSEG; g++) {
         const SegDev &G = hseg[(size_t)g];
         nm.resize((size_t)G.len);
-        for (int64_t got = 0; got < G.len;) {
+        if (F.text) {
+            memcpy(&nm[0], packed.data() + at, (size_t)G.len);
+            at += G.len;
+        }
+        for (int64_t got = 0; !F.text && got < G.len;) {
             const ssize_t k = ::pread(fd.fd, &nm[(size_t)got], (size_t)(G.len - got), (off_t)(G.contig + got));
             if (k < 0 && errno == EINTR) continue;
             if (k <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
@@ -1850,7 +1898,27 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         if (!host || !host->rows || !host->table || !host->free)
             return prep_fail(M6A_EINVAL, "%zu runs need the host half and none was given", crun.size());
         struct m6a_io_rows *hr = nullptr;
-        const int hrc = host->rows(path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, n_threads, &hr);
+        // BGZF input: the host half takes a path, so it gets the declined runs laid end to end in a plain temporary file
+        struct Tmp { std::string path; ~Tmp() { if (!path.empty()) ::unlink(path.c_str()); } } tmp;
+        if (F.text) {
+            std::vector<int64_t> len(crun.size());
+            for (size_t i = 0; i < crun.size(); i++) len[i] = cend[i] - cstart[i];
+            if ((rc = bgzf_gather(m, s, F.text, F.n, cstart, len, packed))) return rc;
+            const char *dir = getenv("TMPDIR");
+            std::string name = std::string(dir && *dir ? dir : "/tmp") + "/m6a_declined_XXXXXX";
+            const int tfd = ::mkstemp(&name[0]);
+            if (tfd < 0) return prep_fail(M6A_EIO, "cannot create a temporary file for the declined runs of %s", path);
+            tmp.path = name;
+            for (size_t got = 0; got < packed.size();) {
+                const ssize_t k = ::write(tfd, packed.data() + got, packed.size() - got);
+                if (k < 0 && errno == EINTR) continue;
+                if (k <= 0) { ::close(tfd); return prep_fail(M6A_EIO, "cannot write %s", name.c_str()); }
+                got += (size_t)k;
+            }
+            ::close(tfd);
+            for (size_t i = 0, at = 0; i < crun.size(); i++) { cstart[i] = (int64_t)at; at += (size_t)len[i]; cend[i] = (int64_t)at; }
+        }
+        const int hrc = host->rows(F.text ? tmp.path.c_str() : path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, n_threads, &hr);
         if (hrc != 0 || !hr) {                              // its own code and text (m6a_io's -1..-4 -> M6A_EINVAL, ENOMEM, EIO, EFORMAT)
             const int code = hrc == -2 ? M6A_ENOMEM : hrc == -3 ? M6A_EIO : hrc == -4 ? M6A_EFORMAT : hrc == -1 ? M6A_EINVAL : M6A_EIO;
             return prep_fail(code, "%s", host->error ? host->error() : "the host half failed on the declined runs");
@@ -1873,6 +1941,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
             }
         }
     }
+    if (F.text) m.release(F.text);                          // names and declined runs are on the host: X needs the room
     const int64_t NH = (int64_t)hpos.size(), NT = (int64_t)tx_runs.size();
     if (NROW + NH > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate rows");
     host_ms += now_ms() - t1;
@@ -2648,4 +2717,6 @@ extern "C" int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_
 
 extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }
 
+#define M6A_BGZF_DEVICE_PART
+#include "m6a_bgzf.h"
 #include "m6a_csv.h"

@@ -31,7 +31,8 @@ class OneOrSeveral(Action):
 def argparser():
     parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter, add_help=False)
     parser.add_argument("--eventalign", required=True, nargs="+", action=OneOrSeveral,
-                        help="eventalign filepath, the output from nanopolish.  Several files are replicates: their sites are pooled "
+                        help="eventalign filepath, the output from nanopolish; plain text or BGZF (bgzip) -- told apart by content, "
+                             "inflated on the device, and replicates may mix the two.  Several files are replicates: their sites are pooled "
                              "as `inference` pools several --input_dir (a site is kept when its reads summed over the files reach 20), "
                              "and read ids are written <id>_<position of the file>.")
     parser.add_argument("--out_dir", required=True, help="directory to output inference results.")
@@ -137,7 +138,8 @@ def main(args):
                 extra = {"csv_writer": "device", "csv_text_bytes": csv["site_bytes"] + csv["indiv_bytes"], "csv_rounds": csv["n_rounds"]}
             print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads, **extra,
                                                 "n_windows": sites.n_windows, "window_bytes": sites.window_bytes,
-                                                "peak_bytes": sites.peak_bytes,
+                                                "peak_bytes": sites.peak_bytes, "inflate": sites.ms_inflate,
+                                                "compressed_bytes": sites.compressed_bytes, "n_bgzf_blocks": sites.n_bgzf_blocks,
                                                 **({"n_replicates": sites.n_replicates} if sites.n_replicates > 1 else {})}), flush=True)
     finally:
         sites.close()

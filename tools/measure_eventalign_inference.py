@@ -36,7 +36,16 @@ every leg with n_windows and peak_bytes, every windowed leg's CSVs compared with
 median to the whole-file median and the best window.  No bar is set for that ratio.  With --parent_tree the default command against
 the parent's, the bar of mode (b).  With --budget_mb B[,B...], on shapes larger than B: one more leg per B with M6A_PREP_BUDGET_MB=B and
 the window with the lowest peak_bytes -- CSVs compared again, peak_bytes recorded, or the refusal's text: the rows of the whole file must
-still fit -- and the whole-file command under the same budget, which must refuse the file."""
+still fit -- and the whole-file command under the same budget, which must refuse the file.
+
+    python tools/measure_eventalign_inference.py --bgzf [--shapes 3.1GB,24.3GB] [--legs 5] [--parent_tree DIR]
+                                                 [--out profiles/r11_eventalign_bgzf.json]
+
+The shape's file and its BGZF twin (m6anet_amd/bgzf.py, level 6, 16 processes) as interleaved legs of the one-file command: medians,
+the phase table of every leg (upload wait, inflate + CRC ms, peak_bytes), the compression ratio of this GENERATED text, the inflate
+rate in GB/s of text produced beside the link's upload rate from the same legs, and the CSVs of the two inputs compared.  The
+compressed leg carries no bar.  With --parent_tree the default command on the plain file against the parent's, the bar of mode (b).
+Both files are read from a warm page cache; a cold read from disk, which is what compressed input is for, is not measured here."""
 import filecmp
 import gzip
 import json
@@ -295,6 +304,60 @@ def windows(tag, sizes, legs, parent, budget_mb, ev_dir, limit):
     return res
 
 
+def bgzf_legs(tag, legs, parent, ev_dir, limit):
+    sys.path.insert(0, REPO)
+    from m6anet_amd import bgzf
+    path, n = write_shape(tag, ev_dir)
+    t0 = time.perf_counter()
+    n_in, n_out = bgzf.compress_file(path, level=6, n_processes=16)
+    gz = path + ".gz"
+    subprocess.run(["cat", gz], stdout=subprocess.DEVNULL, check=True)             # page-cache warm, like the text
+    res = {"copies": n, "eventalign_GB": n_in / 1e9, "compressed_GB": n_out / 1e9, "compression_ratio_of_generated_text": n_in / n_out,
+           "compress_s": time.perf_counter() - t0, "legs": legs, "cold_cache_read": "not measured"}
+    runs = {"plain": [], "bgzf": []}
+    one, par = [], []
+    env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    env.pop("M6A_PREP_WINDOW_KB", None)
+    try:
+        for leg in range(legs):
+            for mode, src in (("plain", path), ("bgzf", gz)):
+                s, p = timed(["eventalign_inference", "--eventalign", src, "--out_dir", os.path.join(ev_dir, mode)] + THREADS, limit, env=env)
+                must(s, p, mode)
+                t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+                t["s"] = s
+                runs[mode].append(t)
+            res["csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "plain", f), os.path.join(ev_dir, "bgzf", f), shallow=False) for f in CSVS)
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit), "default command, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, tree=parent), "default command, parent tree"))
+                res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
+                                                                 shallow=False) for f in CSVS)
+            for d in ("plain", "bgzf", "one", "one_parent"):
+                subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+            print("%s: leg %d of %d: plain %.2f s, bgzf %.2f s" % (tag, leg + 1, legs, runs["plain"][-1]["s"], runs["bgzf"][-1]["s"]),
+                  file=sys.stderr, flush=True)
+        for mode in runs:
+            v = runs[mode]
+            res[mode] = {"median_s": median([x["s"] for x in v]), "upload_wait_ms": median([x["ms"]["upload"] for x in v]),
+                         "upload_GBps": median([x["ms"]["upload_GBps"] for x in v]), "inflate_and_crc_ms": median([x["inflate"] for x in v]),
+                         "peak_bytes": v[-1]["peak_bytes"], "legs": v}
+        res["bgzf"]["inflate_GBps_of_text"] = n_in / (res["bgzf"]["inflate_and_crc_ms"] * 1e6) if res["bgzf"]["inflate_and_crc_ms"] else None
+        res["bgzf"]["n_bgzf_blocks"] = runs["bgzf"][-1]["n_bgzf_blocks"]
+        res["bgzf_over_plain_time"] = res["bgzf"]["median_s"] / res["plain"]["median_s"]
+        if parent:
+            res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                                      "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                                      "within_bar": median(one) <= median(par) + max(par) - min(par)}
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+        res["legs_done"] = runs
+    os.remove(path)
+    os.remove(gz)
+    return res
+
+
 def replicates(tag, K, legs, parent, with_copy_rate, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "replicates": K, "legs": legs}
@@ -372,6 +435,23 @@ def main():
     dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r07_eventalign_inference.json")
     limit = int(sys.argv[sys.argv.index("--timeout") + 1]) if "--timeout" in sys.argv else 900
     res = {}
+    if "--bgzf" in sys.argv:
+        shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB", "24.3GB"]
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r11_eventalign_bgzf.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        if os.path.exists(dest):                            # one shape per call is allowed: the shapes share the file
+            res = json.load(open(dest))
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                res[tag] = bgzf_legs(tag, legs, parent, d, limit)
+                print(json.dumps({tag: res[tag]}), flush=True)
+                os.makedirs(os.path.dirname(dest), exist_ok=True)
+                with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured
+                    json.dump(res, f, indent=1)
+                if "failed" in res[tag]:
+                    break                                   # a failed step: nothing more is started
+        return
     if "--window_mb" in sys.argv:
         sizes = [int(x) for x in sys.argv[sys.argv.index("--window_mb") + 1].split(",")]
         if 0 not in sizes or len(sizes) < 2 or min(sizes) < 0:

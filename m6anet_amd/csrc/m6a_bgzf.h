@@ -5,7 +5,10 @@
 // tests/bgzf_statement.py, malformed files included, under the sanitizers); m6a_prep.hip compiles the same text for gfx950.
 // The three bounds hold by construction: every read of a block's input is `pos < n` checked in fill (past the end it reads zeros,
 // and consuming one of those sets `over`), every write is checked against ISIZE before it happens, every distance against the bytes produced so far.  A
-// malformed block is a reason code, never an out-of-range access.
+// malformed block is a reason code, never an out-of-range access.  The core is held to zlib in tests/test_bgzf_generated.py: on streams
+// that tests/deflate_gen.py writes to cover RFC 1951 and on thousands of damaged ones, through m6a_io_bgzf_inflate and through
+// tests/bgzf_core_main.cpp, a program of its own under ASan and UBSan that also feeds Walker in pieces of every size; the kernels
+// see the same bytes in tests/test_gpu_bgzf_generated.py.
 //
 // Part 2 (M6A_BGZF_DEVICE_PART, m6a_prep.hip only): the kernels and the upload.
 //   layout      one wave per BGZF block, four waves per workgroup.  The Huffman tables of a wave are 1.4 KB of LDS (canonical counts

@@ -63,9 +63,10 @@ def zlib_accepts(stream):
     return d.eof
 
 
-def test_code_length_sets_as_zlib():
+def test_code_length_sets_as_zlib(tmp_path):
     """seeded random literal/length and distance sets, sent through a complete code-length code and followed by the end-of-block
-    code where there is one: the statement accepts exactly the streams zlib accepts"""
+    code where there is one: the statement accepts exactly the streams zlib accepts, and the host build of the decode core
+    (m6a_io_bgzf_inflate) gives the statement's verdict on each of them as a BGZF block"""
     rng = np.random.default_rng(7)
     seen = {True: 0, False: 0}
     for trial in range(400):
@@ -97,10 +98,16 @@ def test_code_length_sets_as_zlib():
         stream = w.done()
         try:
             B.inflate(stream, 0)
-            ours = True
-        except B.Refused:
-            ours = False
+            ours, want = True, None
+        except B.Refused as e:
+            ours, want = False, "BGZF block at byte 0: " + e.args[0]
         assert ours == zlib_accepts(stream), (trial, ll, dd)
+        path = tmp_path / "set.gz"
+        path.write_bytes(bgzf.wrap(stream, 0, 0))
+        try:
+            assert _io.bgzf_inflate_host(str(path)) == b"" and ours, (trial, ll, dd)
+        except _io.M6AIOError as e:
+            assert not ours and e.code == -4 and str(e).endswith("%s: %s" % (path, want)), (trial, ll, dd, str(e))
         seen[ours] += 1
     assert seen[True] > 20 and seen[False] > 20
 

@@ -534,6 +534,50 @@ typedef struct m6a_bgzf_stats {
 } m6a_bgzf_stats;
 int m6a_bgzf_inflate(int device_id, const char *path, char *text, int64_t cap, int64_t *n_bytes, m6a_bgzf_stats *stats);
 
+/* BGZF output: data.site_proba.csv.gz and data.indiv_proba.csv.gz deflated on the device (`eventalign_inference --compress`), files
+ * that zcat, bgzip -d, pandas.read_csv and the reader above open.  tests/bgzf_statement.py reads what is written here.
+ *   blocks       the text is cut into blocks of at most 65 280 bytes (0xff00, as htslib cuts them); a block is the 18-byte header
+ *                1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 02 00 BSIZE, one raw DEFLATE stream, CRC32 and ISIZE.
+ *   stream       one deflate block of fixed Huffman codes (BTYPE 01), or one stored block (BTYPE 00) when the coded stream would
+ *                not be smaller than 5 + ISIZE bytes; so no BGZF block is larger than 65 536 bytes.
+ *   parts        the text of a block is cut into 64 parts of ceil(ISIZE / 64) bytes, each parsed greedily and on its own into
+ *                literals and matches of 3..258 bytes.  A match starts and ends inside its part, and may reach back up to 256 bytes in
+ *                front of the part (into earlier parts, never in front of the block).  The finder is a table of 128 x 2 positions
+ *                per part, so the bytes depend on the text alone: the same text gives the same file on the host and on any device.
+ *   file         the blocks, then the 28-byte end-of-file marker 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 and
+ *                eight zero bytes.  An empty text is the marker alone.
+ * A wave deflates a block, a lane a part, with the lanes' tables in LDS; the parts' bit strings are joined by an exclusive sum of
+ * their lengths.  Blocks are written into slots of 64 KiB and packed by a scan and a second kernel (m6anet_amd/csrc/m6a_deflate.h);
+ * one record of three words comes back per round -- the packed sizes and the stored blocks -- not a word per block.
+ *
+ * m6a_bgzf_deflate: text[0, n) (host memory) deflated on device device_id into out[0, cap), *n_bytes its length, marker included; the
+ * mirror of m6a_bgzf_inflate.  out == NULL is the sizing call: *n_bytes = ceil(n / 65280) * 65536 + 28, an upper bound, and no
+ * device is touched.  Needs no weights and no m6a_ctx.  stats (may be NULL): blocks, stored blocks, the kernels and the copy of the
+ * blocks to the host in ms, and d2h_bytes.  libm6a_io.so's m6a_io_bgzf_deflate gives the same bytes from the host.
+ *
+ * m6a_prep_sites_write_csv_bgzf: m6a_prep_sites_write_csv with the text deflated before it leaves the device.  Each round's two texts
+ * are formatted as there, cut into blocks (a round ends its last block), deflated, packed, copied through the pinned pair and
+ * pwrite()n at a running offset; round k + 1 is formatted and deflated while round k is copied and written.  With write_header the
+ * header line is the first block of its file; without it the blocks go behind what the files hold.  Both files end with the marker.
+ * The files are <out_dir>/data.site_proba.csv.gz and data.indiv_proba.csv.gz; the plain files are not created.  M6A_EDECLINED as for
+ * the plain writer, before any file is opened; every device buffer -- text, slots and sizes of both rounds, which count in
+ * peak_bytes and against the budget -- is allocated before that too, so M6A_ENOMEM leaves no file behind either. */
+typedef struct m6a_deflate_stats {
+    int64_t n_blocks, n_stored;
+    double ms_deflate, ms_copy;
+    int64_t d2h_bytes;
+} m6a_deflate_stats;
+int m6a_bgzf_deflate(int device_id, const char *text, int64_t n, char *out, int64_t cap, int64_t *n_bytes, m6a_deflate_stats *stats);
+typedef struct m6a_csv_bgzf_stats {
+    double ms_format, ms_deflate, ms_copy, ms_write;    /* as m6a_csv_stats, and the three deflate kernels */
+    int64_t site_bytes, indiv_bytes;                    /* text of either file, headers not counted */
+    int64_t site_compressed, indiv_compressed;          /* bytes this call wrote to either file, header block and marker included */
+    int64_t n_blocks, n_stored;                         /* BGZF blocks written (the marker not counted); those that came out stored */
+    int64_t n_declined, d2h_bytes, n_rounds;
+} m6a_csv_bgzf_stats;
+int m6a_prep_sites_write_csv_bgzf(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
+                                  m6a_csv_bgzf_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

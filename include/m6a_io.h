@@ -192,6 +192,12 @@ int m6a_io_dataprep_write(const char *eventalign_path, const char *out_dir, cons
  * its own text for a file that is not gzip, or is gzip but not BGZF. */
 int m6a_io_bgzf_inflate(const char *path, char *text, int64_t cap, int64_t *n_bytes);
 
+/* text[0, n) written as BGZF on the host by the deflate core the HIP kernels compile (m6anet_amd/csrc/m6a_deflate.h; include/m6a.h
+ * states the writer): blocks of at most 65 280 text bytes, then the 28-byte end-of-file marker, into out[0, cap); the bytes are those
+ * m6a_bgzf_deflate gives on a device.  out == NULL is the sizing call: *n_bytes = ceil(n / 65280) * 65536 + 28, an upper bound.
+ * *n_stored (may be NULL): the blocks that came out stored. */
+int m6a_io_bgzf_deflate(const char *text, int64_t n, char *out, int64_t cap, int64_t *n_bytes, int64_t *n_stored);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate"]
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate"]
 _lib = None
 
 
@@ -93,6 +93,7 @@ def load():
     L.m6a_io_sites_from_arrays.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, C.POINTER(vp)]
     L.m6a_io_sites_from_arrays_rep.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, vp, i32, C.POINTER(vp)]
     L.m6a_io_bgzf_inflate.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
+    L.m6a_io_bgzf_deflate.argtypes = [C.c_char_p, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     _lib = L
     return L
 
@@ -219,6 +220,38 @@ def bgzf_inflate(path, device_id=0, stats=None):
     return buf.raw[:n.value]
 
 
+def bgzf_deflate_host(data, stats=None):
+    """m6a_io_bgzf_deflate: `data` as BGZF (blocks of at most 65 280 bytes and the end-of-file marker), written on the host by the
+    deflate core the HIP kernels compile -- the bytes bgzf_deflate gives.  `stats`: a dict that receives n_stored."""
+    L, n, ns = load(), C.c_int64(), C.c_int64()
+    data = bytes(data)
+    _chk(L.m6a_io_bgzf_deflate(data, len(data), None, 0, C.byref(n), None))
+    buf = C.create_string_buffer(n.value)
+    _chk(L.m6a_io_bgzf_deflate(data, len(data), buf, n.value, C.byref(n), C.byref(ns)))
+    if stats is not None:
+        stats.update(n_stored=ns.value)
+    return buf.raw[:n.value]
+
+
+def bgzf_deflate(data, device_id=0, stats=None):
+    """m6a_bgzf_deflate (libm6a_hip.so): `data` as BGZF, deflated by the HIP kernels; byte for byte what bgzf_deflate_host gives.
+    `stats`: a dict that receives the m6a_deflate_stats fields."""
+    from . import _lib
+    L, n, st = _lib.load(), C.c_int64(), _lib.DeflateStats()
+    data = bytes(data)
+
+    def call(buf, cap):
+        rc = L.m6a_bgzf_deflate(int(device_id), data, len(data), buf, cap, C.byref(n), C.byref(st))
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), prep_on_device._CODES.get(rc, rc))
+    call(None, 0)
+    buf = C.create_string_buffer(n.value)
+    call(buf, n.value)
+    if stats is not None:
+        stats.update({k: getattr(st, k) for k, _ in st._fields_})
+    return buf.raw[:n.value]
+
+
 def norm_arrays(norm):
     """Normalisation factors (dict kmer -> (mean[3], std[3]), or None) in m6a_io_load_sites' form: (kmers blob, mean, std, n)."""
     if not norm:
@@ -312,14 +345,16 @@ class prep_sites:
         rep = (self.read_rep, self.n_replicates) if self.n_replicates > 1 else (None, 1)
         return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids, *rep)
 
-    def write_csv(self, out_dir, write_header=True, n_threads=0, n_sites=None):
+    def write_csv(self, out_dir, write_header=True, n_threads=0, n_sites=None, compress=False):
         """m6a_prep_sites_write_csv: both CSV files formatted on the device from the handle's arrays (after the engine has filled
         read_prob / site_prob / mod_ratio) and pwritten from pinned rounds.  Returns the statistics as a dict.  Raises CsvDeclined
-        (nothing opened, nothing written) when a value is outside what the kernels format: write through writer() then."""
+        (nothing opened, nothing written) when a value is outside what the kernels format: write through writer() then.
+        compress=True: m6a_prep_sites_write_csv_bgzf -- the text is deflated on the device and the files are data.site_proba.csv.gz
+        and data.indiv_proba.csv.gz (BGZF); the plain files are not created, and the dict is the m6a_csv_bgzf_stats."""
         from . import _lib
-        st = _lib.CsvStats()
-        rc = self._L.m6a_prep_sites_write_csv(self._h, os.fsencode(out_dir), 1 if write_header else 0, -1 if n_sites is None else int(n_sites),
-                                              int(n_threads), C.byref(st))
+        st = _lib.CsvBgzfStats() if compress else _lib.CsvStats()
+        fn = self._L.m6a_prep_sites_write_csv_bgzf if compress else self._L.m6a_prep_sites_write_csv
+        rc = fn(self._h, os.fsencode(out_dir), 1 if write_header else 0, -1 if n_sites is None else int(n_sites), int(n_threads), C.byref(st))
         self.peak_bytes = int(self.info.peak_bytes)
         stats = {k: getattr(st, k) for k, _ in st._fields_}
         if rc == _lib.M6A_EDECLINED:

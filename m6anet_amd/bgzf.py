@@ -41,9 +41,10 @@ def _span(args):
     return b"".join(block(data[i:i + BLOCK_INPUT], level) for i in range(0, len(data), BLOCK_INPUT))
 
 
-def compress_file(path, out_path=None, level=6, n_processes=1, span_blocks=4096):
+def compress_file(path, out_path=None, level=6, n_processes=1, span_blocks=4096, threads=False):
     """path -> out_path (default path + ".gz"): blocks of BLOCK_INPUT input bytes, then the marker; spans of span_blocks blocks are
-    compressed by n_processes processes and written in order.  Returns (input bytes, output bytes)."""
+    compressed by n_processes processes (threads=True: threads of this process; zlib releases the interpreter lock) and written in
+    order.  Returns (input bytes, output bytes)."""
     out_path = out_path or path + ".gz"
     n = os.path.getsize(path)
     span = span_blocks * BLOCK_INPUT
@@ -52,7 +53,8 @@ def compress_file(path, out_path=None, level=6, n_processes=1, span_blocks=4096)
     with open(out_path, "wb") as out:
         if n_processes > 1 and len(jobs) > 1:
             import multiprocessing as mp
-            with mp.get_context("spawn").Pool(n_processes) as pool:
+            import multiprocessing.pool
+            with (mp.pool.ThreadPool(n_processes) if threads else mp.get_context("spawn").Pool(n_processes)) as pool:
                 for part in pool.imap(_span, jobs):
                     out.write(part)
                     written += len(part)

@@ -1,0 +1,646 @@
+// m6a_deflate.h -- the BGZF writer of `eventalign_inference --compress` (include/m6a.h states it): text in, BGZF blocks out.
+//
+// Part 1, the deflate core: plain C++ marked for host and device, no HIP in it.  m6a_io.cpp compiles it for the CPU
+// (m6a_io_bgzf_deflate, and tests/deflate_core_main.cpp under the sanitizers); m6a_prep.hip compiles the same text for gfx950, and
+// both give the same bytes: nothing below depends on timing or on the order in which lanes run.
+//   block       at most kBlockInput = 65 280 bytes of text become one BGZF block: the 18-byte header, one raw DEFLATE stream
+//               (RFC 1951), CRC-32 and ISIZE.  The stream is ONE block of fixed Huffman codes (BTYPE 01), or one stored block
+//               (BTYPE 00) when the coded stream would not be smaller than 5 + n bytes -- so a BGZF block is at most
+//               18 + 5 + 65 280 + 8 bytes, under the format's 65 536.
+//   parts       the text of a block is cut into 64 parts of per = ceil(n / 64) bytes (the last may be shorter, parts may be empty);
+//               a lane (the CPU: a loop index) parses its part greedily and on its own.  Matches are 3..258 bytes long, start and
+//               end inside the part, and reach back at most kReach = 256 bytes in front of the part -- into earlier parts, never in
+//               front of the block's first byte; every distance is far below 32 768.
+//   finder      a table of kSets x kWays 16-bit positions per lane (512 bytes; 32 KB of LDS for a wave), indexed by a hash of the
+//               next three bytes; a set keeps the last kWays positions with that hash, newest first, and the longest match among
+//               them wins, the nearer one at equal length.  The table is primed with the kReach positions in front of the part.
+//               Only its own lane reads or writes a lane's table.
+//   merging     a part's bit string (part 0 starts with the three header bits, part 63 ends with the end-of-block code) is formed
+//               twice: part_bits() gives its length and its first byte; after an exclusive sum of the lengths part_emit() forms it
+//               again and stores it at its bit offset.  A byte of the stream is stored by the lane whose string holds the byte's
+//               first bit; the bits of later parts that share the byte come from their first bytes.  So every byte has one
+//               writer, and no byte is read back.
+//   CRC-32      m6a_bgzf::crc_lane, the 64 terms XORed.
+//
+// Part 2 (M6A_DEFLATE_DEVICE_PART, m6a_prep.hip only): the kernels, m6a_bgzf_deflate and m6a_prep_sites_write_csv_bgzf.
+//   layout      one wave per BGZF block, one wave per workgroup: the 64 tables (32 KB), the CRC byte table (1 KB) and the parts'
+//               lengths and first bytes (0.5 KB) in LDS, so four waves share a CU's 160 KB.  The text is read from global memory.
+//   placement   block sizes are known only after the parse: bgzf_deflate_kernel writes block b into slot b of 64 KiB and its size
+//               into size[b]; an exclusive scan gives the offsets and bgzf_pack_kernel moves every block to its place in the packed
+//               buffer.  All stores are vector stores in plain C++.
+//   status      the packed sizes and the count of stored blocks come back in one record of three words per round.
+#ifndef M6A_DEFLATE_H
+#define M6A_DEFLATE_H
+#include <stdint.h>
+
+#include "m6a_bgzf.h"
+
+namespace m6a_deflate {
+
+constexpr int32_t kBlockInput = 0xff00;       // text bytes per BGZF block, as htslib's bgzip and m6anet_amd/bgzf.py cut them
+constexpr int32_t kSlot = 65536;              // the largest BGZF block
+constexpr int kParts = 64;
+constexpr int32_t kReach = 256;               // bytes in front of a part that its matches may start in
+constexpr int kSets = 128, kWays = 2;
+constexpr int kTableEntries = kSets * kWays * kParts;      // uint16_t: 32 KB
+constexpr uint16_t kNone = 0xffff;            // positions are below 65 280
+constexpr int32_t kHeader = 18, kFooter = 8;
+constexpr int32_t kEofBytes = 28;
+
+M6A_HD inline int64_t n_blocks(int64_t n) { return (n + kBlockInput - 1) / kBlockInput; }
+M6A_HD inline int64_t bound(int64_t n) { return n_blocks(n) * kSlot + kEofBytes; }
+
+M6A_HD inline uint8_t eof_byte(int i)         // the specification's 28-byte end-of-file marker
+{
+    const uint8_t m[kEofBytes] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return m[i];
+}
+
+// ---- the bit strings ----
+M6A_HD inline uint32_t rev(uint32_t v, int n)               // the low n <= 16 bits of v, reversed
+{
+    v = (v & 0x5555u) << 1 | (v >> 1 & 0x5555u);
+    v = (v & 0x3333u) << 2 | (v >> 2 & 0x3333u);
+    v = (v & 0x0f0fu) << 4 | (v >> 4 & 0x0f0fu);
+    v = (v & 0x00ffu) << 8 | (v >> 8 & 0x00ffu);
+    return v >> (16 - n);
+}
+
+struct Count {                                // a part's length in bits and its first byte
+    uint32_t bits = 0, head = 0;
+    M6A_HD void put(uint32_t v, int n)        // n <= 32 - 7
+    {
+        if (bits < 8) head |= (v << bits) & 0xff;
+        bits += (uint32_t)n;
+    }
+};
+
+struct Emit {                                 // a part's bit string stored from bit `at` of out on; the bits below the first byte
+    uint8_t *out;                             // boundary are dropped (the lane in front stores that byte)
+    uint32_t skip;                            // bits still to drop
+    uint32_t byte;                            // index of the next byte to store
+    uint64_t acc = 0;
+    int cnt = 0;
+    M6A_HD Emit(uint8_t *o, uint32_t at) : out(o), skip((8 - (at & 7)) & 7), byte((at + 7) >> 3) {}
+    M6A_HD void put(uint32_t v, int n)
+    {
+        if (skip) {
+            const int k = (int)skip < n ? (int)skip : n;
+            v >>= k;
+            n -= k;
+            skip -= (uint32_t)k;
+            if (!n) return;
+        }
+        acc |= (uint64_t)v << cnt;
+        cnt += n;
+        while (cnt >= 8) {
+            out[byte++] = (uint8_t)acc;
+            acc >>= 8;
+            cnt -= 8;
+        }
+    }
+};
+
+template <class Sink> M6A_HD inline void put_literal(Sink &s, uint32_t b)
+{
+    if (b < 144) s.put(rev(0x30 + b, 8), 8);
+    else s.put(rev(0x190 + (b - 144), 9), 9);
+}
+
+template <class Sink> M6A_HD inline void put_match(Sink &s, int32_t len, int32_t dist)      // 3 <= len <= 258, 1 <= dist <= 32768
+{
+    const uint32_t l = (uint32_t)(len - 3);
+    uint32_t sym, ext = 0, extra = 0;
+    if (l < 8) sym = 257 + l;
+    else if (l == 255) sym = 285;
+    else {
+        ext = (uint32_t)(31 - __builtin_clz(l)) - 2;
+        sym = 261 + 4 * ext + ((l >> ext) & 3);
+        extra = l & ((1u << ext) - 1);
+    }
+    if (sym < 280) s.put(rev(sym - 256, 7), 7);
+    else s.put(rev(0xc0 + (sym - 280), 8), 8);
+    if (ext) s.put(extra, (int)ext);
+    const uint32_t d = (uint32_t)(dist - 1);
+    uint32_t code = d, dext = 0;
+    if (d >= 4) {
+        dext = (uint32_t)(31 - __builtin_clz(d)) - 1;
+        code = 2 * dext + 2 + ((d >> dext) & 1);
+    }
+    s.put(rev(code, 5), 5);
+    if (dext) s.put(d & ((1u << dext) - 1), (int)dext);
+}
+
+// ---- the finder: lane's table is tab[(set * kWays + way) * kParts + lane] ----
+M6A_HD inline uint32_t hash3(const uint8_t *p) { return ((uint32_t)(p[0] | p[1] << 8 | p[2] << 16) * 0x9e3779b1u) >> 25; }      // < kSets
+
+M6A_HD inline void insert(uint16_t *tab, int lane, const uint8_t *in, int32_t q)
+{
+    uint16_t *t = tab + (hash3(in + q) * kWays) * kParts + lane;
+    t[kParts] = t[0];
+    t[0] = (uint16_t)q;
+}
+
+M6A_HD inline void part_range(int32_t n, int lane, int32_t *lo, int32_t *hi)
+{
+    const int32_t per = (n + kParts - 1) / kParts;
+    *lo = lane * per < n ? lane * per : n;
+    *hi = *lo + per < n ? *lo + per : n;
+}
+
+// the bit string of part `lane` of in[0, n), n <= kBlockInput, into the sink
+template <class Sink> M6A_HD inline void part_code(const uint8_t *in, int32_t n, int lane, uint16_t *tab, Sink &s)
+{
+    int32_t lo, hi;
+    part_range(n, lane, &lo, &hi);
+    if (lane == 0) s.put(3, 3);                             // BFINAL = 1, BTYPE = 01
+    for (int e = 0; e < kSets * kWays; e++) tab[e * kParts + lane] = kNone;
+    for (int32_t q = lo > kReach ? lo - kReach : 0; q < lo; q++)
+        if (q + 2 < n) insert(tab, lane, in, q);
+    for (int32_t i = lo; i < hi;) {
+        int32_t best = 0, best_at = 0;
+        if (i + 2 < hi) {
+            const uint16_t *t = tab + (hash3(in + i) * kWays) * kParts + lane;
+            const int32_t room = hi - i < 258 ? hi - i : 258;
+            for (int w = 0; w < kWays; w++) {
+                const int32_t c = t[w * kParts];
+                if (c == kNone) break;
+                int32_t l = 0;                              // c < i: the table holds positions already passed
+                while (l < room && in[c + l] == in[i + l]) l++;
+                if (l > best) { best = l; best_at = c; }
+            }
+            insert(tab, lane, in, i);
+        }
+        if (best >= 3 && i - best_at <= 32768) {
+            put_match(s, best, i - best_at);
+            for (int32_t q = i + 1; q < i + best; q++)
+                if (q + 2 < hi) insert(tab, lane, in, q);
+            i += best;
+        } else {
+            put_literal(s, in[i]);
+            i++;
+        }
+    }
+    if (lane == kParts - 1) s.put(0, 7);                    // end of block
+}
+
+M6A_HD inline void part_bits(const uint8_t *in, int32_t n, int lane, uint16_t *tab, uint32_t *bits, uint32_t *head)
+{
+    Count c;
+    part_code(in, n, lane, tab, c);
+    *bits = c.bits;
+    *head = c.head;
+}
+
+// start = the sum of bits[0, lane); out = the first byte of the deflate stream
+M6A_HD inline void part_emit(const uint8_t *in, int32_t n, int lane, uint16_t *tab, uint32_t start, const uint32_t *bits, const uint32_t *head,
+                             uint8_t *out)
+{
+    Emit e(out, start);
+    part_code(in, n, lane, tab, e);
+    if (e.cnt && !e.skip) {                                 // the last byte this lane owns: filled up from the parts behind
+        for (int q = lane + 1; q < kParts && e.cnt < 8; q++) {
+            const int k = (int)bits[q] < 8 - e.cnt ? (int)bits[q] : 8 - e.cnt;
+            e.acc |= (uint64_t)(head[q] & ((1u << k) - 1)) << e.cnt;
+            e.cnt += k;
+        }
+        out[e.byte] = (uint8_t)e.acc;
+    }
+}
+
+M6A_HD inline void put_header(uint8_t *blk, int32_t total)
+{
+    const uint8_t h[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    for (int i = 0; i < 16; i++) blk[i] = h[i];
+    blk[16] = (uint8_t)(total - 1);
+    blk[17] = (uint8_t)((total - 1) >> 8);
+}
+M6A_HD inline void put_footer(uint8_t *p, uint32_t crc, int32_t n)
+{
+    for (int i = 0; i < 4; i++) {
+        p[i] = (uint8_t)(crc >> (8 * i));
+        p[4 + i] = (uint8_t)((uint32_t)n >> (8 * i));
+    }
+}
+// bytes of the coded stream of `bits` bits, or of the stored block when that is not larger
+M6A_HD inline int32_t stream_bytes(uint32_t bits, int32_t n, bool *stored)
+{
+    const int32_t coded = (int32_t)((bits + 7) >> 3);
+    *stored = coded >= 5 + n;
+    return *stored ? 5 + n : coded;
+}
+M6A_HD inline void put_stored_head(uint8_t *p, int32_t n)
+{
+    p[0] = 1;
+    p[1] = (uint8_t)n;
+    p[2] = (uint8_t)(n >> 8);
+    p[3] = (uint8_t)~n;
+    p[4] = (uint8_t)(~n >> 8);
+}
+
+// One block on the CPU: in[0, n), 0 < n <= kBlockInput, to blk (kSlot bytes of room); returns its size.  tab: kTableEntries entries.
+inline int32_t block_host(const uint8_t *in, int32_t n, uint8_t *blk, uint16_t *tab, const uint32_t *crc_tab, bool *stored)
+{
+    uint32_t bits[kParts], head[kParts], start[kParts], sum = 0, crc = 0;
+    for (int lane = 0; lane < kParts; lane++) part_bits(in, n, lane, tab, &bits[lane], &head[lane]);
+    for (int lane = 0; lane < kParts; lane++) { start[lane] = sum; sum += bits[lane]; }
+    const int32_t body = stream_bytes(sum, n, stored), total = kHeader + body + kFooter;
+    put_header(blk, total);
+    if (*stored) {
+        put_stored_head(blk + kHeader, n);
+        for (int32_t i = 0; i < n; i++) blk[kHeader + 5 + i] = in[i];
+    } else
+        for (int lane = 0; lane < kParts; lane++) part_emit(in, n, lane, tab, start[lane], bits, head, blk + kHeader);
+    for (int lane = 0; lane < kParts; lane++) crc ^= m6a_bgzf::crc_lane(crc_tab, in, n, lane);
+    put_footer(blk + kHeader + body, crc, n);
+    return total;
+}
+
+// text[0, n) as BGZF blocks into out (bound(n) bytes of room), without the end-of-file marker; returns the bytes written
+inline int64_t blocks_host(const uint8_t *text, int64_t n, uint8_t *out, int64_t *n_stored)
+{
+    uint32_t crc_tab[256];
+    for (uint32_t i = 0; i < 256; i++) crc_tab[i] = m6a_bgzf::crc_entry(i);
+    uint16_t *tab = new uint16_t[kTableEntries];
+    int64_t at = 0;
+    for (int64_t off = 0; off < n; off += kBlockInput) {
+        bool stored;
+        at += block_host(text + off, (int32_t)(n - off < kBlockInput ? n - off : kBlockInput), out + at, tab, crc_tab, &stored);
+        if (stored && n_stored) ++*n_stored;
+    }
+    delete[] tab;
+    return at;
+}
+
+}  // namespace m6a_deflate
+
+#ifdef M6A_DEFLATE_DEVICE_PART
+// ---- part 2: kernels and the two entry points (inside m6a_prep.hip, behind m6a_csv.h: DevMem, PCHK, prep_fail, now_ms, g_d2h, Fd and
+// the CSV writer's plan, launch and pwrite helpers are theirs) ----
+namespace m6a_deflate {
+namespace {
+
+// The text of a round is two ranges of `text`: [0, n0) and [at1, at1 + n1) (the read rows and the site rows; n1 = 0 for one text).
+// Each is cut into blocks of kBlockInput bytes, the first range's blocks first; a range ends its last block.
+struct DeflText {
+    const uint8_t *text;
+    int64_t n0, at1, n1;
+    __host__ __device__ int64_t blocks0() const { return n_blocks(n0); }
+    __host__ __device__ int64_t blocks() const { return n_blocks(n0) + n_blocks(n1); }
+    __device__ const uint8_t *block(int64_t b, int32_t *len) const
+    {
+        const int64_t b0 = blocks0(), base = b < b0 ? 0 : at1, n = b < b0 ? n0 : n1, off = (b < b0 ? b : b - b0) * kBlockInput;
+        *len = (int32_t)(n - off < kBlockInput ? n - off : kBlockInput);
+        return text + base + off;
+    }
+};
+
+// status: [0] bytes of the first range's blocks, [1] bytes of all blocks, [2] stored blocks (zeroed before the launch)
+__global__ void __launch_bounds__(kParts) bgzf_deflate_kernel(DeflText t, uint8_t *__restrict__ slots, int64_t *__restrict__ size,
+                                                              unsigned long long *__restrict__ status)
+{
+    __shared__ uint16_t tab[kTableEntries];
+    __shared__ uint32_t crc_tab[256], bits[kParts], head[kParts];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = blockIdx.x;
+    for (int i = lane; i < 256; i += kParts) crc_tab[i] = m6a_bgzf::crc_entry((uint32_t)i);
+    int32_t n;
+    const uint8_t *in = t.block(b, &n);
+    uint8_t *out = slots + b * kSlot;
+    uint32_t mine, first;
+    part_bits(in, n, lane, tab, &mine, &first);
+    bits[lane] = mine;
+    head[lane] = first;
+    __syncthreads();
+    uint32_t incl = mine;
+    for (int o = 1; o < kParts; o <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
+        if (lane >= o) incl += v;
+    }
+    const uint32_t sum = (uint32_t)__shfl((int)incl, kParts - 1);
+    bool stored;
+    const int32_t body = stream_bytes(sum, n, &stored), total = kHeader + body + kFooter;
+    if (stored) {
+        if (lane == 0) put_stored_head(out + kHeader, n);
+        for (int32_t i = lane; i < n; i += kParts) out[kHeader + 5 + i] = in[i];
+    } else
+        part_emit(in, n, lane, tab, incl - mine, bits, head, out + kHeader);
+    uint32_t c = m6a_bgzf::crc_lane(crc_tab, in, n, lane);
+    for (int o = kParts / 2; o > 0; o >>= 1) c ^= (uint32_t)__shfl_xor((int)c, o);
+    if (lane == 0) {
+        put_header(out, total);
+        put_footer(out + kHeader + body, c, n);
+        size[b] = total;
+        if (stored) atomicAdd(status + 2, 1ull);
+    }
+}
+
+// size[0, n) -> its exclusive sums in size[0, n], by one workgroup; the two totals into status
+__global__ void __launch_bounds__(kBlk) bgzf_offsets_kernel(int64_t *__restrict__ size, int64_t n, int64_t n_first, unsigned long long *__restrict__ status)
+{
+    __shared__ int64_t part[kBlk];
+    const int t = (int)threadIdx.x;
+    const int64_t per = (n + kBlk - 1) / kBlk, lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    int64_t sum = 0;
+    for (int64_t i = lo; i < hi; i++) sum += size[i];
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        int64_t run = 0;
+        for (int i = 0; i < kBlk; i++) { const int64_t v = part[i]; part[i] = run; run += v; }
+        size[n] = run;
+        status[1] = (unsigned long long)run;
+    }
+    __syncthreads();
+    int64_t run = part[t];
+    for (int64_t i = lo; i < hi; i++) { const int64_t v = size[i]; size[i] = run; run += v; }
+    __syncthreads();
+    if (t == 0) status[0] = (unsigned long long)size[n_first];
+}
+
+// block blockIdx.x from its slot to its offset in `packed`
+__global__ void __launch_bounds__(kBlk) bgzf_pack_kernel(const uint8_t *__restrict__ slots, const int64_t *__restrict__ off, uint8_t *__restrict__ packed)
+{
+    const int64_t b = blockIdx.x, at = off[b];
+    const int32_t len = (int32_t)(off[b + 1] - at);
+    const uint8_t *src = slots + b * kSlot;
+    for (int32_t i = (int32_t)threadIdx.x; i < len; i += kBlk) packed[at + i] = src[i];
+}
+
+// the three kernels on stream s; `packed` may be the text's own buffer (it is read before it is written), with room for
+// n0 + n1 + 64 bytes per block
+int deflate_launch(const DeflText &t, uint8_t *slots, int64_t *size, unsigned long long *status, uint8_t *packed, hipStream_t s)
+{
+    const int64_t nb = t.blocks();
+    PCHK(hipMemsetAsync(status, 0, 3 * sizeof *status, s));
+    if (!nb) return M6A_OK;
+    if (nb > 0x7fffffffll) return prep_fail(M6A_EINVAL, "more than 2^31 BGZF blocks in a round");
+    bgzf_deflate_kernel<<<(unsigned)nb, kParts, 0, s>>>(t, slots, size, status);
+    PCHK(hipGetLastError());
+    bgzf_offsets_kernel<<<1, kBlk, 0, s>>>(size, nb, t.blocks0(), status);
+    PCHK(hipGetLastError());
+    bgzf_pack_kernel<<<(unsigned)nb, kBlk, 0, s>>>(slots, size, packed);
+    PCHK(hipGetLastError());
+    return M6A_OK;
+}
+
+inline int64_t packed_room(int64_t n0, int64_t n1) { return n0 + n1 + 64 * (n_blocks(n0) + n_blocks(n1)); }
+
+int deflate_impl(int device_id, const uint8_t *text, int64_t n, uint8_t *out, int64_t cap, int64_t *n_bytes, m6a_deflate_stats &st)
+{
+    DevMem m;
+    int rc = csv_device(device_id, m);
+    if (rc) return rc;
+    m.advice = "deflate it on the host, or in pieces";
+    g_d2h = 0;
+    Streams S;
+    PCHK(hipStreamCreateWithFlags(&S.s[0], hipStreamNonBlocking));
+    hipStream_t s = S.s[0];
+    const int64_t nb = n_blocks(n);
+    uint8_t *dtext, *slots;
+    int64_t *size;
+    unsigned long long *status, h[3] = {0, 0, 0};
+    if ((rc = m.alloc(dtext, (size_t)packed_room(n, 0), "the text")) || (rc = m.alloc(slots, (size_t)(nb * kSlot), "BGZF slots")) ||
+        (rc = m.alloc(size, (size_t)nb + 1, "BGZF sizes")) || (rc = m.alloc(status, 3, "flags")))
+        return rc;
+    if ((rc = h2d(dtext, text, (size_t)n, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    double t0 = now_ms();
+    if ((rc = deflate_launch(DeflText{dtext, n, 0, 0}, slots, size, status, dtext, s)) || (rc = d2h(h, status, 3, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    st.ms_deflate = now_ms() - t0;
+    st.n_blocks = nb;
+    st.n_stored = (int64_t)h[2];
+    const int64_t total = (int64_t)h[1];
+    *n_bytes = total + kEofBytes;
+    if (cap < total + kEofBytes) return prep_fail(M6A_EINVAL, "the blocks take %lld bytes, the buffer holds %lld", (long long)(total + kEofBytes), (long long)cap);
+    t0 = now_ms();
+    if ((rc = d2h(out, dtext, (size_t)total, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    st.ms_copy = now_ms() - t0;
+    for (int i = 0; i < kEofBytes; i++) out[total + i] = eof_byte(i);
+    st.d2h_bytes = g_d2h;
+    return M6A_OK;
+}
+
+struct DeflRound {                         // stream, events, device and pinned buffers of one of the two rounds in flight
+    hipStream_t s = nullptr;
+    hipEvent_t e[6] = {};                  // start, formatted, deflated, status copied, copy begins, copied
+    uint8_t *text = nullptr, *slots = nullptr, *pin = nullptr;
+    int64_t *size = nullptr;
+    unsigned long long *status = nullptr, *hstatus = nullptr;
+    ~DeflRound()
+    {
+        if (s) (void)hipStreamSynchronize(s);
+        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
+        if (pin) (void)hipHostFree(pin);
+        if (hstatus) (void)hipHostFree(hstatus);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+// the header line of a file as a BGZF block of its own, made by the host core
+std::vector<uint8_t> header_block(const char *line, int32_t n)
+{
+    std::vector<uint8_t> blk((size_t)kSlot);
+    int64_t none = 0;
+    blk.resize((size_t)blocks_host((const uint8_t *)line, n, blk.data(), &none));
+    return blk;
+}
+
+int csv_write_bgzf_impl(m6a_prep_sites &P, const char *out_dir, int write_header, int64_t n_limit, int n_threads, m6a_csv_bgzf_stats &st)
+{
+    const m6a_prep_sites_info &I = P.info;
+    const int64_t S = n_limit >= 0 ? std::min<int64_t>(n_limit, I.n_sites) : I.n_sites;
+    if (I.n_sites && !P.csv_ids) return prep_fail(M6A_EINVAL, "the handle holds no read ids on the device");
+    const int nw = n_threads > 0 ? n_threads : m6a_usable_cpus();
+    DevMem m;
+    int rc = csv_device(P.device, m);
+    if (rc) return rc;
+    g_d2h = 0;
+    struct Account {                       // whatever way the call ends, what it copied and allocated is reported
+        m6a_prep_sites &P; DevMem &m; m6a_csv_bgzf_stats &st;
+        ~Account()
+        {
+            st.d2h_bytes = g_d2h;
+            P.info.d2h_bytes += g_d2h;
+            P.info.peak_bytes = std::max<int64_t>(P.info.peak_bytes, (int64_t)(P.held + m.peak));
+        }
+    } account{P, m, st};
+    DeflRound rd[2];
+    for (DeflRound &r : rd) {
+        PCHK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
+        for (hipEvent_t &x : r.e) PCHK(hipEventCreate(&x));
+    }
+    hipStream_t s = rd[0].s;
+
+    // ---- the small uploads, lengths and offsets of the whole job, and the rounds: as the plain writer's
+    uint8_t *blob;
+    int64_t *tx_off;
+    const size_t nblob = (size_t)(I.n_tx ? I.tx_off[I.n_tx] : 0);
+    if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)I.n_tx + 1, "transcript names"))) return rc;
+    if ((rc = h2d(blob, (const uint8_t *)I.tx_blob, nblob, s)) || (rc = h2d(tx_off, I.tx_off, I.n_tx ? (size_t)I.n_tx + 1 : 0, s))) return rc;
+    const CsvDev d{I.off, P.csv_tx, P.csv_pos, P.csv_k7, 7, 1, blob, tx_off, P.csv_ids, nullptr, I.n_rep > 1 ? P.csv_parts : nullptr,
+                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio};
+    double t0 = now_ms();
+    CsvPlan plan;
+    if ((rc = csv_plan(m, d, 0, S, s, plan))) return rc;
+    st.ms_format += now_ms() - t0;
+    st.n_declined = plan.declined;
+    st.site_bytes = plan.site[(size_t)S];
+    st.indiv_bytes = plan.indiv[(size_t)S];
+    if (plan.declined)
+        return prep_fail(M6A_EDECLINED, "%lld values are outside what the device formats (a probability or ratio that is negative or >= 2, "
+                         "a read index that is not an integer in [0, 10^15))", (long long)plan.declined);
+    const char *rk = getenv("M6A_CSV_ROUND_KB");
+    const int64_t round_bytes = (rk && atoll(rk) > 0 ? atoll(rk) : kCsvRoundKB) << 10;
+    std::vector<int64_t> cut{0};
+    int64_t cap_text = 0, cap_blocks = 0;
+    auto ni_of = [&](int64_t a, int64_t b) { return plan.indiv[(size_t)b] - plan.indiv[(size_t)a]; };
+    auto ns_of = [&](int64_t a, int64_t b) { return plan.site[(size_t)b] - plan.site[(size_t)a]; };
+    while (cut.back() < S) {
+        const int64_t a = cut.back();
+        int64_t lo = a + 1, hi = S;                          // the last b with the text of [a, b) <= round_bytes, at least a + 1
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            if (ni_of(a, mid) + ns_of(a, mid) <= round_bytes) lo = mid; else hi = mid - 1;
+        }
+        cut.push_back(lo);
+        const int64_t ni = ni_of(a, lo), ns = ns_of(a, lo);
+        cap_text = std::max(cap_text, std::max(csv_align(ni) + ns, packed_room(ni, ns)));
+        cap_blocks = std::max(cap_blocks, n_blocks(ni) + n_blocks(ns));
+    }
+    const int64_t n_rounds = (int64_t)cut.size() - 1;
+    st.n_rounds = n_rounds;
+
+    // ---- every buffer before a file is opened: over the budget nothing is touched
+    for (int i = 0; i < (n_rounds > 1 ? 2 : n_rounds ? 1 : 0); i++) {
+        DeflRound &r = rd[i];
+        if ((rc = m.alloc(r.text, (size_t)cap_text, "CSV text")) || (rc = m.alloc(r.slots, (size_t)(cap_blocks * kSlot), "BGZF slots")) ||
+            (rc = m.alloc(r.size, (size_t)cap_blocks + 1, "BGZF sizes")) || (rc = m.alloc(r.status, 3, "flags")))
+            return rc;
+        PCHK(hipHostMalloc((void **)&r.pin, (size_t)std::max<int64_t>(cap_text, 16), hipHostMallocDefault));
+        PCHK(hipHostMalloc((void **)&r.hstatus, 3 * sizeof *r.hstatus, hipHostMallocDefault));
+    }
+
+    // ---- the files: the header line is a block of its own
+    const std::string fs = std::string(out_dir) + "/data.site_proba.csv.gz", fi = std::string(out_dir) + "/data.indiv_proba.csv.gz";
+    const int flags = O_WRONLY | O_CREAT | (write_header ? O_TRUNC : 0);
+    Fd f, g;
+    f.fd = ::open(fs.c_str(), flags, 0644);
+    if (f.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fs.c_str());
+    g.fd = ::open(fi.c_str(), flags, 0644);
+    if (g.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fi.c_str());
+    int64_t at_site = 0, at_indiv = 0;
+    if (write_header) {
+        const std::vector<uint8_t> hs = header_block(kCsvSiteHeader, (int32_t)sizeof(kCsvSiteHeader) - 1),
+                                   hi = header_block(kCsvIndivHeader, (int32_t)sizeof(kCsvIndivHeader) - 1);
+        at_site = (int64_t)hs.size();
+        at_indiv = (int64_t)hi.size();
+        st.n_blocks += 2;
+        if (!csv_pwrite_all(f.fd, (const char *)hs.data(), at_site, 0)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
+        if (!csv_pwrite_all(g.fd, (const char *)hi.data(), at_indiv, 0)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
+    } else {                                                // append: behind whatever the files hold (an earlier marker is an empty block)
+        struct stat sb;
+        if (fstat(f.fd, &sb) != 0) return prep_fail(M6A_EIO, "cannot stat %s", fs.c_str());
+        at_site = (int64_t)sb.st_size;
+        if (fstat(g.fd, &sb) != 0) return prep_fail(M6A_EIO, "cannot stat %s", fi.c_str());
+        at_indiv = (int64_t)sb.st_size;
+    }
+    const int64_t site0 = at_site, indiv0 = at_indiv;
+
+    // ---- round k + 1 is formatted and deflated while round k is copied and written
+    auto enqueue = [&](int64_t k) -> int {
+        DeflRound &r = rd[k & 1];
+        const int64_t a = cut[(size_t)k], b = cut[(size_t)k + 1], ni = ni_of(a, b), ns = ns_of(a, b);
+        PCHK(hipEventRecord(r.e[0], r.s));
+        int rc2 = csv_launch(d, plan, 0, a, b, (char *)r.text, csv_align(ni), r.s);
+        if (rc2) return rc2;
+        PCHK(hipEventRecord(r.e[1], r.s));
+        if ((rc2 = deflate_launch(DeflText{r.text, ni, csv_align(ni), ns}, r.slots, r.size, r.status, r.text, r.s))) return rc2;
+        PCHK(hipEventRecord(r.e[2], r.s));
+        PCHK(hipMemcpyAsync(r.hstatus, r.status, 3 * sizeof *r.status, hipMemcpyDeviceToHost, r.s));
+        g_d2h += (int64_t)(3 * sizeof *r.status);
+        PCHK(hipEventRecord(r.e[3], r.s));
+        st.n_blocks += n_blocks(ni) + n_blocks(ns);
+        return M6A_OK;
+    };
+    if (n_rounds && (rc = enqueue(0))) return rc;
+    for (int64_t k = 0; k < n_rounds; k++) {
+        DeflRound &r = rd[k & 1];
+        PCHK(hipEventSynchronize(r.e[3]));
+        const int64_t ci = (int64_t)r.hstatus[0], ct = (int64_t)r.hstatus[1];
+        st.n_stored += (int64_t)r.hstatus[2];
+        PCHK(hipEventRecord(r.e[4], r.s));
+        if (ct) PCHK(hipMemcpyAsync(r.pin, r.text, (size_t)ct, hipMemcpyDeviceToHost, r.s));
+        g_d2h += ct;
+        PCHK(hipEventRecord(r.e[5], r.s));
+        if (k + 1 < n_rounds && (rc = enqueue(k + 1))) return rc;
+        PCHK(hipEventSynchronize(r.e[5]));
+        float fm = 0, dm = 0, cm = 0;
+        PCHK(hipEventElapsedTime(&fm, r.e[0], r.e[1]));
+        PCHK(hipEventElapsedTime(&dm, r.e[1], r.e[2]));
+        PCHK(hipEventElapsedTime(&cm, r.e[4], r.e[5]));
+        st.ms_format += fm;
+        st.ms_deflate += dm;
+        st.ms_copy += cm;
+        t0 = now_ms();
+        if (!csv_pwrite_threads(g.fd, (const char *)r.pin, ci, at_indiv, nw)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
+        if (!csv_pwrite_all(f.fd, (const char *)r.pin + ci, ct - ci, at_site)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
+        st.ms_write += now_ms() - t0;
+        at_indiv += ci;
+        at_site += ct - ci;
+    }
+    char eof[kEofBytes];
+    for (int i = 0; i < kEofBytes; i++) eof[i] = (char)eof_byte(i);
+    if (!csv_pwrite_all(f.fd, eof, kEofBytes, at_site)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
+    if (!csv_pwrite_all(g.fd, eof, kEofBytes, at_indiv)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
+    st.site_compressed = at_site + kEofBytes - (write_header ? 0 : site0);
+    st.indiv_compressed = at_indiv + kEofBytes - (write_header ? 0 : indiv0);
+    const int cf = ::close(f.fd), cg = ::close(g.fd);
+    f.fd = g.fd = -1;
+    if (cf != 0) return prep_fail(M6A_EIO, "cannot close %s", fs.c_str());
+    if (cg != 0) return prep_fail(M6A_EIO, "cannot close %s", fi.c_str());
+    return M6A_OK;
+}
+
+}  // namespace
+}  // namespace m6a_deflate
+
+extern "C" int m6a_bgzf_deflate(int device_id, const char *text, int64_t n, char *out, int64_t cap, int64_t *n_bytes, m6a_deflate_stats *stats)
+{
+    if (!n_bytes || n < 0 || (n && !text)) return prep_fail(M6A_EINVAL, "null argument");
+    *n_bytes = m6a_deflate::bound(n);
+    if (stats) *stats = m6a_deflate_stats{};
+    if (!out) return M6A_OK;                               // the sizing call
+    m6a_deflate_stats st{};
+    int rc;
+    try {
+        rc = m6a_deflate::deflate_impl(device_id, (const uint8_t *)text, n, (uint8_t *)out, cap, n_bytes, st);
+    } catch (const std::bad_alloc &) {
+        rc = prep_fail(M6A_ENOMEM, "out of host memory");
+    } catch (...) {
+        rc = prep_fail(M6A_EIO, "unexpected exception");
+    }
+    if (stats) *stats = st;
+    return rc;
+}
+
+extern "C" int m6a_prep_sites_write_csv_bgzf(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
+                                             m6a_csv_bgzf_stats *stats)
+{
+    if (!p || !out_dir) return prep_fail(M6A_EINVAL, "null argument");
+    m6a_csv_bgzf_stats st{};
+    int rc;
+    try {
+        rc = m6a_deflate::csv_write_bgzf_impl(*p, out_dir, write_header, n_sites_limit, n_threads, st);
+    } catch (const std::bad_alloc &) {
+        rc = prep_fail(M6A_ENOMEM, "out of host memory");
+    } catch (...) {
+        rc = prep_fail(M6A_EIO, "unexpected exception");
+    }
+    if (stats) *stats = st;
+    return rc;
+}
+#endif  // M6A_DEFLATE_DEVICE_PART
+#endif

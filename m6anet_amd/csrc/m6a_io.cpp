@@ -2264,3 +2264,23 @@ extern "C" int m6a_io_bgzf_inflate(const char *path, char *text, int64_t cap, in
         return fail(M6A_IO_ENOMEM, "bgzf: out of memory");
     }
 }
+
+// ---- BGZF written on the host: the deflate core of m6a_deflate.h (the one the HIP kernels compile), the 64 parts in a loop ---------
+#include "m6a_deflate.h"
+
+extern "C" int m6a_io_bgzf_deflate(const char *text, int64_t n, char *out, int64_t cap, int64_t *n_bytes, int64_t *n_stored)
+{
+    if (!n_bytes || n < 0 || (n && !text)) return fail(M6A_IO_EINVAL, "null argument");
+    *n_bytes = m6a_deflate::bound(n);
+    if (n_stored) *n_stored = 0;
+    if (!out) return M6A_IO_OK;
+    if (cap < *n_bytes) return fail(M6A_IO_EINVAL, "the blocks may need %lld bytes, the buffer holds %lld", (long long)*n_bytes, (long long)cap);
+    try {
+        int64_t at = m6a_deflate::blocks_host((const uint8_t *)text, n, (uint8_t *)out, n_stored);
+        for (int i = 0; i < m6a_deflate::kEofBytes; i++) out[at++] = (char)m6a_deflate::eof_byte(i);
+        *n_bytes = at;
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "bgzf: out of memory");
+    }
+}

@@ -2720,3 +2720,5 @@ extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }
 #define M6A_BGZF_DEVICE_PART
 #include "m6a_bgzf.h"
 #include "m6a_csv.h"
+#define M6A_DEFLATE_DEVICE_PART
+#include "m6a_deflate.h"

@@ -53,17 +53,42 @@ def cli_parser():
                              "(0: the whole file, about 3 bytes of device memory per byte of text -- unless M6A_PREP_WINDOW_KB is set, which 0 leaves in force).  With windows the device "
                              "holds two windows and the candidate rows, so a file larger than device memory goes through; the bytes "
                              "written are the same.")
+    parser.add_argument("--compress", action="store_true",
+                        help="write data.site_proba.csv.gz and data.indiv_proba.csv.gz (BGZF: zcat, bgzip -d and pandas.read_csv open "
+                             "them) instead of the two plain files; the text inside is the same.  With --csv device the text is deflated "
+                             "by HIP kernels before it crosses the link (about a third of the bytes); with --csv host, and for values "
+                             "the kernels decline, the host compresses the text it formatted.")
     return parser
 
 
-def write_on_device(sites, out_dir, n_threads, n_sites):
+GZ = ("data.site_proba.csv", "data.indiv_proba.csv")
+
+
+def write_on_host_compressed(writer, out_dir, read_prob, site_prob, mod_ratio, n_threads, n_sites):
+    """--compress without the kernels: the host writer's two files, formatted into a directory of their own under out_dir, then
+    written as BGZF next to it (m6anet_amd/bgzf.py, zlib in threads) and removed.  Returns the bytes of the two .gz files."""
+    import shutil
+    import tempfile
+
+    from .. import _io, bgzf
+    tmp = tempfile.mkdtemp(prefix=".csv_plain_", dir=out_dir)
+    try:
+        writer.write_csv(tmp, read_prob, site_prob, mod_ratio, write_header=True, n_threads=n_threads, n_sites=n_sites)
+        workers = n_threads if n_threads > 0 else _io.usable_cpus()
+        return sum(bgzf.compress_file(os.path.join(tmp, fn), os.path.join(out_dir, fn + ".gz"), n_processes=workers, span_blocks=64,
+                                      threads=True)[1] for fn in GZ)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def write_on_device(sites, out_dir, n_threads, n_sites, compress=False):
     """--csv device: prep_sites.write_csv's statistics, or None after one line on stderr when the kernels declined a value --
     nothing has been opened or written then, and the caller writes the same bytes through the host."""
     import sys
 
     from .. import _io
     try:
-        return sites.write_csv(out_dir, write_header=True, n_threads=n_threads, n_sites=n_sites)
+        return sites.write_csv(out_dir, write_header=True, n_threads=n_threads, n_sites=n_sites, **({"compress": True} if compress else {}))
     except _io.CsvDeclined as e:
         print("eventalign_inference: --csv device declined %d values (%s); writing the CSV files on the host"
               % (e.n_declined, str(e).split(": ", 1)[1]), file=sys.stderr, flush=True)
@@ -82,6 +107,7 @@ def main(args):
     device = inference._device_index(args.device)
     csv_on = getattr(args, "csv", "host")    # argparser() alone (no --csv): the host writer
     window_mb = getattr(args, "window_mb", 0)
+    compress = getattr(args, "compress", False)
     if window_mb < 0:
         raise ValueError("--window_mb must be 0 or more, not %d" % window_mb)
     made = {}
@@ -108,7 +134,10 @@ def main(args):
         pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
         writer = sites.writer() if csv_on == "host" or sites.n_sites == 0 else None       # --csv device needs it only to fall back
         if sites.n_sites == 0:               # what `inference` leaves behind: the two header lines, then the loader's error
-            writer.write_csv(args.out_dir, [], [], [], write_header=True, n_threads=args.n_processes)
+            if compress:
+                write_on_host_compressed(writer, args.out_dir, [], [], [], args.n_processes, None)
+            else:
+                writer.write_csv(args.out_dir, [], [], [], write_header=True, n_threads=args.n_processes)
             raise _io.M6AIOError("m6a_io error -4: no site with at least %d reads" % DEFAULT_MIN_READS, -4)
         i = sites.info
         t0 = time.perf_counter()
@@ -120,13 +149,17 @@ def main(args):
         n_write = None
         if args.drop_unflushed_tail:         # the reference's row set (inference_utils.py:47)
             n_write = reference_written_sites(sites.n_sites, args.batch_size, args.save_per_batch)
-        csv = write_on_device(sites, args.out_dir, args.n_processes, n_write) if csv_on == "device" else None
+        csv = write_on_device(sites, args.out_dir, args.n_processes, n_write, compress) if csv_on == "device" else None
         t2 = time.perf_counter()
+        host_gz = None
         if csv is None:
             read_prob, site_prob, mod_ratio = sites.fetch()
             t2 = time.perf_counter()
             writer = writer or sites.writer()
-            writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes, n_sites=n_write)
+            if compress:
+                host_gz = write_on_host_compressed(writer, args.out_dir, read_prob, site_prob, mod_ratio, args.n_processes, n_write)
+            else:
+                writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes, n_sites=n_write)
         if os.environ.get("M6A_EVENTALIGN_TIMES"):      # phases for tools/measure_eventalign_inference.py
             import json
             ms, d2h = sites.times()
@@ -136,6 +169,12 @@ def main(args):
             if csv is not None:              # the device writer's own phases; they overlap, so they need not add up to csv_write
                 ms.update(csv_format=csv["ms_format"], csv_copy=csv["ms_copy"], csv_pwrite=csv["ms_write"])
                 extra = {"csv_writer": "device", "csv_text_bytes": csv["site_bytes"] + csv["indiv_bytes"], "csv_rounds": csv["n_rounds"]}
+            if compress and csv is not None:     # the deflate kernels' time; file bytes, header blocks and markers included
+                ms.update(csv_deflate=csv["ms_deflate"])
+                extra.update(csv_compressed_bytes=csv["site_compressed"] + csv["indiv_compressed"], csv_stored_blocks=csv["n_stored"])
+            elif compress:                       # the host route: zlib; its time is part of csv_write and it counts no stored blocks
+                ms.update(csv_deflate=0.0)
+                extra.update(csv_compressed_bytes=host_gz, csv_stored_blocks=None)
             print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads, **extra,
                                                 "n_windows": sites.n_windows, "window_bytes": sites.window_bytes,
                                                 "peak_bytes": sites.peak_bytes, "inflate": sites.ms_inflate,

@@ -540,15 +540,34 @@ int m6a_bgzf_inflate(int device_id, const char *path, char *text, int64_t cap, i
  *                1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 02 00 BSIZE, one raw DEFLATE stream, CRC32 and ISIZE.
  *   stream       one deflate block of fixed Huffman codes (BTYPE 01), or one stored block (BTYPE 00) when the coded stream would
  *                not be smaller than 5 + ISIZE bytes; so no BGZF block is larger than 65 536 bytes.
+ *                This is level 1, what every entry point without a level writes.  Level 2 (`--compress_level 2`) is below.
  *   parts        the text of a block is cut into 64 parts of ceil(ISIZE / 64) bytes, each parsed greedily and on its own into
  *                literals and matches of 3..258 bytes.  A match starts and ends inside its part, and may reach back up to 256 bytes in
  *                front of the part (into earlier parts, never in front of the block).  The finder is a table of 128 x 2 positions
  *                per part, so the bytes depend on the text alone: the same text gives the same file on the host and on any device.
  *   file         the blocks, then the 28-byte end-of-file marker 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 and
  *                eight zero bytes.  An empty text is the marker alone.
+ * Level 2 keeps the blocks, the parts, the finder and so the tokens of level 1, and changes only how tokens become bits:
+ *   counts       the block's counts of the literal/length symbols 0..285 and of the distance codes 0..29; end-of-block counts once.
+ *   lengths      one prefix code per alphabet, of at most 15 bits: the used symbols sorted by (count, symbol), Moffat and Katajainen's
+ *                in-place minimum-redundancy depths, depths over the limit cut to it and the Kraft sum repaired as zlib and miniz
+ *                do (a code of the limit's length is dropped and one of the longest shorter codes becomes two codes a bit longer,
+ *                until the sum is 1), the lengths dealt longest first to the rarest symbols.  The code is complete and costs what
+ *                Huffman's costs where that fits the limit; a single used symbol gets length 1, and a block without a match sends
+ *                one distance code of length 0 (RFC 1951, 3.2.7).  Codes are canonical.
+ *   header       HLIT and HDIST drop the trailing unused symbols; the HLIT + HDIST lengths are one sequence, coded with 16 (3..6
+ *                more of the same), 17 (3..10 zeros) and 18 (11..138 zeros, taken first) greedily; the code of those 19 symbols is
+ *                built by the same rule with a limit of 7 bits.
+ *   choice       the bits of the dynamic stream, header included, against those of the fixed stream: the smaller wins, fixed wins a
+ *                tie, and a winner of 5 + ISIZE bytes or more is stored.  So a block is one deflate block of BTYPE 00, 01 or 10, never
+ *                larger than level 1's block of the same text, and the bound and the 64 KiB slots hold.
+ *   emission     as at level 1, with the dynamic header as one more bit string in front of part 0: offsets from the exclusive sum of
+ *                the 65 lengths, one writer per byte, no byte read back.
  * A wave deflates a block, a lane a part, with the lanes' tables in LDS; the parts' bit strings are joined by an exclusive sum of
  * their lengths.  Blocks are written into slots of 64 KiB and packed by a scan and a second kernel (m6anet_amd/csrc/m6a_deflate.h);
- * one record of three words comes back per round -- the packed sizes and the stored blocks -- not a word per block.
+ * one record of three words comes back per round -- the packed sizes and the stored blocks -- not a word per block.  At level 2 a
+ * kernel of its own (bgzf_deflate_dyn_kernel) counts the parts' tokens into one histogram per wave with LDS atomics, lane 0 builds the
+ * codes, and the record has a fourth word, the blocks of dynamic codes.
  *
  * m6a_bgzf_deflate: text[0, n) (host memory) deflated on device device_id into out[0, cap), *n_bytes its length, marker included; the
  * mirror of m6a_bgzf_inflate.  out == NULL is the sizing call: *n_bytes = ceil(n / 65280) * 65536 + 28, an upper bound, and no
@@ -568,6 +587,10 @@ typedef struct m6a_deflate_stats {
     int64_t d2h_bytes;
 } m6a_deflate_stats;
 int m6a_bgzf_deflate(int device_id, const char *text, int64_t n, char *out, int64_t cap, int64_t *n_bytes, m6a_deflate_stats *stats);
+/* m6a_bgzf_deflate at level 1 (its bytes) or 2; another level is M6A_EINVAL.  n_by_type (may be NULL): blocks by BTYPE 0, 1, 2.
+ * libm6a_io.so's m6a_io_bgzf_deflate_level gives the same bytes and counts from the host. */
+int m6a_bgzf_deflate_level(int device_id, const char *text, int64_t n, int level, char *out, int64_t cap, int64_t *n_bytes,
+                           m6a_deflate_stats *stats, int64_t n_by_type[3]);
 typedef struct m6a_csv_bgzf_stats {
     double ms_format, ms_deflate, ms_copy, ms_write;    /* as m6a_csv_stats, and the three deflate kernels */
     int64_t site_bytes, indiv_bytes;                    /* text of either file, headers not counted */
@@ -577,6 +600,10 @@ typedef struct m6a_csv_bgzf_stats {
 } m6a_csv_bgzf_stats;
 int m6a_prep_sites_write_csv_bgzf(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
                                   m6a_csv_bgzf_stats *stats);
+/* m6a_prep_sites_write_csv_bgzf at level 1 (its bytes) or 2; the header line's block is made by the host core at the same level.
+ * n_by_type (may be NULL): the blocks written, header blocks included, by BTYPE 0, 1, 2. */
+int m6a_prep_sites_write_csv_bgzf_level(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
+                                        int level, m6a_csv_bgzf_stats *stats, int64_t n_by_type[3]);
 
 #ifdef __cplusplus
 }

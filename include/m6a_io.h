@@ -198,6 +198,11 @@ int m6a_io_bgzf_inflate(const char *path, char *text, int64_t cap, int64_t *n_by
  * *n_stored (may be NULL): the blocks that came out stored. */
 int m6a_io_bgzf_deflate(const char *text, int64_t n, char *out, int64_t cap, int64_t *n_bytes, int64_t *n_stored);
 
+/* m6a_io_bgzf_deflate at a level of the writer (include/m6a.h states both): 1 gives m6a_io_bgzf_deflate's bytes, 2 codes every block
+ * with the smaller of the fixed and its own Huffman codes; any other level is M6A_IO_EINVAL.  n_by_type (may be NULL): the blocks that
+ * came out as deflate block type 0 (stored), 1 (fixed codes) and 2 (dynamic codes). */
+int m6a_io_bgzf_deflate_level(const char *text, int64_t n, int level, char *out, int64_t cap, int64_t *n_bytes, int64_t n_by_type[3]);
+
 #ifdef __cplusplus
 }
 #endif

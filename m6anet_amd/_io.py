@@ -10,7 +10,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate"]
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level"]
 _lib = None
 
 
@@ -94,6 +94,7 @@ def load():
     L.m6a_io_sites_from_arrays_rep.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, vp, i32, C.POINTER(vp)]
     L.m6a_io_bgzf_inflate.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     L.m6a_io_bgzf_deflate.argtypes = [C.c_char_p, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.m6a_io_bgzf_deflate_level.argtypes = [C.c_char_p, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     _lib = L
     return L
 
@@ -220,11 +221,21 @@ def bgzf_inflate(path, device_id=0, stats=None):
     return buf.raw[:n.value]
 
 
-def bgzf_deflate_host(data, stats=None):
+def bgzf_deflate_host(data, stats=None, level=1):
     """m6a_io_bgzf_deflate: `data` as BGZF (blocks of at most 65 280 bytes and the end-of-file marker), written on the host by the
-    deflate core the HIP kernels compile -- the bytes bgzf_deflate gives.  `stats`: a dict that receives n_stored."""
+    deflate core the HIP kernels compile -- the bytes bgzf_deflate gives.  `stats`: a dict that receives n_stored.
+    level: 1 (fixed Huffman codes) through that symbol; anything else goes to m6a_io_bgzf_deflate_level, where 2 is dynamic codes,
+    and `stats` receives n_by_type, the blocks of deflate block type 0, 1 and 2, as well."""
     L, n, ns = load(), C.c_int64(), C.c_int64()
     data = bytes(data)
+    if level != 1:
+        by = (C.c_int64 * 3)()
+        _chk(L.m6a_io_bgzf_deflate_level(data, len(data), int(level), None, 0, C.byref(n), None))
+        buf = C.create_string_buffer(n.value)
+        _chk(L.m6a_io_bgzf_deflate_level(data, len(data), int(level), buf, n.value, C.byref(n), by))
+        if stats is not None:
+            stats.update(n_stored=by[0], n_by_type=list(by))
+        return buf.raw[:n.value]
     _chk(L.m6a_io_bgzf_deflate(data, len(data), None, 0, C.byref(n), None))
     buf = C.create_string_buffer(n.value)
     _chk(L.m6a_io_bgzf_deflate(data, len(data), buf, n.value, C.byref(n), C.byref(ns)))
@@ -233,15 +244,20 @@ def bgzf_deflate_host(data, stats=None):
     return buf.raw[:n.value]
 
 
-def bgzf_deflate(data, device_id=0, stats=None):
+def bgzf_deflate(data, device_id=0, stats=None, level=1):
     """m6a_bgzf_deflate (libm6a_hip.so): `data` as BGZF, deflated by the HIP kernels; byte for byte what bgzf_deflate_host gives.
-    `stats`: a dict that receives the m6a_deflate_stats fields."""
+    `stats`: a dict that receives the m6a_deflate_stats fields.  level other than 1: m6a_bgzf_deflate_level (2: dynamic Huffman
+    codes), and `stats` receives n_by_type as well."""
     from . import _lib
     L, n, st = _lib.load(), C.c_int64(), _lib.DeflateStats()
     data = bytes(data)
+    by = (C.c_int64 * 3)()
 
     def call(buf, cap):
-        rc = L.m6a_bgzf_deflate(int(device_id), data, len(data), buf, cap, C.byref(n), C.byref(st))
+        if level != 1:
+            rc = L.m6a_bgzf_deflate_level(int(device_id), data, len(data), int(level), buf, cap, C.byref(n), C.byref(st), by)
+        else:
+            rc = L.m6a_bgzf_deflate(int(device_id), data, len(data), buf, cap, C.byref(n), C.byref(st))
         if rc != 0:
             raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), prep_on_device._CODES.get(rc, rc))
     call(None, 0)
@@ -249,6 +265,8 @@ def bgzf_deflate(data, device_id=0, stats=None):
     call(buf, n.value)
     if stats is not None:
         stats.update({k: getattr(st, k) for k, _ in st._fields_})
+        if level != 1:
+            stats.update(n_by_type=list(by))
     return buf.raw[:n.value]
 
 
@@ -345,18 +363,28 @@ class prep_sites:
         rep = (self.read_rep, self.n_replicates) if self.n_replicates > 1 else (None, 1)
         return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids, *rep)
 
-    def write_csv(self, out_dir, write_header=True, n_threads=0, n_sites=None, compress=False):
+    def write_csv(self, out_dir, write_header=True, n_threads=0, n_sites=None, compress=False, level=1):
         """m6a_prep_sites_write_csv: both CSV files formatted on the device from the handle's arrays (after the engine has filled
         read_prob / site_prob / mod_ratio) and pwritten from pinned rounds.  Returns the statistics as a dict.  Raises CsvDeclined
         (nothing opened, nothing written) when a value is outside what the kernels format: write through writer() then.
         compress=True: m6a_prep_sites_write_csv_bgzf -- the text is deflated on the device and the files are data.site_proba.csv.gz
-        and data.indiv_proba.csv.gz (BGZF); the plain files are not created, and the dict is the m6a_csv_bgzf_stats."""
+        and data.indiv_proba.csv.gz (BGZF); the plain files are not created, and the dict is the m6a_csv_bgzf_stats.
+        level (with compress): 1 is that symbol; anything else goes to m6a_prep_sites_write_csv_bgzf_level, where 2 is dynamic Huffman
+        codes, and the dict holds n_by_type, the blocks of deflate block type 0, 1 and 2, as well."""
         from . import _lib
+        if level != 1 and not compress:
+            raise ValueError("level=%r needs compress=True" % (level,))
         st = _lib.CsvBgzfStats() if compress else _lib.CsvStats()
-        fn = self._L.m6a_prep_sites_write_csv_bgzf if compress else self._L.m6a_prep_sites_write_csv
-        rc = fn(self._h, os.fsencode(out_dir), 1 if write_header else 0, -1 if n_sites is None else int(n_sites), int(n_threads), C.byref(st))
+        head = (self._h, os.fsencode(out_dir), 1 if write_header else 0, -1 if n_sites is None else int(n_sites), int(n_threads))
+        by = (C.c_int64 * 3)()
+        if compress and level != 1:
+            rc = self._L.m6a_prep_sites_write_csv_bgzf_level(*head, int(level), C.byref(st), by)
+        else:
+            rc = (self._L.m6a_prep_sites_write_csv_bgzf if compress else self._L.m6a_prep_sites_write_csv)(*head, C.byref(st))
         self.peak_bytes = int(self.info.peak_bytes)
         stats = {k: getattr(st, k) for k, _ in st._fields_}
+        if compress and level != 1:
+            stats["n_by_type"] = list(by)
         if rc == _lib.M6A_EDECLINED:
             raise CsvDeclined("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), rc, stats["n_declined"])
         if rc != 0:

@@ -19,7 +19,8 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
-           "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf"]
+           "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
+           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level"]
 
 _lib = None
 
@@ -190,6 +191,8 @@ def load():
     L.m6a_bgzf_inflate.argtypes = [i32, C.c_char_p, vp, i64, pl, C.POINTER(BgzfStats)]
     L.m6a_bgzf_deflate.argtypes = [i32, C.c_char_p, i64, vp, i64, pl, C.POINTER(DeflateStats)]
     L.m6a_prep_sites_write_csv_bgzf.argtypes = [vp, C.c_char_p, i32, i64, i32, C.POINTER(CsvBgzfStats)]
+    L.m6a_bgzf_deflate_level.argtypes = [i32, C.c_char_p, i64, i32, vp, i64, pl, C.POINTER(DeflateStats), pl]
+    L.m6a_prep_sites_write_csv_bgzf_level.argtypes = [vp, C.c_char_p, i32, i64, i32, i32, C.POINTER(CsvBgzfStats), pl]
     L.m6a_prep_last_error.argtypes = []
     L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:

@@ -2284,3 +2284,21 @@ extern "C" int m6a_io_bgzf_deflate(const char *text, int64_t n, char *out, int64
         return fail(M6A_IO_ENOMEM, "bgzf: out of memory");
     }
 }
+
+extern "C" int m6a_io_bgzf_deflate_level(const char *text, int64_t n, int level, char *out, int64_t cap, int64_t *n_bytes, int64_t n_by_type[3])
+{
+    if (!n_bytes || n < 0 || (n && !text)) return fail(M6A_IO_EINVAL, "null argument");
+    if (level != 1 && level != 2) return fail(M6A_IO_EINVAL, "level %d: the BGZF writer has levels 1 and 2", level);
+    *n_bytes = m6a_deflate::bound(n);
+    if (n_by_type) n_by_type[0] = n_by_type[1] = n_by_type[2] = 0;
+    if (!out) return M6A_IO_OK;
+    if (cap < *n_bytes) return fail(M6A_IO_EINVAL, "the blocks may need %lld bytes, the buffer holds %lld", (long long)*n_bytes, (long long)cap);
+    try {
+        int64_t at = m6a_deflate::blocks_host((const uint8_t *)text, n, level, (uint8_t *)out, n_by_type);
+        for (int i = 0; i < m6a_deflate::kEofBytes; i++) out[at++] = (char)m6a_deflate::eof_byte(i);
+        *n_bytes = at;
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "bgzf: out of memory");
+    }
+}

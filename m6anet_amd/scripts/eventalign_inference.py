@@ -58,6 +58,11 @@ def cli_parser():
                              "them) instead of the two plain files; the text inside is the same.  With --csv device the text is deflated "
                              "by HIP kernels before it crosses the link (about a third of the bytes); with --csv host, and for values "
                              "the kernels decline, the host compresses the text it formatted.")
+    parser.add_argument("--compress_level", type=int, choices=(1, 2), default=1,
+                        help="with --compress and --csv device: 1 codes every BGZF block with the fixed Huffman codes of RFC 1951, "
+                             "2 gives every block its own (dynamic) codes where they are smaller -- the same parse, about 0.6 of "
+                             "level 1's bytes on the CSV text.  The host route (--csv host, declined values) is zlib, which writes "
+                             "dynamic codes at any level, so there the flag changes nothing.  Without --compress it is an error.")
     return parser
 
 
@@ -81,14 +86,15 @@ def write_on_host_compressed(writer, out_dir, read_prob, site_prob, mod_ratio, n
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def write_on_device(sites, out_dir, n_threads, n_sites, compress=False):
+def write_on_device(sites, out_dir, n_threads, n_sites, compress=False, level=1):
     """--csv device: prep_sites.write_csv's statistics, or None after one line on stderr when the kernels declined a value --
     nothing has been opened or written then, and the caller writes the same bytes through the host."""
     import sys
 
     from .. import _io
     try:
-        return sites.write_csv(out_dir, write_header=True, n_threads=n_threads, n_sites=n_sites, **({"compress": True} if compress else {}))
+        return sites.write_csv(out_dir, write_header=True, n_threads=n_threads, n_sites=n_sites, **({"compress": True} if compress else {}),
+                               **({"level": level} if compress and level != 1 else {}))
     except _io.CsvDeclined as e:
         print("eventalign_inference: --csv device declined %d values (%s); writing the CSV files on the host"
               % (e.n_declined, str(e).split(": ", 1)[1]), file=sys.stderr, flush=True)
@@ -103,11 +109,16 @@ def main(args):
     from ..data_utils import load_norm_factors
     from ..engine import reference_written_sites
 
+    if getattr(args, "compress_level", 1) != 1 and not getattr(args, "compress", False):       # an argument error, before anything is touched
+        import sys
+        print("m6anet_amd eventalign_inference: error: --compress_level %d needs --compress" % args.compress_level, file=sys.stderr)
+        raise SystemExit(2)
     weights = inference.resolve_model(args)
     device = inference._device_index(args.device)
     csv_on = getattr(args, "csv", "host")    # argparser() alone (no --csv): the host writer
     window_mb = getattr(args, "window_mb", 0)
     compress = getattr(args, "compress", False)
+    level = getattr(args, "compress_level", 1)
     if window_mb < 0:
         raise ValueError("--window_mb must be 0 or more, not %d" % window_mb)
     made = {}
@@ -149,7 +160,7 @@ def main(args):
         n_write = None
         if args.drop_unflushed_tail:         # the reference's row set (inference_utils.py:47)
             n_write = reference_written_sites(sites.n_sites, args.batch_size, args.save_per_batch)
-        csv = write_on_device(sites, args.out_dir, args.n_processes, n_write, compress) if csv_on == "device" else None
+        csv = write_on_device(sites, args.out_dir, args.n_processes, n_write, compress, level) if csv_on == "device" else None
         t2 = time.perf_counter()
         host_gz = None
         if csv is None:
@@ -172,6 +183,8 @@ def main(args):
             if compress and csv is not None:     # the deflate kernels' time; file bytes, header blocks and markers included
                 ms.update(csv_deflate=csv["ms_deflate"])
                 extra.update(csv_compressed_bytes=csv["site_compressed"] + csv["indiv_compressed"], csv_stored_blocks=csv["n_stored"])
+                if "n_by_type" in csv:           # level 2 ran on the device; header blocks are counted
+                    extra.update(csv_fixed_blocks=csv["n_by_type"][1], csv_dynamic_blocks=csv["n_by_type"][2])
             elif compress:                       # the host route: zlib; its time is part of csv_write and it counts no stored blocks
                 ms.update(csv_deflate=0.0)
                 extra.update(csv_compressed_bytes=host_gz, csv_stored_blocks=None)

@@ -48,12 +48,15 @@ compressed leg carries no bar.  With --parent_tree the default command on the pl
 Both files are read from a warm page cache; a cold read from disk, which is what compressed input is for, is not measured here.
 
     python tools/measure_eventalign_inference.py --compress [--shapes 3.1GB,24.3GB] [--legs 5] [--parent_tree DIR]
-                                                 [--out profiles/r12_csv_bgzf.json]
+                                                 [--out profiles/r13_csv_bgzf_dynamic.json]
 
-`--csv device` without and with `--compress` as interleaved legs of the one-file command: medians, the phase table of every leg
-(csv_format, csv_deflate, csv_copy, csv_pwrite ms), device-to-host bytes per read, the compressed files' size over the text and the
-stored blocks; every leg's .gz files are inflated (`gzip -dc`) and compared with the plain leg's files.  The compressed leg carries no
-bar: which of the two is faster is reported.  With --parent_tree the default command against the parent's, the bar of mode (b)."""
+`--csv device` plain, with `--compress` (level 1, fixed Huffman codes) and with `--compress --compress_level 2` (dynamic codes) as
+interleaved legs of the one-file command: medians, the phase table of every leg (csv_format, csv_deflate, csv_copy, csv_pwrite ms),
+device-to-host bytes per read, the compressed files' size over the text, the stored blocks and at level 2 the fixed and dynamic ones,
+and level 2 over level 1 in csv_deflate ms, bytes and command time; every leg's .gz files are inflated (`gzip -dc`) and compared with
+the plain leg's files.  The compressed legs carry no bar against the plain leg: which is faster is reported.  With --parent_tree the
+default command against the parent's, the bar of mode (b), and this tree's `--compress` leg against the parent's `--compress`
+command under the same rule (parent median + parent spread): level 2 is meant to leave both alone."""
 import filecmp
 import gzip
 import json
@@ -369,12 +372,12 @@ def bgzf_legs(tag, legs, parent, ev_dir, limit):
 def compress_legs(tag, legs, parent, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs}
-    runs = {"plain": [], "compress": []}
-    one, par = [], []
+    runs = {"plain": [], "compress": [], "compress2": []}
+    one, par, par_gz = [], [], []
     env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
     try:
         for leg in range(legs):
-            for mode, flag in (("plain", []), ("compress", ["--compress"])):
+            for mode, flag in (("plain", []), ("compress", ["--compress"]), ("compress2", ["--compress", "--compress_level", "2"])):
                 cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, mode), "--csv", "device"] + flag + THREADS
                 s, p = timed(cmd, limit, env=env)
                 must(s, p, "--csv device " + mode)
@@ -382,41 +385,55 @@ def compress_legs(tag, legs, parent, ev_dir, limit):
                 t["s"] = s
                 runs[mode].append(t)
             same = []
-            for f in CSVS:                                  # the text inside the .gz files is the plain leg's file
-                z = subprocess.Popen(["gzip", "-dc", os.path.join(ev_dir, "compress", f + ".gz")], stdout=subprocess.PIPE)
-                c = subprocess.run(["cmp", "-s", "-", os.path.join(ev_dir, "plain", f)], stdin=z.stdout)
-                z.stdout.close()
-                same.append(z.wait() == 0 and c.returncode == 0)
-            res["gunzipped_identical"] = all(same) and not any(os.path.exists(os.path.join(ev_dir, "compress", f)) for f in CSVS)
+            for mode in ("compress", "compress2"):
+                for f in CSVS:                              # the text inside the .gz files is the plain leg's file
+                    z = subprocess.Popen(["gzip", "-dc", os.path.join(ev_dir, mode, f + ".gz")], stdout=subprocess.PIPE)
+                    c = subprocess.run(["cmp", "-s", "-", os.path.join(ev_dir, "plain", f)], stdin=z.stdout)
+                    z.stdout.close()
+                    same.append(z.wait() == 0 and c.returncode == 0 and not os.path.exists(os.path.join(ev_dir, mode, f)))
+            res["gunzipped_identical"] = all(same)
             if parent:
                 cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
                 one.append(must(*timed(cmd, limit), "default command, this tree"))
                 cmd[4] = os.path.join(ev_dir, "one_parent")
                 par.append(must(*timed(cmd, limit, tree=parent), "default command, parent tree"))
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "gz_parent"), "--csv", "device",
+                       "--compress"] + THREADS                # level 1 is held to the parent's --compress leg of the same session
+                par_gz.append(must(*timed(cmd, limit, tree=parent), "--csv device --compress, parent tree"))
                 res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
                                                                  shallow=False) for f in CSVS)
-            for d in ("plain", "compress", "one", "one_parent"):
+            for d in ("plain", "compress", "compress2", "one", "one_parent", "gz_parent"):
                 subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
-            print("%s: leg %d of %d: --csv device %.2f s, with --compress %.2f s" % (tag, leg + 1, legs, runs["plain"][-1]["s"],
-                                                                                    runs["compress"][-1]["s"]), file=sys.stderr, flush=True)
+            print("%s: leg %d of %d: --csv device %.2f s, with --compress %.2f s, with --compress_level 2 %.2f s" % (
+                tag, leg + 1, legs, runs["plain"][-1]["s"], runs["compress"][-1]["s"], runs["compress2"][-1]["s"]), file=sys.stderr, flush=True)
         for mode in runs:
             v = runs[mode]
             res[mode] = {"median_s": median([x["s"] for x in v]), "d2h_bytes_per_read": v[-1]["d2h_bytes"] / v[-1]["n_reads"],
                          "csv_write_ms": median([x["ms"]["csv_write"] for x in v]), "csv_format_ms": median([x["ms"]["csv_format"] for x in v]),
                          "csv_copy_ms": median([x["ms"]["csv_copy"] for x in v]), "csv_pwrite_ms": median([x["ms"]["csv_pwrite"] for x in v]),
                          "csv_text_bytes": v[-1]["csv_text_bytes"], "peak_bytes": v[-1]["peak_bytes"], "legs": v}
+        for mode in ("compress", "compress2"):
+            c = res[mode]
+            c["csv_deflate_ms"] = median([x["ms"]["csv_deflate"] for x in runs[mode]])
+            c["csv_compressed_bytes"] = runs[mode][-1]["csv_compressed_bytes"]
+            c["csv_stored_blocks"] = runs[mode][-1]["csv_stored_blocks"]
+            c["compressed_over_text"] = c["csv_compressed_bytes"] / c["csv_text_bytes"]
+            c["deflate_GBps_of_text"] = c["csv_text_bytes"] / (c["csv_deflate_ms"] * 1e6) if c["csv_deflate_ms"] else None
+        res["compress2"]["csv_dynamic_blocks"] = runs["compress2"][-1]["csv_dynamic_blocks"]
+        res["compress2"]["csv_fixed_blocks"] = runs["compress2"][-1]["csv_fixed_blocks"]
+        res["level_2_over_level_1"] = {"csv_deflate_ms": res["compress2"]["csv_deflate_ms"] / res["compress"]["csv_deflate_ms"],
+                                       "bytes": res["compress2"]["csv_compressed_bytes"] / res["compress"]["csv_compressed_bytes"],
+                                       "median_s": res["compress2"]["median_s"] / res["compress"]["median_s"]}
         c = res["compress"]
-        c["csv_deflate_ms"] = median([x["ms"]["csv_deflate"] for x in runs["compress"]])
-        c["csv_compressed_bytes"] = runs["compress"][-1]["csv_compressed_bytes"]
-        c["csv_stored_blocks"] = runs["compress"][-1]["csv_stored_blocks"]
-        c["compressed_over_text"] = c["csv_compressed_bytes"] / c["csv_text_bytes"]
-        c["deflate_GBps_of_text"] = c["csv_text_bytes"] / (c["csv_deflate_ms"] * 1e6) if c["csv_deflate_ms"] else None
         res["compress_over_plain_time"] = c["median_s"] / res["plain"]["median_s"]
         res["compress_is"] = "faster" if c["median_s"] < res["plain"]["median_s"] else "slower"
         if parent:
             res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
                                       "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
                                       "within_bar": median(one) <= median(par) + max(par) - min(par)}
+            res["compress_command"] = {"this_median_s": c["median_s"], "parent_s": par_gz, "parent_median_s": median(par_gz),
+                                       "parent_spread_s": max(par_gz) - min(par_gz), "bar_s": median(par_gz) + max(par_gz) - min(par_gz),
+                                       "within_bar": c["median_s"] <= median(par_gz) + max(par_gz) - min(par_gz)}
     except StepFailed as e:
         res["failed"] = e.args[0]
         res["legs_done"] = runs
@@ -520,7 +537,7 @@ def main():
         return
     if "--compress" in sys.argv:
         shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB", "24.3GB"]
-        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r12_csv_bgzf.json")
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r13_csv_bgzf_dynamic.json")
         legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
         parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
         if os.path.exists(dest):                            # one shape per call is allowed: the shapes share the file

@@ -428,6 +428,7 @@ typedef struct m6a_prep_sites_info {
     int64_t n_windows, window_bytes;
     int64_t n_bgzf_blocks, compressed_bytes;    /* BGZF inputs (below): blocks and file bytes, summed over the files; 0 for plain text */
     double ms_inflate;                          /* their inflate and CRC kernels and the newline count over the inflated text */
+    int64_t n_declined_sites;                   /* m6a_json_sites_build (below): sites that went through the host half; else 0 */
 } m6a_prep_sites_info;
 int m6a_prep_sites_build(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
                          const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
@@ -443,6 +444,46 @@ int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, 
 /* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */
 int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_kmers, int64_t *off);
 void m6a_prep_sites_free(m6a_prep_sites *p);
+
+/* `inference --loader device`: one directory of data.info + data.json -> the handle m6a_prep_sites_build returns, with the arrays
+ * m6a_io_load_sites makes of that directory (include/m6a_io.h) -- X bit for bit -- and X, site_kmers and off left in HBM for m6a_infer.
+ * Format: data.info is the loader's (a header line, then <transcript>,<position>,<start>,<end>,<n_reads>; rows with fewer than
+ * min_reads reads are dropped, the others are the sites, in file order); bytes [start, end) of data.json hold the site's record
+ *   {"<transcript>":{"<position>":{"<7-mer>":[[n, n, n, n, n, n, n, n, n, n], ...]}}}
+ * with ' ', '\n', '\r', '\t' allowed between tokens: nine features and the read id per row.  X = (float)((v - mean) / std) in f64 with
+ * the three 5-mers' factors (the norm table in m6a_io_load_sites' form), (float)v with n_norm = 0.
+ * Accepted tokens: an optional '-', digits with at most one '.', at least one digit, no exponent, at most 19 significant digits
+ * and at most 27 digits behind the point; they are converted exactly (the bits of strtod and of Python's float(); the method is
+ * stated in m6anet_amd/csrc/m6a_json.h).
+ * Decline rule: a site is REGULAR when its range lies in the file and is below 2 GB, the record follows the grammar with nothing
+ * but whitespace behind it, the first key is the row's transcript and the second the decimal of its position, there is one
+ * sequence key of 7 bytes without a backslash, every row holds exactly ten accepted tokens, there are n_reads rows, and the three
+ * 5-mers are in the norm table (n_norm > 0) and in the 66-word vocabulary.  The kernels fill the rows of regular sites.  Every other
+ * site is DECLINED -- never failed by the device -- and goes, in ascending order, through `host` (m6a_io_info_open, m6a_io_info_get,
+ * m6a_io_info_rows, m6a_io_info_free, m6a_io_last_error of libm6a_io.so), which runs the loader's own per-site body.
+ * Error rule: a declined site the loader parses (one with 1e-05 or NaN in it) has its rows copied to their place; the first one it
+ * does not parse ends the call with the loader's code (as M6A_EFORMAT / M6A_EIO) and text, which is what m6a_io_load_sites reports
+ * for the directory.  data.info's own errors and "no site with at least <min_reads> reads" are the loader's too.
+ * Refused with M6A_EINVAL before anything is opened or allocated: n_dirs > 1 (replicates stay with the host loader) and a *.m6astore
+ * path.  data.json goes up whole through the pinned chunk pair (M6A_PREP_CHUNK_KB) under the budget (M6A_PREP_BUDGET_MB, or free
+ * memory less a margin), together with everything the handle keeps; over it the call is M6A_ENOMEM and its text names --loader host.
+ * One status byte per site and the read ids come back, nothing else per read; the 7-mers the host needs for the CSV rows it reads
+ * from the pinned chunks on their way up.  Every field of m6a_prep_sites_info is filled (n_rep = 1, n_windows = 1, the BGZF fields
+ * 0, n_declined_sites), so m6a_prep_sites_fetch, _inputs and the CSV writers work on the handle.  ms: [0] upload, [3] kernels, [4]
+ * host (data.info, declined sites), [5] the copy of the read ids, [6] the upload's GB/s, [7] the whole call; [1] and [2] are 0. */
+struct m6a_io_info;
+struct m6a_io_info_table;
+typedef struct m6a_json_host_half {
+    int (*open)(const char *dir, int min_reads, struct m6a_io_info **out);
+    const struct m6a_io_info_table *(*table)(const struct m6a_io_info *info);
+    int (*rows)(struct m6a_io_info *info, const int64_t *sites, int64_t n, const char *norm_kmers, const double *norm_mean,
+                const double *norm_std, int n_norm, int n_threads, float *X, double *read_ids, uint8_t *site_kmers, char *kmer7);
+    void (*free)(struct m6a_io_info *info);
+    const char *(*error)(void);
+} m6a_json_host_half;
+int m6a_json_sites_build(int device_id, const char *const *dirs, int n_dirs, int min_reads, const char *norm_kmers,
+                         const double *norm_mean, const double *norm_std, int n_norm, const m6a_json_host_half *host, int n_threads,
+                         m6a_prep_sites **out);
 
 /* data.site_proba.csv and data.indiv_proba.csv formatted on the device: the bytes m6a_io_write_csv_n writes (include/m6a_io.h),
  *   site row   <tx>,<pos>,<n_reads>,<%.16f of (double)site_prob>,<5-mer>,<%.16f of mod_ratio>\n

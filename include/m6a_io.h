@@ -203,6 +203,34 @@ int m6a_io_bgzf_deflate(const char *text, int64_t n, char *out, int64_t cap, int
  * came out as deflate block type 0 (stored), 1 (fixed codes) and 2 (dynamic codes). */
 int m6a_io_bgzf_deflate_level(const char *text, int64_t n, int level, char *out, int64_t cap, int64_t *n_bytes, int64_t n_by_type[3]);
 
+/* The host half of m6a_json_sites_build (include/m6a.h: `inference --loader device`).
+ * m6a_io_info_open: <dir>/data.info as m6a_io_load_sites reads it for one directory -- parse_info and the min_reads filter -- as a
+ * table: the kept rows in file order with their transcript (names in order of first appearance), position, byte range and read
+ * count.  A table without rows is not an error here.  The table is owned by the handle. */
+typedef struct m6a_io_info m6a_io_info;
+typedef struct m6a_io_info_table {
+    int64_t n_sites, n_reads, n_tx;
+    const uint32_t *site_tx;        /* [S] */
+    const int64_t *pos, *start, *end, *site_reads;   /* [S] */
+    const char *tx_blob;
+    const int64_t *tx_off;          /* [n_tx + 1] */
+} m6a_io_info_table;
+int m6a_io_info_open(const char *dir, int min_reads, m6a_io_info **out);
+const m6a_io_info_table *m6a_io_info_get(const m6a_io_info *info);
+void m6a_io_info_free(m6a_io_info *info);
+/* The rows of the table `sites` [n] names (ascending), through the per-site body of m6a_io_load_sites' workers: the range check,
+ * the record, the 7-mer and 10 columns, "more reads than data.info says", the norm lookup, the count, the vocabulary.  X
+ * [sum of their reads][9] and read_ids are the sites' rows laid end to end in list order, site_kmers [n][3], kmer7 [n][7].  On the
+ * first failing site in list order the call returns the loader's code and text for it (what m6a_io_load_sites reports when that is the
+ * lowest bad site of the directory) and the arrays are undefined.  data.json is mapped by the first call. */
+int m6a_io_info_rows(m6a_io_info *info, const int64_t *sites, int64_t n, const char *norm_kmers, const double *norm_mean,
+                     const double *norm_std, int n_norm, int n_threads, float *X, double *read_ids, uint8_t *site_kmers, char *kmer7);
+/* One record through the decode core the kernels compile (m6anet_amd/csrc/m6a_json.h), on the host: 0 when the kernels take the
+ * site (values [n_reads][10] and kmer7 [7] filled; either may be NULL), else the reason it is declined for, 1..14 in the order of
+ * tests/json_statement.py's REASONS; M6A_IO_EINVAL for a null argument.  norm_kmers as m6a_io_load_sites takes them. */
+int m6a_io_json_walk(const char *record, int64_t n, const char *tx, int64_t pos, int64_t n_reads, const char *norm_kmers, int n_norm,
+                     double *values, char *kmer7);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ from .scripts import bgzip, dataprep, eventalign_inference, inference, pack  # n
 def main(argv=None):
     parser = ArgumentParser(prog="m6anet_amd")
     sub = parser.add_subparsers(dest="command", required=True)
-    sub.add_parser("inference", parents=[inference.argparser()], help="run the MI355X inference hot path")
+    sub.add_parser("inference", parents=[inference.cli_parser()], help="run the MI355X inference hot path")
     sub.add_parser("dataprep", parents=[dataprep.argparser()], help="eventalign.txt -> data.json / data.info (native, host-only)")
     sub.add_parser("pack", parents=[pack.argparser()], help="data.json / data.info -> one binary site store that later runs map")
     sub.add_parser("eventalign_inference", parents=[eventalign_inference.cli_parser()],

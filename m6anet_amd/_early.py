@@ -133,6 +133,8 @@ def maybe_start(argv):
     try:
         if not argv or argv[0] != "inference" or "M6A_RANK" in os.environ or "-h" in argv or "--help" in argv:
             return
+        if _values(argv[1:], "--loader") == ["device"]:      # refused with --gpus N (inference.check_loader): no rank is started
+            return
         g = _values(argv[1:], "--gpus")
         if not g or len(g) != 1 or int(g[0]) < 2 or int(g[0]) > 64:
             return

@@ -10,7 +10,8 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level"]
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
+           "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk"]
 _lib = None
 
 
@@ -20,6 +21,12 @@ class PrepTable(C.Structure):
                 ("n_runs", C.c_int64), ("run_tx", C.c_void_p), ("run_read", C.c_void_p), ("run_start", C.c_void_p),
                 ("run_end", C.c_void_p), ("run_npos", C.c_void_p), ("run_status", C.c_void_p), ("row_off", C.c_void_p),
                 ("n_rows", C.c_int64), ("row_pos", C.c_void_p), ("row_kmer", C.c_void_p), ("row_feat", C.c_void_p)]
+
+
+class InfoTable(C.Structure):
+    """m6a_io_info_table (include/m6a_io.h): data.info after the min_reads filter."""
+    _fields_ = [("n_sites", C.c_int64), ("n_reads", C.c_int64), ("n_tx", C.c_int64), ("site_tx", C.c_void_p), ("pos", C.c_void_p),
+                ("start", C.c_void_p), ("end", C.c_void_p), ("site_reads", C.c_void_p), ("tx_blob", C.c_void_p), ("tx_off", C.c_void_p)]
 
 
 def table_arrays(t):
@@ -95,6 +102,13 @@ def load():
     L.m6a_io_bgzf_inflate.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     L.m6a_io_bgzf_deflate.argtypes = [C.c_char_p, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.m6a_io_bgzf_deflate_level.argtypes = [C.c_char_p, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.m6a_io_info_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
+    L.m6a_io_info_get.argtypes = [vp]
+    L.m6a_io_info_get.restype = C.POINTER(InfoTable)
+    L.m6a_io_info_free.argtypes = [vp]
+    L.m6a_io_info_free.restype = None
+    L.m6a_io_info_rows.argtypes = [vp, vp, i64, C.c_char_p, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.m6a_io_json_walk.argtypes = [C.c_char_p, i64, C.c_char_p, i64, i64, C.c_char_p, i32, vp, C.c_char_p]
     _lib = L
     return L
 
@@ -312,6 +326,11 @@ class prep_sites:
                                                 -1 if window_kb is None else int(window_kb) << 10, C.byref(self._h))
         if rc != 0:
             raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        self._adopt()
+
+    def _adopt(self):
+        """the host copies and counters of the handle in self._h"""
+        L = self._L
         i = self.info = L.m6a_prep_sites_get(self._h).contents
         S, R, T = i.n_sites, i.n_reads, i.n_tx
 
@@ -327,6 +346,7 @@ class prep_sites:
         self.n_replicates, self.peak_bytes = int(i.n_rep), int(i.peak_bytes)
         self.n_windows, self.window_bytes = int(i.n_windows), int(i.window_bytes)
         self.n_bgzf_blocks, self.compressed_bytes, self.ms_inflate = int(i.n_bgzf_blocks), int(i.compressed_bytes), float(i.ms_inflate)
+        self.n_declined_sites = int(i.n_declined_sites)      # json_sites: sites that went through the host half
         tx_off = arr(i.tx_off, C.c_int64, T + 1)
         self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
         self.tx_off = tx_off
@@ -408,6 +428,36 @@ class prep_sites:
             self.close()
         except Exception:
             pass
+
+
+def json_sites(input_dir, min_reads=20, norm=None, n_threads=0, device=0):
+    """m6a_json_sites_build (libm6a_hip.so): one directory of data.info + data.json -> the arrays NativeSites([input_dir], ...) holds,
+    parsed by HIP kernels, with X, site_kmers and off left on the device -- a prep_sites, as prep_sites() returns for eventalign.txt
+    (info, off, site_tx, tx_pos, kmer7, read_ids, names, times(), fetch(), inputs(), writer(), write_csv(), close()).  Sites the
+    kernels decline are parsed by the host loader's own code (n_declined_sites counts them); its errors are raised as M6AIOError with
+    its code and text.  `input_dir` may be a list: more than one directory, or a site store, is refused (ValueError)."""
+    from . import _lib
+    dirs = [input_dir] if isinstance(input_dir, (str, bytes, os.PathLike)) else list(input_dir)
+    L, io = _lib.load(), load()
+    self = prep_sites.__new__(prep_sites)
+    self._L, self._h = L, C.c_void_p()
+    blob, mean, std, n = norm_arrays(norm)
+    host = _lib.JsonHostHalf(*(C.cast(f, C.c_void_p) for f in (io.m6a_io_info_open, io.m6a_io_info_get, io.m6a_io_info_rows, io.m6a_io_info_free,
+                                                                io.m6a_io_last_error)))
+    paths = [os.fsencode(d) for d in dirs]
+    rc = L.m6a_json_sites_build(int(device), (C.c_char_p * len(paths))(*paths), len(paths), int(min_reads), blob,
+                                None if mean is None else mean.ctypes.data, None if std is None else std.ctypes.data, n, C.byref(host),
+                                int(n_threads), C.byref(self._h))
+    if rc != 0:
+        self._h = None
+        text = L.m6a_prep_last_error().decode()
+        if rc == -1 and (len(dirs) != 1 or str(os.fsdecode(dirs[0])).endswith(".m6astore")):
+            raise ValueError(text)
+        code = prep_sites._CODES.get(rc, rc)
+        # M6A_EFORMAT / M6A_EIO carry the host loader's own text: raised as NativeSites raises it
+        raise M6AIOError(("m6a_io error %d: %s" if rc in (-7, -8) else "m6a_prep error %d: %s") % (code if rc in (-7, -8) else rc, text), code)
+    self._adopt()
+    return self
 
 
 class CsvDeclined(M6AIOError):

@@ -20,7 +20,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
-           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level"]
+           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build"]
 
 _lib = None
 
@@ -28,6 +28,11 @@ _lib = None
 class HostHalf(C.Structure):
     """m6a_prep_host_half (include/m6a.h): the libm6a_io.so functions that combine the runs the device declines."""
     _fields_ = [("rows", C.c_void_p), ("table", C.c_void_p), ("free", C.c_void_p), ("error", C.c_void_p)]
+
+
+class JsonHostHalf(C.Structure):
+    """m6a_json_host_half (include/m6a.h): the libm6a_io.so functions behind `inference --loader device`."""
+    _fields_ = [("open", C.c_void_p), ("table", C.c_void_p), ("rows", C.c_void_p), ("free", C.c_void_p), ("error", C.c_void_p)]
 
 
 class PrepSitesInfo(C.Structure):
@@ -38,7 +43,8 @@ class PrepSitesInfo(C.Structure):
                 ("tx_blob", C.c_void_p), ("tx_off", C.c_void_p), ("read_ids", C.c_void_p), ("ms", C.c_double * 8),
                 ("d2h_bytes", C.c_int64), ("n_rep", C.c_int), ("read_rep", C.c_void_p), ("peak_bytes", C.c_int64),
                 ("n_windows", C.c_int64), ("window_bytes", C.c_int64),
-                ("n_bgzf_blocks", C.c_int64), ("compressed_bytes", C.c_int64), ("ms_inflate", C.c_double)]
+                ("n_bgzf_blocks", C.c_int64), ("compressed_bytes", C.c_int64), ("ms_inflate", C.c_double),
+                ("n_declined_sites", C.c_int64)]
 
 
 class BgzfStats(C.Structure):
@@ -179,6 +185,7 @@ def load():
                                              C.POINTER(vp)]
     L.m6a_prep_sites_build_windows.argtypes = [i32, C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(HostHalf), i32,
                                                i64, C.POINTER(vp)]
+    L.m6a_json_sites_build.argtypes = [i32, C.POINTER(C.c_char_p), i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(JsonHostHalf), i32, C.POINTER(vp)]
     L.m6a_prep_sites_get.argtypes = [vp]
     L.m6a_prep_sites_get.restype = C.POINTER(PrepSitesInfo)
     L.m6a_prep_sites_fetch.argtypes = [vp, vp, vp, vp]

@@ -435,6 +435,65 @@ int n_workers(int n_threads, int64_t items)
     return (int)std::max<int64_t>(1, std::min<int64_t>(n, items));
 }
 
+// One site of the loader: its byte ranges parsed (parse_record), checked and normalised, in the order the errors are reported --
+// the range, the JSON, the 7-mer and 10 columns, "more reads than data.info says", the norm table, the count, the vocabulary.
+// X [n_reads][9], ids and rep [n_reads] and kmers [3] are the site's own rows; `kmer` receives the 7-mer.  m6a_io_load_sites'
+// workers and m6a_io_info_rows (the host half of m6a_json_sites_build) call it, so both report one text for one fault.
+int load_site(const std::vector<Mapped> &json, const SiteRef &sr, const std::unordered_map<std::string, int> &norm_ix, int n_norm,
+              const double *norm_mean, const double *norm_std, std::vector<double> &vals, float *X, double *ids, int32_t *rep, uint8_t *kmers,
+              std::string &kmer)
+{
+    const std::string tx(sr.tx);
+    kmer.clear();
+    int64_t row = 0;
+    for (size_t ip = 0; ip < sr.n_parts(); ip++) {
+        const Part &pt = sr.parts_begin()[ip];
+        const Mapped &m = json[(size_t)pt.rep];
+        if (pt.start < 0 || pt.end > (int64_t)m.n || pt.start >= pt.end)
+            return fail(M6A_IO_EFORMAT, "site %s:%lld: byte range outside data.json", tx.c_str(), (long long)sr.pos);
+        vals.clear();
+        std::string k;
+        int ncol = 0;
+        const int rc = parse_record(m.p + pt.start, m.p + pt.end, tx, sr.pos, k, vals, ncol);
+        if (rc) return rc;
+        if (kmer.empty()) kmer = k;
+        else if (kmer != k) return fail(M6A_IO_EFORMAT, "replicates disagree on the sequence of %s:%lld", tx.c_str(), (long long)sr.pos);
+        if (kmer.size() != 7 || ncol != 10)
+            // data prepared with n_neighbors != 1 (the reference's own slice for that case,
+            // data_utils.py:276-277, yields a 4-mer and fails too)
+            return fail(M6A_IO_EFORMAT, "site %s:%lld: %zu-mer with %d columns; only dataprep n_neighbors=1 (7-mer, 10 columns) is supported",
+                        tx.c_str(), (long long)sr.pos, kmer.size(), ncol);
+        const int64_t nrow = (int64_t)vals.size() / 10;
+        if (row + nrow > sr.n_reads) return fail(M6A_IO_EFORMAT, "site %s:%lld has more reads than data.info says", tx.c_str(), (long long)sr.pos);
+        double mean[9], sd[9];
+        for (int c = 0; c < 3; c++) {
+            const std::string k5 = kmer.substr((size_t)c, 5);
+            if (n_norm) {
+                auto it = norm_ix.find(k5);
+                if (it == norm_ix.end()) return fail(M6A_IO_EFORMAT, "no normalisation factors for %s", k5.c_str());
+                for (int j = 0; j < 3; j++) { mean[3 * c + j] = norm_mean[3 * it->second + j]; sd[3 * c + j] = norm_std[3 * it->second + j]; }
+            }
+        }
+        for (int64_t i = 0; i < nrow; i++) {
+            const double *v = vals.data() + 10 * i;
+            float *x = X + 9 * (row + i);
+            for (int j = 0; j < 9; j++) x[j] = n_norm ? (float)((v[j] - mean[j]) / sd[j]) : (float)v[j];
+            ids[row + i] = v[9];
+            rep[row + i] = pt.rep;
+        }
+        row += nrow;
+    }
+    if (row != sr.n_reads)
+        return fail(M6A_IO_EFORMAT, "site %s:%lld: data.info says %lld reads, data.json has %lld", tx.c_str(), (long long)sr.pos, (long long)sr.n_reads,
+                    (long long)row);
+    for (int c = 0; c < 3; c++) {
+        auto it = vocab().find(kmer.substr((size_t)c, 5));
+        if (it == vocab().end()) return fail(M6A_IO_EFORMAT, "site %s:%lld: %s is not a DRACH context", tx.c_str(), (long long)sr.pos, kmer.c_str());
+        kmers[c] = (uint8_t)it->second;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -509,60 +568,15 @@ int m6a_io_load_sites(const char *const *input_dirs, int n_dirs, int min_reads, 
         const int64_t r_lo = R * w / nw, r_hi = R * (w + 1) / nw;
         int64_t s0 = std::lower_bound(res->off.begin(), res->off.end() - 1, r_lo) - res->off.begin();
         int64_t s1 = (w == nw - 1) ? S : std::lower_bound(res->off.begin(), res->off.end() - 1, r_hi) - res->off.begin();
+        std::string kmer;
         for (int64_t s = s0; s < s1; s++) {
             const SiteRef &sr = sites[(size_t)s];
-            std::string tx(sr.tx);
-            std::string kmer;
-            int64_t row = res->off[(size_t)s];
-            for (size_t ip = 0; ip < sr.n_parts(); ip++) {
-                const Part &pt = sr.parts_begin()[ip];
-                const Mapped &m = json[(size_t)pt.rep];
-                if (pt.start < 0 || pt.end > (int64_t)m.n || pt.start >= pt.end) {
-                    rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "site %s:%lld: byte range outside data.json", tx.c_str(), (long long)sr.pos);
-                    errs[(size_t)w] = g_err; return;
-                }
-                vals.clear();
-                std::string k;
-                int ncol = 0;
-                int rc = parse_record(m.p + pt.start, m.p + pt.end, tx, sr.pos, k, vals, ncol);
-                if (rc) { rcs[(size_t)w] = rc; errs[(size_t)w] = g_err; return; }
-                if (kmer.empty()) kmer = k;
-                else if (kmer != k) { rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "replicates disagree on the sequence of %s:%lld", tx.c_str(), (long long)sr.pos); errs[(size_t)w] = g_err; return; }
-                if (kmer.size() != 7 || ncol != 10) {
-                    // data prepared with n_neighbors != 1 (the reference's own slice for that case,
-                    // data_utils.py:276-277, yields a 4-mer and fails too)
-                    rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "site %s:%lld: %zu-mer with %d columns; only dataprep n_neighbors=1 (7-mer, 10 columns) is supported",
-                                          tx.c_str(), (long long)sr.pos, kmer.size(), ncol);
-                    errs[(size_t)w] = g_err; return;
-                }
-                const int64_t nrow = (int64_t)vals.size() / 10;
-                if (row + nrow > res->off[(size_t)s + 1]) { rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "site %s:%lld has more reads than data.info says", tx.c_str(), (long long)sr.pos); errs[(size_t)w] = g_err; return; }
-                double mean[9], sd[9];
-                for (int c = 0; c < 3; c++) {
-                    const std::string k5 = kmer.substr((size_t)c, 5);
-                    if (n_norm) {
-                        auto it = norm_ix.find(k5);
-                        if (it == norm_ix.end()) { rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "no normalisation factors for %s", k5.c_str()); errs[(size_t)w] = g_err; return; }
-                        for (int j = 0; j < 3; j++) { mean[3 * c + j] = norm_mean[3 * it->second + j]; sd[3 * c + j] = norm_std[3 * it->second + j]; }
-                    }
-                }
-                for (int64_t i = 0; i < nrow; i++) {
-                    const double *v = vals.data() + 10 * i;
-                    float *x = res->X.data() + 9 * (row + i);
-                    for (int j = 0; j < 9; j++) x[j] = n_norm ? (float)((v[j] - mean[j]) / sd[j]) : (float)v[j];
-                    res->read_ids[(size_t)(row + i)] = v[9];
-                    res->read_rep[(size_t)(row + i)] = pt.rep;
-                }
-                row += nrow;
-            }
-            if (row != res->off[(size_t)s + 1]) { rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "site %s:%lld: data.info says %lld reads, data.json has %lld", tx.c_str(), (long long)sr.pos, (long long)sr.n_reads, (long long)(row - res->off[(size_t)s])); errs[(size_t)w] = g_err; return; }
-            for (int c = 0; c < 3; c++) {
-                auto it = vocab().find(kmer.substr((size_t)c, 5));
-                if (it == vocab().end()) { rcs[(size_t)w] = fail(M6A_IO_EFORMAT, "site %s:%lld: %s is not a DRACH context", tx.c_str(), (long long)sr.pos, kmer.c_str()); errs[(size_t)w] = g_err; return; }
-                res->site_kmers[(size_t)(3 * s + c)] = (uint8_t)it->second;
-            }
+            const int64_t row = res->off[(size_t)s];
+            const int rc = load_site(json, sr, norm_ix, n_norm, norm_mean, norm_std, vals, res->X.data() + 9 * row, res->read_ids.data() + row,
+                                     res->read_rep.data() + row, res->site_kmers.data() + 3 * s, kmer);
+            if (rc) { rcs[(size_t)w] = rc; errs[(size_t)w] = g_err; return; }
             res->tx_pos[(size_t)s] = sr.pos;
-            res->tx_ids[(size_t)s] = std::move(tx);
+            res->tx_ids[(size_t)s] = std::string(sr.tx);
             res->kmer5[(size_t)s] = kmer.substr(1, 5);
         }
     };
@@ -2301,4 +2315,129 @@ extern "C" int m6a_io_bgzf_deflate_level(const char *text, int64_t n, int level,
     } catch (const std::bad_alloc &) {
         return fail(M6A_IO_ENOMEM, "bgzf: out of memory");
     }
+}
+
+// ---- the host half of m6a_json_sites_build (include/m6a.h): data.info as a table, and the sites its kernels decline ----------------
+#include "m6a_json.h"
+
+struct m6a_io_info {
+    std::string dir, text;                    // the SiteRefs point into `text`
+    std::vector<SiteRef> sites;               // the rows with >= min_reads reads, in file order
+    std::vector<uint32_t> site_tx;
+    std::vector<int64_t> pos, start, end, reads, tx_off;
+    std::string blob;
+    m6a_io_info_table t{};
+    std::vector<Mapped> json;                 // data.json, mapped by the first m6a_io_info_rows
+};
+
+extern "C" int m6a_io_info_open(const char *dir, int min_reads, m6a_io_info **out)
+{
+    if (!out) return M6A_IO_EINVAL;
+    *out = nullptr;
+    if (!dir) return fail(M6A_IO_EINVAL, "no input directory");
+    try {
+        std::unique_ptr<m6a_io_info> I(new m6a_io_info);
+        I->dir = dir;
+        std::vector<SiteRef> all;
+        const int rc = parse_info(I->dir, 0, all, nullptr, I->text);
+        if (rc) return rc;
+        for (auto &s : all) if (s.n_reads >= min_reads) I->sites.push_back(std::move(s));
+        const size_t S = I->sites.size();
+        std::unordered_map<std::string_view, uint32_t> ids;               // transcripts in order of first appearance
+        I->site_tx.resize(S); I->pos.resize(S); I->start.resize(S); I->end.resize(S); I->reads.resize(S);
+        for (size_t i = 0; i < S; i++) {
+            const SiteRef &s = I->sites[i];
+            auto it = ids.find(s.tx);
+            if (it == ids.end()) {
+                it = ids.emplace(s.tx, (uint32_t)ids.size()).first;
+                I->tx_off.push_back((int64_t)I->blob.size());
+                I->blob.append(s.tx.data(), s.tx.size());
+            }
+            I->site_tx[i] = it->second;
+            I->pos[i] = s.pos; I->start[i] = s.one.start; I->end[i] = s.one.end; I->reads[i] = s.n_reads;
+            I->t.n_reads += s.n_reads;
+        }
+        I->tx_off.push_back((int64_t)I->blob.size());
+        I->t.n_sites = (int64_t)S; I->t.n_tx = (int64_t)ids.size();
+        I->t.site_tx = I->site_tx.data(); I->t.pos = I->pos.data(); I->t.start = I->start.data(); I->t.end = I->end.data();
+        I->t.site_reads = I->reads.data(); I->t.tx_blob = I->blob.data(); I->t.tx_off = I->tx_off.data();
+        *out = I.release();
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory");
+    }
+}
+
+extern "C" const m6a_io_info_table *m6a_io_info_get(const m6a_io_info *info) { return info ? &info->t : nullptr; }
+extern "C" void m6a_io_info_free(m6a_io_info *info) { delete info; }
+
+extern "C" int m6a_io_info_rows(m6a_io_info *info, const int64_t *sites, int64_t n, const char *norm_kmers, const double *norm_mean,
+                                const double *norm_std, int n_norm, int n_threads, float *X, double *read_ids, uint8_t *site_kmers, char *kmer7)
+{
+    if (!info || n < 0 || (n && (!sites || !X || !read_ids || !site_kmers || !kmer7))) return fail(M6A_IO_EINVAL, "null argument");
+    if (n_norm < 0 || (n_norm > 0 && (!norm_kmers || !norm_mean || !norm_std))) return fail(M6A_IO_EINVAL, "bad normalisation arguments");
+    const int64_t S = (int64_t)info->sites.size();
+    for (int64_t i = 0; i < n; i++)
+        if (sites[i] < 0 || sites[i] >= S || (i && sites[i] <= sites[i - 1])) return fail(M6A_IO_EINVAL, "site list: not ascending rows of the table");
+    if (!n) return M6A_IO_OK;
+    try {
+        if (info->json.empty()) {
+            std::vector<Mapped> j(1);
+            const int rc = j[0].open(info->dir + "/data.json", 0);         // mapped lazily: few sites are read
+            if (rc) return rc;
+            info->json.swap(j);
+        }
+        std::unordered_map<std::string, int> norm_ix;
+        for (int i = 0; i < n_norm; i++) norm_ix.emplace(std::string(norm_kmers + 5 * i, 5), i);
+        std::vector<int64_t> base((size_t)n + 1, 0);
+        for (int64_t i = 0; i < n; i++) base[(size_t)i + 1] = base[(size_t)i] + info->sites[(size_t)sites[i]].n_reads;
+        // workers own ascending ranges of the list and stop at their first error; the lowest failing worker's is the first in site order
+        const int nw = n_workers(n_threads, n);
+        std::vector<std::string> errs((size_t)nw);
+        std::vector<int> rcs((size_t)nw, 0);
+        auto work = [&](int w) {
+            std::vector<double> vals;
+            std::vector<int32_t> rep;
+            std::string kmer;
+            for (int64_t i = n * w / nw; i < n * (w + 1) / nw; i++) {
+                const SiteRef &sr = info->sites[(size_t)sites[i]];
+                const int64_t row = base[(size_t)i];
+                rep.resize((size_t)std::max<int64_t>(1, sr.n_reads));
+                const int rc = load_site(info->json, sr, norm_ix, n_norm, norm_mean, norm_std, vals, X + 9 * row, read_ids + row, rep.data(),
+                                         site_kmers + 3 * i, kmer);
+                if (rc) { rcs[(size_t)w] = rc; errs[(size_t)w] = g_err; return; }
+                std::memcpy(kmer7 + 7 * i, kmer.data(), 7);
+            }
+        };
+        std::vector<std::thread> th;
+        for (int w = 1; w < nw; w++) th.emplace_back(work, w);
+        work(0);
+        for (auto &t : th) t.join();
+        for (int w = 0; w < nw; w++)
+            if (rcs[(size_t)w]) { g_err = errs[(size_t)w]; return rcs[(size_t)w]; }
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory");
+    }
+}
+
+// the decode core's walk of one record on the host (m6a_json.h): what the kernels of m6a_json_sites_build take, as a reason code
+extern "C" int m6a_io_json_walk(const char *record, int64_t n, const char *tx, int64_t pos, int64_t n_reads, const char *norm_kmers, int n_norm,
+                                double *values, char *kmer7)
+{
+    if (n < 0 || (n && !record) || !tx || n_reads < 0) return fail(M6A_IO_EINVAL, "null argument");
+    std::vector<uint64_t> nk, voc;
+    auto pack = [](const char *k) { uint64_t x = 0; for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)k[j]; return x; };
+    for (int i = 0; i < n_norm; i++) nk.push_back(pack(norm_kmers + 5 * i));
+    std::sort(nk.begin(), nk.end());
+    nk.erase(std::unique(nk.begin(), nk.end()), nk.end());
+    for (const auto &kv : vocab()) voc.push_back(pack(kv.first.c_str()));          // the map is sorted as the packed keys are
+    uint64_t k7 = 0;
+    int na[3], va[3];
+    const uint8_t *p = (const uint8_t *)record;
+    const int r = m6a_json::walk(p, p + n, (const uint8_t *)tx, (int64_t)strlen(tx), pos, n_reads, n_norm ? nk.data() : nullptr, (int)nk.size(),
+                                 voc.data(), (int)voc.size(), [&](int64_t row, int j, double v) { if (values) values[10 * row + j] = v; }, &k7, na, va);
+    if (kmer7 && r != m6a_json::JR_JSON && r != m6a_json::JR_TX && r != m6a_json::JR_POS && r != m6a_json::JR_KEY)
+        for (int i = 0; i < 7; i++) kmer7[i] = (char)(k7 >> (8 * (6 - i)));
+    return r;
 }

@@ -56,6 +56,64 @@ def argparser():
     return parser
 
 
+def cli_parser():
+    """argparser() -- the flags `eventalign_inference` and the ranks of --gpus N copy from -- and the flag that is this command's own"""
+    parser = argparser()
+    parser.add_argument("--loader", choices=("host", "device"), default="host",
+                        help="who parses data.json.  host: the loader's threads, X streamed to the GPU from host memory.  device: the file "
+                             "goes up whole and HIP kernels parse it (m6a_json_sites_build), X never leaves device memory and only read ids "
+                             "and probabilities come back; the bytes written are the same.  Sites the kernels decline (an exponent, NaN, "
+                             "anything malformed) are parsed by the host loader's code, and its errors are reported as its own.  One "
+                             "--input_dir, no site store, --gpus 1.")
+    return parser
+
+
+def check_loader(args):
+    """--loader device: what it refuses, as an argument error before any rank is launched or any file is written"""
+    if getattr(args, "loader", "host") != "device":
+        return
+    import sys
+    why = None
+    if len(args.input_dir) != 1:
+        why = "--loader device takes one --input_dir (%d given): replicates are pooled by the host loader" % len(args.input_dir)
+    elif str(args.input_dir[0]).endswith(STORE_SUFFIX):
+        why = "--loader device parses data.json; %s is a site store, which --loader host maps" % args.input_dir[0]
+    elif args.gpus > 1 or "M6A_RANK" in os.environ:
+        why = "--loader device runs on one GPU (--gpus %d given)" % args.gpus
+    if why:
+        print("m6anet_amd inference: error: %s" % why, file=sys.stderr)
+        raise SystemExit(2)
+
+
+def load_on_device(args):
+    """--loader device, step 1: data.json parsed in HBM (m6a_json_sites_build); the prep_sites that holds X there"""
+    from .. import _io
+    from ..data_utils import load_norm_factors
+    return _io.json_sites(args.input_dir[0], DEFAULT_MIN_READS, load_norm_factors(args.norm_path), args.n_processes, _device_index(args.device))
+
+
+def run_on_device_sites(engine, sites, args):
+    """--loader device, the rest: inference on the handle's device pointers, 13 B per read back, the rows through the host writer
+    under the headers main() wrote -- the bytes run_inference writes for the host loader's arrays."""
+    from ..constants import N_SAMPLES
+    from ..engine import reference_written_sites
+    i = sites.info
+    engine.set_host_offsets(sites.off)
+    engine.infer_ptrs(i.X, i.site_kmers, i.off, sites.n_sites, args.num_iterations, N_SAMPLES, args.read_proba_threshold, args.seed,
+                      args.batch_size, args.save_per_batch, i.read_prob, i.site_prob, i.mod_ratio)
+    engine.sync()
+    read_prob, site_prob, mod_ratio = sites.fetch()
+    n_write = None
+    if getattr(args, "drop_unflushed_tail", False):
+        n_write = reference_written_sites(sites.n_sites, args.batch_size, args.save_per_batch)
+    sites.writer().write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=False, n_threads=args.n_processes, n_sites=n_write)
+    if os.environ.get("M6A_LOADER_TIMES"):               # phases for tools/measure_loader.py
+        import json
+        ms, d2h = sites.times()
+        print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads,
+                                            "n_declined_sites": sites.n_declined_sites, "peak_bytes": sites.peak_bytes}), flush=True)
+
+
 ENCODER_MODES = {"reference": 1, "fast": 4}           # m6a_set_encoder_variant (include/m6a.h)
 ENCODER_ENV_VALUES = ("", "auto", "reference", "general16", "csite12", "walk16", "fast")
 
@@ -125,6 +183,7 @@ def resolve_model(args):
 
 
 def main(args):
+    check_loader(args)
     weights = resolve_model(args)
     if args.gpus < 1:
         raise ValueError("--gpus must be >= 1")
@@ -144,10 +203,13 @@ def main(args):
     import threading
     made = {}
 
+    on_device = getattr(args, "loader", "host") == "device"
+
     def make_engine():
         try:
             made["engine"] = make_engine_for(args, weights, _device_index(args.device))
-            made["engine"].prepare_host_io()     # pinned staging for the host arrays the loader is producing
+            if not on_device:
+                made["engine"].prepare_host_io()     # pinned staging for the host arrays the loader is producing
         except BaseException as exc:        # re-raised on the main thread below
             made["error"] = exc
 
@@ -158,6 +220,24 @@ def main(args):
         f.write(SITE_HEADER)
     with open(os.path.join(args.out_dir, "data.indiv_proba.csv"), "w", encoding="utf-8") as g:
         g.write(INDIV_HEADER)
+    if on_device:                            # data.json is parsed in HBM while the context comes up
+        try:
+            sites = load_on_device(args)
+        except BaseException:
+            starter.join()
+            if "engine" in made:
+                made["engine"].close()
+            raise
+        starter.join()
+        try:
+            if "error" in made:
+                raise made["error"]
+            run_on_device_sites(made["engine"], sites, args)
+        finally:
+            sites.close()
+            if "engine" in made:
+                made["engine"].close()
+        return
     # --n_processes is the reference's host-parallelism flag: here it sizes the loader / writer threads
     if any(str(d).endswith(STORE_SUFFIX) for d in args.input_dir):
         if len(args.input_dir) != 1:

@@ -439,6 +439,34 @@ int m6a_prep_sites_build_multi(int device_id, const char *const *paths, int n_pa
 int m6a_prep_sites_build_windows(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
                                  int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
                                  const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, m6a_prep_sites **out);
+/* Read names (`eventalign_inference --read_names`): nanopolish and f5c run with --print-read-names write the read's UUID into field
+ * 4 where the integer read_index stands otherwise.  m6a_prep_sites_build_names is m6a_prep_sites_build_windows with one more
+ * argument; read_names = 0 is that call exactly.  With read_names != 0:
+ *   format   a read name is exactly 36 bytes, 8-4-4-4-12 lowercase hex digits with '-' at offsets 8, 13, 18 and 23 (128 bits; it
+ *            prints back as the same bytes).  Every body line with at least three tabs carries one in field 4.
+ *   twin     the twin of a named file is the same file with each name replaced by its dense index 0, 1, ... in order of first
+ *            appearance over those lines, in plain digits.  The call gives what it gives on the twin: every array of the handle is
+ *            equal, X bit for bit, and read_ids holds the indices.  A run starts where the contig bytes or the 128-bit name change;
+ *            the names are kept beside the runs (16 B per line while a window is resident, 16 B per run after it, counted against
+ *            the budget) and interned on the device after a file's last window -- a stable radix sort of the run numbers by name,
+ *            group heads, the groups ranked by their first run -- before anything reads a run's read index.  The duplicate rule,
+ *            the host half and the pooling of replicates see integers.
+ *   table    m6a_prep_sites_read_names: names16 [name_off[n_rep]][16], the names' 16 bytes (the 32 hex digits, first digit first);
+ *            file f's names in index order are rows [name_off[f], name_off[f + 1]); every file has a table of its own.  Owned by
+ *            the handle; n_rep = 0 and null pointers for a handle built without names.  One copy of 16 bytes per distinct name
+ *            comes to the host per file and is counted in d2h_bytes -- that is all the names add to it; the table also stays on
+ *            the device, where m6a_prep_sites_write_csv and both _bgzf forms print <uuid> (one file) or <uuid>_<replicate> in the
+ *            read-id column of data.indiv_proba.csv, the twin's other bytes unchanged.
+ *   errors   anything else in field 4 -- upper case, 35 or 37 bytes, a misplaced dash, a plain integer, nothing -- is M6A_EFORMAT
+ *            "<path>: read name at byte <file offset of the field>: not a lowercase UUID".  Of all format errors of the file, "short
+ *            line at byte" included, the one at the lowest file offset is reported, in windows too.
+ * BGZF input needs nothing of its own (the inflated text is the text).  m6a_prep_sites_intern_ms: the time of the interning, also
+ * part of ms[3]. */
+int m6a_prep_sites_build_names(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
+                               int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                               const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, int read_names, m6a_prep_sites **out);
+int m6a_prep_sites_read_names(const m6a_prep_sites *p, const uint8_t **names16, const int64_t **name_off, int *n_rep);
+double m6a_prep_sites_intern_ms(const m6a_prep_sites *p);
 const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p);     /* owned by p */
 int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio);
 /* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */

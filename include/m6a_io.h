@@ -59,6 +59,16 @@ int m6a_io_sites_from_arrays(int64_t n_sites, const int64_t *off, const int64_t 
 int m6a_io_sites_from_arrays_rep(int64_t n_sites, const int64_t *off, const int64_t *tx_pos, const char *tx_blob, const int64_t *tx_off,
                                  int64_t n_tx, const uint32_t *site_tx, const char *kmer5, const double *read_ids, const int32_t *read_rep,
                                  int n_rep, m6a_sites **out);
+/* Read names on sites made by m6a_io_sites_from_arrays[_rep] (m6a_prep_sites_build_names, include/m6a.h): names16 holds 16 bytes per
+ * name -- the 32 hex digits of the UUID, first digit first -- and replicate f's table is rows [name_off[f], name_off[f + 1]),
+ * name_off [n_rep + 1] from 0, n_rep the sites' own.  Copied.  From then on every CSV writer, the _n and shard forms included,
+ * prints the 36-byte UUID of row read_ids[r] of read r's replicate's table where it printed the number: `<uuid>` for one replicate,
+ * `<uuid>_<replicate>` with n_rep > 1.  A read id that is not an integer inside its table is M6A_IO_EINVAL, here, and nothing is set.
+ * m6a_io_uuid_parse / m6a_io_uuid_format: the core the HIP kernels compile (m6anet_amd/csrc/m6a_uuid.h) -- the field [p, p + n) as
+ * 16 such bytes (returns 1) or refused (0: anything but 8-4-4-4-12 lowercase hex digits); 16 bytes as the 36, no terminator. */
+int m6a_io_sites_set_read_names(m6a_sites *s, const uint8_t *names16, const int64_t *name_off, int n_rep);
+int m6a_io_uuid_parse(const char *p, int64_t n, uint8_t *out16);
+void m6a_io_uuid_format(const uint8_t *in16, char *out36);
 
 /* Binary site store: everything m6a_io_load_sites produces -- normalised features,
  * k-mer ids, CSR offsets, ids -- in one file, so a dataset is parsed from data.json ONCE and every later run maps it

@@ -10,7 +10,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
-           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
+           "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_sites_set_read_names", "m6a_io_uuid_parse", "m6a_io_uuid_format", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
            "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk"]
 _lib = None
 
@@ -99,6 +99,10 @@ def load():
     L.m6a_io_runs_rows.argtypes = [C.c_char_p, i64, vp, vp, vp, i32, i32, C.POINTER(vp)]
     L.m6a_io_sites_from_arrays.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, C.POINTER(vp)]
     L.m6a_io_sites_from_arrays_rep.argtypes = [i64, vp, vp, C.c_char_p, vp, i64, vp, C.c_char_p, vp, vp, i32, C.POINTER(vp)]
+    L.m6a_io_sites_set_read_names.argtypes = [vp, vp, vp, i32]
+    L.m6a_io_uuid_parse.argtypes = [C.c_char_p, i64, vp]
+    L.m6a_io_uuid_format.argtypes = [vp, vp]
+    L.m6a_io_uuid_format.restype = None
     L.m6a_io_bgzf_inflate.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     L.m6a_io_bgzf_deflate.argtypes = [C.c_char_p, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.m6a_io_bgzf_deflate_level.argtypes = [C.c_char_p, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
@@ -302,11 +306,15 @@ class prep_sites:
     window_kb: parse each file in windows of that many KB instead of keeping it resident (m6a_prep_sites_build_windows; the arrays
     are the same), 0 for resident, None for what M6A_PREP_WINDOW_KB says; n_windows and window_bytes say what was done.  A file that
     is BGZF (by content) is inflated on the device and gives the arrays of its text; n_bgzf_blocks, compressed_bytes and ms_inflate
-    say so (0 for plain files), and windows over such a file are refused.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
+    say so (0 for plain files), and windows over such a file are refused.  read_names=True (m6a_prep_sites_build_names): field 4 of
+    every file is the read's UUID (nanopolish / f5c --print-read-names), not an index; the arrays are those of the twin file whose
+    names are replaced by 0, 1, ... in order of first appearance, read_ids holds those indices, and `read_names` is (names, offsets):
+    names uint8 [n][16] -- the UUIDs' bytes, file f's in index order at rows [offsets[f], offsets[f + 1]) -- and offsets int64
+    [n_replicates + 1]; None without the flag.  n_read_names and ms_intern count the names and the interning.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
     _CODES = prep_on_device._CODES
 
     def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0,
-                 window_kb=None):
+                 window_kb=None, read_names=False):
         if window_kb is not None and window_kb < 0:
             raise ValueError("window_kb must be 0 or more, not %r" % (window_kb,))
         from . import _lib
@@ -317,13 +325,13 @@ class prep_sites:
                              C.cast(io.m6a_io_rows_free, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
         tail = (int(readcount_min), int(readcount_max), int(min_segment_count), blob, None if mean is None else mean.ctypes.data,
                 None if std is None else std.ctypes.data, n, C.byref(host), int(n_threads))
-        if isinstance(eventalign, (str, bytes, os.PathLike)) and window_kb is None:
+        if isinstance(eventalign, (str, bytes, os.PathLike)) and window_kb is None and not read_names:
             rc = L.m6a_prep_sites_build(int(device_id), os.fsencode(eventalign), *tail, C.byref(self._h))
         else:                                # one path with a window size: the one-file job, asked through the list's entry point
             one = isinstance(eventalign, (str, bytes, os.PathLike))
             paths = [os.fsencode(e) for e in ([eventalign] if one else eventalign)]
-            rc = L.m6a_prep_sites_build_windows(int(device_id), (C.c_char_p * len(paths))(*paths), len(paths), *tail,
-                                                -1 if window_kb is None else int(window_kb) << 10, C.byref(self._h))
+            head = (int(device_id), (C.c_char_p * len(paths))(*paths), len(paths), *tail, -1 if window_kb is None else int(window_kb) << 10)
+            rc = L.m6a_prep_sites_build_names(*head, 1, C.byref(self._h)) if read_names else L.m6a_prep_sites_build_windows(*head, C.byref(self._h))
         if rc != 0:
             raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
         self._adopt()
@@ -351,6 +359,13 @@ class prep_sites:
         self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
         self.tx_off = tx_off
         self.names = [self.tx_blob[tx_off[t]:tx_off[t + 1]].decode() for t in range(T)]
+        names16, name_off, n_tab = C.c_void_p(), C.c_void_p(), C.c_int()
+        L.m6a_prep_sites_read_names(self._h, C.byref(names16), C.byref(name_off), C.byref(n_tab))
+        self.read_names, self.n_read_names, self.ms_intern = None, 0, float(L.m6a_prep_sites_intern_ms(self._h))
+        if n_tab.value:
+            offsets = arr(name_off, C.c_int64, n_tab.value + 1)
+            self.n_read_names = int(offsets[-1])
+            self.read_names = (arr(names16, C.c_uint8, 16 * self.n_read_names).reshape(self.n_read_names, 16), offsets)
 
     def times(self):
         """Phase milliseconds (include/m6a.h) and the device-to-host bytes so far."""
@@ -381,7 +396,10 @@ class prep_sites:
         """The sites as an m6a_sites for the CSV writers (NativeSites.from_arrays)."""
         k5 = np.ascontiguousarray(self.kmer7[:, 1:6])
         rep = (self.read_rep, self.n_replicates) if self.n_replicates > 1 else (None, 1)
-        return NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids, *rep)
+        w = NativeSites.from_arrays(self.off, self.tx_pos, self.tx_blob, self.tx_off, self.site_tx, k5, self.read_ids, *rep)
+        if self.read_names is not None:
+            w.set_read_names(*self.read_names)
+        return w
 
     def write_csv(self, out_dir, write_header=True, n_threads=0, n_sites=None, compress=False, level=1):
         """m6a_prep_sites_write_csv: both CSV files formatted on the device from the handle's arrays (after the engine has filled
@@ -569,6 +587,16 @@ class NativeSites:
                   np.ascontiguousarray(site_tx, np.uint32), k5, np.ascontiguousarray(read_ids, np.float64),
                   None if read_rep is None else np.ascontiguousarray(read_rep, np.int32), n_rep)
         return cls(_arrays=arrays)
+
+    def set_read_names(self, names16, name_off):
+        """m6a_io_sites_set_read_names, on sites made by from_arrays: names16 uint8 [n][16] and name_off int64 [n_replicates + 1]
+        (prep_sites.read_names).  The writers then print the UUID of row read_ids[r] of read r's replicate's table, `_<replicate>`
+        behind it with several replicates; a read id that is no index into its table is M6AIOError (EINVAL)."""
+        names = np.ascontiguousarray(names16, np.uint8)
+        off = np.ascontiguousarray(name_off, np.int64)
+        if off.size != self.n_replicates + 1 or names.size != 16 * int(off[-1]):
+            raise ValueError("name_off must hold n_replicates + 1 offsets and names16 16 bytes per name")
+        _chk(self._L.m6a_io_sites_set_read_names(self._h, names.ctypes.data, off.ctypes.data, int(self.n_replicates)))
 
     def tx_id(self, i):
         return self._L.m6a_io_tx_id(self._h, i).decode()

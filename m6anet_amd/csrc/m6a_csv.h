@@ -6,6 +6,8 @@
 // '%s,%d,%s,%.16f' (m6anet/utils/inference_utils.py:62,66):
 //   site row   <tx>,<pos>,<n_reads>,<%.16f of (double)site_prob>,<5-mer>,<%.16f of mod_ratio>\n
 //   read row   <tx>,<pos>,<id>,<%.16f of (double)read_prob>\n      <id> = <int>.0 (one file) or <int>_<replicate> (pooled)
+//              a handle built with read names (m6a_prep_sites_build_names): <id> = <uuid> or <uuid>_<replicate>, the 36 bytes
+//              m6a_uuid.h formats from row <int> of the read's replicate's table
 // Rows have different lengths, so a range of sites takes three steps:
 //   lengths    csv_len_kernel, a wave per site: the length of its site row and the summed length of its read rows, and the count
 //              of values the device DECLINES -- exactly these: a finite probability or ratio that is negative (-0.0 too) or >= 2;
@@ -52,6 +54,8 @@ struct CsvDev {                            // device pointers; sites and reads a
     int K;                                 // replicates; 1: ids print as <int>.0
     const float *read_prob, *site_prob;    // [R], [S]
     const double *mod_ratio;               // [S]
+    const uint8_t *names16;                // read names, 16 bytes each, or null: replicate f's are rows [name_off[f], name_off[f + 1])
+    const int64_t *name_off;               // [K + 1]
 };
 
 __device__ inline int csv_digits(uint64_t v)
@@ -156,14 +160,28 @@ struct CsvReadRows {
         name_len = d.tx_off[d.site_tx[i] + 1] - t0;
         head_len = 2 + csv_i64_len(pos);
     }
+    // the table row of read r's name, or -1: the id is not an index into its replicate's table (the build makes none such)
+    __device__ int64_t name_row(double id, int rep) const
+    {
+        if (!csv_id_ok(id)) return -1;
+        const int64_t k = d.name_off[rep] + (int64_t)id;
+        return k < d.name_off[rep + 1] ? k : -1;
+    }
     __device__ int64_t len(int64_t j, unsigned &declined) const
     {
         const int64_t r = r0 + j;
         const double id = d.ids[r];
-        const bool ok = csv_id_ok(id);
-        if (!ok) declined++;
-        int n = csv_digits(ok ? (uint64_t)id : 0);
-        n += d.K > 1 ? 1 + csv_digits((uint64_t)csv_read_rep(d, site, r, j)) : 2;
+        int n;
+        if (d.names16) {
+            const int rep = d.K > 1 ? csv_read_rep(d, site, r, j) : 0;
+            if (name_row(id, rep) < 0) declined++;
+            n = m6a_uuid::kLen + (d.K > 1 ? 1 + csv_digits((uint64_t)rep) : 0);
+        } else {
+            const bool ok = csv_id_ok(id);
+            if (!ok) declined++;
+            n = csv_digits(ok ? (uint64_t)id : 0);
+            n += d.K > 1 ? 1 + csv_digits((uint64_t)csv_read_rep(d, site, r, j)) : 2;
+        }
         n += 2 + csv_f16_len((uint64_t)__double_as_longlong((double)d.read_prob[r]), declined);
         return name_len + head_len + n;
     }
@@ -177,17 +195,24 @@ struct CsvReadRows {
         o += csv_put_i64(o, pos);
         *o++ = ',';
         const double id = d.ids[r];
-        const uint64_t u = csv_id_ok(id) ? (uint64_t)id : 0;
-        const int nd = csv_digits(u);
-        csv_put_u64(o, u, nd);
-        o += nd;
+        if (d.names16) {
+            const int64_t k = name_row(id, d.K > 1 ? csv_read_rep(d, site, r, j) : 0);
+            const m6a_uuid::Name nm = k < 0 ? m6a_uuid::Name{0, 0} : m6a_uuid::from_bytes(d.names16 + k * 16);
+            m6a_uuid::format(nm.hi, nm.lo, o);
+            o += m6a_uuid::kLen;
+        } else {
+            const uint64_t u = csv_id_ok(id) ? (uint64_t)id : 0;
+            const int nd = csv_digits(u);
+            csv_put_u64(o, u, nd);
+            o += nd;
+        }
         if (d.K > 1) {
             *o++ = '_';
             const uint64_t rep = (uint64_t)csv_read_rep(d, site, r, j);
             const int nr = csv_digits(rep);
             csv_put_u64(o, rep, nr);
             o += nr;
-        } else {
+        } else if (!d.names16) {
             *o++ = '.';
             *o++ = '0';
         }
@@ -460,7 +485,7 @@ int csv_write_impl(m6a_prep_sites &P, const char *out_dir, int write_header, int
     if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)I.n_tx + 1, "transcript names"))) return rc;
     if ((rc = h2d(blob, (const uint8_t *)I.tx_blob, nblob, s)) || (rc = h2d(tx_off, I.tx_off, I.n_tx ? (size_t)I.n_tx + 1 : 0, s))) return rc;
     const CsvDev d{I.off, P.csv_tx, P.csv_pos, P.csv_k7, 7, 1, blob, tx_off, P.csv_ids, nullptr, I.n_rep > 1 ? P.csv_parts : nullptr,
-                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio};
+                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio, P.csv_names, P.csv_name_off};
     double t0 = now_ms();
     CsvPlan plan;
     if ((rc = csv_plan(m, d, 0, S, s, plan))) return rc;
@@ -606,7 +631,7 @@ int csv_format_impl(int device_id, const m6a_csv_arrays &a, int64_t A, int64_t B
         (rc = h2d(rp, a.read_prob, (size_t)R, s)) || (rc = h2d(sp, a.site_prob, (size_t)S, s)) ||
         (a.n_rep > 1 && (rc = h2d(rep, a.read_rep, (size_t)R, s))))
         return rc;
-    const CsvDev d{off, tx, pos, k5, 5, 0, blob, tx_off, ids, rep, nullptr, a.n_rep, rp, sp, mr};
+    const CsvDev d{off, tx, pos, k5, 5, 0, blob, tx_off, ids, rep, nullptr, a.n_rep, rp, sp, mr, nullptr, nullptr};
     CsvPlan plan;
     if ((rc = csv_plan(m, d, A, B, s, plan))) return rc;
     const int64_t ns = plan.site[(size_t)(B - A)], ni = plan.indiv[(size_t)(B - A)];

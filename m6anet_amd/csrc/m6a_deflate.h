@@ -952,7 +952,7 @@ int csv_write_bgzf_impl(m6a_prep_sites &P, const char *out_dir, int write_header
     if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)I.n_tx + 1, "transcript names"))) return rc;
     if ((rc = h2d(blob, (const uint8_t *)I.tx_blob, nblob, s)) || (rc = h2d(tx_off, I.tx_off, I.n_tx ? (size_t)I.n_tx + 1 : 0, s))) return rc;
     const CsvDev d{I.off, P.csv_tx, P.csv_pos, P.csv_k7, 7, 1, blob, tx_off, P.csv_ids, nullptr, I.n_rep > 1 ? P.csv_parts : nullptr,
-                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio};
+                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio, P.csv_names, P.csv_name_off};
     double t0 = now_ms();
     CsvPlan plan;
     if ((rc = csv_plan(m, d, 0, S, s, plan))) return rc;

@@ -2,6 +2,7 @@
 // Host-only C++17; parsing and formatting are spread over std::threads by site range.
 #include "m6a_io.h"
 #include "m6a_host_cpus.h"
+#include "m6a_uuid.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -283,6 +284,8 @@ struct m6a_sites {
     std::vector<int64_t> off, tx_pos;
     RawBuf<double> read_ids;
     RawBuf<int32_t> read_rep;
+    std::vector<uint8_t> names16;           // m6a_io_sites_set_read_names: the writers print these where they printed read ids
+    std::vector<int64_t> name_off;          // [n_rep + 1], or empty: no names
     std::vector<std::string> tx_ids, kmer5;
     // what the accessors and the writers read: the owned buffers above after m6a_io_load_sites, or the file
     // mapping of a binary site store (m6a_io_open_store) -- zero-copy, the kernel pages it in on first touch
@@ -796,6 +799,48 @@ int m6a_io_sites_from_arrays_rep(int64_t n_sites, const int64_t *off, const int6
     return M6A_IO_OK;
 }
 
+int m6a_io_sites_set_read_names(m6a_sites *s, const uint8_t *names16, const int64_t *name_off, int n_rep)
+{
+    if (!s || !name_off) return fail(M6A_IO_EINVAL, "null argument");
+    if (s->map || s->vX) return fail(M6A_IO_EINVAL, "read names go on sites made by m6a_io_sites_from_arrays");
+    if (n_rep != s->n_rep) return fail(M6A_IO_EINVAL, "%d tables of names for %d replicates", n_rep, s->n_rep);
+    if (name_off[0] != 0) return fail(M6A_IO_EINVAL, "name_off[0] must be 0");
+    for (int f = 0; f < n_rep; f++)
+        if (name_off[f + 1] < name_off[f]) return fail(M6A_IO_EINVAL, "name_off[] must be non-decreasing");
+    if (name_off[n_rep] && !names16) return fail(M6A_IO_EINVAL, "null argument");
+    for (int64_t r = 0; r < s->nR; r++) {
+        const double id = s->vIds[r];
+        const int32_t f = s->n_rep > 1 ? s->vRep[r] : 0;
+        const int64_t n = name_off[f + 1] - name_off[f];
+        if (!(id == std::floor(id)) || std::signbit(id) || !(id < (double)n))
+            return fail(M6A_IO_EINVAL, "read %lld: id %.17g is not an index into the %lld names of replicate %d", (long long)r, id, (long long)n, (int)f);
+    }
+    try {
+        std::vector<uint8_t> names(names16, names16 + name_off[n_rep] * 16);
+        std::vector<int64_t> off(name_off, name_off + n_rep + 1);
+        s->names16.swap(names);
+        s->name_off.swap(off);
+        s->csv_keep.clear();
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory for %lld read names", (long long)name_off[n_rep]);
+    }
+    return M6A_IO_OK;
+}
+
+int m6a_io_uuid_parse(const char *p, int64_t n, uint8_t *out16)
+{
+    m6a_uuid::Name nm;
+    if (!p || !out16 || n < 0 || !m6a_uuid::parse((const uint8_t *)p, (const uint8_t *)p + n, &nm)) return 0;
+    m6a_uuid::to_bytes(nm.hi, nm.lo, out16);
+    return 1;
+}
+
+void m6a_io_uuid_format(const uint8_t *in16, char *out36)
+{
+    const m6a_uuid::Name nm = m6a_uuid::from_bytes(in16);
+    m6a_uuid::format(nm.hi, nm.lo, out36);
+}
+
 int m6a_io_format_f16(double v, char *buf336) { const int k = format_f16(v, buf336); buf336[k] = 0; return k; }
 
 int m6a_io_write_csv(const m6a_sites *s, const char *out_dir, const float *read_prob, const float *site_prob,
@@ -856,7 +901,16 @@ void format_rows(const m6a_sites *s, int64_t i0, int64_t i1, const float *read_p
             b += head;
             k = 0;
             const double id = s->vIds[r];
-            if (s->n_rep > 1) {
+            if (!s->name_off.empty()) {                                      // a read name: set_read_names checked every id
+                const int32_t f = s->n_rep > 1 ? s->vRep[r] : 0;
+                const m6a_uuid::Name nm = m6a_uuid::from_bytes(s->names16.data() + (s->name_off[(size_t)f] + (int64_t)id) * 16);
+                m6a_uuid::format(nm.hi, nm.lo, buf + k);
+                k += m6a_uuid::kLen;
+                if (s->n_rep > 1) {
+                    buf[k++] = '_';
+                    k += format_i64((long long)f, buf + k);
+                }
+            } else if (s->n_rep > 1) {
                 k += format_i64((long long)id, buf + k);
                 buf[k++] = '_';
                 k += format_i64((long long)s->vRep[r], buf + k);

@@ -40,6 +40,7 @@
 
 #include "m6a.h"
 #include "m6a_io.h"
+#include "m6a_uuid.h"
 
 namespace {
 
@@ -210,15 +211,22 @@ __device__ inline bool dev_float(const uint8_t *f, int64_t p, int64_t e, double 
     return true;
 }
 
-// one lane per body line i = first .. nlines - 1 (first = 1: line 0 is the header; 0 in a window behind the first, which has none)
+using Name = m6a_uuid::Name;                // a read name (--read_names): 128 bits, kept beside the line and run records, never in them
+
+// one lane per body line i = first .. nlines - 1 (first = 1: line 0 is the header; 0 in a window behind the first, which has none).
+// NAMES (m6a_prep_sites_build_names): field 4 is a read name, parsed by m6a_uuid.h into lname[i]; `read` stays 0 until the names
+// are interned.  bad_at is then twice the offset, plus 1 for a name that is no UUID (its field's offset) and 0 for a short line
+// (its line's): one atomicMin finds the lowest of either kind.
+template <bool NAMES>
 __global__ void line_kernel(const uint8_t *__restrict__ f, int64_t n, const int64_t *__restrict__ nl, int64_t NL, int64_t nlines, int64_t first,
-                            LineEv *__restrict__ ev, unsigned long long *__restrict__ bad_at)
+                            LineEv *__restrict__ ev, unsigned long long *__restrict__ bad_at, Name *__restrict__ lname)
 {
     const int64_t i = first + (int64_t)blockIdx.x * kBlk + threadIdx.x;
     if (i >= nlines) return;
     const int64_t p = line_start(nl, i), le = line_end(nl, NL, n, i);
     LineEv r;
     r.flags = 0; r.position = r.length = r.kmer = r.read = 0; r.mean = r.sd = r.len_s = 0; r.contig_len = 0;
+    Name nm{0, 0};
     int64_t fe[16];
     int nf = 0, ntab = 0;
     for (int64_t q = p; q < le; ++q)
@@ -227,8 +235,9 @@ __global__ void line_kernel(const uint8_t *__restrict__ f, int64_t n, const int6
     // index_range: no tab -> skipped; fewer than three -> M6A_IO_EFORMAT at the line's offset
     if (ntab >= 1) {
         r.flags |= L_TAB;
-        if (ntab < 3) atomicMin(bad_at, (unsigned long long)p);
-        else r.read = dev_atoll(f, fe[2] + 1, n);
+        if (ntab < 3) atomicMin(bad_at, (unsigned long long)(NAMES ? 2 * p : p));
+        else if (!NAMES) r.read = dev_atoll(f, fe[2] + 1, n);
+        else if (!m6a_uuid::parse(f + fe[2] + 1, f + fe[3], &nm)) atomicMin(bad_at, (unsigned long long)(2 * (fe[2] + 1) + 1));
         r.contig_len = (int32_t)min<int64_t>(fe[0] - p, 0x7fffffff);
         if (fe[0] - p > 0x7fffffff) r.flags |= L_HOST;
     }
@@ -254,6 +263,7 @@ __global__ void line_kernel(const uint8_t *__restrict__ f, int64_t n, const int6
         }
     }
     ev[i] = r;
+    if (NAMES) lname[i] = nm;
 }
 
 __global__ void flag_kernel(const LineEv *__restrict__ ev, int64_t nlines, int64_t first, int64_t *__restrict__ out)
@@ -276,16 +286,18 @@ __device__ inline bool same_bytes(const uint8_t *f, int64_t a, int64_t b, int64_
     return true;
 }
 
-// valid line j starts a run when its contig bytes or its read index differ from valid line j - 1's
+// valid line j starts a run when its contig bytes or its read index (NAMES: its 128-bit read name) differ from valid line j - 1's
+template <bool NAMES>
 __global__ void newrun_kernel(const uint8_t *__restrict__ f, const int64_t *__restrict__ nl, const LineEv *__restrict__ ev,
-                              const int64_t *__restrict__ vline, int64_t NV, int64_t *__restrict__ out)
+                              const int64_t *__restrict__ vline, int64_t NV, int64_t *__restrict__ out, const Name *__restrict__ lname)
 {
     const int64_t j = (int64_t)blockIdx.x * kBlk + threadIdx.x;
     if (j >= NV) return;
     if (j == 0) { out[0] = 1; return; }
     const int64_t a = vline[j - 1], b = vline[j];
     const LineEv &x = ev[a], &y = ev[b];
-    out[j] = x.read != y.read || x.contig_len != y.contig_len || !same_bytes(f, line_start(nl, a), line_start(nl, b), y.contig_len) ? 1 : 0;
+    const bool other = NAMES ? lname[a].hi != lname[b].hi || lname[a].lo != lname[b].lo : x.read != y.read;
+    out[j] = other || x.contig_len != y.contig_len || !same_bytes(f, line_start(nl, a), line_start(nl, b), y.contig_len) ? 1 : 0;
 }
 
 struct RunDev {                            // one run: lines [l0, l1], bytes [start, end)
@@ -293,8 +305,11 @@ struct RunDev {                            // one run: lines [l0, l1], bytes [st
     int32_t contig_len, status, same_contig;
 };
 
+// NAMES: a run's name is its first line's
+template <bool NAMES>
 __global__ void runs_kernel(const uint8_t *__restrict__ f, int64_t n, const int64_t *__restrict__ nl, int64_t NL, const LineEv *__restrict__ ev,
-                            const int64_t *__restrict__ vline, int64_t NV, const int64_t *__restrict__ nr_scan, RunDev *__restrict__ runs)
+                            const int64_t *__restrict__ vline, int64_t NV, const int64_t *__restrict__ nr_scan, RunDev *__restrict__ runs,
+                            const Name *__restrict__ lname, Name *__restrict__ rname)
 {
     const int64_t j = (int64_t)blockIdx.x * kBlk + threadIdx.x;
     if (j >= NV) return;
@@ -312,6 +327,7 @@ __global__ void runs_kernel(const uint8_t *__restrict__ f, int64_t n, const int6
         R.status = M6A_PREP_RUN_OK;
         R.npos = 0;
         R.same_contig = 0;
+        if (NAMES) rname[r] = lname[li];
         if (r > 0) {                                       // same contig bytes as the run before (transcript ids on the host)
             const int64_t pl = vline[j - 1];
             R.same_contig = ev[pl].contig_len == ev[li].contig_len && same_bytes(f, line_start(nl, pl), R.start, ev[li].contig_len);
@@ -648,8 +664,10 @@ int read_index(const char *path, std::vector<std::string> &names, std::vector<ui
 }
 
 // runs of the valid lines from line `first` on (index_range): runs[NR + 1], in `m`; the three work arrays are noted in `scratch`
+// lname (--read_names): the lines' names; the runs' names are then allocated like the runs and returned in rname
 int find_runs(DevMem &m, hipStream_t s, const uint8_t *df, int64_t n, const int64_t *nl, int64_t NL, int64_t nlines, int64_t first,
-              const LineEv *ev, RunDev *&runs, int64_t &NR, std::vector<const void *> *scratch)
+              const LineEv *ev, RunDev *&runs, int64_t &NR, std::vector<const void *> *scratch, const Name *lname = nullptr,
+              Name **rname = nullptr)
 {
     int rc;
     int64_t *vflag, NV = 0;
@@ -664,14 +682,17 @@ int find_runs(DevMem &m, hipStream_t s, const uint8_t *df, int64_t n, const int6
     compact_kernel<<<grid(nlines), kBlk, 0, s>>>(vflag, nlines, first, ev, vline);
     PCHK(hipGetLastError());
     if (NV > 0) {
-        newrun_kernel<<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr);
+        if (lname) newrun_kernel<true><<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr, lname);
+        else newrun_kernel<false><<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr, nullptr);
         PCHK(hipGetLastError());
     }
     if ((rc = scan_total(m, nr, NV, s, NR))) return rc;     // nr[j] = run of valid line j (exclusive scan of the starts) ...
     // ... so valid line j's run is nr[j + 1] - 1: shift by one with an inclusive view
     if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
+    if (lname && (rc = m.alloc(*rname, (size_t)NR + 1, "read names"))) return rc;
     if (NV > 0) {
-        runs_kernel<<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs);
+        if (lname) runs_kernel<true><<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs, lname, *rname);
+        else runs_kernel<false><<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs, nullptr, nullptr);
         PCHK(hipGetLastError());
     }
     return M6A_OK;
@@ -712,6 +733,8 @@ struct Front {
     double *row_feat = nullptr;
     std::vector<const void *> scratch;      // the file, its newlines, lines and combined positions: nothing after the windows reads them
     bool bgzf_ok = false;                   // in: the caller takes BGZF input (sites_impl)
+    bool read_names = false;                // in: field 4 is a read name (m6a_prep_sites_build_names)
+    Name *rnames = nullptr;                 // out, read_names: [NR] the runs' names; RunDev.read is 0 until they are interned
     const uint8_t *text = nullptr;          // out, BGZF input: the inflated text, NOT in scratch -- the caller reads names and runs from it
     int64_t n_blocks = 0, comp_bytes = 0;   // out, BGZF input
     double ms_inflate = 0;
@@ -725,6 +748,13 @@ int bgzf_gather(DevMem &m, hipStream_t s, const uint8_t *text, int64_t n_text, c
                 std::vector<uint8_t> &out);
 
 int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
+
+// the format error line_kernel found lowest in the text that starts at file byte b
+int bad_line(const char *path, bool names, int64_t b, unsigned long long bad_at)
+{
+    if (names && (bad_at & 1)) return prep_fail(M6A_EFORMAT, "%s: read name at byte %lld: not a lowercase UUID", path, (long long)(b + (int64_t)(bad_at >> 1)));
+    return prep_fail(M6A_EFORMAT, "%s: short line at byte %lld", path, (long long)(b + (int64_t)(names ? bad_at >> 1 : bad_at)));
+}
 
 // M6A_PREP_WINDOW_KB as a window size in bytes (unset, 0 or not a number: the whole file)
 int64_t window_from_env()
@@ -850,20 +880,23 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     if ((rc = m.alloc(bad, 1, "flags"))) return rc;
     const unsigned long long none = ~0ull;
     PCHK(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, s));
+    Name *lname = nullptr;
+    if (F.read_names && (rc = m.alloc(lname, (size_t)std::max<int64_t>(nlines, 1), "read names"))) return rc;
     if (nlines > 1) {
-        line_kernel<<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, 1, ev, bad);
+        if (lname) line_kernel<true><<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, 1, ev, bad, lname);
+        else line_kernel<false><<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, 1, ev, bad, nullptr);
         PCHK(hipGetLastError());
     }
     unsigned long long bad_at = none;
     PCHK(hipMemcpyAsync(&bad_at, bad, sizeof bad_at, hipMemcpyDeviceToHost, s));
     g_d2h += (int64_t)sizeof bad_at;
     PCHK(hipStreamSynchronize(s));
-    if (!index_path && bad_at != none) return prep_fail(M6A_EFORMAT, "%s: short line at byte %lld", path, (long long)bad_at);
+    if (!index_path && bad_at != none) return bad_line(path, lname != nullptr, 0, bad_at);
 
     int64_t NR = 0;
     RunDev *runs = nullptr;
     if (!index_path) {
-        if ((rc = find_runs(m, s, df, n, nl, NL, nlines, 1, ev, runs, NR, &F.scratch))) return rc;
+        if ((rc = find_runs(m, s, df, n, nl, NL, nlines, 1, ev, runs, NR, &F.scratch, lname, &F.rnames))) return rc;
     } else {
         NR = (int64_t)istart->size();
         if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
@@ -894,6 +927,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     ms[2] = now_ms() - t1;
     F.NR = NR; F.NROW = NROW; F.runs = runs; F.row_off = row_off; F.row_pos = drow_pos; F.row_kmer = drow_kmer; F.row_feat = drow_feat;
     F.scratch.insert(F.scratch.end(), {bcnt, nl, ev, bad, pos_off, ps});
+    if (lname) F.scratch.push_back(lname);
     if (gz) F.text = df;
     else F.scratch.push_back(df);
     return M6A_OK;
@@ -1000,6 +1034,8 @@ struct Win {                                // one window: file bytes [b, b + n)
     int64_t *nl = nullptr;
     LineEv *ev = nullptr;
     RunDev *runs = nullptr;
+    bool read_names = false;                // in: --read_names
+    Name *rnames = nullptr;                 // [NR] then
 };
 
 // newline scan, lines and runs of a window, and its cut: n, keep (the runs that stay) and next (b of the window after) -- or grow
@@ -1041,17 +1077,20 @@ int window_cut(DevMem &m, hipStream_t s, const char *path, Win &V, double *ms)
     if ((rc = m.alloc(bad, 1, "flags"))) return rc;
     const unsigned long long none = ~0ull;
     PCHK(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, s));
+    Name *lname = nullptr;
+    if (V.read_names && (rc = m.alloc(lname, (size_t)std::max<int64_t>(V.nlines, 1), "read names"))) return rc;
     if (V.nlines > V.first) {
-        line_kernel<<<grid(V.nlines - V.first), kBlk, 0, s>>>(V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, bad);
+        if (lname) line_kernel<true><<<grid(V.nlines - V.first), kBlk, 0, s>>>(V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, bad, lname);
+        else line_kernel<false><<<grid(V.nlines - V.first), kBlk, 0, s>>>(V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, bad, nullptr);
         PCHK(hipGetLastError());
     }
     unsigned long long bad_at = none;
     PCHK(hipMemcpyAsync(&bad_at, bad, sizeof bad_at, hipMemcpyDeviceToHost, s));
     g_d2h += (int64_t)sizeof bad_at;
     PCHK(hipStreamSynchronize(s));
-    // every line in front of this window has been seen, so this is the file's first short line, as whole-file mode reports it
-    if (bad_at != none) return prep_fail(M6A_EFORMAT, "%s: short line at byte %lld", path, (long long)(V.b + (int64_t)bad_at));
-    if ((rc = find_runs(m, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.runs, V.NR, nullptr))) return rc;
+    // every line in front of this window has been seen, so this is the file's first bad line, as whole-file mode reports it
+    if (bad_at != none) return bad_line(path, lname != nullptr, V.b, bad_at);
+    if ((rc = find_runs(m, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.runs, V.NR, nullptr, lname, &V.rnames))) return rc;
     V.keep = V.NR;
     V.next = V.b + V.n;
     if (!V.last && V.NR > 0) {                               // the last run may go on in the next window: that one starts with it
@@ -1069,7 +1108,7 @@ int window_cut(DevMem &m, hipStream_t s, const char *path, Win &V, double *ms)
 
 // what stays of the windows: the job's runs, their row counts and the three row arrays, each grown at its end
 struct Kept {
-    DevVec runs, cnt, pos, kmer, feat;
+    DevVec runs, cnt, pos, kmer, feat, names;             // names: 16 B per kept run, --read_names only
     int64_t NR = 0, NROW = 0;
     // window V's kept runs and their `nrow` rows behind what is there; `ahead` = what the whole file is expected to hold over what is held now
     int append(DevMem &m, hipStream_t s, const Win &V, int w, double ahead, const int64_t *pos_off, const PosRec *ps, const int64_t *row_off,
@@ -1084,6 +1123,9 @@ struct Kept {
             (rc = kmer.fit(m, nw * (size_t)K, (size_t)((double)nw * ahead) * (size_t)K, s, "rows")) ||
             (rc = feat.fit(m, nw * (size_t)NF * 8, (size_t)((double)nw * ahead) * (size_t)NF * 8, s, "rows")))
             return rc;
+        if (V.rnames && (rc = names.fit(m, nr * sizeof(Name), (size_t)((double)nr * ahead) * sizeof(Name), s, "read names"))) return rc;
+        if (V.rnames && V.keep)               // the dropped last run takes its name with it
+            PCHK(hipMemcpyAsync((Name *)names.p + NR, V.rnames, (size_t)V.keep * sizeof(Name), hipMemcpyDeviceToDevice, s));
         if (V.keep) {
             if (nrow) {
                 window_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.df, V.runs, V.keep, pos_off, ps, w, nullptr, row_off, (int64_t *)pos.p + NROW,
@@ -1096,6 +1138,7 @@ struct Kept {
         PCHK(hipStreamSynchronize(s));
         NR += V.keep; NROW += nrow;
         runs.used = (size_t)NR * sizeof(RunDev); cnt.used = (size_t)NR * 8;
+        if (V.rnames) names.used = (size_t)NR * sizeof(Name);
         pos.used = (size_t)NROW * 8; kmer.used = (size_t)(NROW * K); feat.used = (size_t)(NROW * NF) * 8;
         return M6A_OK;
     }
@@ -1150,6 +1193,7 @@ int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chu
         for (;;) {                                           // until the arena holds the window and the window holds a cut
             V = Win();
             V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
+            V.read_names = F.read_names;
             V.last = b + Wk >= n;
             V.len = std::min(Wk, n - b);
             arena.off = 0;
@@ -1215,7 +1259,7 @@ int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chu
     ms[0] = wait_ms;
     ms[5] = copy_ms > 0 ? copied / (copy_ms * 1e6) : 0;
     F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
-    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p;
+    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p; F.rnames = (Name *)kept.names.p;
     F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
     return M6A_OK;
 }
@@ -1727,6 +1771,122 @@ std::vector<uint64_t> vocab_keys()
     return v;
 }
 
+// ---- read names interned (m6a_prep_sites_build_names) -------------------------------------------------------------------------------
+// After the last window of a file and before anything reads RunDev.read, every run's 128-bit name becomes the dense index of the
+// name in order of first appearance -- the read index the twin file (names replaced by 0, 1, ...) carries in field 4:
+//   sort      the run numbers by name: LSD passes of radix_sort over lo, then hi; stable, so a group's runs stay in file order
+//   heads     where the name differs from the one before; a head is its group's smallest run number
+//   rank      a flag on every run that is such a first run, scanned over the run numbers: the groups in order of first appearance
+//   scatter   every run takes its group's rank as RunDev.read; every head writes its name to row `rank` of the table [n][16]
+// The number of names stays on the device (rank[NR]) until sites_impl fetches it together with the segment count.
+struct Intern {
+    uint32_t *val = nullptr;                // [NR] run numbers sorted by name
+    int64_t *gx = nullptr, *rank = nullptr; // [NR + 1] exclusive scans: group heads over the sorted order, first runs over the runs
+};
+
+__global__ void name_key_kernel(const Name *__restrict__ rn, int64_t n, int hi, uint32_t *__restrict__ val, uint64_t *__restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    if (!hi) val[i] = (uint32_t)i;
+    key[i] = hi ? rn[val[i]].hi : rn[i].lo;
+}
+
+__global__ void name_head_kernel(const uint32_t *__restrict__ val, int64_t n, const Name *__restrict__ rn, int64_t *__restrict__ head)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    head[i] = i == 0 || rn[val[i]].hi != rn[val[i - 1]].hi || rn[val[i]].lo != rn[val[i - 1]].lo;
+}
+
+__global__ void name_first_kernel(const uint32_t *__restrict__ val, int64_t n, const int64_t *__restrict__ gx, uint32_t *__restrict__ gfirst,
+                                  int64_t *__restrict__ first)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n || gx[i + 1] == gx[i]) return;
+    gfirst[gx[i]] = val[i];
+    first[val[i]] = 1;
+}
+
+__global__ void name_index_kernel(const uint32_t *__restrict__ val, int64_t n, const int64_t *__restrict__ gx, const uint32_t *__restrict__ gfirst,
+                                  const int64_t *__restrict__ rank, RunDev *__restrict__ runs)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i < n) runs[val[i]].read = rank[gfirst[gx[i + 1] - 1]];
+}
+
+__global__ void name_table_kernel(const uint32_t *__restrict__ val, int64_t n, const int64_t *__restrict__ gx, const int64_t *__restrict__ rank,
+                                  const Name *__restrict__ rn, int64_t n_names, uint8_t *__restrict__ table)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n || gx[i + 1] == gx[i]) return;
+    const int64_t k = rank[val[i]];
+    if (k < n_names) m6a_uuid::to_bytes(rn[val[i]].hi, rn[val[i]].lo, table + k * 16);
+}
+
+// two counts below 2^32, each the total an exclusive scan left behind its array, as one word
+__global__ void pack_totals_kernel(const int64_t *__restrict__ lo, const int64_t *__restrict__ hi, uint64_t *__restrict__ out)
+{
+    out[0] = (uint64_t)lo[0] | (uint64_t)hi[0] << 32;
+}
+
+int intern_runs(DevMem &m, hipStream_t s, RunDev *runs, const Name *rn, int64_t NR, Intern &in)
+{
+    int rc;
+    uint64_t *k1, *k2;
+    uint32_t *val, *val2, *gfirst;
+    if ((rc = m.alloc(k1, (size_t)NR + 1, "read names")) || (rc = m.alloc(k2, (size_t)NR + 1, "read names")) ||
+        (rc = m.alloc(val, (size_t)NR + 1, "read names")) || (rc = m.alloc(val2, (size_t)NR + 1, "read names")))
+        return rc;
+    for (int hi = 0; hi < 2 && NR; hi++) {
+        name_key_kernel<<<grid(NR), kBlk, 0, s>>>(rn, NR, hi, val, k1);
+        PCHK(hipGetLastError());
+        if ((rc = radix_sort(m, k1, val, k2, val2, NR, 64, s))) return rc;
+    }
+    PCHK(hipStreamSynchronize(s));
+    m.release(k1); m.release(k2); m.release(val2);
+    if ((rc = m.alloc(in.gx, (size_t)NR + 1, "read names")) || (rc = m.alloc(in.rank, (size_t)NR + 1, "read names")) ||
+        (rc = m.alloc(gfirst, (size_t)NR + 1, "read names")))
+        return rc;
+    PCHK(hipMemsetAsync(in.gx + NR, 0, sizeof(int64_t), s));
+    PCHK(hipMemsetAsync(in.rank, 0, (size_t)(NR + 1) * sizeof(int64_t), s));
+    if (NR) {
+        name_head_kernel<<<grid(NR), kBlk, 0, s>>>(val, NR, rn, in.gx);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_excl(m, in.gx, NR + 1, s))) return rc;
+    if (NR) {
+        name_first_kernel<<<grid(NR), kBlk, 0, s>>>(val, NR, in.gx, gfirst, in.rank);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_excl(m, in.rank, NR + 1, s))) return rc;
+    if (NR) {
+        name_index_kernel<<<grid(NR), kBlk, 0, s>>>(val, NR, in.gx, gfirst, in.rank, runs);
+        PCHK(hipGetLastError());
+    }
+    PCHK(hipStreamSynchronize(s));
+    m.release(gfirst);
+    in.val = val;
+    return M6A_OK;
+}
+
+// scan_total of a[0..n), and with the same 8 bytes the number of names intern_runs left at in.rank[n] (both are at most n < 2^32)
+int scan_total_and_names(DevMem &m, int64_t *a, int64_t n, hipStream_t s, int64_t &total, const Intern &in, int64_t &n_names)
+{
+    PCHK(hipMemsetAsync(a + n, 0, sizeof(int64_t), s));
+    int rc = scan_excl(m, a, n + 1, s);
+    if (rc) return rc;
+    uint64_t *w, h = 0;
+    if ((rc = m.alloc(w, 1, "flags"))) return rc;
+    pack_totals_kernel<<<1, 1, 0, s>>>(a + n, in.rank + n, w);
+    PCHK(hipGetLastError());
+    if ((rc = d2h(&h, w, 1, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    total = (int64_t)(h & 0xffffffffull);
+    n_names = (int64_t)(h >> 32);
+    return M6A_OK;
+}
+
 }  // namespace
 
 struct m6a_prep_sites;
@@ -1742,6 +1902,8 @@ struct FilePart {
     uint32_t *tx = nullptr;        // [NC]
     int64_t *pos = nullptr, *off = nullptr;   // [NC], [NC + 1]
     uint8_t *k7 = nullptr;         // [NC][7]
+    uint8_t *names = nullptr;      // [n_names][16] the file's read names in index order (--read_names)
+    int64_t n_names = 0;
 };
 
 struct Pool {
@@ -1768,6 +1930,13 @@ struct m6a_prep_sites {
     std::string blob;
     std::vector<double> ids;
     std::vector<int32_t> rep;                // [R] replicate of each read (several files)
+    // --read_names: the files' tables of names, concatenated -- file f's are rows [name_off[f], name_off[f + 1]), 16 bytes each
+    bool read_names = false;
+    std::vector<uint8_t> names16;
+    std::vector<int64_t> name_off{0};
+    const uint8_t *csv_names = nullptr;      // the same on the device, for the CSV kernels
+    const int64_t *csv_name_off = nullptr;   // [n_rep + 1]
+    double ms_intern = 0;
     ~m6a_prep_sites() { for (void *p : dev) (void)hipFree(p); }
 };
 
@@ -1791,6 +1960,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
                const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window, m6a_prep_sites &P, DevMem &m,
                double *ms, Pool *pool)
 {
+    const bool read_names = P.read_names;
     const double t_all = now_ms();
     double fms[6] = {0, 0, 0, 0, 0, 0};
     const size_t mark = m.ptrs.size();
@@ -1803,6 +1973,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     Fd fd;
     Front F;
     F.bgzf_ok = true;
+    F.read_names = read_names;
     int rc = front_half(device_id, path, 1, nullptr, nullptr, window, m, S, fd, F, fms);
     if (rc) return rc;
     P.info.n_bgzf_blocks += F.n_blocks;
@@ -1817,6 +1988,10 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     double t1 = now_ms(), dev_ms = 0, host_ms = 0;
     const int64_t NR = F.NR, NROW = F.NROW;
     if (NR > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 runs");
+    Intern in;
+    double t_in = now_ms();
+    if (read_names && (rc = intern_runs(m, s, F.runs, F.rnames, NR, in))) return rc;   // from here on RunDev.read is the twin's read index
+    if (read_names) P.ms_intern += now_ms() - t_in;
 
     // ---- segments and declined runs, to the host
     int64_t *sx, *dx, NSEG = 0, ND = 0;
@@ -1825,7 +2000,26 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         run_flags_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, dx);
         PCHK(hipGetLastError());
     }
-    if ((rc = scan_total(m, sx, NR, s, NSEG)) || (rc = scan_total(m, dx, NR, s, ND))) return rc;
+    int64_t n_names = 0;
+    if ((rc = read_names ? scan_total_and_names(m, sx, NR, s, NSEG, in, n_names) : scan_total(m, sx, NR, s, NSEG)) ||
+        (rc = scan_total(m, dx, NR, s, ND)))
+        return rc;
+    uint8_t *dnames = nullptr;
+    if (read_names) {                                       // the table: one copy of 16 bytes per name comes to the host
+        t_in = now_ms();
+        if ((rc = m.alloc(dnames, (size_t)n_names * 16, "read names"))) return rc;
+        if (NR) {
+            name_table_kernel<<<grid(NR), kBlk, 0, s>>>(in.val, NR, in.gx, in.rank, F.rnames, n_names, dnames);
+            PCHK(hipGetLastError());
+        }
+        const size_t at = P.names16.size();
+        P.names16.resize(at + (size_t)n_names * 16);
+        if ((rc = d2h(P.names16.data() + at, dnames, (size_t)n_names * 16, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        P.name_off.push_back(P.name_off.back() + n_names);
+        for (const void *p : {(const void *)in.val, (const void *)in.gx, (const void *)in.rank, (const void *)F.rnames}) m.release(p);
+        P.ms_intern += now_ms() - t_in;
+    }
     SegDev *seg;
     DeclDev *decl;
     if ((rc = m.alloc(seg, (size_t)NSEG + 1, "segments")) || (rc = m.alloc(decl, (size_t)ND + 1, "declined runs"))) return rc;
@@ -2172,7 +2366,8 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         }
         PCHK(hipStreamSynchronize(s));
         fp.NC = NS; fp.RC = R; fp.tx = site_tx; fp.pos = site_pos; fp.k7 = site_k7; fp.off = doff;
-        m.release_since(mark, {fp.X, fp.ids, fp.tx, fp.pos, fp.k7, fp.off});
+        fp.names = dnames; fp.n_names = n_names;
+        m.release_since(mark, {fp.X, fp.ids, fp.tx, fp.pos, fp.k7, fp.off, fp.names});
         pool->parts.push_back(fp);
         dev_ms += now_ms() - t1;
         ms[3] = dev_ms; ms[4] = host_ms; ms[5] = 0; ms[7] = now_ms() - t_all;
@@ -2214,13 +2409,20 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     if ((rc = m.alloc(rp, (size_t)R, "read probabilities")) || (rc = m.alloc(sp, (size_t)NS, "site probabilities")) ||
         (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
         return rc;
+    int64_t *dname_off = nullptr;
+    if (read_names) {
+        if ((rc = m.alloc(dname_off, 2, "read names")) || (rc = h2d(dname_off, P.name_off.data(), 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+    }
     for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr,
-                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids}) {
+                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids, (const void *)dnames,
+                          (const void *)dname_off}) {
+        if (!p) continue;
         P.held += m.size_of(p);
         m.detach(p);
         P.dev.push_back((void *)p);
     }
-    P.csv_tx = site_tx; P.csv_pos = site_pos; P.csv_k7 = site_k7; P.csv_ids = dids;
+    P.csv_tx = site_tx; P.csv_pos = site_pos; P.csv_k7 = site_k7; P.csv_ids = dids; P.csv_names = dnames; P.csv_name_off = dname_off;
     m6a_prep_sites_info &I = P.info;
     I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
     I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
@@ -2562,8 +2764,24 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
     if ((rc = m.alloc(rp, (size_t)R, "read probabilities")) || (rc = m.alloc(sp, (size_t)NS, "site probabilities")) ||
         (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
         return rc;
+    uint8_t *dnames = nullptr;
+    int64_t *dname_off = nullptr;
+    if (P.read_names) {                                     // the files' tables, one behind the other
+        if ((rc = m.alloc(dnames, P.names16.size(), "read names")) || (rc = m.alloc(dname_off, P.name_off.size(), "read names")) ||
+            (rc = h2d(dname_off, P.name_off.data(), P.name_off.size(), s)))
+            return rc;
+        for (int f = 0; f < K; f++)
+            if (pool.parts[(size_t)f].n_names)
+                PCHK(hipMemcpyAsync(dnames + P.name_off[(size_t)f] * 16, pool.parts[(size_t)f].names, (size_t)pool.parts[(size_t)f].n_names * 16,
+                                    hipMemcpyDeviceToDevice, s));
+        PCHK(hipStreamSynchronize(s));
+        for (FilePart &fp : pool.parts) { m.release(fp.names); fp.names = nullptr; }
+    }
+    P.csv_names = dnames; P.csv_name_off = dname_off;
     for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr,
-                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids, (const void *)blk_cnt}) {
+                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids, (const void *)blk_cnt,
+                          (const void *)dnames, (const void *)dname_off}) {
+        if (!p) continue;
         P.held += m.size_of(p);
         m.detach(p);
         P.dev.push_back((void *)p);
@@ -2665,6 +2883,15 @@ extern "C" int m6a_prep_sites_build_windows(int device_id, const char *const *pa
                                             int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window_bytes,
                                             m6a_prep_sites **out)
 {
+    return m6a_prep_sites_build_names(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean,
+                                      norm_std, n_norm, host, n_threads, window_bytes, 0, out);
+}
+
+extern "C" int m6a_prep_sites_build_names(int device_id, const char *const *paths, int n_paths, int readcount_min, int readcount_max,
+                                          int min_segment_count, const char *norm_kmers, const double *norm_mean, const double *norm_std,
+                                          int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, int read_names,
+                                          m6a_prep_sites **out)
+{
     if (!paths || !out || n_paths < 1) return prep_fail(M6A_EINVAL, "null argument");
     for (int f = 0; f < n_paths; f++)
         if (!paths[f]) return prep_fail(M6A_EINVAL, "null argument");
@@ -2672,6 +2899,7 @@ extern "C" int m6a_prep_sites_build_windows(int device_id, const char *const *pa
     m6a_prep_sites *p = new (std::nothrow) m6a_prep_sites;
     if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
     p->device = device_id;
+    p->read_names = read_names != 0;
     int rc;
     try {
         rc = sites_multi(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm,
@@ -2687,6 +2915,17 @@ extern "C" int m6a_prep_sites_build_windows(int device_id, const char *const *pa
 }
 
 extern "C" const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p) { return p ? &p->info : nullptr; }
+
+extern "C" int m6a_prep_sites_read_names(const m6a_prep_sites *p, const uint8_t **names16, const int64_t **name_off, int *n_rep)
+{
+    if (!p || !names16 || !name_off || !n_rep) return prep_fail(M6A_EINVAL, "null argument");
+    *names16 = p->read_names ? p->names16.data() : nullptr;
+    *name_off = p->read_names ? p->name_off.data() : nullptr;
+    *n_rep = p->read_names ? (int)p->name_off.size() - 1 : 0;
+    return M6A_OK;
+}
+
+extern "C" double m6a_prep_sites_intern_ms(const m6a_prep_sites *p) { return p ? p->ms_intern : 0; }
 
 extern "C" int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio)
 {

@@ -63,6 +63,13 @@ def cli_parser():
                              "2 gives every block its own (dynamic) codes where they are smaller -- the same parse, about 0.6 of "
                              "level 1's bytes on the CSV text.  The host route (--csv host, declined values) is zlib, which writes "
                              "dynamic codes at any level, so there the flag changes nothing.  Without --compress it is an error.")
+    parser.add_argument("--read_names", action="store_true",
+                        help="column 4 of every eventalign file is the read's name, a lowercase UUID, as nanopolish and f5c write it with "
+                             "--print-read-names (xPore and nanocompore need that form), not the integer read_index.  Runs are keyed by "
+                             "the 128-bit name, the names are interned on the device, and data.indiv_proba.csv carries the UUID (or "
+                             "<uuid>_<position of the file> with replicates) in its read_index column; every other byte is what the same "
+                             "file with indices gives.  Anything else in that column is an error.  Only this command has the flag: "
+                             "data.json stores the read id as a number and cannot hold a name, so `dataprep` and `inference` cannot carry one.")
     return parser
 
 
@@ -119,6 +126,7 @@ def main(args):
     window_mb = getattr(args, "window_mb", 0)
     compress = getattr(args, "compress", False)
     level = getattr(args, "compress_level", 1)
+    read_names = getattr(args, "read_names", False)
     if window_mb < 0:
         raise ValueError("--window_mb must be 0 or more, not %d" % window_mb)
     made = {}
@@ -134,7 +142,7 @@ def main(args):
     try:
         sites = _io.prep_sites(args.eventalign, args.readcount_min, args.readcount_max, args.min_segment_count,
                                load_norm_factors(args.norm_path), args.n_processes, device,
-                               window_kb=window_mb * 1024 if window_mb else None)
+                               window_kb=window_mb * 1024 if window_mb else None, **({"read_names": True} if read_names else {}))
     finally:
         starter.join()
     if "error" in made:
@@ -174,6 +182,8 @@ def main(args):
         if os.environ.get("M6A_EVENTALIGN_TIMES"):      # phases for tools/measure_eventalign_inference.py
             import json
             ms, d2h = sites.times()
+            ms.update(intern=sites.ms_intern)
+            extra_names = {"n_read_names": sites.n_read_names}
             ms.update(infer=(t1 - t0) * 1e3, fetch=(t2 - t1) * 1e3 if csv is None else 0.0,
                       csv_write=(time.perf_counter() - (t2 if csv is None else t1)) * 1e3)        # csv_write: the writer's wall time
             extra = {"csv_writer": "host"}
@@ -188,7 +198,7 @@ def main(args):
             elif compress:                       # the host route: zlib; its time is part of csv_write and it counts no stored blocks
                 ms.update(csv_deflate=0.0)
                 extra.update(csv_compressed_bytes=host_gz, csv_stored_blocks=None)
-            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads, **extra,
+            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": d2h, "n_sites": sites.n_sites, "n_reads": sites.n_reads, **extra, **extra_names,
                                                 "n_windows": sites.n_windows, "window_bytes": sites.window_bytes,
                                                 "peak_bytes": sites.peak_bytes, "inflate": sites.ms_inflate,
                                                 "compressed_bytes": sites.compressed_bytes, "n_bgzf_blocks": sites.n_bgzf_blocks,

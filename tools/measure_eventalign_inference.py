@@ -56,7 +56,16 @@ device-to-host bytes per read, the compressed files' size over the text, the sto
 and level 2 over level 1 in csv_deflate ms, bytes and command time; every leg's .gz files are inflated (`gzip -dc`) and compared with
 the plain leg's files.  The compressed legs carry no bar against the plain leg: which is faster is reported.  With --parent_tree the
 default command against the parent's, the bar of mode (b), and this tree's `--compress` leg against the parent's `--compress`
-command under the same rule (parent median + parent spread): level 2 is meant to leave both alone."""
+command under the same rule (parent median + parent spread): level 2 is meant to leave both alone.
+
+    python tools/measure_eventalign_inference.py --read_names [--shapes 3.1GB] [--legs 5] [--parent_tree DIR]
+                                                 [--out profiles/r15_read_names.json]
+
+The shape's file and its named twin -- every read index replaced by a UUID from a seeded bijection, as nanopolish --print-read-names
+writes the column -- as interleaved legs of the one-file command, the named leg with --read_names: medians, the phase table of every
+leg with the `intern` phase and n_read_names, the named file's size over the indexed one's, data.site_proba.csv of the two compared
+and the rows of data.indiv_proba.csv counted.  The named leg carries no bar (its lines are 30-odd bytes longer, so it uploads more).
+With --parent_tree the default command on the indexed file against the parent's, the bar of mode (b)."""
 import filecmp
 import gzip
 import json
@@ -369,6 +378,80 @@ def bgzf_legs(tag, legs, parent, ev_dir, limit):
     return res
 
 
+def write_named_shape(tag, ev_dir, seed=15):
+    """write_shape's file with field 4 of every body line replaced by the UUID of its read index (one seeded UUID per index)"""
+    import random
+    import re
+    import uuid
+    text = gzip.open(SRC, "rt").read()
+    header, body = text.split("\n", 1)
+    n = int(float(tag[:-2]) * 1e9 / len(body)) if tag.endswith("GB") else int(tag)       # as many copies as the indexed file has
+    rng, book = random.Random(seed), {}
+
+    def name(m):
+        if m.group(2) not in book:
+            book[m.group(2)] = str(uuid.UUID(int=rng.getrandbits(128)))
+        return m.group(1) + book[m.group(2)]
+    body = re.sub(r"^([^\t\n]*\t[^\t\n]*\t[^\t\n]*\t)([^\t\n]*)", name, body, flags=re.M)
+    path = os.path.join(ev_dir, "eventalign_%s_named.txt" % tag)
+    with open(path, "w", buffering=16 << 20) as f:
+        f.write(header + "\n")
+        for k in range(n):
+            f.write(body.replace("ENST", "C%dENST" % k) if k else body)
+    subprocess.run(["cat", path], stdout=subprocess.DEVNULL, check=True)          # page-cache warm
+    return path, len(book)
+
+
+def read_names_legs(tag, legs, parent, ev_dir, limit):
+    path, n = write_shape(tag, ev_dir)
+    named, n_names = write_named_shape(tag, ev_dir)
+    res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "named_GB": os.path.getsize(named) / 1e9,
+           "named_over_indexed_bytes": os.path.getsize(named) / os.path.getsize(path), "names_per_copy": n_names, "legs": legs}
+    runs = {"indexed": [], "named": []}
+    one, par = [], []
+    env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    env.pop("M6A_PREP_WINDOW_KB", None)
+    try:
+        for leg in range(legs):
+            for mode, src, flag in (("indexed", path, []), ("named", named, ["--read_names"])):
+                s, p = timed(["eventalign_inference", "--eventalign", src, "--out_dir", os.path.join(ev_dir, mode)] + flag + THREADS, limit, env=env)
+                must(s, p, mode)
+                t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+                t["s"] = s
+                runs[mode].append(t)
+            a, b = (os.path.join(ev_dir, m) for m in ("indexed", "named"))
+            res["site_proba_identical"] = filecmp.cmp(os.path.join(a, CSVS[0]), os.path.join(b, CSVS[0]), shallow=False)
+            rows = [int(subprocess.run(["wc", "-l", os.path.join(d, CSVS[1])], capture_output=True, text=True, check=True).stdout.split()[0]) for d in (a, b)]
+            res["indiv_proba_rows"] = {"indexed": rows[0], "named": rows[1], "equal": rows[0] == rows[1]}
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit), "default command, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, tree=parent), "default command, parent tree"))
+                res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
+                                                                 shallow=False) for f in CSVS)
+            for d in ("indexed", "named", "one", "one_parent"):
+                subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+            print("%s: leg %d of %d: indexed %.2f s, named %.2f s" % (tag, leg + 1, legs, runs["indexed"][-1]["s"], runs["named"][-1]["s"]),
+                  file=sys.stderr, flush=True)
+        for mode in runs:
+            v = runs[mode]
+            res[mode] = {"median_s": median([x["s"] for x in v]), "upload_wait_ms": median([x["ms"]["upload"] for x in v]),
+                         "intern_ms": median([x["ms"]["intern"] for x in v]), "back_half_ms": median([x["ms"]["back_half"] for x in v]),
+                         "n_read_names": v[-1]["n_read_names"], "peak_bytes": v[-1]["peak_bytes"], "d2h_bytes": v[-1]["d2h_bytes"], "legs": v}
+        res["named_over_indexed_time"] = res["named"]["median_s"] / res["indexed"]["median_s"]
+        if parent:
+            res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                                      "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                                      "within_bar": median(one) <= median(par) + max(par) - min(par)}
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+        res["legs_done"] = runs
+    os.remove(path)
+    os.remove(named)
+    return res
+
+
 def compress_legs(tag, legs, parent, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs}
@@ -528,6 +611,23 @@ def main():
         with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
             for tag in shapes:
                 res[tag] = bgzf_legs(tag, legs, parent, d, limit)
+                print(json.dumps({tag: res[tag]}), flush=True)
+                os.makedirs(os.path.dirname(dest), exist_ok=True)
+                with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured
+                    json.dump(res, f, indent=1)
+                if "failed" in res[tag]:
+                    break                                   # a failed step: nothing more is started
+        return
+    if "--read_names" in sys.argv:
+        shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB"]
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r15_read_names.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        if os.path.exists(dest):                            # one shape per call is allowed: the shapes share the file
+            res = json.load(open(dest))
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                res[tag] = read_names_legs(tag, legs, parent, d, limit)
                 print(json.dumps({tag: res[tag]}), flush=True)
                 os.makedirs(os.path.dirname(dest), exist_ok=True)
                 with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured

@@ -467,6 +467,32 @@ int m6a_prep_sites_build_names(int device_id, const char *const *paths, int n_pa
                                const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, int read_names, m6a_prep_sites **out);
 int m6a_prep_sites_read_names(const m6a_prep_sites *p, const uint8_t **names16, const int64_t **name_off, int *n_rep);
 double m6a_prep_sites_intern_ms(const m6a_prep_sites *p);
+/* Streams (`eventalign_inference --eventalign -`, a FIFO, /dev/fd/N): in all four entry points above a path `-` is file descriptor 0,
+ * and any path that fstat shows is not a regular file is a stream -- text that comes once and in order, of a length known when it
+ * ends.  A regular file takes the paths above untouched.  Replicates may mix files and streams, each parsed on its own, in order;
+ * `-` given twice is M6A_EINVAL before anything is opened.
+ *   windows  a stream is always parsed in windows: window_bytes > 0 or M6A_PREP_WINDOW_KB as for files, and with neither set
+ *            M6A_PREP_STREAM_WINDOW_BYTES (256 MB).  With `data` all the bytes the stream delivered, the windows are those of a
+ *            regular file that holds `data`, at the same size: window k is the `size` bytes from b_k and the last one exactly when no
+ *            byte follows them (the file rule b_k + size >= n), cut and growth as stated above.  So every array of the handle, X
+ *            bit for bit, n_windows, window_bytes and every error's code, text and byte offset are the file's, however the writer
+ *            cut its writes.  In error texts the path is the one given (`-`).
+ *   device   two windows of text, the scratch of one, and the kept runs and rows, as for files: a stream of any length goes through
+ *            as long as what is kept fits.  The bytes a window shares with the next (the dropped run, what follows the last newline)
+ *            are copied on the device and cross the link once; the kept arrays grow geometrically, since no length projects them.
+ *   saved    the back half cannot read a stream again, so every window saves, while its text is resident, the contig bytes of each
+ *            run that can head a segment and the bytes of each declined run, in two device arrays that count against the budget and
+ *            in peak_bytes; what comes back from them (the segment names; the declined runs the host half is given, through a
+ *            temporary file m6a_declined_XXXXXX in TMPDIR, removed before the call returns) counts in d2h_bytes.  Over the budget
+ *            is M6A_ENOMEM with text that names a smaller --window_mb.
+ *   refused  a stream that starts 1f 8b: M6A_EINVAL, compressed input from a stream is not implemented (the text names
+ *            `bgzip -dc FILE |`); m6a_prep_eventalign on a stream, with or without index_path: M6A_EINVAL, since the index and the
+ *            writer read the file again.  A failing read() is M6A_EIO "cannot read <path>".
+ * m6a_prep_sites_stream_bytes: the bytes read from streams, summed over the files; m6a_prep_sites_n_streams: how many of the files
+ * were streams.  Both are 0 for a handle built from regular files. */
+#define M6A_PREP_STREAM_WINDOW_BYTES ((int64_t)256 << 20)
+int64_t m6a_prep_sites_stream_bytes(const m6a_prep_sites *p);
+int64_t m6a_prep_sites_n_streams(const m6a_prep_sites *p);
 const m6a_prep_sites_info *m6a_prep_sites_get(const m6a_prep_sites *p);     /* owned by p */
 int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio);
 /* host copies of X [R][9], site_kmers [S][3] and off [S+1], for inspection (counted in d2h_bytes like every other copy) */

@@ -310,7 +310,11 @@ class prep_sites:
     every file is the read's UUID (nanopolish / f5c --print-read-names), not an index; the arrays are those of the twin file whose
     names are replaced by 0, 1, ... in order of first appearance, read_ids holds those indices, and `read_names` is (names, offsets):
     names uint8 [n][16] -- the UUIDs' bytes, file f's in index order at rows [offsets[f], offsets[f + 1]) -- and offsets int64
-    [n_replicates + 1]; None without the flag.  n_read_names and ms_intern count the names and the interning.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
+    [n_replicates + 1]; None without the flag.  n_read_names and ms_intern count the names and the interning.  A path `-` is the
+    standard input, and any path that is not a regular file (a FIFO, /dev/fd/N) is a stream: it is read once, in order, always in
+    windows (window_kb, M6A_PREP_WINDOW_KB, or 256 MB), and gives the arrays, n_windows and window_bytes of a regular file with the
+    same bytes at the same window size; stream_bytes and n_streams say so (0 for regular files).  Nothing here asks a path for its
+    size or whether it exists: the library opens it.  Errors are M6AIOError with the code of the same failure on the two-step path; close() frees the device arrays."""
     _CODES = prep_on_device._CODES
 
     def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0,
@@ -355,6 +359,8 @@ class prep_sites:
         self.n_windows, self.window_bytes = int(i.n_windows), int(i.window_bytes)
         self.n_bgzf_blocks, self.compressed_bytes, self.ms_inflate = int(i.n_bgzf_blocks), int(i.compressed_bytes), float(i.ms_inflate)
         self.n_declined_sites = int(i.n_declined_sites)      # json_sites: sites that went through the host half
+        # streams (`-`, a FIFO, /dev/fd/N): the bytes read from them, and how many of the files were streams; 0 for regular files
+        self.stream_bytes, self.n_streams = int(L.m6a_prep_sites_stream_bytes(self._h)), int(L.m6a_prep_sites_n_streams(self._h))
         tx_off = arr(i.tx_off, C.c_int64, T + 1)
         self.tx_blob = C.string_at(i.tx_blob, int(tx_off[-1])) if T else b""
         self.tx_off = tx_off

@@ -18,7 +18,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_reference_written_sites",
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
-           "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
+           "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
            "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build"]
 
@@ -190,6 +190,9 @@ def load():
     L.m6a_prep_sites_read_names.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     L.m6a_prep_sites_intern_ms.argtypes = [vp]
     L.m6a_prep_sites_intern_ms.restype = C.c_double
+    for f in (L.m6a_prep_sites_stream_bytes, L.m6a_prep_sites_n_streams):
+        f.argtypes = [vp]
+        f.restype = C.c_int64
     L.m6a_json_sites_build.argtypes = [i32, C.POINTER(C.c_char_p), i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(JsonHostHalf), i32, C.POINTER(vp)]
     L.m6a_prep_sites_get.argtypes = [vp]
     L.m6a_prep_sites_get.restype = C.POINTER(PrepSitesInfo)

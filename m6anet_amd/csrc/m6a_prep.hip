@@ -17,7 +17,8 @@
 //   combine     one lane per run: Kahan sums per (position, k-mer) group, count then write
 //   windows     one lane per run: runs of 2w + 1 consecutive positions with a DRACH centre, count then write
 // With a window size (M6A_PREP_WINDOW_KB, m6a_prep_sites_build_windows) the same kernels run on one window of the file after the other
-// and only runs and rows stay on the device: front_windows, below.
+// and only runs and rows stay on the device: front_windows, below.  Text from a pipe (`-`, a FIFO) goes through the same windows as it
+// arrives, and what the back half would read again is saved from every window: front_stream, below it.
 // Everything is built with -ffp-contract=off (build.py): no multiply-add is fused, and the f64 divisions are IEEE `/`.
 #include <hip/hip_runtime.h>
 
@@ -40,6 +41,7 @@
 
 #include "m6a.h"
 #include "m6a_io.h"
+#include "m6a_stream.h"
 #include "m6a_uuid.h"
 
 namespace {
@@ -477,6 +479,29 @@ __global__ void keep_runs_kernel(const RunDev *__restrict__ runs, int64_t NR, in
     row_cnt[r] = row_off[r + 1] - row_off[r];
 }
 
+// ---- a stream's windows: what the back half will ask for is saved while the window's text is there -------------------------------
+// A file's back half preads the contig bytes of every segment head and hands the byte ranges of declined runs to the host half; a
+// stream cannot be read again.  Per kept run: the bytes of its contig name if it can head a segment (not same_contig: the first
+// run of every window is one, as run_flags_kernel sees it later), and all its bytes if it is not M6A_PREP_RUN_OK -- 0 otherwise.
+// Scanned, the counts are the offsets of the window's part of the two blobs.
+__global__ void save_flag_kernel(const RunDev *__restrict__ runs, int64_t NR, int64_t *__restrict__ head, int64_t *__restrict__ decl)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r >= NR) return;
+    head[r] = runs[r].same_contig ? 0 : runs[r].contig_len;
+    decl[r] = runs[r].status != M6A_PREP_RUN_OK ? runs[r].end - runs[r].start : 0;
+}
+
+// one workgroup per kept run, lane after lane along the bytes; a run with nothing to save (most of them) leaves at once
+__global__ void save_gather_kernel(const uint8_t *__restrict__ f, const RunDev *__restrict__ runs, const int64_t *__restrict__ off, int whole,
+                                   uint8_t *__restrict__ out)
+{
+    const int64_t r = blockIdx.x, at = off[r], len = off[r + 1] - at;
+    if (len <= 0) return;
+    const uint8_t *src = f + (whole ? runs[r].start : runs[r].contig);
+    for (int64_t i = threadIdx.x; i < len; i += blockDim.x) out[at + i] = src[i];
+}
+
 __global__ void run_cols_kernel(const RunDev *__restrict__ runs, int64_t NR, int64_t *__restrict__ npos)
 {
     const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
@@ -599,7 +624,8 @@ struct Streams {
 
 struct Fd {
     int fd = -1;
-    ~Fd() { if (fd >= 0) ::close(fd); }
+    bool own = true;                        // false: descriptor 0 for `-`, which stays the process's
+    ~Fd() { if (own && fd >= 0) ::close(fd); }
 };
 
 int scan_excl(DevMem &m, int64_t *a, int64_t n, hipStream_t s)
@@ -738,6 +764,12 @@ struct Front {
     const uint8_t *text = nullptr;          // out, BGZF input: the inflated text, NOT in scratch -- the caller reads names and runs from it
     int64_t n_blocks = 0, comp_bytes = 0;   // out, BGZF input
     double ms_inflate = 0;
+    // out, a stream (front_stream): n is the bytes it delivered, and what the back half would read from a file again was saved from
+    // every window while its text was there -- NOT in scratch, the caller releases them
+    bool stream = false;
+    const uint8_t *heads = nullptr;         // the contig bytes of every run that can head a segment, end to end in run order
+    const uint8_t *declined = nullptr;      // the bytes [start, end) of every run that is not M6A_PREP_RUN_OK, likewise
+    int64_t n_heads = 0, n_declined = 0;
 };
 
 // m6a_bgzf.h, included at the end of this file
@@ -748,6 +780,16 @@ int bgzf_gather(DevMem &m, hipStream_t s, const uint8_t *text, int64_t n_text, c
                 std::vector<uint8_t> &out);
 
 int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
+int front_stream(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
+
+// `-` is descriptor 0; whatever else fstat shows is no regular file (a FIFO, /dev/fd/N, a character device) is a stream as well
+bool is_stdin(const char *path) { return path[0] == '-' && path[1] == 0; }
+bool is_stream(const char *path)
+{
+    struct stat st;
+    if (is_stdin(path) ? fstat(0, &st) != 0 : stat(path, &st) != 0) return false;      // not there: the caller's open says so
+    return !S_ISREG(st.st_mode);
+}
 
 // the format error line_kernel found lowest in the text that starts at file byte b
 int bad_line(const char *path, bool names, int64_t b, unsigned long long bad_at)
@@ -773,12 +815,17 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
     if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
     PCHK(hipSetDevice(device_id));
-    fd.fd = ::open(path, O_RDONLY);
+    if (is_stdin(path)) { fd.fd = 0; fd.own = false; }
+    else fd.fd = ::open(path, O_RDONLY);
     if (fd.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", path);
     struct stat st;
     if (fstat(fd.fd, &st) != 0) return prep_fail(M6A_EIO, "cannot stat %s", path);
-    int64_t n = (int64_t)st.st_size;
-    const bool gz = bgzf_is_gzip(fd.fd, n);              // by content: 1f 8b.  Text takes the path below untouched.
+    const bool stream = !S_ISREG(st.st_mode);            // a regular file takes the path below untouched
+    if (stream && (index_path || !F.bgzf_ok))
+        return prep_fail(M6A_EINVAL, "%s is a stream: `dataprep --device gpu` and --skip_index read the file again for the index and "
+                         "the rows, and a stream comes once; `eventalign_inference` reads one", path);
+    int64_t n = stream ? 0 : (int64_t)st.st_size;
+    const bool gz = !stream && bgzf_is_gzip(fd.fd, n);   // by content: 1f 8b.  Text takes the path below untouched.
     if (gz && !F.bgzf_ok)
         return prep_fail(M6A_EFORMAT, "%s is gzip-compressed: `dataprep --device gpu` writes an eventalign.index of offsets into the text, "
                          "which is not there; `eventalign_inference` reads BGZF directly", path);
@@ -796,6 +843,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
     }
     int64_t nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);       // 4 KB scan blocks; the buffer is padded to them
+    if (stream && window <= 0) window = M6A_PREP_STREAM_WINDOW_BYTES;           // a stream is always parsed in windows
     const int64_t W = index_path || window <= 0 ? 0 : (window + kScanBytes - 1) / kScanBytes * kScanBytes;
     uint8_t *df = nullptr;
     int64_t *bcnt = nullptr;
@@ -816,6 +864,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
     chunk = std::min<int64_t>(chunk, W ? W : nb * kScanBytes);
     for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&S.pin[i], (size_t)chunk, hipHostMallocDefault));
+    if (stream) return front_stream(device_id, path, w, W, chunk, m, S, fd, F, ms);
     if (W) return front_windows(device_id, path, w, W, chunk, m, S, fd, F, ms);
     if (gz) {                                                // the compressed bytes go up, the text is inflated where the upload would have put it
         if ((rc = bgzf_front(path, fd.fd, n, m, S, chunk, df, n, F, ms))) return rc;
@@ -1106,13 +1155,33 @@ int window_cut(DevMem &m, hipStream_t s, const char *path, Win &V, double *ms)
     return M6A_OK;
 }
 
+// a stream's window: where its kept runs' saved bytes go in the window's part of the two blobs (save_flag_kernel, scanned)
+struct Save {
+    int64_t *head = nullptr, *decl = nullptr;             // [keep + 1] each
+    int64_t n_head = 0, n_decl = 0;
+};
+
+int save_plan(DevMem &m, hipStream_t s, const Win &V, Save &sv)
+{
+    int rc;
+    if ((rc = m.alloc(sv.head, (size_t)V.keep + 1, "saved names")) || (rc = m.alloc(sv.decl, (size_t)V.keep + 1, "saved runs"))) return rc;
+    if (V.keep) {
+        save_flag_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.runs, V.keep, sv.head, sv.decl);
+        PCHK(hipGetLastError());
+    }
+    if ((rc = scan_total(m, sv.head, V.keep, s, sv.n_head))) return rc;
+    return scan_total(m, sv.decl, V.keep, s, sv.n_decl);
+}
+
 // what stays of the windows: the job's runs, their row counts and the three row arrays, each grown at its end
 struct Kept {
     DevVec runs, cnt, pos, kmer, feat, names;             // names: 16 B per kept run, --read_names only
+    DevVec heads, declined;                               // a stream only: Front::heads, Front::declined
     int64_t NR = 0, NROW = 0;
     // window V's kept runs and their `nrow` rows behind what is there; `ahead` = what the whole file is expected to hold over what is held now
+    // sv (a stream): the window's saved bytes go behind the two blobs, which grow as the arrays do
     int append(DevMem &m, hipStream_t s, const Win &V, int w, double ahead, const int64_t *pos_off, const PosRec *ps, const int64_t *row_off,
-               int64_t nrow)
+               int64_t nrow, const Save *sv = nullptr)
     {
         const int64_t K = 5 + 2 * w, NF = 3 * (2 * w + 1);
         const size_t nr = (size_t)(NR + V.keep) + 1, nw = (size_t)(NROW + nrow) + 1;
@@ -1134,6 +1203,21 @@ struct Kept {
             }
             keep_runs_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.runs, V.keep, V.b, row_off, (RunDev *)runs.p + NR, (int64_t *)cnt.p + NR);
             PCHK(hipGetLastError());
+        }
+        if (sv) {
+            const size_t nh = heads.used + (size_t)sv->n_head, nd = declined.used + (size_t)sv->n_decl;
+            if ((rc = heads.fit(m, nh, (size_t)((double)nh * ahead), s, "saved names")) ||
+                (rc = declined.fit(m, nd, (size_t)((double)nd * ahead), s, "saved runs")))
+                return rc;
+            if (sv->n_head) {
+                save_gather_kernel<<<(unsigned)V.keep, kBlk, 0, s>>>(V.df, V.runs, sv->head, 0, heads.p + heads.used);
+                PCHK(hipGetLastError());
+            }
+            if (sv->n_decl) {
+                save_gather_kernel<<<(unsigned)V.keep, kBlk, 0, s>>>(V.df, V.runs, sv->decl, 1, declined.p + declined.used);
+                PCHK(hipGetLastError());
+            }
+            heads.used = nh; declined.used = nd;
         }
         PCHK(hipStreamSynchronize(s));
         NR += V.keep; NROW += nrow;
@@ -1264,9 +1348,237 @@ int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chu
     return M6A_OK;
 }
 
+// ---- the front half on a stream ---------------------------------------------------------------------------------------------------
+// `--eventalign -`, a FIFO, /dev/fd/N: the text comes once and in order, and its length is known when it ends.  The windows are the
+// file's (include/m6a.h; tests/window_statement.py): window k is the `size` bytes from b, the last one exactly when no byte follows
+// them -- the reader's one byte of lookahead (m6a_stream.h) answers that without consuming -- and cut and growth are window_cut's.
+// What front_windows reads again from the file never crosses the link twice here:
+//   carry    the bytes of window k from b of window k + 1 on (the dropped run, what lies behind the last newline) are copied device
+//            to device to the start of the next buffer, which keeps the text 16-byte aligned at its base for the newline scan; the
+//            stream's next bytes are appended behind them, so only the append position is unaligned, and zeros follow the text to
+//            a whole scan block.  A window that grew may leave more than W bytes: the next windows are cut from them first.
+//   growth   the buffer is grown by copy and `size` more bytes are appended.
+//   reading  a thread of the reader's own (m6a_stream::Ring) fills the two pinned chunks from the pipe all the time: it does not wait
+//            for a cut, because the stream's order is fixed.  From the cut of window k on, a second thread takes the next window's
+//            bytes out of the chunks and copies them on the copy stream behind the carried bytes, while the kernel stream counts,
+//            windows and appends window k.
+//   saving   the back half cannot pread a stream: Kept::append saves the contig bytes of segment heads and the bytes of declined
+//            runs from the window's text (save_flag_kernel, scan, save_gather_kernel), and sites_impl gathers from the two blobs.
+// The length is unknown, so the kept arrays grow geometrically (twice what is needed, then DevVec::fit's fallbacks).
+struct Fetch {
+    m6a_stream::Ring &ring;
+    int rc = M6A_OK;
+    std::string err;
+    double ms = 0;
+    int64_t got = 0;
+    bool eof = false;
+    std::thread t;
+    explicit Fetch(m6a_stream::Ring &r) : ring(r) {}
+    void wait() { if (t.joinable()) t.join(); }
+    ~Fetch() { if (t.joinable()) { ring.abandon(); t.join(); } }     // left on an error: nothing more is wanted of the stream
+};
+
+// up to `want` bytes of the stream -> base + have on the copy stream, zeros behind the text to a whole scan block; returns when they
+// have arrived.  got: how many came (fewer than `want` only at the stream's end); eof: whether no byte follows them.  The bytes come
+// out of the pinned pair, which the ring's thread fills from the pipe whether or not anybody is here to take them.
+int stream_fetch(int device_id, m6a_stream::Ring &ring, Streams &S, uint8_t *base, int64_t have, int64_t want, int64_t &got, bool &eof)
+{
+    PCHK(hipSetDevice(device_id));
+    hipError_t bad = hipSuccess;
+    auto copy = [&](const uint8_t *p, int64_t k, int slot, int64_t off) {
+        bad = hipMemcpyAsync(base + have + off, p, (size_t)k, hipMemcpyHostToDevice, S.s[1]);
+        if (bad == hipSuccess) bad = hipEventRecord(S.copied[slot], S.s[1]);
+        return bad == hipSuccess;
+    };
+    auto settle = [&](int slot) { return (bad = hipEventSynchronize(S.copied[slot])) == hipSuccess; };
+    got = 0;
+    const int64_t r = ring.take(want, copy, settle);
+    if (r == -2) return prep_fail(M6A_EHIP, "the copy of a window of the stream: %s", hipGetErrorString(bad));
+    if (r < 0) return prep_fail(M6A_EIO, "%s", ring.R.failed ? ring.R.error.c_str() : "the stream was abandoned");
+    got = r;
+    const int64_t len = have + got, padded = std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes;
+    if (padded > len) PCHK(hipMemsetAsync(base + len, 0, (size_t)(padded - len), S.s[1]));
+    PCHK(hipStreamSynchronize(S.s[1]));
+    const int e = ring.at_eof();
+    if (e < 0) return prep_fail(M6A_EIO, "%s", ring.R.failed ? ring.R.error.c_str() : "the stream was abandoned");
+    eof = e == 1;
+    return M6A_OK;
+}
+
+int front_stream(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
+{
+    hipStream_t s = S.s[0];
+    int rc;
+    const char *const advice = m.advice;
+    struct Advice { DevMem &m; const char *was; ~Advice() { m.advice = was; } } restore{m, advice};
+    m.advice = "a stream is parsed in windows and what is kept of them stays on the device: give a smaller --window_mb, or write the "
+               "text to a file and run `dataprep` and then `inference` (the two-step path)";
+    m6a_stream::Reader R(fd.fd, false, path);               // fd closes the descriptor (or leaves 0 alone)
+    m6a_stream::Ring ring(R, (uint8_t *)S.pin[0], (uint8_t *)S.pin[1], chunk);
+    struct Text { uint8_t *p = nullptr; int64_t cap = 0; } text[2];
+    auto cap_of = [](int64_t len) { return std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes; };
+    auto text_fit = [&](Text &T, int64_t len) -> int {      // what was in it is gone
+        const int64_t cap = cap_of(len);
+        if (cap <= T.cap) return M6A_OK;
+        if (T.p) m.release(T.p);
+        T.p = nullptr; T.cap = 0;
+        const int e = m.alloc(T.p, (size_t)cap, "a window of the stream");
+        if (!e) T.cap = cap;
+        return e;
+    };
+    auto text_grow = [&](Text &T, int64_t len, int64_t keep) -> int {       // what was in it stays: the old and the new both count
+        const int64_t cap = cap_of(len);
+        if (cap <= T.cap) return M6A_OK;
+        uint8_t *q = nullptr;
+        const int e = m.alloc(q, (size_t)cap, "a window of the stream");
+        if (e) return e;
+        if (keep) PCHK(hipMemcpyAsync(q, T.p, (size_t)keep, hipMemcpyDeviceToDevice, s));
+        PCHK(hipStreamSynchronize(s));
+        if (T.p) m.release(T.p);
+        T.p = q; T.cap = cap;
+        return M6A_OK;
+    };
+    Arena arena;
+    auto arena_grow = [&]() -> int {
+        PCHK(hipStreamSynchronize(s));
+        if (arena.base) m.release(arena.base);
+        arena.base = nullptr;
+        const size_t cap = std::max(arena.cap * 2, (arena.need + 4095) & ~(size_t)4095);
+        arena.cap = arena.off = 0;
+        const int e = m.alloc(arena.base, cap, "the scratch of a window");
+        if (!e) arena.cap = cap;
+        return e;
+    };
+    Kept kept;
+    int64_t b = 0, have = 0, n_windows = 0, w_max = 0;
+    bool eof = false;                                        // no byte follows the `have` bytes from b
+    double wait_ms = 0, copy_ms = 0, copied = 0;
+
+    // the first two bytes say whether this is gzip; then window 0 arrives before anything can run
+    {
+        uint8_t magic[2] = {0, 0};
+        const double t0 = now_ms();
+        const int64_t g = R.fill(magic, 2);
+        if (g < 0) return prep_fail(M6A_EIO, "%s", R.error.c_str());
+        if (g == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
+            return prep_fail(M6A_EINVAL, "%s is a gzip-compressed stream: compressed input from a stream is not implemented; inflate it on "
+                             "the way, `bgzip -dc FILE | ... --eventalign -`, or give the BGZF file by its path", path);
+        if ((rc = text_fit(text[0], W))) return rc;
+        if (g) PCHK(hipMemcpyAsync(text[0].p, magic, (size_t)g, hipMemcpyHostToDevice, S.s[1]));
+        PCHK(hipStreamSynchronize(S.s[1]));
+        ring.start();                                        // from here on the reader is the thread's
+        int64_t got = 0;
+        if ((rc = stream_fetch(device_id, ring, S, text[0].p, g, W - g, got, eof))) return rc;
+        have = g + got;
+        wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)have;
+    }
+    arena.need = (size_t)std::min(W, std::max(have, kScanBytes)) * 2;   // newline offsets and line records: about 1.5 bytes per byte of text
+    if ((rc = arena_grow())) return rc;
+    for (int64_t k = 0;; k++) {
+        Text &T = text[k & 1], &T2 = text[(k + 1) & 1];
+        Fetch up(ring);                                      // of window k + 1; joined where it goes out of scope
+        bool started = false;
+        int64_t Wk = W, carry = 0;
+        Win V;
+        for (;;) {                                           // until the arena holds the window and the window holds a cut
+            V = Win();
+            V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
+            V.read_names = F.read_names;
+            V.len = std::min(Wk, have);                      // have > Wk: what a grown window left; Wk is whole scan blocks then
+            V.last = have < Wk || (have == Wk && eof);       // the file rule b + size >= n: no byte follows these bytes
+            arena.off = 0;
+            m.arena = &arena;
+            rc = window_cut(m, s, path, V, ms);
+            int64_t *pos_off = nullptr, *row_off = nullptr, nrow = 0;
+            PosRec *ps = nullptr;
+            Save sv;
+            if (!rc && !V.grow) {
+                if (!V.last && !started) {                   // the cut is known: the carry moves over and the next bytes set out
+                    m.arena = nullptr;
+                    carry = have - (V.next - b);
+                    if ((rc = text_fit(T2, std::max(W, carry)))) return rc;
+                    m.arena = &arena;
+                    if (carry) PCHK(hipMemcpyAsync(T2.p, T.p + (V.next - b), (size_t)carry, hipMemcpyDeviceToDevice, S.s[1]));
+                    uint8_t *const dst = T2.p;
+                    const int64_t at = carry, want = std::max<int64_t>(0, W - carry);
+                    up.t = std::thread([&up, &ring, &S, device_id, dst, at, want]() {
+                        const double t0 = now_ms();
+                        up.rc = stream_fetch(device_id, ring, S, dst, at, want, up.got, up.eof);
+                        if (up.rc) up.err = g_prep_err;     // the text is this thread's; the caller takes it over
+                        up.ms = now_ms() - t0;
+                    });
+                    started = true;
+                }
+                const double t1 = now_ms();
+                rc = count_rows(m, s, V.df, V.ev, V.runs, V.keep, w, pos_off, ps, row_off, nrow);
+                if (!rc) rc = save_plan(m, s, V, sv);
+                ms[2] += now_ms() - t1;
+            }
+            m.arena = nullptr;
+            if (rc == kArenaFull) {
+                if ((rc = arena_grow())) return rc;
+                continue;
+            }
+            if (rc) return rc;
+            if (V.grow) {                                    // twice the window: what is there stays, the rest is appended
+                Wk *= 2;
+                PCHK(hipStreamSynchronize(s));
+                if (have < Wk) {                             // (a grown window is not the last: a byte follows what is there)
+                    if ((rc = text_grow(T, Wk, have))) return rc;
+                    const double t0 = now_ms();
+                    int64_t got = 0;
+                    if ((rc = stream_fetch(device_id, ring, S, T.p, have, Wk - have, got, eof))) return rc;
+                    have += got;
+                    wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)got;
+                }
+                continue;
+            }
+            const double t1 = now_ms();
+            if ((rc = kept.append(m, s, V, w, 2.0, pos_off, ps, row_off, nrow, &sv))) return rc;
+            ms[2] += now_ms() - t1;
+            break;
+        }
+        ++n_windows;
+        w_max = std::max(w_max, Wk);
+        if (started) {
+            const double t0 = now_ms();
+            up.wait();
+            wait_ms += now_ms() - t0; copy_ms += up.ms; copied += (double)up.got;
+            if (up.rc) { g_prep_err = up.err; return up.rc; }
+        }
+        if (V.last) break;
+        b = V.next;
+        have = carry + up.got;
+        eof = up.eof;
+    }
+    if (R.consumed != b + have) return prep_fail(M6A_EHIP, "the windows of %s do not add up", path);
+    F.n = R.consumed;
+    F.stream = true;
+    // the scratch goes before the back half: X needs the room
+    for (Text &T : text)
+        if (T.p) m.release(T.p);
+    m.release(arena.base);
+    const double t1 = now_ms();
+    int64_t total = 0;
+    if ((rc = scan_total(m, (int64_t *)kept.cnt.p, kept.NR, s, total))) return rc;
+    if (total != kept.NROW) return prep_fail(M6A_EHIP, "the windows' rows do not add up");
+    ms[2] += now_ms() - t1;
+    ms[0] = wait_ms;
+    ms[5] = copy_ms > 0 ? copied / (copy_ms * 1e6) : 0;
+    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
+    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p; F.rnames = (Name *)kept.names.p;
+    F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
+    F.heads = kept.heads.p; F.n_heads = (int64_t)kept.heads.used;
+    F.declined = kept.declined.p; F.n_declined = (int64_t)kept.declined.used;
+    return M6A_OK;
+}
+
 int prep_impl(int device_id, const char *path, int w, const char *index_path, m6a_prep &P)
 {
     if (w < 1 || w > 16) return prep_fail(M6A_EINVAL, "n_neighbors must be 1..16");
+    if (is_stream(path))                                    // before anything is opened: opening a FIFO waits for its writer
+        return prep_fail(M6A_EINVAL, "%s is a stream: `dataprep --device gpu` and --skip_index read the file again for the index and the "
+                         "rows, and a stream comes once; `eventalign_inference` reads one", path);
     // --skip_index: the runs come from the file (read before anything touches the device, as the host path does)
     std::vector<std::string> names;
     std::vector<uint32_t> itx;
@@ -1937,6 +2249,7 @@ struct m6a_prep_sites {
     const uint8_t *csv_names = nullptr;      // the same on the device, for the CSV kernels
     const int64_t *csv_name_off = nullptr;   // [n_rep + 1]
     double ms_intern = 0;
+    int64_t stream_bytes = 0, n_streams = 0; // bytes read from streams, and how many of the files were streams
     ~m6a_prep_sites() { for (void *p : dev) (void)hipFree(p); }
 };
 
@@ -1981,6 +2294,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     P.info.ms_inflate += F.ms_inflate;
     P.info.n_windows += F.n_windows;
     P.info.window_bytes = std::max(P.info.window_bytes, F.window_bytes);
+    if (F.stream) { P.stream_bytes += F.n; P.n_streams += 1; }
     ms[0] = fms[0]; ms[1] = fms[1]; ms[2] = fms[2]; ms[6] = fms[5];
     hipStream_t s = S.s[0];
     PCHK(hipStreamSynchronize(s));
@@ -2040,19 +2354,26 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     std::vector<int64_t> tx_runs;
     std::string nm;
     std::vector<uint8_t> packed;                            // BGZF input: the contig bytes of all segments, from the text on the device
-    if (F.text) {
+    const bool resident = F.text || F.stream;              // the bytes come from the device, not from the file
+    if (resident) {
         std::vector<int64_t> src((size_t)NSEG), len((size_t)NSEG);
-        for (int64_t g = 0; g < NSEG; g++) { src[(size_t)g] = hseg[(size_t)g].contig; len[(size_t)g] = hseg[(size_t)g].len; }
-        if ((rc = bgzf_gather(m, s, F.text, F.n, src, len, packed))) return rc;
+        int64_t sum = 0;                                    // a stream: the heads were saved in run order, so segment g's lie at the running sum
+        for (int64_t g = 0; g < NSEG; g++) {
+            src[(size_t)g] = F.stream ? sum : hseg[(size_t)g].contig;
+            len[(size_t)g] = hseg[(size_t)g].len;
+            sum += hseg[(size_t)g].len;
+        }
+        if (F.stream && sum != F.n_heads) return prep_fail(M6A_EHIP, "the saved contig names of %s do not add up", path);
+        if ((rc = F.stream ? bgzf_gather(m, s, F.heads, F.n_heads, src, len, packed) : bgzf_gather(m, s, F.text, F.n, src, len, packed))) return rc;
     }
     for (int64_t g = 0, at = 0; g < NSEG; g++) {
         const SegDev &G = hseg[(size_t)g];
         nm.resize((size_t)G.len);
-        if (F.text) {
+        if (resident) {
             memcpy(&nm[0], packed.data() + at, (size_t)G.len);
             at += G.len;
         }
-        for (int64_t got = 0; !F.text && got < G.len;) {
+        for (int64_t got = 0; !resident && got < G.len;) {
             const ssize_t k = ::pread(fd.fd, &nm[(size_t)got], (size_t)(G.len - got), (off_t)(G.contig + got));
             if (k < 0 && errno == EINTR) continue;
             if (k <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
@@ -2079,11 +2400,17 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     for (SegUp &u : up) u.keep = std::min(tx_runs[u.tx], lim + 1) >= rmin;
     // declined runs the host loop reaches: combined and windowed by the host half
     std::vector<int64_t> cstart, cend, cread, crun;
+    std::vector<int64_t> csaved;                            // a stream: where the run's bytes lie among the saved ones
+    int64_t saved_at = 0;
     for (const DeclDev &d : hdecl) {
+        const int64_t at_saved = saved_at;
+        saved_at += d.end - d.start;
         const int64_t g = (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), d.run, [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
         if (up[(size_t)g].rank0 + (d.run - hseg[(size_t)g].first) > lim) continue;
         cstart.push_back(d.start); cend.push_back(d.end); cread.push_back(d.read); crun.push_back(d.run);
+        csaved.push_back(at_saved);
     }
+    if (F.stream && saved_at != F.n_declined) return prep_fail(M6A_EHIP, "the saved declined runs of %s do not add up", path);
     std::vector<DeclUp> dup;
     std::vector<int64_t> hpos, hrun;
     std::vector<uint8_t> hkmer;
@@ -2092,12 +2419,13 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         if (!host || !host->rows || !host->table || !host->free)
             return prep_fail(M6A_EINVAL, "%zu runs need the host half and none was given", crun.size());
         struct m6a_io_rows *hr = nullptr;
-        // BGZF input: the host half takes a path, so it gets the declined runs laid end to end in a plain temporary file
+        // BGZF input or a stream: the host half takes a path, so it gets the declined runs laid end to end in a plain temporary file
         struct Tmp { std::string path; ~Tmp() { if (!path.empty()) ::unlink(path.c_str()); } } tmp;
-        if (F.text) {
+        if (resident) {
             std::vector<int64_t> len(crun.size());
             for (size_t i = 0; i < crun.size(); i++) len[i] = cend[i] - cstart[i];
-            if ((rc = bgzf_gather(m, s, F.text, F.n, cstart, len, packed))) return rc;
+            if ((rc = F.stream ? bgzf_gather(m, s, F.declined, F.n_declined, csaved, len, packed) : bgzf_gather(m, s, F.text, F.n, cstart, len, packed)))
+                return rc;
             const char *dir = getenv("TMPDIR");
             std::string name = std::string(dir && *dir ? dir : "/tmp") + "/m6a_declined_XXXXXX";
             const int tfd = ::mkstemp(&name[0]);
@@ -2112,7 +2440,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
             ::close(tfd);
             for (size_t i = 0, at = 0; i < crun.size(); i++) { cstart[i] = (int64_t)at; at += (size_t)len[i]; cend[i] = (int64_t)at; }
         }
-        const int hrc = host->rows(F.text ? tmp.path.c_str() : path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, n_threads, &hr);
+        const int hrc = host->rows(resident ? tmp.path.c_str() : path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, n_threads, &hr);
         if (hrc != 0 || !hr) {                              // its own code and text (m6a_io's -1..-4 -> M6A_EINVAL, ENOMEM, EIO, EFORMAT)
             const int code = hrc == -2 ? M6A_ENOMEM : hrc == -3 ? M6A_EIO : hrc == -4 ? M6A_EFORMAT : hrc == -1 ? M6A_EINVAL : M6A_EIO;
             return prep_fail(code, "%s", host->error ? host->error() : "the host half failed on the declined runs");
@@ -2136,6 +2464,8 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         }
     }
     if (F.text) m.release(F.text);                          // names and declined runs are on the host: X needs the room
+    if (F.heads) m.release(F.heads);
+    if (F.declined) m.release(F.declined);
     const int64_t NH = (int64_t)hpos.size(), NT = (int64_t)tx_runs.size();
     if (NROW + NH > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate rows");
     host_ms += now_ms() - t1;
@@ -2893,8 +3223,11 @@ extern "C" int m6a_prep_sites_build_names(int device_id, const char *const *path
                                           m6a_prep_sites **out)
 {
     if (!paths || !out || n_paths < 1) return prep_fail(M6A_EINVAL, "null argument");
-    for (int f = 0; f < n_paths; f++)
+    for (int f = 0, n_stdin = 0; f < n_paths; f++) {
         if (!paths[f]) return prep_fail(M6A_EINVAL, "null argument");
+        if (is_stdin(paths[f]) && ++n_stdin > 1)            // before anything is opened
+            return prep_fail(M6A_EINVAL, "`-` is the standard input and can be read once: it is given twice");
+    }
     *out = nullptr;
     m6a_prep_sites *p = new (std::nothrow) m6a_prep_sites;
     if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
@@ -2926,6 +3259,8 @@ extern "C" int m6a_prep_sites_read_names(const m6a_prep_sites *p, const uint8_t 
 }
 
 extern "C" double m6a_prep_sites_intern_ms(const m6a_prep_sites *p) { return p ? p->ms_intern : 0; }
+extern "C" int64_t m6a_prep_sites_stream_bytes(const m6a_prep_sites *p) { return p ? p->stream_bytes : 0; }
+extern "C" int64_t m6a_prep_sites_n_streams(const m6a_prep_sites *p) { return p ? p->n_streams : 0; }
 
 extern "C" int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, double *mod_ratio)
 {

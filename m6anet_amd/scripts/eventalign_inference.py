@@ -34,7 +34,11 @@ def argparser():
                         help="eventalign filepath, the output from nanopolish; plain text or BGZF (bgzip) -- told apart by content, "
                              "inflated on the device, and replicates may mix the two.  Several files are replicates: their sites are pooled "
                              "as `inference` pools several --input_dir (a site is kept when its reads summed over the files reach 20), "
-                             "and read ids are written <id>_<position of the file>.")
+                             "and read ids are written <id>_<position of the file>.  `-` is the standard input, and a path that is no "
+                             "regular file (a FIFO, a process substitution) is read as a stream too: `f5c eventalign ... | m6anet_amd "
+                             "eventalign_inference --eventalign - ...` needs no eventalign file on disk.  A stream is plain text (inflate "
+                             "a compressed one on the way: `bgzip -dc FILE |`), is read once and in order, always in windows (--window_mb), "
+                             "and gives the bytes the same text in a file gives; replicates may mix files and streams, `-` once.")
     parser.add_argument("--out_dir", required=True, help="directory to output inference results.")
     _copy(dataprep.argparser(), parser, DATAPREP_FLAGS)
     _copy(inference.argparser(), parser, INFERENCE_FLAGS)
@@ -52,7 +56,8 @@ def cli_parser():
                         help="parse each eventalign file in windows of this many MB instead of keeping all of it in device memory "
                              "(0: the whole file, about 3 bytes of device memory per byte of text -- unless M6A_PREP_WINDOW_KB is set, which 0 leaves in force).  With windows the device "
                              "holds two windows and the candidate rows, so a file larger than device memory goes through; the bytes "
-                             "written are the same.")
+                             "written are the same.  A stream (--eventalign -, a FIFO) is always parsed in windows: of this size, or of "
+                             "256 MB with neither this flag nor the variable set.")
     parser.add_argument("--compress", action="store_true",
                         help="write data.site_proba.csv.gz and data.indiv_proba.csv.gz (BGZF: zcat, bgzip -d and pandas.read_csv open "
                              "them) instead of the two plain files; the text inside is the same.  With --csv device the text is deflated "
@@ -202,6 +207,7 @@ def main(args):
                                                 "n_windows": sites.n_windows, "window_bytes": sites.window_bytes,
                                                 "peak_bytes": sites.peak_bytes, "inflate": sites.ms_inflate,
                                                 "compressed_bytes": sites.compressed_bytes, "n_bgzf_blocks": sites.n_bgzf_blocks,
+                                                "stream_bytes": sites.stream_bytes, "n_streams": sites.n_streams,
                                                 **({"n_replicates": sites.n_replicates} if sites.n_replicates > 1 else {})}), flush=True)
     finally:
         sites.close()

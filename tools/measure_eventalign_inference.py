@@ -65,7 +65,17 @@ The shape's file and its named twin -- every read index replaced by a UUID from 
 writes the column -- as interleaved legs of the one-file command, the named leg with --read_names: medians, the phase table of every
 leg with the `intern` phase and n_read_names, the named file's size over the indexed one's, data.site_proba.csv of the two compared
 and the rows of data.indiv_proba.csv counted.  The named leg carries no bar (its lines are 30-odd bytes longer, so it uploads more).
-With --parent_tree the default command on the indexed file against the parent's, the bar of mode (b)."""
+With --parent_tree the default command on the indexed file against the parent's, the bar of mode (b).
+
+    python tools/measure_eventalign_inference.py --stream [--shapes 3.1GB] [--legs 5] [--window_mb 256] [--parent_tree DIR]
+                                                 [--out profiles/r16_stream_input.json]
+
+The shape's file read as a file and as a stream, interleaved legs of the one-file command at the same window size: `--eventalign FILE
+--window_mb W` and `cat FILE | ... --eventalign - --window_mb W` (the time is the pipeline's: cat is started with the command and has
+ended when it has).  Medians, the phase table of every leg with stream_bytes and n_streams, the stream's bytes per second of its
+upload wait, peak and device-to-host bytes, and the CSV files of the two compared.  The stream leg carries no bar: a pipe moves its
+bytes through read() and may be slower than pread from the page cache; which is faster is reported.  With --parent_tree the default
+command (no window, a file) against the parent's, the bar of mode (b)."""
 import filecmp
 import gzip
 import json
@@ -452,6 +462,65 @@ def read_names_legs(tag, legs, parent, ev_dir, limit):
     return res
 
 
+def timed_from_pipe(path, cmd, limit, env=None):
+    """`cat path | python -m m6anet_amd cmd`: the wall time of the two and the command's result"""
+    t0 = time.perf_counter()
+    cat = subprocess.Popen(["cat", path], stdout=subprocess.PIPE)
+    try:
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, "-m", "m6anet_amd"] + cmd, stdin=cat.stdout, capture_output=True,
+                           text=True, cwd=REPO, env=env)
+    finally:
+        cat.stdout.close()                                  # a command that ended early: cat meets a closed pipe and ends
+        cat.wait()
+    return time.perf_counter() - t0, p
+
+
+def stream_legs(tag, legs, window_mb, parent, ev_dir, limit):
+    path, n = write_shape(tag, ev_dir)
+    res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs, "window_mb": window_mb}
+    runs = {"file": [], "stream": []}
+    one, par = [], []
+    env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    env.pop("M6A_PREP_WINDOW_KB", None)
+    flags = ["--window_mb", str(window_mb)] + THREADS
+    try:
+        for leg in range(legs):
+            s, p = timed(["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "file")] + flags, limit, env=env)
+            must(s, p, "file")
+            runs["file"].append(dict(json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0]), s=s))
+            s, p = timed_from_pipe(path, ["eventalign_inference", "--eventalign", "-", "--out_dir", os.path.join(ev_dir, "stream")] + flags, limit, env=env)
+            must(s, p, "stream")
+            runs["stream"].append(dict(json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0]), s=s))
+            res["csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "file", f), os.path.join(ev_dir, "stream", f), shallow=False) for f in CSVS)
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit), "default command, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, tree=parent), "default command, parent tree"))
+                res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
+                                                                 shallow=False) for f in CSVS)
+            for d in ("file", "stream", "one", "one_parent"):
+                subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+            print("%s: leg %d of %d: file %.2f s, stream %.2f s" % (tag, leg + 1, legs, runs["file"][-1]["s"], runs["stream"][-1]["s"]),
+                  file=sys.stderr, flush=True)
+        for mode in runs:
+            v = runs[mode]
+            res[mode] = {"median_s": median([x["s"] for x in v]), "upload_wait_ms": median([x["ms"]["upload"] for x in v]),
+                         "upload_GBps": median([x["ms"]["upload_GBps"] for x in v]), "back_half_ms": median([x["ms"]["back_half"] for x in v]),
+                         "n_windows": v[-1]["n_windows"], "window_bytes": v[-1]["window_bytes"], "stream_bytes": v[-1]["stream_bytes"],
+                         "n_streams": v[-1]["n_streams"], "peak_bytes": v[-1]["peak_bytes"], "d2h_bytes": v[-1]["d2h_bytes"], "legs": v}
+        res["stream_over_file_time"] = res["stream"]["median_s"] / res["file"]["median_s"]
+        if parent:
+            res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                                      "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                                      "within_bar": median(one) <= median(par) + max(par) - min(par)}
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+        res["legs_done"] = runs
+    os.remove(path)
+    return res
+
+
 def compress_legs(tag, legs, parent, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs}
@@ -611,6 +680,24 @@ def main():
         with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
             for tag in shapes:
                 res[tag] = bgzf_legs(tag, legs, parent, d, limit)
+                print(json.dumps({tag: res[tag]}), flush=True)
+                os.makedirs(os.path.dirname(dest), exist_ok=True)
+                with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured
+                    json.dump(res, f, indent=1)
+                if "failed" in res[tag]:
+                    break                                   # a failed step: nothing more is started
+        return
+    if "--stream" in sys.argv:
+        shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB"]
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r16_stream_input.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
+        window_mb = int(sys.argv[sys.argv.index("--window_mb") + 1]) if "--window_mb" in sys.argv else 256
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        if os.path.exists(dest):                            # one shape per call is allowed: the shapes share the file
+            res = json.load(open(dest))
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                res[tag] = stream_legs(tag, legs, window_mb, parent, d, limit)
                 print(json.dumps({tag: res[tag]}), flush=True)
                 os.makedirs(os.path.dirname(dest), exist_ok=True)
                 with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured

@@ -587,6 +587,48 @@ int m6a_csv_format(int device_id, const m6a_csv_arrays *a, int64_t site_begin, i
 int m6a_prep_sites_write_csv(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
                              m6a_csv_stats *stats);
 
+/* `dataprep --device gpu --writer device`: eventalign.index, data.json, data.info and data.log from arrays that never leave device
+ * memory -- the bytes m6a_io_dataprep writes (include/m6a_io.h); tests/dataprep_json_statement.py states them in plain Python:
+ *   data.json         per kept site {"<tx>":{"<pos>":{"<7-mer>":[[f,f,f,f,f,f,f,f,f,<read>.0],[...]]}}}\n  -- f = repr(float) of the nine
+ *                     features in f64 (of np.round(f, 3) with `compress`), sites by transcript (order of first appearance), then
+ *                     position, a site's reads in the order the host writer gives them
+ *   eventalign.index  transcript_id,read_index,pos_start,pos_end\n, then <tx>,<read>,<start>,<end>\n per run, in file order
+ *   data.info         transcript_id,transcript_position,start,end,n_reads\n, then <tx>,<pos>,<start>,<end>,<n_reads>\n per kept site:
+ *                     [start, end) is the site's record in data.json
+ *   data.log          <tx>: Data preparation ... Done.\n per transcript that passed the readcount cut with a candidate row
+ * Numbers are printed by the core of m6anet_amd/csrc/m6a_repr.h, which DECLINES, and the kernels count: a feature that, after the
+ * rounding of `compress`, is not a finite value with 1e-4 <= v < 1e16 (zero, negatives, what repr writes with an exponent, NaN, the
+ * infinities), and a read index outside [0, 2^53).
+ *
+ * m6a_repr_format: HOST array in, every v[i] printed on device device_id (round3: np.round(v, 3) first), the texts out back to back:
+ * value i is text[off[i], off[i + 1]); a declined value takes no bytes and is counted in *n_declined.  off [n + 1] and *n_declined are
+ * always set; text = NULL is the sizing call, else cap must be >= off[n].  Needs no weights and no m6a_ctx.
+ *
+ * m6a_prep_dataprep_write: the back half of m6a_prep_sites_build under dataprep's rules (n_neighbors = 1; sites kept at
+ * >= min_segment_count reads, no 20-read floor; no normalisation, no vocabulary; reads that disagree on a site's 7-mer are M6A_EFORMAT
+ * with the host writer's text), then lengths (json_len_kernel, index_len_kernel), 64-bit scans -- both file sizes, every record's
+ * [start, end) and the declined count are known before a file is opened -- and the text (json_write_kernel, index_write_kernel: a
+ * wave stages text in LDS and stores aligned dwords) in rounds of whole sites / whole index rows bounded by M6A_JSON_ROUND_KB of text
+ * (default 32768; a larger site is a round of its own), double-buffered in pinned memory and pwrite()n at their offsets by n_threads
+ * threads (0: the CPUs this process may use).  Per kept site position, transcript, [start, end) and n_reads come back, per
+ * transcript one byte; data.info and data.log are printed from them on the host.  Runs the front half declines go through `host`
+ * as in m6a_prep_sites_build.  M6A_PREP_WINDOW_KB and M6A_PREP_CHUNK_KB as there; BGZF files and streams are refused (M6A_EINVAL).
+ * With anything declined the call returns M6A_EDECLINED, has opened no file, and the caller writes through the host
+ * (m6a_io_dataprep_write).  Other errors carry the host path's codes and texts (short line, no header, disagreeing sequence, missing
+ * file); over the device budget is M6A_ENOMEM naming --device cpu.  On any error none of the four files is left behind.  stats (may
+ * be NULL) is filled on every return. */
+typedef struct m6a_dataprep_stats {
+    double ms_front, ms_back, ms_format, ms_copy, ms_write;   /* front half; back half; lengths + scans + write kernels; device -> pinned; pwrite */
+    int64_t json_bytes, index_bytes;                          /* sizes of data.json and eventalign.index (its header counted) */
+    int64_t n_sites, n_runs, n_declined, n_rounds;            /* n_rounds: of data.json and of eventalign.index together */
+    int64_t d2h_bytes, peak_bytes;
+} m6a_dataprep_stats;
+int m6a_repr_format(int device_id, const double *v, int64_t n, int round3, char *text, int64_t cap, int64_t *off /* [n + 1] */,
+                    int64_t *n_declined);
+int m6a_prep_dataprep_write(int device_id, const char *path, const char *out_dir, int readcount_min, int readcount_max,
+                            int min_segment_count, int compress, const m6a_prep_host_half *host, int n_threads,
+                            m6a_dataprep_stats *stats);
+
 /* BGZF input (htslib's bgzip; SAM specification section 4.1).  m6a_prep_sites_build, _multi and _windows take a file of either kind,
  * and replicates may mix them; tests/bgzf_statement.py states the same in plain Python.
  *   detection    by content, never by name: a file whose first bytes are not 1f 8b is text and takes the path above untouched.  A file

@@ -127,6 +127,11 @@ int m6a_io_py_repr(double v, char *buf40);
  * double for 0 < |v| < 1e9; returns the length, or -1 where the fast path declines (zero, huge, not the double nearest to
  * k / 10^digits, digits other than 1 or 3) and m6a_io_py_repr's general algorithm is used.  Exported for the tests. */
 int m6a_io_repr_rounded(double v, int digits, char *buf40);
+/* The number core the device writer of data.json compiles (m6anet_amd/csrc/m6a_repr.h), on the host: repr(v), or with round3
+ * repr(np.round(v, 3)), for exactly the finite values with 1e-4 <= v < 1e16 after the rounding -- the bytes m6a_io_py_repr gives,
+ * at most 24 of them, NUL-terminated.  Returns the length, or -1 where the core DECLINES (zero, negatives, below 1e-4, 1e16 and
+ * above, NaN, the infinities; buf40 then holds an empty string).  Exported so the CPU tests reach the core without a GPU. */
+int m6a_io_repr_core(double v, int round3, char *buf40);
 
 /* `m6anet dataprep` (m6anet/scripts/dataprep.py:54-70 -> m6anet/utils/dataprep_utils.py):
  * eventalign.txt -> <out_dir>/eventalign.index (parallel_index, :187-266), data.json + data.info +

@@ -8,7 +8,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("M6A_IO_LIB") or os.path.join(_PKG, "libm6a_io.so")   # M6A_IO_LIB: e.g. the sanitizer build (tests/sanitize.sh)
 SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_sites", "m6a_io_n_reads",
            "m6a_io_n_replicates", "m6a_io_X", "m6a_io_site_kmers", "m6a_io_off", "m6a_io_tx_pos",
-           "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded",
+           "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded", "m6a_io_repr_core",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
            "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_sites_set_read_names", "m6a_io_uuid_parse", "m6a_io_uuid_format", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
            "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk"]
@@ -85,6 +85,8 @@ def load():
     L.m6a_io_py_repr.restype = i32
     L.m6a_io_repr_rounded.argtypes = [C.c_double, i32, C.c_char_p]
     L.m6a_io_repr_rounded.restype = i32
+    L.m6a_io_repr_core.argtypes = [C.c_double, i32, C.c_char_p]
+    L.m6a_io_repr_core.restype = i32
     L.m6a_io_save_store.argtypes = [vp, C.c_char_p, C.c_char_p]
     L.m6a_io_open_store.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.m6a_io_store_tag.argtypes = [vp]
@@ -138,20 +140,91 @@ def _chk(rc):
 
 
 def dataprep(eventalign, out_dir, n_threads=0, readcount_min=1, readcount_max=1000, min_segment_count=20,
-             n_neighbors=1, compress=False, skip_index=False, device="cpu", device_id=0):
+             n_neighbors=1, compress=False, skip_index=False, device="cpu", device_id=0, writer="host", stats=None):
     """Native `m6anet dataprep` (m6anet/scripts/dataprep.py:54-70).  device="gpu": the line scan, parse, combine and windows run
     in HIP (m6a_prep_eventalign, include/m6a.h) and the host writes the same four files from their table
-    (m6a_io_dataprep_write); a file larger than the device budget is an error, never a silent host run."""
+    (m6a_io_dataprep_write); a file larger than the device budget is an error, never a silent host run.
+    writer="device" (with device="gpu", n_neighbors=1 and no skip_index; anything else is a ValueError before a file is touched):
+    m6a_prep_dataprep_write -- the back half runs on the device as well and the four files are formatted there, byte for byte the
+    host writer's.  Where the device's number printer declines a value (include/m6a.h) nothing has been written: one line goes to
+    stderr and the files are written by the writer="host" route from the start.  `stats`: a dict that receives the
+    m6a_dataprep_stats fields and `writer`, "device" or "host" -- which one wrote the files; M6A_DATAPREP_TIMES=1 prints them as one
+    `M6A_TIMES {json}` line on stderr."""
     if device not in ("cpu", "gpu"):
         raise ValueError("device must be 'cpu' or 'gpu', not %r" % (device,))
+    if writer not in ("host", "device"):
+        raise ValueError("writer must be 'host' or 'device', not %r" % (writer,))
+    if writer == "device":
+        conflict = dataprep_writer_conflict(device, skip_index, n_neighbors)
+        if conflict:
+            raise ValueError(conflict)
     os.makedirs(out_dir, exist_ok=True)
     if device == "cpu":
         _chk(load().m6a_io_dataprep(os.fsencode(eventalign), os.fsencode(out_dir), int(n_threads), int(readcount_min),
                                     int(readcount_max), int(min_segment_count), int(n_neighbors), 1 if compress else 0,
                                     1 if skip_index else 0))
         return
+    if writer == "device":
+        st = _dataprep_on_device(eventalign, out_dir, n_threads, readcount_min, readcount_max, min_segment_count, compress, device_id)
+        if st["writer"] == "host":
+            import sys
+            print("dataprep: --writer device declined %d values; writing on the host" % st["n_declined"], file=sys.stderr)
+        if stats is not None:
+            stats.update(st)
+        if os.environ.get("M6A_DATAPREP_TIMES") == "1":
+            import json
+            import sys
+            print("M6A_TIMES " + json.dumps(st), file=sys.stderr)
+        if st["writer"] == "device":
+            return
     with prep_on_device(eventalign, n_neighbors, os.path.join(out_dir, "eventalign.index") if skip_index else None, device_id) as table:
         write_table(eventalign, out_dir, table, n_threads, readcount_min, readcount_max, min_segment_count, compress, not skip_index)
+
+
+def dataprep_writer_conflict(device, skip_index, n_neighbors):
+    """What `--writer device` cannot be combined with: the text of the argument error, naming the flag, or None."""
+    if device != "gpu":
+        return "--writer device formats the files on the GPU and conflicts with --device cpu: give --device gpu"
+    if skip_index:
+        return "--writer device writes eventalign.index itself and conflicts with --skip_index"
+    if int(n_neighbors) != 1:
+        return "--writer device prints one neighbour either side and conflicts with --n_neighbors %d: only --n_neighbors 1" % int(n_neighbors)
+    return None
+
+
+def _dataprep_on_device(eventalign, out_dir, n_threads, readcount_min, readcount_max, min_segment_count, compress, device_id):
+    """m6a_prep_dataprep_write: the statistics as a dict, with `writer` = "device", or "host" where values were declined (nothing
+    written then).  Errors are M6AIOError with the host path's code."""
+    from . import _lib
+    L, io = _lib.load(), load()
+    host = _lib.HostHalf(C.cast(io.m6a_io_runs_rows, C.c_void_p), C.cast(io.m6a_io_rows_table, C.c_void_p),
+                         C.cast(io.m6a_io_rows_free, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
+    st = _lib.DataprepStats()
+    rc = L.m6a_prep_dataprep_write(int(device_id), os.fsencode(eventalign), os.fsencode(out_dir), int(readcount_min), int(readcount_max),
+                                   int(min_segment_count), 1 if compress else 0, C.byref(host), int(n_threads), C.byref(st))
+    out = {k: getattr(st, k) for k, _ in st._fields_}
+    out["writer"] = "host" if rc == _lib.M6A_EDECLINED else "device"
+    if rc not in (0, _lib.M6A_EDECLINED):
+        raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), prep_on_device._CODES.get(rc, rc))
+    return out
+
+
+def repr_format(values, round3=False, device_id=0):
+    """m6a_repr_format (libm6a_hip.so): repr(float) of every value -- of np.round(v, 3) with round3 -- printed on the device by the
+    core the data.json writer uses.  Returns (text, off, n_declined): value i is text[off[i]:off[i + 1]], empty where declined."""
+    from . import _lib
+    L = _lib.load()
+    v = np.ascontiguousarray(values, np.float64)
+    off, nd = np.zeros(v.size + 1, np.int64), C.c_int64()
+
+    def call(buf, cap):
+        rc = L.m6a_repr_format(int(device_id), v.ctypes.data, v.size, 1 if round3 else 0, buf, cap, off.ctypes.data, C.byref(nd))
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, L.m6a_prep_last_error().decode()), prep_on_device._CODES.get(rc, rc))
+    call(None, 0)
+    buf = C.create_string_buffer(max(1, int(off[-1])))
+    call(buf, int(off[-1]))
+    return buf.raw[:int(off[-1])], off, nd.value
 
 
 def write_table(eventalign, out_dir, table, n_threads=0, readcount_min=1, readcount_max=1000, min_segment_count=20, compress=False,

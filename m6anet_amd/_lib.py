@@ -20,7 +20,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
-           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build"]
+           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_repr_format", "m6a_prep_dataprep_write"]
 
 _lib = None
 
@@ -76,6 +76,13 @@ class CsvStats(C.Structure):
     """m6a_csv_stats (include/m6a.h)."""
     _fields_ = [("ms_format", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double), ("site_bytes", C.c_int64),
                 ("indiv_bytes", C.c_int64), ("n_declined", C.c_int64), ("d2h_bytes", C.c_int64), ("n_rounds", C.c_int64)]
+
+
+class DataprepStats(C.Structure):
+    """m6a_dataprep_stats (include/m6a.h)."""
+    _fields_ = [("ms_front", C.c_double), ("ms_back", C.c_double), ("ms_format", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double),
+                ("json_bytes", C.c_int64), ("index_bytes", C.c_int64), ("n_sites", C.c_int64), ("n_runs", C.c_int64), ("n_declined", C.c_int64),
+                ("n_rounds", C.c_int64), ("d2h_bytes", C.c_int64), ("peak_bytes", C.c_int64)]
 
 
 class M6AError(RuntimeError):
@@ -208,6 +215,8 @@ def load():
     L.m6a_prep_sites_write_csv_bgzf.argtypes = [vp, C.c_char_p, i32, i64, i32, C.POINTER(CsvBgzfStats)]
     L.m6a_bgzf_deflate_level.argtypes = [i32, C.c_char_p, i64, i32, vp, i64, pl, C.POINTER(DeflateStats), pl]
     L.m6a_prep_sites_write_csv_bgzf_level.argtypes = [vp, C.c_char_p, i32, i64, i32, i32, C.POINTER(CsvBgzfStats), pl]
+    L.m6a_repr_format.argtypes = [i32, vp, i64, i32, vp, i64, vp, pl]
+    L.m6a_prep_dataprep_write.argtypes = [i32, C.c_char_p, C.c_char_p, i32, i32, i32, i32, C.POINTER(HostHalf), i32, C.POINTER(DataprepStats)]
     L.m6a_prep_last_error.argtypes = []
     L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:

@@ -2,6 +2,7 @@
 // Host-only C++17; parsing and formatting are spread over std::threads by site range.
 #include "m6a_io.h"
 #include "m6a_host_cpus.h"
+#include "m6a_repr.h"
 #include "m6a_uuid.h"
 
 #include <fcntl.h>
@@ -1687,6 +1688,14 @@ extern "C" int m6a_io_repr_rounded(double v, int digits, char *buf40)
     if (!repr_rounded(v, digits == 1 ? 10.0 : 1000.0, digits, s) || s.size() >= 40) return -1;
     std::memcpy(buf40, s.c_str(), s.size() + 1);
     return (int)s.size();
+}
+
+// the number core of the device writer (m6a_repr.h), as this compiler builds it
+extern "C" int m6a_io_repr_core(double v, int round3, char *buf40)
+{
+    const int n = m6a_repr::feature<true>(v, round3, buf40);
+    buf40[n < 0 ? 0 : n] = 0;
+    return n;
 }
 
 static int dataprep_impl(const char *eventalign_path, const char *out_dir, int n_threads,

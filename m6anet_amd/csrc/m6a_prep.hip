@@ -2026,6 +2026,31 @@ __global__ void x_kernel(const uint32_t *__restrict__ L, const int64_t *__restri
 
 const unsigned long long kMinMax0[2] = {~0ull, 0}, kNone = ~0ull;
 
+// `dataprep --writer device` (m6a_dataprep.h, included at the end of this file): what sites_impl hands to the writer
+struct DataprepJob { const char *out_dir; int compress, n_threads; m6a_dataprep_stats *st; };
+struct JsonDev {                           // device pointers: the back half's sorted rows and kept sites
+    const uint32_t *L;                     // [NL] candidate rows sorted by (transcript, position, place)
+    const int64_t *src, *off;              // [S] where site i starts in L; [S + 1] its reads are off[i + 1] - off[i]
+    RowSrc rs;
+    const uint32_t *row_run;               // row -> run
+    const RunDev *runs;
+    const uint32_t *site_tx;               // [S]
+    const int64_t *site_pos;               // [S]
+    const uint8_t *site_k7;                // [S][7]
+    const uint8_t *tx_blob;
+    const int64_t *tx_off;
+    int round3;                            // --compress
+};
+
+struct DataprepSrc {
+    JsonDev json;                          // tx_blob, tx_off and round3 are the writer's to fill
+    const uint32_t *run_tx;                // [NR]
+    int64_t NS, NR, NL, NT;
+    const std::string *blob;               // the transcript names on the host
+    const std::vector<int64_t> *tx_off;    // [NT + 1]
+};
+int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const DataprepSrc &src);
+
 int bits_for(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 
 // stable sort of (key, val) by the low `bits` bits of key; key / val end up pointing at the sorted pair (swapped with key2 / val2)
@@ -2271,7 +2296,7 @@ uint32_t Pool::global_tx(const std::string &nm, m6a_prep_sites &P)
 // on the device as a FilePart, and everything else the file needed -- its text, line records, candidate rows -- is released.
 int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
                const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window, m6a_prep_sites &P, DevMem &m,
-               double *ms, Pool *pool)
+               double *ms, Pool *pool, const DataprepJob *job = nullptr)
 {
     const bool read_names = P.read_names;
     const double t_all = now_ms();
@@ -2285,7 +2310,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     Streams S;
     Fd fd;
     Front F;
-    F.bgzf_ok = true;
+    F.bgzf_ok = !job;                                       // dataprep's index holds offsets into the text: BGZF and streams stay refused
     F.read_names = read_names;
     int rc = front_half(device_id, path, 1, nullptr, nullptr, window, m, S, fd, F, fms);
     if (rc) return rc;
@@ -2637,7 +2662,7 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
                          (long long)hp[1]);
     }
     if (NS0) {
-        site_keep_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, pool ? (int64_t)min_seg : std::max<int64_t>(min_seg, 20), kx);
+        site_keep_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, pool || job ? (int64_t)min_seg : std::max<int64_t>(min_seg, 20), kx);
         PCHK(hipGetLastError());
     }
     if ((rc = scan_total(m, kx, NS0, s, NS))) return rc;
@@ -2650,6 +2675,30 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
     }
     int64_t R = 0;
     if ((rc = scan_total(m, doff, NS, s, R))) return rc;
+
+    if (job) {                                              // dataprep: no normalisation, no vocabulary, and text instead of X
+        uint32_t *jtx;
+        int64_t *jpos;
+        uint8_t *jk7, *jkm;
+        int32_t *jnorm;
+        if ((rc = m.alloc(jtx, (size_t)NS + 1, "sites")) || (rc = m.alloc(jpos, (size_t)NS + 1, "sites")) || (rc = m.alloc(jk7, (size_t)NS * 7 + 1, "sites")) ||
+            (rc = m.alloc(jkm, (size_t)NS * 3 + 1, "sites")) || (rc = m.alloc(jnorm, (size_t)NS * 3 + 1, "sites")))
+            return rc;
+        if (NS) {
+            site_info_kernel<<<grid(NS), kBlk, 0, s>>>(L, src, NS, rs, row_run, run_tx, nullptr, nullptr, 0, nullptr, 0, jnorm, jkm, jtx, jpos, jk7, bad,
+                                                       nullptr, 1);
+            PCHK(hipGetLastError());
+        }
+        PCHK(hipStreamSynchronize(s));
+        for (const void *p : {(const void *)jkm, (const void *)jnorm, (const void *)k1, (const void *)k2, (const void *)L2, (const void *)shx,
+                              (const void *)start, (const void *)kx})
+            m.release(p);
+        dev_ms += now_ms() - t1;
+        job->st->ms_front = fms[0] + fms[1] + fms[2];
+        job->st->ms_back = dev_ms + host_ms;
+        const DataprepSrc ds{JsonDev{L, src, doff, rs, row_run, F.runs, jtx, jpos, jk7, nullptr, nullptr, 0}, run_tx, NS, NR, NL, NT, &blob, &tx_off};
+        return dataprep_emit(m, s, *job, ds);
+    }
 
     // ---- normalisation, vocabulary, X
     std::vector<uint64_t> nk, voc = vocab_keys();
@@ -3294,6 +3343,7 @@ extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }
 #define M6A_BGZF_DEVICE_PART
 #include "m6a_bgzf.h"
 #include "m6a_csv.h"
+#include "m6a_dataprep.h"
 #define M6A_DEFLATE_DEVICE_PART
 #include "m6a_deflate.h"
 #define M6A_JSON_DEVICE_PART

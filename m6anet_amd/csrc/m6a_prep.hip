@@ -17,8 +17,8 @@
 //   combine     one lane per run: Kahan sums per (position, k-mer) group, count then write
 //   windows     one lane per run: runs of 2w + 1 consecutive positions with a DRACH centre, count then write
 // With a window size (M6A_PREP_WINDOW_KB, m6a_prep_sites_build_windows) the same kernels run on one window of the file after the other
-// and only runs and rows stay on the device: front_windows, below.  Text from a pipe (`-`, a FIFO) goes through the same windows as it
-// arrives, and what the back half would read again is saved from every window: front_stream, below it.
+// and only runs and rows stay on the device: front_windows, below, over a FileSource.  Text from a pipe (`-`, a FIFO) goes through the
+// same windows as it arrives, and what the back half would read again is saved from every window: the same loop over a StreamSource.
 // Everything is built with -ffp-contract=off (build.py): no multiply-add is fused, and the f64 divisions are IEEE `/`.
 #include <hip/hip_runtime.h>
 
@@ -596,6 +596,7 @@ struct DevMem {
             }
     }
     void release(const void *p) { drop(p, true); }
+    void release(std::initializer_list<const void *> ps) { for (const void *p : ps) drop(p, true); }
     void detach(const void *p) { drop(p, false); }
     size_t size_of(const void *p) const
     {
@@ -628,6 +629,68 @@ struct Fd {
     ~Fd() { if (own && fd >= 0) ::close(fd); }
 };
 
+// one lane per item: grid(n) blocks of kBlk on s, and nothing at n <= 0
+template <class... P, class... A> int launch(void (*kernel)(P...), int64_t n, hipStream_t s, A... args)
+{
+    if (n <= 0) return M6A_OK;
+    kernel<<<grid(n), kBlk, 0, s>>>(args...);
+    PCHK(hipGetLastError());
+    return M6A_OK;
+}
+
+// len rounded up to whole scan blocks, one at the least: what a text buffer holds, zeros behind the text
+inline int64_t padded(int64_t len) { return std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes; }
+
+// one value device -> host, there when this returns
+template <class T> int fetch(T &host, const T *dev, hipStream_t s)
+{
+    PCHK(hipMemcpyAsync(&host, dev, sizeof(T), hipMemcpyDeviceToHost, s));
+    g_d2h += (int64_t)sizeof(T);
+    PCHK(hipStreamSynchronize(s));
+    return M6A_OK;
+}
+
+// file bytes [off, off + len) -> dst, all of them
+int read_fully(int fd, void *dst, int64_t len, int64_t off, const char *path)
+{
+    for (int64_t got = 0; got < len;) {
+        const ssize_t r = ::pread(fd, (char *)dst + got, (size_t)(len - got), (off_t)(off + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
+        got += r;
+    }
+    return M6A_OK;
+}
+
+int write_fully(int fd, const void *src, size_t len, const char *path)
+{
+    for (size_t got = 0; got < len;) {
+        const ssize_t k = ::write(fd, (const char *)src + got, len - got);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) return prep_fail(M6A_EIO, "cannot write %s", path);
+        got += (size_t)k;
+    }
+    return M6A_OK;
+}
+
+// names -> ids in order of first appearance; a new name goes behind blob, where tx_off says it starts (the caller closes tx_off)
+struct Interner {
+    std::string &blob;
+    std::vector<int64_t> &tx_off;
+    std::unordered_map<std::string, uint32_t> ids;
+    Interner(std::string &b, std::vector<int64_t> &o) : blob(b), tx_off(o) {}
+    uint32_t id(const std::string &nm)
+    {
+        auto it = ids.find(nm);
+        if (it != ids.end()) return it->second;
+        const uint32_t t = (uint32_t)ids.size();
+        ids.emplace(nm, t);
+        tx_off.push_back((int64_t)blob.size());
+        blob += nm;
+        return t;
+    }
+};
+
 int scan_excl(DevMem &m, int64_t *a, int64_t n, hipStream_t s)
 {
     const int64_t per = kBlk * 4, nb = (n + per - 1) / per;
@@ -650,11 +713,7 @@ int scan_total(DevMem &m, int64_t *a, int64_t n, hipStream_t s, int64_t &total)
 {
     PCHK(hipMemsetAsync(a + n, 0, sizeof(int64_t), s));
     int rc = scan_excl(m, a, n + 1, s);
-    if (rc) return rc;
-    PCHK(hipMemcpyAsync(&total, a + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    g_d2h += (int64_t)sizeof(int64_t);
-    PCHK(hipStreamSynchronize(s));
-    return M6A_OK;
+    return rc ? rc : fetch(total, a + n, s);
 }
 
 // the rows of an existing eventalign.index, as m6a_io.cpp's read_index_file reads them
@@ -698,30 +757,22 @@ int find_runs(DevMem &m, hipStream_t s, const uint8_t *df, int64_t n, const int6
     int rc;
     int64_t *vflag, NV = 0;
     if ((rc = m.alloc(vflag, (size_t)nlines + 1, "valid lines"))) return rc;
-    flag_kernel<<<grid(nlines), kBlk, 0, s>>>(ev, nlines, first, vflag);
-    PCHK(hipGetLastError());
+    if ((rc = launch(flag_kernel, nlines, s, ev, nlines, first, vflag))) return rc;
     if ((rc = scan_total(m, vflag, nlines, s, NV))) return rc;
     int64_t *vline, *nr;
     if ((rc = m.alloc(vline, (size_t)NV + 1, "valid lines"))) return rc;
     if ((rc = m.alloc(nr, (size_t)NV + 1, "run starts"))) return rc;
     if (scratch) scratch->insert(scratch->end(), {vflag, vline, nr});
-    compact_kernel<<<grid(nlines), kBlk, 0, s>>>(vflag, nlines, first, ev, vline);
-    PCHK(hipGetLastError());
-    if (NV > 0) {
-        if (lname) newrun_kernel<true><<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr, lname);
-        else newrun_kernel<false><<<grid(NV), kBlk, 0, s>>>(df, nl, ev, vline, NV, nr, nullptr);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(compact_kernel, nlines, s, vflag, nlines, first, ev, vline))) return rc;
+    if ((rc = lname ? launch(newrun_kernel<true>, NV, s, df, nl, ev, vline, NV, nr, lname)
+                    : launch(newrun_kernel<false>, NV, s, df, nl, ev, vline, NV, nr, nullptr)))
+        return rc;
     if ((rc = scan_total(m, nr, NV, s, NR))) return rc;     // nr[j] = run of valid line j (exclusive scan of the starts) ...
     // ... so valid line j's run is nr[j + 1] - 1: shift by one with an inclusive view
     if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
     if (lname && (rc = m.alloc(*rname, (size_t)NR + 1, "read names"))) return rc;
-    if (NV > 0) {
-        if (lname) runs_kernel<true><<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs, lname, *rname);
-        else runs_kernel<false><<<grid(NV), kBlk, 0, s>>>(df, n, nl, NL, ev, vline, NV, nr + 1, runs, nullptr, nullptr);
-        PCHK(hipGetLastError());
-    }
-    return M6A_OK;
+    return lname ? launch(runs_kernel<true>, NV, s, df, n, nl, NL, ev, vline, NV, nr + 1, runs, lname, *rname)
+                 : launch(runs_kernel<false>, NV, s, df, n, nl, NL, ev, vline, NV, nr + 1, runs, nullptr, nullptr);
 }
 
 // combine of runs[0, NR) (count, then write ps at pos_off) and the count of their candidate rows: row_off is the exclusive scan
@@ -731,21 +782,13 @@ int count_rows(DevMem &m, hipStream_t s, const uint8_t *df, const LineEv *ev, Ru
     int rc;
     int64_t NP = 0;
     if ((rc = m.alloc(pos_off, (size_t)NR + 1, "positions"))) return rc;
-    if (NR) {
-        combine_kernel<<<grid(NR), kBlk, 0, s>>>(df, ev, runs, NR, nullptr, nullptr);
-        PCHK(hipGetLastError());
-        run_cols_kernel<<<grid(NR), kBlk, 0, s>>>(runs, NR, pos_off);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(combine_kernel, NR, s, df, ev, runs, NR, nullptr, nullptr)) || (rc = launch(run_cols_kernel, NR, s, runs, NR, pos_off))) return rc;
     if ((rc = scan_total(m, pos_off, NR, s, NP))) return rc;
     if ((rc = m.alloc(ps, (size_t)NP + 1, "combined positions"))) return rc;
     if ((rc = m.alloc(row_off, (size_t)NR + 1, "rows"))) return rc;
-    if (NR) {
-        combine_kernel<<<grid(NR), kBlk, 0, s>>>(df, ev, runs, NR, pos_off, ps);
-        PCHK(hipGetLastError());
-        window_kernel<<<grid(NR), kBlk, 0, s>>>(df, runs, NR, pos_off, ps, w, row_off, nullptr, nullptr, nullptr, nullptr);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(combine_kernel, NR, s, df, ev, runs, NR, pos_off, ps)) ||
+        (rc = launch(window_kernel, NR, s, df, runs, NR, pos_off, ps, w, row_off, nullptr, nullptr, nullptr, nullptr)))
+        return rc;
     return scan_total(m, row_off, NR, s, NROW);
 }
 
@@ -764,7 +807,7 @@ struct Front {
     const uint8_t *text = nullptr;          // out, BGZF input: the inflated text, NOT in scratch -- the caller reads names and runs from it
     int64_t n_blocks = 0, comp_bytes = 0;   // out, BGZF input
     double ms_inflate = 0;
-    // out, a stream (front_stream): n is the bytes it delivered, and what the back half would read from a file again was saved from
+    // out, a stream (StreamSource): n is the bytes it delivered, and what the back half would read from a file again was saved from
     // every window while its text was there -- NOT in scratch, the caller releases them
     bool stream = false;
     const uint8_t *heads = nullptr;         // the contig bytes of every run that can head a segment, end to end in run order
@@ -778,9 +821,6 @@ bool bgzf_is_gzip(int fd, int64_t n);
 int bgzf_front(const char *path, int fd, int64_t n_file, DevMem &m, Streams &S, int64_t chunk, uint8_t *&text, int64_t &n_text, Front &F, double *ms);
 int bgzf_gather(DevMem &m, hipStream_t s, const uint8_t *text, int64_t n_text, const std::vector<int64_t> &src, const std::vector<int64_t> &len,
                 std::vector<uint8_t> &out);
-
-int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
-int front_stream(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms);
 
 // `-` is descriptor 0; whatever else fstat shows is no regular file (a FIFO, /dev/fd/N, a character device) is a stream as well
 bool is_stdin(const char *path) { return path[0] == '-' && path[1] == 0; }
@@ -805,8 +845,577 @@ int64_t window_from_env()
     return e && atoll(e) > 0 ? atoll(e) << 10 : 0;
 }
 
-// istart / iend: the runs of an eventalign.index (--skip_index), or null.  ms[0..2], ms[5] as m6a_prep_times reports them.
-// window > 0 (rounded up to whole 4 KB blocks) and no index: the file goes through in windows (front_windows); else it is resident.
+// file bytes [off, off + len) -> dst on the copy stream, zeros behind them to a whole scan block; returns when they have arrived.
+// per_chunk(slot, done, part) is called when the copy of bytes [done, done + part) has been recorded as S.copied[slot]: the resident
+// file counts the chunk's newlines behind that event while the next chunk is read (the zeros go first, so the last block is whole then)
+template <class Hook>
+int upload_range(int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk, Hook per_chunk)
+{
+    int rc;
+    PCHK(hipSetDevice(device_id));
+    if (padded(len) > len) PCHK(hipMemsetAsync(dst + len, 0, (size_t)(padded(len) - len), S.s[1]));
+    for (int64_t k = 0, done = 0; done < len; k++, done += chunk) {
+        const int slot = (int)(k & 1);
+        PCHK(hipEventSynchronize(S.copied[slot]));          // the copy that last used this buffer is done
+        const int64_t part = std::min(chunk, len - done);
+        if ((rc = read_fully(fd, S.pin[slot], part, off + done, path))) return rc;
+        PCHK(hipMemcpyAsync(dst + done, S.pin[slot], (size_t)part, hipMemcpyHostToDevice, S.s[1]));
+        PCHK(hipEventRecord(S.copied[slot], S.s[1]));
+        if ((rc = per_chunk(slot, done, part))) return rc;
+    }
+    PCHK(hipStreamSynchronize(S.s[1]));
+    return M6A_OK;
+}
+
+int upload_range(int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk)
+{
+    return upload_range(device_id, fd, path, S, dst, off, len, chunk, [](int, int64_t, int64_t) { return M6A_OK; });
+}
+
+// One window: file bytes [b, b + n); `len` bytes from b are in df, zeros behind them.  A resident file is the one window that starts
+// at 0 and is the last.
+struct Win {
+    const uint8_t *df = nullptr;
+    int64_t b = 0, len = 0, n = 0, first = 0;
+    bool last = false, grow = false;
+    bool index = false;                     // in: --skip_index -- no header line is asked for, and a short line is not reported here
+    int64_t NL = 0, nlines = 0, NR = 0, keep = 0, next = 0;
+    int64_t *bcnt = nullptr;                // in: the newlines of every scan block, [blocks + 1]; lines_of scans them
+    int64_t *nl = nullptr;
+    LineEv *ev = nullptr;
+    unsigned long long *bad = nullptr;      // [1] line_kernel's bad_at
+    Name *lname = nullptr;                  // [nlines] with read_names
+    RunDev *runs = nullptr;
+    bool read_names = false;                // in: --read_names
+    Name *rnames = nullptr;                 // [NR] then
+};
+
+// The line pass: from the newline counts of V's scan blocks to the newline offsets, n and the line count, the line records (and
+// names) and the file's first bad line -- or V.grow, where a window that is not the last holds no newline.  t0: when the newline
+// phase began (a window counts its newlines inside it).  ms[1] takes the newline part, ms[2] the lines.
+int lines_of(DevMem &m, hipStream_t s, const char *path, Win &V, double t0, double *ms)
+{
+    int rc;
+    const int64_t nb = padded(V.len) / kScanBytes;
+    if ((rc = scan_total(m, V.bcnt, nb, s, V.NL))) return rc;
+    if (!V.index && V.last && V.b == 0 && V.NL == 0) return prep_fail(M6A_EFORMAT, "%s: no header line", path);
+    V.grow = !V.last && V.NL == 0;                           // a line longer than the window
+    if (V.grow) return M6A_OK;
+    if ((rc = m.alloc(V.nl, (size_t)V.NL + 1, "newline offsets"))) return rc;
+    nl_write_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)V.df, nb, V.bcnt, V.nl);
+    PCHK(hipGetLastError());
+    if (V.last) {                                            // the only window that may end without a newline
+        uint8_t end = '\n';
+        if (V.len > 0) { if ((rc = fetch(end, V.df + V.len - 1, s))) return rc; }
+        else PCHK(hipStreamSynchronize(s));
+        V.n = V.len;
+        V.nlines = V.NL + (end != '\n' ? 1 : 0);
+    } else {                                                 // it ends behind its last newline; what follows is the next window's
+        int64_t at = 0;
+        if ((rc = fetch(at, V.nl + V.NL - 1, s))) return rc;
+        V.n = at + 1;
+        V.nlines = V.NL;
+    }
+    ms[1] += now_ms() - t0;
+
+    const double t1 = now_ms();
+    if ((rc = m.alloc(V.ev, (size_t)std::max<int64_t>(V.nlines, 1), "line records"))) return rc;
+    if ((rc = m.alloc(V.bad, 1, "flags"))) return rc;
+    const unsigned long long none = ~0ull;
+    PCHK(hipMemcpyAsync(V.bad, &none, sizeof none, hipMemcpyHostToDevice, s));
+    if (V.read_names && (rc = m.alloc(V.lname, (size_t)std::max<int64_t>(V.nlines, 1), "read names"))) return rc;
+    rc = V.lname ? launch(line_kernel<true>, V.nlines - V.first, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.bad, V.lname)
+                 : launch(line_kernel<false>, V.nlines - V.first, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.bad, nullptr);
+    if (rc) return rc;
+    unsigned long long bad_at = none;
+    if ((rc = fetch(bad_at, V.bad, s))) return rc;
+    // every line in front of this window has been seen, so this is the file's first bad line, as whole-file mode reports it
+    if (!V.index && bad_at != none) return bad_line(path, V.lname != nullptr, V.b, bad_at);
+    ms[2] += now_ms() - t1;
+    return M6A_OK;
+}
+
+// ---- the front half in windows ---------------------------------------------------------------------------------------------------
+// The text goes through HBM W bytes at a time and only runs and candidate rows stay (include/m6a.h states the cut; the stream's
+// windows are the file's, tests/window_statement.py).  Window k is bytes [b, e): e is the byte after the last '\n' among the W bytes
+// from b, or the text's end in the last window; lines, runs, combine and windows are the whole-file kernels on that text (line 0 is
+// the header in window 0 only).  The last run of a window that is not the last may go on behind e: it is left out, and the next window
+// starts at its first byte -- so every kept run was seen whole, and a window whose only run starts at b is done again at twice the
+// size.  The first run of a window has same_contig = 0: a contig cut by a window becomes two segments, which both consumers intern
+// under one name, and sites_impl's rank0 of the second is the number of runs the transcript had before it (tx_runs) --
+// run_select_kernel's rank0 + (r - first) is then the rank the run has in the one segment of whole-file mode, because the two segments
+// are consecutive runs.
+// One loop (front_windows) asks a Source for the bytes; there are two.  Two text buffers and one arena serve both: while the kernel
+// stream combines and windows window k, a thread brings window k + 1 through the pinned pair and the copy stream, and the kernels of
+// two windows never overlap.
+//   a file     (FileSource) the thread preads.  It starts when window k's cut is known and reads from b of k + 1, so the bytes between
+//              that and window k's end are read again (not copied from window k's buffer: the next text then starts 16-byte aligned
+//              at its buffer's start, which the newline scan needs).  A window that grows is read again from b at twice the size.
+//   a stream   (StreamSource) `--eventalign -`, a FIFO, /dev/fd/N: the text comes once and in order, and its length is known when it
+//              ends.  Window k is the `size` bytes from b, the last one exactly when no byte follows them -- the reader's one byte of
+//              lookahead (m6a_stream.h) answers that without consuming.  Nothing crosses the link twice:
+//     carry    the bytes of window k from b of window k + 1 on (the dropped run, what lies behind the last newline) are copied device
+//              to device to the start of the next buffer, which keeps the text 16-byte aligned at its base; the stream's next bytes
+//              are appended behind them, so only the append position is unaligned, and zeros follow the text to a whole scan block.
+//              A window that grew may leave more than W bytes: the next windows are cut from them first.
+//     growth   the buffer is grown by copy and `size` more bytes are appended.
+//     reading  a thread of the reader's own (m6a_stream::Ring) fills the two pinned chunks from the pipe all the time: it does not
+//              wait for a cut, because the stream's order is fixed.  From the cut of window k on, the second thread takes the next
+//              window's bytes out of the chunks and copies them behind the carried bytes.
+//     saving   the back half cannot pread a stream: Kept::append saves the contig bytes of segment heads and the bytes of declined
+//              runs from the window's text (save_flag_kernel, scan, save_gather_kernel), and sites_impl gathers from the two blobs.
+// What stays is appended in place: kept runs, their row counts and the three row arrays grow as device vectors.  A file projects their
+// capacity from the rows per byte so far, so the usual peak is the rows plus a margin; a stream's length is unknown, so they grow
+// geometrically (twice what is needed, then DevVec::fit's fallbacks).  (Result blocks per window, flattened at the end with each block
+// released as it is copied, would hold the rows twice at the moment the flat arrays are allocated.)  A vector that outgrows its
+// capacity is copied into a new one and both exist during the copy: a wrong projection costs up to twice that array for that moment,
+// and where the budget cannot take the projection the vector grows by half, not window by window.
+
+// a device array that grows at its end; everything in it is counted in `m`
+struct DevVec {
+    uint8_t *p = nullptr;
+    size_t cap = 0, used = 0;                               // bytes
+    // room for `need` bytes: `hope` (the projection) if the budget allows it, else half as much again as there is, else just `need`.
+    // What is there stays (s is idle); while it is copied the old and the new array both count against the budget.
+    int fit(DevMem &m, size_t need, size_t hope, hipStream_t s, const char *what)
+    {
+        if (p && need <= cap) return M6A_OK;
+        Arena *const a = m.arena;
+        m.arena = nullptr;
+        uint8_t *q = nullptr;
+        int rc = M6A_OK;
+        const size_t tries[3] = {hope, cap + cap / 2, need};
+        for (size_t t : tries) {
+            if (t < need || (t > need && m.used + t > m.budget)) continue;
+            hope = t;
+            rc = m.alloc(q, t, what);
+            break;
+        }
+        m.arena = a;
+        if (rc) return rc;
+        if (used) {
+            PCHK(hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, s));
+            PCHK(hipStreamSynchronize(s));
+        }
+        if (p) m.release(p);
+        p = q;
+        cap = std::max<size_t>(16, hope);
+        return M6A_OK;
+    }
+};
+
+// newline count, lines and runs of a window, and its cut: n, keep (the runs that stay) and next (b of the window after) -- or grow
+int window_cut(DevMem &m, hipStream_t s, const char *path, Win &V, double *ms)
+{
+    double t1 = now_ms();
+    int rc;
+    const int64_t nb = padded(V.len) / kScanBytes;
+    if ((rc = m.alloc(V.bcnt, (size_t)nb + 1, "newline counts"))) return rc;
+    nl_count_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)V.df, 0, V.bcnt);
+    PCHK(hipGetLastError());
+    if ((rc = lines_of(m, s, path, V, t1, ms)) || V.grow) return rc;
+
+    t1 = now_ms();
+    if ((rc = find_runs(m, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.runs, V.NR, nullptr, V.lname, &V.rnames))) return rc;
+    V.keep = V.NR;
+    V.next = V.b + V.n;
+    if (!V.last && V.NR > 0) {                               // the last run may go on in the next window: that one starts with it
+        int64_t start = 0;
+        if ((rc = fetch(start, &V.runs[V.NR - 1].start, s))) return rc;
+        V.keep = V.NR - 1;
+        V.next = V.b + start;
+        V.grow = V.next == V.b;                              // its only run, from its first byte: no cut in here
+    }
+    ms[2] += now_ms() - t1;
+    return M6A_OK;
+}
+
+// a stream's window: where its kept runs' saved bytes go in the window's part of the two blobs (save_flag_kernel, scanned)
+struct Save {
+    int64_t *head = nullptr, *decl = nullptr;             // [keep + 1] each
+    int64_t n_head = 0, n_decl = 0;
+};
+
+int save_plan(DevMem &m, hipStream_t s, const Win &V, Save &sv)
+{
+    int rc;
+    if ((rc = m.alloc(sv.head, (size_t)V.keep + 1, "saved names")) || (rc = m.alloc(sv.decl, (size_t)V.keep + 1, "saved runs"))) return rc;
+    if ((rc = launch(save_flag_kernel, V.keep, s, V.runs, V.keep, sv.head, sv.decl))) return rc;
+    if ((rc = scan_total(m, sv.head, V.keep, s, sv.n_head))) return rc;
+    return scan_total(m, sv.decl, V.keep, s, sv.n_decl);
+}
+
+// what stays of the windows: the job's runs, their row counts and the three row arrays, each grown at its end
+struct Kept {
+    DevVec runs, cnt, pos, kmer, feat, names;             // names: 16 B per kept run, --read_names only
+    DevVec heads, declined;                               // a stream only: Front::heads, Front::declined
+    int64_t NR = 0, NROW = 0;
+    // window V's kept runs and their `nrow` rows behind what is there; `ahead` = what the whole file is expected to hold over what is held now
+    // sv (a stream): the window's saved bytes go behind the two blobs, which grow as the arrays do
+    int append(DevMem &m, hipStream_t s, const Win &V, int w, double ahead, const int64_t *pos_off, const PosRec *ps, const int64_t *row_off,
+               int64_t nrow, const Save *sv = nullptr)
+    {
+        const int64_t K = 5 + 2 * w, NF = 3 * (2 * w + 1);
+        const size_t nr = (size_t)(NR + V.keep) + 1, nw = (size_t)(NROW + nrow) + 1;
+        int rc;
+        if ((rc = runs.fit(m, nr * sizeof(RunDev), (size_t)((double)nr * ahead) * sizeof(RunDev), s, "runs")) ||
+            (rc = cnt.fit(m, nr * 8, (size_t)((double)nr * ahead) * 8, s, "rows")) ||
+            (rc = pos.fit(m, nw * 8, (size_t)((double)nw * ahead) * 8, s, "rows")) ||
+            (rc = kmer.fit(m, nw * (size_t)K, (size_t)((double)nw * ahead) * (size_t)K, s, "rows")) ||
+            (rc = feat.fit(m, nw * (size_t)NF * 8, (size_t)((double)nw * ahead) * (size_t)NF * 8, s, "rows")))
+            return rc;
+        if (V.rnames && (rc = names.fit(m, nr * sizeof(Name), (size_t)((double)nr * ahead) * sizeof(Name), s, "read names"))) return rc;
+        if (V.rnames && V.keep)               // the dropped last run takes its name with it
+            PCHK(hipMemcpyAsync((Name *)names.p + NR, V.rnames, (size_t)V.keep * sizeof(Name), hipMemcpyDeviceToDevice, s));
+        if (nrow && (rc = launch(window_kernel, V.keep, s, V.df, V.runs, V.keep, pos_off, ps, w, nullptr, row_off, (int64_t *)pos.p + NROW,
+                                 kmer.p + NROW * K, (double *)feat.p + NROW * NF)))
+            return rc;
+        if ((rc = launch(keep_runs_kernel, V.keep, s, V.runs, V.keep, V.b, row_off, (RunDev *)runs.p + NR, (int64_t *)cnt.p + NR))) return rc;
+        if (sv) {
+            const size_t nh = heads.used + (size_t)sv->n_head, nd = declined.used + (size_t)sv->n_decl;
+            if ((rc = heads.fit(m, nh, (size_t)((double)nh * ahead), s, "saved names")) ||
+                (rc = declined.fit(m, nd, (size_t)((double)nd * ahead), s, "saved runs")))
+                return rc;
+            if (sv->n_head) {
+                save_gather_kernel<<<(unsigned)V.keep, kBlk, 0, s>>>(V.df, V.runs, sv->head, 0, heads.p + heads.used);
+                PCHK(hipGetLastError());
+            }
+            if (sv->n_decl) {
+                save_gather_kernel<<<(unsigned)V.keep, kBlk, 0, s>>>(V.df, V.runs, sv->decl, 1, declined.p + declined.used);
+                PCHK(hipGetLastError());
+            }
+            heads.used = nh; declined.used = nd;
+        }
+        PCHK(hipStreamSynchronize(s));
+        NR += V.keep; NROW += nrow;
+        runs.used = (size_t)NR * sizeof(RunDev); cnt.used = (size_t)NR * 8;
+        if (V.rnames) names.used = (size_t)NR * sizeof(Name);
+        pos.used = (size_t)NROW * 8; kmer.used = (size_t)(NROW * K); feat.used = (size_t)(NROW * NF) * 8;
+        return M6A_OK;
+    }
+};
+
+// the thread that brings window k + 1 while window k is combined; joined where it goes out of scope
+struct Upload {
+    int rc = M6A_OK;
+    std::string err;
+    double ms = 0;
+    int64_t got = 0;                        // the bytes it brought, and (a stream) whether no byte follows them
+    bool eof = false;
+    m6a_stream::Ring *ring = nullptr;       // a stream: left running on an error, nothing more is wanted of it
+    std::thread t;
+    template <class Work> void start(Work work)
+    {
+        t = std::thread([this, work]() {
+            const double t0 = now_ms();
+            rc = work();
+            if (rc) err = g_prep_err;                       // the text is this thread's; the caller takes it over
+            ms = now_ms() - t0;
+        });
+    }
+    void wait() { if (t.joinable()) t.join(); }
+    ~Upload() { if (t.joinable()) { if (ring) ring->abandon(); t.join(); } }
+};
+
+struct Text { uint8_t *p = nullptr; int64_t cap = 0; };
+
+// what the window loop and its source share: the two text buffers, the arena, and what the link did
+struct Windows {
+    int device_id;
+    const char *path;
+    int64_t W, chunk;
+    DevMem &m;
+    Streams &S;
+    const char *text_what = "";             // the source's name for a text buffer in the budget error
+    Text text[2];
+    Arena arena;
+    double wait_ms = 0, copy_ms = 0, copied = 0;
+    Windows(int device, const char *p, int64_t w, int64_t c, DevMem &mem, Streams &st) : device_id(device), path(p), W(w), chunk(c), m(mem), S(st) {}
+    int text_fit(Text &T, int64_t len)      // what was in it is gone
+    {
+        const int64_t cap = padded(len);
+        if (cap <= T.cap) return M6A_OK;
+        if (T.p) m.release(T.p);
+        T.p = nullptr; T.cap = 0;
+        const int e = m.alloc(T.p, (size_t)cap, text_what);
+        if (!e) T.cap = cap;
+        return e;
+    }
+    int arena_grow()
+    {
+        PCHK(hipStreamSynchronize(S.s[0]));
+        if (arena.base) m.release(arena.base);
+        arena.base = nullptr;
+        const size_t cap = std::max(arena.cap * 2, (arena.need + 4095) & ~(size_t)4095);
+        arena.cap = arena.off = 0;
+        const int e = m.alloc(arena.base, cap, "the scratch of a window");
+        if (!e) arena.cap = cap;
+        return e;
+    }
+    // the first arena, for a text of `bytes`: newline offsets and line records are about 1.5 bytes per byte of text
+    int arena_start(int64_t bytes) { arena.need = (size_t)std::min(W, std::max(bytes, kScanBytes)) * 2; return arena_grow(); }
+    // `bytes` arrived while the loop waited, from t0 on
+    void arrived(double t0, int64_t bytes) { const double dt = now_ms() - t0; wait_ms += dt; copy_ms += dt; copied += (double)bytes; }
+};
+
+// where the windows' bytes come from: a file or a stream
+struct Source {
+    Windows &C;
+    explicit Source(Windows &c) : C(c) {}
+    virtual ~Source() {}
+    virtual int first(Text &T) = 0;                                         // window 0 arrives, and the first arena is made
+    virtual void extent(Win &V, int64_t Wk) const = 0;                      // V.len and V.last of the window of Wk bytes at V.b
+    virtual int start_next(const Win &V, Text &T, Text &T2, Upload &up) = 0;    // V's cut is known: window k + 1 sets out for T2
+    virtual int grow(const Win &V, Text &T, int64_t Wk) = 0;               // V holds no cut: Wk bytes from V.b, waited for
+    virtual void advance(const Upload &) {}                                 // window k + 1 has arrived and becomes the window at hand
+    virtual double ahead(const Win &V) const = 0;                           // Kept::append's projection
+    virtual bool saves() const = 0;                                         // heads and declined runs are saved from the text
+    virtual int finish(int64_t b, Front &F) = 0;                            // after the last window, which began at b
+};
+
+struct FileSource : Source {
+    const int fd;
+    const int64_t n;
+    FileSource(Windows &c, int fd_, int64_t n_) : Source(c), fd(fd_), n(n_) { C.text_what = "a window of the file"; }
+    int bring(Text &T, int64_t off, int64_t len)
+    {
+        int rc;
+        if ((rc = C.text_fit(T, len))) return rc;
+        const double t0 = now_ms();
+        if ((rc = upload_range(C.device_id, fd, C.path, C.S, T.p, off, len, C.chunk))) return rc;
+        C.arrived(t0, len);
+        return M6A_OK;
+    }
+    int first(Text &T) override { const int rc = C.arena_start(n); return rc ? rc : bring(T, 0, std::min(C.W, n)); }
+    void extent(Win &V, int64_t Wk) const override { V.last = V.b + Wk >= n; V.len = std::min(Wk, n - V.b); }
+    int start_next(const Win &V, Text &, Text &T2, Upload &up) override
+    {
+        const int64_t off = V.next, len = std::min(C.W, n - V.next);
+        const int rc = C.text_fit(T2, len);
+        if (rc) return rc;
+        Windows &c = C;
+        uint8_t *const dst = T2.p;
+        const int f = fd;
+        up.got = len;
+        up.start([&c, f, dst, off, len]() { return upload_range(c.device_id, f, c.path, c.S, dst, off, len, c.chunk); });
+        return M6A_OK;
+    }
+    int grow(const Win &V, Text &T, int64_t Wk) override                   // read again from b
+    {
+        PCHK(hipStreamSynchronize(C.S.s[0]));
+        return bring(T, V.b, std::min(Wk, n - V.b));
+    }
+    // rows per byte so far, carried over the whole file, and 5 % more
+    double ahead(const Win &V) const override { return (double)n / (double)std::max<int64_t>(V.next, 1) * 1.05; }
+    bool saves() const override { return false; }
+    int finish(int64_t, Front &) override { return M6A_OK; }
+};
+
+// up to `want` bytes of the stream -> base + have on the copy stream, zeros behind the text to a whole scan block; returns when they
+// have arrived.  got: how many came (fewer than `want` only at the stream's end); eof: whether no byte follows them.  The bytes come
+// out of the pinned pair, which the ring's thread fills from the pipe whether or not anybody is here to take them.
+int stream_fetch(int device_id, m6a_stream::Ring &ring, Streams &S, uint8_t *base, int64_t have, int64_t want, int64_t &got, bool &eof)
+{
+    PCHK(hipSetDevice(device_id));
+    hipError_t bad = hipSuccess;
+    auto copy = [&](const uint8_t *p, int64_t k, int slot, int64_t off) {
+        bad = hipMemcpyAsync(base + have + off, p, (size_t)k, hipMemcpyHostToDevice, S.s[1]);
+        if (bad == hipSuccess) bad = hipEventRecord(S.copied[slot], S.s[1]);
+        return bad == hipSuccess;
+    };
+    auto settle = [&](int slot) { return (bad = hipEventSynchronize(S.copied[slot])) == hipSuccess; };
+    got = 0;
+    const int64_t r = ring.take(want, copy, settle);
+    if (r == -2) return prep_fail(M6A_EHIP, "the copy of a window of the stream: %s", hipGetErrorString(bad));
+    if (r < 0) return prep_fail(M6A_EIO, "%s", ring.R.failed ? ring.R.error.c_str() : "the stream was abandoned");
+    got = r;
+    const int64_t len = have + got;
+    if (padded(len) > len) PCHK(hipMemsetAsync(base + len, 0, (size_t)(padded(len) - len), S.s[1]));
+    PCHK(hipStreamSynchronize(S.s[1]));
+    const int e = ring.at_eof();
+    if (e < 0) return prep_fail(M6A_EIO, "%s", ring.R.failed ? ring.R.error.c_str() : "the stream was abandoned");
+    eof = e == 1;
+    return M6A_OK;
+}
+
+struct StreamSource : Source {
+    const char *const advice_was;
+    m6a_stream::Reader R;                                   // the caller's Fd closes the descriptor (or leaves 0 alone)
+    m6a_stream::Ring ring;
+    int64_t have = 0, carry = 0;                            // `have` bytes from b are in the text; `carry` of them are the next window's
+    bool eof = false;                                       // no byte follows the `have` bytes from b
+    StreamSource(Windows &c, int fd)
+        : Source(c), advice_was(c.m.advice), R(fd, false, c.path), ring(R, (uint8_t *)c.S.pin[0], (uint8_t *)c.S.pin[1], c.chunk)
+    {
+        C.text_what = "a window of the stream";
+        C.m.advice = "a stream is parsed in windows and what is kept of them stays on the device: give a smaller --window_mb, or write the "
+                     "text to a file and run `dataprep` and then `inference` (the two-step path)";
+    }
+    ~StreamSource() override { C.m.advice = advice_was; }
+    // the first two bytes say whether this is gzip; then window 0 arrives before anything can run
+    int first(Text &T) override
+    {
+        int rc;
+        uint8_t magic[2] = {0, 0};
+        const double t0 = now_ms();
+        const int64_t g = R.fill(magic, 2);
+        if (g < 0) return prep_fail(M6A_EIO, "%s", R.error.c_str());
+        if (g == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
+            return prep_fail(M6A_EINVAL, "%s is a gzip-compressed stream: compressed input from a stream is not implemented; inflate it on "
+                             "the way, `bgzip -dc FILE | ... --eventalign -`, or give the BGZF file by its path", C.path);
+        if ((rc = C.text_fit(T, C.W))) return rc;
+        if (g) PCHK(hipMemcpyAsync(T.p, magic, (size_t)g, hipMemcpyHostToDevice, C.S.s[1]));
+        PCHK(hipStreamSynchronize(C.S.s[1]));
+        ring.start();                                        // from here on the reader is the thread's
+        int64_t got = 0;
+        if ((rc = stream_fetch(C.device_id, ring, C.S, T.p, g, C.W - g, got, eof))) return rc;
+        have = g + got;
+        C.arrived(t0, have);
+        return C.arena_start(have);
+    }
+    void extent(Win &V, int64_t Wk) const override
+    {
+        V.len = std::min(Wk, have);                          // have > Wk: what a grown window left; Wk is whole scan blocks then
+        V.last = have < Wk || (have == Wk && eof);           // the file rule b + size >= n: no byte follows these bytes
+    }
+    int start_next(const Win &V, Text &T, Text &T2, Upload &up) override    // the carry moves over and the next bytes set out
+    {
+        carry = have - (V.next - V.b);
+        const int rc = C.text_fit(T2, std::max(C.W, carry));
+        if (rc) return rc;
+        if (carry) PCHK(hipMemcpyAsync(T2.p, T.p + (V.next - V.b), (size_t)carry, hipMemcpyDeviceToDevice, C.S.s[1]));
+        Windows &c = C;
+        m6a_stream::Ring &r = ring;
+        uint8_t *const dst = T2.p;
+        const int64_t at = carry, want = std::max<int64_t>(0, C.W - carry);
+        up.ring = &ring;
+        up.start([&c, &r, &up, dst, at, want]() { return stream_fetch(c.device_id, r, c.S, dst, at, want, up.got, up.eof); });
+        return M6A_OK;
+    }
+    int grow(const Win &, Text &T, int64_t Wk) override                    // what is there stays, the rest is appended
+    {
+        PCHK(hipStreamSynchronize(C.S.s[0]));
+        if (have >= Wk) return M6A_OK;                       // (a grown window is not the last: a byte follows what is there)
+        const int64_t cap = padded(Wk);
+        if (cap > T.cap) {                                   // the old and the new buffer both count while the text is copied
+            uint8_t *q = nullptr;
+            const int e = C.m.alloc(q, (size_t)cap, C.text_what);
+            if (e) return e;
+            if (have) PCHK(hipMemcpyAsync(q, T.p, (size_t)have, hipMemcpyDeviceToDevice, C.S.s[0]));
+            PCHK(hipStreamSynchronize(C.S.s[0]));
+            if (T.p) C.m.release(T.p);
+            T.p = q; T.cap = cap;
+        }
+        const double t0 = now_ms();
+        int64_t got = 0;
+        const int rc = stream_fetch(C.device_id, ring, C.S, T.p, have, Wk - have, got, eof);
+        if (rc) return rc;
+        have += got;
+        C.arrived(t0, got);
+        return M6A_OK;
+    }
+    void advance(const Upload &up) override { have = carry + up.got; eof = up.eof; }
+    double ahead(const Win &) const override { return 2.0; }               // the length is unknown: twice what is needed
+    bool saves() const override { return true; }
+    int finish(int64_t b, Front &F) override
+    {
+        if (R.consumed != b + have) return prep_fail(M6A_EHIP, "the windows of %s do not add up", C.path);
+        F.n = R.consumed;
+        F.stream = true;
+        return M6A_OK;
+    }
+};
+
+int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
+{
+    DevMem &m = C.m;
+    hipStream_t s = C.S.s[0];
+    int rc;
+    // window 0 arrives before anything can run; from then on window k + 1 arrives under window k's combine and windows
+    if ((rc = src.first(C.text[0]))) return rc;
+    Kept kept;
+    int64_t b = 0, n_windows = 0, w_max = 0;
+    for (int64_t k = 0;; k++) {
+        Text &T = C.text[k & 1], &T2 = C.text[(k + 1) & 1];
+        Upload up;                                           // of window k + 1
+        bool started = false;
+        int64_t Wk = C.W;
+        Win V;
+        for (;;) {                                           // until the arena holds the window and the window holds a cut
+            V = Win();
+            V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
+            V.read_names = F.read_names;
+            src.extent(V, Wk);
+            C.arena.off = 0;
+            m.arena = &C.arena;
+            rc = window_cut(m, s, C.path, V, ms);
+            int64_t *pos_off = nullptr, *row_off = nullptr, nrow = 0;
+            PosRec *ps = nullptr;
+            Save sv;
+            if (!rc && !V.grow) {
+                if (!V.last && !started) {                   // the cut is known: the next window sets out
+                    m.arena = nullptr;
+                    if ((rc = src.start_next(V, T, T2, up))) return rc;
+                    m.arena = &C.arena;
+                    started = true;
+                }
+                const double t1 = now_ms();
+                rc = count_rows(m, s, V.df, V.ev, V.runs, V.keep, w, pos_off, ps, row_off, nrow);
+                if (!rc && src.saves()) rc = save_plan(m, s, V, sv);
+                ms[2] += now_ms() - t1;
+            }
+            m.arena = nullptr;
+            if (rc == kArenaFull) {
+                if ((rc = C.arena_grow())) return rc;
+                continue;
+            }
+            if (rc) return rc;
+            if (V.grow) {                                    // twice the window
+                Wk *= 2;
+                if ((rc = src.grow(V, T, Wk))) return rc;
+                continue;
+            }
+            const double t1 = now_ms();
+            if ((rc = kept.append(m, s, V, w, src.ahead(V), pos_off, ps, row_off, nrow, src.saves() ? &sv : nullptr))) return rc;
+            ms[2] += now_ms() - t1;
+            break;
+        }
+        ++n_windows;
+        w_max = std::max(w_max, Wk);
+        if (started) {
+            const double t0 = now_ms();
+            up.wait();
+            C.wait_ms += now_ms() - t0; C.copy_ms += up.ms; C.copied += (double)up.got;
+            if (up.rc) { g_prep_err = up.err; return up.rc; }
+        }
+        if (V.last) break;
+        b = V.next;
+        src.advance(up);
+    }
+    if ((rc = src.finish(b, F))) return rc;
+    // the scratch goes before the back half: X needs the room
+    for (Text &T : C.text)
+        if (T.p) m.release(T.p);
+    m.release(C.arena.base);
+    // row_off: one exclusive scan of the row counts of all runs
+    const double t1 = now_ms();
+    int64_t total = 0;
+    if ((rc = scan_total(m, (int64_t *)kept.cnt.p, kept.NR, s, total))) return rc;
+    if (total != kept.NROW) return prep_fail(M6A_EHIP, "the windows' rows do not add up");
+    ms[2] += now_ms() - t1;
+    ms[0] = C.wait_ms;
+    ms[5] = C.copy_ms > 0 ? C.copied / (C.copy_ms * 1e6) : 0;
+    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
+    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p; F.rnames = (Name *)kept.names.p;
+    F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
+    F.heads = kept.heads.p; F.n_heads = (int64_t)kept.heads.used;
+    F.declined = kept.declined.p; F.n_declined = (int64_t)kept.declined.used;
+    return M6A_OK;
+}
+
+// The front half of one file.  istart / iend: the runs of an eventalign.index (--skip_index), or null.  ms[0..2], ms[5] as
+// m6a_prep_times reports them.  A stream, or window > 0 (rounded up to whole 4 KB blocks) and no index: the text goes through in
+// windows (front_windows); else it is resident, the one window that starts at 0 and is the last.
 int front_half(int device_id, const char *path, int w, const std::vector<int64_t> *istart, const std::vector<int64_t> *iend, int64_t window,
                DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
 {
@@ -842,7 +1451,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         const char *b = getenv("M6A_PREP_BUDGET_MB");
         if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
     }
-    int64_t nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);       // 4 KB scan blocks; the buffer is padded to them
+    int64_t nb = padded(n) / kScanBytes;                                        // 4 KB scan blocks; the buffer is padded to them
     if (stream && window <= 0) window = M6A_PREP_STREAM_WINDOW_BYTES;           // a stream is always parsed in windows
     const int64_t W = index_path || window <= 0 ? 0 : (window + kScanBytes - 1) / kScanBytes * kScanBytes;
     uint8_t *df = nullptr;
@@ -864,39 +1473,35 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
     chunk = std::min<int64_t>(chunk, W ? W : nb * kScanBytes);
     for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&S.pin[i], (size_t)chunk, hipHostMallocDefault));
-    if (stream) return front_stream(device_id, path, w, W, chunk, m, S, fd, F, ms);
-    if (W) return front_windows(device_id, path, w, W, chunk, m, S, fd, F, ms);
+    if (W) {
+        Windows C(device_id, path, W, chunk, m, S);
+        if (stream) { StreamSource src(C, fd.fd); return front_windows(C, src, w, F, ms); }
+        FileSource src(C, fd.fd, n);
+        return front_windows(C, src, w, F, ms);
+    }
     if (gz) {                                                // the compressed bytes go up, the text is inflated where the upload would have put it
         if ((rc = bgzf_front(path, fd.fd, n, m, S, chunk, df, n, F, ms))) return rc;
         F.n = n;
-        nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);
+        nb = padded(n) / kScanBytes;
         const double t_nl = now_ms();
         if ((rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts"))) return rc;
         nl_count_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)df, 0, bcnt);
         PCHK(hipGetLastError());
         PCHK(hipStreamSynchronize(s));
         F.ms_inflate += now_ms() - t_nl;
-    } else
-        PCHK(hipMemsetAsync(df + (nb - 1) * kScanBytes, 0, (size_t)kScanBytes, S.s[1]));        // the zero padding of the last block
+    }
 
     // ---- upload: pread chunk k into one pinned buffer while chunk k - 1 is copied and counted
     const double t_up = now_ms();
-    for (int64_t k = 0, off = 0; !gz && off < n; k++, off += chunk) {
-        const int slot = (int)(k & 1);
-        PCHK(hipEventSynchronize(S.copied[slot]));          // the copy that last used this buffer is done
-        const int64_t len = std::min(chunk, n - off);
-        for (int64_t got = 0; got < len;) {
-            const ssize_t r = ::pread(fd.fd, (char *)S.pin[slot] + got, (size_t)(len - got), (off_t)(off + got));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
-            got += r;
-        }
-        PCHK(hipMemcpyAsync(df + off, S.pin[slot], (size_t)len, hipMemcpyHostToDevice, S.s[1]));
-        PCHK(hipEventRecord(S.copied[slot], S.s[1]));
-        PCHK(hipStreamWaitEvent(s, S.copied[slot], 0));
-        const int64_t b0 = off / kScanBytes, b1 = std::min(nb, (off + len + kScanBytes - 1) / kScanBytes);
-        nl_count_kernel<<<(unsigned)(b1 - b0), kBlk, 0, s>>>((const uint4 *)df, b0, bcnt);
-        PCHK(hipGetLastError());
+    if (!gz) {
+        rc = upload_range(device_id, fd.fd, path, S, df, 0, n, chunk, [&](int slot, int64_t off, int64_t len) -> int {
+            PCHK(hipStreamWaitEvent(s, S.copied[slot], 0));
+            const int64_t b0 = off / kScanBytes, b1 = std::min(nb, (off + len + kScanBytes - 1) / kScanBytes);
+            nl_count_kernel<<<(unsigned)(b1 - b0), kBlk, 0, s>>>((const uint4 *)df, b0, bcnt);
+            PCHK(hipGetLastError());
+            return M6A_OK;
+        });
+        if (rc) return rc;
     }
     if (n == 0) PCHK(hipMemsetAsync(bcnt, 0, sizeof(int64_t), s));
     PCHK(hipStreamSynchronize(S.s[1]));
@@ -906,61 +1511,30 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         ms[5] = ms[0] > 0 ? (double)n / (ms[0] * 1e6) : 0;
     }
 
-    // ---- newline offsets
-    double t1 = now_ms();
-    int64_t NL = 0;
-    if ((rc = scan_total(m, bcnt, nb, s, NL))) return rc;
-    if (!index_path && NL == 0) return prep_fail(M6A_EFORMAT, "%s: no header line", path);
-    int64_t *nl;
-    if ((rc = m.alloc(nl, (size_t)NL + 1, "newline offsets"))) return rc;
-    nl_write_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)df, nb, bcnt, nl);
-    PCHK(hipGetLastError());
-    uint8_t last = '\n';
-    if (n > 0) { PCHK(hipMemcpyAsync(&last, df + n - 1, 1, hipMemcpyDeviceToHost, s)); g_d2h += 1; }
-    PCHK(hipStreamSynchronize(s));
-    const int64_t nlines = NL + (last != '\n' ? 1 : 0);
-    ms[1] = now_ms() - t1;
+    // ---- newline offsets and lines
+    Win V;
+    V.df = df; V.len = n; V.last = true; V.first = 1; V.index = index_path; V.bcnt = bcnt;
+    V.read_names = F.read_names;
+    if ((rc = lines_of(m, s, path, V, now_ms(), ms))) return rc;
 
-    // ---- lines, runs, combine, windows
-    t1 = now_ms();
-    LineEv *ev;
-    unsigned long long *bad;
-    if ((rc = m.alloc(ev, (size_t)std::max<int64_t>(nlines, 1), "line records"))) return rc;
-    if ((rc = m.alloc(bad, 1, "flags"))) return rc;
-    const unsigned long long none = ~0ull;
-    PCHK(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, s));
-    Name *lname = nullptr;
-    if (F.read_names && (rc = m.alloc(lname, (size_t)std::max<int64_t>(nlines, 1), "read names"))) return rc;
-    if (nlines > 1) {
-        if (lname) line_kernel<true><<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, 1, ev, bad, lname);
-        else line_kernel<false><<<grid(nlines - 1), kBlk, 0, s>>>(df, n, nl, NL, nlines, 1, ev, bad, nullptr);
-        PCHK(hipGetLastError());
-    }
-    unsigned long long bad_at = none;
-    PCHK(hipMemcpyAsync(&bad_at, bad, sizeof bad_at, hipMemcpyDeviceToHost, s));
-    g_d2h += (int64_t)sizeof bad_at;
-    PCHK(hipStreamSynchronize(s));
-    if (!index_path && bad_at != none) return bad_line(path, lname != nullptr, 0, bad_at);
-
+    // ---- runs, combine, windows
+    const double t1 = now_ms();
     int64_t NR = 0;
     RunDev *runs = nullptr;
     if (!index_path) {
-        if ((rc = find_runs(m, s, df, n, nl, NL, nlines, 1, ev, runs, NR, &F.scratch, lname, &F.rnames))) return rc;
+        if ((rc = find_runs(m, s, df, n, V.nl, V.NL, V.nlines, 1, V.ev, runs, NR, &F.scratch, V.lname, &F.rnames))) return rc;
     } else {
         NR = (int64_t)istart->size();
         if ((rc = m.alloc(runs, (size_t)NR + 1, "runs"))) return rc;
         std::vector<RunDev> h((size_t)NR);
         for (int64_t r = 0; r < NR; r++) { h[(size_t)r].start = (*istart)[(size_t)r]; h[(size_t)r].end = (*iend)[(size_t)r]; }
         if (NR) PCHK(hipMemcpyAsync(runs, h.data(), (size_t)NR * sizeof(RunDev), hipMemcpyHostToDevice, s));
-        if (NR) {
-            runs_from_index_kernel<<<grid(NR), kBlk, 0, s>>>(n, nl, NL, nlines, runs, NR);
-            PCHK(hipGetLastError());
-        }
+        if ((rc = launch(runs_from_index_kernel, NR, s, n, V.nl, V.NL, V.nlines, runs, NR))) return rc;
         PCHK(hipStreamSynchronize(s));                        // h goes out of scope
     }
     int64_t *pos_off, *row_off, NROW = 0;
     PosRec *ps;
-    if ((rc = count_rows(m, s, df, ev, runs, NR, w, pos_off, ps, row_off, NROW))) return rc;
+    if ((rc = count_rows(m, s, df, V.ev, runs, NR, w, pos_off, ps, row_off, NROW))) return rc;
     const int64_t K = 5 + 2 * w, NF = 3 * (2 * w + 1);
     int64_t *drow_pos;
     uint8_t *drow_kmer;
@@ -968,608 +1542,14 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
     if ((rc = m.alloc(drow_pos, (size_t)NROW, "rows"))) return rc;
     if ((rc = m.alloc(drow_kmer, (size_t)(NROW * K), "rows"))) return rc;
     if ((rc = m.alloc(drow_feat, (size_t)(NROW * NF), "rows"))) return rc;
-    if (NR && NROW) {
-        window_kernel<<<grid(NR), kBlk, 0, s>>>(df, runs, NR, pos_off, ps, w, nullptr, row_off, drow_pos, drow_kmer, drow_feat);
-        PCHK(hipGetLastError());
-    }
+    if (NROW && (rc = launch(window_kernel, NR, s, df, runs, NR, pos_off, ps, w, nullptr, row_off, drow_pos, drow_kmer, drow_feat))) return rc;
     PCHK(hipStreamSynchronize(s));
-    ms[2] = now_ms() - t1;
+    ms[2] += now_ms() - t1;
     F.NR = NR; F.NROW = NROW; F.runs = runs; F.row_off = row_off; F.row_pos = drow_pos; F.row_kmer = drow_kmer; F.row_feat = drow_feat;
-    F.scratch.insert(F.scratch.end(), {bcnt, nl, ev, bad, pos_off, ps});
-    if (lname) F.scratch.push_back(lname);
+    F.scratch.insert(F.scratch.end(), {bcnt, V.nl, V.ev, V.bad, pos_off, ps});
+    if (V.lname) F.scratch.push_back(V.lname);
     if (gz) F.text = df;
     else F.scratch.push_back(df);
-    return M6A_OK;
-}
-
-// ---- the front half in windows ---------------------------------------------------------------------------------------------------
-// The file goes through HBM W bytes at a time and only runs and candidate rows stay (include/m6a.h states the cut).  Window k is file
-// bytes [b, e): e is the byte after the last '\n' among the W bytes from b, or the file's end in the last window; lines, runs,
-// combine and windows are the whole-file kernels on that text (line 0 is the header in window 0 only).  The last run of a window that
-// is not the last may go on behind e: it is left out, and the next window starts at its first byte -- so every kept run was seen
-// whole, and a window whose only run starts at b is done again at twice the size.  The first run of a window has same_contig = 0:
-// a contig cut by a window becomes two segments, which both consumers intern under one name, and sites_impl's rank0 of the second
-// is the number of runs the transcript had before it (tx_runs) -- run_select_kernel's rank0 + (r - first) is then the rank the run
-// has in the one segment of whole-file mode, because the two segments are consecutive runs.
-// Two text buffers: while the kernel stream combines and windows window k, a thread preads window k + 1 through the pinned pair and
-// copies it on the copy stream.  It starts when window k's cut is known and reads from b of k + 1, so the bytes between that and
-// window k's end are read again (not copied from window k's buffer: the next text then starts 16-byte aligned at its buffer's
-// start, which the newline scan needs).  One arena serves both: the kernels of two windows never overlap.
-// What stays is appended in place: kept runs, their row counts and the three row arrays grow as device vectors whose capacity is
-// projected from the rows per byte so far, so the usual peak is the rows plus a margin.  (Result blocks per window, flattened at the
-// end with each block released as it is copied, would hold the rows twice at the moment the flat arrays are allocated.)  A vector
-// that outgrows its capacity is copied into a new one and both exist during the copy: a wrong projection costs up to twice that
-// array for that moment, and where the budget cannot take the projection the vector grows by half, not window by window.
-struct Upload {
-    int rc = M6A_OK;
-    std::string err;
-    double ms = 0;
-    std::thread t;
-    void wait() { if (t.joinable()) t.join(); }
-    ~Upload() { wait(); }
-};
-
-// file bytes [off, off + len) -> dst on the copy stream, zeros behind them to a whole scan block; returns when they have arrived
-int upload_range(int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk)
-{
-    PCHK(hipSetDevice(device_id));
-    for (int64_t k = 0, done = 0; done < len; k++, done += chunk) {
-        const int slot = (int)(k & 1);
-        PCHK(hipEventSynchronize(S.copied[slot]));
-        const int64_t part = std::min(chunk, len - done);
-        for (int64_t got = 0; got < part;) {
-            const ssize_t r = ::pread(fd, (char *)S.pin[slot] + got, (size_t)(part - got), (off_t)(off + done + got));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
-            got += r;
-        }
-        PCHK(hipMemcpyAsync(dst + done, S.pin[slot], (size_t)part, hipMemcpyHostToDevice, S.s[1]));
-        PCHK(hipEventRecord(S.copied[slot], S.s[1]));
-    }
-    const int64_t padded = std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes;
-    if (padded > len) PCHK(hipMemsetAsync(dst + len, 0, (size_t)(padded - len), S.s[1]));
-    PCHK(hipStreamSynchronize(S.s[1]));
-    return M6A_OK;
-}
-
-void upload_start(Upload &u, int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk)
-{
-    u.t = std::thread([&u, device_id, fd, path, &S, dst, off, len, chunk]() {
-        const double t0 = now_ms();
-        u.rc = upload_range(device_id, fd, path, S, dst, off, len, chunk);
-        if (u.rc) u.err = g_prep_err;                       // the text is this thread's; the caller takes it over
-        u.ms = now_ms() - t0;
-    });
-}
-
-// a device array that grows at its end; everything in it is counted in `m`
-struct DevVec {
-    uint8_t *p = nullptr;
-    size_t cap = 0, used = 0;                               // bytes
-    // room for `need` bytes: `hope` (the projection) if the budget allows it, else half as much again as there is, else just `need`.
-    // What is there stays (s is idle); while it is copied the old and the new array both count against the budget.
-    int fit(DevMem &m, size_t need, size_t hope, hipStream_t s, const char *what)
-    {
-        if (p && need <= cap) return M6A_OK;
-        Arena *const a = m.arena;
-        m.arena = nullptr;
-        uint8_t *q = nullptr;
-        int rc = M6A_OK;
-        const size_t tries[3] = {hope, cap + cap / 2, need};
-        for (size_t t : tries) {
-            if (t < need || (t > need && m.used + t > m.budget)) continue;
-            hope = t;
-            rc = m.alloc(q, t, what);
-            break;
-        }
-        m.arena = a;
-        if (rc) return rc;
-        if (used) {
-            PCHK(hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, s));
-            PCHK(hipStreamSynchronize(s));
-        }
-        if (p) m.release(p);
-        p = q;
-        cap = std::max<size_t>(16, hope);
-        return M6A_OK;
-    }
-};
-
-struct Win {                                // one window: file bytes [b, b + n); `len` bytes from b are in df, zeros behind them
-    const uint8_t *df = nullptr;
-    int64_t b = 0, len = 0, n = 0, first = 0;
-    bool last = false, grow = false;
-    int64_t NL = 0, nlines = 0, NR = 0, keep = 0, next = 0;
-    int64_t *nl = nullptr;
-    LineEv *ev = nullptr;
-    RunDev *runs = nullptr;
-    bool read_names = false;                // in: --read_names
-    Name *rnames = nullptr;                 // [NR] then
-};
-
-// newline scan, lines and runs of a window, and its cut: n, keep (the runs that stay) and next (b of the window after) -- or grow
-int window_cut(DevMem &m, hipStream_t s, const char *path, Win &V, double *ms)
-{
-    double t1 = now_ms();
-    int rc;
-    const int64_t nb = std::max<int64_t>(1, (V.len + kScanBytes - 1) / kScanBytes);
-    int64_t *bcnt;
-    if ((rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts"))) return rc;
-    nl_count_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)V.df, 0, bcnt);
-    PCHK(hipGetLastError());
-    if ((rc = scan_total(m, bcnt, nb, s, V.NL))) return rc;
-    if (V.last && V.b == 0 && V.NL == 0) return prep_fail(M6A_EFORMAT, "%s: no header line", path);
-    V.grow = !V.last && V.NL == 0;                           // a line longer than the window
-    if (V.grow) return M6A_OK;
-    if ((rc = m.alloc(V.nl, (size_t)V.NL + 1, "newline offsets"))) return rc;
-    nl_write_kernel<<<(unsigned)nb, kBlk, 0, s>>>((const uint4 *)V.df, nb, bcnt, V.nl);
-    PCHK(hipGetLastError());
-    if (V.last) {                                            // the only window that may end without a newline
-        uint8_t end = '\n';
-        if (V.len > 0) { PCHK(hipMemcpyAsync(&end, V.df + V.len - 1, 1, hipMemcpyDeviceToHost, s)); g_d2h += 1; }
-        PCHK(hipStreamSynchronize(s));
-        V.n = V.len;
-        V.nlines = V.NL + (end != '\n' ? 1 : 0);
-    } else {                                                 // it ends behind its last newline; what follows is the next window's
-        int64_t at = 0;
-        PCHK(hipMemcpyAsync(&at, V.nl + V.NL - 1, sizeof at, hipMemcpyDeviceToHost, s));
-        g_d2h += (int64_t)sizeof at;
-        PCHK(hipStreamSynchronize(s));
-        V.n = at + 1;
-        V.nlines = V.NL;
-    }
-    ms[1] += now_ms() - t1;
-
-    t1 = now_ms();
-    unsigned long long *bad;
-    if ((rc = m.alloc(V.ev, (size_t)std::max<int64_t>(V.nlines, 1), "line records"))) return rc;
-    if ((rc = m.alloc(bad, 1, "flags"))) return rc;
-    const unsigned long long none = ~0ull;
-    PCHK(hipMemcpyAsync(bad, &none, sizeof none, hipMemcpyHostToDevice, s));
-    Name *lname = nullptr;
-    if (V.read_names && (rc = m.alloc(lname, (size_t)std::max<int64_t>(V.nlines, 1), "read names"))) return rc;
-    if (V.nlines > V.first) {
-        if (lname) line_kernel<true><<<grid(V.nlines - V.first), kBlk, 0, s>>>(V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, bad, lname);
-        else line_kernel<false><<<grid(V.nlines - V.first), kBlk, 0, s>>>(V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, bad, nullptr);
-        PCHK(hipGetLastError());
-    }
-    unsigned long long bad_at = none;
-    PCHK(hipMemcpyAsync(&bad_at, bad, sizeof bad_at, hipMemcpyDeviceToHost, s));
-    g_d2h += (int64_t)sizeof bad_at;
-    PCHK(hipStreamSynchronize(s));
-    // every line in front of this window has been seen, so this is the file's first bad line, as whole-file mode reports it
-    if (bad_at != none) return bad_line(path, lname != nullptr, V.b, bad_at);
-    if ((rc = find_runs(m, s, V.df, V.n, V.nl, V.NL, V.nlines, V.first, V.ev, V.runs, V.NR, nullptr, lname, &V.rnames))) return rc;
-    V.keep = V.NR;
-    V.next = V.b + V.n;
-    if (!V.last && V.NR > 0) {                               // the last run may go on in the next window: that one starts with it
-        int64_t start = 0;
-        PCHK(hipMemcpyAsync(&start, &V.runs[V.NR - 1].start, sizeof start, hipMemcpyDeviceToHost, s));
-        g_d2h += (int64_t)sizeof start;
-        PCHK(hipStreamSynchronize(s));
-        V.keep = V.NR - 1;
-        V.next = V.b + start;
-        V.grow = V.next == V.b;                              // its only run, from its first byte: no cut in here
-    }
-    ms[2] += now_ms() - t1;
-    return M6A_OK;
-}
-
-// a stream's window: where its kept runs' saved bytes go in the window's part of the two blobs (save_flag_kernel, scanned)
-struct Save {
-    int64_t *head = nullptr, *decl = nullptr;             // [keep + 1] each
-    int64_t n_head = 0, n_decl = 0;
-};
-
-int save_plan(DevMem &m, hipStream_t s, const Win &V, Save &sv)
-{
-    int rc;
-    if ((rc = m.alloc(sv.head, (size_t)V.keep + 1, "saved names")) || (rc = m.alloc(sv.decl, (size_t)V.keep + 1, "saved runs"))) return rc;
-    if (V.keep) {
-        save_flag_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.runs, V.keep, sv.head, sv.decl);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, sv.head, V.keep, s, sv.n_head))) return rc;
-    return scan_total(m, sv.decl, V.keep, s, sv.n_decl);
-}
-
-// what stays of the windows: the job's runs, their row counts and the three row arrays, each grown at its end
-struct Kept {
-    DevVec runs, cnt, pos, kmer, feat, names;             // names: 16 B per kept run, --read_names only
-    DevVec heads, declined;                               // a stream only: Front::heads, Front::declined
-    int64_t NR = 0, NROW = 0;
-    // window V's kept runs and their `nrow` rows behind what is there; `ahead` = what the whole file is expected to hold over what is held now
-    // sv (a stream): the window's saved bytes go behind the two blobs, which grow as the arrays do
-    int append(DevMem &m, hipStream_t s, const Win &V, int w, double ahead, const int64_t *pos_off, const PosRec *ps, const int64_t *row_off,
-               int64_t nrow, const Save *sv = nullptr)
-    {
-        const int64_t K = 5 + 2 * w, NF = 3 * (2 * w + 1);
-        const size_t nr = (size_t)(NR + V.keep) + 1, nw = (size_t)(NROW + nrow) + 1;
-        int rc;
-        if ((rc = runs.fit(m, nr * sizeof(RunDev), (size_t)((double)nr * ahead) * sizeof(RunDev), s, "runs")) ||
-            (rc = cnt.fit(m, nr * 8, (size_t)((double)nr * ahead) * 8, s, "rows")) ||
-            (rc = pos.fit(m, nw * 8, (size_t)((double)nw * ahead) * 8, s, "rows")) ||
-            (rc = kmer.fit(m, nw * (size_t)K, (size_t)((double)nw * ahead) * (size_t)K, s, "rows")) ||
-            (rc = feat.fit(m, nw * (size_t)NF * 8, (size_t)((double)nw * ahead) * (size_t)NF * 8, s, "rows")))
-            return rc;
-        if (V.rnames && (rc = names.fit(m, nr * sizeof(Name), (size_t)((double)nr * ahead) * sizeof(Name), s, "read names"))) return rc;
-        if (V.rnames && V.keep)               // the dropped last run takes its name with it
-            PCHK(hipMemcpyAsync((Name *)names.p + NR, V.rnames, (size_t)V.keep * sizeof(Name), hipMemcpyDeviceToDevice, s));
-        if (V.keep) {
-            if (nrow) {
-                window_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.df, V.runs, V.keep, pos_off, ps, w, nullptr, row_off, (int64_t *)pos.p + NROW,
-                                                            kmer.p + NROW * K, (double *)feat.p + NROW * NF);
-                PCHK(hipGetLastError());
-            }
-            keep_runs_kernel<<<grid(V.keep), kBlk, 0, s>>>(V.runs, V.keep, V.b, row_off, (RunDev *)runs.p + NR, (int64_t *)cnt.p + NR);
-            PCHK(hipGetLastError());
-        }
-        if (sv) {
-            const size_t nh = heads.used + (size_t)sv->n_head, nd = declined.used + (size_t)sv->n_decl;
-            if ((rc = heads.fit(m, nh, (size_t)((double)nh * ahead), s, "saved names")) ||
-                (rc = declined.fit(m, nd, (size_t)((double)nd * ahead), s, "saved runs")))
-                return rc;
-            if (sv->n_head) {
-                save_gather_kernel<<<(unsigned)V.keep, kBlk, 0, s>>>(V.df, V.runs, sv->head, 0, heads.p + heads.used);
-                PCHK(hipGetLastError());
-            }
-            if (sv->n_decl) {
-                save_gather_kernel<<<(unsigned)V.keep, kBlk, 0, s>>>(V.df, V.runs, sv->decl, 1, declined.p + declined.used);
-                PCHK(hipGetLastError());
-            }
-            heads.used = nh; declined.used = nd;
-        }
-        PCHK(hipStreamSynchronize(s));
-        NR += V.keep; NROW += nrow;
-        runs.used = (size_t)NR * sizeof(RunDev); cnt.used = (size_t)NR * 8;
-        if (V.rnames) names.used = (size_t)NR * sizeof(Name);
-        pos.used = (size_t)NROW * 8; kmer.used = (size_t)(NROW * K); feat.used = (size_t)(NROW * NF) * 8;
-        return M6A_OK;
-    }
-};
-
-int front_windows(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
-{
-    const int64_t n = F.n;
-    hipStream_t s = S.s[0];
-    int rc;
-    struct Text { uint8_t *p = nullptr; int64_t cap = 0; } text[2];
-    auto text_fit = [&](Text &T, int64_t len) -> int {      // what was in it is gone
-        const int64_t cap = std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes;
-        if (cap <= T.cap) return M6A_OK;
-        if (T.p) m.release(T.p);
-        T.p = nullptr; T.cap = 0;
-        const int e = m.alloc(T.p, (size_t)cap, "a window of the file");
-        if (!e) T.cap = cap;
-        return e;
-    };
-    Arena arena;
-    auto arena_grow = [&]() -> int {
-        PCHK(hipStreamSynchronize(s));
-        if (arena.base) m.release(arena.base);
-        arena.base = nullptr;
-        const size_t cap = std::max(arena.cap * 2, (arena.need + 4095) & ~(size_t)4095);
-        arena.cap = arena.off = 0;
-        const int e = m.alloc(arena.base, cap, "the scratch of a window");
-        if (!e) arena.cap = cap;
-        return e;
-    };
-    arena.need = (size_t)std::min(W, std::max(n, kScanBytes)) * 2;    // newline offsets and line records: about 1.5 bytes per byte of text
-    if ((rc = arena_grow())) return rc;
-    Kept kept;
-    int64_t b = 0, n_windows = 0, w_max = 0;
-    double wait_ms = 0, copy_ms = 0, copied = 0;
-
-    // window 0 arrives before anything can run; from then on window k + 1 arrives under window k's combine and windows
-    {
-        const int64_t len = std::min(W, n);
-        if ((rc = text_fit(text[0], len))) return rc;
-        const double t0 = now_ms();
-        if ((rc = upload_range(device_id, fd.fd, path, S, text[0].p, 0, len, chunk))) return rc;
-        wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)len;
-    }
-    for (int64_t k = 0;; k++) {
-        Text &T = text[k & 1], &T2 = text[(k + 1) & 1];
-        Upload up;                                           // of window k + 1; joined where it goes out of scope
-        bool started = false;
-        int64_t Wk = W;
-        Win V;
-        for (;;) {                                           // until the arena holds the window and the window holds a cut
-            V = Win();
-            V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
-            V.read_names = F.read_names;
-            V.last = b + Wk >= n;
-            V.len = std::min(Wk, n - b);
-            arena.off = 0;
-            m.arena = &arena;
-            rc = window_cut(m, s, path, V, ms);
-            int64_t *pos_off = nullptr, *row_off = nullptr, nrow = 0;
-            PosRec *ps = nullptr;
-            if (!rc && !V.grow) {
-                if (!V.last && !started) {                   // the cut is known: the next window sets out
-                    m.arena = nullptr;
-                    if ((rc = text_fit(T2, std::min(W, n - V.next)))) return rc;
-                    m.arena = &arena;
-                    upload_start(up, device_id, fd.fd, path, S, T2.p, V.next, std::min(W, n - V.next), chunk);
-                    started = true;
-                }
-                const double t1 = now_ms();
-                rc = count_rows(m, s, V.df, V.ev, V.runs, V.keep, w, pos_off, ps, row_off, nrow);
-                ms[2] += now_ms() - t1;
-            }
-            m.arena = nullptr;
-            if (rc == kArenaFull) {
-                if ((rc = arena_grow())) return rc;
-                continue;
-            }
-            if (rc) return rc;
-            if (V.grow) {                                    // twice the window, read again from b
-                Wk *= 2;
-                const int64_t len = std::min(Wk, n - b);
-                PCHK(hipStreamSynchronize(s));
-                if ((rc = text_fit(T, len))) return rc;
-                const double t0 = now_ms();
-                if ((rc = upload_range(device_id, fd.fd, path, S, T.p, b, len, chunk))) return rc;
-                wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)len;
-                continue;
-            }
-            const double t1 = now_ms();
-            // rows per byte so far, carried over the whole file, and 5 % more
-            if ((rc = kept.append(m, s, V, w, (double)n / (double)std::max<int64_t>(V.next, 1) * 1.05, pos_off, ps, row_off, nrow))) return rc;
-            ms[2] += now_ms() - t1;
-            break;
-        }
-        ++n_windows;
-        w_max = std::max(w_max, Wk);
-        if (started) {
-            const double t0 = now_ms();
-            up.wait();
-            wait_ms += now_ms() - t0; copy_ms += up.ms; copied += (double)std::min(W, n - V.next);
-            if (up.rc) { g_prep_err = up.err; return up.rc; }
-        }
-        if (V.last) break;
-        b = V.next;
-    }
-    // the scratch goes before the back half: X needs the room
-    for (Text &T : text)
-        if (T.p) m.release(T.p);
-    m.release(arena.base);
-    // row_off: one exclusive scan of the row counts of all runs
-    const double t1 = now_ms();
-    int64_t total = 0;
-    if ((rc = scan_total(m, (int64_t *)kept.cnt.p, kept.NR, s, total))) return rc;
-    if (total != kept.NROW) return prep_fail(M6A_EHIP, "the windows' rows do not add up");
-    ms[2] += now_ms() - t1;
-    ms[0] = wait_ms;
-    ms[5] = copy_ms > 0 ? copied / (copy_ms * 1e6) : 0;
-    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
-    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p; F.rnames = (Name *)kept.names.p;
-    F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
-    return M6A_OK;
-}
-
-// ---- the front half on a stream ---------------------------------------------------------------------------------------------------
-// `--eventalign -`, a FIFO, /dev/fd/N: the text comes once and in order, and its length is known when it ends.  The windows are the
-// file's (include/m6a.h; tests/window_statement.py): window k is the `size` bytes from b, the last one exactly when no byte follows
-// them -- the reader's one byte of lookahead (m6a_stream.h) answers that without consuming -- and cut and growth are window_cut's.
-// What front_windows reads again from the file never crosses the link twice here:
-//   carry    the bytes of window k from b of window k + 1 on (the dropped run, what lies behind the last newline) are copied device
-//            to device to the start of the next buffer, which keeps the text 16-byte aligned at its base for the newline scan; the
-//            stream's next bytes are appended behind them, so only the append position is unaligned, and zeros follow the text to
-//            a whole scan block.  A window that grew may leave more than W bytes: the next windows are cut from them first.
-//   growth   the buffer is grown by copy and `size` more bytes are appended.
-//   reading  a thread of the reader's own (m6a_stream::Ring) fills the two pinned chunks from the pipe all the time: it does not wait
-//            for a cut, because the stream's order is fixed.  From the cut of window k on, a second thread takes the next window's
-//            bytes out of the chunks and copies them on the copy stream behind the carried bytes, while the kernel stream counts,
-//            windows and appends window k.
-//   saving   the back half cannot pread a stream: Kept::append saves the contig bytes of segment heads and the bytes of declined
-//            runs from the window's text (save_flag_kernel, scan, save_gather_kernel), and sites_impl gathers from the two blobs.
-// The length is unknown, so the kept arrays grow geometrically (twice what is needed, then DevVec::fit's fallbacks).
-struct Fetch {
-    m6a_stream::Ring &ring;
-    int rc = M6A_OK;
-    std::string err;
-    double ms = 0;
-    int64_t got = 0;
-    bool eof = false;
-    std::thread t;
-    explicit Fetch(m6a_stream::Ring &r) : ring(r) {}
-    void wait() { if (t.joinable()) t.join(); }
-    ~Fetch() { if (t.joinable()) { ring.abandon(); t.join(); } }     // left on an error: nothing more is wanted of the stream
-};
-
-// up to `want` bytes of the stream -> base + have on the copy stream, zeros behind the text to a whole scan block; returns when they
-// have arrived.  got: how many came (fewer than `want` only at the stream's end); eof: whether no byte follows them.  The bytes come
-// out of the pinned pair, which the ring's thread fills from the pipe whether or not anybody is here to take them.
-int stream_fetch(int device_id, m6a_stream::Ring &ring, Streams &S, uint8_t *base, int64_t have, int64_t want, int64_t &got, bool &eof)
-{
-    PCHK(hipSetDevice(device_id));
-    hipError_t bad = hipSuccess;
-    auto copy = [&](const uint8_t *p, int64_t k, int slot, int64_t off) {
-        bad = hipMemcpyAsync(base + have + off, p, (size_t)k, hipMemcpyHostToDevice, S.s[1]);
-        if (bad == hipSuccess) bad = hipEventRecord(S.copied[slot], S.s[1]);
-        return bad == hipSuccess;
-    };
-    auto settle = [&](int slot) { return (bad = hipEventSynchronize(S.copied[slot])) == hipSuccess; };
-    got = 0;
-    const int64_t r = ring.take(want, copy, settle);
-    if (r == -2) return prep_fail(M6A_EHIP, "the copy of a window of the stream: %s", hipGetErrorString(bad));
-    if (r < 0) return prep_fail(M6A_EIO, "%s", ring.R.failed ? ring.R.error.c_str() : "the stream was abandoned");
-    got = r;
-    const int64_t len = have + got, padded = std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes;
-    if (padded > len) PCHK(hipMemsetAsync(base + len, 0, (size_t)(padded - len), S.s[1]));
-    PCHK(hipStreamSynchronize(S.s[1]));
-    const int e = ring.at_eof();
-    if (e < 0) return prep_fail(M6A_EIO, "%s", ring.R.failed ? ring.R.error.c_str() : "the stream was abandoned");
-    eof = e == 1;
-    return M6A_OK;
-}
-
-int front_stream(int device_id, const char *path, int w, int64_t W, int64_t chunk, DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
-{
-    hipStream_t s = S.s[0];
-    int rc;
-    const char *const advice = m.advice;
-    struct Advice { DevMem &m; const char *was; ~Advice() { m.advice = was; } } restore{m, advice};
-    m.advice = "a stream is parsed in windows and what is kept of them stays on the device: give a smaller --window_mb, or write the "
-               "text to a file and run `dataprep` and then `inference` (the two-step path)";
-    m6a_stream::Reader R(fd.fd, false, path);               // fd closes the descriptor (or leaves 0 alone)
-    m6a_stream::Ring ring(R, (uint8_t *)S.pin[0], (uint8_t *)S.pin[1], chunk);
-    struct Text { uint8_t *p = nullptr; int64_t cap = 0; } text[2];
-    auto cap_of = [](int64_t len) { return std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes; };
-    auto text_fit = [&](Text &T, int64_t len) -> int {      // what was in it is gone
-        const int64_t cap = cap_of(len);
-        if (cap <= T.cap) return M6A_OK;
-        if (T.p) m.release(T.p);
-        T.p = nullptr; T.cap = 0;
-        const int e = m.alloc(T.p, (size_t)cap, "a window of the stream");
-        if (!e) T.cap = cap;
-        return e;
-    };
-    auto text_grow = [&](Text &T, int64_t len, int64_t keep) -> int {       // what was in it stays: the old and the new both count
-        const int64_t cap = cap_of(len);
-        if (cap <= T.cap) return M6A_OK;
-        uint8_t *q = nullptr;
-        const int e = m.alloc(q, (size_t)cap, "a window of the stream");
-        if (e) return e;
-        if (keep) PCHK(hipMemcpyAsync(q, T.p, (size_t)keep, hipMemcpyDeviceToDevice, s));
-        PCHK(hipStreamSynchronize(s));
-        if (T.p) m.release(T.p);
-        T.p = q; T.cap = cap;
-        return M6A_OK;
-    };
-    Arena arena;
-    auto arena_grow = [&]() -> int {
-        PCHK(hipStreamSynchronize(s));
-        if (arena.base) m.release(arena.base);
-        arena.base = nullptr;
-        const size_t cap = std::max(arena.cap * 2, (arena.need + 4095) & ~(size_t)4095);
-        arena.cap = arena.off = 0;
-        const int e = m.alloc(arena.base, cap, "the scratch of a window");
-        if (!e) arena.cap = cap;
-        return e;
-    };
-    Kept kept;
-    int64_t b = 0, have = 0, n_windows = 0, w_max = 0;
-    bool eof = false;                                        // no byte follows the `have` bytes from b
-    double wait_ms = 0, copy_ms = 0, copied = 0;
-
-    // the first two bytes say whether this is gzip; then window 0 arrives before anything can run
-    {
-        uint8_t magic[2] = {0, 0};
-        const double t0 = now_ms();
-        const int64_t g = R.fill(magic, 2);
-        if (g < 0) return prep_fail(M6A_EIO, "%s", R.error.c_str());
-        if (g == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
-            return prep_fail(M6A_EINVAL, "%s is a gzip-compressed stream: compressed input from a stream is not implemented; inflate it on "
-                             "the way, `bgzip -dc FILE | ... --eventalign -`, or give the BGZF file by its path", path);
-        if ((rc = text_fit(text[0], W))) return rc;
-        if (g) PCHK(hipMemcpyAsync(text[0].p, magic, (size_t)g, hipMemcpyHostToDevice, S.s[1]));
-        PCHK(hipStreamSynchronize(S.s[1]));
-        ring.start();                                        // from here on the reader is the thread's
-        int64_t got = 0;
-        if ((rc = stream_fetch(device_id, ring, S, text[0].p, g, W - g, got, eof))) return rc;
-        have = g + got;
-        wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)have;
-    }
-    arena.need = (size_t)std::min(W, std::max(have, kScanBytes)) * 2;   // newline offsets and line records: about 1.5 bytes per byte of text
-    if ((rc = arena_grow())) return rc;
-    for (int64_t k = 0;; k++) {
-        Text &T = text[k & 1], &T2 = text[(k + 1) & 1];
-        Fetch up(ring);                                      // of window k + 1; joined where it goes out of scope
-        bool started = false;
-        int64_t Wk = W, carry = 0;
-        Win V;
-        for (;;) {                                           // until the arena holds the window and the window holds a cut
-            V = Win();
-            V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
-            V.read_names = F.read_names;
-            V.len = std::min(Wk, have);                      // have > Wk: what a grown window left; Wk is whole scan blocks then
-            V.last = have < Wk || (have == Wk && eof);       // the file rule b + size >= n: no byte follows these bytes
-            arena.off = 0;
-            m.arena = &arena;
-            rc = window_cut(m, s, path, V, ms);
-            int64_t *pos_off = nullptr, *row_off = nullptr, nrow = 0;
-            PosRec *ps = nullptr;
-            Save sv;
-            if (!rc && !V.grow) {
-                if (!V.last && !started) {                   // the cut is known: the carry moves over and the next bytes set out
-                    m.arena = nullptr;
-                    carry = have - (V.next - b);
-                    if ((rc = text_fit(T2, std::max(W, carry)))) return rc;
-                    m.arena = &arena;
-                    if (carry) PCHK(hipMemcpyAsync(T2.p, T.p + (V.next - b), (size_t)carry, hipMemcpyDeviceToDevice, S.s[1]));
-                    uint8_t *const dst = T2.p;
-                    const int64_t at = carry, want = std::max<int64_t>(0, W - carry);
-                    up.t = std::thread([&up, &ring, &S, device_id, dst, at, want]() {
-                        const double t0 = now_ms();
-                        up.rc = stream_fetch(device_id, ring, S, dst, at, want, up.got, up.eof);
-                        if (up.rc) up.err = g_prep_err;     // the text is this thread's; the caller takes it over
-                        up.ms = now_ms() - t0;
-                    });
-                    started = true;
-                }
-                const double t1 = now_ms();
-                rc = count_rows(m, s, V.df, V.ev, V.runs, V.keep, w, pos_off, ps, row_off, nrow);
-                if (!rc) rc = save_plan(m, s, V, sv);
-                ms[2] += now_ms() - t1;
-            }
-            m.arena = nullptr;
-            if (rc == kArenaFull) {
-                if ((rc = arena_grow())) return rc;
-                continue;
-            }
-            if (rc) return rc;
-            if (V.grow) {                                    // twice the window: what is there stays, the rest is appended
-                Wk *= 2;
-                PCHK(hipStreamSynchronize(s));
-                if (have < Wk) {                             // (a grown window is not the last: a byte follows what is there)
-                    if ((rc = text_grow(T, Wk, have))) return rc;
-                    const double t0 = now_ms();
-                    int64_t got = 0;
-                    if ((rc = stream_fetch(device_id, ring, S, T.p, have, Wk - have, got, eof))) return rc;
-                    have += got;
-                    wait_ms += now_ms() - t0; copy_ms += now_ms() - t0; copied += (double)got;
-                }
-                continue;
-            }
-            const double t1 = now_ms();
-            if ((rc = kept.append(m, s, V, w, 2.0, pos_off, ps, row_off, nrow, &sv))) return rc;
-            ms[2] += now_ms() - t1;
-            break;
-        }
-        ++n_windows;
-        w_max = std::max(w_max, Wk);
-        if (started) {
-            const double t0 = now_ms();
-            up.wait();
-            wait_ms += now_ms() - t0; copy_ms += up.ms; copied += (double)up.got;
-            if (up.rc) { g_prep_err = up.err; return up.rc; }
-        }
-        if (V.last) break;
-        b = V.next;
-        have = carry + up.got;
-        eof = up.eof;
-    }
-    if (R.consumed != b + have) return prep_fail(M6A_EHIP, "the windows of %s do not add up", path);
-    F.n = R.consumed;
-    F.stream = true;
-    // the scratch goes before the back half: X needs the room
-    for (Text &T : text)
-        if (T.p) m.release(T.p);
-    m.release(arena.base);
-    const double t1 = now_ms();
-    int64_t total = 0;
-    if ((rc = scan_total(m, (int64_t *)kept.cnt.p, kept.NR, s, total))) return rc;
-    if (total != kept.NROW) return prep_fail(M6A_EHIP, "the windows' rows do not add up");
-    ms[2] += now_ms() - t1;
-    ms[0] = wait_ms;
-    ms[5] = copy_ms > 0 ? copied / (copy_ms * 1e6) : 0;
-    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
-    F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p; F.rnames = (Name *)kept.names.p;
-    F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
-    F.heads = kept.heads.p; F.n_heads = (int64_t)kept.heads.used;
-    F.declined = kept.declined.p; F.n_declined = (int64_t)kept.declined.used;
     return M6A_OK;
 }
 
@@ -1629,27 +1609,15 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
         P.tx_off.push_back((int64_t)P.blob.size());
         P.run_tx = itx; P.run_read = iread; P.run_start = istart; P.run_end = iend;
     } else {
-        std::unordered_map<std::string, uint32_t> ids;
+        Interner tx(P.blob, P.tx_off);
         std::string nm;
         uint32_t cur = 0;
         for (int64_t r = 0; r < NR; r++) {
             const RunDev &R = hr[(size_t)r];
             if (r == 0 || !R.same_contig) {
                 nm.resize((size_t)R.contig_len);
-                for (int64_t got = 0; got < R.contig_len;) {
-                    const ssize_t k = ::pread(fd.fd, &nm[(size_t)got], (size_t)(R.contig_len - got), (off_t)(R.contig + got));
-                    if (k < 0 && errno == EINTR) continue;
-                    if (k <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
-                    got += k;
-                }
-                auto it = ids.find(nm);
-                if (it != ids.end()) cur = it->second;
-                else {
-                    cur = (uint32_t)ids.size();
-                    ids.emplace(nm, cur);
-                    P.tx_off.push_back((int64_t)P.blob.size());
-                    P.blob += nm;
-                }
+                if ((rc = read_fully(fd.fd, &nm[0], R.contig_len, R.contig, path))) return rc;
+                cur = tx.id(nm);
             }
             P.run_tx[(size_t)r] = cur;
             P.run_read[(size_t)r] = R.read;
@@ -2075,6 +2043,29 @@ int radix_sort(DevMem &m, uint64_t *&key, uint32_t *&val, uint64_t *&key2, uint3
     return M6A_OK;
 }
 
+// stable sort of (key, val) by up to three fields, given by their bit widths, least significant first.  As many fields as fit into
+// 64 bits go into one key: make_key(use, shift) launches the caller's key kernel for the fields whose bit is set in `use`, field f at
+// bit shift[f], and radix_sort sorts by what was packed; the fields that are left follow in further passes (LSD, stable).
+template <class MakeKey>
+int sort_by_fields(DevMem &m, hipStream_t s, const int *bits, int n_fields, uint64_t *&key, uint32_t *&val, uint64_t *&key2, uint32_t *&val2, int64_t n,
+                   MakeKey make_key)
+{
+    int rc, shift[3] = {0, 0, 0}, at = 0;
+    unsigned use = 0;
+    for (int f = 0; f <= n_fields; f++) {
+        if (f == n_fields || (bits[f] && at + bits[f] > 64)) {          // sort by what is packed so far
+            if (use && ((rc = make_key(use, shift)) || (rc = radix_sort(m, key, val, key2, val2, n, at, s)))) return rc;
+            use = 0;
+            at = 0;
+        }
+        if (f == n_fields || !bits[f]) continue;
+        shift[f] = at;
+        use |= 1u << f;
+        at += bits[f];
+    }
+    return M6A_OK;
+}
+
 template <class T> int d2h(T *dst, const T *src, size_t count, hipStream_t s)
 {
     if (!count) return M6A_OK;
@@ -2175,32 +2166,18 @@ int intern_runs(DevMem &m, hipStream_t s, RunDev *runs, const Name *rn, int64_t 
     if ((rc = m.alloc(k1, (size_t)NR + 1, "read names")) || (rc = m.alloc(k2, (size_t)NR + 1, "read names")) ||
         (rc = m.alloc(val, (size_t)NR + 1, "read names")) || (rc = m.alloc(val2, (size_t)NR + 1, "read names")))
         return rc;
-    for (int hi = 0; hi < 2 && NR; hi++) {
-        name_key_kernel<<<grid(NR), kBlk, 0, s>>>(rn, NR, hi, val, k1);
-        PCHK(hipGetLastError());
-        if ((rc = radix_sort(m, k1, val, k2, val2, NR, 64, s))) return rc;
-    }
+    for (int hi = 0; hi < 2 && NR; hi++)
+        if ((rc = launch(name_key_kernel, NR, s, rn, NR, hi, val, k1)) || (rc = radix_sort(m, k1, val, k2, val2, NR, 64, s))) return rc;
     PCHK(hipStreamSynchronize(s));
-    m.release(k1); m.release(k2); m.release(val2);
+    m.release({k1, k2, val2});
     if ((rc = m.alloc(in.gx, (size_t)NR + 1, "read names")) || (rc = m.alloc(in.rank, (size_t)NR + 1, "read names")) ||
         (rc = m.alloc(gfirst, (size_t)NR + 1, "read names")))
         return rc;
     PCHK(hipMemsetAsync(in.gx + NR, 0, sizeof(int64_t), s));
     PCHK(hipMemsetAsync(in.rank, 0, (size_t)(NR + 1) * sizeof(int64_t), s));
-    if (NR) {
-        name_head_kernel<<<grid(NR), kBlk, 0, s>>>(val, NR, rn, in.gx);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_excl(m, in.gx, NR + 1, s))) return rc;
-    if (NR) {
-        name_first_kernel<<<grid(NR), kBlk, 0, s>>>(val, NR, in.gx, gfirst, in.rank);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_excl(m, in.rank, NR + 1, s))) return rc;
-    if (NR) {
-        name_index_kernel<<<grid(NR), kBlk, 0, s>>>(val, NR, in.gx, gfirst, in.rank, runs);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(name_head_kernel, NR, s, val, NR, rn, in.gx)) || (rc = scan_excl(m, in.gx, NR + 1, s))) return rc;
+    if ((rc = launch(name_first_kernel, NR, s, val, NR, in.gx, gfirst, in.rank)) || (rc = scan_excl(m, in.rank, NR + 1, s))) return rc;
+    if ((rc = launch(name_index_kernel, NR, s, val, NR, in.gx, gfirst, in.rank, runs))) return rc;
     PCHK(hipStreamSynchronize(s));
     m.release(gfirst);
     in.val = val;
@@ -2217,8 +2194,7 @@ int scan_total_and_names(DevMem &m, int64_t *a, int64_t n, hipStream_t s, int64_
     if ((rc = m.alloc(w, 1, "flags"))) return rc;
     pack_totals_kernel<<<1, 1, 0, s>>>(a + n, in.rank + n, w);
     PCHK(hipGetLastError());
-    if ((rc = d2h(&h, w, 1, s))) return rc;
-    PCHK(hipStreamSynchronize(s));
+    if ((rc = fetch(h, w, s))) return rc;
     total = (int64_t)(h & 0xffffffffull);
     n_names = (int64_t)(h >> 32);
     return M6A_OK;
@@ -2244,9 +2220,9 @@ struct FilePart {
 };
 
 struct Pool {
-    std::unordered_map<std::string, uint32_t> ids;         // transcript names of all files, in order of first appearance
+    Interner tx;                                            // transcript names of all files, in order of first appearance: the job's
     std::vector<FilePart> parts;
-    uint32_t global_tx(const std::string &nm, m6a_prep_sites &P);
+    Pool(std::string &blob, std::vector<int64_t> &tx_off) : tx(blob, tx_off) {}
 };
 
 }  // namespace
@@ -2280,506 +2256,528 @@ struct m6a_prep_sites {
 
 namespace {
 
-uint32_t Pool::global_tx(const std::string &nm, m6a_prep_sites &P)
+// the normalisation 5-mers packed like pack5, sorted, each once: keys, and per key the index of the first of equal 5-mers (the
+// loader's map keeps the first)
+void norm_keys(const char *norm_kmers, int n_norm, std::vector<uint64_t> &keys, std::vector<int32_t> &first)
 {
-    auto it = ids.find(nm);
-    if (it != ids.end()) return it->second;
-    const uint32_t t = (uint32_t)ids.size();
-    ids.emplace(nm, t);
-    P.tx_off.push_back((int64_t)P.blob.size());
-    P.blob += nm;
-    return t;
-}
-
-// One file.  pool == nullptr: the whole job (m6a_prep_sites_build), P filled.  Else the file is one replicate of several: its sites
-// with >= min_seg reads (the 20-read floor and the per-site checks wait for the pooled sites, pool_impl), their X and read ids stay
-// on the device as a FilePart, and everything else the file needed -- its text, line records, candidate rows -- is released.
-int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
-               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window, m6a_prep_sites &P, DevMem &m,
-               double *ms, Pool *pool, const DataprepJob *job = nullptr)
-{
-    const bool read_names = P.read_names;
-    const double t_all = now_ms();
-    double fms[6] = {0, 0, 0, 0, 0, 0};
-    const size_t mark = m.ptrs.size();
-    std::string own_blob;                                   // pooled: this file's names, for its own error texts; P's are the job's
-    std::vector<int64_t> own_tx_off;
-    std::string &blob = pool ? own_blob : P.blob;
-    std::vector<int64_t> &tx_off = pool ? own_tx_off : P.tx_off;
-    std::vector<uint32_t> l2g;                              // this file's transcript ids -> the job's
-    Streams S;
-    Fd fd;
-    Front F;
-    F.bgzf_ok = !job;                                       // dataprep's index holds offsets into the text: BGZF and streams stay refused
-    F.read_names = read_names;
-    int rc = front_half(device_id, path, 1, nullptr, nullptr, window, m, S, fd, F, fms);
-    if (rc) return rc;
-    P.info.n_bgzf_blocks += F.n_blocks;
-    P.info.compressed_bytes += F.comp_bytes;
-    P.info.ms_inflate += F.ms_inflate;
-    P.info.n_windows += F.n_windows;
-    P.info.window_bytes = std::max(P.info.window_bytes, F.window_bytes);
-    if (F.stream) { P.stream_bytes += F.n; P.n_streams += 1; }
-    ms[0] = fms[0]; ms[1] = fms[1]; ms[2] = fms[2]; ms[6] = fms[5];
-    hipStream_t s = S.s[0];
-    PCHK(hipStreamSynchronize(s));
-    for (const void *p : F.scratch) m.release(p);          // the file and its line records: X needs the room
-    double t1 = now_ms(), dev_ms = 0, host_ms = 0;
-    const int64_t NR = F.NR, NROW = F.NROW;
-    if (NR > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 runs");
-    Intern in;
-    double t_in = now_ms();
-    if (read_names && (rc = intern_runs(m, s, F.runs, F.rnames, NR, in))) return rc;   // from here on RunDev.read is the twin's read index
-    if (read_names) P.ms_intern += now_ms() - t_in;
-
-    // ---- segments and declined runs, to the host
-    int64_t *sx, *dx, NSEG = 0, ND = 0;
-    if ((rc = m.alloc(sx, (size_t)NR + 1, "segments")) || (rc = m.alloc(dx, (size_t)NR + 1, "declined runs"))) return rc;
-    if (NR) {
-        run_flags_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, dx);
-        PCHK(hipGetLastError());
-    }
-    int64_t n_names = 0;
-    if ((rc = read_names ? scan_total_and_names(m, sx, NR, s, NSEG, in, n_names) : scan_total(m, sx, NR, s, NSEG)) ||
-        (rc = scan_total(m, dx, NR, s, ND)))
-        return rc;
-    uint8_t *dnames = nullptr;
-    if (read_names) {                                       // the table: one copy of 16 bytes per name comes to the host
-        t_in = now_ms();
-        if ((rc = m.alloc(dnames, (size_t)n_names * 16, "read names"))) return rc;
-        if (NR) {
-            name_table_kernel<<<grid(NR), kBlk, 0, s>>>(in.val, NR, in.gx, in.rank, F.rnames, n_names, dnames);
-            PCHK(hipGetLastError());
-        }
-        const size_t at = P.names16.size();
-        P.names16.resize(at + (size_t)n_names * 16);
-        if ((rc = d2h(P.names16.data() + at, dnames, (size_t)n_names * 16, s))) return rc;
-        PCHK(hipStreamSynchronize(s));
-        P.name_off.push_back(P.name_off.back() + n_names);
-        for (const void *p : {(const void *)in.val, (const void *)in.gx, (const void *)in.rank, (const void *)F.rnames}) m.release(p);
-        P.ms_intern += now_ms() - t_in;
-    }
-    SegDev *seg;
-    DeclDev *decl;
-    if ((rc = m.alloc(seg, (size_t)NSEG + 1, "segments")) || (rc = m.alloc(decl, (size_t)ND + 1, "declined runs"))) return rc;
-    if (NR) {
-        run_lists_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, dx, seg, decl);
-        PCHK(hipGetLastError());
-    }
-    std::vector<SegDev> hseg((size_t)NSEG);
-    std::vector<DeclDev> hdecl((size_t)ND);
-    if ((rc = d2h(hseg.data(), seg, (size_t)NSEG, s)) || (rc = d2h(hdecl.data(), decl, (size_t)ND, s))) return rc;
-    PCHK(hipStreamSynchronize(s));
-    dev_ms += now_ms() - t1;
-
-    // ---- the host: transcript names (read from the file where the contig changes), ranks, the readcount verdict, declined runs
-    t1 = now_ms();
-    std::unordered_map<std::string, uint32_t> ids;
-    std::vector<SegUp> up((size_t)NSEG);
-    std::vector<int64_t> tx_runs;
-    std::string nm;
-    std::vector<uint8_t> packed;                            // BGZF input: the contig bytes of all segments, from the text on the device
-    const bool resident = F.text || F.stream;              // the bytes come from the device, not from the file
-    if (resident) {
-        std::vector<int64_t> src((size_t)NSEG), len((size_t)NSEG);
-        int64_t sum = 0;                                    // a stream: the heads were saved in run order, so segment g's lie at the running sum
-        for (int64_t g = 0; g < NSEG; g++) {
-            src[(size_t)g] = F.stream ? sum : hseg[(size_t)g].contig;
-            len[(size_t)g] = hseg[(size_t)g].len;
-            sum += hseg[(size_t)g].len;
-        }
-        if (F.stream && sum != F.n_heads) return prep_fail(M6A_EHIP, "the saved contig names of %s do not add up", path);
-        if ((rc = F.stream ? bgzf_gather(m, s, F.heads, F.n_heads, src, len, packed) : bgzf_gather(m, s, F.text, F.n, src, len, packed))) return rc;
-    }
-    for (int64_t g = 0, at = 0; g < NSEG; g++) {
-        const SegDev &G = hseg[(size_t)g];
-        nm.resize((size_t)G.len);
-        if (resident) {
-            memcpy(&nm[0], packed.data() + at, (size_t)G.len);
-            at += G.len;
-        }
-        for (int64_t got = 0; !resident && got < G.len;) {
-            const ssize_t k = ::pread(fd.fd, &nm[(size_t)got], (size_t)(G.len - got), (off_t)(G.contig + got));
-            if (k < 0 && errno == EINTR) continue;
-            if (k <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
-            got += k;
-        }
-        auto it = ids.find(nm);
-        uint32_t t;
-        if (it != ids.end()) t = it->second;
-        else {
-            t = (uint32_t)ids.size();
-            ids.emplace(nm, t);
-            tx_off.push_back((int64_t)blob.size());
-            blob += nm;
-            tx_runs.push_back(0);
-            if (pool) l2g.push_back(pool->global_tx(nm, P));
-        }
-        const int64_t len = (g + 1 < NSEG ? hseg[(size_t)g + 1].first : NR) - G.first;
-        up[(size_t)g].rank0 = tx_runs[t];
-        up[(size_t)g].tx = t;
-        tx_runs[t] += len;
-    }
-    tx_off.push_back((int64_t)blob.size());
-    const int64_t lim = std::max(0, rmax);                  // `if ++readcount > readcount_max: break` after the first run
-    for (SegUp &u : up) u.keep = std::min(tx_runs[u.tx], lim + 1) >= rmin;
-    // declined runs the host loop reaches: combined and windowed by the host half
-    std::vector<int64_t> cstart, cend, cread, crun;
-    std::vector<int64_t> csaved;                            // a stream: where the run's bytes lie among the saved ones
-    int64_t saved_at = 0;
-    for (const DeclDev &d : hdecl) {
-        const int64_t at_saved = saved_at;
-        saved_at += d.end - d.start;
-        const int64_t g = (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), d.run, [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
-        if (up[(size_t)g].rank0 + (d.run - hseg[(size_t)g].first) > lim) continue;
-        cstart.push_back(d.start); cend.push_back(d.end); cread.push_back(d.read); crun.push_back(d.run);
-        csaved.push_back(at_saved);
-    }
-    if (F.stream && saved_at != F.n_declined) return prep_fail(M6A_EHIP, "the saved declined runs of %s do not add up", path);
-    std::vector<DeclUp> dup;
-    std::vector<int64_t> hpos, hrun;
-    std::vector<uint8_t> hkmer;
-    std::vector<double> hfeat;
-    if (!crun.empty()) {
-        if (!host || !host->rows || !host->table || !host->free)
-            return prep_fail(M6A_EINVAL, "%zu runs need the host half and none was given", crun.size());
-        struct m6a_io_rows *hr = nullptr;
-        // BGZF input or a stream: the host half takes a path, so it gets the declined runs laid end to end in a plain temporary file
-        struct Tmp { std::string path; ~Tmp() { if (!path.empty()) ::unlink(path.c_str()); } } tmp;
-        if (resident) {
-            std::vector<int64_t> len(crun.size());
-            for (size_t i = 0; i < crun.size(); i++) len[i] = cend[i] - cstart[i];
-            if ((rc = F.stream ? bgzf_gather(m, s, F.declined, F.n_declined, csaved, len, packed) : bgzf_gather(m, s, F.text, F.n, cstart, len, packed)))
-                return rc;
-            const char *dir = getenv("TMPDIR");
-            std::string name = std::string(dir && *dir ? dir : "/tmp") + "/m6a_declined_XXXXXX";
-            const int tfd = ::mkstemp(&name[0]);
-            if (tfd < 0) return prep_fail(M6A_EIO, "cannot create a temporary file for the declined runs of %s", path);
-            tmp.path = name;
-            for (size_t got = 0; got < packed.size();) {
-                const ssize_t k = ::write(tfd, packed.data() + got, packed.size() - got);
-                if (k < 0 && errno == EINTR) continue;
-                if (k <= 0) { ::close(tfd); return prep_fail(M6A_EIO, "cannot write %s", name.c_str()); }
-                got += (size_t)k;
-            }
-            ::close(tfd);
-            for (size_t i = 0, at = 0; i < crun.size(); i++) { cstart[i] = (int64_t)at; at += (size_t)len[i]; cend[i] = (int64_t)at; }
-        }
-        const int hrc = host->rows(resident ? tmp.path.c_str() : path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, n_threads, &hr);
-        if (hrc != 0 || !hr) {                              // its own code and text (m6a_io's -1..-4 -> M6A_EINVAL, ENOMEM, EIO, EFORMAT)
-            const int code = hrc == -2 ? M6A_ENOMEM : hrc == -3 ? M6A_EIO : hrc == -4 ? M6A_EFORMAT : hrc == -1 ? M6A_EINVAL : M6A_EIO;
-            return prep_fail(code, "%s", host->error ? host->error() : "the host half failed on the declined runs");
-        }
-        struct Guard { const m6a_prep_host_half *h; struct m6a_io_rows *r; ~Guard() { h->free(r); } } guard{host, hr};
-        const m6a_io_prep_table *T = host->table(hr);
-        if (!T || T->n_runs != (int64_t)crun.size() || T->n_neighbors != 1) return prep_fail(M6A_EINVAL, "the host half returned a bad table");
-        for (size_t i = 0; i < crun.size(); i++) {
-            if (T->run_status[i] != M6A_PREP_RUN_OK) {
-                const int64_t g = (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), crun[i], [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
-                const uint32_t t = up[(size_t)g].tx;
-                return prep_fail(M6A_EFORMAT, "malformed eventalign line for %.*s", (int)(tx_off[t + 1] - tx_off[t]), blob.data() + tx_off[t]);
-            }
-            dup.push_back(DeclUp{crun[i], T->run_npos[i]});
-            for (int64_t k = T->row_off[i]; k < T->row_off[i + 1]; k++) {
-                hpos.push_back(T->row_pos[k]);
-                hkmer.insert(hkmer.end(), T->row_kmer + k * 7, T->row_kmer + k * 7 + 7);
-                hfeat.insert(hfeat.end(), T->row_feat + k * 9, T->row_feat + k * 9 + 9);
-                hrun.push_back(crun[i]);
-            }
-        }
-    }
-    if (F.text) m.release(F.text);                          // names and declined runs are on the host: X needs the room
-    if (F.heads) m.release(F.heads);
-    if (F.declined) m.release(F.declined);
-    const int64_t NH = (int64_t)hpos.size(), NT = (int64_t)tx_runs.size();
-    if (NROW + NH > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate rows");
-    host_ms += now_ms() - t1;
-
-    // ---- runs: used or not, and their place
-    t1 = now_ms();
-    SegUp *dup_seg;
-    DeclUp *ddecl;
-    int64_t *dhpos, *dhrun;
-    uint8_t *dhkmer;
-    double *dhfeat;
-    if ((rc = m.alloc(dup_seg, (size_t)NSEG + 1, "segments")) || (rc = m.alloc(ddecl, dup.size() + 1, "declined runs")) ||
-        (rc = m.alloc(dhpos, (size_t)NH + 1, "host rows")) || (rc = m.alloc(dhrun, (size_t)NH + 1, "host rows")) ||
-        (rc = m.alloc(dhkmer, (size_t)NH * 7 + 1, "host rows")) || (rc = m.alloc(dhfeat, (size_t)NH * 9 + 1, "host rows")))
-        return rc;
-    if ((rc = h2d(dup_seg, up.data(), up.size(), s)) || (rc = h2d(ddecl, dup.data(), dup.size(), s)) || (rc = h2d(dhpos, hpos.data(), hpos.size(), s)) ||
-        (rc = h2d(dhrun, hrun.data(), hrun.size(), s)) || (rc = h2d(dhkmer, hkmer.data(), hkmer.size(), s)) ||
-        (rc = h2d(dhfeat, hfeat.data(), hfeat.size(), s)))
-        return rc;
-    if (!dup.empty()) {
-        decl_patch_kernel<<<grid((int64_t)dup.size()), kBlk, 0, s>>>(F.runs, ddecl, (int64_t)dup.size());
-        PCHK(hipGetLastError());
-    }
-    const RowSrc rs{F.row_pos, dhpos, F.row_kmer, dhkmer, F.row_feat, dhfeat, NROW};
-    uint32_t *run_tx;
-    int64_t *run_rank, *elig, NE = 0;
-    if ((rc = m.alloc(run_tx, (size_t)NR + 1, "runs")) || (rc = m.alloc(run_rank, (size_t)NR + 1, "runs")) || (rc = m.alloc(elig, (size_t)NR + 1, "runs")))
-        return rc;
-    if (NR) {
-        run_select_kernel<<<grid(NR), kBlk, 0, s>>>(F.runs, NR, sx, seg, dup_seg, lim, run_tx, run_rank, elig);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, elig, NR, s, NE))) return rc;
-    uint64_t *k1, *k2;
-    uint32_t *E, *E2;
-    if ((rc = m.alloc(k1, (size_t)NE + 1, "runs")) || (rc = m.alloc(k2, (size_t)NE + 1, "runs")) || (rc = m.alloc(E, (size_t)NE + 1, "runs")) ||
-        (rc = m.alloc(E2, (size_t)NE + 1, "runs")))
-        return rc;
-    unsigned long long *mm, hmm[2] = {kNone, 0};
-    if ((rc = m.alloc(mm, 2, "flags"))) return rc;
-    if (NR) {
-        compact_u32_kernel<<<grid(NR), kBlk, 0, s>>>(elig, NR, E);
-        PCHK(hipGetLastError());
-    }
-    if (NE) {
-        PCHK(hipMemcpyAsync(mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
-        minmax_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, 0, F.runs, rs, mm);
-        PCHK(hipGetLastError());
-        if ((rc = d2h(hmm, mm, 2, s))) return rc;
-        PCHK(hipStreamSynchronize(s));
-        const int rb = bits_for(hmm[1] - hmm[0]), tb = bits_for((uint64_t)std::max<int64_t>(NT - 1, 0));
-        // (transcript, read) in one key when it fits, else the read first and the transcript after it (LSD, stable)
-        const unsigned both = (rb ? 1u : 0u) | (tb ? 2u : 0u);
-        const unsigned passes[2] = {rb + tb <= 64 ? both : 1u, rb + tb <= 64 ? 0u : 2u};
-        for (unsigned use : passes) {
-            if (!use) continue;
-            const int bits = (use & 1 ? rb : 0) + (use & 2 ? tb : 0);
-            run_key_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, F.runs, run_tx, hmm[0], use & 1 ? rb : 0, use, k1);
-            PCHK(hipGetLastError());
-            if ((rc = radix_sort(m, k1, E, k2, E2, NE, bits, s))) return rc;
-        }
-    }
-    uint8_t *used;
-    int64_t *run_place, *gx, *gfirst, NG = 0;
-    if ((rc = m.alloc(used, (size_t)NR + 1, "runs")) || (rc = m.alloc(run_place, (size_t)NR + 1, "runs")) || (rc = m.alloc(gx, (size_t)NE + 2, "runs")))
-        return rc;
-    PCHK(hipMemsetAsync(used, 0, (size_t)NR + 1, s));
-    if (NE) {
-        dup_head_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, F.runs, run_tx, gx);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, gx, NE, s, NG))) return rc;
-    if ((rc = m.alloc(gfirst, (size_t)NG + 1, "runs"))) return rc;
-    if (NE) {
-        dup_first_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, gx, run_rank, gfirst);
-        PCHK(hipGetLastError());
-        dup_last_kernel<<<grid(NE), kBlk, 0, s>>>(E, NE, gx, gfirst, used, run_place);
-        PCHK(hipGetLastError());
-    }
-    PCHK(hipStreamSynchronize(s));
-    for (const void *p : {(const void *)k1, (const void *)k2, (const void *)E, (const void *)E2, (const void *)gx, (const void *)gfirst,
-                          (const void *)elig, (const void *)sx, (const void *)dx})
-        m.release(p);
-
-    // ---- rows of the used runs, sorted by (transcript, position, place)
-    int64_t *rx, NL0 = 0, *hx, NLH = 0;
-    if ((rc = m.alloc(rx, (size_t)NR + 1, "rows")) || (rc = m.alloc(hx, (size_t)NH + 1, "rows"))) return rc;
-    if (NR) {
-        used_rows_count_kernel<<<grid(NR), kBlk, 0, s>>>(used, F.row_off, NR, rx);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, rx, NR, s, NL0))) return rc;
-    if (NH) {
-        host_flag_kernel<<<grid(NH), kBlk, 0, s>>>(used, dhrun, NH, hx);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, hx, NH, s, NLH))) return rc;
-    const int64_t NL = NL0 + NLH;
-    uint32_t *L, *L2, *row_run;
-    if ((rc = m.alloc(L, (size_t)NL + 1, "rows")) || (rc = m.alloc(L2, (size_t)NL + 1, "rows")) || (rc = m.alloc(row_run, (size_t)(NROW + NH) + 1, "rows")) ||
-        (rc = m.alloc(k1, (size_t)NL + 1, "rows")) || (rc = m.alloc(k2, (size_t)NL + 1, "rows")))
-        return rc;
-    if (NR) {
-        used_rows_write_kernel<<<grid(NR), kBlk, 0, s>>>(used, F.row_off, NR, rx, L, row_run);
-        PCHK(hipGetLastError());
-    }
-    if (NH) {
-        host_rows_kernel<<<grid(NH), kBlk, 0, s>>>(dhrun, NH, NROW, NL0, hx, L, row_run);
-        PCHK(hipGetLastError());
-    }
-    if (NL) {
-        PCHK(hipMemcpyAsync(mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
-        minmax_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, 1, F.runs, rs, mm);
-        PCHK(hipGetLastError());
-        if ((rc = d2h(hmm, mm, 2, s))) return rc;
-        PCHK(hipStreamSynchronize(s));
-        RowKey key{hmm[0], 0, 0, 0, 0};
-        const int fb[3] = {bits_for((uint64_t)lim), bits_for(hmm[1] - hmm[0]), bits_for((uint64_t)std::max<int64_t>(NT - 1, 0))};
-        const unsigned fu[3] = {4, 2, 1};                  // place, position, transcript: least significant first
-        int at = 0;
-        for (int f = 0; f <= 3; f++) {
-            if (f == 3 || (fb[f] && at + fb[f] > 64)) {   // sort by what is packed so far
-                if (key.use) {
-                    row_key_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, rs, row_run, run_tx, run_place, key, k1);
-                    PCHK(hipGetLastError());
-                    if ((rc = radix_sort(m, k1, L, k2, L2, NL, at, s))) return rc;
-                }
-                key.use = 0;
-                at = 0;
-            }
-            if (f == 3 || !fb[f]) continue;
-            if (f == 0) key.sh_place = at;
-            if (f == 1) key.sh_pos = at;
-            if (f == 2) key.sh_tx = at;
-            key.use |= fu[f];
-            at += fb[f];
-        }
-    }
-
-    // ---- sites: cut, checked, filtered
-    int64_t *shx, NS0 = 0;
-    if ((rc = m.alloc(shx, (size_t)NL + 1, "sites"))) return rc;
-    if (NL) {
-        site_head_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, rs, row_run, run_tx, shx);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, shx, NL, s, NS0))) return rc;
-    int64_t *start, *kx, NS = 0;
-    unsigned long long *bad, hbad = kNone;
-    if ((rc = m.alloc(start, (size_t)NS0 + 1, "sites")) || (rc = m.alloc(kx, (size_t)NS0 + 1, "sites")) || (rc = m.alloc(bad, 1, "flags"))) return rc;
-    PCHK(hipMemcpyAsync(bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
-    if (NL) {
-        site_start_kernel<<<grid(NL), kBlk, 0, s>>>(shx, NL, start);
-        PCHK(hipGetLastError());
-        site_check_kernel<<<grid(NL), kBlk, 0, s>>>(L, NL, rs, shx, start, bad);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = d2h(&hbad, bad, 1, s))) return rc;
-    PCHK(hipStreamSynchronize(s));
-    if (hbad != ~0ull) {
-        int64_t *probe, hp[2] = {0, 0};
-        if ((rc = m.alloc(probe, 2, "flags"))) return rc;
-        probe_kernel<<<1, 1, 0, s>>>(L, start, (int64_t)hbad, rs, row_run, run_tx, probe);
-        PCHK(hipGetLastError());
-        if ((rc = d2h(hp, probe, 2, s))) return rc;
-        PCHK(hipStreamSynchronize(s));
-        const int64_t t = hp[0];
-        return prep_fail(M6A_EFORMAT, "reads disagree on the sequence at %.*s:%lld", (int)(tx_off[t + 1] - tx_off[t]), blob.data() + tx_off[t],
-                         (long long)hp[1]);
-    }
-    if (NS0) {
-        site_keep_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, pool || job ? (int64_t)min_seg : std::max<int64_t>(min_seg, 20), kx);
-        PCHK(hipGetLastError());
-    }
-    if ((rc = scan_total(m, kx, NS0, s, NS))) return rc;
-    int64_t *src, *doff;
-    if ((rc = m.alloc(src, (size_t)NS + 1, "sites")) || (rc = m.alloc(doff, (size_t)NS + 1, "the offsets"))) return rc;
-    PCHK(hipMemsetAsync(doff + NS, 0, sizeof(int64_t), s));
-    if (NS0) {
-        site_emit_kernel<<<grid(NS0), kBlk, 0, s>>>(start, NS0, kx, src, doff);
-        PCHK(hipGetLastError());
-    }
-    int64_t R = 0;
-    if ((rc = scan_total(m, doff, NS, s, R))) return rc;
-
-    if (job) {                                              // dataprep: no normalisation, no vocabulary, and text instead of X
-        uint32_t *jtx;
-        int64_t *jpos;
-        uint8_t *jk7, *jkm;
-        int32_t *jnorm;
-        if ((rc = m.alloc(jtx, (size_t)NS + 1, "sites")) || (rc = m.alloc(jpos, (size_t)NS + 1, "sites")) || (rc = m.alloc(jk7, (size_t)NS * 7 + 1, "sites")) ||
-            (rc = m.alloc(jkm, (size_t)NS * 3 + 1, "sites")) || (rc = m.alloc(jnorm, (size_t)NS * 3 + 1, "sites")))
-            return rc;
-        if (NS) {
-            site_info_kernel<<<grid(NS), kBlk, 0, s>>>(L, src, NS, rs, row_run, run_tx, nullptr, nullptr, 0, nullptr, 0, jnorm, jkm, jtx, jpos, jk7, bad,
-                                                       nullptr, 1);
-            PCHK(hipGetLastError());
-        }
-        PCHK(hipStreamSynchronize(s));
-        for (const void *p : {(const void *)jkm, (const void *)jnorm, (const void *)k1, (const void *)k2, (const void *)L2, (const void *)shx,
-                              (const void *)start, (const void *)kx})
-            m.release(p);
-        dev_ms += now_ms() - t1;
-        job->st->ms_front = fms[0] + fms[1] + fms[2];
-        job->st->ms_back = dev_ms + host_ms;
-        const DataprepSrc ds{JsonDev{L, src, doff, rs, row_run, F.runs, jtx, jpos, jk7, nullptr, nullptr, 0}, run_tx, NS, NR, NL, NT, &blob, &tx_off};
-        return dataprep_emit(m, s, *job, ds);
-    }
-
-    // ---- normalisation, vocabulary, X
-    std::vector<uint64_t> nk, voc = vocab_keys();
     std::vector<std::pair<uint64_t, int32_t>> norm;
     for (int i = 0; i < n_norm; i++) {
         uint64_t x = 0;
         for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)norm_kmers[5 * i + j];
         norm.emplace_back(x, i);
     }
-    std::sort(norm.begin(), norm.end());                   // a repeated 5-mer: the loader's map keeps the first
-    std::vector<int32_t> nix;
+    std::sort(norm.begin(), norm.end());
     for (size_t i = 0; i < norm.size(); i++)
-        if (i == 0 || norm[i].first != norm[i - 1].first) { nk.push_back(norm[i].first); nix.push_back(norm[i].second); }
-    uint64_t *dnk, *dvoc;
-    int32_t *dnix, *site_norm;
+        if (i == 0 || norm[i].first != norm[i - 1].first) { keys.push_back(norm[i].first); first.push_back(norm[i].second); }
+}
+
+// the error of the lowest bad site (8 site + what) that site_info_kernel or, pooled, pool_site_kernel found; the sites are in P
+int bad_site(const m6a_prep_sites &P, unsigned long long bad, bool pooled)
+{
+    const int64_t bs = (int64_t)(bad >> 3), what = (int64_t)(bad & 7);
+    const char *k = P.k7.data() + bs * 7;
+    if (what < 3) return prep_fail(M6A_EFORMAT, "no normalisation factors for %.5s", k + what);
+    const uint32_t t = P.tx[(size_t)bs];
+    const int len = (int)(P.tx_off[t + 1] - P.tx_off[t]);
+    if (pooled && what == 3)
+        return prep_fail(M6A_EFORMAT, "replicates disagree on the sequence of %.*s:%lld", len, P.blob.data() + P.tx_off[t], (long long)P.pos[(size_t)bs]);
+    return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", len, P.blob.data() + P.tx_off[t], (long long)P.pos[(size_t)bs], k);
+}
+
+// what the build leaves on the device becomes P's: out of `m`, into P.dev, and under the names the model and the CSV writer read
+struct Result {
+    int64_t NS, R, NT;
+    int n_rep;
+    float *X;
+    uint8_t *site_kmers;
+    int64_t *off;
+    float *read_prob, *site_prob;
+    double *mod_ratio;
+    const uint32_t *site_tx;
+    const int64_t *site_pos;
+    const uint8_t *site_k7;
+    const double *ids;
+    const int32_t *parts;                   // several files, else null
+    const uint8_t *names;                   // --read_names, else null
+    const int64_t *name_off;
+};
+
+void publish(m6a_prep_sites &P, DevMem &m, const Result &r)
+{
+    for (const void *p : std::initializer_list<const void *>{r.X, r.site_kmers, r.off, r.read_prob, r.site_prob, r.mod_ratio, r.site_tx, r.site_pos,
+                                                             r.site_k7, r.ids, r.parts, r.names, r.name_off}) {
+        if (!p) continue;
+        P.held += m.size_of(p);
+        m.detach(p);
+        P.dev.push_back((void *)p);
+    }
+    P.csv_tx = r.site_tx; P.csv_pos = r.site_pos; P.csv_k7 = r.site_k7; P.csv_ids = r.ids; P.csv_parts = r.parts;
+    P.csv_names = r.names; P.csv_name_off = r.name_off;
+    m6a_prep_sites_info &I = P.info;
+    I.n_sites = r.NS; I.n_reads = r.R; I.n_tx = r.NT;
+    I.X = r.X; I.site_kmers = r.site_kmers; I.off = r.off; I.read_prob = r.read_prob; I.site_prob = r.site_prob; I.mod_ratio = r.mod_ratio;
+    I.off_host = P.off.data(); I.site_tx = P.tx.data(); I.site_pos = P.pos.data(); I.site_kmer7 = P.k7.data();
+    I.tx_blob = P.blob.data(); I.tx_off = P.tx_off.data(); I.read_ids = P.ids.data();
+    I.n_rep = r.n_rep; I.read_rep = P.rep.data();
+}
+
+// One file's back half: what its stages hand on, in their order.  Everything on the device is in `m`.
+struct Back {
+    const char *path;
+    int rmin, rmax, n_threads;
+    const m6a_prep_host_half *host;
+    m6a_prep_sites &P;
+    DevMem &m;
+    Streams S;
+    Fd fd;
+    Front F;
+    hipStream_t s = nullptr;
+    double fms[6] = {0, 0, 0, 0, 0, 0}, dev_ms = 0, host_ms = 0, t1 = 0;    // t1: when the device part now running began
+    int64_t NR = 0, NROW = 0;
+    std::string blob;                       // this file's transcript names, in order of first appearance
+    std::vector<int64_t> tx_off;
+    // segments_to_host
+    int64_t *sx = nullptr, *dx = nullptr, NSEG = 0, n_names = 0;
+    uint8_t *dnames = nullptr;              // [n_names][16] --read_names: the file's table of names
+    SegDev *seg = nullptr;
+    std::vector<SegDev> hseg;
+    std::vector<DeclDev> hdecl;
+    // host_part
+    std::vector<SegUp> up;
+    std::vector<DeclUp> dup;                // the declined runs the host half combined, and their rows
+    std::vector<int64_t> hpos, hrun;
+    std::vector<uint8_t> hkmer;
+    std::vector<double> hfeat;
+    int64_t lim = 0, NT = 0, NH = 0;
+    // place_runs
+    RowSrc rs{};
+    uint32_t *run_tx = nullptr;
+    int64_t *run_place = nullptr, *dhrun = nullptr;
+    uint8_t *used = nullptr;
+    unsigned long long *mm = nullptr;
+    // sort_rows
+    uint32_t *L = nullptr, *L2 = nullptr, *row_run = nullptr;
+    uint64_t *k1 = nullptr, *k2 = nullptr;
+    int64_t NL = 0;
+    // cut_sites
+    int64_t *shx = nullptr, *start = nullptr, *kx = nullptr, *src = nullptr, *doff = nullptr, NS = 0, R = 0;
+    unsigned long long *bad = nullptr;
+    Back(const char *path_, int rmin_, int rmax_, const m6a_prep_host_half *host_, int n_threads_, m6a_prep_sites &P_, DevMem &m_)
+        : path(path_), rmin(rmin_), rmax(rmax_), n_threads(n_threads_), host(host_), P(P_), m(m_) {}
+    const char *tx_name(uint32_t t) const { return blob.data() + tx_off[t]; }
+    int tx_len(uint32_t t) const { return (int)(tx_off[t + 1] - tx_off[t]); }
+    int64_t seg_of(int64_t run) const       // the segment that holds the run
+    {
+        return (int64_t)(std::upper_bound(hseg.begin(), hseg.end(), run, [](int64_t r, const SegDev &x) { return r < x.first; }) - hseg.begin()) - 1;
+    }
+};
+
+// ---- read names interned; segments and declined runs, to the host (with the name table under read_names)
+int segments_to_host(Back &B)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    const int64_t NR = B.NR;
+    const bool read_names = B.P.read_names;
+    int rc;
+    Intern in;
+    double t_in = now_ms();
+    if (read_names && (rc = intern_runs(m, s, B.F.runs, B.F.rnames, NR, in))) return rc;   // from here on RunDev.read is the twin's read index
+    if (read_names) B.P.ms_intern += now_ms() - t_in;
+    int64_t ND = 0;
+    if ((rc = m.alloc(B.sx, (size_t)NR + 1, "segments")) || (rc = m.alloc(B.dx, (size_t)NR + 1, "declined runs"))) return rc;
+    if ((rc = launch(run_flags_kernel, NR, s, B.F.runs, NR, B.sx, B.dx))) return rc;
+    if ((rc = read_names ? scan_total_and_names(m, B.sx, NR, s, B.NSEG, in, B.n_names) : scan_total(m, B.sx, NR, s, B.NSEG)) ||
+        (rc = scan_total(m, B.dx, NR, s, ND)))
+        return rc;
+    if (read_names) {                                       // the table: one copy of 16 bytes per name comes to the host
+        t_in = now_ms();
+        if ((rc = m.alloc(B.dnames, (size_t)B.n_names * 16, "read names"))) return rc;
+        if ((rc = launch(name_table_kernel, NR, s, in.val, NR, in.gx, in.rank, B.F.rnames, B.n_names, B.dnames))) return rc;
+        const size_t at = B.P.names16.size();
+        B.P.names16.resize(at + (size_t)B.n_names * 16);
+        if ((rc = d2h(B.P.names16.data() + at, B.dnames, (size_t)B.n_names * 16, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        B.P.name_off.push_back(B.P.name_off.back() + B.n_names);
+        m.release({in.val, in.gx, in.rank, B.F.rnames});
+        B.P.ms_intern += now_ms() - t_in;
+    }
+    DeclDev *decl;
+    if ((rc = m.alloc(B.seg, (size_t)B.NSEG + 1, "segments")) || (rc = m.alloc(decl, (size_t)ND + 1, "declined runs"))) return rc;
+    if ((rc = launch(run_lists_kernel, NR, s, B.F.runs, NR, B.sx, B.dx, B.seg, decl))) return rc;
+    B.hseg.resize((size_t)B.NSEG);
+    B.hdecl.resize((size_t)ND);
+    if ((rc = d2h(B.hseg.data(), B.seg, (size_t)B.NSEG, s)) || (rc = d2h(B.hdecl.data(), decl, (size_t)ND, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    return M6A_OK;
+}
+
+// the transcript names of the segments (from the file where the contig changes; from the text or the saved heads where the bytes are
+// on the device), every segment's transcript, the rank of its first run in it and the readcount verdict
+int name_segments(Back &B)
+{
+    const Front &F = B.F;
+    const int64_t NSEG = B.NSEG;
+    int rc;
+    std::vector<uint8_t> packed;                            // the contig bytes of all segments, from the device
+    const bool resident = F.text || F.stream;
+    if (resident) {
+        std::vector<int64_t> src((size_t)NSEG), len((size_t)NSEG);
+        int64_t sum = 0;                                    // a stream: the heads were saved in run order, so segment g's lie at the running sum
+        for (int64_t g = 0; g < NSEG; g++) {
+            src[(size_t)g] = F.stream ? sum : B.hseg[(size_t)g].contig;
+            len[(size_t)g] = B.hseg[(size_t)g].len;
+            sum += B.hseg[(size_t)g].len;
+        }
+        if (F.stream && sum != F.n_heads) return prep_fail(M6A_EHIP, "the saved contig names of %s do not add up", B.path);
+        if ((rc = F.stream ? bgzf_gather(B.m, B.s, F.heads, F.n_heads, src, len, packed) : bgzf_gather(B.m, B.s, F.text, F.n, src, len, packed))) return rc;
+    }
+    Interner tx(B.blob, B.tx_off);
+    std::vector<int64_t> tx_runs;
+    std::string nm;
+    B.up.resize((size_t)NSEG);
+    for (int64_t g = 0, at = 0; g < NSEG; g++) {
+        const SegDev &G = B.hseg[(size_t)g];
+        nm.resize((size_t)G.len);
+        if (resident) {
+            memcpy(&nm[0], packed.data() + at, (size_t)G.len);
+            at += G.len;
+        } else if ((rc = read_fully(B.fd.fd, &nm[0], G.len, G.contig, B.path)))
+            return rc;
+        const uint32_t t = tx.id(nm);
+        if (t == tx_runs.size()) tx_runs.push_back(0);
+        const int64_t len = (g + 1 < NSEG ? B.hseg[(size_t)g + 1].first : B.NR) - G.first;
+        B.up[(size_t)g].rank0 = tx_runs[t];
+        B.up[(size_t)g].tx = t;
+        tx_runs[t] += len;
+    }
+    B.tx_off.push_back((int64_t)B.blob.size());
+    B.NT = (int64_t)tx_runs.size();
+    B.lim = std::max(0, B.rmax);                            // `if ++readcount > readcount_max: break` after the first run
+    for (SegUp &u : B.up) u.keep = std::min(tx_runs[u.tx], B.lim + 1) >= B.rmin;
+    return M6A_OK;
+}
+
+// the declined runs the host loop reaches, combined and windowed by the host half: their npos (dup) and their rows (hpos, ...)
+int host_half_rows(Back &B)
+{
+    const Front &F = B.F;
+    int rc;
+    std::vector<int64_t> cstart, cend, cread, crun;
+    std::vector<int64_t> csaved;                            // a stream: where the run's bytes lie among the saved ones
+    int64_t saved_at = 0;
+    for (const DeclDev &d : B.hdecl) {
+        const int64_t at_saved = saved_at;
+        saved_at += d.end - d.start;
+        const int64_t g = B.seg_of(d.run);
+        if (B.up[(size_t)g].rank0 + (d.run - B.hseg[(size_t)g].first) > B.lim) continue;
+        cstart.push_back(d.start); cend.push_back(d.end); cread.push_back(d.read); crun.push_back(d.run);
+        csaved.push_back(at_saved);
+    }
+    if (F.stream && saved_at != F.n_declined) return prep_fail(M6A_EHIP, "the saved declined runs of %s do not add up", B.path);
+    if (crun.empty()) return M6A_OK;
+    const m6a_prep_host_half *host = B.host;
+    if (!host || !host->rows || !host->table || !host->free)
+        return prep_fail(M6A_EINVAL, "%zu runs need the host half and none was given", crun.size());
+    struct m6a_io_rows *hr = nullptr;
+    // BGZF input or a stream: the host half takes a path, so it gets the declined runs laid end to end in a plain temporary file
+    struct Tmp { std::string path; ~Tmp() { if (!path.empty()) ::unlink(path.c_str()); } } tmp;
+    const bool resident = F.text || F.stream;
+    if (resident) {
+        std::vector<uint8_t> packed;
+        std::vector<int64_t> len(crun.size());
+        for (size_t i = 0; i < crun.size(); i++) len[i] = cend[i] - cstart[i];
+        if ((rc = F.stream ? bgzf_gather(B.m, B.s, F.declined, F.n_declined, csaved, len, packed) : bgzf_gather(B.m, B.s, F.text, F.n, cstart, len, packed)))
+            return rc;
+        const char *dir = getenv("TMPDIR");
+        std::string name = std::string(dir && *dir ? dir : "/tmp") + "/m6a_declined_XXXXXX";
+        const int tfd = ::mkstemp(&name[0]);
+        if (tfd < 0) return prep_fail(M6A_EIO, "cannot create a temporary file for the declined runs of %s", B.path);
+        tmp.path = name;
+        rc = write_fully(tfd, packed.data(), packed.size(), name.c_str());
+        ::close(tfd);
+        if (rc) return rc;
+        for (size_t i = 0, at = 0; i < crun.size(); i++) { cstart[i] = (int64_t)at; at += (size_t)len[i]; cend[i] = (int64_t)at; }
+    }
+    const int hrc = host->rows(resident ? tmp.path.c_str() : B.path, (int64_t)crun.size(), cstart.data(), cend.data(), cread.data(), 1, B.n_threads, &hr);
+    if (hrc != 0 || !hr) {                                  // its own code and text (m6a_io's -1..-4 -> M6A_EINVAL, ENOMEM, EIO, EFORMAT)
+        const int code = hrc == -2 ? M6A_ENOMEM : hrc == -3 ? M6A_EIO : hrc == -4 ? M6A_EFORMAT : hrc == -1 ? M6A_EINVAL : M6A_EIO;
+        return prep_fail(code, "%s", host->error ? host->error() : "the host half failed on the declined runs");
+    }
+    struct Guard { const m6a_prep_host_half *h; struct m6a_io_rows *r; ~Guard() { h->free(r); } } guard{host, hr};
+    const m6a_io_prep_table *T = host->table(hr);
+    if (!T || T->n_runs != (int64_t)crun.size() || T->n_neighbors != 1) return prep_fail(M6A_EINVAL, "the host half returned a bad table");
+    for (size_t i = 0; i < crun.size(); i++) {
+        if (T->run_status[i] != M6A_PREP_RUN_OK) {
+            const uint32_t t = B.up[(size_t)B.seg_of(crun[i])].tx;
+            return prep_fail(M6A_EFORMAT, "malformed eventalign line for %.*s", B.tx_len(t), B.tx_name(t));
+        }
+        B.dup.push_back(DeclUp{crun[i], T->run_npos[i]});
+        for (int64_t k = T->row_off[i]; k < T->row_off[i + 1]; k++) {
+            B.hpos.push_back(T->row_pos[k]);
+            B.hkmer.insert(B.hkmer.end(), T->row_kmer + k * 7, T->row_kmer + k * 7 + 7);
+            B.hfeat.insert(B.hfeat.end(), T->row_feat + k * 9, T->row_feat + k * 9 + 9);
+            B.hrun.push_back(crun[i]);
+        }
+    }
+    return M6A_OK;
+}
+
+// ---- the host: transcript names, ranks, the readcount verdict, declined runs
+int host_part(Back &B)
+{
+    int rc;
+    if ((rc = name_segments(B)) || (rc = host_half_rows(B))) return rc;
+    B.m.release({B.F.text, B.F.heads, B.F.declined});       // names and declined runs are on the host: X needs the room
+    B.NH = (int64_t)B.hpos.size();
+    if (B.NROW + B.NH > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate rows");
+    return M6A_OK;
+}
+
+// ---- runs: used or not, and their place
+int place_runs(Back &B)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    const int64_t NR = B.NR, NH = B.NH;
+    RunDev *runs = B.F.runs;
+    int rc;
+    SegUp *dup_seg;
+    DeclUp *ddecl;
+    int64_t *dhpos;
+    uint8_t *dhkmer;
+    double *dhfeat;
+    if ((rc = m.alloc(dup_seg, (size_t)B.NSEG + 1, "segments")) || (rc = m.alloc(ddecl, B.dup.size() + 1, "declined runs")) ||
+        (rc = m.alloc(dhpos, (size_t)NH + 1, "host rows")) || (rc = m.alloc(B.dhrun, (size_t)NH + 1, "host rows")) ||
+        (rc = m.alloc(dhkmer, (size_t)NH * 7 + 1, "host rows")) || (rc = m.alloc(dhfeat, (size_t)NH * 9 + 1, "host rows")))
+        return rc;
+    if ((rc = h2d(dup_seg, B.up.data(), B.up.size(), s)) || (rc = h2d(ddecl, B.dup.data(), B.dup.size(), s)) ||
+        (rc = h2d(dhpos, B.hpos.data(), B.hpos.size(), s)) || (rc = h2d(B.dhrun, B.hrun.data(), B.hrun.size(), s)) ||
+        (rc = h2d(dhkmer, B.hkmer.data(), B.hkmer.size(), s)) || (rc = h2d(dhfeat, B.hfeat.data(), B.hfeat.size(), s)))
+        return rc;
+    if ((rc = launch(decl_patch_kernel, (int64_t)B.dup.size(), s, runs, ddecl, (int64_t)B.dup.size()))) return rc;
+    B.rs = RowSrc{B.F.row_pos, dhpos, B.F.row_kmer, dhkmer, B.F.row_feat, dhfeat, B.NROW};
+    int64_t *run_rank, *elig, NE = 0;
+    if ((rc = m.alloc(B.run_tx, (size_t)NR + 1, "runs")) || (rc = m.alloc(run_rank, (size_t)NR + 1, "runs")) || (rc = m.alloc(elig, (size_t)NR + 1, "runs")))
+        return rc;
+    if ((rc = launch(run_select_kernel, NR, s, runs, NR, B.sx, B.seg, dup_seg, B.lim, B.run_tx, run_rank, elig))) return rc;
+    if ((rc = scan_total(m, elig, NR, s, NE))) return rc;
+    uint64_t *k1, *k2;
+    uint32_t *E, *E2;
+    if ((rc = m.alloc(k1, (size_t)NE + 1, "runs")) || (rc = m.alloc(k2, (size_t)NE + 1, "runs")) || (rc = m.alloc(E, (size_t)NE + 1, "runs")) ||
+        (rc = m.alloc(E2, (size_t)NE + 1, "runs")))
+        return rc;
+    unsigned long long hmm[2] = {kNone, 0};
+    if ((rc = m.alloc(B.mm, 2, "flags"))) return rc;
+    if ((rc = launch(compact_u32_kernel, NR, s, elig, NR, E))) return rc;
+    if (NE) {
+        PCHK(hipMemcpyAsync(B.mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
+        if ((rc = launch(minmax_kernel, NE, s, E, NE, 0, runs, B.rs, B.mm)) || (rc = d2h(hmm, B.mm, 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        // (transcript, read): the read is the less significant
+        const int bits[2] = {bits_for(hmm[1] - hmm[0]), bits_for((uint64_t)std::max<int64_t>(B.NT - 1, 0))};
+        rc = sort_by_fields(m, s, bits, 2, k1, E, k2, E2, NE, [&](unsigned use, const int *shift) {
+            return launch(run_key_kernel, NE, s, E, NE, runs, B.run_tx, hmm[0], shift[1], use, k1);
+        });
+        if (rc) return rc;
+    }
+    int64_t *gx, *gfirst, NG = 0;
+    if ((rc = m.alloc(B.used, (size_t)NR + 1, "runs")) || (rc = m.alloc(B.run_place, (size_t)NR + 1, "runs")) || (rc = m.alloc(gx, (size_t)NE + 2, "runs")))
+        return rc;
+    PCHK(hipMemsetAsync(B.used, 0, (size_t)NR + 1, s));
+    if ((rc = launch(dup_head_kernel, NE, s, E, NE, runs, B.run_tx, gx))) return rc;
+    if ((rc = scan_total(m, gx, NE, s, NG))) return rc;
+    if ((rc = m.alloc(gfirst, (size_t)NG + 1, "runs"))) return rc;
+    if ((rc = launch(dup_first_kernel, NE, s, E, NE, gx, run_rank, gfirst)) || (rc = launch(dup_last_kernel, NE, s, E, NE, gx, gfirst, B.used, B.run_place)))
+        return rc;
+    PCHK(hipStreamSynchronize(s));
+    m.release({k1, k2, E, E2, gx, gfirst, elig, B.sx, B.dx});
+    return M6A_OK;
+}
+
+// ---- rows of the used runs, sorted by (transcript, position, place)
+int sort_rows(Back &B)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    const int64_t NR = B.NR, NH = B.NH;
+    int rc;
+    int64_t *rx, NL0 = 0, *hx, NLH = 0;
+    if ((rc = m.alloc(rx, (size_t)NR + 1, "rows")) || (rc = m.alloc(hx, (size_t)NH + 1, "rows"))) return rc;
+    if ((rc = launch(used_rows_count_kernel, NR, s, B.used, B.F.row_off, NR, rx))) return rc;
+    if ((rc = scan_total(m, rx, NR, s, NL0))) return rc;
+    if ((rc = launch(host_flag_kernel, NH, s, B.used, B.dhrun, NH, hx))) return rc;
+    if ((rc = scan_total(m, hx, NH, s, NLH))) return rc;
+    const int64_t NL = B.NL = NL0 + NLH;
+    if ((rc = m.alloc(B.L, (size_t)NL + 1, "rows")) || (rc = m.alloc(B.L2, (size_t)NL + 1, "rows")) ||
+        (rc = m.alloc(B.row_run, (size_t)(B.NROW + NH) + 1, "rows")) || (rc = m.alloc(B.k1, (size_t)NL + 1, "rows")) ||
+        (rc = m.alloc(B.k2, (size_t)NL + 1, "rows")))
+        return rc;
+    if ((rc = launch(used_rows_write_kernel, NR, s, B.used, B.F.row_off, NR, rx, B.L, B.row_run)) ||
+        (rc = launch(host_rows_kernel, NH, s, B.dhrun, NH, B.NROW, NL0, hx, B.L, B.row_run)))
+        return rc;
+    if (!NL) return M6A_OK;
+    unsigned long long hmm[2] = {kNone, 0};
+    PCHK(hipMemcpyAsync(B.mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
+    if ((rc = launch(minmax_kernel, NL, s, B.L, NL, 1, B.F.runs, B.rs, B.mm)) || (rc = d2h(hmm, B.mm, 2, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    // place, position, transcript: least significant first
+    const int bits[3] = {bits_for((uint64_t)B.lim), bits_for(hmm[1] - hmm[0]), bits_for((uint64_t)std::max<int64_t>(B.NT - 1, 0))};
+    return sort_by_fields(m, s, bits, 3, B.k1, B.L, B.k2, B.L2, NL, [&](unsigned use, const int *shift) {
+        const RowKey key{hmm[0], shift[2], shift[1], shift[0], (use & 4 ? 1u : 0u) | (use & 2) | (use & 1 ? 4u : 0u)};
+        return launch(row_key_kernel, NL, s, B.L, NL, B.rs, B.row_run, B.run_tx, B.run_place, key, B.k1);
+    });
+}
+
+// ---- sites: cut, checked, filtered -- kept with at least `need` reads
+int cut_sites(Back &B, int64_t need)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    const int64_t NL = B.NL;
+    int rc;
+    int64_t NS0 = 0;
+    if ((rc = m.alloc(B.shx, (size_t)NL + 1, "sites"))) return rc;
+    if ((rc = launch(site_head_kernel, NL, s, B.L, NL, B.rs, B.row_run, B.run_tx, B.shx))) return rc;
+    if ((rc = scan_total(m, B.shx, NL, s, NS0))) return rc;
+    unsigned long long hbad = kNone;
+    if ((rc = m.alloc(B.start, (size_t)NS0 + 1, "sites")) || (rc = m.alloc(B.kx, (size_t)NS0 + 1, "sites")) || (rc = m.alloc(B.bad, 1, "flags"))) return rc;
+    PCHK(hipMemcpyAsync(B.bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
+    if ((rc = launch(site_start_kernel, NL, s, B.shx, NL, B.start)) || (rc = launch(site_check_kernel, NL, s, B.L, NL, B.rs, B.shx, B.start, B.bad)))
+        return rc;
+    if ((rc = fetch(hbad, B.bad, s))) return rc;
+    if (hbad != ~0ull) {
+        int64_t *probe, hp[2] = {0, 0};
+        if ((rc = m.alloc(probe, 2, "flags"))) return rc;
+        probe_kernel<<<1, 1, 0, s>>>(B.L, B.start, (int64_t)hbad, B.rs, B.row_run, B.run_tx, probe);
+        PCHK(hipGetLastError());
+        if ((rc = d2h(hp, probe, 2, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        return prep_fail(M6A_EFORMAT, "reads disagree on the sequence at %.*s:%lld", B.tx_len((uint32_t)hp[0]), B.tx_name((uint32_t)hp[0]), (long long)hp[1]);
+    }
+    if ((rc = launch(site_keep_kernel, NS0, s, B.start, NS0, need, B.kx))) return rc;
+    if ((rc = scan_total(m, B.kx, NS0, s, B.NS))) return rc;
+    if ((rc = m.alloc(B.src, (size_t)B.NS + 1, "sites")) || (rc = m.alloc(B.doff, (size_t)B.NS + 1, "the offsets"))) return rc;
+    PCHK(hipMemsetAsync(B.doff + B.NS, 0, sizeof(int64_t), s));
+    if ((rc = launch(site_emit_kernel, NS0, s, B.start, NS0, B.kx, B.src, B.doff))) return rc;
+    return scan_total(m, B.doff, B.NS, s, B.R);
+}
+
+// dataprep: no normalisation, no vocabulary, and text instead of X
+int finish_dataprep(Back &B, const DataprepJob &job)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    const int64_t NS = B.NS;
+    int rc;
+    uint32_t *jtx;
+    int64_t *jpos;
+    uint8_t *jk7, *jkm;
+    int32_t *jnorm;
+    if ((rc = m.alloc(jtx, (size_t)NS + 1, "sites")) || (rc = m.alloc(jpos, (size_t)NS + 1, "sites")) || (rc = m.alloc(jk7, (size_t)NS * 7 + 1, "sites")) ||
+        (rc = m.alloc(jkm, (size_t)NS * 3 + 1, "sites")) || (rc = m.alloc(jnorm, (size_t)NS * 3 + 1, "sites")))
+        return rc;
+    if ((rc = launch(site_info_kernel, NS, s, B.L, B.src, NS, B.rs, B.row_run, B.run_tx, nullptr, nullptr, 0, nullptr, 0, jnorm, jkm, jtx, jpos, jk7,
+                     B.bad, nullptr, 1)))
+        return rc;
+    PCHK(hipStreamSynchronize(s));
+    m.release({jkm, jnorm, B.k1, B.k2, B.L2, B.shx, B.start, B.kx});
+    B.dev_ms += now_ms() - B.t1;
+    job.st->ms_front = B.fms[0] + B.fms[1] + B.fms[2];
+    job.st->ms_back = B.dev_ms + B.host_ms;
+    const DataprepSrc ds{JsonDev{B.L, B.src, B.doff, B.rs, B.row_run, B.F.runs, jtx, jpos, jk7, nullptr, nullptr, 0}, B.run_tx, NS, B.NR, B.NL, B.NT,
+                         &B.blob, &B.tx_off};
+    return dataprep_emit(m, s, job, ds);
+}
+
+// normalisation and vocabulary of the kept sites (site_info_kernel), for finish_part and finish_single
+struct SiteInfo {
+    int32_t *site_norm;
     double *dmean, *dstd;
     uint32_t *site_tx;
     int64_t *site_pos;
     uint8_t *site_k7, *site_kmers;
+};
+
+// tx_map (one replicate of several): this file's transcript ids -> the job's, and the checks wait for the pooled sites
+int site_info(Back &B, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm, const std::vector<uint32_t> *tx_map, SiteInfo &I)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    const int64_t NS = B.NS;
+    int rc;
+    std::vector<uint64_t> nk, voc = vocab_keys();
+    std::vector<int32_t> nix;
+    norm_keys(norm_kmers, n_norm, nk, nix);
+    uint64_t *dnk, *dvoc;
+    int32_t *dnix;
     if ((rc = m.alloc(dnk, nk.size() + 1, "norm")) || (rc = m.alloc(dnix, nix.size() + 1, "norm")) || (rc = m.alloc(dvoc, voc.size(), "norm")) ||
-        (rc = m.alloc(dmean, (size_t)n_norm * 3 + 1, "norm")) || (rc = m.alloc(dstd, (size_t)n_norm * 3 + 1, "norm")) ||
-        (rc = m.alloc(site_norm, (size_t)NS * 3 + 1, "sites")) || (rc = m.alloc(site_tx, (size_t)NS + 1, "sites")) ||
-        (rc = m.alloc(site_pos, (size_t)NS + 1, "sites")) || (rc = m.alloc(site_k7, (size_t)NS * 7 + 1, "sites")) ||
-        (rc = m.alloc(site_kmers, (size_t)NS * 3 + 1, "site k-mers")))
+        (rc = m.alloc(I.dmean, (size_t)n_norm * 3 + 1, "norm")) || (rc = m.alloc(I.dstd, (size_t)n_norm * 3 + 1, "norm")) ||
+        (rc = m.alloc(I.site_norm, (size_t)NS * 3 + 1, "sites")) || (rc = m.alloc(I.site_tx, (size_t)NS + 1, "sites")) ||
+        (rc = m.alloc(I.site_pos, (size_t)NS + 1, "sites")) || (rc = m.alloc(I.site_k7, (size_t)NS * 7 + 1, "sites")) ||
+        (rc = m.alloc(I.site_kmers, (size_t)NS * 3 + 1, "site k-mers")))
         return rc;
-    uint32_t *dl2g = nullptr;
-    if (pool && ((rc = m.alloc(dl2g, l2g.size() + 1, "transcripts")) || (rc = h2d(dl2g, l2g.data(), l2g.size(), s)))) return rc;
+    uint32_t *dmap = nullptr;
+    if (tx_map && ((rc = m.alloc(dmap, tx_map->size() + 1, "transcripts")) || (rc = h2d(dmap, tx_map->data(), tx_map->size(), s)))) return rc;
     if ((rc = h2d(dnk, nk.data(), nk.size(), s)) || (rc = h2d(dnix, nix.data(), nix.size(), s)) || (rc = h2d(dvoc, voc.data(), voc.size(), s)) ||
-        (rc = h2d(dmean, norm_mean, (size_t)n_norm * 3, s)) || (rc = h2d(dstd, norm_std, (size_t)n_norm * 3, s)))
+        (rc = h2d(I.dmean, norm_mean, (size_t)n_norm * 3, s)) || (rc = h2d(I.dstd, norm_std, (size_t)n_norm * 3, s)))
         return rc;
-    PCHK(hipMemcpyAsync(bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
-    if (NS) {
-        site_info_kernel<<<grid(NS), kBlk, 0, s>>>(L, src, NS, rs, row_run, run_tx, dnk, dnix, (int)nk.size(), dvoc, (int)voc.size(), site_norm,
-                                                   site_kmers, site_tx, site_pos, site_k7, bad, dl2g, pool ? 1 : 0);
-        PCHK(hipGetLastError());
-    }
-    if (pool) {                                             // one replicate of several: X per candidate read, and what pool_impl needs of the sites
-        if (R > 0x7fffffffll) return prep_fail(M6A_EINVAL, "more than 2^31 candidate reads in %s", path);
-        FilePart fp;
-        if ((rc = m.alloc(fp.X, (size_t)R * 9, "X")) || (rc = m.alloc(fp.ids, (size_t)R + 1, "read ids"))) return rc;
-        if (R) {
-            x_kernel<<<grid(R), kBlk, 0, s>>>(L, src, doff, NS, R, rs, row_run, F.runs, site_norm, dmean, dstd, n_norm, fp.X, fp.ids);
-            PCHK(hipGetLastError());
-        }
-        PCHK(hipStreamSynchronize(s));
-        fp.NC = NS; fp.RC = R; fp.tx = site_tx; fp.pos = site_pos; fp.k7 = site_k7; fp.off = doff;
-        fp.names = dnames; fp.n_names = n_names;
-        m.release_since(mark, {fp.X, fp.ids, fp.tx, fp.pos, fp.k7, fp.off, fp.names});
-        pool->parts.push_back(fp);
-        dev_ms += now_ms() - t1;
-        ms[3] = dev_ms; ms[4] = host_ms; ms[5] = 0; ms[7] = now_ms() - t_all;
-        return M6A_OK;
-    }
-    P.off.resize((size_t)NS + 1);
-    P.tx.resize((size_t)NS);
-    P.pos.resize((size_t)NS);
-    P.k7.resize((size_t)NS * 7);
-    unsigned long long hb2 = kNone;
-    if ((rc = d2h(&hb2, bad, 1, s)) || (rc = d2h(P.off.data(), doff, (size_t)NS + 1, s)) || (rc = d2h(P.tx.data(), site_tx, (size_t)NS, s)) ||
-        (rc = d2h(P.pos.data(), site_pos, (size_t)NS, s)) || (rc = d2h((uint8_t *)P.k7.data(), site_k7, (size_t)NS * 7, s)))
+    PCHK(hipMemcpyAsync(B.bad, &kNone, sizeof kNone, hipMemcpyHostToDevice, s));
+    return launch(site_info_kernel, NS, s, B.L, B.src, NS, B.rs, B.row_run, B.run_tx, dnk, dnix, (int)nk.size(), dvoc, (int)voc.size(), I.site_norm,
+                  I.site_kmers, I.site_tx, I.site_pos, I.site_k7, B.bad, dmap, tx_map ? 1 : 0);
+}
+
+// one replicate of several: X per candidate read, and what pool_impl needs of the sites, stay as a FilePart; the rest of the file goes
+int finish_part(Back &B, Pool &pool, size_t mark, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    int rc;
+    std::vector<uint32_t> l2g;                              // this file's transcript ids -> the job's
+    for (int64_t t = 0; t < B.NT; t++) l2g.push_back(pool.tx.id(std::string(B.tx_name((uint32_t)t), (size_t)B.tx_len((uint32_t)t))));
+    SiteInfo I;
+    if ((rc = site_info(B, norm_kmers, norm_mean, norm_std, n_norm, &l2g, I))) return rc;
+    if (B.R > 0x7fffffffll) return prep_fail(M6A_EINVAL, "more than 2^31 candidate reads in %s", B.path);
+    FilePart fp;
+    if ((rc = m.alloc(fp.X, (size_t)B.R * 9, "X")) || (rc = m.alloc(fp.ids, (size_t)B.R + 1, "read ids"))) return rc;
+    if ((rc = launch(x_kernel, B.R, s, B.L, B.src, B.doff, B.NS, B.R, B.rs, B.row_run, B.F.runs, I.site_norm, I.dmean, I.dstd, n_norm, fp.X, fp.ids)))
         return rc;
     PCHK(hipStreamSynchronize(s));
-    if (hb2 != ~0ull) {
-        const int64_t bs = (int64_t)(hb2 >> 3), what = (int64_t)(hb2 & 7);
-        const char *k = P.k7.data() + bs * 7;
-        if (what < 3) return prep_fail(M6A_EFORMAT, "no normalisation factors for %.5s", k + what);
-        const uint32_t t = P.tx[(size_t)bs];
-        return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", (int)(tx_off[t + 1] - tx_off[t]), blob.data() + tx_off[t],
-                         (long long)P.pos[(size_t)bs], k);
-    }
+    fp.NC = B.NS; fp.RC = B.R; fp.tx = I.site_tx; fp.pos = I.site_pos; fp.k7 = I.site_k7; fp.off = B.doff;
+    fp.names = B.dnames; fp.n_names = B.n_names;
+    m.release_since(mark, {fp.X, fp.ids, fp.tx, fp.pos, fp.k7, fp.off, fp.names});
+    pool.parts.push_back(fp);
+    B.dev_ms += now_ms() - B.t1;
+    return M6A_OK;
+}
+
+// the whole job (m6a_prep_sites_build): P filled
+int finish_single(Back &B, const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm, double *ms)
+{
+    DevMem &m = B.m;
+    hipStream_t s = B.s;
+    m6a_prep_sites &P = B.P;
+    const int64_t NS = B.NS, R = B.R;
+    int rc;
+    P.blob.swap(B.blob);                                    // the file's names are the job's
+    P.tx_off.swap(B.tx_off);
+    SiteInfo I;
+    if ((rc = site_info(B, norm_kmers, norm_mean, norm_std, n_norm, nullptr, I))) return rc;
+    P.off.resize((size_t)NS + 1); P.tx.resize((size_t)NS); P.pos.resize((size_t)NS); P.k7.resize((size_t)NS * 7);
+    unsigned long long hbad = kNone;
+    if ((rc = d2h(&hbad, B.bad, 1, s)) || (rc = d2h(P.off.data(), B.doff, (size_t)NS + 1, s)) || (rc = d2h(P.tx.data(), I.site_tx, (size_t)NS, s)) ||
+        (rc = d2h(P.pos.data(), I.site_pos, (size_t)NS, s)) || (rc = d2h((uint8_t *)P.k7.data(), I.site_k7, (size_t)NS * 7, s)))
+        return rc;
+    PCHK(hipStreamSynchronize(s));
+    if (hbad != ~0ull) return bad_site(P, hbad, false);
     float *X;
     double *dids;
     if ((rc = m.alloc(X, (size_t)R * 9, "X")) || (rc = m.alloc(dids, (size_t)R + 1, "read ids"))) return rc;
-    if (R) {
-        x_kernel<<<grid(R), kBlk, 0, s>>>(L, src, doff, NS, R, rs, row_run, F.runs, site_norm, dmean, dstd, n_norm, X, dids);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(x_kernel, R, s, B.L, B.src, B.doff, NS, R, B.rs, B.row_run, B.F.runs, I.site_norm, I.dmean, I.dstd, n_norm, X, dids))) return rc;
     P.ids.resize((size_t)R);
     PCHK(hipStreamSynchronize(s));
-    dev_ms += now_ms() - t1;
-    t1 = now_ms();
+    B.dev_ms += now_ms() - B.t1;
+    const double t1 = now_ms();
     if ((rc = d2h(P.ids.data(), dids, (size_t)R, s))) return rc;
     PCHK(hipStreamSynchronize(s));
     ms[5] = now_ms() - t1;
@@ -2789,27 +2787,56 @@ int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg,
         (rc = m.alloc(mr, (size_t)NS, "mod ratios")))
         return rc;
     int64_t *dname_off = nullptr;
-    if (read_names) {
+    if (P.read_names) {
         if ((rc = m.alloc(dname_off, 2, "read names")) || (rc = h2d(dname_off, P.name_off.data(), 2, s))) return rc;
         PCHK(hipStreamSynchronize(s));
     }
-    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr,
-                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids, (const void *)dnames,
-                          (const void *)dname_off}) {
-        if (!p) continue;
-        P.held += m.size_of(p);
-        m.detach(p);
-        P.dev.push_back((void *)p);
-    }
-    P.csv_tx = site_tx; P.csv_pos = site_pos; P.csv_k7 = site_k7; P.csv_ids = dids; P.csv_names = dnames; P.csv_name_off = dname_off;
-    m6a_prep_sites_info &I = P.info;
-    I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
-    I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
-    I.off_host = P.off.data(); I.site_tx = P.tx.data(); I.site_pos = P.pos.data(); I.site_kmer7 = P.k7.data();
-    I.tx_blob = blob.data(); I.tx_off = tx_off.data(); I.read_ids = P.ids.data();
     P.rep.assign((size_t)R, 0);
-    I.n_rep = 1; I.read_rep = P.rep.data();
-    ms[3] = dev_ms; ms[4] = host_ms; ms[7] = now_ms() - t_all;
+    publish(P, m, Result{NS, R, B.NT, 1, X, I.site_kmers, B.doff, rp, sp, mr, I.site_tx, I.site_pos, I.site_k7, dids, nullptr, B.dnames, dname_off});
+    return M6A_OK;
+}
+
+// One file.  pool == nullptr and job == nullptr: the whole job (m6a_prep_sites_build), P filled.  pool: the file is one replicate of
+// several -- its sites with >= min_seg reads (the 20-read floor and the per-site checks wait for the pooled sites, pool_impl), their X
+// and read ids stay on the device as a FilePart, and everything else the file needed -- its text, line records, candidate rows -- is
+// released.  job: `dataprep --writer device` (m6a_dataprep.h).
+int sites_impl(int device_id, const char *path, int rmin, int rmax, int min_seg, const char *norm_kmers, const double *norm_mean,
+               const double *norm_std, int n_norm, const m6a_prep_host_half *host, int n_threads, int64_t window, m6a_prep_sites &P, DevMem &m,
+               double *ms, Pool *pool, const DataprepJob *job = nullptr)
+{
+    const double t_all = now_ms();
+    const size_t mark = m.ptrs.size();
+    Back B(path, rmin, rmax, host, n_threads, P, m);
+    Front &F = B.F;
+    F.bgzf_ok = !job;                                       // dataprep's index holds offsets into the text: BGZF and streams stay refused
+    F.read_names = P.read_names;
+    int rc = front_half(device_id, path, 1, nullptr, nullptr, window, m, B.S, B.fd, F, B.fms);
+    if (rc) return rc;
+    P.info.n_bgzf_blocks += F.n_blocks;
+    P.info.compressed_bytes += F.comp_bytes;
+    P.info.ms_inflate += F.ms_inflate;
+    P.info.n_windows += F.n_windows;
+    P.info.window_bytes = std::max(P.info.window_bytes, F.window_bytes);
+    if (F.stream) { P.stream_bytes += F.n; P.n_streams += 1; }
+    ms[0] = B.fms[0]; ms[1] = B.fms[1]; ms[2] = B.fms[2]; ms[6] = B.fms[5];
+    B.s = B.S.s[0];
+    PCHK(hipStreamSynchronize(B.s));
+    for (const void *p : F.scratch) m.release(p);          // the file and its line records: X needs the room
+    B.NR = F.NR; B.NROW = F.NROW;
+    if (B.NR > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 runs");
+
+    B.t1 = now_ms();
+    if ((rc = segments_to_host(B))) return rc;
+    B.dev_ms += now_ms() - B.t1;
+    B.t1 = now_ms();
+    if ((rc = host_part(B))) return rc;
+    B.host_ms += now_ms() - B.t1;
+    B.t1 = now_ms();                                        // the finishes close this interval
+    if ((rc = place_runs(B)) || (rc = sort_rows(B)) || (rc = cut_sites(B, pool || job ? (int64_t)min_seg : std::max<int64_t>(min_seg, 20)))) return rc;
+    if (job) return finish_dataprep(B, *job);
+    if ((rc = pool ? finish_part(B, *pool, mark, norm_kmers, norm_mean, norm_std, n_norm) : finish_single(B, norm_kmers, norm_mean, norm_std, n_norm, ms)))
+        return rc;
+    ms[3] = B.dev_ms; ms[4] = B.host_ms; ms[7] = now_ms() - t_all;
     return M6A_OK;
 }
 
@@ -2968,7 +2995,7 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
     int64_t NC = 0;
     for (const FilePart &fp : pool.parts) NC += fp.NC;
     if (NC > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate sites");
-    const int64_t NT = (int64_t)pool.ids.size();
+    const int64_t NT = (int64_t)pool.tx.ids.size();
     P.tx_off.push_back((int64_t)P.blob.size());
     int rc;
 
@@ -2991,13 +3018,12 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
         PCHK(hipMemcpyAsync(c_tx + base, fp.tx, (size_t)fp.NC * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         PCHK(hipMemcpyAsync(c_pos + base, fp.pos, (size_t)fp.NC * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
         PCHK(hipMemcpyAsync(c_k7 + base * 7, fp.k7, (size_t)fp.NC * 7, hipMemcpyDeviceToDevice, s));
-        cand_fill_kernel<<<grid(fp.NC), kBlk, 0, s>>>(fp.off, fp.NC, base, f, c_src, c_cnt, c_file, val);
-        PCHK(hipGetLastError());
+        if ((rc = launch(cand_fill_kernel, fp.NC, s, fp.off, fp.NC, base, f, c_src, c_cnt, c_file, val))) return rc;
         base += fp.NC;
     }
     PCHK(hipStreamSynchronize(s));
     for (FilePart &fp : pool.parts) {
-        for (const void *p : {(const void *)fp.tx, (const void *)fp.pos, (const void *)fp.k7, (const void *)fp.off}) m.release(p);
+        m.release({fp.tx, fp.pos, fp.k7, fp.off});
         fp.tx = nullptr; fp.pos = fp.off = nullptr; fp.k7 = nullptr;
     }
 
@@ -3006,37 +3032,22 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
     if ((rc = m.alloc(mm, 2, "flags"))) return rc;
     if (NC) {
         PCHK(hipMemcpyAsync(mm, kMinMax0, sizeof kMinMax0, hipMemcpyHostToDevice, s));
-        cand_minmax_kernel<<<grid(NC), kBlk, 0, s>>>(c_pos, NC, mm);
-        PCHK(hipGetLastError());
-        if ((rc = d2h(hmm, mm, 2, s))) return rc;
+        if ((rc = launch(cand_minmax_kernel, NC, s, c_pos, NC, mm)) || (rc = d2h(hmm, mm, 2, s))) return rc;
         PCHK(hipStreamSynchronize(s));
-        const int pb = bits_for(hmm[1] - hmm[0]), tb = bits_for((uint64_t)std::max<int64_t>(NT - 1, 0));
-        // (transcript, position) in one key when it fits, else the position first and the transcript after it (LSD, stable)
-        const unsigned both = (pb ? 1u : 0u) | (tb ? 2u : 0u);
-        const unsigned passes[2] = {pb + tb <= 64 ? both : 1u, pb + tb <= 64 ? 0u : 2u};
-        for (unsigned use : passes) {
-            if (!use) continue;
-            const int bits = (use & 1 ? pb : 0) + (use & 2 ? tb : 0);
-            cand_key_kernel<<<grid(NC), kBlk, 0, s>>>(val, NC, c_tx, c_pos, hmm[0], use & 1 ? pb : 0, use, k1);
-            PCHK(hipGetLastError());
-            if ((rc = radix_sort(m, k1, val, k2, val2, NC, bits, s))) return rc;
-        }
+        // (transcript, position): the position is the less significant
+        const int bits[2] = {bits_for(hmm[1] - hmm[0]), bits_for((uint64_t)std::max<int64_t>(NT - 1, 0))};
+        rc = sort_by_fields(m, s, bits, 2, k1, val, k2, val2, NC, [&](unsigned use, const int *shift) {
+            return launch(cand_key_kernel, NC, s, val, NC, c_tx, c_pos, hmm[0], shift[1], use, k1);
+        });
+        if (rc) return rc;
     }
     int64_t *gx, *gstart, *ux, NG = 0, NU = 0;
     if ((rc = m.alloc(gx, (size_t)NC + 1, "pooled sites")) || (rc = m.alloc(ux, (size_t)NC + 1, "pooled sites"))) return rc;
-    if (NC) {
-        cand_head_kernel<<<grid(NC), kBlk, 0, s>>>(val, NC, c_tx, c_pos, gx);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(cand_head_kernel, NC, s, val, NC, c_tx, c_pos, gx))) return rc;
     if ((rc = scan_total(m, gx, NC, s, NG))) return rc;
     if ((rc = m.alloc(gstart, (size_t)NG + 1, "pooled sites"))) return rc;
     PCHK(hipMemsetAsync(ux, 0, (size_t)(NC + 1) * sizeof(int64_t), s));
-    if (NC) {
-        site_start_kernel<<<grid(NC), kBlk, 0, s>>>(gx, NC, gstart);
-        PCHK(hipGetLastError());
-        group_first_kernel<<<grid(NG), kBlk, 0, s>>>(val, gstart, NG, ux);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(site_start_kernel, NC, s, gx, NC, gstart)) || (rc = launch(group_first_kernel, NG, s, val, gstart, NG, ux))) return rc;
     if ((rc = scan_total(m, ux, NC, s, NU))) return rc;
     if (NU != NG) return prep_fail(M6A_EINVAL, "pooled sites: %lld groups, %lld first members", (long long)NG, (long long)NU);
 
@@ -3045,27 +3056,16 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
     if ((rc = m.alloc(usum, (size_t)NG + 1, "pooled sites")) || (rc = m.alloc(ugrp, (size_t)NG + 1, "pooled sites")) ||
         (rc = m.alloc(kx, (size_t)NG + 1, "pooled sites")))
         return rc;
-    if (NG) {
-        group_sum_kernel<<<grid(NG), kBlk, 0, s>>>(val, gstart, NG, c_cnt, ux, usum, ugrp, kx);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(group_sum_kernel, NG, s, val, gstart, NG, c_cnt, ux, usum, ugrp, kx))) return rc;
     if ((rc = scan_total(m, kx, NG, s, NS))) return rc;
     if ((rc = m.alloc(kgrp, (size_t)NS + 1, "pooled sites")) || (rc = m.alloc(doff, (size_t)NS + 1, "the offsets"))) return rc;
-    if (NG) {
-        pool_emit_kernel<<<grid(NG), kBlk, 0, s>>>(kx, NG, usum, ugrp, doff, kgrp);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(pool_emit_kernel, NG, s, kx, NG, usum, ugrp, doff, kgrp))) return rc;
     if ((rc = scan_total(m, doff, NS, s, R))) return rc;
 
     // ---- per kept site: its arrays, its blocks, its checks
     std::vector<uint64_t> nk, voc = vocab_keys();
-    for (int i = 0; i < n_norm; i++) {
-        uint64_t x = 0;
-        for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)norm_kmers[5 * i + j];
-        nk.push_back(x);
-    }
-    std::sort(nk.begin(), nk.end());
-    nk.erase(std::unique(nk.begin(), nk.end()), nk.end());
+    std::vector<int32_t> nix;                               // not needed here: the files' X is normalised already
+    norm_keys(norm_kmers, n_norm, nk, nix);
     uint64_t *dnk, *dvoc;
     uint32_t *site_tx;
     int64_t *site_pos, *blk_src, *blk_dst;
@@ -3083,11 +3083,9 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
     PCHK(hipMemsetAsync(blk_cnt, 0, (NB + 1) * sizeof(int32_t), s));
     PCHK(hipMemsetAsync(blk_src, 0, (NB + 1) * sizeof(int64_t), s));
     PCHK(hipMemsetAsync(blk_dst, 0, (NB + 1) * sizeof(int64_t), s));
-    if (NS) {
-        pool_site_kernel<<<grid(NS), kBlk, 0, s>>>(val, gstart, kgrp, NS, K, doff, c_tx, c_pos, c_k7, c_src, c_cnt, c_file, dnk, (int)nk.size(), dvoc,
-                                                   (int)voc.size(), site_tx, site_pos, site_k7, site_kmers, blk_src, blk_dst, blk_cnt, bad);
-        PCHK(hipGetLastError());
-    }
+    if ((rc = launch(pool_site_kernel, NS, s, val, gstart, kgrp, NS, K, doff, c_tx, c_pos, c_k7, c_src, c_cnt, c_file, dnk, (int)nk.size(), dvoc,
+                     (int)voc.size(), site_tx, site_pos, site_k7, site_kmers, blk_src, blk_dst, blk_cnt, bad)))
+        return rc;
     P.off.resize((size_t)NS + 1);
     P.tx.resize((size_t)NS);
     P.pos.resize((size_t)NS);
@@ -3098,16 +3096,7 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
         (rc = d2h(cnt.data(), blk_cnt, NB, s)))
         return rc;
     PCHK(hipStreamSynchronize(s));
-    if (hbad != ~0ull) {
-        const int64_t bs = (int64_t)(hbad >> 3), what = (int64_t)(hbad & 7);
-        const char *k = P.k7.data() + bs * 7;
-        if (what < 3) return prep_fail(M6A_EFORMAT, "no normalisation factors for %.5s", k + what);
-        const uint32_t t = P.tx[(size_t)bs];
-        const int len = (int)(P.tx_off[t + 1] - P.tx_off[t]);
-        if (what == 3)
-            return prep_fail(M6A_EFORMAT, "replicates disagree on the sequence of %.*s:%lld", len, P.blob.data() + P.tx_off[t], (long long)P.pos[(size_t)bs]);
-        return prep_fail(M6A_EFORMAT, "site %.*s:%lld: %.7s is not a DRACH context", len, P.blob.data() + P.tx_off[t], (long long)P.pos[(size_t)bs], k);
-    }
+    if (hbad != ~0ull) return bad_site(P, hbad, true);
 
     // ---- the pooled X and read ids
     float *X;
@@ -3156,22 +3145,7 @@ int pool_impl(Pool &pool, const char *norm_kmers, int n_norm, DevMem &m, m6a_pre
         PCHK(hipStreamSynchronize(s));
         for (FilePart &fp : pool.parts) { m.release(fp.names); fp.names = nullptr; }
     }
-    P.csv_names = dnames; P.csv_name_off = dname_off;
-    for (const void *p : {(const void *)X, (const void *)site_kmers, (const void *)doff, (const void *)rp, (const void *)sp, (const void *)mr,
-                          (const void *)site_tx, (const void *)site_pos, (const void *)site_k7, (const void *)dids, (const void *)blk_cnt,
-                          (const void *)dnames, (const void *)dname_off}) {
-        if (!p) continue;
-        P.held += m.size_of(p);
-        m.detach(p);
-        P.dev.push_back((void *)p);
-    }
-    P.csv_tx = site_tx; P.csv_pos = site_pos; P.csv_k7 = site_k7; P.csv_ids = dids; P.csv_parts = blk_cnt;
-    m6a_prep_sites_info &I = P.info;
-    I.n_sites = NS; I.n_reads = R; I.n_tx = NT;
-    I.X = X; I.site_kmers = site_kmers; I.off = doff; I.read_prob = rp; I.site_prob = sp; I.mod_ratio = mr;
-    I.off_host = P.off.data(); I.site_tx = P.tx.data(); I.site_pos = P.pos.data(); I.site_kmer7 = P.k7.data();
-    I.tx_blob = P.blob.data(); I.tx_off = P.tx_off.data(); I.read_ids = P.ids.data();
-    I.n_rep = K; I.read_rep = P.rep.data();
+    publish(P, m, Result{NS, R, NT, K, X, site_kmers, doff, rp, sp, mr, site_tx, site_pos, site_k7, dids, blk_cnt, dnames, dname_off});
     return M6A_OK;
 }
 
@@ -3191,7 +3165,7 @@ int sites_multi(int device_id, const char *const *paths, int n_paths, int rmin, 
         if ((rc = sites_impl(device_id, paths[0], rmin, rmax, min_seg, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, window, P, m, ms, nullptr)))
             return rc;
     } else {
-        Pool pool;
+        Pool pool(P.blob, P.tx_off);
         double bytes = 0;
         for (int f = 0; f < n_paths; f++) {
             double fm[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -1,4 +1,4 @@
-// m6a_stream.h -- eventalign text from a pipe: the reader the stream front half (m6a_prep.hip: front_stream) takes its bytes from.
+// m6a_stream.h -- eventalign text from a pipe: the reader the stream front half (m6a_prep.hip: StreamSource) takes its bytes from.
 // Plain C++ with no HIP in it; tests/stream_core_main.cpp holds it to a seeded buffer delivered through a real pipe() in pieces of
 // every size, as a program of its own under ASan and UBSan.
 //   fill      the caller's buffer gets exactly the bytes asked for, or what there is before the end: read() is looped over short

@@ -97,50 +97,15 @@ __device__ __forceinline__ float relu2(float x)
 //     enc_site16_kernel 2.229 -> 2.201 ms, enc_csite_kernel 2.070 -> 2.035, enc_kernel 2.241 -> 2.213 per 20 M reads (four interleaved
 //     legs, profiles/r06_encoder_ab_phase.json; epilogue 1 or body 1: the same within noise; starting the second wave of a SIMD half a
 //     tile late on top: +0.1-0.3 %, not taken; priorities inside the body -- the fmas above or below the MFMAs -- cost 1 %).
-// Same instructions, same bits.  -DM6A_AB_NO_PRIO / -DM6A_AB_PRIO_BODY=.. -DM6A_AB_PRIO_EPI=.. (tools/encoder_ab.py) build the others.
-#ifndef M6A_AB_PRIO_BODY
-#define M6A_AB_PRIO_BODY 0
-#define M6A_AB_PRIO_EPI 3
-#endif
+// Same instructions, same bits.
 __device__ __forceinline__ void tile_body_priority()
 {
-#ifndef M6A_AB_NO_PRIO
-    __builtin_amdgcn_s_setprio(M6A_AB_PRIO_BODY);
-#endif
+    __builtin_amdgcn_s_setprio(0);
 }
 __device__ __forceinline__ void tile_epilogue_priority()
 {
-#ifndef M6A_AB_NO_PRIO
-    __builtin_amdgcn_s_setprio(M6A_AB_PRIO_EPI);
-#endif
+    __builtin_amdgcn_s_setprio(3);
 }
-#ifdef M6A_AB_PHASE
-#ifndef M6A_AB_PHASE_SLEEP
-#define M6A_AB_PHASE_SLEEP 127
-#endif
-// A/B build only: the second workgroup to arrive on a CU starts its tile loop M6A_AB_PHASE x 8 128 cycles late, so the two waves of a
-// SIMD run half a tile apart (atomicInc wraps 0 -> 1 -> 0: the counter is back at 0 when both have arrived).
-__device__ unsigned m6a_ab_cu_slot[2048];
-__device__ __forceinline__ void phase_shift_second_workgroup()
-{
-#ifdef M6A_AB_PHASE_HWID
-    // the partner by its hardware wave slot: the two waves of a SIMD sit in slots 0 and 1 (tools/encoder_timeline.py: every pair)
-    if (__builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 1)
-        for (int i = 0; i < M6A_AB_PHASE; i++) __builtin_amdgcn_s_sleep(M6A_AB_PHASE_SLEEP);
-    return;
-#endif
-    __shared__ unsigned s_slot;
-    if (threadIdx.x == 0) {
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) & 7;
-        s_slot = atomicInc(&m6a_ab_cu_slot[(xcc << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xf)], 1u);
-    }
-    __syncthreads();
-    if (s_slot)
-        for (int i = 0; i < M6A_AB_PHASE; i++) __builtin_amdgcn_s_sleep(M6A_AB_PHASE_SLEEP);
-}
-#else
-__device__ __forceinline__ void phase_shift_second_workgroup() {}
-#endif
 
 __device__ __forceinline__ void clamp_keeps_nan()
 {
@@ -160,9 +125,7 @@ __device__ __forceinline__ float bn_relu(float y, float alpha, float beta)
 // the 38 loads' latency exposed: 2.135-2.15 ms for the 12-slot kernel against 2.07-2.09 this way, which is what the kernel
 // took with the batch norm folded into the weights; blocks of 8 need 16 registers the 12-slot kernel does not have (spills:
 // 2.25), blocks of 2 measure 2.10.  profiles/r04_encoder_order_timing.txt.)
-#ifndef BN_BLOCK
 #define BN_BLOCK 4
-#endif
 struct BnPairs { float4 v[BN_BLOCK / 2]; };
 __device__ __forceinline__ void bn_pairs_load(BnPairs &pq, const float *p)
 {
@@ -175,77 +138,20 @@ __device__ __forceinline__ void layer2_with_bn(f32x16 &acc2, f32x16 &cur, const 
     constexpr int n = L2_REGS(M), m_next = M < 4 ? M + 1 : 0;
 #pragma unroll
     for (int b = 0; b * BN_BLOCK < n; b++) {
-#ifdef M6A_AB_PRIO_BLOCK_VALU
-        __builtin_amdgcn_s_setprio(M6A_AB_PRIO_BLOCK_VALU);               // A/B build only: the block's fmas at another priority than its MFMAs
-#endif
 #pragma unroll
         for (int i = 0; i < BN_BLOCK / 2; i++) {
             const int q = b * BN_BLOCK + 2 * i;
-#ifdef M6A_AB_BN_PK
-            // A/B build only (tools/encoder_ab.py): two hidden units per VALU instruction -- v_pk_fma_f32 with the clamp modifier on the
-            // register pair (cur[q], cur[q+1]); the kernel's preamble stores the pairs as (alpha, alpha', beta, beta').  Same fmas, same bits.
-            f32x2 y = {cur[q], cur[q + 1]};
-            const f32x2 al = {pq.v[i].x, pq.v[i].y}, be = {pq.v[i].z, pq.v[i].w};
-            asm("v_pk_fma_f32 %0, %0, %1, %2 clamp" : "+v"(y) : "v"(al), "v"(be));
-            cur[q] = y.x;
-            cur[q + 1] = y.y;
-#else
-#ifndef M6A_AB_NO_BN                    // knock-out build only (WRONG results): layer 2 straight on layer 1's accumulators -- no fmas, no pair loads
             cur[q] = bn_relu(cur[q], pq.v[i].x, pq.v[i].y);
             cur[q + 1] = bn_relu(cur[q + 1], pq.v[i].z, pq.v[i].w);
-#endif
-#endif
         }
-#ifndef M6A_AB_NO_BN
         bn_pairs_load(pq, (b + 1) * BN_BLOCK < n ? bn_half + M * 64 + 2 * (b + 1) * BN_BLOCK : bn_half + m_next * 64);
-#endif
         __builtin_amdgcn_sched_barrier(0);
-#ifdef M6A_AB_PRIO_BLOCK_VALU
-        __builtin_amdgcn_s_setprio(M6A_AB_PRIO_BLOCK_MFMA);
-#endif
 #pragma unroll
         for (int q = b * BN_BLOCK; q < (b + 1) * BN_BLOCK; q++)
             acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[M * 16 + q], cur[q], acc2, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-
-#ifdef M6A_AB_W3
-// A/B build only (tools/encoder_ab.py, -DM6A_AB_W3): THREE waves per SIMD.  Layer 2's 80 A-operand registers per lane are what stands between the kernel
-// and 168 registers, so they live in LDS as [block of four hidden units][lane] float4 and come in one block ahead of their MFMAs, behind the block's first
-// MFMA, into two alternating float4 buffers (19 blocks per tile: the last block refills buffer 0 for the next tile after its own MFMAs).
-template <int M>
-__device__ __forceinline__ void layer2_with_bn_lds(f32x16 &acc2, f32x16 &cur, float4 (&wq)[2], const float4 *w2lane, BnPairs &pq, const float *bn_half)
-{
-    static_assert(BN_BLOCK == 4, "one float4 of A operands per block");
-    constexpr int n = L2_REGS(M), m_next = M < 4 ? M + 1 : 0;
-#pragma unroll
-    for (int b = 0; b * 4 < n; b++) {
-        const int g = M * 4 + b;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int q = b * 4 + 2 * i;
-            cur[q] = bn_relu(cur[q], pq.v[i].x, pq.v[i].y);
-            cur[q + 1] = bn_relu(cur[q + 1], pq.v[i].z, pq.v[i].w);
-        }
-        bn_pairs_load(pq, (b + 1) * 4 < n ? bn_half + M * 64 + 2 * (b + 1) * 4 : bn_half + m_next * 64);
-        __builtin_amdgcn_sched_barrier(0);
-        const float4 w = wq[g & 1];
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, cur[b * 4], acc2, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g < 18) wq[(g + 1) & 1] = w2lane[(g + 1) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, cur[b * 4 + 1], acc2, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, cur[b * 4 + 2], acc2, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, cur[b * 4 + 3], acc2, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (g == 18) wq[0] = w2lane[0];
-    }
-}
-#define M6A_SITE16_WAVES_PER_SIMD 3
-#else
-#define M6A_SITE16_WAVES_PER_SIMD 2
-#endif
 
 // exp as torch's vectorised sigmoid computes it -- Sleef's expf with the 1.0-ulp bound (sleefsimdsp.c `xexpf`; restated from the
 // published algorithm): Cody-Waite reduction by ln 2 in two parts, a degree-6 polynomial in fma form,
@@ -362,11 +268,7 @@ __global__ __launch_bounds__(256, 2) void enc_kernel(EncArgs a)
     __shared__ float s_emb[132];
     __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
     for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
-#ifdef M6A_AB_BN_PK
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[(i & ~3) | ((i & 1) << 1) | ((i & 2) >> 1)];   // (a, b, a', b') -> (a, a', b, b')
-#else
     for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
-#endif
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -521,45 +423,14 @@ __global__ __launch_bounds__(256, 2) void enc_kernel(EncArgs a)
 // A tile that would need a fourth site raises the error flag (the host launches this kernel only when the smallest bag
 // has >= 16 reads and the job fits 32-bit indices; enc_kernel stays the path for everything else).
 // =====================================================================================
-#ifdef M6A_AB_STAMPS
-// Diagnostic build only (tools/encoder_timeline.py; never the product): every wave of enc_site16_kernel stamps s_memtime at ten points
-// of each of M6A_AB_STAMP_TILES consecutive tiles from its M6A_AB_STAMP_FIRST-th on, with its hardware slot (HW_ID, XCC_ID), so the two
-// waves that share a SIMD can be laid side by side.  The stamps are scalar instructions with no wait; lane 0 stores them after the
-// last stamp of a tile.
-#define M6A_AB_STAMP_TILES 16
-#define M6A_AB_STAMP_FIRST 100
-#define M6A_AB_STAMP_POINTS 10
-__device__ unsigned long long m6a_ab_stamp_buf[4096][M6A_AB_STAMP_TILES][M6A_AB_STAMP_POINTS];
-__device__ unsigned m6a_ab_stamp_hw[4096][2];
-extern "C" int m6a_ab_read_stamps(unsigned long long *stamps, unsigned *hw)
-{
-    if (hipMemcpyFromSymbol(stamps, HIP_SYMBOL(m6a_ab_stamp_buf), sizeof(m6a_ab_stamp_buf)) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(hw, HIP_SYMBOL(m6a_ab_stamp_hw), sizeof(m6a_ab_stamp_hw)) != hipSuccess) return -1;
-    return 0;
-}
-#define M6A_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); ts[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define M6A_STAMP(k) do { } while (0)
-#endif
-__global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_kernel(EncArgs a)
+__global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
 {
     clamp_keeps_nan();
     m6a_clk_stamp(a.clk, 0);
     __shared__ float s_emb[132];
     __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
     for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
-#ifdef M6A_AB_BN_PK
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[(i & ~3) | ((i & 1) << 1) | ((i & 2) >> 1)];   // (a, b, a', b') -> (a, a', b, b')
-#else
     for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
-#endif
-#ifdef M6A_AB_W3
-    __shared__ float4 s_w2q[19 * 64];
-    for (int idx = threadIdx.x; idx < 19 * 64; idx += 256) {
-        const int g = idx >> 6, ln = idx & 63, u = (g >> 2) * 16 + (g & 3) * 4;
-        s_w2q[idx] = make_float4(a.wfrag[(40 + u) * 64 + ln], a.wfrag[(41 + u) * 64 + ln], a.wfrag[(42 + u) * 64 + ln], a.wfrag[(43 + u) * 64 + ln]);
-    }
-#endif
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -574,20 +445,11 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
     const int n_sites = (int)a.n_sites;
     const int last_lim = (int)(a.n_reads - 1 - (int64_t)(n_tiles - 1) * 32);   // last valid column of the last tile
 
-#ifdef M6A_AB_W3
-    float w1[40], w3[16];
-    float4 wq[2];
-    const float4 *w2lane = s_w2q + lane;
-    wq[0] = w2lane[0];
-#pragma unroll
-    for (int i = 0; i < 40; i++) w1[i] = a.wfrag[i * 64 + lane];
-#else
     float w1[40], w2[80], w3[16];
 #pragma unroll
     for (int i = 0; i < 40; i++) w1[i] = a.wfrag[i * 64 + lane];
 #pragma unroll
     for (int i = 0; i < 80; i++) w2[i] = a.wfrag[(40 + i) * 64 + lane];
-#endif
 #pragma unroll
     for (int i = 0; i < 16; i++) w3[i] = a.wfrag[(120 + i) * 64 + lane];
 
@@ -623,18 +485,8 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
         too_small |= lim >= d2 ? 1 : 0;
         const int room = last_site - base;                                        // sites after the base site
         const int ksr = kq_site < room ? kq_site : room;
-#ifdef M6A_AB_ADDR64
-        kid = (int)(a.site_kmers + (int64_t)base * 3)[ksr * 3 + kq_byte];
-#else
         kid = (int)(a.site_kmers + (int64_t)base * 3)[__umul24((unsigned)ksr, 3u) + (unsigned)kq_byte];      // scalar base + unsigned 32-bit lane offset (see the x loads)
-#endif
         // K slot 2i + half holds feature 2i + half, as in enc_kernel
-#ifdef M6A_AB_ADDR64
-        const float *xp = a.X + rbase * 9 + (crel * 9 + half);
-#pragma unroll
-        for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
-        x[4] = xp[half ? 6 : 8];
-#else
         // the tile's base is wave-uniform and the lane's part fits 32 unsigned bits: global_load ... v_off, s[base] offset:imm -- no 64-bit
         // address arithmetic on the VALU (a signed lane offset made hipcc form every address with v_mad_u64_u32 / v_lshl_add_u64, quarter-
         // and half-rate instructions on the datapath the MFMAs use)
@@ -643,7 +495,6 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
 #pragma unroll
         for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
         x[4] = *(const float *)((const char *)xt + (unsigned)(4 * (crel * 9 + (half ? 7 : 8))));
-#endif
     };
     auto link2 = [&](int kid, float &ev) { ev = s_emb[2 * kid + (lane & 1)]; };
     // lanes 0..17 hold float q % 6 of site a + q / 6; a lane of half h wants floats (1 - h), (1 - h) + 2, (1 - h) + 4 of
@@ -674,7 +525,6 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
         s_base += __builtin_amdgcn_readfirstlane(__shfl(rel, 31, 64));
     }
 
-    phase_shift_second_workgroup();
     BnPairs bnq;
     bn_pairs_load(bnq, bn_half);
     for (int tile = tile0; tile < tile1; ++tile) {
@@ -683,10 +533,6 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
         float fn[8], evn;
         int64_t o[3];
         int reln, kidn;
-#ifdef M6A_AB_STAMPS
-        unsigned long long ts[M6A_AB_STAMP_POINTS];
-#endif
-        M6A_STAMP(0);
         link0(s_base, o);
         tile_body_priority();
 
@@ -696,12 +542,10 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
 #pragma unroll
         for (int st = 0; st < 8; st++)
             h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);
-        M6A_STAMP(1);
 #pragma unroll
         for (int m = 0; m < 5; m++) {
             f32x16 &cur = (m & 1) ? h1b : h1a;
             f32x16 &nxt = (m & 1) ? h1a : h1b;
-#ifndef M6A_AB_L2_FIRST
             if (m < 4) {
 #pragma unroll
                 for (int q = 0; q < 16; q++) nxt[q] = 0.0f;
@@ -710,80 +554,25 @@ __global__ __launch_bounds__(256, M6A_SITE16_WAVES_PER_SIMD) void enc_site16_ker
                     nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(m + 1) * 8 + st], f[st], nxt, 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-#endif
             // where the three links of the next tile's input chain sit: behind the layer-1 MFMAs of unit tiles 2, 3 and 4 (round 6; rounds 2-6a: 1, 2 and 4 --
             // m = 0, 1, 3 here).  Measured over two runs of interleaved legs (profiles/r06_encoder_ab_schedule.json, r06_encoder_ab_links.json): -0.5 %;
-            // 0/1/4, 2/3/4, 1/3/4: +-0.2 %; 0/2/3, 0/2/4, 0/3/4: +0.4 .. +1.3 %.  -DM6A_AB_LINK1_AT=.. builds the others.
-#ifndef M6A_AB_LINK1_AT
-#define M6A_AB_LINK1_AT 1
-#define M6A_AB_LINK2_AT 2
-#define M6A_AB_LINK3_AT 3
-#endif
-#ifdef M6A_AB_NO_LINKS                   // knock-out build only (WRONG results): no input chain -- every tile computes on the first tile's features
-            if (m == 0) {
-#pragma unroll
-                for (int i = 0; i < 8; i++) fn[i] = f[i];
-                reln = 0; kidn = 0; evn = 0.0f;
-            }
-#else
-            if (m == M6A_AB_LINK1_AT) link1(tn, s_base, o, reln, kidn, fn);
-            if (m == M6A_AB_LINK2_AT) link2(kidn, evn);
-            if (m == M6A_AB_LINK3_AT) link3(evn, reln, fn);
-#endif
-#ifdef M6A_AB_W3
-            if (m == 0) layer2_with_bn_lds<0>(acc2, cur, wq, w2lane, bnq, bn_half);
-            if (m == 1) layer2_with_bn_lds<1>(acc2, cur, wq, w2lane, bnq, bn_half);
-            if (m == 2) layer2_with_bn_lds<2>(acc2, cur, wq, w2lane, bnq, bn_half);
-            if (m == 3) layer2_with_bn_lds<3>(acc2, cur, wq, w2lane, bnq, bn_half);
-            if (m == 4) layer2_with_bn_lds<4>(acc2, cur, wq, w2lane, bnq, bn_half);
-#else
+            // 0/1/4, 2/3/4, 1/3/4: +-0.2 %; 0/2/3, 0/2/4, 0/3/4: +0.4 .. +1.3 %.
+            if (m == 1) link1(tn, s_base, o, reln, kidn, fn);
+            if (m == 2) link2(kidn, evn);
+            if (m == 3) link3(evn, reln, fn);
             if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
             if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
             if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
             if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
             if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
-#endif
-#ifdef M6A_AB_L2_FIRST
-            if (m < 4) {
-#pragma unroll
-                for (int q = 0; q < 16; q++) nxt[q] = 0.0f;
-#pragma unroll
-                for (int st = 0; st < 8; st++)
-                    nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(m + 1) * 8 + st], f[st], nxt, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-            M6A_STAMP(2 + m);
         }
         tile_epilogue_priority();
-#ifdef M6A_AB_NO_EPILOGUE
-        // knock-out build only (tools/encoder_ab.py): what the 32 -> 1 layer + sigmoid cost in place -- an upper bound on what
-        // moving them under the next tile's MFMAs could buy.  WRONG results by construction; never the product.
-        const float p = (acc2[0] + acc2[5]) + w3[0];
-#else
         const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;
-        M6A_STAMP(7);
         const float p = 1.0f / (1.0f + sleef_expf_u10(-z));
-#endif
         if (half == 0 && col <= (tile == n_tiles - 1 ? last_lim : 31)) (a.read_prob + (int64_t)tile * 32)[col] = p;
-        M6A_STAMP(8);
         if (tn != tile) s_base += __builtin_amdgcn_readfirstlane(__shfl(reln, 31, 64));
 #pragma unroll
         for (int i = 0; i < 8; i++) f[i] = fn[i];
-#ifdef M6A_AB_STAMPS
-        M6A_STAMP(9);
-        {
-            const int k = tile - tile0 - M6A_AB_STAMP_FIRST;
-            if (k >= 0 && k < M6A_AB_STAMP_TILES && wave < 4096 && lane == 0) {
-#pragma unroll
-                for (int i = 0; i < M6A_AB_STAMP_POINTS; i++) m6a_ab_stamp_buf[wave][k][i] = ts[i];
-                if (k == 0) {
-                    m6a_ab_stamp_hw[wave][0] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));       // HW_REG_HW_ID
-                    m6a_ab_stamp_hw[wave][1] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));      // HW_REG_XCC_ID
-                }
-            }
-        }
-#endif
     }
     if (too_small && lane == 0) atomicExch(a.err, 2);
     m6a_clk_stamp(a.clk, 1);
@@ -821,11 +610,7 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
     for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
     for (int i = threadIdx.x; i < 35 * 32; i += 256) s_w1e[i] = a.w1e_tab[i];
     __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
-#ifdef M6A_AB_BN_PK
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[(i & ~3) | ((i & 1) << 1) | ((i & 2) >> 1)];   // (a, b, a', b') -> (a, a', b, b')
-#else
     for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
-#endif
     // W3 in the order the layer-2 accumulator holds the 32 units: [half][q] (16 VGPRs the tile loop needs more)
     __shared__ float s_w3[32];
     if (threadIdx.x < 64) s_w3[(threadIdx.x >> 5) * 16 + (threadIdx.x & 15)] = a.wfrag[(120 + (threadIdx.x & 15)) * 64 + (threadIdx.x & 32)];
@@ -899,27 +684,16 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
         too_small |= lim >= d2 ? 1 : 0;
         const int room = last_site - base;                                        // sites after the base site
         const int ksr = kq_site < room ? kq_site : room;
-#ifdef M6A_AB_ADDR64
-        kid = (int)(a.site_kmers + (int64_t)base * 3)[ksr * 3 + kq_byte];
-#else
         kid = (int)(a.site_kmers + (int64_t)base * 3)[__umul24((unsigned)ksr, 3u) + (unsigned)kq_byte];      // scalar base + unsigned 32-bit lane offset (see the x loads)
-#endif
         // K slot 2st+half holds feature 2st+half: the features enter the sum in the order the reference's dot product
         // has them.  (One 16-byte load per lane -- half 0 x0..x3, half 1 x4..x7, weights permuted to match -- is the
         // same speed and moves the summation order away from the reference's: the worst use of the rtol 1e-5 bar over
         // 10 M reads rose from 0.81 to 0.89 on the arabidopsis weights, 0.936 to 0.951 on HEK293T.)
-#ifdef M6A_AB_ADDR64
-        const float *xp = a.X + rbase * 9 + (crel * 9 + half);
-#pragma unroll
-        for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
-        x[4] = xp[half ? 6 : 8];                             // x8 on half 0 (half 1: a valid dummy)
-#else
         const float *xt = a.X + rbase * 9;                   // scalar base + unsigned 32-bit lane offset, as in enc_site16_kernel
         const float *xp = (const float *)((const char *)xt + (unsigned)(4 * (crel * 9 + half)));
 #pragma unroll
         for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
         x[4] = *(const float *)((const char *)xt + (unsigned)(4 * (crel * 9 + (half ? 7 : 8))));      // x8 on half 0 (half 1: a valid dummy)
-#endif
     };
     // link2: the embedding float itself
     auto link2 = [&](int kid, float &ev) { ev = s_emb[2 * kid + (lane & 1)]; };
@@ -945,18 +719,6 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
 #pragma unroll
         for (int m = 0; m < 5; m++) {
             const float *wr = s_w1e + (m * 7) * 32 + col;
-#ifdef M6A_AB_CSITE_SCALAR_FMA
-            // A/B build only (tools/encoder_ab.py): the same 60 fmas as 60 plain v_fma_f32 -- the MI355X guide lists
-            // packed-f32 VALU beside MFMAs as an anti-lever.  asm: plain C would be SLP-packed back into v_pk_fma_f32.  Same bits.
-            float cx = wr[6 * 32], cy = cx;
-#pragma unroll
-            for (int q = 0; q < 6; q++) {
-                const float wq = wr[q * 32];
-                asm("v_fma_f32 %0, %1, %2, %0" : "+v"(cx) : "v"(wq), "v"(e2[q].x));
-                asm("v_fma_f32 %0, %1, %2, %0" : "+v"(cy) : "v"(wq), "v"(e2[q].y));
-            }
-            const f32x2 c = {cx, cy};
-#else
             f32x2 c = {wr[6 * 32], wr[6 * 32]};
 #pragma unroll
             for (int q = 0; q < 6; q++) {
@@ -964,14 +726,8 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
                 const f32x2 w2v = {wq, wq};
                 c = __builtin_elementwise_fma(w2v, e2[q], c);
             }
-#endif
             a4[m] = half ? c.x : w8[m];          // step 4: h=0 x8, h=1 I(a)
             a5[m] = c.y;                         // step 5: h=0 I(a+1), h=1 I(a+2)
-#ifdef M6A_AB_CSITE_PIN
-            // A/B build only: hipcc sinks this loop's arithmetic (pure, used by the NEXT tile) behind the epilogue, where no MFMA
-            // covers it; the empty volatile asm keeps it where it is written, between the MFMA groups.  Same bits.
-            asm volatile("" : "+v"(a4[m]), "+v"(a5[m]));
-#endif
         }
         x[4] = half ? (rel == 0 ? 1.0f : 0.0f) : x8;
         x[5] = (rel == (half ? 2 : 1)) ? 1.0f : 0.0f;

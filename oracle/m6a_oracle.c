@@ -144,9 +144,10 @@ static void enc_prepare(const float *w, enc_tables *t)
  * checked bit for bit against the reference's logits (tests/golden/reference_layers.npz):
  *     s = x0*w0;   16 lanes of products k = 1 + l, lane 0 = fma(x1, w1, s);   butterfly l+8, l+4, l+2, l+1;
  *     the same for k = 17 + l (lane 15 empty), lane 0 = fma(x17, w17, sum so far).
- * This is one MKL kernel on one ISA, not m6anet's algorithm: the HIP kernels do NOT follow it.  The
- * oracle does, because it is pinned to captures made on that machine and stands in for the reference on the GPU box -- with
- * it (and Sleef's exp), the oracle's read probabilities ARE the capture's, bit for bit, on every read of a 20-read-bag job. */
+ * This is one MKL kernel on one ISA, not m6anet's algorithm.  The two 16-slot HIP kernels follow it all the same (gemv32_as_mkl in
+ * m6a_kernels.hip; the 12-slot kernel keeps its own order), and so does the oracle, because it is pinned to
+ * captures made on that machine and stands in for the reference on the GPU box -- with it (and Sleef's exp), the oracle's read
+ * probabilities ARE the capture's, bit for bit, on every read of a 20-read-bag job. */
 static inline float butterfly16(float *v)
 {
     for (int step = 8; step >= 1; step >>= 1)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Where a tile's wall time goes inside enc_site16_kernel, from the kernel's own clock: a diagnostic build (-DM6A_AB_STAMPS, never the
-product) stamps s_memtime at ten points of 16 consecutive tiles of EVERY wave, with the wave's hardware slot, so the two waves that
-share a SIMD can be laid side by side.
+"""Where a tile's wall time goes inside enc_site16_kernel, from the kernel's own clock: a diagnostic build (never the product) stamps
+s_memtime at ten points of 16 consecutive tiles of EVERY wave, with the wave's hardware slot, so the two waves that share a SIMD can
+be laid side by side.  The stamp buffer, its reader and the ten stamp points are not in m6a_kernels.hip: stamps() below inserts them
+into a copy (tools/variant_build.py), on top of encoder_ab.py's priority edits for stamps_noprio / stamps_body3_epi0.
 
     python tools/encoder_timeline.py --build     (here: cross-compiles tools/ko/libm6a_ab_stamps.so, which travels to the GPU box)
     python tools/encoder_timeline.py             (GPU box: one JSON object)
@@ -18,6 +19,10 @@ Sections of a tile (stamp i -> i+1) and the MFMAs this wave issues in each:
   8-9  site base for the next tile (shuffle + readfirstlane), feature registers handed over   0
   9-0' loop back (in the stamped tiles also: lane 0 stores the ten stamps)          0
 With two waves per SIMD taking turns on the matrix pipe, a section with n MFMAs lasts >= 128 n cycles while the partner is in its body too.
+
+No longer built: stamps_phase, stamps_phase_noprio, stamps_phase_body3_epi0, stamps_phase_eqprio (the second workgroup of a CU started half
+a tile late: an `#ifdef M6A_AB_PHASE` branch of the kernel source itself).  Their results are in profiles/r06_encoder_timeline.json; the last
+commit that can build them is 53ba79eec7177618b64cf16fbcc604bc27170bd0.
 """
 import ctypes
 import json
@@ -25,32 +30,61 @@ import os
 import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from encoder_ab import lib, no_prio, prio
+from variant_build import REPO, build, swap, within
+
 sys.path.insert(0, REPO)
-KO = os.path.join(REPO, "tools", "ko")
-VARIANTS = {"stamps": [], "stamps_noprio": ["-DM6A_AB_NO_PRIO"], "stamps_body3_epi0": ["-DM6A_AB_PRIO_BODY=3", "-DM6A_AB_PRIO_EPI=0"],
-            "stamps_phase": ["-DM6A_AB_PHASE=1"], "stamps_phase_noprio": ["-DM6A_AB_PHASE=1", "-DM6A_AB_NO_PRIO"],
-            "stamps_phase_body3_epi0": ["-DM6A_AB_PHASE=1", "-DM6A_AB_PRIO_BODY=3", "-DM6A_AB_PRIO_EPI=0"],
-            "stamps_phase_eqprio": ["-DM6A_AB_PHASE=1", "-DM6A_AB_PRIO_BODY=1", "-DM6A_AB_PRIO_EPI=1"]}
-
-
-def lib(name):
-    return os.path.join(KO, "libm6a_ab_%s.so" % name)
 TILES, POINTS, FIRST, MAXW = 16, 10, 100, 4096
+
+STAMP_STATE = """// Diagnostic build only: every wave of enc_site16_kernel stamps s_memtime at ten points of each of %(TILES)d consecutive tiles from its
+// %(FIRST)d-th on, with its hardware slot (HW_ID, XCC_ID).  The stamps are scalar instructions with no wait; lane 0 stores them after the
+// last stamp of a tile.
+__device__ unsigned long long m6a_ab_stamp_buf[%(MAXW)d][%(TILES)d][%(POINTS)d];
+__device__ unsigned m6a_ab_stamp_hw[%(MAXW)d][2];
+extern "C" int m6a_ab_read_stamps(unsigned long long *stamps, unsigned *hw)
+{
+    if (hipMemcpyFromSymbol(stamps, HIP_SYMBOL(m6a_ab_stamp_buf), sizeof(m6a_ab_stamp_buf)) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(hw, HIP_SYMBOL(m6a_ab_stamp_hw), sizeof(m6a_ab_stamp_hw)) != hipSuccess) return -1;
+    return 0;
+}
+#define M6A_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); ts[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+""" % {"TILES": TILES, "POINTS": POINTS, "FIRST": FIRST, "MAXW": MAXW}
+STAMP_STORE = """        M6A_STAMP(9);
+        {
+            const int k = tile - tile0 - %(FIRST)d;
+            if (k >= 0 && k < %(TILES)d && wave < %(MAXW)d && lane == 0) {
+#pragma unroll
+                for (int i = 0; i < %(POINTS)d; i++) m6a_ab_stamp_buf[wave][k][i] = ts[i];
+                if (k == 0) {
+                    m6a_ab_stamp_hw[wave][0] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));       // HW_REG_HW_ID
+                    m6a_ab_stamp_hw[wave][1] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));      // HW_REG_XCC_ID
+                }
+            }
+        }
+""" % {"TILES": TILES, "POINTS": POINTS, "FIRST": FIRST, "MAXW": MAXW}
+KERNEL = "__global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)\n"
+
+
+def stamps(s):
+    """The stamp buffer and its reader in front of enc_site16_kernel, the ten stamp points and the store into its tile loop."""
+    def tile_loop(k):
+        k = swap(k, "        int reln, kidn;\n        link0(s_base, o);\n", "        int reln, kidn;\n        unsigned long long ts[%d];\n        M6A_STAMP(0);\n        link0(s_base, o);\n" % POINTS)
+        for line, stamp in (("            h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);\n", "        M6A_STAMP(1);\n"),
+                            ("            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);\n", "            M6A_STAMP(2 + m);\n"),
+                            ("        const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;\n", "        M6A_STAMP(7);\n"),
+                            ("(a.read_prob + (int64_t)tile * 32)[col] = p;\n", "        M6A_STAMP(8);\n"),
+                            ("        for (int i = 0; i < 8; i++) f[i] = fn[i];\n", STAMP_STORE)):
+            k = swap(k, line, line + stamp)
+        return k
+    s = within(s, KERNEL, "\n}\n", tile_loop)
+    return swap(s, KERNEL, STAMP_STATE + KERNEL)
+
+
+VARIANTS = {"stamps": stamps, "stamps_noprio": lambda s: stamps(no_prio(s)), "stamps_body3_epi0": lambda s: stamps(prio(3, 0)(s))}
 MFMA = [8, 24, 24, 24, 24, 12, 0, 0, 0, 0]
 NAMES = ["link0 + L1(0)", "L1(1) + link1 + BN/L2(0)", "L1(2) + link2 + BN/L2(1)", "L1(3) + BN/L2(2)", "L1(4) + link3 + BN/L2(3)", "BN/L2(4)",
          "32->1 layer", "sigmoid + store", "site base + hand-over", "loop back (+ stamp stores)"]
-
-
-def build():
-    from m6anet_amd import build as B
-    os.makedirs(KO, exist_ok=True)
-    jump = os.path.join(B.PKG, "assets", "mt19937_jump.bin")
-    for name, flags in VARIANTS.items():
-        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-               '-DM6A_MT_JUMP_PATH="%s"' % jump, "-DM6A_AB_STAMPS", "-I" + B.INCLUDE, "-I" + B.CSRC] + flags + [os.path.join(B.CSRC, s) for s in B.SOURCES] + ["-o", lib(name)]
-        subprocess.check_call(cmd)
-        print("built", lib(name))
 
 
 def med(v):
@@ -60,7 +94,7 @@ def med(v):
 
 def main():
     if "--build" in sys.argv:
-        build()
+        build("m6a_kernels.hip", VARIANTS, "libm6a_ab_%s.so")
         return
     if "--one" not in sys.argv:
         out = {}
@@ -70,7 +104,6 @@ def main():
             o = subprocess.run([sys.executable, os.path.abspath(__file__), "--one"], env=dict(os.environ, M6A_HIP_LIB=lib(name)), capture_output=True, text=True, timeout=600)
             try:
                 out[name] = json.loads(o.stdout.strip().splitlines()[-1])
-                out[name]["build_flags"] = ["-DM6A_AB_STAMPS"] + VARIANTS[name]
             except (ValueError, IndexError):
                 out[name] = {"error": (o.stderr or o.stdout)[-400:]}
         print(json.dumps(out))
@@ -142,7 +175,7 @@ def main():
         a, b = pairs[len(pairs) // 2]
         t0 = int(min(st[a, 4, 0], st[b, 4, 0]))
         ex = {"waves": [a, b], "stamps_minus_t0": {"a": (st[a, 4:8] - t0).tolist(), "b": (st[b, 4:8] - t0).tolist()}}
-    out = {"what": "enc_site16_kernel, 20 M reads (1 M sites x 20), s_memtime stamps of tiles %d..%d of every wave (diagnostic build -DM6A_AB_STAMPS)" % (FIRST, FIRST + TILES - 1),
+    out = {"what": "enc_site16_kernel, 20 M reads (1 M sites x 20), s_memtime stamps of tiles %d..%d of every wave (diagnostic build)" % (FIRST, FIRST + TILES - 1),
            "kernel_ms": ms / n, "waves": int(len(live)), "tile_cycles_median": float(np.median(tile)), "tile_cycles_mean": float(tile.mean()),
            "mfma_cycles_per_tile_of_both_waves": 2 * 116 * 64,
            "matrix_pipe_busy_from_stamps": 2 * 116 * 64 / float(np.median(tile)),

@@ -13,16 +13,9 @@ import re
 import subprocess
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CSRC = os.path.join(REPO, "m6anet_amd", "csrc")
-KO = os.path.join(HERE, "ko")
-
-
-def sub(pattern, repl, s, count=1, flags=0):
-    out, n = re.subn(pattern, repl, s, count=count, flags=flags)
-    assert n >= 1, pattern
-    return out
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import variant_build
+from variant_build import KO, REPO, sub
 
 
 def no_loop_loads(s):
@@ -90,27 +83,7 @@ VARIANTS = {
 
 
 def build():
-    os.makedirs(KO, exist_ok=True)
-    src = open(os.path.join(CSRC, "m6a_pool_reg.hip")).read()
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-w",
-             '-DM6A_MT_JUMP_PATH="%s"' % os.path.join(REPO, "m6anet_amd", "assets", "mt19937_jump.bin"),
-             "-I" + os.path.join(REPO, "include"), "-I" + CSRC]
-    objs = []
-    sys.path.insert(0, REPO)
-    from m6anet_amd.build import SOURCES
-    for f in [x for x in SOURCES if x != "m6a_pool_reg.hip"]:
-        o = os.path.join(KO, f.replace(".hip", ".o"))
-        if not os.path.exists(o) or os.path.getmtime(o) < os.path.getmtime(os.path.join(CSRC, f)):
-            subprocess.check_call([hipcc] + flags + ["-c", os.path.join(CSRC, f), "-o", o])
-        objs.append(o)
-    for name, fn in VARIANTS.items():
-        p = os.path.join(KO, "pool_reg_%s.hip" % name)
-        open(p, "w").write(fn(src))
-        o = p.replace(".hip", ".o")
-        subprocess.check_call([hipcc] + flags + ["-c", p, "-o", o])
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + [o, "-o", os.path.join(KO, "libm6a_%s.so" % name)])
-        print("built", name)
+    variant_build.build("m6a_pool_reg.hip", VARIANTS, "libm6a_%s.so")
 
 
 def time_one():

@@ -14,25 +14,19 @@ import os
 import subprocess
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CSRC = os.path.join(REPO, "m6anet_amd", "csrc")
-KO = os.path.join(HERE, "ko")
-
-
-def rep(s, a, b, count=1):
-    assert s.count(a) >= 1, a
-    return s.replace(a, b, count)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import variant_build
+from variant_build import KO, REPO, swap
 
 
 def allbytes(s):
-    return rep(s, "    const bool bytes = n <= M6A_RTAB_U8_MAX_N;", "    const bool bytes = true;")
+    return swap(s, "    const bool bytes = n <= M6A_RTAB_U8_MAX_N;", "    const bool bytes = true;")
 
 
 def rows16(s):
-    s = rep(s, "        constexpr int AL = MODE - 2, ND = (AL + 20 + 3) / 4;", "        constexpr int AL = MODE - 2, ND = (AL + 16 + 3) / 4;")
-    s = rep(s, "        constexpr int b = J + MODE - 2;", "        constexpr int b = (J & 15) + MODE - 2;")
-    s = rep(s, "    const int64_t row_bytes = (int64_t)K * esz;", "    const int64_t row_bytes = bytes ? 16 : (int64_t)K * esz;")
+    s = swap(s, "        constexpr int AL = MODE - 2, ND = (AL + 20 + 3) / 4;", "        constexpr int AL = MODE - 2, ND = (AL + 16 + 3) / 4;")
+    s = swap(s, "        constexpr int b = J + MODE - 2;", "        constexpr int b = (J & 15) + MODE - 2;")
+    s = swap(s, "    const int64_t row_bytes = (int64_t)K * esz;", "    const int64_t row_bytes = bytes ? 16 : (int64_t)K * esz;")
     return s
 
 
@@ -40,27 +34,7 @@ VARIANTS = {"asis": lambda s: s, "allbytes": allbytes, "rows16": rows16}
 
 
 def build():
-    os.makedirs(KO, exist_ok=True)
-    src = open(os.path.join(CSRC, "m6a_pool_rtab.hip")).read()
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-w",
-             '-DM6A_MT_JUMP_PATH="%s"' % os.path.join(REPO, "m6anet_amd", "assets", "mt19937_jump.bin"),
-             "-I" + os.path.join(REPO, "include"), "-I" + CSRC]
-    objs = []
-    sys.path.insert(0, REPO)
-    from m6anet_amd.build import SOURCES
-    for f in [x for x in SOURCES if x != "m6a_pool_rtab.hip"]:
-        o = os.path.join(KO, "rt_" + f.replace(".hip", ".o"))
-        if not os.path.exists(o) or os.path.getmtime(o) < os.path.getmtime(os.path.join(CSRC, f)):
-            subprocess.check_call([hipcc] + flags + ["-c", os.path.join(CSRC, f), "-o", o])
-        objs.append(o)
-    for name, fn in VARIANTS.items():
-        p = os.path.join(KO, "pool_rtab_%s.hip" % name)
-        open(p, "w").write(fn(src))
-        o = p.replace(".hip", ".o")
-        subprocess.check_call([hipcc] + flags + ["-c", p, "-o", o])
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + [o, "-o", os.path.join(KO, "libm6a_rt_%s.so" % name)])
-        print("built", name)
+    variant_build.build("m6a_pool_rtab.hip", VARIANTS, "libm6a_rt_%s.so")
 
 
 def time_one():

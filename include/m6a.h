@@ -742,6 +742,60 @@ int m6a_prep_sites_write_csv_bgzf(m6a_prep_sites *p, const char *out_dir, int wr
 int m6a_prep_sites_write_csv_bgzf_level(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
                                         int level, m6a_csv_bgzf_stats *stats, int64_t n_by_type[3]);
 
+/* `train`: fitting the m6anet.toml model (m6anet/scripts/train.py -> train_one_epoch, m6anet/utils/training_utils.py; the model of
+ * m6anet/model/configs/model_configs/m6anet.toml, which has no dropout, so a step is a deterministic function of its batch).  The
+ * operation, stated once (tests/train_statement.py is the same in NumPy float64; the kernels of m6anet_amd/csrc/m6a_train.hip compute
+ * it in float32).  One step on B bags of `bag` reads, N = B * bag reads:
+ *   x    = [X (9) | E[k0] | E[k1] | E[k2]], 15 values;  z1 = W1 x + b1
+ *   batch norm in training mode over the N reads: mu = mean(z1), var = the biased variance, xhat = (z1 - mu) / sqrt(var + 1e-5),
+ *          y1 = gamma xhat + beta;  running_mean <- 0.9 running_mean + 0.1 mu;  running_var <- 0.9 running_var + 0.1 var N / (N - 1)
+ *   a1   = relu(y1), a2 = relu(W2 a1 + b2), p = sigmoid(W3 a2 + b3)
+ *   s_b  = 1 - prod_k (1 - p_bk), the product in float32, left to right, as m6a_bag_forward forms it
+ *   loss = torch.nn.BCELoss(): the mean over the B sites of -(y max(log s, -100) + (1 - y) max(log(1 - s), -100)); its backward is
+ *          dL/ds = (s - y) / max((1 - s) s, 1e-12) / B
+ *   ds/dp_k = prod_{j != k} (1 - p_j), from the products before and behind read k -- nothing is divided by 1 - p_k, so a read with
+ *          p = 1.0f gives its site the loss term 100 (y = 0) or 0 (y = 1) and a gradient of exactly zero
+ *   Adam as torch.optim.Adam applies it: g += weight_decay theta, m and v, theta -= lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *          over the 7 697 trainable floats E, W1, b1, gamma, beta, W2, b2, W3, b3; the two running statistics are not parameters.
+ * Not built: gradient clipping (the reference's command never sets it), the weighted loss, other topologies.
+ * Sums run in a fixed order and no float is added atomically: the same state and batch give the same bits.
+ *
+ *   m6a_train_create   weights: the 7 997-float blob of m6a_create (a HOST pointer, raw values); the trainer keeps its own copy, with
+ *                      Adam's m and v at zero and t = 0, and never touches the context's inference layout.  cfg NULL = lr 4e-4, betas
+ *                      0.9 / 0.999, eps 1e-8, weight_decay 0.  The trainer works on the context's device and stream (m6a_set_stream is
+ *                      honoured) and must be destroyed before its context.
+ *   m6a_train_step     X [n_bags * bag][9], site_kmers [n_bags][3], y [n_bags] (0 or 1), loss [1], y_pred [n_bags] = s (either may be
+ *                      NULL).
+ *   m6a_train_epoch    X / site_kmers / off / y describe n_sites sites as everywhere.  Step k takes order[k * batch_size :
+ *                      (k + 1) * batch_size]; the last batch may be short (DataLoader's drop_last=False).  Position i of `order`
+ *                      draws its `bag` reads by the rule of m6anet_amd/csrc/m6a_train_draw.h and the kernels read X in place through
+ *                      those indices: no batch is materialised.  loss [ceil(n_order / batch_size)], y_pred [n_order].  All steps
+ *                      are queued back to back: the call waits for the stream once to learn that its arguments are valid (and once
+ *                      more to deliver host outputs), however many steps there are.
+ *   m6a_train_sample   the same indices on the host: read_idx [n_order * bag] global read numbers (off, order: host pointers).
+ *   m6a_train_grads    the last step's gradient in blob order, zeros in the 300 running-statistic slots (before weight decay, as
+ *                      torch's p.grad).
+ *   m6a_train_weights  the blob with the running statistics in place: it goes straight into m6a_create.  n_steps (may be NULL) = t.
+ *   m6a_train_stats    steps taken, kernels launched, waits for the stream -- each may be NULL.
+ * Pointers are all host or all device, as everywhere; a host dataset is uploaded once per call, device-pointer calls are stream-ordered
+ * after the one wait named above (m6a_sync before reading their outputs).
+ * M6A_EINVAL: bag outside 1..M6A_MAX_SAMPLES; a batch of fewer than 2 reads (torch refuses a one-value batch norm) or of more than
+ * 2^20; a site with fewer than `bag` reads; a k-mer id outside 0..65; an `order` entry outside [0, n_sites); a label that is not 0 or
+ * 1.  Nothing is changed by a refused call. */
+typedef struct m6a_trainer m6a_trainer;
+typedef struct { float lr, beta1, beta2, eps, weight_decay; } m6a_train_config;
+int m6a_train_create(m6a_ctx *ctx, const float *weights, size_t n_floats, const m6a_train_config *cfg, m6a_trainer **out);
+void m6a_train_destroy(m6a_trainer *t);
+int m6a_train_step(m6a_trainer *t, const float *X, const uint8_t *site_kmers, const float *y, int64_t n_bags, int bag,
+                   float *loss, float *y_pred);
+int m6a_train_epoch(m6a_trainer *t, const float *X, const uint8_t *site_kmers, const int64_t *off, const float *y, int64_t n_sites,
+                    const int64_t *order, int64_t n_order, int64_t batch_size, int bag, uint64_t seed,
+                    float *loss, float *y_pred);
+int m6a_train_sample(const int64_t *off, const int64_t *order, int64_t n_order, int bag, uint64_t seed, int64_t *read_idx);
+int m6a_train_grads(m6a_trainer *t, float *grads);
+int m6a_train_weights(m6a_trainer *t, float *weights, int64_t *n_steps);
+int m6a_train_stats(const m6a_trainer *t, int64_t *n_steps, int64_t *n_launches, int64_t *n_syncs);
+
 #ifdef __cplusplus
 }
 #endif

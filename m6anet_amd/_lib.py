@@ -20,7 +20,8 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
-           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_repr_format", "m6a_prep_dataprep_write"]
+           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_repr_format", "m6a_prep_dataprep_write",
+           "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats"]
 
 _lib = None
 
@@ -83,6 +84,11 @@ class DataprepStats(C.Structure):
     _fields_ = [("ms_front", C.c_double), ("ms_back", C.c_double), ("ms_format", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double),
                 ("json_bytes", C.c_int64), ("index_bytes", C.c_int64), ("n_sites", C.c_int64), ("n_runs", C.c_int64), ("n_declined", C.c_int64),
                 ("n_rounds", C.c_int64), ("d2h_bytes", C.c_int64), ("peak_bytes", C.c_int64)]
+
+
+class TrainConfig(C.Structure):
+    """m6a_train_config (include/m6a.h)."""
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
 
 
 class M6AError(RuntimeError):
@@ -217,6 +223,15 @@ def load():
     L.m6a_prep_sites_write_csv_bgzf_level.argtypes = [vp, C.c_char_p, i32, i64, i32, i32, C.POINTER(CsvBgzfStats), pl]
     L.m6a_repr_format.argtypes = [i32, vp, i64, i32, vp, i64, vp, pl]
     L.m6a_prep_dataprep_write.argtypes = [i32, C.c_char_p, C.c_char_p, i32, i32, i32, i32, C.POINTER(HostHalf), i32, C.POINTER(DataprepStats)]
+    L.m6a_train_create.argtypes = [vp, vp, sz, C.POINTER(TrainConfig), C.POINTER(vp)]
+    L.m6a_train_destroy.argtypes = [vp]
+    L.m6a_train_destroy.restype = None
+    L.m6a_train_step.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
+    L.m6a_train_epoch.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64, i64, i32, C.c_uint64, vp, vp]
+    L.m6a_train_sample.argtypes = [vp, vp, i64, i32, C.c_uint64, vp]
+    L.m6a_train_grads.argtypes = [vp, vp]
+    L.m6a_train_weights.argtypes = [vp, vp, pl]
+    L.m6a_train_stats.argtypes = [vp, pl, pl, pl]
     L.m6a_prep_last_error.argtypes = []
     L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:

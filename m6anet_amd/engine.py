@@ -49,6 +49,44 @@ def weights_from_state_dict(sd):
     return w
 
 
+STATE_DICT_KEYS = [("read_level_encoder.1.embedding_layer.weight", (66, 2)), ("read_level_encoder.3.layers.0.weight", (150, 15)),
+                   ("read_level_encoder.3.layers.0.bias", (150,)), ("read_level_encoder.3.layers.1.weight", (150,)),
+                   ("read_level_encoder.3.layers.1.bias", (150,)), ("read_level_encoder.3.layers.1.running_mean", (150,)),
+                   ("read_level_encoder.3.layers.1.running_var", (150,)), ("read_level_encoder.4.layers.0.weight", (32, 150)),
+                   ("read_level_encoder.4.layers.0.bias", (32,)), ("pooling_filter.probability_layer.0.weight", (1, 32)),
+                   ("pooling_filter.probability_layer.0.bias", (1,))]
+
+
+def state_dict_from_weights(w, num_batches_tracked=0):
+    """The inverse of weights_from_state_dict: the reference's keys -> NumPy arrays in the shapes of m6anet/model/model.py:40-69,
+    plus the batch norm's num_batches_tracked (int64 scalar).  No torch."""
+    w = np.ascontiguousarray(w, np.float32)
+    if w.size != N_WEIGHT_FLOATS:
+        raise ValueError("weights must have %d floats" % N_WEIGHT_FLOATS)
+    sd, o = {}, 0
+    for key, shape in STATE_DICT_KEYS:
+        n = int(np.prod(shape))
+        sd[key] = w[o:o + n].reshape(shape).copy()
+        o += n
+        if key.endswith("running_var"):
+            sd[key[:-len("running_var")] + "num_batches_tracked"] = np.array(int(num_batches_tracked), np.int64)
+    return sd
+
+
+def init_weights(seed):
+    """A fresh blob by torch's default initialisation RULE, in NumPy: U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for the weights and biases
+    of the three linear layers, N(0, 1) for the embedding, gamma = 1, beta = 0, running statistics 0 and 1.  The rule, not torch's
+    draws: MILModel(...) under torch.manual_seed(seed) holds other numbers."""
+    g = np.random.Generator(np.random.PCG64(int(seed)))
+    lin = lambda fan_out, fan_in: (g.uniform(-1, 1, (fan_out, fan_in)) / np.sqrt(fan_in), g.uniform(-1, 1, fan_out) / np.sqrt(fan_in))
+    E = g.standard_normal((66, 2))
+    W1, b1 = lin(150, 15)
+    W2, b2 = lin(32, 150)
+    W3, b3 = lin(1, 32)
+    parts = [E, W1, b1, np.ones(150), np.zeros(150), np.zeros(150), np.ones(150), W2, b2, W3, b3]
+    return np.concatenate([np.asarray(p, np.float64).ravel() for p in parts]).astype(np.float32)
+
+
 _libc = None
 
 
@@ -428,6 +466,11 @@ class M6ANetEngine:
         return site
 
 
+    def trainer(self, weights=None, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """A Trainer on this engine's device and stream (include/m6a.h: m6a_train_create), starting from `weights` (a 7 997-float
+        blob; None = init_weights(0)).  The engine's own weights are not touched."""
+        return Trainer(self, init_weights(0) if weights is None else weights, lr, betas, eps, weight_decay)
+
     def validate_pool(self, read_probs, off, n_iterations=1, n_samples=N_SAMPLES, seed=0):
         """The prediction part of the reference's `validate` (training_utils.py:233-253) from read
         probabilities: each pass samples n_samples reads per site without replacement
@@ -455,6 +498,95 @@ class M6ANetEngine:
                                        int(seed) & 0xffffffff, aP.ptr if aP else None, aY.ptr, aA.ptr))
         y = y.reshape(int(n_iterations), S)
         return (y, avg, rp) if want_read_probs else (y, avg)
+
+
+class Trainer:
+    """Training-mode forward, backward and Adam of the m6anet.toml model on the GPU (include/m6a.h: m6a_train_*).  Arrays are numpy
+    arrays or torch tensors on the engine's GPU, all of a kind per call; with device tensors a call is queued on the engine's
+    stream (`engine.sync()` before the outputs are read)."""
+
+    def __init__(self, engine, weights, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self._engine, self._L = engine, engine._L               # the context must outlive the trainer
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.size != N_WEIGHT_FLOATS:
+            raise ValueError("weights must have %d floats" % N_WEIGHT_FLOATS)
+        cfg = _lib.TrainConfig(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+        h = C.c_void_p()
+        engine._chk(self._L.m6a_train_create(engine._h, w.ctypes.data, w.size, C.byref(cfg), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._engine, "_h", None):
+            self._L.m6a_train_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, X, site_kmers, y, bag=N_SAMPLES):
+        """One step on X [B * bag, 9], site_kmers [B, 3], y [B] (0 / 1).  Returns (loss, y_pred [B]): loss is a float for numpy
+        inputs, a one-element tensor for device tensors."""
+        aX, aK, aY = _Arg(X, np.float32, "float32"), _Arg(site_kmers, np.uint8, "uint8"), _Arg(y, np.float32, "float32")
+        B = aY.size
+        if aK.size != 3 * B or aX.size != B * int(bag) * 9:
+            raise ValueError("X must be [B * bag, 9], site_kmers [B, 3], y [B]")
+        loss, pred = self._engine._out(aX.is_dev, 1, np.float32, "float32"), self._engine._out(aX.is_dev, B, np.float32, "float32")
+        aL, aP = _Arg(loss, np.float32, "float32"), _Arg(pred, np.float32, "float32")
+        self._engine._chk(self._L.m6a_train_step(self._h, aX.ptr, aK.ptr, aY.ptr, B, int(bag), aL.ptr, aP.ptr))
+        return (loss if aX.is_dev else float(loss[0])), pred
+
+    def epoch(self, X, site_kmers, off, y, order, batch_size, bag=N_SAMPLES, seed=0):
+        """One pass over `order` (site numbers, repeats allowed) in batches of batch_size, every position drawing `bag` reads of its
+        site.  Returns (loss [ceil(len(order) / batch_size)], y_pred [len(order)])."""
+        aX, aK, aO = _Arg(X, np.float32, "float32"), _Arg(site_kmers, np.uint8, "uint8"), _Arg(off, np.int64, "int64")
+        aY, aR = _Arg(y, np.float32, "float32"), _Arg(order, np.int64, "int64")
+        S = aO.size - 1
+        if aK.size != 3 * S or aY.size != S:
+            raise ValueError("site_kmers must be [n_sites, 3] and y [n_sites]")
+        bs = int(batch_size)
+        n_steps = (aR.size + bs - 1) // bs if bs > 0 else 0
+        loss, pred = self._engine._out(aX.is_dev, n_steps, np.float32, "float32"), self._engine._out(aX.is_dev, aR.size, np.float32, "float32")
+        aL, aP = _Arg(loss, np.float32, "float32"), _Arg(pred, np.float32, "float32")
+        self._engine._chk(self._L.m6a_train_epoch(self._h, aX.ptr, aK.ptr, aO.ptr, aY.ptr, S, aR.ptr, aR.size, bs, int(bag),
+                                                  int(seed) & 0xffffffffffffffff, aL.ptr, aP.ptr))
+        return loss, pred
+
+    def weights(self):
+        """The blob as it stands, running statistics included: what M6ANetEngine(weights=...) and --model_state_dict x.bin take."""
+        w, n = np.empty(N_WEIGHT_FLOATS, np.float32), C.c_int64()
+        self._engine._chk(self._L.m6a_train_weights(self._h, w.ctypes.data, C.byref(n)))
+        return w
+
+    def grads(self):
+        """The last step's gradient in blob order (zeros in the running-statistic slots)."""
+        g = np.empty(N_WEIGHT_FLOATS, np.float32)
+        self._engine._chk(self._L.m6a_train_grads(self._h, g.ctypes.data))
+        return g
+
+    def stats(self):
+        """{'n_steps', 'n_launches', 'n_syncs'} (m6a_train_stats)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._engine._chk(self._L.m6a_train_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"n_steps": a.value, "n_launches": b.value, "n_syncs": c.value}
+
+    def state_dict(self):
+        """The reference's state_dict keys -> NumPy arrays (state_dict_from_weights), num_batches_tracked = the steps taken."""
+        return state_dict_from_weights(self.weights(), self.stats()["n_steps"])
+
+
+def train_sample(off, order, bag=N_SAMPLES, seed=0):
+    """The global read indices [len(order) * bag] an epoch with this seed feeds, computed on the host (m6a_train_sample)."""
+    off, order = np.ascontiguousarray(off, np.int64), np.ascontiguousarray(order, np.int64)
+    if order.size and (order.min() < 0 or order.max() >= off.size - 1):
+        raise ValueError("order holds a site outside [0, n_sites)")
+    out = np.empty(order.size * int(bag), np.int64)
+    rc = _lib.load().m6a_train_sample(off.ctypes.data, order.ctypes.data, order.size, int(bag), int(seed) & 0xffffffffffffffff, out.ctypes.data)
+    if rc != 0:
+        raise _lib.M6AError(rc, "m6a_train_sample: bag outside 1..64 or a site with fewer than bag reads")
+    return out
 
 
 def comm_unique_id():

@@ -1,0 +1,388 @@
+"""The training kernels (m6anet_amd/csrc/m6a_train.hip, include/m6a.h: m6a_train_*) on the GPU, held to tests/train_statement.py
+and to torch autograd of the same model under the bar of tests/train_torch.py:
+
+    E_ref(t) = max over the family's seeds of |torch float32 - torch float64|,  E_hip(t) = the same with the kernels,
+    required E_hip(t) <= 8 E_ref(t), per tensor, in absolute terms.
+
+Every E_ref / E_hip is printed before it is judged and, with M6A_TRAIN_PARITY_JSON set, written to that file
+(profiles/r19_train_parity.json is one such run).
+
+b1 has an exactly zero gradient under batch norm: what Adam sees of it is rounding noise, in torch float32 as much as here, so b1
+random-walks by about lr per step in both and its reference error after ten steps is wide (about 2e-3), and so is running_mean's,
+which b1 shifts.  That is expected; the bar is relative to it."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import train_statement as TS
+import train_torch as TT
+from m6anet_amd import _lib
+from m6anet_amd.engine import M6ANetEngine, load_weights, train_sample
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HCT = "HCT116_RNA002"
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = M6ANetEngine(pretrained_model=HCT)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def bundled():
+    d = np.load(os.path.join(GOLD, "bundled_inputs.npz"))
+    return d["X"], d["site_kmers"], d["off"]
+
+
+def make_batch(bundled, B, bag, seed, kmers=None):
+    """Rows of bundled_inputs.npz recycled with a seeded permutation; labels from the seed, both classes present when B > 1."""
+    X, km, _ = bundled
+    g = np.random.Generator(np.random.PCG64(seed))
+    rows = g.permutation(X.shape[0])[np.arange(B * bag) % X.shape[0]]
+    sites = g.permutation(km.shape[0])[np.arange(B) % km.shape[0]]
+    y = (g.random(B) < 0.5).astype(np.float32)
+    if B > 1:
+        y[0], y[1] = 0.0, 1.0
+    k = km[sites] if kmers is None else np.broadcast_to(np.asarray(kmers, np.uint8), (B, 3))
+    return np.ascontiguousarray(X[rows]), np.ascontiguousarray(k, np.uint8), y, bag
+
+
+def hip_run(eng, w, batches, zero=None, **cfg):
+    tr = eng.trainer(w, **cfg)
+    losses, preds = [], []
+    for X, km, y, bag in batches:
+        loss, pred = tr.step(X, km, y, bag)
+        losses.append(loss)
+        preds.append(pred)
+    out = {"loss": np.asarray(losses, np.float32), "y_pred": preds, "grad": tr.grads(), "blob": tr.weights()}
+    tr.close()
+    return out
+
+
+def family(eng, name, w, batch_lists, zero_sites=None, **cfg):
+    """One case family: one list of batches per seed.  The reference is torch float64, or -- zero_sites given -- the statement with
+    those sites' dL/dlogit zeroed."""
+    e_ref, e_hip = [], []
+    for batches in batch_lists:
+        f32, f64 = TT.run(w, batches, torch.float32, **cfg), TT.run(w, batches, torch.float64, **cfg)
+        want = f64 if zero_sites is None else TT.statement_run(w, batches, zero_sites=zero_sites, **cfg)
+        got = hip_run(eng, w, batches, **cfg)
+        assert all(np.isfinite(got[k]).all() for k in ("loss", "grad", "blob")) and all(np.isfinite(p).all() for p in got["y_pred"])
+        e_ref.append(TT.errors(f32, f64))
+        e_hip.append(TT.errors(got, want))
+    TT.hold(name, TT.pooled(e_ref), TT.pooled(e_hip))
+
+
+def condition(w, batches, **cfg):
+    """Every site probability of the float64 statement is <= 1 - 1e-3: above that 1 - s cancels in float32 and the reference's own
+    gradient is noise.  A case that breaks it gets another seed, never a wider bar."""
+    for p in TT.statement_run(w, batches, **cfg)["y_pred"]:
+        assert p.max() <= 1 - 1e-3, p.max()
+
+
+SEEDS = (11, 12, 13, 14)
+SHAPES = [(1, 20), (3, 20), (13, 20), (64, 20), (256, 20), (2, 1), (7, 5), (5, 64)]
+
+
+@pytest.mark.parametrize("B,bag", SHAPES)
+def test_step_shapes(eng, bundled, B, bag):
+    w = load_weights(HCT)
+    lists = [[make_batch(bundled, B, bag, 1000 * B + 10 * bag + s)] for s in SEEDS]
+    for batches in lists:
+        condition(w, batches)
+    family(eng, "step %dx%d" % (B, bag), w, lists)
+
+
+def test_step_all_reads_share_one_kmer_triple(eng, bundled):
+    w = load_weights(HCT)
+    lists = [[make_batch(bundled, 8, 20, 70 + s, kmers=(3, 17, 42))] for s in SEEDS]
+    for batches in lists:
+        condition(w, batches)
+    family(eng, "step shared k-mers", w, lists)
+
+
+def test_step_kmer_ids_0_and_65(eng, bundled):
+    w = load_weights(HCT)
+    lists = []
+    for s in SEEDS:
+        X, km, y, bag = make_batch(bundled, 6, 20, 80 + s)
+        km = np.array([[0, 65, 0], [65, 65, 65], [0, 0, 0], [65, 0, 1], [64, 65, 0], [0, 1, 65]], np.uint8)
+        lists.append([(X, km, y, bag)])
+        condition(w, lists[-1])
+    family(eng, "step k-mer ids 0 and 65", w, lists)
+
+
+def test_step_dead_and_constant_hidden_unit(eng, bundled):
+    w = load_weights(HCT).copy()
+    w[TS.SLICES["beta"][0]][5] = -100.0                                  # dead: relu(y1) = 0 for every read
+    w[TS.SLICES["W1"][0]].reshape(150, 15)[7] = 0.0                     # constant: z1 = b1, variance 0
+    lists = [[make_batch(bundled, 9, 20, 90 + s)] for s in SEEDS]
+    for batches in lists:
+        condition(w, batches)
+    family(eng, "step dead and constant unit", w, lists)
+
+
+def test_step_weight_decay(eng, bundled):
+    w = load_weights(HCT)
+    lists = [[make_batch(bundled, 16, 20, 100 + s)] for s in SEEDS]
+    for batches in lists:
+        condition(w, batches, weight_decay=0.01)
+    family(eng, "step weight_decay 0.01", w, lists, weight_decay=0.01)
+
+
+def saturating_blob():
+    """HCT116 with layer-2 unit 0 rewired into a detector: it fires only for a read whose hidden unit J stands more than three
+    batch standard deviations above the batch mean, and the head weighs it so that such a read's logit is far above 40."""
+    w = load_weights(HCT).copy()
+    P = TS.unpack(w)
+    J = int(np.argmax(P["gamma"]))
+    gam, bet = float(P["gamma"][J]), float(P["beta"][J])
+    assert gam > 0
+    P["W2"][0, :] = 0.0
+    P["W2"][0, J] = 1.0
+    P["b2"][0] = -(3.0 * gam + bet)
+    P["W3"][0] = 100.0 / gam
+    return w, J
+
+
+@pytest.mark.parametrize("n_hot", [1, 2])
+def test_saturated_reads_are_decided_exactly(eng, bundled, n_hot):
+    """The family: both labels of the saturated site, two batches each."""
+    w, J = saturating_blob()
+    W1 = TS.unpack(w)["W1"]
+    site, lists = 2, []
+    for label in (0.0, 1.0):
+        for seed in (120, 121):
+            X, km, y, bag = make_batch(bundled, 4, 20, seed + 10 * n_hot)
+            y[site] = label
+            hot = [site * bag + 3 + 5 * r for r in range(n_hot)]
+            X[hot] = 300.0 * np.sign(W1[J, :9])                             # far out along unit J's weights
+            logit = TS.step_gradient(w, X, km, y, bag, logits_only=True)
+            assert logit[hot].min() > 40 and np.delete(logit, hot).max() < 10
+            assert np.delete(TT.statement_run(w, [(X, km, y, bag)])["y_pred"][0], site).max() <= 1 - 1e-3
+            tr = eng.trainer(w)
+            loss, pred = tr.step(X, km, y, bag)
+            g = tr.grads()
+            tr.close()
+            assert pred[site] == 1.0                                       # p = 1.0f, whoever computes it
+            p64 = pred.astype(np.float64)
+            with np.errstate(divide="ignore"):
+                terms = -(y * np.maximum(np.log(p64), -100) + (1 - y) * np.maximum(np.log1p(-p64), -100))
+            assert terms[site] == (100.0 if label == 0 else 0.0)
+            assert abs(loss - terms.mean()) <= 4 * np.finfo(np.float32).eps * terms.mean()
+            assert np.isfinite(g).all()
+            lists.append([(X, km, y, bag)])
+    family(eng, "saturated, %d read%s" % (n_hot, "s" * (n_hot > 1)), w, lists, zero_sites=(site,))
+
+
+def test_same_state_and_batch_give_the_same_bits(eng, bundled):
+    w = load_weights(HCT)
+    batches = [make_batch(bundled, 64, 20, 200 + k) for k in range(3)]
+    a, b = hip_run(eng, w, batches), hip_run(eng, w, batches)
+    for k in ("loss", "grad", "blob"):
+        assert a[k].tobytes() == b[k].tobytes(), k
+    assert all(p.tobytes() == q.tobytes() for p, q in zip(a["y_pred"], b["y_pred"]))
+    assert np.abs(a["grad"]).max() > 0 and not np.array_equal(a["blob"], w)
+
+
+def test_ten_steps(eng, bundled):
+    w = load_weights(HCT)
+    lists = [[make_batch(bundled, 64, 20, 300 + 20 * s + k) for k in range(10)] for s in range(6)]
+    for batches in lists:
+        condition(w, batches)
+    family(eng, "ten steps 64x20", w, lists)
+
+
+def epoch_inputs(bundled, seed=5):
+    X, km, off = bundled
+    S = len(off) - 1
+    y = (np.arange(S) % 3 == 0).astype(np.float32)
+    rs = np.random.RandomState(seed)
+    pos, neg = np.flatnonzero(y == 1), np.flatnonzero(y == 0)
+    order = np.concatenate([neg, rs.choice(pos, len(neg), replace=True)])     # over-sampled: repeats
+    rs.shuffle(order)
+    return X, km, off, y, np.ascontiguousarray(order, np.int64)
+
+
+def only_sites(X, km, off, y, keep):
+    """The data set cut down to the sites `keep`."""
+    rows = np.concatenate([np.arange(off[s], off[s + 1]) for s in keep])
+    off2 = np.concatenate([[0], np.cumsum(np.diff(off)[keep])]).astype(np.int64)
+    return np.ascontiguousarray(X[rows]), np.ascontiguousarray(km[keep]), off2, np.ascontiguousarray(y[keep])
+
+
+@pytest.mark.parametrize("bs,bag", [(1, 20), (16, 20), (101, 20), (256, 20), (16, 1), (64, 64)])
+def test_epoch_equals_its_steps_bit_for_bit(eng, bundled, bs, bag):
+    X, km, off, y, order = epoch_inputs(bundled)
+    assert len(order) == 134 and len(set(order)) < len(order)             # 67 + 67 over-sampled: repeats; 134 = 8 * 16 + 6 = 101 + 33
+    if bs == 1:
+        order = order[:37]
+    if bag == 64:                                                          # every site of a call needs >= bag reads
+        keep = np.flatnonzero(np.diff(off) >= 64)
+        assert len(keep) >= 3
+        X, km, off, y = only_sites(X, km, off, y, keep)
+        order = np.ascontiguousarray(order % len(keep), np.int64)
+    w, seed = load_weights(HCT), 77
+    idx = train_sample(off, order, bag, seed)
+    assert np.array_equal(idx, TS.sample(off, order, bag, seed))
+    per_site = idx.reshape(-1, bag)
+    assert all(len(set(r)) == bag and off[s] <= r.min() and r.max() < off[s + 1] for r, s in zip(per_site, order))
+    tr = eng.trainer(w)
+    s0 = tr.stats()
+    loss, pred = tr.epoch(X, km, off, y, order, bs, bag, seed)
+    s1 = tr.stats()
+    ew, eg = tr.weights(), tr.grads()
+    tr.close()
+    n_steps = -(-len(order) // bs)
+    assert loss.shape == (n_steps,) and pred.shape == (len(order),) and s1["n_steps"] - s0["n_steps"] == n_steps
+    tr = eng.trainer(w)
+    for k in range(n_steps):
+        o = order[k * bs:(k + 1) * bs]
+        l, p = tr.step(X[idx[k * bs * bag:(k + 1) * bs * bag]], km[o], y[o], bag)
+        assert np.float32(l).tobytes() == loss[k].tobytes(), k
+        assert p.tobytes() == pred[k * bs:(k + 1) * bs].tobytes(), k
+    assert tr.weights().tobytes() == ew.tobytes() and tr.grads().tobytes() == eg.tobytes()
+    tr.close()
+    assert np.isfinite(loss).all() and np.isfinite(ew).all()
+
+
+def test_epoch_twice_and_on_device_tensors_same_bits_and_constant_syncs(eng, bundled):
+    X, km, off, y, order = epoch_inputs(bundled)
+    w = load_weights(HCT)
+    runs, syncs = [], {}
+    for rep in range(2):
+        tr = eng.trainer(w)
+        runs.append(tr.epoch(X, km, off, y, order, 16, 20, 9) + (tr.weights(), tr.grads()))
+        tr.close()
+    dX, dK, dO, dY = (torch.from_numpy(a).cuda() for a in (X, km, off, y))
+    for n in (32, len(order)):                                             # 2 steps and 9 steps
+        tr = eng.trainer(w)
+        s0 = tr.stats()
+        loss, pred = tr.epoch(dX, dK, dO, dY, torch.from_numpy(order[:n]).cuda(), 16, 20, 9)
+        s1 = tr.stats()
+        eng.sync()
+        syncs[n] = s1["n_syncs"] - s0["n_syncs"]
+        assert s1["n_launches"] - s0["n_launches"] == 2 + 6 * -(-n // 16)
+        dev = (loss.cpu().numpy(), pred.cpu().numpy(), tr.weights(), tr.grads())
+        tr.close()
+    assert syncs[32] == syncs[len(order)] == 1, syncs
+    for a, b, c in zip(runs[0], runs[1], dev):
+        assert a.tobytes() == b.tobytes() == c.tobytes()
+    tr = eng.trainer(w)                                                   # host arrays: one more wait, to deliver the outputs
+    s0 = tr.stats()
+    tr.epoch(X, km, off, y, order, 16, 20, 9)
+    assert tr.stats()["n_syncs"] - s0["n_syncs"] == 2
+    tr.close()
+
+
+def test_trained_weights_round_trip_into_inference(eng, bundled):
+    from oracle import m6a_oracle
+    m6a_oracle.build()
+    w = load_weights(HCT)
+    tr = eng.trainer(w)
+    for k in range(3):
+        tr.step(*make_batch(bundled, 32, 20, 400 + k))
+    blob, sd = tr.weights(), tr.state_dict()
+    tr.close()
+    assert int(sd["read_level_encoder.3.layers.1.num_batches_tracked"]) == 3
+    assert not np.array_equal(blob[TS.SLICES["running_mean"][0]], w[TS.SLICES["running_mean"][0]])
+    X, km, _, bag = make_batch(bundled, 50, 20, 410)
+    e2 = M6ANetEngine(weights=blob)
+    got = e2.forward(X, km, bag=bag)
+    e2.close()
+    p = m6a_oracle.encode_reads(blob, X, km, np.arange(51, dtype=np.int64) * bag).reshape(50, bag)
+    want = np.ones(50, np.float32)
+    for k in range(bag):
+        want = (want * (np.float32(1) - p[:, k])).astype(np.float32)
+    want = np.float32(1) - want
+    assert np.allclose(got, want, rtol=1e-5, atol=1e-7)                    # test_gpu_parity.py's bar for m6a_bag_forward
+
+
+def test_every_refusal_then_a_correct_call(eng, bundled):
+    X, km, off, y, order = epoch_inputs(bundled)
+    w = load_weights(HCT)
+    tr = eng.trainer(w)
+    Xb, kb, yb, bag = make_batch(bundled, 4, 20, 500)
+    S = len(off) - 1
+
+    def refused(call, word):
+        before = tr.weights()
+        with pytest.raises(_lib.M6AError) as e:
+            call()
+        assert e.value.code == -1 and word in str(e.value), str(e.value)
+        assert tr.weights().tobytes() == before.tobytes()                  # nothing is changed by a refused call
+        loss, pred = tr.step(Xb, kb, yb, bag)                              # ... and the next correct call runs
+        assert np.isfinite(loss) and pred.shape == (4,)
+
+    def step_raw(B, bag_):
+        return lambda: tr._engine._chk(tr._L.m6a_train_step(tr._h, Xb.ctypes.data, kb.ctypes.data, yb.ctypes.data, B, bag_, None, None))
+
+    refused(step_raw(4, 0), "bag must be in 1..64")
+    refused(step_raw(1, 65), "bag must be in 1..64")
+    refused(step_raw(1, 1), ">= 2 reads")
+    refused(lambda: tr.epoch(X, km, off, y, order[:33], 16, 1, 0), "fewer than 2 reads")      # the short last batch is one read
+    refused(lambda: tr.epoch(X, km, off, y, order, 1, 1, 0), "fewer than 2 reads")
+    refused(lambda: tr.epoch(X, km, off, y, order, 16, 65, 0), "bag must be in 1..64")
+    refused(lambda: tr.epoch(X, km, off, y, order, 16, 64, 0), "fewer reads than bag")       # the bundled sites start at 20 reads
+    k2 = kb.copy(); k2[2, 1] = 66
+    refused(lambda: tr.step(Xb, k2, yb, bag), "k-mer id outside 0..65")
+    k3 = km.copy(); k3[S - 1, 0] = 200
+    refused(lambda: tr.epoch(X, k3, off, y, order, 16, 20, 0), "k-mer id outside 0..65")
+    for bad in (-1, S):
+        o2 = order.copy(); o2[40] = bad
+        refused(lambda: tr.epoch(X, km, off, y, o2, 16, 20, 0), "order[40]")
+    for bad in (2.0, 0.5, np.nan):
+        y2 = yb.copy(); y2[3] = bad
+        refused(lambda: tr.step(Xb, kb, y2, bag), "label is not 0 or 1")
+        y3 = y.copy(); y3[7] = bad
+        refused(lambda: tr.epoch(X, km, off, y3, order, 16, 20, 0), "site 7: the label")
+    big = (1 << 20) // 20 + 1
+    refused(lambda: tr._engine._chk(tr._L.m6a_train_step(tr._h, Xb.ctypes.data, kb.ctypes.data, yb.ctypes.data, big, 20, None, None)), "2^20 reads")
+    refused(lambda: tr.epoch(X, km, off, y, np.zeros(2 * big, np.int64), big, 20, 0), "2^20 reads")
+    with pytest.raises(_lib.M6AError):
+        eng.trainer(w, lr=-1.0)
+    with pytest.raises(ValueError):
+        eng.trainer(w[:100])
+    tr.close()
+
+
+def test_train_command_then_inference_on_its_checkpoint(tmp_path, capsys):
+    """The command, run in this process (the interpreter and torch are already up): its files, then `inference` on a checkpoint."""
+    import json
+    import train_gen as TG
+    from m6anet_amd.__main__ import main
+    from m6anet_amd.engine import weights_from_state_dict
+    data = TG.write_dir(str(tmp_path / "data"))
+    cfg = TG.write_config(tmp_path / "train.toml", data, batch_size=16)
+    out = tmp_path / "run"
+    main(["train", "--train_config", cfg, "--save_dir", str(out), "--epochs", "2", "--save_per_epoch", "1", "--num_iterations", "2",
+          "--n_processes", "2", "--seed", "3"])
+    stdout = capsys.readouterr().out
+    assert stdout.count("Epoch:[") == 2 and stdout.count("Test Loss:") == 3
+    files = ["train_info.json", "train_results.json", "val_results.json"]
+    files += ["model_states/%d/model_states.%s" % (e, ext) for e in (1, 2) for ext in ("bin", "pt")]
+    files += ["%s.%s" % (c, ext) for c in ("avg_loss", "roc_auc", "pr_auc") for ext in ("bin", "pt")]
+    for f in files:
+        assert (out / f).is_file(), f
+    tr, va = json.load(open(out / "train_results.json")), json.load(open(out / "val_results.json"))
+    assert set(tr) == {"compute_time", "avg_loss", "roc_auc", "pr_auc"} and all(len(v) == 2 for v in tr.values())
+    assert {"y_pred", "y_true", "compute_time", "roc_auc", "pr_auc", "avg_loss"} <= set(va) and len(va["avg_loss"]) == 2
+    # a fresh noisy-or over 20 reads starts near s = 1: about 14 per unmodified site, so the loss is finite, positive and not small
+    assert all(np.isfinite(tr["avg_loss"])) and all(x > 0.0 for x in tr["avg_loss"])
+    blob = np.fromfile(out / "avg_loss.bin", np.float32)
+    assert blob.size == 7997 and np.isfinite(blob).all()
+    assert blob.tobytes() in [np.fromfile(out / "model_states" / str(e) / "model_states.bin", np.float32).tobytes() for e in (1, 2)]
+    sd = torch.load(out / "avg_loss.pt", map_location="cpu", weights_only=True)
+    assert weights_from_state_dict(sd).tobytes() == blob.tobytes()
+    inf = tmp_path / "inf"
+    with pytest.warns(UserWarning, match="model_state_dict"):
+        main(["inference", "--input_dir", data, "--out_dir", str(inf), "--model_state_dict", str(out / "avg_loss.bin"), "--num_iterations", "5",
+              "--n_processes", "2"])
+    rows = open(inf / "data.site_proba.csv").read().splitlines()
+    assert len(rows) == 1 + 101 and all(0.0 <= float(l.split(",")[3]) <= 1.0 for l in rows[1:])

@@ -182,7 +182,7 @@ bool base_is_group_start(int64_t base, int64_t bs, int64_t spb)
     return it0 == 0 || (it0 % spb) != 0;     // batch it0-1 closed a group
 }
 
-int ensure_groups(m6a_ctx *c, int64_t S, int64_t bs, int64_t spb)
+int ensure_groups(m6a_ctx *c, hipStream_t st, int64_t S, int64_t bs, int64_t spb)
 {
     const int64_t base = c->job_offset;
     if (c->goff_key.valid && c->goff_key.S == S && c->goff_key.bs == bs && c->goff_key.spb == spb &&
@@ -195,8 +195,8 @@ int ensure_groups(m6a_ctx *c, int64_t S, int64_t bs, int64_t spb)
     int64_t gmax = 0;
     for (int64_t i = 0; i < G; i++) gmax = std::max(gmax, g[i + 1] - g[i]);
     HIPCHK(c, c->goff.ensure(g.size() * sizeof(int64_t)));
-    HIPCHK(c, hipMemcpyAsync(c->goff.p, g.data(), g.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // g goes out of scope
+    HIPCHK(c, hipMemcpyAsync(c->goff.p, g.data(), g.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // g goes out of scope
     c->goff_key = {S, bs, spb, base, G, gmax, true};
     return M6A_OK;
 }
@@ -242,7 +242,7 @@ const JumpRegime *jump_regimes(int *n_out)
     return reg;
 }
 
-int launch_stream(m6a_ctx *c, uint32_t seed, int64_t len, uint32_t *raw)
+int launch_stream(m6a_ctx *c, hipStream_t st, uint32_t seed, int64_t len, uint32_t *raw)
 {
     int n_reg = 0;
     const JumpRegime *reg = jump_regimes(&n_reg);
@@ -254,7 +254,7 @@ int launch_stream(m6a_ctx *c, uint32_t seed, int64_t len, uint32_t *raw)
         for (int r = 0; r < n_reg; r++) if (len <= (int64_t)(kJumpPerRegime + 1) * reg[r].G) { use = &reg[r]; break; }
     }
     if (!use) {
-        hipLaunchKernelGGL(mt19937_kernel, dim3(1), dim3(640), 0, c->stream, seed, len, raw, (const uint32_t *)nullptr, len,
+        hipLaunchKernelGGL(mt19937_kernel, dim3(1), dim3(640), 0, st, seed, len, raw, (const uint32_t *)nullptr, len,
                            (uint32_t *)nullptr, (int64_t)0);
         HIPCHK(c, hipGetLastError());
         return M6A_OK;
@@ -265,20 +265,20 @@ int launch_stream(m6a_ctx *c, uint32_t seed, int64_t len, uint32_t *raw)
     uint32_t *xhead = (uint32_t *)c->mt_scratch.p, *hist = xhead + kXheadWords;
     uint64_t *d_polys = (uint64_t *)(hist + (size_t)kJumpPerRegime * 1078);
     if (c->mt_polys_G != use->G) {                           // the blob is static host memory: the copy may complete whenever it likes
-        HIPCHK(c, hipMemcpyAsync(d_polys, use->polys, poly_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_polys, use->polys, poly_bytes, hipMemcpyHostToDevice, st));
         c->mt_polys_G = use->G;
     }
-    hipLaunchKernelGGL(mt19937_kernel, dim3(1), dim3(640), 0, c->stream, seed, kXheadWords - 624, raw, (const uint32_t *)nullptr,
+    hipLaunchKernelGGL(mt19937_kernel, dim3(1), dim3(640), 0, st, seed, kXheadWords - 624, raw, (const uint32_t *)nullptr,
                        kXheadWords, xhead, kXheadWords);
-    hipLaunchKernelGGL(mt_jump_kernel, dim3(17, (unsigned)(n_seg - 1)), dim3(256), 0, c->stream, (const uint32_t *)xhead,
+    hipLaunchKernelGGL(mt_jump_kernel, dim3(17, (unsigned)(n_seg - 1)), dim3(256), 0, st, (const uint32_t *)xhead,
                        (const uint64_t *)d_polys, hist);
-    hipLaunchKernelGGL(mt19937_kernel, dim3((unsigned)n_seg), dim3(640), 0, c->stream, seed, len, raw, (const uint32_t *)hist, use->G,
+    hipLaunchKernelGGL(mt19937_kernel, dim3((unsigned)n_seg), dim3(640), 0, st, seed, len, raw, (const uint32_t *)hist, use->G,
                        (uint32_t *)nullptr, (int64_t)0);
     HIPCHK(c, hipGetLastError());
     return M6A_OK;
 }
 
-int ensure_raw(m6a_ctx *c, uint32_t seed, int64_t len)
+int ensure_raw(m6a_ctx *c, hipStream_t st, uint32_t seed, int64_t len)
 {
     if (c->raw_len >= len && c->raw_seed == seed) return M6A_OK;
     if (len > ((int64_t)1 << 31) - 512)
@@ -288,7 +288,7 @@ int ensure_raw(m6a_ctx *c, uint32_t seed, int64_t len)
     c->raw_len = 0;
     c->rt.valid = false;                       // the index tables describe the old stream
     HIPCHK(c, c->raw.ensure((size_t)len * 4));
-    int rc = launch_stream(c, seed, len, (uint32_t *)c->raw.p);
+    int rc = launch_stream(c, st, seed, len, (uint32_t *)c->raw.p);
     if (rc) return rc;
     c->raw_seed = seed; c->raw_len = len;
     return M6A_OK;
@@ -374,7 +374,7 @@ void build_mean_plan(int T, MeanPlan &p)
     }
 }
 
-int ensure_mean_plan(m6a_ctx *c, int T)
+int ensure_mean_plan(m6a_ctx *c, hipStream_t st, int T)
 {
     if (c->plan.T == T && c->plan_dev.p) return M6A_OK;
     build_mean_plan(T, c->plan);
@@ -384,12 +384,12 @@ int ensure_mean_plan(m6a_ctx *c, int T)
     const size_t b3 = p.reg_ctl.size() * 4;
     HIPCHK(c, c->plan_dev.ensure(b0 + b1 + b2 + b3));
     char *d = (char *)c->plan_dev.p;
-    HIPCHK(c, hipMemcpyAsync(d, p.leaf_start.data(), b0, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + b0, p.merge_after.data(), p.merge_after.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d, p.leaf_start.data(), b0, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d + b0, p.merge_after.data(), p.merge_after.size(), hipMemcpyHostToDevice, st));
     if (!p.row_meta.empty())
-        HIPCHK(c, hipMemcpyAsync(d + b0 + b1, p.row_meta.data(), p.row_meta.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + b0 + b1 + b2, p.reg_ctl.data(), b3, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(d + b0 + b1, p.row_meta.data(), p.row_meta.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d + b0 + b1 + b2, p.reg_ctl.data(), b3, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     c->plan_off[0] = 0; c->plan_off[1] = b0; c->plan_off[2] = b0 + b1; c->plan_off[3] = b0 + b1 + b2;
     c->tab_key.valid = false;           // the table layout follows the plan
     return M6A_OK;
@@ -438,11 +438,11 @@ int rtab_missing(const m6a_ctx *c, uint32_t seed, int T, int K, int64_t need, co
 
 // Builds the tables of every bag size in `hist` that lacks one.  *usable = false (and M6A_OK) when the tables would
 // not fit the memory budget: the caller then takes the scan kernels.
-int ensure_rtab(m6a_ctx *c, uint32_t seed, int T, int K, int64_t gmax, const uint32_t *hist, bool *usable)
+int ensure_rtab(m6a_ctx *c, hipStream_t st, uint32_t seed, int T, int K, int64_t gmax, const uint32_t *hist, bool *usable)
 {
     *usable = false;
     const int64_t need = stream_need(gmax, T, K);
-    int rc = ensure_raw(c, seed, need);
+    int rc = ensure_raw(c, st, seed, need);
     if (rc) return rc;
     auto &rt = c->rt;
     const int64_t n_blk = c->raw_len / 64;
@@ -477,9 +477,9 @@ int ensure_rtab(m6a_ctx *c, uint32_t seed, int T, int K, int64_t gmax, const uin
         if (hipMalloc((void **)&nC, (size_t)new_cap * c_stride * 2 + 64) != hipSuccess) { (void)hipGetLastError(); return M6A_OK; }
         if (hipMalloc((void **)&nRS, (size_t)new_cap * (n_blk + 1) * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(nC); return M6A_OK; }
         if (!fresh && rt.used) {
-            HIPCHK(c, hipMemcpyAsync(nC, rt.C, (size_t)rt.used * c_stride * 2, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(nRS, rt.RS, (size_t)rt.used * (n_blk + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipMemcpyAsync(nC, rt.C, (size_t)rt.used * c_stride * 2, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(nRS, rt.RS, (size_t)rt.used * (n_blk + 1) * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipStreamSynchronize(st));
             // hipFree waits for the WHOLE device: behind m6a_infer's running encoder that was 3.3 ms of the first ragged call
             // (profiles/r04_first_call_ragged.txt), and it kept the build kernels below from being queued.  The outgrown arena
             // is dropped at the next point where the context is idle anyway (m6a_sync / m6a_destroy).
@@ -488,8 +488,8 @@ int ensure_rtab(m6a_ctx *c, uint32_t seed, int T, int K, int64_t gmax, const uin
         rt.C = nC; rt.RS = nRS; rt.cap = new_cap;
         if (fresh) {
             // slot 0: a table of zeros for bags of one read (randint(0,1) draws no words, every draw is read 0)
-            HIPCHK(c, hipMemsetAsync(rt.C, 0, (size_t)c_stride * 2, c->stream));
-            HIPCHK(c, hipMemsetAsync(rt.RS, 0, (size_t)(n_blk + 1) * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(rt.C, 0, (size_t)c_stride * 2, st));
+            HIPCHK(c, hipMemsetAsync(rt.RS, 0, (size_t)(n_blk + 1) * 4, st));
             rt.used = 1;
         }
         rt.valid = true; rt.seed = seed; rt.A = (int64_t)T * K; rt.n_blk = n_blk;
@@ -499,18 +499,18 @@ int ensure_rtab(m6a_ctx *c, uint32_t seed, int T, int K, int64_t gmax, const uin
         for (size_t i = 0; i < todo.size(); i++) { bn[i] = todo[i]; bs[i] = rt.used; rt.slot_of_n[todo[i]] = rt.used++; }
         HIPCHK(c, c->ctl_dev.ensure(kCtlWords * 4));
         int32_t *d_bn = (int32_t *)c->ctl_dev.p + (ctl_build_n(c) - (int32_t *)c->h_ctl);
-        HIPCHK(c, hipMemcpyAsync(d_bn, bn, (size_t)2 * M6A_RTAB_MAX_N * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_bn, bn, (size_t)2 * M6A_RTAB_MAX_N * 4, hipMemcpyHostToDevice, st));
         RtabBuild b;
         b.raw = (const uint32_t *)c->raw.p; b.n_blk = (uint32_t)n_blk; b.build_n = d_bn; b.build_slot = d_bn + M6A_RTAB_MAX_N;
         b.C = rt.C; b.RS = rt.RS; b.c_stride = c_stride; b.n_build = (int)todo.size();
         const unsigned gx = (unsigned)std::min<int64_t>((n_blk + 63) / 64, 65535);   // 4 waves x 16 blocks per workgroup
         const unsigned gn = (unsigned)((todo.size() + 7) / 8);                        // RTAB_GROUP = 8 bag sizes share every stream read
-        hipLaunchKernelGGL(rtab_count_kernel, dim3(gn, gx), dim3(256), 0, c->stream, b);
-        hipLaunchKernelGGL(rtab_scan_kernel, dim3((unsigned)todo.size()), dim3(256), 0, c->stream, b);
-        hipLaunchKernelGGL(rtab_fill_kernel, dim3(gn, gx), dim3(256), 0, c->stream, b);
+        hipLaunchKernelGGL(rtab_count_kernel, dim3(gn, gx), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(rtab_scan_kernel, dim3((unsigned)todo.size()), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(rtab_fill_kernel, dim3(gn, gx), dim3(256), 0, st, b);
         HIPCHK(c, hipGetLastError());
         // the pinned build list is reused by the next call: it must have been consumed
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(st));
     }
     *usable = true;
     return M6A_OK;
@@ -520,20 +520,20 @@ int ensure_rtab(m6a_ctx *c, uint32_t seed, int T, int K, int64_t gmax, const uin
 // [j*T*K, (j+1)*T*K) of the accepted sequence C_n -- a slice of the GPU-built index table of bag size n (both uniform
 // pooling kernels cut their tables out of it; nothing on an inference path runs a host generator).  Builds C_n if it is
 // missing and checks that the stream holds jmax sites' worth of accepted draws.  *C = nullptr for n = 1 (no draws).
-int uniform_slice(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax, const uint16_t **C)
+int uniform_slice(m6a_ctx *c, hipStream_t st, uint32_t seed, int n, int T, int K, int jmax, const uint16_t **C)
 {
     *C = nullptr;
     if (n < 2) return M6A_OK;
     std::vector<uint32_t> hist(M6A_HIST_BINS, 0u);
     hist[n] = 1;
     bool usable = false;
-    int rc = ensure_rtab(c, seed, T, K, jmax, hist.data(), &usable);
+    int rc = ensure_rtab(c, st, seed, T, K, jmax, hist.data(), &usable);
     if (rc) return rc;
     if (!usable) return fail(c, M6A_ENOMEM, "no device memory for the index table of bag size %d", n);
     const int64_t slot = c->rt.slot_of_n[n], A = (int64_t)T * K;
     uint32_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, c->rt.RS + slot * (c->rt.n_blk + 1) + c->rt.n_blk, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&total, c->rt.RS + slot * (c->rt.n_blk + 1) + c->rt.n_blk, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     if ((int64_t)total < A * jmax) return fail(c, M6A_ESTREAM, "MT19937 stream too short for a flush group");
     *C = c->rt.C + slot * c->rt.n_blk * 64;
     return M6A_OK;
@@ -542,7 +542,7 @@ int uniform_slice(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax, cons
 // accepted indices for pool_reg_kernel: idx16[j][T + 8][K] 16-bit words (0x1000 | 2 x index: the draw's M0, a register pair
 // per bag entry), iterations in order, one round of zero padding for the prefetch past the end.  Bags of one read: all zero
 // (no operand indexed: every draw reads entry 0).
-int ensure_table_reg(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax)
+int ensure_table_reg(m6a_ctx *c, hipStream_t st, uint32_t seed, int n, int T, int K, int jmax)
 {
     auto &k = c->tab_reg_key;
     if (k.valid && k.seed == seed && k.n == n && k.T == T && k.K == K && k.jmax >= jmax) return M6A_OK;
@@ -550,13 +550,13 @@ int ensure_table_reg(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax)
     const size_t per_j = (size_t)(T + 8) * K;              // 16-bit words per position; K = 20: 40 bytes per iteration
     const size_t bytes = (size_t)jmax * per_j * 2 + 4096;  // the kernel's look-ahead touches up to 2 KB past the last row
     HIPCHK(c, c->tab_reg.ensure(bytes));
-    HIPCHK(c, hipMemsetAsync(c->tab_reg.p, 0, bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->tab_reg.p, 0, bytes, st));
     const uint16_t *C = nullptr;
-    int rc = uniform_slice(c, seed, n, T, K, jmax, &C);
+    int rc = uniform_slice(c, st, seed, n, T, K, jmax, &C);
     if (rc) return rc;
     if (C) {
         const int64_t A = (int64_t)T * K;
-        hipLaunchKernelGGL(rtab_to_reg_table_kernel, dim3((unsigned)((A * jmax + 255) / 256)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(rtab_to_reg_table_kernel, dim3((unsigned)((A * jmax + 255) / 256)), dim3(256), 0, st,
                            C, A, (int64_t)per_j, jmax, (uint16_t *)c->tab_reg.p);
         HIPCHK(c, hipGetLastError());
     }
@@ -566,9 +566,9 @@ int ensure_table_reg(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax)
 
 // accepted-index table of pool_table_kernel (the LDS-gather fallback for uniform bags): tab[j][row][plane][lane],
 // 4 byte offsets (8 * index) per dword, lane = accumulator chain of the pairwise sum (plan_iteration)
-int ensure_table(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax)
+int ensure_table(m6a_ctx *c, hipStream_t st, uint32_t seed, int n, int T, int K, int jmax)
 {
-    int rc = ensure_mean_plan(c, T);    // invalidates the key when the plan changes
+    int rc = ensure_mean_plan(c, st, T);    // invalidates the key when the plan changes
     if (rc) return rc;
     auto &k = c->tab_key;
     if (k.valid && k.seed == seed && k.n == n && k.T == T && k.K == K && k.jmax >= jmax) return M6A_OK;
@@ -582,16 +582,16 @@ int ensure_table(m6a_ctx *c, uint32_t seed, int n, int T, int K, int jmax)
     const size_t words = (size_t)jmax * rows * 5 * 64;
     HIPCHK(c, c->tab.ensure(words * 4 + c->iter_of.size() * 4));
     int *d_iter = (int *)((uint32_t *)c->tab.p + words);
-    HIPCHK(c, hipMemcpyAsync(d_iter, c->iter_of.data(), c->iter_of.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_iter, c->iter_of.data(), c->iter_of.size() * 4, hipMemcpyHostToDevice, st));
     const uint16_t *C = nullptr;
-    rc = uniform_slice(c, seed, n, T, K, jmax, &C);
+    rc = uniform_slice(c, st, seed, n, T, K, jmax, &C);
     if (rc) return rc;
     if (C) {
-        hipLaunchKernelGGL(rtab_to_lds_table_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(rtab_to_lds_table_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st,
                            C, (int64_t)T * K, K, rows, jmax, (const int *)d_iter, (uint32_t *)c->tab.p);
         HIPCHK(c, hipGetLastError());
     } else {
-        HIPCHK(c, hipMemsetAsync(c->tab.p, 0, words * 4, c->stream));   // bags of one read: every draw is read 0
+        HIPCHK(c, hipMemsetAsync(c->tab.p, 0, words * 4, st));   // bags of one read: every draw is read 0
     }
     k = {seed, n, T, K, jmax, true};
     return M6A_OK;
@@ -722,10 +722,10 @@ RtabUse rtab_use(m6a_ctx *c, int64_t nmax, uint32_t si_base = 0, uint32_t si_cou
 
 // Ragged bags, first half: decide whether this call pools through the per-bag-size index tables, build the ones
 // that are missing and launch the preparation -- every site's rank in its table and the bag-size order -- all on
-// the context's current stream.  Needs only off[] and the histogram of query_bags / host_bag_range, not the read
-// probabilities, so m6a_infer runs it on the side stream next to the encoder (pool_setup_aside; a latency chain on a
-// few waves: 0.1 ms that would otherwise sit between the two big kernels).  a: off, goff, n_groups, n_sites, T, K, err.
-int rtab_prepare(m6a_ctx *c, PoolArgs a, int64_t nmax, int64_t gmax, uint32_t seed, bool *use)
+// st.  Needs only off[] and the histogram of query_bags / host_bag_range, not the read probabilities, so m6a_infer
+// runs it on the side stream next to the encoder (a latency chain on a few waves: 0.1 ms that would otherwise sit
+// between the two big kernels).  a: off, goff, n_groups, n_sites, T, K, err.
+int rtab_prepare(m6a_ctx *c, hipStream_t st, PoolArgs a, int64_t nmax, int64_t gmax, uint32_t seed, bool *use)
 {
     *use = false;
     const int T = a.T, K = a.K;
@@ -749,7 +749,7 @@ int rtab_prepare(m6a_ctx *c, PoolArgs a, int64_t nmax, int64_t gmax, uint32_t se
     bool use_rtab = c->scan_driver == 3 || missing == 0 || c->rt_credit + S >= (int64_t)16 * missing;
     if (use_rtab) c->rt_credit = 0; else c->rt_credit += S;
     if (!use_rtab) return M6A_OK;
-    int rc = ensure_rtab(c, seed, T, K, gmax, c->h_hist, &use_rtab);      // false: over the memory budget
+    int rc = ensure_rtab(c, st, seed, T, K, gmax, c->h_hist, &use_rtab);      // false: over the memory budget
     if (rc) return rc;
     if (!use_rtab) return M6A_OK;
     a.raw = (const uint32_t *)c->raw.p; a.raw_len = c->raw_len;
@@ -761,7 +761,7 @@ int rtab_prepare(m6a_ctx *c, PoolArgs a, int64_t nmax, int64_t gmax, uint32_t se
     // sizes are dealt to the eighths by n mod 8, so every XCD gets the whole range of sizes and still owns the
     // tables of "its" sizes; largest first inside an eighth, so the longest sites do not start last.
     HIPCHK(c, hipEventSynchronize(c->ev_ctl));                // the previous call's upload from h_ctl (calls need not block any more)
-    // Bags above M6A_RTAB_SMALL_N reads come first, as a block of their own: launch_pool gives them a launch with the
+    // Bags above M6A_RTAB_SMALL_N reads come first, as a block of their own: pool_run gives them a launch with the
     // LDS bag they need (16 KB at 4 096 reads, nine sites per CU) and everybody else one with a small bag.
     uint32_t *cur = ctl_cursor(c);
     uint32_t run = 0;
@@ -769,180 +769,170 @@ int rtab_prepare(m6a_ctx *c, PoolArgs a, int64_t nmax, int64_t gmax, uint32_t se
     for (int x = 0; x < 8; x++)
         for (int n = M6A_RTAB_SMALL_N - ((M6A_RTAB_SMALL_N - x) & 7); n >= 0; n -= 8) { cur[n] = run; run += c->h_hist[n]; }
     std::memcpy(ctl_slot(c), c->rt.slot_of_n, sizeof c->rt.slot_of_n);
-    HIPCHK(c, hipMemcpyAsync(c->ctl_dev.p, c->h_ctl, (size_t)(M6A_HIST_BINS + M6A_RTAB_MAX_N + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_ctl, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ctl_dev.p, c->h_ctl, (size_t)(M6A_HIST_BINS + M6A_RTAB_MAX_N + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->ev_ctl, st));
     const RtabUse u = rtab_use(c, nmax);
     const unsigned n_order_blocks = (unsigned)((S + 255) / 256);
     const unsigned n_chain_blocks = (unsigned)std::min<int64_t>((a.n_groups + 3) / 4, (int64_t)c->n_cu * 16);
-    hipLaunchKernelGGL(rtab_prep_kernel, dim3(n_order_blocks + n_chain_blocks), dim3(256), 0, c->stream, a, u,
+    hipLaunchKernelGGL(rtab_prep_kernel, dim3(n_order_blocks + n_chain_blocks), dim3(256), 0, st, a, u,
                        (uint32_t *)c->ctl_dev.p, (uint32_t *)c->rt_order.p, n_order_blocks);
     HIPCHK(c, hipGetLastError());
     *use = true;
     return M6A_OK;
 }
 
-// dry: do everything the pooling of this call needs EXCEPT the pooling kernels -- flush-group offsets, the mean plan,
-// the MT19937 stream, index tables, and for ragged bags the rank / order preparation -- on the context's current stream.
-// m6a_infer runs it on the side stream while the encoder is busy (pool_setup_aside), then calls again for the kernels.
-int launch_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr,
-                uint32_t seed, int64_t bs, int64_t spb, float *site, double *mod, bool dry)
-{
-    // did a dry run already do the ragged preparation of exactly this call?  One-shot.
-    const bool prepared = c->prep.ready && c->prep.off == off && c->prep.S == S && c->prep.T == T && c->prep.K == K &&
-                          c->prep.seed == seed && c->prep.bs == bs && c->prep.spb == spb;
-    c->prep.ready = false;
-    if (S <= 0) return M6A_OK;
-    int rc = ensure_groups(c, S, bs, spb);
-    if (rc) return rc;
-    const int64_t nmin = c->bag_min, nmax = c->bag_max;      // from query_bags()
-    if (nmin < 0 || nmax > 0x7fffffff) return fail(c, M6A_EINVAL, "off[] is not a non-decreasing CSR array");
+// What pool_plan decided for one call and what pool_run needs to launch it: nothing here depends on the read
+// probabilities or the outputs, so the plan can be made on another stream while the encoder still runs.
+struct PoolPlan {
+    enum Kind { none, table_reg, table, ragged_table, scan_group, scan_site } kind = none;   // none: no sites, no launch
+    PoolArgs a = {};                          // everything but read_prob, site_prob, mod_ratio, thr and clk
+    unsigned blocks = 0, start_blocks = 0;    // grid of the pooling kernel; scan_site: of pool_scan_start_kernel in front of it
+    size_t lds = 0;                           // dynamic LDS of the pooling kernel (ragged_table sizes its own from the bag caps)
+    int64_t n_big = 0, cap_big = 0, cap_small = 0;   // ragged_table: bags above M6A_RTAB_SMALL_N reads, and the largest bag of either launch
+};
 
-    PoolArgs a;
-    memset(&a, 0, sizeof a);
-    a.read_prob = rp; a.off = off; a.goff = (const int64_t *)c->goff.p; a.site_prob = site; a.mod_ratio = mod;
-    a.err = c->d_err; a.n_groups = c->goff_key.G; a.n_sites = S; a.T = T; a.K = K; a.thr = thr;
-    a.clk = dry ? nullptr : c->prof.clk_for(1);
+// Everything the pooling of this call needs EXCEPT the pooling kernels, on st: flush-group offsets, the mean plan, the
+// MT19937 stream, index tables, for ragged bags the rank / order preparation -- and with them the choice of the kernel.
+// c->bag_min / bag_max / n_reads / h_hist must describe `off` (query_bags / host_bag_range ran for this call).
+int pool_plan(m6a_ctx *c, hipStream_t st, const int64_t *off, int64_t S, int T, int K, uint32_t seed, int64_t bs, int64_t spb,
+              PoolPlan *p)
+{
+    *p = PoolPlan();
+    PoolArgs &a = p->a;
+    if (S <= 0) return M6A_OK;
+    int rc = ensure_groups(c, st, S, bs, spb);
+    if (rc) return rc;
+    const int64_t nmin = c->bag_min, nmax = c->bag_max;
+    if (nmin < 0 || nmax > 0x7fffffff) return fail(c, M6A_EINVAL, "off[] is not a non-decreasing CSR array");
+    a.off = off; a.goff = (const int64_t *)c->goff.p; a.err = c->d_err;
+    a.n_groups = c->goff_key.G; a.n_sites = S; a.T = T; a.K = K;
     const int64_t gmax = c->goff_key.gmax;
 
-    rc = ensure_mean_plan(c, T);
+    rc = ensure_mean_plan(c, st, T);
     if (rc) return rc;
+    plan_args(c, a);
     const bool uniform = nmin == nmax && nmin >= 1 && nmin <= M6A_TABLE_MAX_N && K == 20 && gmax <= 4096;
     // register kernel: stack in 8 register quads, 32-bit byte offsets into read_prob, table <= 256 MB
     const bool reg_ok = uniform && c->plan.depth <= M6A_REG_STACK && c->n_reads < (int64_t)1 << 30 &&
                         (int64_t)gmax * (T + 8) * K * 2 <= (int64_t)256 << 20;
     if (uniform && reg_ok && c->table_variant != 1) {
-        rc = ensure_table_reg(c, seed, (int)nmin, T, K, (int)gmax);
+        rc = ensure_table_reg(c, st, seed, (int)nmin, T, K, (int)gmax);
         if (rc) return rc;
-        plan_args(c, a);
         a.tab = (const uint32_t *)c->tab_reg.p; a.uniform_n = (int)nmin; a.jmax = (int)gmax;
-        if (dry) return M6A_OK;
-        c->pool_variant = "table-reg";
-        prof_begin(c, 1);
         // one wavefront = position j of 256 flush groups (4 sites per lane); the grid is 8 x ceil(items / 8) so that every
         // XCD takes a contiguous run of items (m6a_pool_reg.hip: the waves that share cache lines of read_prob share an L2)
         const int64_t wpj = (a.n_groups + 255) / 256;
         a.reg_items = wpj * a.jmax;
-        hipLaunchKernelGGL(pool_reg_kernel, dim3((unsigned)((a.reg_items + 7) / 8 * 8)), dim3(64), 0, c->stream, a);
-        prof_end(c, 1);
-    } else if (uniform && c->plan.max_merge <= 15) {
-        rc = ensure_table(c, seed, (int)nmin, T, K, (int)gmax);
+        p->blocks = (unsigned)((a.reg_items + 7) / 8 * 8);
+        p->kind = PoolPlan::table_reg;
+        return M6A_OK;
+    }
+    if (uniform && c->plan.max_merge <= 15) {
+        rc = ensure_table(c, st, seed, (int)nmin, T, K, (int)gmax);
         if (rc) return rc;
-        if (dry) return M6A_OK;
-        plan_args(c, a);
         a.tab = (const uint32_t *)c->tab.p; a.uniform_n = (int)nmin; a.jmax = (int)gmax;
         // workgroups are bound to a position j: jmax x nbj of them, 5 resident per CU (LDS)
         const int64_t gblocks = (a.n_groups + 7) / 8;
         int64_t nbj = std::max<int64_t>(1, ((int64_t)c->n_cu * 5 + a.jmax - 1) / a.jmax);
         nbj = std::min<int64_t>(nbj, (gblocks + 3) / 4);
-        const unsigned blocks = (unsigned)(nbj * a.jmax);
-        c->pool_variant = "table";
-        prof_begin(c, 1);
-        const size_t mean_lds = (size_t)4 * (128 + 8 * a.stack_depth) * sizeof(float);
-        hipLaunchKernelGGL(pool_table_kernel, dim3(blocks), dim3(256), mean_lds, c->stream, a);
-        prof_end(c, 1);
-    } else {
-        // Ragged bags.  Default: per-bag-size index tables (pool_rtab_kernel) when every bag fits one (n <= 4096)
-        // and the work seen so far pays for the tables still lacking (a table = one pass over the stream, about
-        // what 50 sites cost the scan kernels); otherwise the scan kernels replay the stream per site.
-        const int64_t need = stream_need(gmax, T, K);
-        bool use_rtab = false;
-        if (prepared && !dry) {
-            use_rtab = c->prep.use;                           // the dry run decided (and, if so, built and launched)
-        } else {
-            rc = rtab_prepare(c, a, nmax, gmax, seed, &use_rtab);
-            if (rc) return rc;
-        }
-        if (dry) {
-            c->prep.ready = true; c->prep.use = use_rtab;
-            c->prep.off = off; c->prep.S = S; c->prep.bs = bs; c->prep.spb = spb; c->prep.T = T; c->prep.K = K; c->prep.seed = seed;
-            if (!use_rtab) {                                  // the scan kernels' share of the set-up
-                rc = ensure_raw(c, seed, need);
-                if (rc) return rc;
-                HIPCHK(c, c->start_pos.ensure((size_t)S * sizeof(uint32_t)));
-            }
-            return M6A_OK;
-        }
-        if (use_rtab) {
-            plan_args(c, a);
-            a.raw = (const uint32_t *)c->raw.p; a.raw_len = c->raw_len;
-            c->pool_variant = "ragged-table";
-            // positions [0, n_big) of the bag-size order hold the bags above M6A_RTAB_SMALL_N reads (rtab_prepare)
-            int64_t n_big = 0;
-            for (int n = M6A_RTAB_SMALL_N + 1; n < M6A_HIST_BINS; n++) n_big += c->h_hist[n];
-            prof_begin(c, 1);
-            auto launch = [&](int64_t base, int64_t count, int64_t cap_n) {
-                if (count <= 0) return;
-                const RtabUse u = rtab_use(c, cap_n, (uint32_t)base, (uint32_t)count);
-                const size_t lds = (size_t)(u.bag_cap + 16 + M6A_MEAN_STACK) * sizeof(float);
-                const unsigned blocks = (unsigned)((count + 7) / 8 * 8);    // one wavefront (workgroup) per site
-                if (K == 20) hipLaunchKernelGGL(pool_rtab_kernel<20>, dim3(blocks), dim3(64), lds, c->stream, a, u);
-                else hipLaunchKernelGGL(pool_rtab_kernel<0>, dim3(blocks), dim3(64), lds, c->stream, a, u);
-            };
-            launch(0, n_big, nmax);
-            launch(n_big, S - n_big, std::min<int64_t>(nmax, M6A_RTAB_SMALL_N));
-            prof_end(c, 1);
-            HIPCHK(c, hipGetLastError());
-            return M6A_OK;
-        }
-        rc = ensure_raw(c, seed, need);
-        if (rc) return rc;
-        plan_args(c, a);
-        a.raw = (const uint32_t *)c->raw.p; a.raw_len = c->raw_len;
-        HIPCHK(c, c->start_pos.ensure((size_t)S * sizeof(uint32_t)));
-        a.start_pos = (uint32_t *)c->start_pos.p;
-        // LDS bag sized to the largest bag of this call (bags beyond M6A_BAG_LDS gather from global)
-        // a power of two: a masked stream word (< 2^ceil(log2 n)) is then always a valid LDS bag index, so the
-        // fast path gathers without clamping
-        int64_t cap = 64;
-        while (cap < nmax && cap < M6A_BAG_LDS) cap *= 2;
-        a.bag_cap = (int)cap;
-        const size_t lds = (size_t)4 * (a.bag_cap + (32 * K + 256) * 5 / 4 + 32 + M6A_MEAN_STACK) * sizeof(float);
-        // resident workgroups per CU: what LDS allows, but with big bags (random gathers over >= 1 KB per wave) five
-        // measured best -- 4.19 ms against 4.6 ms at six on the 50..500-read shape; small bags keep gaining up to 6-8
-        const int64_t wg_per_cu = std::max<int64_t>(1, std::min<int64_t>(a.bag_cap >= 256 ? 5 : 8, (160 * 1024) / (int64_t)lds));
-        const int64_t wave_slots = (int64_t)c->n_cu * wg_per_cu * 4;
-        // enough flush groups to fill most of the chip: walk each group's sites in sequence (the stream is
-        // scanned once); otherwise buy 32x the parallelism with a counting pass that finds every site's start
-        // position first.  Measured on 50..500-read bags: at 0.3 x the wave slots the per-site driver wins
-        // (1.3 vs 1.9 ms), at 0.6 x they tie, at 1.2 x the per-group driver is 11 % ahead, at 5 x 22 %.
-        const bool by_group = c->scan_driver ? c->scan_driver == 1 : a.n_groups * 5 >= wave_slots * 3;
-        c->pool_variant = by_group ? "scan-group" : "scan-site";
-        prof_begin(c, 1);
-        if (by_group) {
-            const unsigned blocks = (unsigned)std::min<int64_t>((a.n_groups + 3) / 4, wave_slots / 4);
-            if (K == 20) hipLaunchKernelGGL(pool_scan_group_kernel<20>, dim3(blocks), dim3(256), lds, c->stream, a);
-            else hipLaunchKernelGGL(pool_scan_group_kernel<0>, dim3(blocks), dim3(256), lds, c->stream, a);
-        } else {
-            hipLaunchKernelGGL(pool_scan_start_kernel, dim3((unsigned)std::min<int64_t>((a.n_groups + 3) / 4, (int64_t)c->n_cu * 8)),
-                               dim3(256), 0, c->stream, a);
-            const unsigned blocks = (unsigned)std::min<int64_t>((S + 3) / 4, wave_slots / 4);
-            if (K == 20) hipLaunchKernelGGL(pool_scan_site_kernel<20>, dim3(blocks), dim3(256), lds, c->stream, a);
-            else hipLaunchKernelGGL(pool_scan_site_kernel<0>, dim3(blocks), dim3(256), lds, c->stream, a);
-        }
-        prof_end(c, 1);
+        p->blocks = (unsigned)(nbj * a.jmax);
+        p->lds = (size_t)4 * (128 + 8 * a.stack_depth) * sizeof(float);
+        p->kind = PoolPlan::table;
+        return M6A_OK;
     }
+    // Ragged bags: the index tables where rtab_prepare takes them, the scan kernels otherwise.
+    bool use_rtab = false;
+    rc = rtab_prepare(c, st, a, nmax, gmax, seed, &use_rtab);
+    if (rc) return rc;
+    if (use_rtab) {
+        a.raw = (const uint32_t *)c->raw.p; a.raw_len = c->raw_len;
+        // positions [0, n_big) of the bag-size order hold the bags above M6A_RTAB_SMALL_N reads (rtab_prepare)
+        for (int n = M6A_RTAB_SMALL_N + 1; n < M6A_HIST_BINS; n++) p->n_big += c->h_hist[n];
+        p->cap_big = nmax; p->cap_small = std::min<int64_t>(nmax, M6A_RTAB_SMALL_N);
+        p->kind = PoolPlan::ragged_table;
+        return M6A_OK;
+    }
+    rc = ensure_raw(c, st, seed, stream_need(gmax, T, K));
+    if (rc) return rc;
+    a.raw = (const uint32_t *)c->raw.p; a.raw_len = c->raw_len;
+    HIPCHK(c, c->start_pos.ensure((size_t)S * sizeof(uint32_t)));
+    a.start_pos = (uint32_t *)c->start_pos.p;
+    // LDS bag sized to the largest bag of this call (bags beyond M6A_BAG_LDS gather from global)
+    // a power of two: a masked stream word (< 2^ceil(log2 n)) is then always a valid LDS bag index, so the
+    // fast path gathers without clamping
+    int64_t cap = 64;
+    while (cap < nmax && cap < M6A_BAG_LDS) cap *= 2;
+    a.bag_cap = (int)cap;
+    p->lds = (size_t)4 * (a.bag_cap + (32 * K + 256) * 5 / 4 + 32 + M6A_MEAN_STACK) * sizeof(float);
+    // resident workgroups per CU: what LDS allows, but with big bags (random gathers over >= 1 KB per wave) five
+    // measured best -- 4.19 ms against 4.6 ms at six on the 50..500-read shape; small bags keep gaining up to 6-8
+    const int64_t wg_per_cu = std::max<int64_t>(1, std::min<int64_t>(a.bag_cap >= 256 ? 5 : 8, (160 * 1024) / (int64_t)p->lds));
+    const int64_t wave_slots = (int64_t)c->n_cu * wg_per_cu * 4;
+    // enough flush groups to fill most of the chip: walk each group's sites in sequence (the stream is
+    // scanned once); otherwise buy 32x the parallelism with a counting pass that finds every site's start
+    // position first.  Measured on 50..500-read bags: at 0.3 x the wave slots the per-site driver wins
+    // (1.3 vs 1.9 ms), at 0.6 x they tie, at 1.2 x the per-group driver is 11 % ahead, at 5 x 22 %.
+    const bool by_group = c->scan_driver ? c->scan_driver == 1 : a.n_groups * 5 >= wave_slots * 3;
+    p->kind = by_group ? PoolPlan::scan_group : PoolPlan::scan_site;
+    p->blocks = (unsigned)std::min<int64_t>(((by_group ? a.n_groups : S) + 3) / 4, wave_slots / 4);
+    p->start_blocks = (unsigned)std::min<int64_t>((a.n_groups + 3) / 4, (int64_t)c->n_cu * 8);   // the counting pass of scan_site
+    return M6A_OK;
+}
+
+// The pooling kernels of a plan, on the context's stream: no allocation, no copy, no host synchronisation here.
+int pool_run(m6a_ctx *c, const PoolPlan &p, const float *rp, float thr, float *site, double *mod)
+{
+    if (p.kind == PoolPlan::none) return M6A_OK;
+    static const char *const names[] = {"none", "table-reg", "table", "ragged-table", "scan-group", "scan-site"};
+    PoolArgs a = p.a;
+    a.read_prob = rp; a.site_prob = site; a.mod_ratio = mod; a.thr = thr;
+    a.clk = c->prof.clk_for(1);
+    c->pool_variant = names[p.kind];
+    const bool k20 = a.K == 20;               // the kernels that draw per site have an instantiation for the reference's 20 samples
+    prof_begin(c, 1);
+    switch (p.kind) {
+    case PoolPlan::none: break;
+    case PoolPlan::table_reg:
+        hipLaunchKernelGGL(pool_reg_kernel, dim3(p.blocks), dim3(64), 0, c->stream, a);
+        break;
+    case PoolPlan::table:
+        hipLaunchKernelGGL(pool_table_kernel, dim3(p.blocks), dim3(256), p.lds, c->stream, a);
+        break;
+    case PoolPlan::ragged_table: {
+        auto launch = [&](int64_t base, int64_t count, int64_t cap_n) {
+            if (count <= 0) return;
+            const RtabUse u = rtab_use(c, cap_n, (uint32_t)base, (uint32_t)count);
+            const size_t lds = (size_t)(u.bag_cap + 16 + M6A_MEAN_STACK) * sizeof(float);
+            const unsigned blocks = (unsigned)((count + 7) / 8 * 8);    // one wavefront (workgroup) per site
+            if (k20) hipLaunchKernelGGL(pool_rtab_kernel<20>, dim3(blocks), dim3(64), lds, c->stream, a, u);
+            else hipLaunchKernelGGL(pool_rtab_kernel<0>, dim3(blocks), dim3(64), lds, c->stream, a, u);
+        };
+        launch(0, p.n_big, p.cap_big);
+        launch(p.n_big, a.n_sites - p.n_big, p.cap_small);
+        break;
+    }
+    case PoolPlan::scan_group:
+        if (k20) hipLaunchKernelGGL(pool_scan_group_kernel<20>, dim3(p.blocks), dim3(256), p.lds, c->stream, a);
+        else hipLaunchKernelGGL(pool_scan_group_kernel<0>, dim3(p.blocks), dim3(256), p.lds, c->stream, a);
+        break;
+    case PoolPlan::scan_site:
+        hipLaunchKernelGGL(pool_scan_start_kernel, dim3(p.start_blocks), dim3(256), 0, c->stream, a);
+        if (k20) hipLaunchKernelGGL(pool_scan_site_kernel<20>, dim3(p.blocks), dim3(256), p.lds, c->stream, a);
+        else hipLaunchKernelGGL(pool_scan_site_kernel<0>, dim3(p.blocks), dim3(256), p.lds, c->stream, a);
+        break;
+    }
+    prof_end(c, 1);
     HIPCHK(c, hipGetLastError());
     return M6A_OK;
 }
 
-// m6a_infer, device pointers, after the encoder has been launched: the pooling's set-up (a dry launch_pool) runs on the
-// side stream next to it -- in the steady state that is the ragged rank / order kernel (0.1 ms), in the first call the
-// MT19937 stream and the index tables as well (milliseconds, incl. host syncs that now wait for the side stream only).
-// The caller recorded ev_main on the context's stream BEFORE the encoder: the set-up orders itself behind everything
-// queued up to there (the previous call's pooling still reads what it rebuilds), not behind the encoder.
-int pool_setup_aside(m6a_ctx *c, const int64_t *off, int64_t S, int T, int K, uint32_t seed, int64_t bs, int64_t spb)
+// set-up and kernels on the context's stream (device-pointer m6a_infer plans on the side stream instead, next to its encoder)
+int launch_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr,
+                uint32_t seed, int64_t bs, int64_t spb, float *site, double *mod)
 {
-    c->prep.ready = false;
-    if (S <= 0 || !c->s_prep) return M6A_OK;
-    HIPCHK(c, hipStreamWaitEvent(c->s_prep, c->ev_main, 0));
-    hipStream_t main_stream = c->stream;
-    c->stream = c->s_prep;
-    const int rc = launch_pool(c, nullptr, off, S, T, K, 0.0f, seed, bs, spb, nullptr, nullptr, true);
-    c->stream = main_stream;
-    if (rc) { c->prep.ready = false; return rc; }
-    HIPCHK(c, hipEventRecord(c->ev_prep, c->s_prep));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_prep, 0));
-    return M6A_OK;
+    PoolPlan p;
+    const int rc = pool_plan(c, c->stream, off, S, T, K, seed, bs, spb, &p);
+    return rc ? rc : pool_run(c, p, rp, thr, site, mod);
 }
 
 // smallest and largest bag of a CSR array.  The baseline x86-64 target has no 64-bit vector compare, so the plain loop stays
@@ -1047,15 +1037,14 @@ void warm_default(m6a_ctx *c)
     const uint32_t seed = 0;
     const int T = 1000, K = 20, n = 20;
     const int64_t gmax = 32;
-    hipStream_t main_stream = c->stream;
-    c->stream = c->s_prep;
+    hipStream_t st = c->s_prep;
     // map the code object of every translation unit now: the first launch of a kernel from each costs 0.3-1.2 ms otherwise
-    hipLaunchKernelGGL(m6a_touch_kernels, dim3(1), dim3(1), 0, c->s_prep);
-    hipLaunchKernelGGL(m6a_touch_pool_reg, dim3(1), dim3(1), 0, c->s_prep);
-    hipLaunchKernelGGL(m6a_touch_pool_rtab, dim3(1), dim3(1), 0, c->s_prep);
+    hipLaunchKernelGGL(m6a_touch_kernels, dim3(1), dim3(1), 0, st);
+    hipLaunchKernelGGL(m6a_touch_pool_reg, dim3(1), dim3(1), 0, st);
+    hipLaunchKernelGGL(m6a_touch_pool_rtab, dim3(1), dim3(1), 0, st);
     (void)hipGetLastError();
-    int rc = ensure_mean_plan(c, T);
-    if (!rc) rc = ensure_raw(c, seed, stream_need(gmax, T, K));
+    int rc = ensure_mean_plan(c, st, T);
+    if (!rc) rc = ensure_raw(c, st, seed, stream_need(gmax, T, K));
     if (!rc) {
         // The ragged kernels' per-bag-size index tables are NOT built on speculation (rounds 2-3 built sizes 2..511 here: 1.4 GB
         // and a 1.2 ms pass that a uniform-bag or small caller never uses); a first ragged call builds the sizes it meets inside
@@ -1063,19 +1052,18 @@ void warm_default(m6a_ctx *c)
         // the reference's default read cap); the memory is then taken at the caller's word.
         const char *e = getenv("M6A_WARM_SLOTS");
         c->rt_presize = e && atoi(e) > 0 ? std::min(atoi(e), M6A_RTAB_MAX_N + 1) : 0;
-        rc = ensure_table_reg(c, seed, n, T, K, (int)gmax);
+        rc = ensure_table_reg(c, st, seed, n, T, K, (int)gmax);
         if (!rc && c->rt_presize > 2) {
             // ... and the index table of every bag size the arena was sized for: one pass over the stream for all of them
             // (1.2 ms of an idle GPU); a first call then only builds tables for bags beyond that
             std::vector<uint32_t> hist(M6A_HIST_BINS, 0u);
             for (int m = 2; m < c->rt_presize && m <= M6A_RTAB_MAX_N; m++) hist[m] = 1;
             bool usable = false;
-            rc = ensure_rtab(c, seed, T, K, gmax, hist.data(), &usable);
+            rc = ensure_rtab(c, st, seed, T, K, gmax, hist.data(), &usable);
         }
         c->rt_presize = 0;
     }
-    (void)hipStreamSynchronize(c->s_prep);
-    c->stream = main_stream;
+    (void)hipStreamSynchronize(st);
     if (rc) { c->tab_reg_key.valid = false; c->err.clear(); }   // not an error of anybody's call: the first call builds what it needs
 }
 
@@ -1413,9 +1401,20 @@ int m6a_infer(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off,
         HIPCHK(c, hipEventRecord(c->ev_main, c->stream));
         rc = launch_encode(c, X, km, off, S, R, p);
         if (rc) return rc;
-        rc = pool_setup_aside(c, off, S, T, K, seed, bs, spb);
+        // The pooling's set-up runs on the side stream next to the encoder -- in the steady state that is the ragged rank /
+        // order kernel (0.1 ms), in the first call the MT19937 stream and the index tables as well (milliseconds, incl. host
+        // syncs that wait for the side stream only).  ev_main was recorded BEFORE the encoder: the set-up orders itself behind
+        // everything queued up to there (the previous call's pooling still reads what it rebuilds), not behind the encoder.
+        hipStream_t st = c->s_prep ? c->s_prep : c->stream;
+        if (st != c->stream) HIPCHK(c, hipStreamWaitEvent(st, c->ev_main, 0));
+        PoolPlan plan;
+        rc = pool_plan(c, st, off, S, T, K, seed, bs, spb, &plan);
         if (rc) return rc;
-        return launch_pool(c, p, off, S, T, K, thr, seed, bs, spb, site, mod);
+        if (st != c->stream) {
+            HIPCHK(c, hipEventRecord(c->ev_prep, st));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_prep, 0));
+        }
+        return pool_run(c, plan, p, thr, site, mod);
     }
     if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
     for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
@@ -1526,9 +1525,9 @@ int m6a_random_stream(m6a_ctx *c, uint32_t seed, int64_t n_words, uint32_t *word
     if (n_words == 0) return M6A_OK;
     if (!words) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    if (is_device_ptr(words)) return launch_stream(c, seed, n_words, words);
+    if (is_device_ptr(words)) return launch_stream(c, c->stream, seed, n_words, words);
     HIPCHK(c, c->val_idx.ensure((size_t)n_words * 4));
-    int rc = launch_stream(c, seed, n_words, (uint32_t *)c->val_idx.p);
+    int rc = launch_stream(c, c->stream, seed, n_words, (uint32_t *)c->val_idx.p);
     if (rc) return rc;
     rc = d2h_through_ring(c, words, c->val_idx.p, (size_t)n_words * 4);
     if (rc) return rc;

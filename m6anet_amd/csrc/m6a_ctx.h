@@ -1,5 +1,5 @@
 // m6a_ctx.h -- internal to libm6a_hip.so: the context behind include/m6a.h and what its translation units share.
-//   m6a_api.hip        the C ABI proper: context, weights, random stream, pairwise-sum plan, index tables, launches, encode / pool / infer
+//   m6a_api.hip        the C ABI proper: context, weights, random stream, pairwise-sum plan, index tables, pool_plan / pool_run, launches, encode / pool / infer
 //   m6a_host_ring.hip  host-pointer calls: pinned staging ring, copy threads, H2D || encoder || D2H
 //   m6a_job.hip        the streaming job (m6a_job_begin / feed / end): the reference's batch loop fed as the loader produces it
 //   m6a_comm.hip       RCCL bound at run time, m6a_comm_*, m6a_gather, m6a_gather_reads, m6a_device_link
@@ -224,13 +224,13 @@ struct m6a_ctx {
     std::vector<uint32_t> hist_part;         // host_bag_range: eight interleaved histograms
     uint32_t *h_ctl = nullptr;                // [cursor HIST_BINS | slot_of_n MAX_N+1 | build_n MAX_N | build_slot MAX_N]
     DevBuf ctl_dev, rt_rank, rt_order;
-    // m6a_infer runs the pooling's set-up on a side stream next to the encoder (pool_setup_aside)
+    // m6a_infer runs the pooling's set-up (pool_plan) on the side stream s_prep next to the encoder; the set-up functions take
+    // their stream as an argument, and nothing but m6a_create and m6a_set_stream assigns `stream`
     bool side_work = false;                   // something is queued on s_prep that the main stream does not wait for
     const int64_t *hint_off = nullptr;        // m6a_set_host_offsets: host copy of the next device call's off[]
     hipEvent_t ev_ctl = nullptr;              // the last upload from h_ctl (the host rewrites it per call)
     hipStream_t s_prep = nullptr;
     hipEvent_t ev_main = nullptr, ev_prep = nullptr;
-    struct { bool ready = false, use = false; const int64_t *off = nullptr; int64_t S = 0, bs = 0, spb = 0; int T = 0, K = 0; uint32_t seed = 0; } prep;
     // per-bag-size index tables (m6a_pool_rtab.hip), valid for (seed, T*K, stream length)
     struct {
         bool valid = false; uint32_t seed = 0; int64_t A = 0, n_blk = 0;
@@ -291,7 +291,7 @@ int fail(m6a_ctx *c, int code, const char *fmt, ...);
 
 // ---- shared between the translation units (definitions: see the list at the top) ----------------------------------
 bool is_device_ptr(const void *p);
-// Every entry point that touches the stream, the sampling state or the error text waits for m6a_create's background set-up first.
+// Every entry point that touches the sampling state, the side stream or the error text waits for m6a_create's background set-up first.
 inline void settle(m6a_ctx *c) { if (c && c->warm.joinable()) c->warm.join(); }
 int job_busy(m6a_ctx *c);
 int check_pool_args(m6a_ctx *c, int64_t S, int T, int K, int rng_mode, int64_t bs, int64_t spb);
@@ -306,11 +306,9 @@ struct HintScope {
     ~HintScope() { if (c) c->hint_off = nullptr; }
 };
 // m6a_api.hip
-int ensure_raw(m6a_ctx *c, uint32_t seed, int64_t len);
-int launch_stream(m6a_ctx *c, uint32_t seed, int64_t len, uint32_t *raw);
 int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *rp);
 int launch_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr, uint32_t seed, int64_t bs, int64_t spb,
-                float *site, double *mod, bool dry = false);
+                float *site, double *mod);
 int bag_stats(m6a_ctx *c, const int64_t *d_off, int64_t S);
 void host_bag_range(m6a_ctx *c, const int64_t *off, int64_t S);
 void prof_begin(m6a_ctx *c, int kind);

@@ -1027,7 +1027,7 @@ def test_host_is_pinned_checks_the_whole_range(eng):
 
 
 def test_infer_equals_encode_then_pool_for_every_pooling_kernel(engines):
-    """m6a_infer sets the pooling up on a side stream while the encoder runs (a dry launch_pool); whatever kernel the
+    """m6a_infer sets the pooling up on a side stream while the encoder runs (pool_plan, then pool_run); whatever kernel the
     pooling takes -- forced scan drivers, index tables, both uniform-bag kernels -- the fused call must give what
     m6a_encode_reads followed by m6a_site_pool gives, bit for bit, also when the kernel choice changes between calls."""
     import torch
@@ -1051,6 +1051,52 @@ def test_infer_equals_encode_then_pool_for_every_pooling_kernel(engines):
     finally:
         eng.set_scan_driver(0)
         eng.set_table_variant(0)
+
+
+def test_first_calls_do_not_depend_on_the_background_setup(orc, weights, monkeypatch):
+    """m6a_create's background thread builds the default job's plan, stream and register table on the side stream, and with
+    M6A_WARM_SLOTS the index tables of bag sizes 2 .. N-1.  Whether it ran, ran plainly or presized the tables, the first calls
+    on a fresh context give the same bits: a call with exactly the warmed parameters, a ragged call on index tables (bag sizes
+    inside the presized range, one bag of one read, one bag beyond the range), and a call that rebuilds everything that differs."""
+    import torch
+    from m6anet_amd.engine import M6ANetEngine
+    dev = torch.device("cuda:0")
+    g = np.random.Generator(np.random.PCG64(2024))
+    ragged = list(g.integers(2, 64, size=94)) + [1, 70]
+    assert len(ragged) == 96 and min(ragged[:94]) >= 2 and max(ragged[:94]) <= 63
+    uni, rag = rand_sites(31, [20] * 64), rand_sites(32, ragged)
+    calls = (("A", uni, 1000, 0, 0, "table-reg"), ("B", rag, 100, 0, 3, "ragged-table"), ("C", uni, 37, 7, 0, None))
+    results = []
+    for env in ({"M6A_WARMUP": "0"}, {}, {"M6A_WARM_SLOTS": "64"}):
+        monkeypatch.delenv("M6A_WARMUP", raising=False)
+        monkeypatch.delenv("M6A_WARM_SLOTS", raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        e = M6ANetEngine(weights=weights["hct116"])
+        try:
+            got = {}
+            for name, (X, km, off), T, seed, driver, variant in calls:
+                tX, tk, to = (torch.from_numpy(x).to(dev) for x in (X, km, off))
+                e.set_scan_driver(driver)
+                try:
+                    rp, site, mod = e.infer(tX, tk, to, T, seed=seed)
+                finally:
+                    e.set_scan_driver(0)
+                e.sync()
+                assert variant is None or e.last_pool_variant == variant, (env, name)
+                got[name] = (off, T, seed, rp.cpu().numpy(), site.cpu().numpy(), mod.cpu().numpy())
+            results.append(got)
+        finally:
+            e.close()
+    for name in "ABC":
+        off, T, seed, rp, site, mod = results[0][name]
+        for other in results[1:]:
+            for x, y in zip(other[name][3:], (rp, site, mod)):
+                assert np.array_equal(x, y), name
+        want_site, want_mod = orc.site_pool(rp, off, T, THR, seed=seed)
+        for got in results:
+            assert same_sites(got[name][4], want_site), name
+            assert np.array_equal(got[name][5], want_mod, equal_nan=True), name
 
 
 def test_launch_timing_modes(engines):

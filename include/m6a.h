@@ -539,6 +539,47 @@ int m6a_json_sites_build(int device_id, const char *const *dirs, int n_dirs, int
                          const double *norm_mean, const double *norm_std, int n_norm, const m6a_json_host_half *host, int n_threads,
                          m6a_prep_sites **out);
 
+/* `compute_norm_factors`: the per-5-mer mean and std of the nine features that `train` and `inference` normalise with, from the
+ * Train rows of data.info.labelled and data.json.  The operation, on this route and on m6a_io_norm_factors (include/m6a_io.h), whose
+ * bits this one returns; tests/norm_statement.py states it in plain Python:
+ *   sites     n_sites rows in the caller's order (the Train rows in file order; no read-count filter; a row given twice counts twice):
+ *             transcript tx_blob[tx_off[i], tx_off[i + 1]), pos[i], bytes [start[i], end[i]) of json_path -- one record in the format
+ *             stated at m6a_json_sites_build -- and n_reads[i].  Every number is the double Python's float() gives.
+ *   entries   a site with 7-mer q gives three, c = 0, 1, 2: entry c belongs to the 5-mer q[c, c + 5) (five plain bytes, no
+ *             vocabulary), covers columns 3c, 3c + 1, 3c + 2 and carries n_reads[i]; ordered by site, then by c.
+ *   sums      per entry and column s = colsum(v[0..n)) and s2 = colsum(v[i] * v[i]), every product rounded on its own, n the rows of
+ *             the record.  colsum is np.sum of a Fortran-contiguous column: pieces of 8 192 elements, the first piece's sum, then
+ *             each later piece's sum added in order; a piece is summed pairwise -- n < 8 sequentially from 0.0; 8 <= n <= 128 with
+ *             eight accumulators r[j] = a[j], r[j] += a[i + j] for i = 8, 16, ... below n - n % 8, ((r0 + r1) + (r2 + r3)) +
+ *             ((r4 + r5) + (r6 + r7)), then the last n % 8 elements one by one; n > 128 as the sum of the first n2 = n / 2 - (n / 2) % 8
+ *             elements plus the sum of the rest (m6anet_amd/csrc/m6a_norm.h).
+ *   fold      per 5-mer and column S and S2: the entries' sums added one by one in list order, from the first entry's; N the sum
+ *             of n_reads (int64).  mean = S / N, std = sqrt(S2 / N - mean * mean), one IEEE operation each; a negative argument gives
+ *             NaN.  Not pinned: the sign of a zero sum and the payload of a NaN.
+ * Out, for the K 5-mers in bytewise order (K <= 3 n_sites, the capacity of every array): kmers [K][5], N [K], S, S2, mean, std
+ * [K][3]; *n_kmers = K; status [n_sites] (may be NULL) 0 or the reason the kernels declined the site for; kmer7 [n_sites][7] (may be
+ * NULL).  data.json goes up whole through the pinned chunk pair (M6A_PREP_CHUNK_KB) under the budget (M6A_PREP_BUDGET_MB, or free
+ * memory less a margin), which also counts the rows' raw doubles (72 B per read); over it the call is M6A_ENOMEM and its text names
+ * `--device cpu`.  Decline rule: that of m6a_json_sites_build less its two table checks.  Declined sites go, in ascending order,
+ * through host->partials (m6a_io_norm_partials of libm6a_io.so) and their partial sums take their place before the fold; the
+ * first one the loader does not parse ends the call with the loader's code (as M6A_EFORMAT / M6A_EIO) and text.  A row whose n_reads
+ * is not the record's row count is M6A_EFORMAT "site <tx>:<pos>: data.info.labelled says <n> reads, data.json has <m>" (the
+ * reference divides by the wrong count).  A status byte and the 7-mer per site and 64 bytes per 5-mer come back; nothing per read. */
+typedef struct m6a_norm_host_half {
+    int (*partials)(const char *json_path, int64_t n_sites, const char *tx_blob, const int64_t *tx_off, const int64_t *pos,
+                    const int64_t *start, const int64_t *end, const int64_t *n_reads, const int64_t *sites, int64_t n, int n_threads,
+                    double *s, double *s2, char *kmer7);
+    const char *(*error)(void);
+} m6a_norm_host_half;
+typedef struct m6a_norm_stats {
+    double ms_upload, ms_kernels, ms_host, ms_fold, ms_total;     /* ms_host: the declined sites */
+    int64_t n_sites, n_reads, n_kmers, n_declined, d2h_bytes, peak_bytes;
+} m6a_norm_stats;
+int m6a_norm_factors_build(int device_id, const char *json_path, int64_t n_sites, const char *tx_blob, const int64_t *tx_off,
+                           const int64_t *pos, const int64_t *start, const int64_t *end, const int64_t *n_reads,
+                           const m6a_norm_host_half *host, int n_threads, char *kmers, int64_t *N, double *S, double *S2, double *mean,
+                           double *std, int64_t *n_kmers, uint8_t *status, char *kmer7, m6a_norm_stats *stats);
+
 /* data.site_proba.csv and data.indiv_proba.csv formatted on the device: the bytes m6a_io_write_csv_n writes (include/m6a_io.h),
  *   site row   <tx>,<pos>,<n_reads>,<%.16f of (double)site_prob>,<5-mer>,<%.16f of mod_ratio>\n
  *   read row   <tx>,<pos>,<id>,<%.16f of (double)read_prob>\n     <id> = <int>.0 when n_rep = 1, <int>_<replicate> when n_rep > 1

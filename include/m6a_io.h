@@ -246,6 +246,26 @@ int m6a_io_info_rows(m6a_io_info *info, const int64_t *sites, int64_t n, const c
 int m6a_io_json_walk(const char *record, int64_t n, const char *tx, int64_t pos, int64_t n_reads, const char *norm_kmers, int n_norm,
                      double *values, char *kmer7);
 
+/* `compute_norm_factors --device cpu`: the per-5-mer mean and std of the nine features over a list of sites, the operation
+ * include/m6a.h states at m6a_norm_factors_build, on the host.
+ * The site table is given as arrays of n_sites rows (the Train rows of data.info.labelled, in file order): row i is transcript
+ * tx_blob[tx_off[i], tx_off[i + 1]) (tx_off holds n_sites + 1 ascending offsets), position pos[i], bytes [start[i], end[i]) of the
+ * file json_path, n_reads[i] reads.  Every record goes through the loader's own per-site parser and its numbers stay doubles; the
+ * loader's errors keep its code and text (range, JSON, 7-mer and 10 columns), and a row whose n_reads is not the record's row count is
+ * M6A_IO_EFORMAT "site <tx>:<pos>: data.info.labelled says <n> reads, data.json has <m>".  The first failing row in table order is
+ * reported.  No read-count filter, no vocabulary check.
+ * m6a_io_norm_factors: threaded over the sites, folded in table order.  Out, for the K 5-mers in bytewise order (K <= 3 n_sites, the
+ * capacity every array must have): kmers [K][5], N [K], S [K][3], S2 [K][3], mean [K][3], std [K][3]; *n_kmers = K; kmer7 [n_sites][7]
+ * (may be NULL) the sites' 7-mers.
+ * m6a_io_norm_partials: the host half of m6a_norm_factors_build -- s [n][9], s2 [n][9] (column sums of the values and of their squares,
+ * in np.sum's order) and kmer7 [n][7] of the rows `sites` [n] names (ascending; NULL with n = n_sites: all of them). */
+int m6a_io_norm_factors(const char *json_path, int64_t n_sites, const char *tx_blob, const int64_t *tx_off, const int64_t *pos,
+                        const int64_t *start, const int64_t *end, const int64_t *n_reads, int n_threads, char *kmers, int64_t *N, double *S,
+                        double *S2, double *mean, double *std, int64_t *n_kmers, char *kmer7);
+int m6a_io_norm_partials(const char *json_path, int64_t n_sites, const char *tx_blob, const int64_t *tx_off, const int64_t *pos,
+                         const int64_t *start, const int64_t *end, const int64_t *n_reads, const int64_t *sites, int64_t n, int n_threads,
+                         double *s, double *s2, char *kmer7);
+
 #ifdef __cplusplus
 }
 #endif

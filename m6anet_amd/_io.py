@@ -11,7 +11,8 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_read_ids", "m6a_io_read_rep", "m6a_io_tx_id", "m6a_io_kmer5", "m6a_io_write_csv", "m6a_io_write_csv_n", "m6a_io_csv_shard_size", "m6a_io_csv_shard_write", "m6a_io_csv_header_bytes", "m6a_io_format_f16", "m6a_io_py_repr", "m6a_io_repr_rounded", "m6a_io_repr_core",
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
            "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_sites_set_read_names", "m6a_io_uuid_parse", "m6a_io_uuid_format", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
-           "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk"]
+           "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk",
+           "m6a_io_norm_factors", "m6a_io_norm_partials"]
 _lib = None
 
 
@@ -115,6 +116,8 @@ def load():
     L.m6a_io_info_free.restype = None
     L.m6a_io_info_rows.argtypes = [vp, vp, i64, C.c_char_p, vp, vp, i32, i32, vp, vp, vp, vp]
     L.m6a_io_json_walk.argtypes = [C.c_char_p, i64, C.c_char_p, i64, i64, C.c_char_p, i32, vp, C.c_char_p]
+    L.m6a_io_norm_factors.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i64), vp]
+    L.m6a_io_norm_partials.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -555,6 +558,69 @@ def json_sites(input_dir, min_reads=20, norm=None, n_threads=0, device=0):
         raise M6AIOError(("m6a_io error %d: %s" if rc in (-7, -8) else "m6a_prep error %d: %s") % (code if rc in (-7, -8) else rc, text), code)
     self._adopt()
     return self
+
+
+def _norm_table(tx, pos, start, end, n_reads):
+    names = [os.fsencode(t) if not isinstance(t, bytes) else t for t in tx]
+    tx_off = np.zeros(len(names) + 1, np.int64)
+    np.cumsum([len(t) for t in names], out=tx_off[1:])
+    cols = [np.ascontiguousarray(a, np.int64) for a in (pos, start, end, n_reads)]
+    if any(a.shape != (len(names),) for a in cols):
+        raise ValueError("the site table's columns differ in length")
+    return b"".join(names) + b"\0", tx_off, cols
+
+
+def norm_partials(json_path, tx, pos, start, end, n_reads, sites=None, n_threads=0):
+    """m6a_io_norm_partials (libm6a_io.so): (s [n][9], s2 [n][9], 7-mers) of the table's rows `sites` (ascending; None: all)."""
+    L = load()
+    blob, tx_off, (pos, start, end, n_reads) = _norm_table(tx, pos, start, end, n_reads)
+    sel = None if sites is None else np.ascontiguousarray(sites, np.int64)
+    n = len(pos) if sel is None else len(sel)
+    s, s2, k7 = np.zeros((n, 9)), np.zeros((n, 9)), np.zeros((n, 7), np.uint8)
+    _chk(L.m6a_io_norm_partials(os.fsencode(json_path), len(pos), blob, tx_off.ctypes.data, pos.ctypes.data, start.ctypes.data, end.ctypes.data,
+                                n_reads.ctypes.data, None if sel is None else sel.ctypes.data, n, int(n_threads), s.ctypes.data, s2.ctypes.data,
+                                k7.ctypes.data))
+    return s, s2, [bytes(k).decode("latin-1") for k in k7]
+
+
+def norm_factors(json_path, tx, pos, start, end, n_reads, device="cpu", n_threads=0):
+    """The per-5-mer sums and factors of `compute_norm_factors` (include/m6a.h states the operation at m6a_norm_factors_build) over
+    the table's rows in their order: device "cpu" is m6a_io_norm_factors (libm6a_io.so), an integer the HIP device of
+    m6a_norm_factors_build (libm6a_hip.so); both return the same bits.  -> dict: kmers (list of str, bytewise order), N [K], S, S2,
+    mean, std [K][3], kmer7 (list of str); the device route adds status [n_sites] (0, or the reason the kernels declined the site
+    for) and stats (phase times in ms, n_sites, n_reads, n_kmers, n_declined, d2h_bytes, peak_bytes).  The loader's errors are raised
+    as M6AIOError with its code and text on both routes."""
+    io = load()
+    blob, tx_off, (pos, start, end, n_reads) = _norm_table(tx, pos, start, end, n_reads)
+    n, cap = len(pos), max(1, 3 * len(pos))
+    kmers, N, k7 = np.zeros((cap, 5), np.uint8), np.zeros(cap, np.int64), np.zeros((max(1, n), 7), np.uint8)
+    S, S2, mean, std = (np.zeros((cap, 3)) for _ in range(4))
+    K = C.c_int64(0)
+    out = {}
+    if device == "cpu":
+        _chk(io.m6a_io_norm_factors(os.fsencode(json_path), n, blob, tx_off.ctypes.data, pos.ctypes.data, start.ctypes.data, end.ctypes.data,
+                                    n_reads.ctypes.data, int(n_threads), kmers.ctypes.data, N.ctypes.data, S.ctypes.data, S2.ctypes.data,
+                                    mean.ctypes.data, std.ctypes.data, C.byref(K), k7.ctypes.data))
+    else:
+        from . import _lib
+        L = _lib.load()
+        host = _lib.NormHostHalf(C.cast(io.m6a_io_norm_partials, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
+        status, st = np.zeros(max(1, n), np.uint8), _lib.NormStats()
+        rc = L.m6a_norm_factors_build(int(device), os.fsencode(json_path), n, blob, tx_off.ctypes.data, pos.ctypes.data, start.ctypes.data,
+                                      end.ctypes.data, n_reads.ctypes.data, C.byref(host), int(n_threads), kmers.ctypes.data, N.ctypes.data,
+                                      S.ctypes.data, S2.ctypes.data, mean.ctypes.data, std.ctypes.data, C.byref(K), status.ctypes.data,
+                                      k7.ctypes.data, C.byref(st))
+        if rc != 0:
+            code = prep_sites._CODES.get(rc, rc)
+            text = L.m6a_prep_last_error().decode()
+            # M6A_EFORMAT / M6A_EIO carry the host loader's own text: raised as the host route raises it
+            raise M6AIOError(("m6a_io error %d: %s" if rc in (-7, -8) else "m6a_prep error %d: %s") % (code if rc in (-7, -8) else rc, text), code)
+        out["status"] = status[:n]
+        out["stats"] = {f: getattr(st, f) for f, _ in st._fields_}
+    k = K.value
+    out.update(kmers=[bytes(x).decode("latin-1") for x in kmers[:k]], N=N[:k], S=S[:k], S2=S2[:k], mean=mean[:k], std=std[:k],
+               kmer7=[bytes(x).decode("latin-1") for x in k7[:n]])
+    return out
 
 
 class CsvDeclined(M6AIOError):

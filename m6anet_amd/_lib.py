@@ -20,7 +20,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
-           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_repr_format", "m6a_prep_dataprep_write",
+           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_norm_factors_build", "m6a_repr_format", "m6a_prep_dataprep_write",
            "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats"]
 
 _lib = None
@@ -34,6 +34,18 @@ class HostHalf(C.Structure):
 class JsonHostHalf(C.Structure):
     """m6a_json_host_half (include/m6a.h): the libm6a_io.so functions behind `inference --loader device`."""
     _fields_ = [("open", C.c_void_p), ("table", C.c_void_p), ("rows", C.c_void_p), ("free", C.c_void_p), ("error", C.c_void_p)]
+
+
+class NormHostHalf(C.Structure):
+    """m6a_norm_host_half (include/m6a.h): the libm6a_io.so functions behind `compute_norm_factors --device gpu`."""
+    _fields_ = [("partials", C.c_void_p), ("error", C.c_void_p)]
+
+
+class NormStats(C.Structure):
+    """m6a_norm_stats (include/m6a.h)."""
+    _fields_ = [("ms_upload", C.c_double), ("ms_kernels", C.c_double), ("ms_host", C.c_double), ("ms_fold", C.c_double),
+                ("ms_total", C.c_double), ("n_sites", C.c_int64), ("n_reads", C.c_int64), ("n_kmers", C.c_int64),
+                ("n_declined", C.c_int64), ("d2h_bytes", C.c_int64), ("peak_bytes", C.c_int64)]
 
 
 class PrepSitesInfo(C.Structure):
@@ -207,6 +219,8 @@ def load():
         f.argtypes = [vp]
         f.restype = C.c_int64
     L.m6a_json_sites_build.argtypes = [i32, C.POINTER(C.c_char_p), i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(JsonHostHalf), i32, C.POINTER(vp)]
+    L.m6a_norm_factors_build.argtypes = [i32, C.c_char_p, i64, vp, vp, vp, vp, vp, vp, C.POINTER(NormHostHalf), i32, vp, vp, vp, vp, vp, vp,
+                                         C.POINTER(i64), vp, vp, C.POINTER(NormStats)]
     L.m6a_prep_sites_get.argtypes = [vp]
     L.m6a_prep_sites_get.restype = C.POINTER(PrepSitesInfo)
     L.m6a_prep_sites_fetch.argtypes = [vp, vp, vp, vp]

@@ -2504,3 +2504,144 @@ extern "C" int m6a_io_json_walk(const char *record, int64_t n, const char *tx, i
         for (int i = 0; i < 7; i++) kmer7[i] = (char)(k7 >> (8 * (6 - i)));
     return r;
 }
+
+// ---- compute_norm_factors (include/m6a.h states the operation at m6a_norm_factors_build): the host route and the host half ----------
+#include "m6a_norm.h"
+
+namespace {
+
+struct NormTable {
+    int64_t S;
+    const char *blob;
+    const int64_t *tx_off, *pos, *start, *end, *reads;
+};
+
+// One site: its record through the loader's own parser (parse_record), the loader's checks in the loader's order and text, the count
+// against data.info.labelled, then the nine column sums and the nine of the squares in colsum's order.
+int norm_site(const Mapped &m, const NormTable &T, int64_t i, std::vector<double> &vals, double *s, double *s2, char *kmer7)
+{
+    const std::string tx(T.blob + T.tx_off[i], (size_t)(T.tx_off[i + 1] - T.tx_off[i]));
+    const long long pos = (long long)T.pos[i];
+    if (T.start[i] < 0 || T.end[i] > (int64_t)m.n || T.start[i] >= T.end[i])
+        return fail(M6A_IO_EFORMAT, "site %s:%lld: byte range outside data.json", tx.c_str(), pos);
+    vals.clear();
+    std::string kmer;
+    int ncol = 0;
+    const int rc = parse_record(m.p + T.start[i], m.p + T.end[i], tx, T.pos[i], kmer, vals, ncol);
+    if (rc) return rc;
+    if (kmer.size() != 7 || ncol != 10)
+        return fail(M6A_IO_EFORMAT, "site %s:%lld: %zu-mer with %d columns; only dataprep n_neighbors=1 (7-mer, 10 columns) is supported",
+                    tx.c_str(), pos, kmer.size(), ncol);
+    const int64_t n = (int64_t)vals.size() / 10;
+    if (n != T.reads[i])
+        return fail(M6A_IO_EFORMAT, "site %s:%lld: data.info.labelled says %lld reads, data.json has %lld", tx.c_str(), pos, (long long)T.reads[i],
+                    (long long)n);
+    const double *v = vals.data();
+    for (int j = 0; j < 9; j++) {
+        s[j] = m6a_norm::colsum([&](int64_t r) { return v[10 * r + j]; }, n);
+        s2[j] = m6a_norm::colsum([&](int64_t r) { const double x = v[10 * r + j]; return x * x; }, n);
+    }
+    std::memcpy(kmer7, kmer.data(), 7);
+    return 0;
+}
+
+int norm_table_check(const NormTable &T)
+{
+    if (T.S < 0 || (T.S && (!T.blob || !T.tx_off || !T.pos || !T.start || !T.end || !T.reads))) return fail(M6A_IO_EINVAL, "null argument");
+    for (int64_t i = 0; i < T.S; i++)
+        if (T.tx_off[i + 1] < T.tx_off[i] || T.tx_off[i] < 0) return fail(M6A_IO_EINVAL, "site table: transcript offsets are not ascending");
+    return 0;
+}
+
+// sites[n] (NULL: all rows of the table) on the threads; workers own ascending ranges of the list and stop at their first error, so
+// the lowest failing worker's is the first in list order
+int norm_partials(const char *json_path, const NormTable &T, const int64_t *sites, int64_t n, int n_threads, double *s, double *s2, char *kmer7)
+{
+    Mapped m;
+    int rc = m.open(json_path, 0);
+    if (rc) return rc;
+    const int nw = n_workers(n_threads, n);
+    std::vector<std::string> errs((size_t)nw);
+    std::vector<int> rcs((size_t)nw, 0);
+    auto work = [&](int w) {
+        std::vector<double> vals;
+        for (int64_t k = n * w / nw; k < n * (w + 1) / nw; k++) {
+            const int r = norm_site(m, T, sites ? sites[k] : k, vals, s + 9 * k, s2 + 9 * k, kmer7 + 7 * k);
+            if (r) { rcs[(size_t)w] = r; errs[(size_t)w] = g_err; return; }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int w = 1; w < nw; w++) th.emplace_back(work, w);
+    work(0);
+    for (auto &t : th) t.join();
+    for (int w = 0; w < nw; w++)
+        if (rcs[(size_t)w]) { g_err = errs[(size_t)w]; return rcs[(size_t)w]; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int m6a_io_norm_partials(const char *json_path, int64_t n_sites, const char *tx_blob, const int64_t *tx_off, const int64_t *pos,
+                                    const int64_t *start, const int64_t *end, const int64_t *n_reads, const int64_t *sites, int64_t n, int n_threads,
+                                    double *s, double *s2, char *kmer7)
+{
+    const NormTable T{n_sites, tx_blob, tx_off, pos, start, end, n_reads};
+    if (!json_path || n < 0 || (n && (!s || !s2 || !kmer7))) return fail(M6A_IO_EINVAL, "null argument");
+    if (int rc = norm_table_check(T)) return rc;
+    if (!sites && n != n_sites) return fail(M6A_IO_EINVAL, "site list: NULL stands for all %lld rows of the table", (long long)n_sites);
+    for (int64_t k = 0; sites && k < n; k++)
+        if (sites[k] < 0 || sites[k] >= n_sites || (k && sites[k] <= sites[k - 1])) return fail(M6A_IO_EINVAL, "site list: not ascending rows of the table");
+    if (!n) return M6A_IO_OK;
+    try {
+        return norm_partials(json_path, T, sites, n, n_threads, s, s2, kmer7);
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory");
+    }
+}
+
+extern "C" int m6a_io_norm_factors(const char *json_path, int64_t n_sites, const char *tx_blob, const int64_t *tx_off, const int64_t *pos,
+                                   const int64_t *start, const int64_t *end, const int64_t *n_reads, int n_threads, char *kmers, int64_t *N, double *S,
+                                   double *S2, double *mean, double *sd, int64_t *n_kmers, char *kmer7)
+{
+    const NormTable T{n_sites, tx_blob, tx_off, pos, start, end, n_reads};
+    if (!json_path || !n_kmers || (n_sites > 0 && (!kmers || !N || !S || !S2 || !mean || !sd))) return fail(M6A_IO_EINVAL, "null argument");
+    *n_kmers = 0;
+    if (int rc = norm_table_check(T)) return rc;
+    if (!n_sites) return M6A_IO_OK;
+    try {
+        std::vector<double> s((size_t)n_sites * 9), s2((size_t)n_sites * 9);
+        std::vector<char> k7((size_t)n_sites * 7);
+        const int rc = norm_partials(json_path, T, nullptr, n_sites, n_threads, s.data(), s2.data(), k7.data());
+        if (rc) return rc;
+        // the fold: entries by site in table order, then by c; every 5-mer's chain in that order, from its first entry's sums
+        struct Acc { int64_t N; double S[3], S2[3]; };
+        std::map<std::string, Acc> acc;
+        for (int64_t i = 0; i < n_sites; i++)
+            for (int c = 0; c < 3; c++) {
+                const double *a = s.data() + 9 * i + 3 * c, *b = s2.data() + 9 * i + 3 * c;
+                auto it = acc.find(std::string(k7.data() + 7 * i + c, 5));
+                if (it == acc.end()) {
+                    acc.emplace(std::string(k7.data() + 7 * i + c, 5), Acc{n_reads[i], {a[0], a[1], a[2]}, {b[0], b[1], b[2]}});
+                } else {
+                    it->second.N += n_reads[i];
+                    for (int j = 0; j < 3; j++) { it->second.S[j] += a[j]; it->second.S2[j] += b[j]; }
+                }
+            }
+        int64_t k = 0;
+        for (const auto &kv : acc) {                       // std::string compares as unsigned bytes: the bytewise order
+            std::memcpy(kmers + 5 * k, kv.first.data(), 5);
+            N[k] = kv.second.N;
+            for (int j = 0; j < 3; j++) {
+                S[3 * k + j] = kv.second.S[j];
+                S2[3 * k + j] = kv.second.S2[j];
+                m6a_norm::finish(kv.second.S[j], kv.second.S2[j], kv.second.N, mean + 3 * k + j, sd + 3 * k + j);
+            }
+            ++k;
+        }
+        *n_kmers = k;
+        if (kmer7) std::memcpy(kmer7, k7.data(), k7.size());
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory");
+    }
+}

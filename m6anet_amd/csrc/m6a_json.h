@@ -312,17 +312,12 @@ struct JsonSite { int64_t start, end, pos; uint32_t tx, pad; };       // end = s
 
 constexpr int kJsonWaves = kBlk / 64;      // sites per workgroup
 
-__global__ void __launch_bounds__(kBlk)
-json_scan_kernel(const uint8_t *__restrict__ f, const JsonSite *__restrict__ sites, const int64_t *__restrict__ off, int64_t S,
-                 const uint8_t *__restrict__ blob, const int64_t *__restrict__ tx_off, const uint64_t *__restrict__ nk,
-                 const int32_t *__restrict__ nix, int n_nk, const uint64_t *__restrict__ voc, int n_voc, int32_t *__restrict__ row_start,
-                 int32_t *__restrict__ site_norm, uint8_t *__restrict__ site_kmers, uint8_t *__restrict__ site_k7, uint8_t *__restrict__ status)
+// One wave's scan of a site of n rows whose row starts go to row_start[base ..]: the header, then the '[' of the body.  The reason
+// (wave-uniform) and the 7-mer; json_scan_kernel and norm_scan_kernel (m6a_norm.h) share it.
+__device__ inline int json_scan_site(const uint8_t *__restrict__ f, const JsonSite &st, int64_t base, int64_t n, int lane,
+                                     const uint8_t *__restrict__ blob, const int64_t *__restrict__ tx_off, int32_t *__restrict__ row_start,
+                                     uint64_t *k7_out)
 {
-    const int lane = (int)(threadIdx.x & 63);
-    const int64_t s = (int64_t)blockIdx.x * kJsonWaves + (threadIdx.x >> 6);
-    if (s >= S) return;
-    const JsonSite st = sites[s];
-    const int64_t base = off[s], n = off[s + 1] - base;
     const uint8_t *const e = f + st.end;
     const uint8_t *body = nullptr;
     uint64_t k7 = 0;
@@ -371,6 +366,23 @@ json_scan_kernel(const uint8_t *__restrict__ f, const JsonSite *__restrict__ sit
         if (cnt != n) reason = JR_COUNT;
         else if (__any(first_bad)) reason = JR_ROW;
     }
+    *k7_out = k7;
+    return reason;
+}
+
+__global__ void __launch_bounds__(kBlk)
+json_scan_kernel(const uint8_t *__restrict__ f, const JsonSite *__restrict__ sites, const int64_t *__restrict__ off, int64_t S,
+                 const uint8_t *__restrict__ blob, const int64_t *__restrict__ tx_off, const uint64_t *__restrict__ nk,
+                 const int32_t *__restrict__ nix, int n_nk, const uint64_t *__restrict__ voc, int n_voc, int32_t *__restrict__ row_start,
+                 int32_t *__restrict__ site_norm, uint8_t *__restrict__ site_kmers, uint8_t *__restrict__ site_k7, uint8_t *__restrict__ status)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t s = (int64_t)blockIdx.x * kJsonWaves + (threadIdx.x >> 6);
+    if (s >= S) return;
+    const JsonSite st = sites[s];
+    const int64_t base = off[s];
+    uint64_t k7 = 0;
+    int reason = json_scan_site(f, st, base, off[s + 1] - base, lane, blob, tx_off, row_start, &k7);
     if (!reason) {
         bool no_norm = false, no_voc = false;
 #pragma unroll
@@ -410,21 +422,17 @@ struct JsonSink {
     }
 };
 
-__global__ void __launch_bounds__(kBlk)
-json_rows_kernel(const uint8_t *__restrict__ f, const JsonSite *__restrict__ sites, const int64_t *__restrict__ off, int64_t S,
-                 const int32_t *__restrict__ row_start, const int32_t *__restrict__ site_norm, const double *__restrict__ mean,
-                 const double *__restrict__ sd, int n_norm, float *__restrict__ X, double *__restrict__ ids, uint8_t *status)
+// One wave's rows of a site the scan took, a lane per row: sink_of(r) receives row r's ten numbers.  The first reason met by the
+// lowest lane that met one (wave-uniform), 0 when every row and what lies between the rows is good; json_rows_kernel and
+// norm_rows_kernel (m6a_norm.h) share it.
+template <class SinkOf>
+__device__ inline int json_rows_site(const uint8_t *__restrict__ f, const JsonSite &st, int64_t base, int64_t n, int lane,
+                                     const int32_t *__restrict__ row_start, SinkOf &&sink_of)
 {
-    const int lane = (int)(threadIdx.x & 63);
-    const int64_t s = (int64_t)blockIdx.x * kJsonWaves + (threadIdx.x >> 6);
-    if (s >= S || status[s]) return;
-    const JsonSite st = sites[s];
-    const int64_t base = off[s], n = off[s + 1] - base;
     const uint8_t *const p0 = f + st.start, *const e = f + st.end;
-    const int32_t n0 = n_norm ? site_norm[3 * s] : 0, n1 = n_norm ? site_norm[3 * s + 1] : 0, n2 = n_norm ? site_norm[3 * s + 2] : 0;
     int reason = JR_OK;
     for (int64_t r = lane; r < n; r += 64) {
-        const JsonSink sink{X + 9 * (base + r), ids + base + r, mean, sd, n0, n1, n2, n_norm > 0};
+        const auto sink = sink_of(r);
         const uint8_t *after = nullptr, *next = nullptr;
         int rc = row(p0 + row_start[base + r], e, sink, &after);
         if (!rc) {
@@ -435,10 +443,24 @@ json_rows_kernel(const uint8_t *__restrict__ f, const JsonSite *__restrict__ sit
         if (rc && !reason) reason = rc;
     }
     const unsigned long long bad = __ballot(reason != 0);
-    if (bad) {
-        const int r0 = __shfl(reason, __ffsll((long long)bad) - 1, 64);
-        if (lane == 0) status[s] = (uint8_t)r0;
-    }
+    return bad ? __shfl(reason, __ffsll((long long)bad) - 1, 64) : JR_OK;
+}
+
+__global__ void __launch_bounds__(kBlk)
+json_rows_kernel(const uint8_t *__restrict__ f, const JsonSite *__restrict__ sites, const int64_t *__restrict__ off, int64_t S,
+                 const int32_t *__restrict__ row_start, const int32_t *__restrict__ site_norm, const double *__restrict__ mean,
+                 const double *__restrict__ sd, int n_norm, float *__restrict__ X, double *__restrict__ ids, uint8_t *status)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t s = (int64_t)blockIdx.x * kJsonWaves + (threadIdx.x >> 6);
+    if (s >= S || status[s]) return;
+    const JsonSite st = sites[s];
+    const int64_t base = off[s], n = off[s + 1] - base;
+    const int32_t n0 = n_norm ? site_norm[3 * s] : 0, n1 = n_norm ? site_norm[3 * s + 1] : 0, n2 = n_norm ? site_norm[3 * s + 2] : 0;
+    const int r0 = json_rows_site(f, st, base, n, lane, row_start, [&](int64_t r) {
+        return JsonSink{X + 9 * (base + r), ids + base + r, mean, sd, n0, n1, n2, n_norm > 0};
+    });
+    if (r0 && lane == 0) status[s] = (uint8_t)r0;
 }
 
 int json_host_fail(const m6a_json_host_half *host, int hrc)

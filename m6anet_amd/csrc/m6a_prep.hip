@@ -3322,3 +3322,5 @@ extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }
 #include "m6a_deflate.h"
 #define M6A_JSON_DEVICE_PART
 #include "m6a_json.h"
+#define M6A_NORM_DEVICE_PART
+#include "m6a_norm.h"

@@ -37,6 +37,75 @@ def load_norm_factors(path):
     return {k: (np.asarray(v[0], np.float64), np.asarray(v[1], np.float64)) for k, v in d.items()}
 
 
+NORM_COLUMNS = ("transcript_id", "transcript_position", "start", "end", "n_reads", "set_type")
+
+
+def read_norm_sites(input_dir):
+    """The Train rows of <input_dir>/data.info.labelled in file order, as compute_norm_factors takes them: (tx list, pos, start, end,
+    n_reads as int64 arrays).  No read-count filter (the reference has none); transcript_position may be an integer-valued decimal
+    (the reference casts the column).  ValueError for a missing file or column, a bad number, start >= end, or no Train row."""
+    path = os.path.join(input_dir, "data.info.labelled")
+    for p in (path, os.path.join(input_dir, "data.json")):
+        if not os.path.isfile(p):
+            raise ValueError("%s: no such file" % p)
+    tx, cols = [], ([], [], [], [])
+    with open(path, newline="") as f:
+        rd = csv.DictReader(f)
+        missing = sorted(set(NORM_COLUMNS) - set(rd.fieldnames or ()))
+        if missing:
+            raise ValueError("%s: missing column(s) %s" % (path, missing))
+        for line, r in enumerate(rd, 2):
+            if r["set_type"] != "Train":
+                continue
+            try:
+                p = float(r["transcript_position"])
+                if p != int(p):
+                    raise ValueError
+                v = [int(p)] + [int(r[k]) for k in ("start", "end", "n_reads")]
+                if any(abs(x) >= 1 << 62 for x in v):
+                    raise ValueError
+            except (ValueError, TypeError, OverflowError):
+                raise ValueError("%s line %d: transcript_position, start, end and n_reads must be integers" % (path, line)) from None
+            if v[1] < 0 or v[1] >= v[2]:
+                raise ValueError("%s line %d: start %d and end %d are no byte range" % (path, line, v[1], v[2]))
+            if v[3] < 0:
+                raise ValueError("%s line %d: n_reads %d" % (path, line, v[3]))
+            tx.append(r["transcript_id"])
+            for c, x in zip(cols, v):
+                c.append(x)
+    if not tx:
+        raise ValueError("%s: no row with set_type Train" % path)
+    return (tx,) + tuple(np.array(c, np.int64) for c in cols)
+
+
+def compute_norm_factors(input_dir, device="cpu", n_threads=0, stats=None):
+    """`compute_norm_factors` of the reference (m6anet/scripts/compute_norm_factors.py) on one directory of data.json +
+    data.info.labelled: dict kmer -> (mean f64[3], std f64[3]) in sorted order, what load_norm_factors returns.  device: "cpu" (the
+    host route of libm6a_io.so) or the index of a HIP device (the kernels of libm6a_hip.so); the same bits either way (include/m6a.h
+    states the operation).  stats (a dict) receives the counts and, on the device route, the phase times."""
+    from . import _io
+    tx, pos, start, end, n_reads = read_norm_sites(input_dir)
+    r = _io.norm_factors(os.path.join(input_dir, "data.json"), tx, pos, start, end, n_reads, device=device, n_threads=n_threads)
+    if stats is not None:
+        stats.update(r.get("stats", {}), n_sites=len(tx), n_reads=int(n_reads.sum()), n_kmers=len(r["kmers"]))
+    return {k: (r["mean"][i].copy(), r["std"][i].copy()) for i, k in enumerate(r["kmers"])}
+
+
+def save_norm_factors(path_stem, d):
+    """<path_stem>.npz in the layout of the bundled tables (kmers, mean [K][3], std [K][3]) and, when joblib can be imported,
+    <path_stem>.joblib as the reference writes it: dict kmer -> (mean, std), in sorted order.  -> the paths written."""
+    kmers = sorted(d)
+    np.savez(path_stem + ".npz", kmers=np.array(kmers), mean=np.array([d[k][0] for k in kmers], np.float64).reshape(len(kmers), 3),
+             std=np.array([d[k][1] for k in kmers], np.float64).reshape(len(kmers), 3))
+    paths = [path_stem + ".npz"]
+    try:
+        import joblib
+    except ImportError:
+        return paths
+    joblib.dump({k: (np.asarray(d[k][0], np.float64), np.asarray(d[k][1], np.float64)) for k in kmers}, path_stem + ".joblib")
+    return paths + [path_stem + ".joblib"]
+
+
 def _read_info(root_dir):
     rows = []
     with open(os.path.join(root_dir, "data.info"), newline="") as f:

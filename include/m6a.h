@@ -796,9 +796,13 @@ int m6a_prep_sites_write_csv_bgzf_level(m6a_prep_sites *p, const char *out_dir, 
  *          dL/ds = (s - y) / max((1 - s) s, 1e-12) / B
  *   ds/dp_k = prod_{j != k} (1 - p_j), from the products before and behind read k -- nothing is divided by 1 - p_k, so a read with
  *          p = 1.0f gives its site the loss term 100 (y = 0) or 0 (y = 1) and a gradient of exactly zero
+ *   clip (only after m6a_train_set_clip(max_norm > 0); the reference's clip_grad, torch.nn.utils.clip_grad_norm_ with the 2-norm,
+ *          between backward() and the optimizer's step): total = sqrt(sum g^2) over the 7 697 trainable floats, the sum in float64
+ *          in a fixed order, total in float32; coef = min(1, max_norm / (total + 1e-6)) in float32; g <- coef g, always multiplied
+ *          (at coef = 1 no bit changes).  It comes after the gradient is complete and before Adam adds weight_decay theta.
  *   Adam as torch.optim.Adam applies it: g += weight_decay theta, m and v, theta -= lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
  *          over the 7 697 trainable floats E, W1, b1, gamma, beta, W2, b2, W3, b3; the two running statistics are not parameters.
- * Not built: gradient clipping (the reference's command never sets it), the weighted loss, other topologies.
+ * Not built: the weighted loss, other topologies, more than one GPU.
  * Sums run in a fixed order and no float is added atomically: the same state and batch give the same bits.
  *
  *   m6a_train_create   weights: the 7 997-float blob of m6a_create (a HOST pointer, raw values); the trainer keeps its own copy, with
@@ -815,14 +819,26 @@ int m6a_prep_sites_write_csv_bgzf_level(m6a_prep_sites *p, const char *out_dir, 
  *                      more to deliver host outputs), however many steps there are.
  *   m6a_train_sample   the same indices on the host: read_idx [n_order * bag] global read numbers (off, order: host pointers).
  *   m6a_train_grads    the last step's gradient in blob order, zeros in the 300 running-statistic slots (before weight decay, as
- *                      torch's p.grad).
+ *                      torch's p.grad; with clipping on, the clipped gradient, as p.grad is after clip_grad_norm_).
  *   m6a_train_weights  the blob with the running statistics in place: it goes straight into m6a_create.  n_steps (may be NULL) = t.
- *   m6a_train_stats    steps taken, kernels launched, waits for the stream -- each may be NULL.
+ *   m6a_train_stats    steps taken, kernels launched, waits for the stream -- each may be NULL.  A step is 6 launches, 7 with
+ *                      clipping on (the norm must be known in every block before Adam runs: one more kernel boundary); the waits
+ *                      per call are the same either way.
+ *   m6a_train_set_clip  max_norm of the clip above for every later step; 0 = off, the default, and then a step is what it is
+ *                      on a trainer this was never called on, bit for bit.
+ *   m6a_train_last_norm  the last step's `total`, from before the scaling.  M6A_EINVAL with clipping off (the default chain does
+ *                      not compute the norm) and before the first step after m6a_train_set_clip.
+ *   m6a_train_state_get  Adam's m and v (HOST pointers, M6A_N_WEIGHTS floats each in blob order, zeros in the 300
+ *                      running-statistic slots) and t (n_steps, may be NULL).
+ *   m6a_train_state_set  the inverse: on a trainer created from the blob m6a_train_weights gave, it makes the trainer that m, v and
+ *                      t were taken from -- its next steps have that trainer's bits (the blob carries the running statistics).  The
+ *                      running-statistic slots of m and v are stored as zeros.
  * Pointers are all host or all device, as everywhere; a host dataset is uploaded once per call, device-pointer calls are stream-ordered
  * after the one wait named above (m6a_sync before reading their outputs).
  * M6A_EINVAL: bag outside 1..M6A_MAX_SAMPLES; a batch of fewer than 2 reads (torch refuses a one-value batch norm) or of more than
  * 2^20; a site with fewer than `bag` reads; a k-mer id outside 0..65; an `order` entry outside [0, n_sites); a label that is not 0 or
- * 1.  Nothing is changed by a refused call. */
+ * 1; max_norm negative, NaN or infinite; a device pointer to m6a_train_state_get / _set; n_steps < 0; a v that is negative or not
+ * finite, an m that is not finite.  Nothing is changed by a refused call. */
 typedef struct m6a_trainer m6a_trainer;
 typedef struct { float lr, beta1, beta2, eps, weight_decay; } m6a_train_config;
 int m6a_train_create(m6a_ctx *ctx, const float *weights, size_t n_floats, const m6a_train_config *cfg, m6a_trainer **out);
@@ -836,6 +852,10 @@ int m6a_train_sample(const int64_t *off, const int64_t *order, int64_t n_order, 
 int m6a_train_grads(m6a_trainer *t, float *grads);
 int m6a_train_weights(m6a_trainer *t, float *weights, int64_t *n_steps);
 int m6a_train_stats(const m6a_trainer *t, int64_t *n_steps, int64_t *n_launches, int64_t *n_syncs);
+int m6a_train_set_clip(m6a_trainer *t, float max_norm);   /* 0 = off (the default) */
+int m6a_train_last_norm(m6a_trainer *t, float *total_norm);
+int m6a_train_state_get(m6a_trainer *t, float *m, float *v, int64_t *n_steps);
+int m6a_train_state_set(m6a_trainer *t, const float *m, const float *v, int64_t n_steps);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,8 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
            "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_norm_factors_build", "m6a_repr_format", "m6a_prep_dataprep_write",
-           "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats"]
+           "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats",
+           "m6a_train_set_clip", "m6a_train_last_norm", "m6a_train_state_get", "m6a_train_state_set"]
 
 _lib = None
 
@@ -246,6 +247,10 @@ def load():
     L.m6a_train_grads.argtypes = [vp, vp]
     L.m6a_train_weights.argtypes = [vp, vp, pl]
     L.m6a_train_stats.argtypes = [vp, pl, pl, pl]
+    L.m6a_train_set_clip.argtypes = [vp, C.c_float]
+    L.m6a_train_last_norm.argtypes = [vp, vp]
+    L.m6a_train_state_get.argtypes = [vp, vp, vp, pl]
+    L.m6a_train_state_set.argtypes = [vp, vp, vp, i64]
     L.m6a_prep_last_error.argtypes = []
     L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:

@@ -1,7 +1,9 @@
 // m6a_train.hip -- training of the m6anet.toml model: training-mode forward, backward and Adam (include/m6a.h: m6a_train_*; the
 // operation is stated once in tests/train_statement.py).  Internal declarations: m6a_ctx.h.
 //
-// One step is a chain of six plain launches on the context's stream; nothing comes back to the host between steps:
+// One step is a chain of six plain launches on the context's stream (seven with gradient clipping on, where train_adam_kernel is
+// train_grad_kernel -- the same folds, the gradient and a sum of g^2 per block -- and train_clip_adam_kernel -- the norm, the scale,
+// Adam: every block needs the whole gradient's norm, and that takes a kernel boundary); nothing comes back to the host between steps:
 //   train_fwd1_kernel    per chunk of reads: gather x (features | three embeddings), z1 = W1 x + b1, and the chunk's sums of z1 and
 //                        z1^2 per hidden unit in float64;
 //   train_stats_kernel   the chunks' sums in chunk order -> mu, 1 / sqrt(var + eps); the running statistics;
@@ -399,6 +401,74 @@ __global__ __launch_bounds__(64) void train_adam_kernel(Batch bt, const float *_
     adam_apply(e, gr, a, P, M, V, G);
 }
 
+// ---- the step with gradient clipping: train_adam_kernel in two, because every block needs the whole gradient's norm ----------------
+constexpr int kGradBlocks = kEmbEntries + (M6A_N_WEIGHTS - kEmbEntries + 63) / 64;      // the grid of train_adam_kernel
+constexpr int kClipThreads = 256;
+
+// The folds of train_adam_kernel on its grid, in its order; G = the gradient (unclipped), sq[block] = the block's sum of g^2 in
+// float64: an embedding block has one value, the others the wave_sum butterfly of their 64 lanes' values.
+__global__ __launch_bounds__(64) void train_grad_kernel(Batch bt, const float *__restrict__ part, int n_chunks, const double *__restrict__ tot,
+                                                        const float *__restrict__ dxe, float *__restrict__ G, double *__restrict__ sq)
+{
+    const int lane = threadIdx.x;
+    if (blockIdx.x < kEmbEntries) {
+        const int e = blockIdx.x, v = e >> 1, d = e & 1;
+        double acc = 0.0;
+        for (int64_t b = lane; b < bt.B; b += 64) {
+            const int64_t site = bt.sidx ? bt.sidx[b] : b;
+            for (int s = 0; s < 3; s++)
+                if (bt.km[site * 3 + s] == v)
+                    for (int k = 0; k < bt.bag; k++) acc += (double)dxe[(b * bt.bag + k) * 6 + 2 * s + d];
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) {
+            const float gr = (float)acc;
+            G[e] = gr;
+            sq[e] = (double)gr * (double)gr;
+        }
+        return;
+    }
+    const int e = kEmbEntries + (blockIdx.x - kEmbEntries) * 64 + lane;
+    float gr = 0.f;
+    if (e < M6A_N_WEIGHTS && !(e >= oMean && e < oW2)) {          // the running statistics are not parameters: they count as 0
+        if (e >= oGamma && e < oBeta) gr = (float)tot[kH1 + e - oGamma];
+        else if (e >= oBeta && e < oMean) gr = (float)tot[e - oBeta];
+        else {
+            double acc = 0.0;
+            for (int c0 = 0; c0 < n_chunks; c0 += kBatch) {
+                float v[kBatch];
+                for (int u = 0; u < kBatch; u++) v[u] = c0 + u < n_chunks ? part[(size_t)(c0 + u) * M6A_N_WEIGHTS + e] : 0.f;
+                for (int u = 0; u < kBatch; u++) if (c0 + u < n_chunks) acc += (double)v[u];
+            }
+            gr = (float)acc;
+        }
+    }
+    if (e < M6A_N_WEIGHTS) G[e] = gr;
+    const double s = wave_sum((double)gr * (double)gr);           // every lane of the block is here
+    if (lane == 0) sq[blockIdx.x] = s;
+}
+
+// A thread per float of the blob.  Every thread adds the kGradBlocks partial sums in block-index order, so all of them hold the same
+// total = sqrt(sum g^2) and coef = min(1, max_norm / (total + 1e-6)) (torch.nn.utils.clip_grad_norm_, both float32); then
+// g <- coef g (at coef = 1 no bit changes) and Adam.  *norm = total, from before the scaling.
+__global__ __launch_bounds__(kClipThreads) void train_clip_adam_kernel(const double *__restrict__ sq, float max_norm, AdamArgs a,
+                                                                       float *__restrict__ P, float *__restrict__ M, float *__restrict__ V,
+                                                                       float *__restrict__ G, float *__restrict__ norm)
+{
+    __shared__ double sqs[kGradBlocks];                           // one global load per thread, then the ordered sum out of LDS
+    for (int b = threadIdx.x; b < kGradBlocks; b += kClipThreads) sqs[b] = sq[b];
+    __syncthreads();
+    double acc = 0.0;
+    for (int b = 0; b < kGradBlocks; b++) acc += sqs[b];
+    const float total = (float)sqrt(acc);
+    const float coef = fminf(max_norm / (total + 1e-6f), 1.0f);
+    const int e = blockIdx.x * kClipThreads + threadIdx.x;
+    if (e == 0) *norm = total;
+    if (e >= M6A_N_WEIGHTS) return;
+    if (e >= oMean && e < oW2) return;                            // G is 0 there already
+    adam_apply(e, G[e] * coef, a, P, M, V, G);
+}
+
 }  // namespace
 
 struct m6a_trainer {
@@ -410,6 +480,10 @@ struct m6a_trainer {
     unsigned long long *d_err = nullptr, *h_err = nullptr;
     DevBuf z1, dy1, xbuf, h2, dlogit, dxe, wpart, loss_term, ridx;      // scratch, sized for the largest batch seen
     DevBuf sX, sK, sOff, sY, sOrder, sLoss, sPred;                      // host-pointer calls
+    double *sq = nullptr;                                               // [kGradBlocks] sums of g^2 (clipping)
+    float *norm = nullptr;                                              // the last clipped step's total norm
+    float clip = 0.f;                                                   // max_norm, 0 = no clipping
+    bool have_norm = false;
     int64_t n_steps = 0, n_launches = 0, n_syncs = 0;
 };
 
@@ -485,10 +559,18 @@ int queue_step(m6a_trainer *t, const Batch &bt, float *loss, float *y_pred)
     hipLaunchKernelGGL(train_bwd1_kernel, dim3((unsigned)n_chunks), dim3(192), 0, st, N, chunk, (const float *)z1, (const float *)dy1,
                        (const float *)xbuf, (const float *)h2, (const float *)dl, (const double *)t->stat, (const double *)t->tot,
                        (const float *)t->P, t->part2, dxe);
-    const unsigned adam_blocks = kEmbEntries + (M6A_N_WEIGHTS - kEmbEntries + 63) / 64;
-    hipLaunchKernelGGL(train_adam_kernel, dim3(adam_blocks), dim3(64), 0, st, bt, (const float *)t->part2, n_chunks, (const double *)t->tot,
-                       (const float *)dxe, a, t->P, t->M, t->V, t->G);
-    t->n_launches += 6;
+    if (t->clip > 0.f) {
+        hipLaunchKernelGGL(train_grad_kernel, dim3(kGradBlocks), dim3(64), 0, st, bt, (const float *)t->part2, n_chunks, (const double *)t->tot,
+                           (const float *)dxe, t->G, t->sq);
+        hipLaunchKernelGGL(train_clip_adam_kernel, dim3((M6A_N_WEIGHTS + kClipThreads - 1) / kClipThreads), dim3(kClipThreads), 0, st,
+                           (const double *)t->sq, t->clip, a, t->P, t->M, t->V, t->G, t->norm);
+        t->have_norm = true;
+        t->n_launches += 7;
+    } else {
+        hipLaunchKernelGGL(train_adam_kernel, dim3(kGradBlocks), dim3(64), 0, st, bt, (const float *)t->part2, n_chunks, (const double *)t->tot,
+                           (const float *)dxe, a, t->P, t->M, t->V, t->G);
+        t->n_launches += 6;
+    }
     HIPCHK(c, hipGetLastError());
     return M6A_OK;
 }
@@ -533,7 +615,7 @@ int m6a_train_create(m6a_ctx *c, const float *weights, size_t n_floats, const m6
     t->cfg = k;
     const size_t wb = (size_t)M6A_N_WEIGHTS * 4;
     hipError_t e = hipMalloc((void **)&t->P, 4 * wb);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->stat, (size_t)(2 + kMaxChunks) * 2 * kH1 * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->stat, ((size_t)(2 + kMaxChunks) * 2 * kH1 + kGradBlocks + 1) * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&t->part2, (size_t)kMaxChunks * wb);
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_err, 8);
     if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_err, 8);
@@ -547,6 +629,7 @@ int m6a_train_create(m6a_ctx *c, const float *weights, size_t n_floats, const m6
     }
     t->M = t->P + M6A_N_WEIGHTS; t->V = t->M + M6A_N_WEIGHTS; t->G = t->V + M6A_N_WEIGHTS;
     t->tot = t->stat + 2 * kH1; t->part1 = t->tot + 2 * kH1;
+    t->sq = t->part1 + (size_t)kMaxChunks * 2 * kH1; t->norm = (float *)(t->sq + kGradBlocks);
     *out = t;
     return M6A_OK;
 }
@@ -712,6 +795,66 @@ int m6a_train_weights(m6a_trainer *t, float *weights, int64_t *n_steps)
     if (n_steps) *n_steps = t->n_steps;
     if (!weights) return fail(t->c, M6A_EINVAL, "null pointer argument");
     return copy_out(t, weights, t->P, (size_t)M6A_N_WEIGHTS * 4);
+}
+
+int m6a_train_set_clip(m6a_trainer *t, float max_norm)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    if (!(max_norm >= 0.f) || std::isinf(max_norm)) return fail(t->c, M6A_EINVAL, "max_norm must be finite and >= 0 (0 = no clipping)");
+    t->clip = max_norm;
+    t->have_norm = false;
+    return M6A_OK;
+}
+
+int m6a_train_last_norm(m6a_trainer *t, float *total_norm)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    if (!total_norm) return fail(t->c, M6A_EINVAL, "null pointer argument");
+    if (!(t->clip > 0.f)) return fail(t->c, M6A_EINVAL, "clipping is off: the step does not compute the gradient's norm (m6a_train_set_clip)");
+    if (!t->have_norm) return fail(t->c, M6A_EINVAL, "no step has been taken since clipping was set");
+    return copy_out(t, total_norm, t->norm, 4);
+}
+
+int m6a_train_state_get(m6a_trainer *t, float *m, float *v, int64_t *n_steps)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    m6a_ctx *c = t->c;
+    if (!m || !v) return fail(c, M6A_EINVAL, "null pointer argument");
+    if (is_device_ptr(m) || is_device_ptr(v)) return fail(c, M6A_EINVAL, "m and v are host pointers");
+    const size_t wb = (size_t)M6A_N_WEIGHTS * 4;
+    HIPCHK(c, hipMemcpyAsync(m, t->M, wb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(v, t->V, wb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t->n_syncs++;
+    if (n_steps) *n_steps = t->n_steps;
+    return M6A_OK;
+}
+
+int m6a_train_state_set(m6a_trainer *t, const float *m, const float *v, int64_t n_steps)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    m6a_ctx *c = t->c;
+    if (!m || !v) return fail(c, M6A_EINVAL, "null pointer argument");
+    if (is_device_ptr(m) || is_device_ptr(v)) return fail(c, M6A_EINVAL, "m and v are host pointers");
+    if (n_steps < 0) return fail(c, M6A_EINVAL, "n_steps must be >= 0");
+    for (int e = 0; e < M6A_N_WEIGHTS; e++) {
+        if (!std::isfinite(m[e])) return fail(c, M6A_EINVAL, "m[%d] is not finite", e);
+        if (!(v[e] >= 0.f) || !std::isfinite(v[e])) return fail(c, M6A_EINVAL, "v[%d] is negative or not finite", e);
+    }
+    // staged, with the running-statistic slots at zero: they are not parameters and the kernels never touch them
+    std::vector<float> mv((size_t)2 * M6A_N_WEIGHTS);
+    std::copy(m, m + M6A_N_WEIGHTS, mv.begin());
+    std::copy(v, v + M6A_N_WEIGHTS, mv.begin() + M6A_N_WEIGHTS);
+    for (int e = oMean; e < oW2; e++) mv[e] = mv[M6A_N_WEIGHTS + e] = 0.f;
+    HIPCHK(c, hipMemcpyAsync(t->M, mv.data(), mv.size() * 4, hipMemcpyHostToDevice, c->stream));    // M and V are adjacent
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t->n_syncs++;
+    t->n_steps = n_steps;
+    return M6A_OK;
 }
 
 int m6a_train_stats(const m6a_trainer *t, int64_t *n_steps, int64_t *n_launches, int64_t *n_syncs)

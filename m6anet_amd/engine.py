@@ -466,10 +466,17 @@ class M6ANetEngine:
         return site
 
 
-    def trainer(self, weights=None, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def trainer(self, weights=None, lr=4e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad=None):
         """A Trainer on this engine's device and stream (include/m6a.h: m6a_train_create), starting from `weights` (a 7 997-float
-        blob; None = init_weights(0)).  The engine's own weights are not touched."""
-        return Trainer(self, init_weights(0) if weights is None else weights, lr, betas, eps, weight_decay)
+        blob; None = init_weights(0)).  The engine's own weights are not touched.  clip_grad: Trainer.set_clip's max_norm."""
+        t = Trainer(self, init_weights(0) if weights is None else weights, lr, betas, eps, weight_decay)
+        if clip_grad is not None:
+            try:
+                t.set_clip(clip_grad)
+            except Exception:
+                t.close()
+                raise
+        return t
 
     def validate_pool(self, read_probs, off, n_iterations=1, n_samples=N_SAMPLES, seed=0):
         """The prediction part of the reference's `validate` (training_utils.py:233-253) from read
@@ -571,6 +578,30 @@ class Trainer:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         self._engine._chk(self._L.m6a_train_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"n_steps": a.value, "n_launches": b.value, "n_syncs": c.value}
+
+    def set_clip(self, max_norm):
+        """Gradient clipping for every later step: torch's clip_grad_norm_(params, max_norm) between the gradient and Adam
+        (include/m6a.h).  0 = off, the default."""
+        self._engine._chk(self._L.m6a_train_set_clip(self._h, float(max_norm)))
+
+    def last_norm(self):
+        """The last step's total gradient norm from before the scaling (clip_grad_norm_'s return value).  Raises with clipping off."""
+        v = C.c_float()
+        self._engine._chk(self._L.m6a_train_last_norm(self._h, C.byref(v)))
+        return float(v.value)
+
+    def optimizer_state(self):
+        """{'m', 'v', 'n_steps'}: Adam's moments in blob order (zeros in the running-statistic slots) and its step count t."""
+        m, v, n = np.empty(N_WEIGHT_FLOATS, np.float32), np.empty(N_WEIGHT_FLOATS, np.float32), C.c_int64()
+        self._engine._chk(self._L.m6a_train_state_get(self._h, m.ctypes.data, v.ctypes.data, C.byref(n)))
+        return {"m": m, "v": v, "n_steps": int(n.value)}
+
+    def load_optimizer_state(self, state):
+        """The inverse of optimizer_state(): on a Trainer made from weights(), this is the trainer both were taken from."""
+        m, v = np.ascontiguousarray(state["m"], np.float32).ravel(), np.ascontiguousarray(state["v"], np.float32).ravel()
+        if m.size != N_WEIGHT_FLOATS or v.size != N_WEIGHT_FLOATS:
+            raise ValueError("m and v must have %d floats" % N_WEIGHT_FLOATS)
+        self._engine._chk(self._L.m6a_train_state_set(self._h, m.ctypes.data, v.ctypes.data, int(state["n_steps"])))
 
     def state_dict(self):
         """The reference's state_dict keys -> NumPy arrays (state_dict_from_weights), num_batches_tracked = the steps taken."""

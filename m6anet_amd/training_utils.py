@@ -8,7 +8,7 @@ sampled reads of every site in every pass).
 `train_one_epoch` and `train` (training_utils.py:61-210) on engine.Trainer: the forward in training mode, the
 backward pass and Adam run in HIP (include/m6a.h: m6a_train_epoch) on the data set held as the flat arrays of
 include/m6a.h, and the samplers of m6anet/utils/sampler_utils.py as functions of (labels, RandomState).
-DESIGN.md section 8 says what is not built (gradient clipping, the weighted loss, the per-motif samplers).
+DESIGN.md section 8 says what is not built (the weighted loss, the per-motif samplers, more than one GPU).
 """
 import os
 import time
@@ -205,19 +205,43 @@ def subset(X, site_kmers, off, sites):
     return np.ascontiguousarray(X[rows]), np.ascontiguousarray(site_kmers[sites]), np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
 
 
+def _takes_checkpoint(save):
+    """Whether a save callback accepts the keyword `checkpoint` (by name or through **kwargs)."""
+    import inspect
+    try:
+        params = inspect.signature(save).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(p.kind is p.VAR_KEYWORD or (p.name == "checkpoint" and p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)) for p in params)
+
+
 def train(trainer, make_engine, data, y, splits, sampler, n_epoch, batch_size, seed, save_dir=None, save_per_epoch=10, n_iterations=1,
-          save=None, verbose=True):
+          save=None, verbose=True, clip_grad=None, start_epoch=0, rs=None, rs_state=None, results=None):
     """The reference's train loop (training_utils.py:61-145).  data = (X, site_kmers, off) of every loaded site, y their labels,
     splits = join_labels' site numbers.  Each epoch: the sampler's order over the Train sites, train_one_epoch, then `validate`
     on a fresh engine made from the trainer's weights (make_engine(weights)) over the Val sites; the per-epoch lists are kept and
-    every save_per_epoch epochs save(epoch, weights, state_dict) is called.  Returns (train_results, val_results)."""
+    every save_per_epoch epochs save(epoch, weights, state_dict) is called.  Returns (train_results, val_results).
+
+    clip_grad: the reference's clip_grad (clip_grad_norm_ between backward and the optimizer's step; None leaves the trainer as it is).
+    Continuing a run: start_epoch = the epochs already done (epochs are numbered start_epoch + 1 .. n_epoch), `rs` the sampler's
+    RandomState or `rs_state` its get_state() at that point, `results` = (train_results, val_results) so far, which are extended; the
+    trainer is expected to hold that epoch's weights and optimizer state.  A `save` that takes the keyword `checkpoint` also receives
+    checkpoint = {"epoch", "optimizer" (Trainer.optimizer_state()), "rs_state", "train_results", "val_results"}."""
     assert save_per_epoch <= n_epoch
+    assert 0 <= start_epoch <= n_epoch
     X, site_kmers, off = data
-    rs = np.random.RandomState(seed)
+    if rs is None:
+        rs = np.random.RandomState(seed)
+    if rs_state is not None:
+        rs.set_state(rs_state)
+    if clip_grad is not None:
+        trainer.set_clip(clip_grad)
     train_sites = splits["Train"]
     val = subset(X, site_kmers, off, splits["Val"])
-    train_results, val_results, total = {}, {}, 0.0
-    for epoch in range(1, n_epoch + 1):
+    train_results, val_results = results if results is not None else ({}, {})
+    total = 0.0
+    with_checkpoint = save is not None and _takes_checkpoint(save)
+    for epoch in range(start_epoch + 1, n_epoch + 1):
         order = np.ascontiguousarray(train_sites[sampler(y[train_sites], rs)], np.int64)
         tr = train_one_epoch(trainer, X, site_kmers, off, y, order, batch_size, seed=(int(seed) << 20) + epoch)
         weights = trainer.weights()
@@ -236,5 +260,10 @@ def train(trainer, make_engine, data, y, splits, sampler, n_epoch, batch_size, s
             for k, v in res.items():
                 out.setdefault(k, []).append(v)
         if save is not None and epoch % save_per_epoch == 0:
-            save(epoch, weights, trainer.state_dict())
+            if with_checkpoint:
+                save(epoch, weights, trainer.state_dict(),
+                     checkpoint={"epoch": epoch, "optimizer": trainer.optimizer_state(), "rs_state": rs.get_state(),
+                                 "train_results": train_results, "val_results": val_results})
+            else:
+                save(epoch, weights, trainer.state_dict())
     return train_results, val_results

@@ -4,7 +4,9 @@ over-sampled order, through m6a_train_epoch with the data set resident in device
 indices, m6a_train_sample) through the float32 torch restatement of the model (tests/train_torch.py) on the CPUs this process is
 granted.  Writes one JSON object (default profiles/r19_train_epoch.json).
 
-    python tools/measure_train.py [--sites 100000] [--cpu_steps 100] [--out profiles/r19_train_epoch.json]
+    python tools/measure_train.py [--sites 100000] [--cpu_steps 100] [--clip_grad 1.0] [--out profiles/r19_train_epoch.json]
+
+--clip_grad times the step with gradient clipping on (seven launches instead of six; the torch run clips with clip_grad_norm_).
 
 The GPU figure is a host clock around the call and the stream synchronise behind it, the median of --repeats epochs after one warm-up
 epoch (same trainer state at the start of each: a new trainer per epoch).  The CPU figure times --cpu_steps steps and scales to
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--batch_size", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--cpu_steps", type=int, default=100)
+    ap.add_argument("--clip_grad", type=float, default=None, help="max_norm of gradient clipping; not set: the default step")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r19_train_epoch.json"))
     a = ap.parse_args()
     import torch
@@ -48,7 +51,7 @@ def main():
     dev = [torch.from_numpy(v).cuda() for v in (X, km, off, y, order)]
     times, stats = [], None
     for rep in range(a.repeats + 1):
-        tr = eng.trainer(w)
+        tr = eng.trainer(w, clip_grad=a.clip_grad) if a.clip_grad is not None else eng.trainer(w)
         s0 = tr.stats()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -69,11 +72,16 @@ def main():
     for k in range(k_steps):
         o = order[k * a.batch_size:(k + 1) * a.batch_size]
         batches.append((X[idx[k * a.batch_size * bag:(k + 1) * a.batch_size * bag]], km[o], y[o], bag))
-    TT.run(w, batches[:3], torch.float32)                                   # warm-up
+    if a.clip_grad is None:
+        cpu_run = lambda b: TT.run(w, b, torch.float32)
+    else:
+        import train_clip_torch as CT
+        cpu_run = lambda b: CT.run(w, b, torch.float32, a.clip_grad)
+    cpu_run(batches[:3])                                                    # warm-up
     t0 = time.perf_counter()
-    TT.run(w, batches, torch.float32)
+    cpu_run(batches)
     cpu_s = (time.perf_counter() - t0) / k_steps * n_steps
-    res = {"sites": a.sites, "order": int(len(order)), "batch_size": a.batch_size, "bag": bag, "steps": n_steps,
+    res = {"clip_grad": a.clip_grad, "sites": a.sites, "order": int(len(order)), "batch_size": a.batch_size, "bag": bag, "steps": n_steps,
            "gpu_epoch_s": gpu_s, "gpu_epoch_s_all": times, "gpu_us_per_step": gpu_s / n_steps * 1e6,
            "launches_per_epoch": stats["n_launches"], "launches_per_step": (stats["n_launches"] - 2) / n_steps, "syncs_per_epoch": stats["n_syncs"],
            "cpu_threads": torch.get_num_threads(), "cpu_steps_timed": k_steps, "cpu_epoch_s_scaled": cpu_s, "cpu_us_per_step": cpu_s / n_steps * 1e6,

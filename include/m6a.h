@@ -143,6 +143,56 @@ int m6a_infer(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, const int
               uint32_t seed, int rng_mode, int64_t batch_size, int64_t save_per_batch,
               float *read_prob, float *site_prob, double *mod_ratio);
 
+/* The site probability in closed form.  The reference's estimator draws n_samples reads of a site uniformly, independently and
+ * with replacement, n_iters times, and averages 1 - prod(1 - p) (m6anet/utils/inference_utils.py:74-104); what it estimates is
+ *     E = 1 - (mean_i (1 - p_i)) ^ n_samples
+ * and m6a_site_expectation computes E itself: no random stream, no flush groups, no seed -- the result depends on the site's
+ * reads and n_samples alone, not on the kernel variant, the host-offsets hint, batch boundaries, m6a_set_job_offset or the shard.
+ * The operation (tests/site_expectation_statement.py states it in NumPy float64; host and device give the same bits), for a site
+ * with reads p_0 .. p_{n-1} (float32) and K = n_samples:
+ *   pairs m2^K - (m1^K)^2 cancels -- one unit in the last place of a power is 1e-16 / mc_sigma in the root -- so the sums and the
+ *         powers are carried as unevaluated pairs (hi, lo) of doubles and rounded once.  Every operation below is one IEEE
+ *         addition, subtraction or multiplication of doubles, evaluated as written (no fma, no reassociation):
+ *           two_sum(a, b):   s = a + b;  bb = s - a;  e = (a - (s - bb)) + (b - bb)               -> (s, e), a + b = s + e exactly
+ *           quick(s, e):     hi = s + e;  lo = e - (hi - s)                                        -> (hi, lo)
+ *           split(a):        c = 134217729.0 * a;  h = c - (c - a);  l = a - h                     -> (h, l)
+ *           add_d(x, b):     (s, e) = two_sum(x.hi, b);  quick(s, e + x.lo)
+ *           add(x, y):       (s, e) = two_sum(x.hi, y.hi);  quick(s, e + (x.lo + y.lo))
+ *           mul(x, y):       p = x.hi * y.hi;  (ah, al) = split(x.hi);  (bh, bl) = split(y.hi);
+ *                            e = ((ah * bh - p) + ah * bl + al * bh) + al * bl;  quick(p, e + (x.hi * y.lo + x.lo * y.hi))
+ *   u_i   = 1.0 - (double)p_i;  w_i = u_i * u_i (one rounded product)
+ *   sums  64 partial pairs a[j], b[j], j = 0..63, all (0, 0) at first; for i = 0, 1, .., n-1 in this order
+ *             a[i % 64] = add_d(a[i % 64], u_i);   b[i % 64] = add_d(b[i % 64], w_i)
+ *         then for h = 32, 16, 8, 4, 2, 1:  a[j] = add(a[j], a[j + h]) and b[j] = add(b[j], b[j + h]) for j < h;
+ *         S1 = a[0].hi, S2 = b[0].hi
+ *         (a partial that took no read is (0, 0) and add(x, (0, 0)) = x for every finite pair, while a partial that took an
+ *         infinite or NaN value is NaN from that addition on; so a bag of <= 32 reads folded 16, 8, 4, 2, 1 by one lane has the
+ *         bits a wavefront per site gives it: both kernel variants follow this one order)
+ *   m1    = S1 / (double)n,  m2 = S2 / (double)n
+ *   x^K   r = (1, 0), b = (x, 0), e = K;  while e != 0: { if (e & 1) r = mul(r, b);  e >>= 1;  if (e != 0) b = mul(b, b); };
+ *         x^K = r.hi -- IEEE multiplications and additions only, no pow / exp / log
+ *   site_prob = (float)(1.0 - m1^K)
+ *   mc_sigma  = sqrt(max(m2^K - m1^K * m1^K, 0.0)), a double: the standard deviation of ONE iteration of the reference's
+ *         estimator; mc_sigma / sqrt(n_iters) is the standard error of the number m6a_site_pool writes in its default mode
+ *   mod_ratio = m6a_site_pool's: (double)count(p_i >= thr) / (double)n
+ * read_prob values outside [0, 1] and NaN are not checked: they propagate through the arithmetic above (a NaN read makes the
+ * site's site_prob and mc_sigma NaN and counts as below the threshold).  n_samples in 1..M6A_MAX_SAMPLES, an empty bag gives NaN
+ * in all three outputs, pointers all host (synchronous) or all device (stream-ordered; m6a_set_host_offsets applies) -- the
+ * rules of m6a_site_pool.  mc_sigma [S] may be NULL.  No reference counterpart: the reference has only the estimator. */
+int m6a_site_expectation(m6a_ctx *ctx, const float *read_prob, const int64_t *off, int64_t n_sites, int n_samples,
+                         float read_proba_threshold, float *site_prob, double *mod_ratio, double *mc_sigma);
+/* What site_prob means in m6a_site_pool, m6a_infer and m6a_job_end on this context (and so in the inference a command runs from
+ * an m6a_prep_sites handle).  M6A_SITE_SAMPLED (the default): the replay of the reference's random stream described at
+ * m6a_site_pool.  M6A_SITE_EXPECTED: m6a_site_expectation's site_prob; n_iters, seed, rng_mode, batch_size and save_per_batch
+ * (and the job offset against them) are validated as before and otherwise ignored, and no random stream, pairwise-sum plan or
+ * index table is built or waited for -- m6a_create's background set-up stops at its next step when the mode is set.  mod_ratio
+ * is the same in both modes.  Setting the mode back gives the default's bits again; a context on which the mode was never set
+ * behaves as before.  Any other value is M6A_EINVAL and changes nothing.  m6a_last_pool_variant reports "expected-lane"
+ * (every bag of the same n <= 32 reads: a lane per site) or "expected-wave" (a wavefront per site) for calls in this mode
+ * and for m6a_site_expectation. */
+enum { M6A_SITE_SAMPLED = 0, M6A_SITE_EXPECTED = 1 };
+int m6a_set_site_mode(m6a_ctx *ctx, int mode);
+
 /* Streaming form of m6a_infer: the batch loop of run_inference (m6anet/utils/inference_utils.py:33-54) fed as the
  * DataLoader produces it, so a reference-side binding keeps its loader and its loop.
  *   m6a_job_begin   the arguments calculate_site_proba / the flush test get per job (inference_utils.py:47,54);
@@ -315,7 +365,8 @@ int m6a_set_scan_driver(m6a_ctx *ctx, int mode);
  * VGPR index mode).  Results are identical. */
 int m6a_set_table_variant(m6a_ctx *ctx, int mode);
 /* pooling kernel variant used by the last pool/infer call:
- * "table-reg" | "table" (uniform bags) | "ragged-table" | "scan-group" | "scan-site" (ragged bags) */
+ * "table-reg" | "table" (uniform bags) | "ragged-table" | "scan-group" | "scan-site" (ragged bags) |
+ * "expected-lane" | "expected-wave" (M6A_SITE_EXPECTED and m6a_site_expectation) */
 const char *m6a_last_pool_variant(const m6a_ctx *ctx);
 
 const char *m6a_version(void);

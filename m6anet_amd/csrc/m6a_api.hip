@@ -784,8 +784,9 @@ int rtab_prepare(m6a_ctx *c, hipStream_t st, PoolArgs a, int64_t nmax, int64_t g
 // What pool_plan decided for one call and what pool_run needs to launch it: nothing here depends on the read
 // probabilities or the outputs, so the plan can be made on another stream while the encoder still runs.
 struct PoolPlan {
-    enum Kind { none, table_reg, table, ragged_table, scan_group, scan_site } kind = none;   // none: no sites, no launch
+    enum Kind { none, table_reg, table, ragged_table, scan_group, scan_site, expected } kind = none;   // none: no sites, no launch
     PoolArgs a = {};                          // everything but read_prob, site_prob, mod_ratio, thr and clk
+    int64_t bag_min = 0, bag_max = 0;         // expected: they choose the variant of site_expect_kernel
     unsigned blocks = 0, start_blocks = 0;    // grid of the pooling kernel; scan_site: of pool_scan_start_kernel in front of it
     size_t lds = 0;                           // dynamic LDS of the pooling kernel (ragged_table sizes its own from the bag caps)
     int64_t n_big = 0, cap_big = 0, cap_small = 0;   // ragged_table: bags above M6A_RTAB_SMALL_N reads, and the largest bag of either launch
@@ -800,6 +801,18 @@ int pool_plan(m6a_ctx *c, hipStream_t st, const int64_t *off, int64_t S, int T, 
     *p = PoolPlan();
     PoolArgs &a = p->a;
     if (S <= 0) return M6A_OK;
+    if (c->site_mode == M6A_SITE_EXPECTED) {
+        // the closed form needs none of the set-up below (and nothing on st); the job offset is held to the flush geometry as
+        // in the default mode, so that a call which is wrong there is wrong here
+        if (!base_is_group_start(c->job_offset, bs, spb))
+            return fail(c, M6A_EINVAL, "job offset %lld does not start a flush group for batch_size=%lld save_per_batch=%lld",
+                        (long long)c->job_offset, (long long)bs, (long long)spb);
+        if (c->bag_min < 0 || c->bag_max > 0x7fffffff) return fail(c, M6A_EINVAL, "off[] is not a non-decreasing CSR array");
+        a.off = off; a.n_sites = S; a.K = K;
+        p->bag_min = c->bag_min; p->bag_max = c->bag_max;
+        p->kind = PoolPlan::expected;
+        return M6A_OK;
+    }
     int rc = ensure_groups(c, st, S, bs, spb);
     if (rc) return rc;
     const int64_t nmin = c->bag_min, nmax = c->bag_max;
@@ -879,10 +892,39 @@ int pool_plan(m6a_ctx *c, hipStream_t st, const int64_t *off, int64_t S, int T, 
     return M6A_OK;
 }
 
+// The closed-form site probability (m6a_expect.hip) on the context's stream.  Every bag of the same n <= 32 reads: a lane per site,
+// whole float4s where the bags are (n a multiple of 4, read_prob 16-byte aligned); otherwise a wavefront per site, four sites per
+// turn, on the four wavefronts per SIMD its registers admit (the sums are pairs of doubles).  The bits are the same (one summation order, include/m6a.h).
+int launch_expect(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int K, float thr, int64_t nmin, int64_t nmax,
+                  float *site, double *mod, double *sigma)
+{
+    if (S <= 0) return M6A_OK;
+    ExpectArgs a;
+    a.read_prob = rp; a.off = off; a.site_prob = site; a.mod_ratio = mod; a.mc_sigma = sigma;
+    a.n_sites = S; a.K = K; a.thr = thr;
+    const bool lane = nmin == nmax && nmin >= 1 && nmin <= 32;
+    a.uniform_n = lane ? (int)nmin : 0;
+    c->pool_variant = lane ? "expected-lane" : "expected-wave";
+    prof_begin(c, 1);
+    if (lane) {
+        const unsigned blocks = (unsigned)std::min<int64_t>((S + 255) / 256, (int64_t)c->n_cu * 8);
+        if (nmin % 4 == 0 && (uintptr_t)rp % 16 == 0) hipLaunchKernelGGL(site_expect_lane_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(site_expect_lane_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, a);
+    } else {
+        const unsigned blocks = (unsigned)std::min<int64_t>((S + 15) / 16, (int64_t)c->n_cu * 4);
+        hipLaunchKernelGGL(site_expect_wave_kernel, dim3(blocks), dim3(256), 0, c->stream, a);
+    }
+    prof_end(c, 1);
+    HIPCHK(c, hipGetLastError());
+    return M6A_OK;
+}
+
 // The pooling kernels of a plan, on the context's stream: no allocation, no copy, no host synchronisation here.
 int pool_run(m6a_ctx *c, const PoolPlan &p, const float *rp, float thr, float *site, double *mod)
 {
     if (p.kind == PoolPlan::none) return M6A_OK;
+    if (p.kind == PoolPlan::expected)
+        return launch_expect(c, rp, p.a.off, p.a.n_sites, p.a.K, thr, p.bag_min, p.bag_max, site, mod, nullptr);
     static const char *const names[] = {"none", "table-reg", "table", "ragged-table", "scan-group", "scan-site"};
     PoolArgs a = p.a;
     a.read_prob = rp; a.site_prob = site; a.mod_ratio = mod; a.thr = thr;
@@ -891,7 +933,7 @@ int pool_run(m6a_ctx *c, const PoolPlan &p, const float *rp, float thr, float *s
     const bool k20 = a.K == 20;               // the kernels that draw per site have an instantiation for the reference's 20 samples
     prof_begin(c, 1);
     switch (p.kind) {
-    case PoolPlan::none: break;
+    case PoolPlan::none: case PoolPlan::expected: break;
     case PoolPlan::table_reg:
         hipLaunchKernelGGL(pool_reg_kernel, dim3(p.blocks), dim3(64), 0, c->stream, a);
         break;
@@ -1042,10 +1084,14 @@ void warm_default(m6a_ctx *c)
     hipLaunchKernelGGL(m6a_touch_kernels, dim3(1), dim3(1), 0, st);
     hipLaunchKernelGGL(m6a_touch_pool_reg, dim3(1), dim3(1), 0, st);
     hipLaunchKernelGGL(m6a_touch_pool_rtab, dim3(1), dim3(1), 0, st);
+    hipLaunchKernelGGL(m6a_touch_expect, dim3(1), dim3(1), 0, st);
     (void)hipGetLastError();
-    int rc = ensure_mean_plan(c, st, T);
-    if (!rc) rc = ensure_raw(c, st, seed, stream_need(gmax, T, K));
-    if (!rc) {
+    // m6a_set_site_mode(M6A_SITE_EXPECTED) needs none of what follows: each step that has not begun is skipped (a later call
+    // in the default mode builds what it misses, as after M6A_WARMUP=0)
+    auto cancelled = [c] { return c->warm_cancel.load(std::memory_order_relaxed); };
+    int rc = cancelled() ? 0 : ensure_mean_plan(c, st, T);
+    if (!rc && !cancelled()) rc = ensure_raw(c, st, seed, stream_need(gmax, T, K));
+    if (!rc && !cancelled()) {
         // The ragged kernels' per-bag-size index tables are NOT built on speculation (rounds 2-3 built sizes 2..511 here: 1.4 GB
         // and a 1.2 ms pass that a uniform-bag or small caller never uses); a first ragged call builds the sizes it meets inside
         // the call.  M6A_WARM_SLOTS=N asks for sizes 2..N-1 up front (a service that knows ragged jobs are coming: 512 covers
@@ -1206,7 +1252,7 @@ void m6a_destroy(m6a_ctx *c)
     for (void *p : c->graveyard) (void)hipFree(p);
     if (c->rt.C) (void)hipFree(c->rt.C);
     if (c->rt.RS) (void)hipFree(c->rt.RS);
-    for (DevBuf *b : {&c->ctl_dev, &c->rt_rank, &c->rt_order, &c->sOffChunk, &c->jX, &c->jP, &c->jOff, &c->gSite, &c->gMod, &c->gP, &c->mt_scratch}) b->release();
+    for (DevBuf *b : {&c->ctl_dev, &c->rt_rank, &c->rt_order, &c->sOffChunk, &c->jX, &c->jP, &c->jOff, &c->gSite, &c->gMod, &c->gP, &c->mt_scratch, &c->sSigma}) b->release();
     for (auto e : c->job.ev_h2d) (void)hipEventDestroy(e);
     for (auto e : c->job.ev_enc) (void)hipEventDestroy(e);
     release_staging(c);
@@ -1374,6 +1420,61 @@ int m6a_site_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, in
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(site, c->sSite.p, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(mod, c->sMod.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync_and_check(c);
+}
+
+int m6a_set_site_mode(m6a_ctx *c, int mode)
+{
+    if (!c) return M6A_EINVAL;
+    if (mode != M6A_SITE_SAMPLED && mode != M6A_SITE_EXPECTED) {
+        settle(c);                                             // the background set-up writes the same error text
+        return fail(c, M6A_EINVAL, "site mode must be M6A_SITE_SAMPLED (0) or M6A_SITE_EXPECTED (1), not %d", mode);
+    }
+    if (mode == M6A_SITE_EXPECTED) c->warm_cancel.store(true, std::memory_order_relaxed);   // before anybody waits for it
+    settle(c);
+    if (c->job.open) return job_busy(c);                       // m6a_job_end pools in the mode the job was begun in
+    c->site_mode = mode;
+    return M6A_OK;
+}
+
+int m6a_site_expectation(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int K, float thr,
+                         float *site, double *mod, double *sigma)
+{
+    settle(c);
+    HintScope hint_scope(c);
+    if (c && c->job.open) return job_busy(c);
+    int rc = check_pool_args(c, S, 1, K, M6A_RNG_NUMPY, 1, 1);
+    if (rc) return rc;
+    if (S == 0) return M6A_OK;
+    if (!rp || !off || !site || !mod) return fail(c, M6A_EINVAL, "null pointer argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev = is_device_ptr(rp);
+    if (dev != is_device_ptr(off) || dev != is_device_ptr(site) || dev != is_device_ptr(mod) || (sigma && dev != is_device_ptr(sigma)))
+        return fail(c, M6A_EINVAL, "read_prob, off, site_prob, mod_ratio, mc_sigma must be all host or all device pointers");
+    if (dev) {
+        rc = bag_stats(c, off, S);
+        if (rc) return rc;
+        if (c->bag_min < 0 || c->bag_max > 0x7fffffff) return fail(c, M6A_EINVAL, "off[] is not a non-decreasing CSR array");
+        return launch_expect(c, rp, off, S, K, thr, c->bag_min, c->bag_max, site, mod, sigma);
+    }
+    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
+    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+    const int64_t R = off[S];
+    HIPCHK(c, c->sP.ensure((size_t)std::max<int64_t>(R, 1) * 4));
+    HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
+    HIPCHK(c, c->sSite.ensure((size_t)S * 4));
+    HIPCHK(c, c->sMod.ensure((size_t)S * 8));
+    if (sigma) HIPCHK(c, c->sSigma.ensure((size_t)S * 8));
+    HIPCHK(c, hipMemcpyAsync(c->sP.p, rp, (size_t)R * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    host_bag_range(c, off, S);
+    if (c->bag_max > 0x7fffffff) return fail(c, M6A_EINVAL, "a bag of more than 2^31 reads");
+    rc = launch_expect(c, (const float *)c->sP.p, (const int64_t *)c->sOff.p, S, K, thr, c->bag_min, c->bag_max,
+                       (float *)c->sSite.p, (double *)c->sMod.p, sigma ? (double *)c->sSigma.p : nullptr);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(site, c->sSite.p, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(mod, c->sMod.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sigma) HIPCHK(c, hipMemcpyAsync(sigma, c->sSigma.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_and_check(c);
 }
 

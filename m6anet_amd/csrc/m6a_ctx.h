@@ -3,6 +3,7 @@
 //   m6a_host_ring.hip  host-pointer calls: pinned staging ring, copy threads, H2D || encoder || D2H
 //   m6a_job.hip        the streaming job (m6a_job_begin / feed / end): the reference's batch loop fed as the loader produces it
 //   m6a_comm.hip       RCCL bound at run time, m6a_comm_*, m6a_gather, m6a_gather_reads, m6a_device_link
+//   m6a_expect.hip     the closed-form site probability: site_expect_kernel (its launches are in m6a_api.hip)
 //   m6a_validate.hip   validation forward: the without-replacement sampler on host threads, m6a_validate / m6a_validate_pool
 #pragma once
 #include <hip/hip_runtime.h>
@@ -273,6 +274,9 @@ struct m6a_ctx {
     int comm_rank = 0, comm_world = 0;
     Profiler prof;
     const char *pool_variant = "none";
+    int site_mode = M6A_SITE_SAMPLED;         // m6a_set_site_mode: what site_prob means in pool / infer / job_end
+    std::atomic<bool> warm_cancel{false};     // the background set-up stops at its next step (the mode went to M6A_SITE_EXPECTED)
+    DevBuf sSigma;                            // host-pointer m6a_site_expectation: mc_sigma [S]
 };
 
 namespace m6a_detail {

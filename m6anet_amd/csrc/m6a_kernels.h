@@ -87,6 +87,18 @@ struct PoolArgs {
     unsigned long long *clk;      // clock stamps of a profiled launch, else null (m6a_clk_stamp)
 };
 
+// the closed-form site probability (m6a_expect.hip)
+struct ExpectArgs {
+    const float *read_prob;       // [R]
+    const int64_t *off;           // [S+1]
+    float *site_prob;             // [S]
+    double *mod_ratio;            // [S]
+    double *mc_sigma;             // [S] or null
+    int64_t n_sites;
+    int K, uniform_n;             // site_expect_lane_kernel: every bag has this many reads (1..32), off[s] = s * uniform_n is not loaded
+    float thr;
+};
+
 // per-bag-size index tables (m6a_pool_rtab.hip): slot k holds C (accepted draws of the whole stream as u16 byte
 // offsets 4*v) and RS (number of accepted words before every 64-word block, n_blk + 1 entries)
 struct RtabBuild {
@@ -137,9 +149,12 @@ __global__ void rtab_to_reg_table_kernel(const uint16_t *C, int64_t A, int64_t r
 __global__ void rtab_to_lds_table_kernel(const uint16_t *C, int64_t A, int K, int rows, int jmax, const int *iter_of, uint32_t *tab);
 __global__ void rtab_prep_kernel(PoolArgs a, RtabUse u, uint32_t *cursor, uint32_t *order, unsigned n_order_blocks);
 template <int KT> __global__ void pool_rtab_kernel(PoolArgs a, RtabUse u);
+__global__ void site_expect_wave_kernel(ExpectArgs a);
+template <bool VEC4> __global__ void site_expect_lane_kernel(ExpectArgs a);
 
 __global__ void m6a_touch_kernels();
 __global__ void m6a_touch_pool_reg();
 __global__ void m6a_touch_pool_rtab();
+__global__ void m6a_touch_expect();
 
 #endif

@@ -354,6 +354,31 @@ class M6ANetEngine:
                                         _lib.RNG_NUMPY, int(batch_size), int(save_per_batch), aS.ptr, aM.ptr))
         return site, mod
 
+    SITE_MODES = {"sampled": 0, "expected": 1}            # M6A_SITE_SAMPLED / M6A_SITE_EXPECTED (include/m6a.h)
+
+    def set_site_mode(self, mode):
+        """What site_probs means in calculate_site_proba / infer / job_end on this engine.  "sampled" (the default): the replay of
+        the reference's random draws.  "expected": the closed form those draws estimate, 1 - mean(1 - p)^n_samples -- n_iters,
+        seed, batch_size and save_per_batch are still checked and otherwise have no effect (include/m6a.h: m6a_set_site_mode)."""
+        if mode not in self.SITE_MODES:
+            raise ValueError("site mode must be 'sampled' or 'expected', not %r" % (mode,))
+        self._chk(self._L.m6a_set_site_mode(self._h, self.SITE_MODES[mode]))
+
+    def site_expectation(self, read_probs, off, n_samples=N_SAMPLES, want_sigma=False, read_proba_threshold=DEFAULT_READ_THRESHOLD):
+        """The closed-form site probability (include/m6a.h: m6a_site_expectation), whatever the engine's site mode.  Returns
+        (site_probs float32 [S], mod_ratios float64 [S]) or, with want_sigma, (site_probs, mod_ratios, mc_sigma float64 [S]):
+        mc_sigma / sqrt(n_iters) is the standard error of the sampled mode's site probability."""
+        aP, aO = _Arg(read_probs, np.float32, "float32"), _Arg(off, np.int64, "int64")
+        S = aO.size - 1
+        site = self._out(aP.is_dev, S, np.float32, "float32")
+        mod = self._out(aP.is_dev, S, np.float64, "float64")
+        sigma = self._out(aP.is_dev, S, np.float64, "float64") if want_sigma else None
+        aS, aM = _Arg(site, np.float32, "float32"), _Arg(mod, np.float64, "float64")
+        aG = _Arg(sigma, np.float64, "float64") if want_sigma else None
+        self._chk(self._L.m6a_site_expectation(self._h, aP.ptr, aO.ptr, S, int(n_samples), float(np.float32(read_proba_threshold)),
+                                               aS.ptr, aM.ptr, aG.ptr if aG else None))
+        return (site, mod, sigma) if want_sigma else (site, mod)
+
     def infer(self, X, site_kmers, off, n_iters, n_samples=N_SAMPLES,
               read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16, save_per_batch=2,
               want_read_probs=True, out=None):

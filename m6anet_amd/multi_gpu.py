@@ -104,6 +104,8 @@ def rank_argv(args):
             argv += ["--" + name, str(v)]
     if args.drop_unflushed_tail:
         argv.append("--drop_unflushed_tail")
+    if getattr(args, "site_proba", "sampled") != "sampled":  # the command's own flag (inference.command_parser); the default is not spelled out
+        argv += ["--site_proba", args.site_proba]
     return argv
 
 

@@ -78,6 +78,11 @@ def cli_parser():
     return parser
 
 
+def command_parser():
+    """cli_parser() and `inference`'s --site_proba: the parser of the `eventalign_inference` command"""
+    return inference.add_site_proba(cli_parser())
+
+
 GZ = ("data.site_proba.csv", "data.indiv_proba.csv")
 
 

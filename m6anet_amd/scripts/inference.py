@@ -68,6 +68,25 @@ def cli_parser():
     return parser
 
 
+SITE_PROBA_MODES = ("sampled", "expected")            # M6ANetEngine.set_site_mode
+
+
+def add_site_proba(parser):
+    """--site_proba, which `inference` and `eventalign_inference` add on top of their cli_parser()"""
+    parser.add_argument("--site_proba", choices=SITE_PROBA_MODES, default="sampled",
+                        help="what probability_modified in data.site_proba.csv is.  sampled: the reference's Monte-Carlo estimate, its "
+                             "random draws replayed to the bit.  expected: the quantity those draws estimate, in closed form -- "
+                             "1 - mean(1 - p)^20 over the site's reads -- which is deterministic and does not depend on the flush groups or "
+                             "on --gpus; with it --num_iterations and --seed have no effect.  Every other column and data.indiv_proba.csv "
+                             "are the same in both modes.")
+    return parser
+
+
+def command_parser():
+    """cli_parser() and --site_proba: the parser of the `inference` command"""
+    return add_site_proba(cli_parser())
+
+
 def check_loader(args):
     """--loader device: what it refuses, as an argument error before any rank is launched or any file is written"""
     if getattr(args, "loader", "host") != "device":
@@ -127,6 +146,8 @@ def make_engine_for(args, weights, device):
     if env is not None and env not in ENCODER_ENV_VALUES:
         raise ValueError("M6A_ENCODER=%s: must be one of %s" % (env, "|".join(v for v in ENCODER_ENV_VALUES if v)))
     engine = M6ANetEngine(weights=weights, device=device)
+    if getattr(args, "site_proba", "sampled") == "expected":     # first: the context's background set-up for the sampling stops
+        engine.set_site_mode("expected")
     choice = getattr(args, "encoder", None)
     if choice is not None:
         engine.set_encoder_variant(ENCODER_MODES[choice])

@@ -55,6 +55,7 @@ enum { M6A_RNG_NUMPY = 0 };
 #define M6A_N_WEIGHTS 7997
 #define M6A_N_FEATURES 9     /* [dwell, std, mean] x {-1,0,+1}: DeaggregateNanopolish, blocks.py:113 */
 #define M6A_MAX_SAMPLES 64
+#define M6A_N_REPR 32        /* floats of the read representation: the width of the encoder's second layer (m6anet.toml:23-28) */
 #define M6A_N_KMERS 66       /* vocabulary of 5-mers the DRACH 7-mers are made of (constants.py:29-36): k-mer ids are 0..65 */
 
 /* Flat float32 weight blob, in this order (state-dict keys of m6anet/model/model.py:40-69,
@@ -120,6 +121,24 @@ int m6a_host_is_pinned(const void *p, size_t bytes);
  *   read_prob  [R] float32 out */
 int m6a_encode_reads(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, const int64_t *off,
                      int64_t n_sites, float *read_prob);
+
+/* The read representation.  Replaces MILModel.get_read_representation({'X','kmer'}) (m6anet/model/model.py:85-97) on the
+ * m6anet.toml topology: the output of the encoder's second layer after its ReLU,
+ *     repr[r][o] = relu(b2[o] + sum_k W2[o][k] * relu(batchnorm(b1[k] + sum_j W1[k][j] * [x(9) | emb(6)][j]))),   o = 0..31,
+ * every float32 sum in the order the reference's CPU arithmetic runs it (an fma chain over j, then + b1; one fma for the
+ * batch norm; an fma chain over k = 0..149, then + b2: the order stated above enc_kernel in m6a_kernels.hip), so the
+ * values are the reference's bits.  relu keeps NaN, as torch's does.
+ *   X, site_kmers, off, n_sites  as m6a_encode_reads takes and checks them (m6a_set_host_offsets is consumed; n_sites == 0
+ *              is M6A_OK with nothing written)
+ *   repr       [R][M6A_N_REPR] float32 out, row r = read r, unit o at repr[r * 32 + o]; NULL is M6A_EINVAL and nothing is
+ *              launched; a device pointer must be 16-byte aligned
+ *   read_prob  [R] float32 out, or NULL: what m6a_encode_reads gives with the default encoder, bit for bit
+ * The arithmetic does not depend on m6a_set_encoder_variant or M6A_ENCODER: one kernel (enc_repr_kernel) serves every bag
+ * size.  Device pointers: queued on the context's stream.  Host pointers: the job is cut into chunks at site boundaries;
+ * each chunk is uploaded, encoded and copied back in order on the context's stream (plain copies, not the pinned ring of
+ * m6a_encode_reads: 128 bytes per read come back); the call returns when repr is complete. */
+int m6a_read_representation(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, const int64_t *off,
+                            int64_t n_sites, float *repr, float *read_prob);
 
 /* Site pooling.  Replaces calculate_site_proba(read_probs, n_iters, n_samples, n_processes) +
  * the mod_ratio line (m6anet/utils/inference_utils.py:53-54,74-104) for ALL flush groups of a

@@ -135,6 +135,8 @@ def maybe_start(argv):
             return
         if _values(argv[1:], "--loader") == ["device"]:      # refused with --gpus N (inference.check_loader): no rank is started
             return
+        if any(len(a) > 7 and "--read_representation".startswith(a.split("=")[0]) for a in argv[1:]):
+            return                                           # refused with --gpus N too (inference.check_read_representation)
         g = _values(argv[1:], "--gpus")
         if not g or len(g) != 1 or int(g[0]) < 2 or int(g[0]) > 64:
             return

@@ -37,6 +37,7 @@ DEFAULT_PRETRAINED_MODEL = "HCT116_RNA002"
 # the reference only accepts these three on the command line (constants.py:8, inference.py:77-78)
 DEFAULT_PRETRAINED_MODELS = ["HCT116_RNA002", "arabidopsis_RNA002", "HEK293T_RNA004"]
 
+N_REPR = 32              # floats of the read representation: the width of the encoder's second layer (include/m6a.h: M6A_N_REPR)
 N_WEIGHT_FLOATS = 7997   # E 66x2, W1 150x15, b1, gamma, beta, mu, var (150 each), W2 32x150, b2 32, W3 32, b3
 
 

@@ -709,6 +709,31 @@ int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *
     return M6A_OK;
 }
 
+// enc_repr_kernel on device pointers: always the reference's arithmetic behind the per-lane walk (every bag size), whatever
+// encoder variant the context has selected.  rp may be null.
+int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *repr, float *rp)
+{
+    if (R <= 0 || S <= 0) return M6A_OK;
+    EncReprArgs ra;
+    EncArgs &a = ra.enc;
+    a.X = X; a.site_kmers = km; a.off = off; a.wfrag = c->d_wfrag; a.emb = c->d_emb; a.read_prob = rp;
+    a.wfrag2 = c->d_wfrag2; a.w1e_tab = c->d_w1e; a.bn = c->d_w1e + M6A_W1E_FLOATS; a.err = c->d_err;
+    a.n_sites = S; a.n_reads = R; a.n_tiles = (R + 31) / 32; a.b3 = c->b3;
+    a.clk = nullptr;
+    ra.repr = repr;
+    const int64_t max_waves = (int64_t)c->n_cu * 8;        // 2 blocks/CU x 4 waves, as launch_encode
+    a.tiles_per_wave = (a.n_tiles + max_waves - 1) / max_waves;
+    const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    c->enc_variant_used = "general16";
+    c->enc_kernel_used = "enc_repr_kernel";
+    prof_begin(c, 0);
+    hipLaunchKernelGGL(enc_repr_kernel, dim3(blocks), dim3(256), 0, c->stream, ra);
+    prof_end(c, 0);
+    HIPCHK(c, hipGetLastError());
+    return M6A_OK;
+}
+
 RtabUse rtab_use(m6a_ctx *c, int64_t nmax, uint32_t si_base = 0, uint32_t si_count = 0)
 {
     RtabUse u;
@@ -1252,7 +1277,7 @@ void m6a_destroy(m6a_ctx *c)
     for (void *p : c->graveyard) (void)hipFree(p);
     if (c->rt.C) (void)hipFree(c->rt.C);
     if (c->rt.RS) (void)hipFree(c->rt.RS);
-    for (DevBuf *b : {&c->ctl_dev, &c->rt_rank, &c->rt_order, &c->sOffChunk, &c->jX, &c->jP, &c->jOff, &c->gSite, &c->gMod, &c->gP, &c->mt_scratch, &c->sSigma}) b->release();
+    for (DevBuf *b : {&c->ctl_dev, &c->rt_rank, &c->rt_order, &c->sOffChunk, &c->jX, &c->jP, &c->jOff, &c->gSite, &c->gMod, &c->gP, &c->mt_scratch, &c->sSigma, &c->sRepr}) b->release();
     for (auto e : c->job.ev_h2d) (void)hipEventDestroy(e);
     for (auto e : c->job.ev_enc) (void)hipEventDestroy(e);
     release_staging(c);
@@ -1384,6 +1409,69 @@ int m6a_encode_reads(m6a_ctx *c, const float *X, const uint8_t *km, const int64_
     int rc = bag_stats(c, off, S);
     if (rc) return rc;
     return launch_encode(c, X, km, off, S, c->n_reads, rp);
+}
+
+int m6a_read_representation(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, float *repr, float *rp)
+{
+    settle(c);
+    HintScope hint_scope(c);
+    if (c && c->job.open) return job_busy(c);
+    if (!c) return M6A_EINVAL;
+    if (S < 0) return fail(c, M6A_EINVAL, "n_sites < 0");
+    if (!repr) return fail(c, M6A_EINVAL, "repr is NULL: m6a_encode_reads is the call without the representation");
+    if (S == 0) return M6A_OK;
+    if (!X || !km || !off) return fail(c, M6A_EINVAL, "null pointer argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev = is_device_ptr(X);
+    if (dev != is_device_ptr(km) || dev != is_device_ptr(off) || dev != is_device_ptr(repr) || (rp && dev != is_device_ptr(rp)))
+        return fail(c, M6A_EINVAL, "X, site_kmers, off, repr, read_prob must be all host or all device pointers");
+    if (dev) {
+        if ((uintptr_t)repr & 15) return fail(c, M6A_EINVAL, "repr must be 16-byte aligned in device memory");
+        int rc = bag_stats(c, off, S);
+        if (rc) return rc;
+        return launch_repr(c, X, km, off, S, c->n_reads, repr, rp);
+    }
+    // Host pointers: chunks cut at site boundaries -- upload the chunk's rows of X, launch, copy its representation (and
+    // probabilities) back, in order, all on the context's stream.  128 B per read come back for 36 B that went: the return
+    // copy is the whole cost, and the pinned ring of m6a_encode_reads (sized for 4 B per read) is left as it is.
+    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
+    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+    const int64_t R = off[S];
+    if (R == 0) return M6A_OK;
+    const int64_t chunk_reads = (int64_t)1 << 20;             // 128 MB of representation per chunk (a larger bag is its own chunk)
+    std::vector<int64_t> cs{0};
+    int64_t widest = 0;
+    while (cs.back() < S) {
+        const int64_t s0 = cs.back();
+        int64_t s1 = std::upper_bound(off + s0, off + S + 1, off[s0] + chunk_reads) - off - 1;
+        s1 = std::min<int64_t>(S, std::max<int64_t>(s1, s0 + 1));
+        widest = std::max(widest, off[s1] - off[s0]);
+        cs.push_back(s1);
+    }
+    const int64_t nchunk = (int64_t)cs.size() - 1;
+    HIPCHK(c, c->sX.ensure((size_t)widest * 9 * 4));
+    HIPCHK(c, c->sK.ensure((size_t)S * 3));
+    HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
+    HIPCHK(c, c->sOffChunk.ensure((size_t)(S + nchunk) * 8));
+    HIPCHK(c, c->sRepr.ensure((size_t)widest * M6A_N_REPR * 4));
+    if (rp) HIPCHK(c, c->sP.ensure((size_t)widest * 4));
+    HIPCHK(c, hipMemcpyAsync(c->sK.p, km, (size_t)S * 3, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    for (int64_t k = 0; k < nchunk; k++) {
+        const int64_t s0 = cs[k], s1 = cs[k + 1], r0 = off[s0], nr = off[s1] - r0;
+        if (nr == 0) continue;
+        HIPCHK(c, hipMemcpyAsync(c->sX.p, X + r0 * 9, (size_t)nr * 9 * 4, hipMemcpyHostToDevice, c->stream));
+        int64_t *d_off = (int64_t *)c->sOffChunk.p + s0 + k;   // the chunk's own CSR row, starting at 0
+        hipLaunchKernelGGL(rebase_off_kernel, dim3((unsigned)((s1 - s0 + 1 + 255) / 256)), dim3(256), 0, c->stream,
+                           (const int64_t *)c->sOff.p + s0, s1 - s0 + 1, d_off);
+        int rc = launch_repr(c, (const float *)c->sX.p, (const uint8_t *)c->sK.p + s0 * 3, d_off, s1 - s0, nr, (float *)c->sRepr.p,
+                             rp ? (float *)c->sP.p : nullptr);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(repr + r0 * M6A_N_REPR, c->sRepr.p, (size_t)nr * M6A_N_REPR * 4, hipMemcpyDeviceToHost, c->stream));
+        if (rp) HIPCHK(c, hipMemcpyAsync(rp + r0, c->sP.p, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));           // the chunk's buffers are reused by the next one
+    }
+    return sync_and_check(c);
 }
 
 int m6a_site_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr,

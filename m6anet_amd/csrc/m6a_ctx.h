@@ -277,6 +277,7 @@ struct m6a_ctx {
     int site_mode = M6A_SITE_SAMPLED;         // m6a_set_site_mode: what site_prob means in pool / infer / job_end
     std::atomic<bool> warm_cancel{false};     // the background set-up stops at its next step (the mode went to M6A_SITE_EXPECTED)
     DevBuf sSigma;                            // host-pointer m6a_site_expectation: mc_sigma [S]
+    DevBuf sRepr;                             // host-pointer m6a_read_representation: one chunk of repr [chunk reads][32]
 };
 
 namespace m6a_detail {
@@ -311,6 +312,7 @@ struct HintScope {
 };
 // m6a_api.hip
 int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *rp);
+int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *repr, float *rp);
 int launch_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr, uint32_t seed, int64_t bs, int64_t spb,
                 float *site, double *mod);
 int bag_stats(m6a_ctx *c, const int64_t *d_off, int64_t S);

@@ -61,6 +61,12 @@ struct EncArgs {
     unsigned long long *clk;      // clock stamps of a profiled launch, else null (m6a_clk_stamp)
 };
 
+// enc_repr_kernel: the encoder's arguments (read_prob may be null there) and where layer 2 after its ReLU goes
+struct EncReprArgs {
+    EncArgs enc;
+    float *repr;                  // [R][32], 16-byte aligned
+};
+
 struct PoolArgs {
     const float *read_prob;       // [R]
     const int64_t *off;           // [S+1]
@@ -126,6 +132,7 @@ struct RtabUse {
 __global__ void enc_kernel(EncArgs a);
 __global__ void enc_site16_kernel(EncArgs a);
 __global__ void enc_csite_kernel(EncArgs a);
+__global__ void enc_repr_kernel(EncReprArgs ra);
 __global__ void pool_scan_start_kernel(PoolArgs a);
 template <int KT> __global__ void pool_scan_group_kernel(PoolArgs a);
 template <int KT> __global__ void pool_scan_site_kernel(PoolArgs a);

@@ -6,6 +6,7 @@
 //                      half-0 operand first), every sum through layer 2 in the order the reference's float32 arithmetic
 //                      runs it -- enc_kernel all the way to the probability (the reference's bits); the csite variant
 //                      folds the per-site constants (12 K-slots, bags >= 16 reads) and keeps a plain 32 -> 1 sum.
+//   enc_repr_kernel    enc_kernel that also stores layer 2 after its ReLU: the read representation, [R][32] (m6a_read_representation)
 //   pool_scan_start_kernel + pool_scan_site_kernel, pool_scan_group_kernel
 //                      site pooling, exact NumPy-stream replay, any bag sizes: a counting pass per
 //                      flush group finds where each site starts in the shared MT19937 word stream
@@ -1580,6 +1581,177 @@ __global__ __launch_bounds__(256) void bag_verify_kernel(const unsigned long lon
     if (threadIdx.x == 0) {
         for (int i = 1; i < 256; i++) h += s_part[i];
         if (got[0] != mn || got[1] != mx || got[2] != reads || h != hash) atomicExch(err, 3);
+    }
+}
+
+// =====================================================================================
+// Read representation: enc_kernel that also stores layer 2 after its ReLU, the 32 floats per read the reference's
+// MILModel.get_read_representation returns (m6anet/model/model.py:85-97).
+//
+// Every float32 operation up to the probability is enc_kernel's (same fragments, same K-slot wiring, layer2_with_bn, the
+// per-lane walk of off[] that takes every bag size, the same epilogue); the body below is enc_kernel's, line for line, so
+// that the shipped kernels stay as they are.  What is new sits between the tile body and the epilogue: the store.
+//
+// Where the 32 outputs of a read are: register q of lane half 0 holds output unit 2q + 1, register q of half 1 unit 2q + 2,
+// and register 15 of half 1 unit 0 (m6a_api.hip build_fragments out_unit: the wiring gemv32_as_mkl wants).  The two lanes
+// of a read (lane, lane ^ 32) swap eight values -- half 0 gives away units 17, 19, .., 31 (registers 8..15) and gets units
+// 0, 2, .., 14; half 1 gives away register 15 and registers 0..6 -- after which half 0 holds units 0..15 and half 1 units
+// 16..31 in order: four 16-byte stores per lane, 64 contiguous bytes, repr[r][16 half .. 16 half + 16).  The exchange is
+// executed by all lanes; only the stores are guarded (the last tile is partial, its spare lanes compute on a clamped read).
+// relu is the oracle's a < 0 ? 0 : a on the accumulator itself (keeps NaN, as torch's does), not relu2's doubled value.
+// read_prob may be null: the epilogue is then skipped (wave-uniform).
+// =====================================================================================
+__global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
+{
+    const EncArgs a = ra.enc;
+    clamp_keeps_nan();
+    __shared__ float s_emb[132];
+    __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
+    for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
+    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int col = lane & 31;
+    const int half = lane >> 5;
+    const float *bn_half = s_bn + half * 32;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t tile0 = wave * a.tiles_per_wave;
+    if (tile0 >= a.n_tiles) return;
+    const int64_t tile1 = (tile0 + a.tiles_per_wave < a.n_tiles) ? tile0 + a.tiles_per_wave : a.n_tiles;
+
+    float w1[40], w2[80], w3[16];
+#pragma unroll
+    for (int i = 0; i < 40; i++) w1[i] = a.wfrag[i * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < 80; i++) w2[i] = a.wfrag[(40 + i) * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < 16; i++) w3[i] = a.wfrag[(120 + i) * 64 + lane];
+
+    int64_t s_base;
+    {
+        const int64_t r = tile0 * 32;
+        int64_t lo = 0, hi = a.n_sites;          // invariant: off[lo] <= r < off[hi]
+        while (hi - lo > 1) {
+            int64_t mid = (lo + hi) >> 1;
+            if (a.off[mid] <= r) lo = mid; else hi = mid;
+        }
+        s_base = lo;
+    }
+    const int64_t last_site = a.n_sites - 1;
+
+    // the three links of the input chain, as in enc_kernel
+    auto link0 = [&](int64_t base, int64_t (&o)[3]) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int64_t si = base + 1 + i;
+            o[i] = a.off[si <= a.n_sites ? si : a.n_sites];
+        }
+    };
+    auto link1 = [&](int64_t tile, int64_t base, const int64_t (&o)[3], int64_t &s, int (&km)[3], float (&x)[8]) {
+        const int64_t r = tile * 32 + col;
+        const int64_t rc = r < a.n_reads ? r : a.n_reads - 1;
+        s = base + (rc >= o[0] ? 1 : 0) + (rc >= o[1] ? 1 : 0);
+        if (__any(rc >= o[2])) {                 // bags smaller than 16 reads: walk
+            s = base;
+            while (a.off[s + 1] <= rc) ++s;
+        }
+        s = s < last_site ? s : last_site;
+        const uint8_t *kp = a.site_kmers + s * 3;
+        km[0] = kp[0]; km[1] = kp[1]; km[2] = kp[2];
+        const float *xp = a.X + rc * 9 + half;
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
+        x[4] = xp[half ? 6 : 8];
+    };
+    auto link2 = [&](const int (&km)[3], float (&x)[8]) {
+        const float e0 = s_emb[2 * km[0] + 1 - half], e1 = s_emb[2 * km[1] + 1 - half], e2 = s_emb[2 * km[2] + 1 - half];
+        x[4] = half ? e0 : x[4];
+        x[5] = half ? e1 : e0;
+        x[6] = half ? e2 : e1;
+        x[7] = half ? 1.0f : e2;
+    };
+
+    float f[8];
+    s_base = uniform_i64(s_base);
+    {
+        int64_t o[3], s;
+        int km[3];
+        link0(s_base, o);
+        link1(tile0, s_base, o, s, km, f);
+        link2(km, f);
+        s_base = uniform_i64(__shfl(s, 31, 64));
+    }
+
+    BnPairs bnq;
+    bn_pairs_load(bnq, bn_half);
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const int64_t tn = tile + 1 < tile1 ? tile + 1 : tile;
+        float fn[8];
+        int64_t o[3], sn;
+        int km[3];
+        link0(s_base, o);
+        tile_body_priority();
+
+        f32x16 acc2, h1a, h1b;
+#pragma unroll
+        for (int q = 0; q < 16; q++) { acc2[q] = 0.0f; h1a[q] = 0.0f; }
+#pragma unroll
+        for (int st = 0; st < 8; st++)
+            h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < 5; m++) {
+            f32x16 &cur = (m & 1) ? h1b : h1a;
+            f32x16 &nxt = (m & 1) ? h1a : h1b;
+            if (m < 4) {
+#pragma unroll
+                for (int q = 0; q < 16; q++) nxt[q] = 0.0f;
+#pragma unroll
+                for (int st = 0; st < 8; st++)
+                    nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(m + 1) * 8 + st], f[st], nxt, 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (m == 0) link1(tn, s_base, o, sn, km, fn);
+            if (m == 2) link2(km, fn);
+            if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
+            if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
+            if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
+            if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
+            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
+        }
+        tile_epilogue_priority();
+        const int64_t r = tile * 32 + col;
+        {
+            float h[16], got[8];
+#pragma unroll
+            for (int q = 0; q < 16; q++) h[q] = acc2[q] < 0.0f ? 0.0f : acc2[q];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                float give = half ? h[(i + 15) & 15] : h[8 + i];
+                got[i] = __shfl_xor(give, 32, 64);                    // all lanes: the guard is on the stores
+            }
+            float4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                v[j].x = half ? h[7 + 2 * j] : got[2 * j];
+                v[j].y = half ? got[2 * j] : h[2 * j];
+                v[j].z = half ? h[8 + 2 * j] : got[2 * j + 1];
+                v[j].w = half ? got[2 * j + 1] : h[2 * j + 1];
+            }
+            if (r < a.n_reads) {
+                float4 *dst = (float4 *)(ra.repr + r * 32 + half * 16);
+#pragma unroll
+                for (int j = 0; j < 4; j++) dst[j] = v[j];
+            }
+        }
+        if (a.read_prob) {                                            // kernel argument: wave-uniform
+            const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;
+            const float p = 1.0f / (1.0f + sleef_expf_u10(-z));
+            if (half == 0 && r < a.n_reads) a.read_prob[r] = p;
+        }
+        if (tn != tile) s_base = uniform_i64(__shfl(sn, 31, 64));
+#pragma unroll
+        for (int i = 0; i < 8; i++) f[i] = fn[i];
     }
 }
 

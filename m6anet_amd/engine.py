@@ -4,6 +4,8 @@ the C ABI (include/m6a.h).  Names follow the reference:
   M6ANetEngine.get_read_probability(X, site_kmers, off)
       == model.get_read_representation({'X','kmer'}) + model.pooling_filter.probability_layer(.)
          (m6anet/utils/inference_utils.py:35-37)
+  M6ANetEngine.get_read_representation(X, site_kmers, off)
+      == model.get_read_representation({'X','kmer'}) itself: float32 [R, 32] (m6anet/model/model.py:85-97)
   M6ANetEngine.calculate_site_proba(read_probs, off, n_iters, n_samples, ...)
       == calculate_site_proba(read_probs, n_iters, n_samples, n_processes=1) + mod_ratio
          (m6anet/utils/inference_utils.py:53-54,90-104)
@@ -19,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .constants import (DEFAULT_PRETRAINED_MODEL, DEFAULT_READ_THRESHOLD, N_SAMPLES, N_WEIGHT_FLOATS,
+from .constants import (DEFAULT_PRETRAINED_MODEL, DEFAULT_READ_THRESHOLD, N_REPR, N_SAMPLES, N_WEIGHT_FLOATS,
                         PRETRAINED_CONFIGS, asset_path)
 
 
@@ -210,7 +212,7 @@ class M6ANetEngine:
 
     @property
     def last_encoder_kernel(self):
-        """Name of the __global__ function the last encode launched (enc_kernel | enc_site16_kernel | enc_csite_kernel)."""
+        """Name of the __global__ function the last encode launched (enc_kernel | enc_site16_kernel | enc_csite_kernel | enc_repr_kernel)."""
         return self._L.m6a_last_encoder_kernel(self._h).decode()
 
     def set_scan_driver(self, mode):
@@ -339,6 +341,33 @@ class M6ANetEngine:
             raise ValueError("read_prob must have one float per read")
         self._chk(self._L.m6a_encode_reads(self._h, aX.ptr, aK.ptr, aO.ptr, S, aP.ptr))
         return rp
+
+    def get_read_representation(self, X, site_kmers, off, out=None, want_read_probs=False):
+        """MILModel.get_read_representation (m6anet/model/model.py:85-97): layer 2 after its ReLU, float32 [R, 32], the
+        reference's bits whatever encoder variant is selected (include/m6a.h: m6a_read_representation).  `out` = a
+        preallocated [R, 32] array or tensor, or the pair (repr, read_prob).  Returns repr, or
+        (repr, read_prob [R]) with want_read_probs."""
+        aX, aK, aO = _Arg(X, np.float32, "float32"), _Arg(site_kmers, np.uint8, "uint8"), _Arg(off, np.int64, "int64")
+        S = aO.size - 1
+        R = aX.size // 9
+        if aK.size != 3 * S:
+            raise ValueError("site_kmers must be [n_sites, 3]")
+        rep, rp = out if isinstance(out, (tuple, list)) else (out, None)
+        if rep is None:
+            rep = self._out(aX.is_dev, R * N_REPR, np.float32, "float32").reshape(R, N_REPR)
+        if want_read_probs and rp is None:
+            rp = self._out(aX.is_dev, R, np.float32, "float32")
+        for o in (rep, rp):                                  # an output the binding would have to copy is an error, not a copy
+            if o is not None and not _is_torch(o) and not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous):
+                raise TypeError("out must be C-contiguous float32")
+        aH = _Arg(rep, np.float32, "float32")
+        aP = _Arg(rp, np.float32, "float32") if rp is not None else None
+        if aH.size != R * N_REPR:
+            raise ValueError("repr must be [n_reads, %d]" % N_REPR)
+        if aP is not None and aP.size != R:
+            raise ValueError("read_prob must have one float per read")
+        self._chk(self._L.m6a_read_representation(self._h, aX.ptr, aK.ptr, aO.ptr, S, aH.ptr, aP.ptr if aP else None))
+        return (rep, rp) if want_read_probs else rep
 
     def calculate_site_proba(self, read_probs, off, n_iters, n_samples=N_SAMPLES,
                              read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16,

@@ -6,7 +6,7 @@ import warnings
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from ..constants import (DEFAULT_MIN_READS, DEFAULT_PRETRAINED_MODEL, DEFAULT_PRETRAINED_MODELS,
-                         DEFAULT_READ_THRESHOLD, N_WEIGHT_FLOATS, PRETRAINED_CONFIGS)
+                         DEFAULT_READ_THRESHOLD, N_REPR, N_WEIGHT_FLOATS, PRETRAINED_CONFIGS)
 from ..data_utils import STORE_SUFFIX, load_sites, load_sites_native, open_store
 from ..engine import M6ANetEngine, load_weights, weights_from_state_dict
 from ..inference_utils import INDIV_HEADER, SITE_HEADER, run_inference
@@ -56,6 +56,10 @@ def argparser():
     return parser
 
 
+REPR_FILE = "data.read_representation.npy"
+REPR_PIECE_READS = 1 << 20                            # rows per engine call and per write: 128 MB of representation at a time
+
+
 def cli_parser():
     """argparser() -- the flags `eventalign_inference` and the ranks of --gpus N copy from -- and the flag that is this command's own"""
     parser = argparser()
@@ -83,8 +87,20 @@ def add_site_proba(parser):
 
 
 def command_parser():
-    """cli_parser() and --site_proba: the parser of the `inference` command"""
+    """cli_parser() and --site_proba: what `inference` shares with the ranks of --gpus N"""
     return add_site_proba(cli_parser())
+
+
+def full_parser():
+    """command_parser() and --read_representation, which no rank ever sees: the parser of the `inference` command"""
+    parser = command_parser()
+    parser.add_argument("--read_representation", action="store_true",
+                        help="also write OUT_DIR/%s: float32 [n_reads][32], the read encoder's output -- layer 2 after its ReLU, "
+                             "what the reference's MILModel.get_read_representation returns, bit for bit -- one row per data row of "
+                             "data.indiv_proba.csv, in its order (np.load(..., mmap_mode='r') reads it without loading it: 128 bytes per "
+                             "read).  Both CSVs are the bytes of a run without the flag.  One GPU, host loader: an argument error with "
+                             "--gpus N > 1 or --loader device." % REPR_FILE)
+    return parser
 
 
 def check_loader(args):
@@ -102,6 +118,51 @@ def check_loader(args):
     if why:
         print("m6anet_amd inference: error: %s" % why, file=sys.stderr)
         raise SystemExit(2)
+
+
+def check_read_representation(args):
+    """--read_representation: what it refuses, as an argument error before any rank is launched, any file is written or a GPU is touched"""
+    if not getattr(args, "read_representation", False):
+        return
+    import sys
+    why = None
+    if args.gpus > 1 or "M6A_RANK" in os.environ:
+        why = "--read_representation writes one file from one GPU (--gpus %d given)" % args.gpus
+    elif getattr(args, "loader", "host") == "device":
+        why = "--read_representation takes the host loader's arrays (--loader device given)"
+    if why:
+        print("m6anet_amd inference: error: %s" % why, file=sys.stderr)
+        raise SystemExit(2)
+
+
+def write_read_representation(engine, batch, args):
+    """OUT_DIR/data.read_representation.npy, row i = data row i of data.indiv_proba.csv: pieces of whole sites go through
+    engine.get_read_representation into one reused buffer and from there into the memory-mapped file, so the process never holds
+    more than a piece of it."""
+    import numpy as np
+    n_sites = batch.n_sites
+    if getattr(args, "drop_unflushed_tail", False):
+        from ..engine import reference_written_sites
+        n_sites = reference_written_sites(batch.n_sites, args.batch_size, args.save_per_batch)
+    off = np.ascontiguousarray(batch.off, np.int64)
+    n_rows = int(off[n_sites])
+    if n_rows == 0:                                       # an empty file cannot be mapped
+        np.save(os.path.join(args.out_dir, REPR_FILE), np.empty((0, N_REPR), np.float32))
+        return
+    out = np.lib.format.open_memmap(os.path.join(args.out_dir, REPR_FILE), mode="w+", dtype=np.float32, shape=(n_rows, N_REPR))
+    widest = int(np.diff(off[:n_sites + 1]).max(initial=0))      # a bag larger than a piece is a piece of its own
+    piece = np.empty((min(max(widest, REPR_PIECE_READS), n_rows), N_REPR), np.float32)
+    s0 = 0
+    while s0 < n_sites:
+        s1 = int(np.searchsorted(off, off[s0] + REPR_PIECE_READS, side="right")) - 1
+        s1 = min(n_sites, max(s1, s0 + 1))
+        r0, r1 = int(off[s0]), int(off[s1])
+        if r1 > r0:
+            engine.get_read_representation(batch.X[r0:r1], batch.site_kmers[s0:s1], off[s0:s1 + 1] - r0, out=piece[:r1 - r0])
+            out[r0:r1] = piece[:r1 - r0]
+        s0 = s1
+    out.flush()
+    del out
 
 
 def load_on_device(args):
@@ -205,6 +266,7 @@ def resolve_model(args):
 
 def main(args):
     check_loader(args)
+    check_read_representation(args)
     weights = resolve_model(args)
     if args.gpus < 1:
         raise ValueError("--gpus must be >= 1")
@@ -274,4 +336,6 @@ def main(args):
         raise made["error"]
     engine = made["engine"]
     run_inference(engine, batch, args)
+    if getattr(args, "read_representation", False):
+        write_read_representation(engine, batch, args)
     engine.close()

@@ -140,6 +140,23 @@ int m6a_encode_reads(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, co
 int m6a_read_representation(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, const int64_t *off,
                             int64_t n_sites, float *repr, float *read_prob);
 
+/* m6a_read_representation with an output type.
+ *   dtype      M6A_REPR_F32: repr is [R][M6A_N_REPR] float32 and the call is m6a_read_representation, bit for bit.
+ *              M6A_REPR_F16: repr is [R][M6A_N_REPR] IEEE binary16, unit o of read r at ((uint16_t *)repr)[r * 32 + o]: the float32
+ *              value the other form stores, converted once with round-to-nearest-even -- np.float32(v).astype(np.float16)
+ *              exactly: NaN stays NaN, what rounds above 65504 is +inf, results in the binary16 subnormal range (below 2^-14)
+ *              are produced, not flushed, and a value at or below 2^-25 is 0.  The kernel (enc_repr_kernel<true>) converts in
+ *              registers and stores 32 contiguous bytes per lane; the float32 array is never written.
+ *              Any other value is M6A_EINVAL and nothing is launched.
+ *   repr       a device pointer must be 16-byte aligned (either type); host pointers go through m6a_read_representation's
+ *              chunk loop, and 64 bytes per read come back with M6A_REPR_F16
+ *   read_prob  unchanged by dtype: float32 [R] or NULL
+ * Every other argument, check and error is m6a_read_representation's. */
+#define M6A_REPR_F32 0
+#define M6A_REPR_F16 1
+int m6a_read_representation_dtype(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, const int64_t *off,
+                                  int64_t n_sites, void *repr, int dtype, float *read_prob);
+
 /* Site pooling.  Replaces calculate_site_proba(read_probs, n_iters, n_samples, n_processes) +
  * the mod_ratio line (m6anet/utils/inference_utils.py:53-54,74-104) for ALL flush groups of a
  * job at once, with the reference's n_processes=1 semantics: the NumPy MT19937 stream restarts
@@ -852,6 +869,43 @@ int m6a_prep_sites_write_csv_bgzf(m6a_prep_sites *p, const char *out_dir, int wr
  * n_by_type (may be NULL): the blocks written, header blocks included, by BTYPE 0, 1, 2. */
 int m6a_prep_sites_write_csv_bgzf_level(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
                                         int level, m6a_csv_bgzf_stats *stats, int64_t n_by_type[3]);
+
+/* `eventalign_inference --read_representation`: data.read_representation.npy written from the handle's device arrays -- X,
+ * site_kmers and off never leave the device, and the process never holds more of the array than two rounds of it.
+ *
+ * The file is NumPy's .npy version 1.0 of a C-ordered [n_rows][32] array, n_rows = off[n], n = n_sites_limit (< 0: every site;
+ * larger than the handle's count: every site), dtype '<f4' (M6A_REPR_F32) or '<f2' (M6A_REPR_F16).  Its header is byte for byte what
+ * np.lib.format.open_memmap(path, mode="w+", dtype=np.float32 | np.float16, shape=(n_rows, 32)) writes (NumPy 1.24 and later):
+ *     0x93 'N' 'U' 'M' 'P' 'Y' 0x01 0x00, then 0x76 0x00 (the little-endian length, 118, of what follows),
+ *     {'descr': '<f4', 'fortran_order': False, 'shape': (<n_rows>, 32), }       ('<f2' for binary16)
+ *     21 - (decimal digits of n_rows) spaces, which make dictionary and spaces 80 bytes at every n_rows,
+ *     37 spaces and '\n'
+ * -- 128 bytes, whatever n_rows is; tests/repr_file_statement.py states them in Python.  Row i follows at byte 128 + i * 32 *
+ * itemsize and is what m6a_read_representation_dtype gives for read i: the row of data row i of data.indiv_proba.csv.
+ *
+ * Rounds of whole sites: a round takes as many sites as together have at most max(1, M6A_REPR_ROUND_KB * 1024 / (32 * itemsize))
+ * rows (default 131072 KB), and at least one, so a site with more rows is a round of its own.  Two device buffers and two pinned
+ * buffers of the largest round are allocated before the first round and none after it.  Round k's kernel runs on ctx's stream
+ * straight from the handle's arrays; its device-to-host copy runs on a second stream behind an event; its pwrite() runs on the
+ * host at the round's offset.  Round k + 1 is queued before round k's copy is waited for, so that copy runs under round k + 1's
+ * kernel and round k - 1's pwrite().  The file is opened with O_TRUNC and sized once, before the first round.
+ *
+ * The four buffers count against the budget of the m6a_prep_* family (free device memory less a margin, or M6A_PREP_BUDGET_MB):
+ * over it is M6A_ENOMEM with a text that names a smaller M6A_REPR_ROUND_KB.  The handle's d2h_bytes grows by the bytes copied
+ * (n_rows * 32 * itemsize, stats->d2h_bytes) and its peak_bytes rises to the handle's arrays plus the buffers if that is higher.
+ * M6A_EINVAL: p, ctx or path NULL; ctx on another device than p; a dtype that is neither constant; a handle with no site.
+ * M6A_EIO with the path: the file cannot be opened, sized, written or closed.  A call that fails leaves no file at path.  Text in
+ * m6a_prep_last_error().  ctx must be idle (no open job) and is left with nothing queued.  stats (may be NULL) is filled on every
+ * return: the kernel and copy times are summed over the rounds from events, so with overlap they need not add up to the call. */
+typedef struct m6a_repr_write_stats {
+    double ms_kernel, ms_copy, ms_write;    /* the rounds' kernels; their device -> pinned copies; their pwrite()s */
+    int64_t n_rounds, n_rows;
+    int64_t bytes;                          /* the file: header and rows */
+    int64_t round_bytes;                    /* each of the buffers: the largest round */
+    int64_t d2h_bytes;
+} m6a_repr_write_stats;
+int m6a_prep_sites_write_read_representation(m6a_prep_sites *p, m6a_ctx *ctx, const char *path, int dtype, int64_t n_sites_limit,
+                                             m6a_repr_write_stats *stats);
 
 /* `train`: fitting the m6anet.toml model (m6anet/scripts/train.py -> train_one_epoch, m6anet/utils/training_utils.py; the model of
  * m6anet/model/configs/model_configs/m6anet.toml, which has no dropout, so a step is a deterministic function of its batch).  The

@@ -137,6 +137,8 @@ def maybe_start(argv):
             return
         if any(len(a) > 7 and "--read_representation".startswith(a.split("=")[0]) for a in argv[1:]):
             return                                           # refused with --gpus N too (inference.check_read_representation)
+        if any(len(a) > 4 and "--representation_dtype".startswith(a.split("=")[0]) for a in argv[1:]):
+            return                                           # needs --read_representation: refused above with it, an argument error without
         g = _values(argv[1:], "--gpus")
         if not g or len(g) != 1 or int(g[0]) < 2 or int(g[0]) > 64:
             return

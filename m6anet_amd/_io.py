@@ -511,6 +511,24 @@ class prep_sites:
             raise M6AIOError("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
         return stats
 
+    def write_read_representation(self, engine, path, dtype="float32", n_sites=None):
+        """m6a_prep_sites_write_read_representation: the .npy file `path`, [off[n_sites]][32] float32 or float16 ("float32" |
+        "float16", or M6A_REPR_F32 | M6A_REPR_F16), the rows of the first n_sites sites (None: all), computed by `engine` (an
+        M6ANetEngine on the handle's device) from the handle's device arrays in rounds of M6A_REPR_ROUND_KB and pwritten from
+        pinned buffers.  Returns the m6a_repr_write_stats as a dict.  A call that raises leaves no file."""
+        from . import _lib
+        st = _lib.ReprWriteStats()
+        code = _lib.REPR_DTYPES.get(dtype, dtype) if isinstance(dtype, str) else dtype
+        if isinstance(code, str):
+            raise ValueError("dtype must be 'float32' or 'float16', not %r" % (dtype,))
+        rc = self._L.m6a_prep_sites_write_read_representation(self._h, getattr(engine, "_h", engine), None if path is None else os.fsencode(path),
+                                                              int(code), -1 if n_sites is None else int(n_sites), C.byref(st))
+        if self.info is not None:
+            self.peak_bytes = int(self.info.peak_bytes)
+        if rc != 0:
+            raise M6AIOError("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.m6a_prep_sites_free(self._h)

@@ -11,16 +11,17 @@ ERRORS = {-1: "M6A_EINVAL", -2: "M6A_ENOMEM", -3: "M6A_EHIP", -4: "M6A_ESTREAM",
           -6: "M6A_EUNSUPPORTED", -7: "M6A_EFORMAT", -8: "M6A_EIO", -9: "M6A_EDECLINED"}
 M6A_EDECLINED = -9
 RNG_NUMPY = 0
+REPR_DTYPES = {"float32": 0, "float16": 1}           # M6A_REPR_F32, M6A_REPR_F16
 
 # every symbol include/m6a.h declares (tests check the .so exports exactly these)
 SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a_set_job_offset", "m6a_set_scan_driver", "m6a_set_table_variant", "m6a_set_encoder_variant", "m6a_last_encoder_variant", "m6a_last_encoder_kernel", "m6a_sync", "m6a_set_host_offsets", "m6a_prepare_host_io", "m6a_host_alloc", "m6a_host_free", "m6a_host_is_pinned",
-           "m6a_encode_reads", "m6a_read_representation", "m6a_site_pool", "m6a_site_expectation", "m6a_set_site_mode", "m6a_infer", "m6a_job_begin", "m6a_job_feed", "m6a_job_feed_collated", "m6a_job_size", "m6a_job_end", "m6a_job_abort", "m6a_bag_forward", "m6a_validate_pool", "m6a_validate", "m6a_flush_groups",
+           "m6a_encode_reads", "m6a_read_representation", "m6a_read_representation_dtype", "m6a_site_pool", "m6a_site_expectation", "m6a_set_site_mode", "m6a_infer", "m6a_job_begin", "m6a_job_feed", "m6a_job_feed_collated", "m6a_job_size", "m6a_job_end", "m6a_job_abort", "m6a_bag_forward", "m6a_validate_pool", "m6a_validate", "m6a_flush_groups",
            "m6a_reference_written_sites",
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
-           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_json_sites_build", "m6a_norm_factors_build", "m6a_repr_format", "m6a_prep_dataprep_write",
+           "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_prep_sites_write_read_representation", "m6a_json_sites_build", "m6a_norm_factors_build", "m6a_repr_format", "m6a_prep_dataprep_write",
            "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats",
            "m6a_train_set_clip", "m6a_train_last_norm", "m6a_train_state_get", "m6a_train_state_set"]
 
@@ -90,6 +91,12 @@ class CsvStats(C.Structure):
     """m6a_csv_stats (include/m6a.h)."""
     _fields_ = [("ms_format", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double), ("site_bytes", C.c_int64),
                 ("indiv_bytes", C.c_int64), ("n_declined", C.c_int64), ("d2h_bytes", C.c_int64), ("n_rounds", C.c_int64)]
+
+
+class ReprWriteStats(C.Structure):
+    """m6a_repr_write_stats (include/m6a.h)."""
+    _fields_ = [("ms_kernel", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double), ("n_rounds", C.c_int64), ("n_rows", C.c_int64),
+                ("bytes", C.c_int64), ("round_bytes", C.c_int64), ("d2h_bytes", C.c_int64)]
 
 
 class DataprepStats(C.Structure):
@@ -168,6 +175,7 @@ def load():
     L.m6a_last_encoder_kernel.restype = C.c_char_p
     L.m6a_encode_reads.argtypes = [vp, vp, vp, vp, i64, vp]
     L.m6a_read_representation.argtypes = [vp, vp, vp, vp, i64, vp, vp]
+    L.m6a_read_representation_dtype.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp]
     L.m6a_site_pool.argtypes = [vp, vp, vp, i64, i32, i32, f32, u32, i32, i64, i64, vp, vp]
     L.m6a_site_expectation.argtypes = [vp, vp, vp, i64, i32, f32, vp, vp, vp]
     L.m6a_set_site_mode.argtypes = [vp, i32]
@@ -239,6 +247,7 @@ def load():
     L.m6a_prep_sites_write_csv_bgzf.argtypes = [vp, C.c_char_p, i32, i64, i32, C.POINTER(CsvBgzfStats)]
     L.m6a_bgzf_deflate_level.argtypes = [i32, C.c_char_p, i64, i32, vp, i64, pl, C.POINTER(DeflateStats), pl]
     L.m6a_prep_sites_write_csv_bgzf_level.argtypes = [vp, C.c_char_p, i32, i64, i32, i32, C.POINTER(CsvBgzfStats), pl]
+    L.m6a_prep_sites_write_read_representation.argtypes = [vp, vp, C.c_char_p, i32, i64, C.POINTER(ReprWriteStats)]
     L.m6a_repr_format.argtypes = [i32, vp, i64, i32, vp, i64, vp, pl]
     L.m6a_prep_dataprep_write.argtypes = [i32, C.c_char_p, C.c_char_p, i32, i32, i32, i32, C.POINTER(HostHalf), i32, C.POINTER(DataprepStats)]
     L.m6a_train_create.argtypes = [vp, vp, sz, C.POINTER(TrainConfig), C.POINTER(vp)]

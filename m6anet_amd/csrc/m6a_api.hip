@@ -710,8 +710,9 @@ int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *
 }
 
 // enc_repr_kernel on device pointers: always the reference's arithmetic behind the per-lane walk (every bag size), whatever
-// encoder variant the context has selected.  rp may be null.
-int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *repr, float *rp)
+// encoder variant the context has selected.  rp may be null.  dtype: M6A_REPR_F32 ([R][32] float32) or M6A_REPR_F16 ([R][32]
+// binary16, the float32 values rounded to nearest even by enc_repr_kernel<true>); the callers have checked it.
+int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, void *repr, int dtype, float *rp)
 {
     if (R <= 0 || S <= 0) return M6A_OK;
     EncReprArgs ra;
@@ -726,12 +727,40 @@ int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *of
     const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
     const unsigned blocks = (unsigned)((waves + 3) / 4);
     c->enc_variant_used = "general16";
-    c->enc_kernel_used = "enc_repr_kernel";
+    c->enc_kernel_used = dtype == M6A_REPR_F16 ? "enc_repr_kernel<true>" : "enc_repr_kernel";
     prof_begin(c, 0);
-    hipLaunchKernelGGL(enc_repr_kernel, dim3(blocks), dim3(256), 0, c->stream, ra);
+    if (dtype == M6A_REPR_F16)
+        hipLaunchKernelGGL(enc_repr_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, ra);
+    else
+        hipLaunchKernelGGL(enc_repr_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, ra);
     prof_end(c, 0);
     HIPCHK(c, hipGetLastError());
     return M6A_OK;
+}
+
+// The context's side of m6a_prep_sites_write_read_representation (m6a_npy_write.h, compiled into m6a_prep.hip, which does not see
+// m6a_ctx).  repr_writer_begin: the context is idle, lives on `device` and hands out its stream.  repr_writer_round: one round
+// of whole sites [s0, s1) -- reads [r0, r0 + nr) -- queued on the context's stream straight from the job's device arrays: the
+// round's own CSR row (off[s0..s1] - off[s0], into off_round [s1 - s0 + 1]) and enc_repr_kernel into repr.  Errors: the code,
+// with the text in m6a_last_error(c).
+int repr_writer_begin(m6a_ctx *c, int device, hipStream_t *stream)
+{
+    settle(c);
+    HintScope hint_scope(c);
+    if (c->job.open) return job_busy(c);
+    if (c->device != device) return fail(c, M6A_EINVAL, "the context is on device %d, the sites are on device %d", c->device, device);
+    HIPCHK(c, hipSetDevice(c->device));
+    *stream = c->stream;
+    return M6A_OK;
+}
+
+int repr_writer_round(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t *off_round, int64_t s0, int64_t s1,
+                      int64_t r0, int64_t nr, void *repr, int dtype)
+{
+    if (nr <= 0 || s1 <= s0) return M6A_OK;
+    hipLaunchKernelGGL(rebase_off_kernel, dim3((unsigned)((s1 - s0 + 1 + 255) / 256)), dim3(256), 0, c->stream, off + s0, s1 - s0 + 1, off_round);
+    HIPCHK(c, hipGetLastError());
+    return launch_repr(c, X + r0 * 9, km + s0 * 3, off_round, s1 - s0, nr, repr, dtype, nullptr);
 }
 
 RtabUse rtab_use(m6a_ctx *c, int64_t nmax, uint32_t si_base = 0, uint32_t si_count = 0)
@@ -1413,10 +1442,17 @@ int m6a_encode_reads(m6a_ctx *c, const float *X, const uint8_t *km, const int64_
 
 int m6a_read_representation(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, float *repr, float *rp)
 {
+    return m6a_read_representation_dtype(c, X, km, off, S, repr, M6A_REPR_F32, rp);
+}
+
+int m6a_read_representation_dtype(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, void *repr, int dtype, float *rp)
+{
     settle(c);
     HintScope hint_scope(c);
     if (c && c->job.open) return job_busy(c);
     if (!c) return M6A_EINVAL;
+    if (dtype != M6A_REPR_F32 && dtype != M6A_REPR_F16) return fail(c, M6A_EINVAL, "dtype %d is neither M6A_REPR_F32 nor M6A_REPR_F16", dtype);
+    const size_t row_bytes = dtype == M6A_REPR_F16 ? M6A_N_REPR * 2 : M6A_N_REPR * 4;
     if (S < 0) return fail(c, M6A_EINVAL, "n_sites < 0");
     if (!repr) return fail(c, M6A_EINVAL, "repr is NULL: m6a_encode_reads is the call without the representation");
     if (S == 0) return M6A_OK;
@@ -1429,10 +1465,10 @@ int m6a_read_representation(m6a_ctx *c, const float *X, const uint8_t *km, const
         if ((uintptr_t)repr & 15) return fail(c, M6A_EINVAL, "repr must be 16-byte aligned in device memory");
         int rc = bag_stats(c, off, S);
         if (rc) return rc;
-        return launch_repr(c, X, km, off, S, c->n_reads, repr, rp);
+        return launch_repr(c, X, km, off, S, c->n_reads, repr, dtype, rp);
     }
     // Host pointers: chunks cut at site boundaries -- upload the chunk's rows of X, launch, copy its representation (and
-    // probabilities) back, in order, all on the context's stream.  128 B per read come back for 36 B that went: the return
+    // probabilities) back, in order, all on the context's stream.  128 B per read (64 in binary16) come back for 36 B that went: the return
     // copy is the whole cost, and the pinned ring of m6a_encode_reads (sized for 4 B per read) is left as it is.
     if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
     for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
@@ -1453,7 +1489,7 @@ int m6a_read_representation(m6a_ctx *c, const float *X, const uint8_t *km, const
     HIPCHK(c, c->sK.ensure((size_t)S * 3));
     HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
     HIPCHK(c, c->sOffChunk.ensure((size_t)(S + nchunk) * 8));
-    HIPCHK(c, c->sRepr.ensure((size_t)widest * M6A_N_REPR * 4));
+    HIPCHK(c, c->sRepr.ensure((size_t)widest * row_bytes));
     if (rp) HIPCHK(c, c->sP.ensure((size_t)widest * 4));
     HIPCHK(c, hipMemcpyAsync(c->sK.p, km, (size_t)S * 3, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
@@ -1464,10 +1500,10 @@ int m6a_read_representation(m6a_ctx *c, const float *X, const uint8_t *km, const
         int64_t *d_off = (int64_t *)c->sOffChunk.p + s0 + k;   // the chunk's own CSR row, starting at 0
         hipLaunchKernelGGL(rebase_off_kernel, dim3((unsigned)((s1 - s0 + 1 + 255) / 256)), dim3(256), 0, c->stream,
                            (const int64_t *)c->sOff.p + s0, s1 - s0 + 1, d_off);
-        int rc = launch_repr(c, (const float *)c->sX.p, (const uint8_t *)c->sK.p + s0 * 3, d_off, s1 - s0, nr, (float *)c->sRepr.p,
+        int rc = launch_repr(c, (const float *)c->sX.p, (const uint8_t *)c->sK.p + s0 * 3, d_off, s1 - s0, nr, c->sRepr.p, dtype,
                              rp ? (float *)c->sP.p : nullptr);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(repr + r0 * M6A_N_REPR, c->sRepr.p, (size_t)nr * M6A_N_REPR * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync((char *)repr + (size_t)r0 * row_bytes, c->sRepr.p, (size_t)nr * row_bytes, hipMemcpyDeviceToHost, c->stream));
         if (rp) HIPCHK(c, hipMemcpyAsync(rp + r0, c->sP.p, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));           // the chunk's buffers are reused by the next one
     }

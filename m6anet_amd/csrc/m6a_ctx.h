@@ -312,7 +312,10 @@ struct HintScope {
 };
 // m6a_api.hip
 int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *rp);
-int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *repr, float *rp);
+int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, void *repr, int dtype, float *rp);
+int repr_writer_begin(m6a_ctx *c, int device, hipStream_t *stream);       // declared again in m6a_npy_write.h, which does not see this file
+int repr_writer_round(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t *off_round, int64_t s0, int64_t s1,
+                      int64_t r0, int64_t nr, void *repr, int dtype);
 int launch_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr, uint32_t seed, int64_t bs, int64_t spb,
                 float *site, double *mod);
 int bag_stats(m6a_ctx *c, const int64_t *d_off, int64_t S);

@@ -61,10 +61,10 @@ struct EncArgs {
     unsigned long long *clk;      // clock stamps of a profiled launch, else null (m6a_clk_stamp)
 };
 
-// enc_repr_kernel: the encoder's arguments (read_prob may be null there) and where layer 2 after its ReLU goes
+// enc_repr_kernel<F16>: the encoder's arguments (read_prob may be null there) and where layer 2 after its ReLU goes
 struct EncReprArgs {
     EncArgs enc;
-    float *repr;                  // [R][32], 16-byte aligned
+    void *repr;                   // [R][32] float32, or binary16 with F16; 16-byte aligned
 };
 
 struct PoolArgs {
@@ -132,7 +132,7 @@ struct RtabUse {
 __global__ void enc_kernel(EncArgs a);
 __global__ void enc_site16_kernel(EncArgs a);
 __global__ void enc_csite_kernel(EncArgs a);
-__global__ void enc_repr_kernel(EncReprArgs ra);
+template <bool F16> __global__ void enc_repr_kernel(EncReprArgs ra);     // F16: [R][32] binary16 instead of float32
 __global__ void pool_scan_start_kernel(PoolArgs a);
 template <int KT> __global__ void pool_scan_group_kernel(PoolArgs a);
 template <int KT> __global__ void pool_scan_site_kernel(PoolArgs a);

@@ -7,6 +7,7 @@
 //                      runs it -- enc_kernel all the way to the probability (the reference's bits); the csite variant
 //                      folds the per-site constants (12 K-slots, bags >= 16 reads) and keeps a plain 32 -> 1 sum.
 //   enc_repr_kernel    enc_kernel that also stores layer 2 after its ReLU: the read representation, [R][32] (m6a_read_representation)
+//   enc_repr_kernel<true>  the same with the 32 values stored as binary16 (m6a_read_representation_dtype, M6A_REPR_F16)
 //   pool_scan_start_kernel + pool_scan_site_kernel, pool_scan_group_kernel
 //                      site pooling, exact NumPy-stream replay, any bag sizes: a counting pass per
 //                      flush group finds where each site starts in the shared MT19937 word stream
@@ -1600,8 +1601,24 @@ __global__ __launch_bounds__(256) void bag_verify_kernel(const unsigned long lon
 // executed by all lanes; only the stores are guarded (the last tile is partial, its spare lanes compute on a clamped read).
 // relu is the oracle's a < 0 ? 0 : a on the accumulator itself (keeps NaN, as torch's does), not relu2's doubled value.
 // read_prob may be null: the epilogue is then skipped (wave-uniform).
+//
+// The kernel is a template over the output type with two instantiations.  enc_repr_kernel<false> (float32) is the kernel as it was:
+// the same arithmetic, the same four stores.  enc_repr_kernel<true> stores IEEE binary16: after the same swap the lane's 16 values
+// are converted, each from the float32 value the other kernel stores, and leave as 32 contiguous bytes, two guarded 16-byte
+// stores, repr[r][16 half .. 16 half + 16) of a [R][32] binary16 array.  The conversion is v_cvt_f16_f32 under the mode the
+// build gives every kernel here: round to nearest even, float_denorm_mode_32 = 3 and float_denorm_mode_16_64 = 3 (the kernel
+// descriptor's defaults; clamp_keeps_nan touches DX10_CLAMP alone), so a float32 subnormal is read as it is and a result in
+// the binary16 subnormal range is produced, not flushed; FP16_OVFL is clear, so what rounds above 65504 is +inf; a NaN stays
+// a NaN with the top bits of its payload.  That is np.float32(v).astype(np.float16) on every value this kernel can produce.
 // =====================================================================================
-__global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t f16_pair(float lo, float hi)
+{
+    const f32x2 v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+}
+template <bool F16> __global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
 {
     const EncArgs a = ra.enc;
     clamp_keeps_nan();
@@ -1738,8 +1755,22 @@ __global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
                 v[j].z = half ? h[8 + 2 * j] : got[2 * j + 1];
                 v[j].w = half ? got[2 * j + 1] : h[2 * j + 1];
             }
-            if (r < a.n_reads) {
-                float4 *dst = (float4 *)(ra.repr + r * 32 + half * 16);
+            if constexpr (F16) {
+                uint4 w[2];
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    w[j].x = f16_pair(v[2 * j].x, v[2 * j].y);
+                    w[j].y = f16_pair(v[2 * j].z, v[2 * j].w);
+                    w[j].z = f16_pair(v[2 * j + 1].x, v[2 * j + 1].y);
+                    w[j].w = f16_pair(v[2 * j + 1].z, v[2 * j + 1].w);
+                }
+                if (r < a.n_reads) {
+                    uint4 *dst = (uint4 *)((uint16_t *)ra.repr + r * 32 + half * 16);
+                    dst[0] = w[0];
+                    dst[1] = w[1];
+                }
+            } else if (r < a.n_reads) {
+                float4 *dst = (float4 *)((float *)ra.repr + r * 32 + half * 16);
 #pragma unroll
                 for (int j = 0; j < 4; j++) dst[j] = v[j];
             }
@@ -1754,6 +1785,9 @@ __global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
         for (int i = 0; i < 8; i++) f[i] = fn[i];
     }
 }
+
+template __global__ void enc_repr_kernel<false>(EncReprArgs ra);
+template __global__ void enc_repr_kernel<true>(EncReprArgs ra);
 
 // An empty kernel per translation unit: HIP maps a code object on the first launch of any kernel in it (0.3-1.2 ms, measured
 // in the first call's timeline, profiles/r03_first_call_timeline.txt); m6a_create's background set-up launches these instead.

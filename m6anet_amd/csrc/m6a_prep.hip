@@ -3317,6 +3317,7 @@ extern "C" void m6a_prep_sites_free(m6a_prep_sites *p) { delete p; }
 #define M6A_BGZF_DEVICE_PART
 #include "m6a_bgzf.h"
 #include "m6a_csv.h"
+#include "m6a_npy_write.h"
 #include "m6a_dataprep.h"
 #define M6A_DEFLATE_DEVICE_PART
 #include "m6a_deflate.h"

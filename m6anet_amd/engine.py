@@ -342,11 +342,16 @@ class M6ANetEngine:
         self._chk(self._L.m6a_encode_reads(self._h, aX.ptr, aK.ptr, aO.ptr, S, aP.ptr))
         return rp
 
-    def get_read_representation(self, X, site_kmers, off, out=None, want_read_probs=False):
+    def get_read_representation(self, X, site_kmers, off, out=None, want_read_probs=False, dtype="float32"):
         """MILModel.get_read_representation (m6anet/model/model.py:85-97): layer 2 after its ReLU, float32 [R, 32], the
         reference's bits whatever encoder variant is selected (include/m6a.h: m6a_read_representation).  `out` = a
         preallocated [R, 32] array or tensor, or the pair (repr, read_prob).  Returns repr, or
-        (repr, read_prob [R]) with want_read_probs."""
+        (repr, read_prob [R]) with want_read_probs.  dtype="float16" (m6a_read_representation_dtype, M6A_REPR_F16): repr is
+        np.float16 / torch.half, exactly the float32 result's .astype(np.float16), converted in the kernel; read_prob stays
+        float32."""
+        if dtype not in _lib.REPR_DTYPES:
+            raise ValueError("dtype must be 'float32' or 'float16', not %r" % (dtype,))
+        np_dt = np.float16 if dtype == "float16" else np.float32
         aX, aK, aO = _Arg(X, np.float32, "float32"), _Arg(site_kmers, np.uint8, "uint8"), _Arg(off, np.int64, "int64")
         S = aO.size - 1
         R = aX.size // 9
@@ -354,20 +359,32 @@ class M6ANetEngine:
             raise ValueError("site_kmers must be [n_sites, 3]")
         rep, rp = out if isinstance(out, (tuple, list)) else (out, None)
         if rep is None:
-            rep = self._out(aX.is_dev, R * N_REPR, np.float32, "float32").reshape(R, N_REPR)
+            rep = self._out(aX.is_dev, R * N_REPR, np_dt, dtype).reshape(R, N_REPR)
         if want_read_probs and rp is None:
             rp = self._out(aX.is_dev, R, np.float32, "float32")
-        for o in (rep, rp):                                  # an output the binding would have to copy is an error, not a copy
-            if o is not None and not _is_torch(o) and not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous):
-                raise TypeError("out must be C-contiguous float32")
-        aH = _Arg(rep, np.float32, "float32")
+        for o, dt, name in ((rep, np_dt, dtype), (rp, np.float32, "float32")):   # an output the binding would have to copy is an error, not a copy
+            if o is not None and not _is_torch(o) and not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous):
+                raise TypeError("out must be C-contiguous %s" % name)
+        aH = _Arg(rep, np_dt, dtype)
         aP = _Arg(rp, np.float32, "float32") if rp is not None else None
         if aH.size != R * N_REPR:
             raise ValueError("repr must be [n_reads, %d]" % N_REPR)
         if aP is not None and aP.size != R:
             raise ValueError("read_prob must have one float per read")
-        self._chk(self._L.m6a_read_representation(self._h, aX.ptr, aK.ptr, aO.ptr, S, aH.ptr, aP.ptr if aP else None))
+        if dtype == "float32":
+            self._chk(self._L.m6a_read_representation(self._h, aX.ptr, aK.ptr, aO.ptr, S, aH.ptr, aP.ptr if aP else None))
+        else:
+            self._chk(self._L.m6a_read_representation_dtype(self._h, aX.ptr, aK.ptr, aO.ptr, S, aH.ptr, _lib.REPR_DTYPES[dtype],
+                                                            aP.ptr if aP else None))
         return (rep, rp) if want_read_probs else rep
+
+    def read_representation_ptrs(self, X, site_kmers, off, n_sites, repr, dtype="float32", read_prob=None):
+        """m6a_read_representation_dtype on raw addresses (ints) the caller owns, as infer_ptrs is m6a_infer on them: all host or
+        all device; repr holds [R][32] of `dtype` ("float32" | "float16", or M6A_REPR_F32 | M6A_REPR_F16 -- any other number is
+        passed on and refused by the library), read_prob [R] float32 or None.  With device pointers the call is queued on the
+        context's stream: `sync()` before repr is read; `set_host_offsets` first spares the read-back of off."""
+        code = _lib.REPR_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+        self._chk(self._L.m6a_read_representation_dtype(self._h, X, site_kmers, off, int(n_sites), repr, code, read_prob))
 
     def calculate_site_proba(self, read_probs, off, n_iters, n_samples=N_SAMPLES,
                              read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16,

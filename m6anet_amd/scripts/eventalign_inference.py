@@ -83,6 +83,20 @@ def command_parser():
     return inference.add_site_proba(cli_parser())
 
 
+def full_parser():
+    """command_parser() and the two flags of the read representation: the parser of the `eventalign_inference` command"""
+    parser = command_parser()
+    parser.add_argument("--read_representation", action="store_true",
+                        help="also write OUT_DIR/%s: [n_reads][32], the read encoder's output -- layer 2 after its ReLU, what the "
+                             "reference's MILModel.get_read_representation returns, bit for bit -- one row per data row of "
+                             "data.indiv_proba.csv, in its order: the bytes `dataprep` and `inference --read_representation` write for the "
+                             "same text.  It is computed from the features in device memory after the CSV files are written, in rounds "
+                             "(M6A_REPR_ROUND_KB, default 131072) whose copies and writes overlap the next round's kernel, so neither "
+                             "data.json nor the whole array is ever held.  Works with every other flag; --compress leaves it a plain "
+                             ".npy, and with --drop_unflushed_tail it has the rows the CSV has." % inference.REPR_FILE)
+    return inference.add_representation_dtype(parser)
+
+
 GZ = ("data.site_proba.csv", "data.indiv_proba.csv")
 
 
@@ -130,6 +144,7 @@ def main(args):
         import sys
         print("m6anet_amd eventalign_inference: error: --compress_level %d needs --compress" % args.compress_level, file=sys.stderr)
         raise SystemExit(2)
+    inference.check_representation_dtype(args, "eventalign_inference")
     weights = inference.resolve_model(args)
     device = inference._device_index(args.device)
     csv_on = getattr(args, "csv", "host")    # argparser() alone (no --csv): the host writer
@@ -137,6 +152,7 @@ def main(args):
     compress = getattr(args, "compress", False)
     level = getattr(args, "compress_level", 1)
     read_names = getattr(args, "read_names", False)
+    want_repr = getattr(args, "read_representation", False)
     if window_mb < 0:
         raise ValueError("--window_mb must be 0 or more, not %d" % window_mb)
     made = {}
@@ -189,13 +205,21 @@ def main(args):
                 host_gz = write_on_host_compressed(writer, args.out_dir, read_prob, site_prob, mod_ratio, args.n_processes, n_write)
             else:
                 writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes, n_sites=n_write)
+        t3 = time.perf_counter()
+        rep = {"n_rounds": 0, "bytes": 0, "ms_kernel": 0.0, "ms_copy": 0.0, "ms_write": 0.0}
+        if want_repr:                        # after the CSV files: X, site_kmers and off are still where infer_ptrs read them
+            rep = sites.write_read_representation(engine, os.path.join(args.out_dir, inference.REPR_FILE),
+                                                  getattr(args, "representation_dtype", "float32"), n_write)
         if os.environ.get("M6A_EVENTALIGN_TIMES"):      # phases for tools/measure_eventalign_inference.py
             import json
             ms, d2h = sites.times()
             ms.update(intern=sites.ms_intern)
-            extra_names = {"n_read_names": sites.n_read_names}
+            ms.update(repr_kernel=rep["ms_kernel"], repr_copy=rep["ms_copy"], repr_write=rep["ms_write"],
+                      repr_total=(time.perf_counter() - t3) * 1e3 if want_repr else 0.0)      # repr_total: the writer's wall time
+            extra_names = {"repr_rounds": rep["n_rounds"], "repr_bytes": rep["bytes"]}
+            extra_names.update(n_read_names=sites.n_read_names)
             ms.update(infer=(t1 - t0) * 1e3, fetch=(t2 - t1) * 1e3 if csv is None else 0.0,
-                      csv_write=(time.perf_counter() - (t2 if csv is None else t1)) * 1e3)        # csv_write: the writer's wall time
+                      csv_write=(t3 - (t2 if csv is None else t1)) * 1e3)        # csv_write: the writer's wall time
             extra = {"csv_writer": "host"}
             if csv is not None:              # the device writer's own phases; they overlap, so they need not add up to csv_write
                 ms.update(csv_format=csv["ms_format"], csv_copy=csv["ms_copy"], csv_pwrite=csv["ms_write"])

@@ -100,7 +100,27 @@ def full_parser():
                              "data.indiv_proba.csv, in its order (np.load(..., mmap_mode='r') reads it without loading it: 128 bytes per "
                              "read).  Both CSVs are the bytes of a run without the flag.  One GPU, host loader: an argument error with "
                              "--gpus N > 1 or --loader device." % REPR_FILE)
+    add_representation_dtype(parser)
     return parser
+
+
+def add_representation_dtype(parser):
+    """--representation_dtype, which `inference` and `eventalign_inference` add beside their --read_representation"""
+    from argparse import SUPPRESS
+    parser.add_argument("--representation_dtype", choices=("float32", "float16"), default=SUPPRESS,     # absent unless given: the check below
+                        help="with --read_representation: the type of %s, float32 unless given.  float16 is each float32 value rounded once to the nearest "
+                             "IEEE binary16 (ties to even; above 65504 is inf; subnormals kept) in the kernel that computes it -- exactly "
+                             "what numpy's .astype(np.float16) makes of the float32 file -- at 64 bytes per read instead of 128, in the "
+                             "file and across the link.  Without --read_representation it is an argument error." % REPR_FILE)
+    return parser
+
+
+def check_representation_dtype(args, command):
+    """--representation_dtype without --read_representation: an argument error, before anything is written or a GPU is touched"""
+    if hasattr(args, "representation_dtype") and not getattr(args, "read_representation", False):
+        import sys
+        print("m6anet_amd %s: error: --representation_dtype %s needs --read_representation" % (command, args.representation_dtype), file=sys.stderr)
+        raise SystemExit(2)
 
 
 def check_loader(args):
@@ -122,6 +142,7 @@ def check_loader(args):
 
 def check_read_representation(args):
     """--read_representation: what it refuses, as an argument error before any rank is launched, any file is written or a GPU is touched"""
+    check_representation_dtype(args, "inference")
     if not getattr(args, "read_representation", False):
         return
     import sys
@@ -138,8 +159,10 @@ def check_read_representation(args):
 def write_read_representation(engine, batch, args):
     """OUT_DIR/data.read_representation.npy, row i = data row i of data.indiv_proba.csv: pieces of whole sites go through
     engine.get_read_representation into one reused buffer and from there into the memory-mapped file, so the process never holds
-    more than a piece of it."""
+    more than a piece of it.  --representation_dtype float16: the memmap and the buffer are float16 and the engine is asked for it."""
     import numpy as np
+    name = getattr(args, "representation_dtype", "float32")
+    dtype = np.dtype(name)
     n_sites = batch.n_sites
     if getattr(args, "drop_unflushed_tail", False):
         from ..engine import reference_written_sites
@@ -147,18 +170,19 @@ def write_read_representation(engine, batch, args):
     off = np.ascontiguousarray(batch.off, np.int64)
     n_rows = int(off[n_sites])
     if n_rows == 0:                                       # an empty file cannot be mapped
-        np.save(os.path.join(args.out_dir, REPR_FILE), np.empty((0, N_REPR), np.float32))
+        np.save(os.path.join(args.out_dir, REPR_FILE), np.empty((0, N_REPR), dtype))
         return
-    out = np.lib.format.open_memmap(os.path.join(args.out_dir, REPR_FILE), mode="w+", dtype=np.float32, shape=(n_rows, N_REPR))
+    out = np.lib.format.open_memmap(os.path.join(args.out_dir, REPR_FILE), mode="w+", dtype=dtype, shape=(n_rows, N_REPR))
     widest = int(np.diff(off[:n_sites + 1]).max(initial=0))      # a bag larger than a piece is a piece of its own
-    piece = np.empty((min(max(widest, REPR_PIECE_READS), n_rows), N_REPR), np.float32)
+    piece = np.empty((min(max(widest, REPR_PIECE_READS), n_rows), N_REPR), dtype)
     s0 = 0
     while s0 < n_sites:
         s1 = int(np.searchsorted(off, off[s0] + REPR_PIECE_READS, side="right")) - 1
         s1 = min(n_sites, max(s1, s0 + 1))
         r0, r1 = int(off[s0]), int(off[s1])
         if r1 > r0:
-            engine.get_read_representation(batch.X[r0:r1], batch.site_kmers[s0:s1], off[s0:s1 + 1] - r0, out=piece[:r1 - r0])
+            engine.get_read_representation(batch.X[r0:r1], batch.site_kmers[s0:s1], off[s0:s1 + 1] - r0, out=piece[:r1 - r0],
+                                           **({"dtype": name} if name != "float32" else {}))
             out[r0:r1] = piece[:r1 - r0]
         s0 = s1
     out.flush()

@@ -22,6 +22,17 @@ Legs run in child processes, one tree per process, alternating parent / this bui
 calls of its legs are interleaved as well.  Every device call is made by the children; a child that finds no GPU fails.
 
     python tools/measure_read_representation.py [--parent-tree DIR] [--out profiles/r23_read_representation.json]
+
+--eventalign SHAPE (a size such as 3.1GB, or a number of copies of the bundled file: tools/measure_eventalign_inference.py's shapes)
+measures `eventalign_inference --read_representation` instead -> profiles/r24_repr_eventalign.json:
+
+  the command without the flag, with it, and with it in float16 (and, with --parent-tree, the parent's command without the flag),
+  --legs interleaved runs each in processes of their own: wall seconds and the M6A_EVENTALIGN_TIMES phases;
+  the writer against its parts with no overlap: its own repr_kernel + one plain hipMemcpy of the same bytes into pinned memory + one
+  pwrite of the same bytes into the same directory, timed in the same session (child `parts`); the writer's wall time (repr_total) must
+  not exceed that sum plus the spread of the sum's legs;
+  the float32 kernel of this build against the parent's at 1 M sites x 20 reads (bar: the parent's median plus its own spread), the
+  float16 kernel beside it, and bench.py against the parent as above.
 """
 import argparse
 import ctypes as C
@@ -87,6 +98,9 @@ def child(args):
             return a.elapsed_time(b)
         legs["repr"] = lambda: kernel_ms(lambda: eng.get_read_representation(X, km, off, out=(rep, rp)))
         legs["write"] = write
+        if hasattr(_lib, "REPR_DTYPES"):                         # a build with m6a_read_representation_dtype
+            rep16 = torch.empty((R, 32), dtype=torch.float16, device=dev)
+            legs["repr_f16"] = lambda: kernel_ms(lambda: eng.get_read_representation(X, km, off, out=(rep16, rp), dtype="float16"))
     times = {k: [] for k in legs}
     for f in legs.values():                                      # warm-up: code objects, first touch of the outputs
         f()
@@ -96,6 +110,115 @@ def child(args):
     out = {"lib": os.path.relpath(_lib.LIB_PATH, os.path.abspath(args.tree) if args.tree else REPO), "kernel": eng.last_encoder_kernel, "device": torch.cuda.get_device_name(0),
            "ms": {k: statistics.median(v) for k, v in times.items()}, "calls_ms": times}
     print("LEG " + json.dumps(out), flush=True)
+
+
+def parts_child(args):
+    """The writer's parts with no overlap: one hipMemcpy of --bytes from device into pinned memory, one pwrite of them into --dir."""
+    import time
+    import numpy as np
+    import torch
+    n = args.bytes
+    dev = torch.empty(n, dtype=torch.uint8, device="cuda:0").fill_(7)
+    pin = torch.empty(n, dtype=torch.uint8).pin_memory()
+    host = pin.numpy()
+    path = os.path.join(args.dir, "parts.bin")
+    copy_ms, write_ms = [], []
+    for k in range(args.calls + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pin.copy_(dev)                                           # blocking hipMemcpy into pinned memory
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+        os.ftruncate(fd, n)
+        at = 0
+        view = memoryview(host)
+        while at < n:
+            at += os.pwrite(fd, view[at:at + (1 << 30)], at)
+        os.close(fd)
+        t2 = time.perf_counter()
+        if k:                                                    # the first pass touches the pages
+            copy_ms.append((t1 - t0) * 1e3)
+            write_ms.append((t2 - t1) * 1e3)
+    os.remove(path)
+    assert int(np.asarray(host[:1])[0]) == 7
+    print("LEG " + json.dumps({"copy_ms": copy_ms, "write_ms": write_ms, "bytes": n}), flush=True)
+
+
+def eventalign_legs(args):
+    """`eventalign_inference` without the flag, with it and with it in float16 (and the parent's command without it), interleaved"""
+    import shutil
+    import tempfile
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import measure_eventalign_inference as ME
+    ev_dir = tempfile.mkdtemp(prefix="repr_eventalign_", dir=args.ev_dir)
+    try:
+        path, n = ME.write_shape(args.eventalign, ev_dir)
+        kinds = {"plain": (REPO, []), "repr": (REPO, ["--read_representation"]),
+                 "repr_f16": (REPO, ["--read_representation", "--representation_dtype", "float16"])}
+        if args.parent_tree:
+            kinds["parent_plain"] = (os.path.abspath(args.parent_tree), [])
+        runs = {k: [] for k in kinds}
+        env = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+        for _ in range(args.legs):
+            for kind, (tree, flags) in kinds.items():
+                out = os.path.join(ev_dir, "out_" + kind)
+                s, p = ME.timed(["eventalign_inference", "--eventalign", path, "--out_dir", out] + ME.THREADS + flags, args.leg_timeout, env=env, tree=tree)
+                if p.returncode != 0:
+                    raise SystemExit("%s failed (%d):\n%s" % (kind, p.returncode, p.stderr[-3000:]))
+                t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+                runs[kind].append({"wall_s": s, "ms": t["ms"], "d2h_bytes": t["d2h_bytes"], "peak_bytes": t["peak_bytes"], "n_reads": t["n_reads"],
+                                   **{k: t[k] for k in ("repr_rounds", "repr_bytes") if k in t}})
+                shutil.rmtree(out, ignore_errors=True)
+                print("%s: %.2f s" % (kind, s), file=sys.stderr, flush=True)
+        res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": args.legs, "n_reads": runs["plain"][0]["n_reads"], "runs": runs}
+        for kind, v in runs.items():
+            w = [r["wall_s"] for r in v]
+            res[kind + "_wall_s"] = {"median": statistics.median(w), "spread": max(w) - min(w)}
+        if args.parent_tree:
+            bar = res["parent_plain_wall_s"]["median"] + res["parent_plain_wall_s"]["spread"]
+            res["plain_against_parent"] = {"bar_s": bar, "this_s": res["plain_wall_s"]["median"], "meets_bar": res["plain_wall_s"]["median"] <= bar}
+        for kind in ("repr", "repr_f16"):
+            nbytes = runs[kind][0]["repr_bytes"] - 128
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "parts", "--bytes", str(nbytes), "--dir", ev_dir, "--calls", str(args.legs)],
+                               capture_output=True, text=True, timeout=args.leg_timeout)
+            lines = [ln for ln in r.stdout.splitlines() if ln.startswith("LEG ")]
+            if r.returncode != 0 or not lines:
+                raise SystemExit("parts failed (%d):\n%s" % (r.returncode, r.stderr[-3000:]))
+            parts = json.loads(lines[-1][4:])
+            sums = [a["ms"]["repr_kernel"] + c + w for a, c, w in zip(runs[kind], parts["copy_ms"], parts["write_ms"])]
+            total = statistics.median([a["ms"]["repr_total"] for a in runs[kind]])
+            bar = statistics.median(sums) + max(sums) - min(sums)
+            res[kind + "_writer"] = {"bytes": nbytes, "rounds": runs[kind][0]["repr_rounds"],
+                                     "repr_kernel_ms": statistics.median([a["ms"]["repr_kernel"] for a in runs[kind]]),
+                                     "repr_copy_ms": statistics.median([a["ms"]["repr_copy"] for a in runs[kind]]),
+                                     "repr_write_ms": statistics.median([a["ms"]["repr_write"] for a in runs[kind]]),
+                                     "plain_hipMemcpy_ms": statistics.median(parts["copy_ms"]), "plain_pwrite_ms": statistics.median(parts["write_ms"]),
+                                     "sum_of_parts_ms": statistics.median(sums), "sum_spread_ms": max(sums) - min(sums), "bar_ms": bar,
+                                     "writer_wall_ms": total, "meets_bar": total <= bar, "below_the_sum_ms": statistics.median(sums) - total,
+                                     "flag_costs_s": res[kind + "_wall_s"]["median"] - res["plain_wall_s"]["median"]}
+        return res
+    finally:
+        shutil.rmtree(ev_dir, ignore_errors=True)
+
+
+def kernels_against_parent(args):
+    """enc_repr_kernel of this build and of the parent at the r23 shape, and the float16 kernel beside them"""
+    legs = {"parent_repr": [], "repr": [], "repr_f16": []}
+    for _ in range(args.rounds):
+        if args.parent_tree:
+            legs["parent_repr"].append(run_child("repr", args.parent_tree, args)["ms"]["repr"])
+        n = run_child("repr", None, args)
+        legs["repr"].append(n["ms"]["repr"])
+        legs["repr_f16"].append(n["ms"]["repr_f16"])
+        print("kernels: %s" % {k: v[-1] for k, v in legs.items() if v}, file=sys.stderr, flush=True)
+    res = {"shape": {"sites": args.sites, "reads_per_site": BAG}, "legs_ms": legs,
+           "T_repr_ms": statistics.median(legs["repr"]), "T_repr_f16_ms": statistics.median(legs["repr_f16"]),
+           "r23_T_repr_ms": 2.752}
+    if args.parent_tree:
+        med, spread = statistics.median(legs["parent_repr"]), max(legs["parent_repr"]) - min(legs["parent_repr"])
+        res.update(T_parent_repr_ms=med, parent_spread_ms=spread, bar_ms=med + spread, meets_bar=res["T_repr_ms"] <= med + spread)
+    return res
 
 
 def run_child(kind, tree, args):
@@ -149,11 +272,38 @@ def main():
     ap.add_argument("--calls", type=int, default=7, help="timed calls per leg")
     ap.add_argument("--bench-rounds", type=int, default=4, help="with --parent-tree: bench.py runs per tree, alternating (0: none)")
     ap.add_argument("--leg-timeout", type=float, default=240.0, help="seconds a child process may take")
-    ap.add_argument("--child", choices=("walk", "repr"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child", choices=("walk", "repr", "parts"), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--eventalign", default=None, help="a shape (3.1GB, or copies of the bundled file): measure the command, write r24_repr_eventalign.json")
+    ap.add_argument("--legs", type=int, default=5, help="with --eventalign: interleaved runs per kind of command")
+    ap.add_argument("--ev-dir", default=None, help="with --eventalign: where the generated file and the outputs go (default: the temporary directory)")
+    ap.add_argument("--bytes", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--dir", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child == "parts":
+        return parts_child(args)
     if args.child:
         return child(args)
+    if args.eventalign:
+        out = args.out if "r23_" not in os.path.basename(args.out) else os.path.join(REPO, "profiles", "r24_repr_eventalign.json")
+        res = {"what": "eventalign_inference --read_representation [--representation_dtype float16] against the command without the flag, "
+                       "the writer against its parts with no overlap, and the default paths against the parent commit",
+               "parent_tree_given": bool(args.parent_tree)}
+
+        def save():
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+        res["eventalign"] = eventalign_legs(args)
+        save()
+        res["kernels"] = kernels_against_parent(args)
+        save()
+        if args.parent_tree and args.bench_rounds > 0:
+            res["bench"] = bench_alternating(args)
+            save()
+        print(json.dumps({k: (v if k != "eventalign" else {a: b for a, b in v.items() if a != "runs"}) for k, v in res.items()}))
+        return
     legs = {"walk": [], "repr": [], "write": []}
     meta = {}
     for _ in range(args.rounds):

@@ -66,7 +66,16 @@ enum { M6A_RNG_NUMPY = 0 };
  * `weights` is a host pointer.  The weights are laid out for the kernels here; BatchNorm (eval, eps 1e-5) becomes the
  * (alpha, beta) = (gamma / sqrt(var + eps), fma(-mean, alpha, bias)) pair torch forms, applied per read in the kernel as
  * torch applies it -- nothing is folded into W1: the encoder's float32 sums run in the reference's order.
- * M6A_EUNSUPPORTED for a layer-2 weight or bias of magnitude >= 2^63 (the kernels carry them scaled by 2^64). */
+ * M6A_EUNSUPPORTED for a layer-2 weight or bias of magnitude >= 2^63 (the kernels carry them scaled by 2^64).
+ * Which blobs the bit-for-bit claim of the 16-slot kernels (m6a_set_encoder_variant) covers -- any finite blob, trained here or
+ * elsewhere, for which
+ *   - every hidden activation relu(fma(z1, alpha, beta)) stays below 2^64 (the kernels hold it scaled by 2^-64 under a clamp to
+ *     [0, 1]: beyond 2^64 it saturates there where the reference carries it on);
+ *   - every alpha and beta above is 0 or at least 2^-62 in magnitude (smaller ones lose low bits in that scaling);
+ *   - every layer-2 weight and bias stays below 2^63 in magnitude (refused above).
+ * Inside that domain nothing else is asked of the weights: any sign, any zero (a gamma of 0 prunes its unit), running_var down
+ * to 0 (alpha = gamma / sqrt(1e-5f), about 316 gamma).  A NaN weight gives NaN wherever the reference's arithmetic gives NaN.
+ * tests/weight_families.py generates blobs across this domain; tests/test_gpu_encoder_weights.py runs every kernel on them. */
 int m6a_create(m6a_ctx **out, const float *weights, size_t n_floats, int device_id);
 void m6a_destroy(m6a_ctx *ctx);
 const char *m6a_last_error(const m6a_ctx *ctx);   /* ctx may be NULL: last create error */

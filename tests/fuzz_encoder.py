@@ -32,6 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from m6anet_amd.constants import DEFAULT_PRETRAINED_MODELS  # noqa: E402
 from m6anet_amd.engine import M6ANetEngine, load_weights  # noqa: E402
 from oracle import m6a_oracle as orc  # noqa: E402
+import weight_families as WF  # noqa: E402  (tests/, this script's directory)
 
 
 def main():
@@ -53,9 +54,8 @@ def main():
         name = models[int(g.integers(0, len(models)))]
         w = load_weights(name).copy()
         perturbed = g.random() < 0.3
-        if perturbed:                                              # other weights than the four the fixtures pin
-            w *= (1.0 + 0.05 * g.standard_normal(w.size)).astype(np.float32)
-            w[2982:3132] = np.abs(w[2982:3132]) + 1e-3             # BatchNorm running variance stays positive
+        if perturbed:                                              # other weights than the four the fixtures pin: a random family and seed
+            w = WF.blob(WF.FAMILIES[int(g.integers(0, len(WF.FAMILIES)))], int(g.integers(0, 2 ** 31)))
         key = name if not perturbed else None
         eng = engines.get(key) if key else None
         if eng is None:

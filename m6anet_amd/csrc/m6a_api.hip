@@ -674,20 +674,29 @@ int bag_stats(m6a_ctx *c, const int64_t *d_off, int64_t S)
 }
 
 // ---- launches (all pointers are device pointers here) ------------------------------------------
+// What every encoder launch has in common: the argument block (no clock stamps: launch_encode adds them when it is profiled)
+// and the geometry -- workgroups of 4 waves, each wave `tiles_per_wave` consecutive 32-read tiles, at most 2 workgroups per CU.
+// Returns the number of workgroups.
+static unsigned enc_args(m6a_ctx *c, EncArgs &a, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *rp)
+{
+    a.X = X; a.site_kmers = km; a.off = off; a.wfrag = c->d_wfrag; a.emb = c->d_emb; a.read_prob = rp;
+    a.wfrag2 = c->d_wfrag2; a.w1e_tab = c->d_w1e; a.bn = c->d_w1e + M6A_W1E_FLOATS; a.err = c->d_err;
+    a.n_sites = S; a.n_reads = R; a.n_tiles = (R + 31) / 32; a.b3 = c->b3;
+    a.clk = nullptr;
+    const int64_t max_waves = (int64_t)c->n_cu * 8;        // 2 blocks/CU x 4 waves
+    a.tiles_per_wave = (a.n_tiles + max_waves - 1) / max_waves;
+    const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
+    return (unsigned)((waves + 3) / 4);
+}
+
 // c->bag_min must describe `off` (query_bags / host_bag_range ran for this call)
 int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S,
                   int64_t R, float *rp)
 {
     if (R <= 0 || S <= 0) return M6A_OK;
     EncArgs a;
-    a.X = X; a.site_kmers = km; a.off = off; a.wfrag = c->d_wfrag; a.emb = c->d_emb; a.read_prob = rp;
-    a.wfrag2 = c->d_wfrag2; a.w1e_tab = c->d_w1e; a.bn = c->d_w1e + M6A_W1E_FLOATS; a.err = c->d_err;
-    a.n_sites = S; a.n_reads = R; a.n_tiles = (R + 31) / 32; a.b3 = c->b3;
+    const unsigned blocks = enc_args(c, a, X, km, off, S, R, rp);
     a.clk = c->prof.clk_for(0);
-    const int64_t max_waves = (int64_t)c->n_cu * 8;        // 2 blocks/CU x 4 waves
-    a.tiles_per_wave = (a.n_tiles + max_waves - 1) / max_waves;
-    const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
     // every bag >= 16 reads: a 32-read tile spans <= 3 sites, and the site lookup is the scalar 32-bit chain of
     // enc_site16_kernel (the reference's 16 slots, 116 MFMAs per tile: auto) / enc_csite_kernel (12-slot layer 1, 106: opt-in);
     // otherwise enc_kernel: the same 16-slot arithmetic behind a per-lane 64-bit walk of off[].
@@ -716,16 +725,8 @@ int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *of
 {
     if (R <= 0 || S <= 0) return M6A_OK;
     EncReprArgs ra;
-    EncArgs &a = ra.enc;
-    a.X = X; a.site_kmers = km; a.off = off; a.wfrag = c->d_wfrag; a.emb = c->d_emb; a.read_prob = rp;
-    a.wfrag2 = c->d_wfrag2; a.w1e_tab = c->d_w1e; a.bn = c->d_w1e + M6A_W1E_FLOATS; a.err = c->d_err;
-    a.n_sites = S; a.n_reads = R; a.n_tiles = (R + 31) / 32; a.b3 = c->b3;
-    a.clk = nullptr;
+    const unsigned blocks = enc_args(c, ra.enc, X, km, off, S, R, rp);
     ra.repr = repr;
-    const int64_t max_waves = (int64_t)c->n_cu * 8;        // 2 blocks/CU x 4 waves, as launch_encode
-    a.tiles_per_wave = (a.n_tiles + max_waves - 1) / max_waves;
-    const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
     c->enc_variant_used = "general16";
     c->enc_kernel_used = dtype == M6A_REPR_F16 ? "enc_repr_kernel<true>" : "enc_repr_kernel";
     prof_begin(c, 0);

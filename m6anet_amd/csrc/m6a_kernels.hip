@@ -1,13 +1,16 @@
 // m6a_kernels.hip -- gfx950 (MI355X / CDNA4) kernels of the m6A inference hot path.
 //
-//   enc_kernel, enc_csite_kernel
+//   enc_kernel, enc_site16_kernel, enc_csite_kernel
 //                      read encoder: [x(9) | emb(6) | 1] -> 150 -> batch norm -> ReLU -> 32 -> ReLU
 //                      -> 1 -> sigmoid, all in registers on v_mfma_f32_32x32x2_f32 (two IEEE fmas per output, k = the
 //                      half-0 operand first), every sum through layer 2 in the order the reference's float32 arithmetic
-//                      runs it -- enc_kernel all the way to the probability (the reference's bits); the csite variant
-//                      folds the per-site constants (12 K-slots, bags >= 16 reads) and keeps a plain 32 -> 1 sum.
+//                      runs it -- enc_kernel (per-lane walk, any bags) and enc_site16_kernel (scalar input chain, bags >= 16
+//                      reads) all the way to the probability (the reference's bits); the csite variant folds the per-site
+//                      constants (12 K-slots, bags >= 16 reads) and keeps a plain 32 -> 1 sum.
 //   enc_repr_kernel    enc_kernel that also stores layer 2 after its ReLU: the read representation, [R][32] (m6a_read_representation)
 //   enc_repr_kernel<true>  the same with the 32 values stored as binary16 (m6a_read_representation_dtype, M6A_REPR_F16)
+//                      The five are compositions of one set of pieces (LDS staging, fragment loads, start-site search, the
+//                      unit-tile loop, the reference-order epilogue), one per-lane walk body and one scalar chain.
 //   pool_scan_start_kernel + pool_scan_site_kernel, pool_scan_group_kernel
 //                      site pooling, exact NumPy-stream replay, any bag sizes: a counting pass per
 //                      flush group finds where each site starts in the shared MT19937 word stream
@@ -251,57 +254,192 @@ __device__ __forceinline__ void wave_lds_fence()
 // K slot 2s + h holds feature 2s + h: half 0 lanes load x0, x2, x4, x6, x8, e1, e3, e5; half 1 lanes x1, x3,
 // x5, x7, e0, e2, e4, 1.  With that, layers 1 and 2 of this kernel are the reference's bits; the epilogue
 // (gemv32_as_mkl, sleef_expf_u10 above) carries that on to the probability.
+//
+// The five kernels are compositions of the pieces below, each of which exists once: the LDS staging, the fragment loads, the
+// start-site search, the unit-tile loop (around the kernel's layer 1 and its placement of the input chain's links) and the
+// reference-order epilogue.  What a kernel keeps to itself is what really differs: how a lane finds its site (the per-lane
+// walk of enc_kernel / enc_repr_kernel, the scalar chain of enc_site16_kernel / enc_csite_kernel), where the links sit
+// between the MFMA groups (measured per kernel), and what follows the tile.
 // =====================================================================================
+// what every encoder kernel stages into LDS: the embedding table and the batch-norm pairs
+struct EncLds {
+    float emb[132];
+    __attribute__((aligned(16))) float bn[M6A_BN_FLOATS];
+};
+__device__ __forceinline__ void stage_lds(EncLds &s, const EncArgs &a)
+{
+    for (int i = threadIdx.x; i < 132; i += 256) s.emb[i] = a.emb[i];
+    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s.bn[i] = a.bn[i];
+}
+
+// weight fragments, lane-major on the host side: one coalesced load per register
+template <int N> __device__ __forceinline__ void load_frag(float (&w)[N], const float *frag, int lane)
+{
+#pragma unroll
+    for (int i = 0; i < N; i++) w[i] = frag[i * 64 + lane];
+}
+__device__ __forceinline__ void load_frags16(const float *wfrag, int lane, float (&w1)[40], float (&w2)[80], float (&w3)[16])
+{
+    load_frag(w1, wfrag, lane);
+    load_frag(w2, wfrag + 40 * 64, lane);
+    load_frag(w3, wfrag + 120 * 64, lane);
+}
+
+// site of the wave's first read: largest s with off[s] <= r (upper_bound - 1)
+template <typename I> __device__ __forceinline__ I first_site(const int64_t *off, I n_sites, int64_t r)
+{
+    I lo = 0, hi = n_sites;                      // invariant: off[lo] <= r < off[hi]
+    while (hi - lo > 1) {
+        const I mid = (I)(((int64_t)lo + hi) >> 1);
+        if (off[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Layer 1 of unit tile m with all 16 K slots: 8 MFMAs from w1[]
+__device__ __forceinline__ void layer1_16(int m, f32x16 &acc, const float (&w1)[40], const float (&f)[8])
+{
+#pragma unroll
+    for (int q = 0; q < 16; q++) acc[q] = 0.0f;
+#pragma unroll
+    for (int st = 0; st < 8; st++)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[m * 8 + st], f[st], acc, 0, 0, 0);
+}
+
+// The unit-tile loop of one 32-read tile: layers 1 and 2 into acc2.  Layer 1 of unit-tile m+1 is issued ahead of layer 2 of
+// unit-tile m (ping-pong accumulators).  Batch norm + ReLU of the finished tile and the layer-2 MFMAs that consume it go in
+// blocks of four hidden units (layer2_with_bn): four clamped fmas, the next block's pairs fetched from LDS, four MFMAs.
+//   layer1(m, acc)   the kernel's layer 1 of unit tile m into acc (zeroed there);
+//   links(m)         the links of the NEXT tile's input chain the kernel places behind the layer-1 MFMAs of unit tile m + 1.
+template <class Layer1, class Links>
+__device__ __forceinline__ void unit_tile_loop(f32x16 &acc2, const float (&w2)[80], BnPairs &bnq, const float *bn_half, Layer1 &&layer1, Links &&links)
+{
+    f32x16 h1a, h1b;
+#pragma unroll
+    for (int q = 0; q < 16; q++) acc2[q] = 0.0f;
+    layer1(0, h1a);
+#pragma unroll
+    for (int m = 0; m < 5; m++) {
+        f32x16 &cur = (m & 1) ? h1b : h1a;
+        f32x16 &nxt = (m & 1) ? h1a : h1b;
+        if (m < 4) layer1(m + 1, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        links(m);
+        if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
+        if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
+        if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
+        if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
+        if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
+    }
+}
+
+// The reference-order epilogue: Linear(32, 1) as the reference's sgemv adds it, the sigmoid through Sleef's expf, and the
+// store by the half-0 lane of a read that exists (`mine`).
+__device__ __forceinline__ void store_prob_as_reference(const f32x16 &acc2, const float (&w3)[16], int half, float b3, bool mine, float *dst)
+{
+    const float z = gemv32_as_mkl(acc2, w3, half) + b3;
+    const float p = 1.0f / (1.0f + sleef_expf_u10(-z));
+    if (half == 0 && mine) *dst = p;
+}
+
+// =====================================================================================
+// Read representation: layer 2 after its ReLU, the 32 floats per read the reference's MILModel.get_read_representation
+// returns (m6anet/model/model.py:85-97), stored between the tile body and the epilogue of enc_repr_kernel.
+//
+// Where the 32 outputs of a read are: register q of lane half 0 holds output unit 2q + 1, register q of half 1 unit 2q + 2,
+// and register 15 of half 1 unit 0 (m6a_api.hip build_fragments out_unit: the wiring gemv32_as_mkl wants).  The two lanes
+// of a read (lane, lane ^ 32) swap eight values -- half 0 gives away units 17, 19, .., 31 (registers 8..15) and gets units
+// 0, 2, .., 14; half 1 gives away register 15 and registers 0..6 -- after which half 0 holds units 0..15 and half 1 units
+// 16..31 in order: four 16-byte stores per lane, 64 contiguous bytes, repr[r][16 half .. 16 half + 16).  The exchange is
+// executed by all lanes; only the stores are guarded (the last tile is partial, its spare lanes compute on a clamped read).
+// relu is the oracle's a < 0 ? 0 : a on the accumulator itself (keeps NaN, as torch's does), not relu2's doubled value.
+//
+// A template over the output type.  float32 is the arithmetic above and the four stores.  binary16: after the same swap the lane's
+// 16 values are converted, each from the float32 value the other form stores, and leave as 32 contiguous bytes, two guarded 16-byte
+// stores, repr[r][16 half .. 16 half + 16) of a [R][32] binary16 array.  The conversion is v_cvt_f16_f32 under the mode the
+// build gives every kernel here: round to nearest even, float_denorm_mode_32 = 3 and float_denorm_mode_16_64 = 3 (the kernel
+// descriptor's defaults; clamp_keeps_nan touches DX10_CLAMP alone), so a float32 subnormal is read as it is and a result in
+// the binary16 subnormal range is produced, not flushed; FP16_OVFL is clear, so what rounds above 65504 is +inf; a NaN stays
+// a NaN with the top bits of its payload.  That is np.float32(v).astype(np.float16) on every value this kernel can produce.
+// =====================================================================================
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t f16_pair(float lo, float hi)
+{
+    const f32x2 v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+}
+template <bool F16> __device__ __forceinline__ void store_repr(const f32x16 &acc2, int half, bool mine, void *repr, int64_t r)
+{
+    float h[16], got[8];
+#pragma unroll
+    for (int q = 0; q < 16; q++) h[q] = acc2[q] < 0.0f ? 0.0f : acc2[q];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        float give = half ? h[(i + 15) & 15] : h[8 + i];
+        got[i] = __shfl_xor(give, 32, 64);                    // all lanes: the guard is on the stores
+    }
+    float4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        v[j].x = half ? h[7 + 2 * j] : got[2 * j];
+        v[j].y = half ? got[2 * j] : h[2 * j];
+        v[j].z = half ? h[8 + 2 * j] : got[2 * j + 1];
+        v[j].w = half ? got[2 * j + 1] : h[2 * j + 1];
+    }
+    if constexpr (F16) {
+        uint4 w[2];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            w[j].x = f16_pair(v[2 * j].x, v[2 * j].y);
+            w[j].y = f16_pair(v[2 * j].z, v[2 * j].w);
+            w[j].z = f16_pair(v[2 * j + 1].x, v[2 * j + 1].y);
+            w[j].w = f16_pair(v[2 * j + 1].z, v[2 * j + 1].w);
+        }
+        if (mine) {
+            uint4 *dst = (uint4 *)((uint16_t *)repr + r * 32 + half * 16);
+            dst[0] = w[0];
+            dst[1] = w[1];
+        }
+    } else if (mine) {
+        float4 *dst = (float4 *)((float *)repr + r * 32 + half * 16);
+#pragma unroll
+        for (int j = 0; j < 4; j++) dst[j] = v[j];
+    }
+}
+
+// =====================================================================================
+// The per-lane walk: enc_kernel and both enc_repr_kernel instantiations.  Takes every bag size and 64-bit indices.
+//
 // Input pipeline: the features of tile t+1 are fetched while tile t is on the matrix pipe.  The
 // site lookup is a dependent chain (CSR offsets -> k-mer ids -> embedding rows); its three links
 // are issued between the five 24-MFMA groups of the current tile, so no link ever waits in front
 // of an MFMA.  A 32-read tile that starts in site `a` normally ends by site a+2 (bags >= 16
 // reads); off[a+1..a+3] are fetched up front (wave-uniform) and lanes pick their site by
 // comparison.  Smaller bags take the (rare) per-lane walk.
-struct EncTile {
-    float f[8];        // this lane's 8 B-operand features of the tile
-    int64_t s_last;    // site of the tile's last read (wave-uniform)
-};
-
-__global__ __launch_bounds__(256, 2) void enc_kernel(EncArgs a)
+//
+// What follows the tile is the template's part: the probability (always with REPR_NONE; with a representation only when
+// read_prob is non-null: a kernel argument, wave-uniform) and the representation store (none / float32 / binary16).
+// =====================================================================================
+enum { REPR_NONE, REPR_F32, REPR_F16 };
+template <int REPR> __device__ __forceinline__ void enc_walk_tiles(const EncArgs &a, void *repr)
 {
-    clamp_keeps_nan();
-    m6a_clk_stamp(a.clk, 0);
-    __shared__ float s_emb[132];
-    __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
-    for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
+    __shared__ EncLds lds;
+    stage_lds(lds, a);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const int col = lane & 31;
     const int half = lane >> 5;
-    const float *bn_half = s_bn + half * 32;
+    const float *bn_half = lds.bn + half * 32;
     const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar tile loop
     const int64_t tile0 = wave * a.tiles_per_wave;
-    if (tile0 >= a.n_tiles) return;
+    if (tile0 >= a.n_tiles) return;              // never wave 0 of a workgroup (the host launches no empty one), the wave that stamps enc_kernel's clock
     const int64_t tile1 = (tile0 + a.tiles_per_wave < a.n_tiles) ? tile0 + a.tiles_per_wave : a.n_tiles;
 
-    // weight fragments, lane-major on the host side: one coalesced load per register
     float w1[40], w2[80], w3[16];
-#pragma unroll
-    for (int i = 0; i < 40; i++) w1[i] = a.wfrag[i * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 80; i++) w2[i] = a.wfrag[(40 + i) * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 16; i++) w3[i] = a.wfrag[(120 + i) * 64 + lane];
+    load_frags16(a.wfrag, lane, w1, w2, w3);
 
-    // site of the wave's first read: largest s with off[s] <= r (upper_bound - 1)
-    int64_t s_base;
-    {
-        const int64_t r = tile0 * 32;
-        int64_t lo = 0, hi = a.n_sites;          // invariant: off[lo] <= r < off[hi]
-        while (hi - lo > 1) {
-            int64_t mid = (lo + hi) >> 1;
-            if (a.off[mid] <= r) lo = mid; else hi = mid;
-        }
-        s_base = lo;
-    }
+    int64_t s_base = first_site<int64_t>(a.off, a.n_sites, tile0 * 32);
     const int64_t last_site = a.n_sites - 1;
 
     // ---- the three links of the input chain for one tile -------------------------------------
@@ -338,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void enc_kernel(EncArgs a)
     // link 2: embedding floats from LDS: features 9..14 = e0..e5 (float c&1 of k-mer c>>1), feature 15 = the constant 1
     // that adds b1; half 0 takes the odd floats into slots 5..7, half 1 the even ones into slots 4..6
     auto link2 = [&](const int (&km)[3], float (&x)[8]) {
-        const float e0 = s_emb[2 * km[0] + 1 - half], e1 = s_emb[2 * km[1] + 1 - half], e2 = s_emb[2 * km[2] + 1 - half];
+        const float e0 = lds.emb[2 * km[0] + 1 - half], e1 = lds.emb[2 * km[1] + 1 - half], e2 = lds.emb[2 * km[2] + 1 - half];
         x[4] = half ? e0 : x[4];
         x[5] = half ? e1 : e0;
         x[6] = half ? e2 : e1;
@@ -368,127 +506,118 @@ __global__ __launch_bounds__(256, 2) void enc_kernel(EncArgs a)
         link0(s_base, o);
         tile_body_priority();
 
-        // Layer 1 of unit-tile m+1 is issued ahead of layer 2 of unit-tile m (ping-pong
-        // accumulators).  Batch norm + ReLU of the finished tile and the layer-2 MFMAs that consume it go in blocks
-        // of four hidden units (layer2_with_bn): four clamped fmas, the next block's pairs fetched from LDS, four MFMAs.
-        f32x16 acc2, h1a, h1b;
-#pragma unroll
-        for (int q = 0; q < 16; q++) { acc2[q] = 0.0f; h1a[q] = 0.0f; }
-#pragma unroll
-        for (int st = 0; st < 8; st++)
-            h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < 5; m++) {
-            f32x16 &cur = (m & 1) ? h1b : h1a;
-            f32x16 &nxt = (m & 1) ? h1a : h1b;
-            if (m < 4) {
-#pragma unroll
-                for (int q = 0; q < 16; q++) nxt[q] = 0.0f;
-#pragma unroll
-                for (int st = 0; st < 8; st++)
-                    nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(m + 1) * 8 + st], f[st], nxt, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc2;
+        unit_tile_loop(acc2, w2, bnq, bn_half, [&](int m, f32x16 &acc) { layer1_16(m, acc, w1, f); }, [&](int m) {
             if (m == 0) link1(tn, s_base, o, sn, km, fn);
             if (m == 2) link2(km, fn);
-            if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
-            if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
-            if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
-            if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
-            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
-        }
+        });
         tile_epilogue_priority();
-        const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;
-        const float p = 1.0f / (1.0f + sleef_expf_u10(-z));
         const int64_t r = tile * 32 + col;
-        if (half == 0 && r < a.n_reads) a.read_prob[r] = p;
+        if (REPR != REPR_NONE) store_repr<REPR == REPR_F16>(acc2, half, r < a.n_reads, repr, r);
+        if (REPR == REPR_NONE || a.read_prob) store_prob_as_reference(acc2, w3, half, a.b3, r < a.n_reads, a.read_prob + r);
         if (tn != tile) s_base = uniform_i64(__shfl(sn, 31, 64));
 #pragma unroll
         for (int i = 0; i < 8; i++) f[i] = fn[i];
     }
-    m6a_clk_stamp(a.clk, 1);
 }
 
-// =====================================================================================
-// Read encoder, 16 slots, bags >= 16 reads: enc_kernel's arithmetic behind enc_csite_kernel's input chain.
-//
-// Every float32 operation is enc_kernel's (same fragments, same K-slot wiring, same epilogue: the reference's bits); what
-// differs is how a lane finds its site and its six embedding floats.  enc_kernel walks the CSR array per lane with 64-bit
-// indices (vector loads of off[], three k-mer byte loads and three LDS reads per lane, 64-bit clamps on the VALU -- the
-// datapath the f32 MFMAs use); here, as in the 12-slot kernel below, a 32-read tile spans at most three sites, so
-//   link0  off[a+1..a+3] come through scalar loads (constant address space), tile and site indices are 32-bit SALU values;
-//   link1  the lane's site is `rel` = 0, 1, 2 relative to the wave-uniform base, by two 32-bit compares; lanes 0..17 fetch
-//          ONE k-mer id byte each (float q of site a + q/6), then the x loads;
-//   link2  the embedding float, one LDS read per lane;
-//   link3  three ds_bpermute (LDS crossbar, not the VALU) hand every lane its site's floats: half 0 the odd ones
-//          (e1, e3, e5: K slots 5..7), half 1 the even ones (e0, e2, e4: slots 4..6) and the constant 1.
-// A tile that would need a fourth site raises the error flag (the host launches this kernel only when the smallest bag
-// has >= 16 reads and the job fits 32-bit indices; enc_kernel stays the path for everything else).
-// =====================================================================================
-__global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
+__global__ __launch_bounds__(256, 2) void enc_kernel(EncArgs a)
 {
     clamp_keeps_nan();
     m6a_clk_stamp(a.clk, 0);
-    __shared__ float s_emb[132];
-    __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
-    for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
-    __syncthreads();
+    enc_walk_tiles<REPR_NONE>(a, nullptr);
+    m6a_clk_stamp(a.clk, 1);
+}
 
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 31;
-    const int half = lane >> 5;
-    const float *bn_half = s_bn + half * 32;
-    const int wave = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int n_tiles = (int)a.n_tiles, tpw = (int)a.tiles_per_wave;
-    const int tile0 = wave * tpw;
-    if (tile0 >= n_tiles) return;
-    const int tile1 = (tile0 + tpw < n_tiles) ? tile0 + tpw : n_tiles;
-    const int n_sites = (int)a.n_sites;
-    const int last_lim = (int)(a.n_reads - 1 - (int64_t)(n_tiles - 1) * 32);   // last valid column of the last tile
+// enc_kernel that also stores the read representation, [R][32]: float32 (m6a_read_representation), or binary16 with F16
+// (m6a_read_representation_dtype, M6A_REPR_F16).  read_prob may be null: the epilogue is then skipped.
+template <bool F16> __global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
+{
+    clamp_keeps_nan();
+    enc_walk_tiles<F16 ? REPR_F16 : REPR_F32>(ra.enc, ra.repr);
+}
+template __global__ void enc_repr_kernel<false>(EncReprArgs ra);
+template __global__ void enc_repr_kernel<true>(EncReprArgs ra);
 
-    float w1[40], w2[80], w3[16];
-#pragma unroll
-    for (int i = 0; i < 40; i++) w1[i] = a.wfrag[i * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 80; i++) w2[i] = a.wfrag[(40 + i) * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 16; i++) w3[i] = a.wfrag[(120 + i) * 64 + lane];
+// =====================================================================================
+// The scalar chain: what the input chains of enc_site16_kernel and enc_csite_kernel have in common (bags >= 16 reads).
+//
+// enc_kernel walks the CSR array per lane with 64-bit indices (vector loads of off[], three k-mer byte loads and three LDS
+// reads per lane, 64-bit clamps on the VALU -- the datapath the f32 MFMAs use); here a 32-read tile spans at most three sites, so
+//   link0  off[a+1..a+3] come through scalar loads (constant address space), tile and site indices are 32-bit SALU values;
+//   link1  the lane's site is `rel` = 0, 1, 2 relative to the wave-uniform base, by two 32-bit compares; lanes 0..17 fetch
+//          ONE k-mer id byte each (float q of site a + q/6 is E[kmer (q%6)/2][q&1]), THEN the x loads (4 per lane, + x8 on
+//          half 0) -- vector loads retire in order, the k-mer ids must not queue behind the x stream;
+//   link2  the embedding float, one LDS read per lane;
+//   link3  is each kernel's own: how the 18 floats of lanes 0..17 reach the lanes that need them.
+// Tile and site indices are 32-bit here (the host sends jobs beyond 2^31 sites or tiles to enc_kernel) and wave-uniform: the
+// SALU has 32-bit ordered compares but no 64-bit ones, so 64-bit indices would put every clamp and loop test on the VALU -- at
+// half rate, on the datapath the MFMAs need.  A tile that would need a fourth site raises the error flag (the host launches
+// these kernels only when the smallest bag has >= 16 reads and the job fits 32-bit indices; enc_kernel stays the path for
+// everything else).
+// =====================================================================================
+struct ScalarChain {
+    const EncArgs &a;
+    const float *s_emb;
+    // (through the constant address space: the kernels also store to global memory, and without it the compiler issues
+    // link0's uniform loads as vector loads -- three more VMEM instructions in the MFMA stream per tile)
+    const __attribute__((address_space(4))) int64_t *off_c;
+    int lane, col, half, wave;
+    int n_tiles, tile0, tile1, n_sites, last_site;
+    int last_lim;                                            // last valid column of the last tile
+    int kq_site, kq_byte;
+    int too_small = 0;                                       // wave-uniform
 
-    int s_base;
+    __device__ __forceinline__ ScalarChain(const EncArgs &args, const float *emb)
+        : a(args), s_emb(emb), off_c((const __attribute__((address_space(4))) int64_t *)args.off)
     {
-        const int64_t r = (int64_t)tile0 * 32;
-        int lo = 0, hi = n_sites;                // invariant: off[lo] <= r < off[hi]
-        while (hi - lo > 1) {
-            const int mid = (int)(((int64_t)lo + hi) >> 1);
-            if (a.off[mid] <= r) lo = mid; else hi = mid;
-        }
-        s_base = lo;
+        lane = threadIdx.x & 63;
+        col = lane & 31;
+        half = lane >> 5;
+        wave = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        n_tiles = (int)a.n_tiles;
+        const int tpw = (int)a.tiles_per_wave;
+        tile0 = wave * tpw;
+        tile1 = (tile0 + tpw < n_tiles) ? tile0 + tpw : n_tiles;
+        n_sites = (int)a.n_sites;
+        last_site = n_sites - 1;
+        last_lim = (int)(a.n_reads - 1 - (int64_t)(n_tiles - 1) * 32);
+        const int kq = lane < 18 ? lane : 17;                // every lane loads a valid byte: no merge
+        kq_site = kq / 6;
+        kq_byte = (kq % 6) / 2;
     }
-    const int last_site = n_sites - 1;
-
-    const __attribute__((address_space(4))) int64_t *off_c = (const __attribute__((address_space(4))) int64_t *)a.off;
-    auto link0 = [&](int base, int64_t (&o)[3]) {
+    // last valid column of a tile
+    __device__ __forceinline__ int lim(int tile) const { return tile == n_tiles - 1 ? last_lim : 31; }
+    // site of the wave's first read
+    __device__ __forceinline__ int start() const { return __builtin_amdgcn_readfirstlane(first_site<int>(a.off, n_sites, (int64_t)tile0 * 32)); }
+    // link0: the three CSR offsets after the base site -- scalar loads (base is uniform)
+    __device__ __forceinline__ void link0(int base, int64_t (&o)[3]) const
+    {
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             const int si = base + 1 + i;
             o[i] = off_c[si <= n_sites ? si : n_sites];
         }
-    };
-    const int kq = lane < 18 ? lane : 17;                    // every lane loads a valid byte: no merge
-    const int kq_site = kq / 6, kq_byte = (kq % 6) / 2;
-    int too_small = 0;                                       // wave-uniform
-    auto link1 = [&](int tile, int base, const int64_t (&o)[3], int &rel, int &kid, float (&x)[8]) {
+    }
+    // link1: x[0..3] = the lane's x0/x1, x2/x3, x4/x5, x6/x7 (half 0 / half 1), x[4] = x8 on half 0 (half 1: x7, a valid dummy)
+    template <int N> __device__ __forceinline__ void link1(int tile, int base, const int64_t (&o)[3], int &rel, int &kid, float (&x)[N])
+    {
         const int64_t rbase = (int64_t)tile * 32;                                 // uniform
-        const int lim = tile == n_tiles - 1 ? last_lim : 31;                      // last valid column of this tile
-        const int crel = col < lim ? col : lim;                                   // the lane's read, clamped into the job
+        const int crel = col < lim(tile) ? col : lim(tile);                       // the lane's read, clamped into the job
+        // site boundaries relative to the tile: o[i] > rbase (base holds the tile's first read) and a bag is
+        // far smaller than 2^31 reads, so the low words are enough
         const int d0 = (int)o[0] - (int)rbase, d1 = (int)o[1] - (int)rbase, d2 = (int)o[2] - (int)rbase;
         rel = (crel >= d0 ? 1 : 0) + (crel >= d1 ? 1 : 0);
-        too_small |= lim >= d2 ? 1 : 0;
+        // a lane beyond the third site boundary would need a 4th site (precondition broken): the tile's last column is
+        // the largest crel, so the test is scalar; the flag is raised once, after the tile loop
+        too_small |= lim(tile) >= d2 ? 1 : 0;
         const int room = last_site - base;                                        // sites after the base site
         const int ksr = kq_site < room ? kq_site : room;
         kid = (int)(a.site_kmers + (int64_t)base * 3)[__umul24((unsigned)ksr, 3u) + (unsigned)kq_byte];      // scalar base + unsigned 32-bit lane offset (see the x loads)
-        // K slot 2i + half holds feature 2i + half, as in enc_kernel
+        // K slot 2i + half holds feature 2i + half, as in enc_kernel: the features enter the sum in the order the reference's
+        // dot product has them.  (One 16-byte load per lane -- half 0 x0..x3, half 1 x4..x7, weights permuted to match -- is
+        // the same speed and moves the summation order away from the reference's: in the 12-slot kernel the worst use of the
+        // rtol 1e-5 bar over 10 M reads rose from 0.81 to 0.89 on the arabidopsis weights, 0.936 to 0.951 on HEK293T.)
         // the tile's base is wave-uniform and the lane's part fits 32 unsigned bits: global_load ... v_off, s[base] offset:imm -- no 64-bit
         // address arithmetic on the VALU (a signed lane offset made hipcc form every address with v_mad_u64_u32 / v_lshl_add_u64, quarter-
         // and half-rate instructions on the datapath the MFMAs use)
@@ -497,10 +626,43 @@ __global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
 #pragma unroll
         for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
         x[4] = *(const float *)((const char *)xt + (unsigned)(4 * (crel * 9 + (half ? 7 : 8))));
-    };
-    auto link2 = [&](int kid, float &ev) { ev = s_emb[2 * kid + (lane & 1)]; };
+    }
+    // link2: the embedding float itself
+    __device__ __forceinline__ void link2(int kid, float &ev) const { ev = s_emb[2 * kid + (lane & 1)]; }
+    // the next tile's base site: the site of this tile's last read
+    __device__ __forceinline__ int advance(int rel) const { return __builtin_amdgcn_readfirstlane(__shfl(rel, 31, 64)); }
+    __device__ __forceinline__ void raise_too_small() const
+    {
+        if (too_small && lane == 0) atomicExch(a.err, 2);
+    }
+};
+
+// =====================================================================================
+// Read encoder, 16 slots, bags >= 16 reads: enc_kernel's arithmetic behind the scalar chain.
+//
+// Every float32 operation is enc_kernel's (same fragments, same K-slot wiring, same epilogue: the reference's bits); what
+// differs is how a lane finds its site and its six embedding floats: links 0..2 of the scalar chain above, and
+//   link3  three ds_bpermute (LDS crossbar, not the VALU) hand every lane its site's floats: half 0 the odd ones
+//          (e1, e3, e5: K slots 5..7), half 1 the even ones (e0, e2, e4: slots 4..6) and the constant 1.
+// =====================================================================================
+__global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
+{
+    clamp_keeps_nan();
+    m6a_clk_stamp(a.clk, 0);
+    __shared__ EncLds lds;
+    stage_lds(lds, a);
+    __syncthreads();
+
+    ScalarChain sc(a, lds.emb);
+    const int lane = sc.lane, col = sc.col, half = sc.half, tile0 = sc.tile0, tile1 = sc.tile1;
+    const float *bn_half = lds.bn + half * 32;
+    if (tile0 >= sc.n_tiles) return;
+
+    float w1[40], w2[80], w3[16];
+    load_frags16(a.wfrag, lane, w1, w2, w3);
+
     // lanes 0..17 hold float q % 6 of site a + q / 6; a lane of half h wants floats (1 - h), (1 - h) + 2, (1 - h) + 4 of
-    // site a + rel.  (A site beyond the job's last -- `room` above -- is never selected: rel counts real boundaries.)
+    // site a + rel.  (A site beyond the job's last -- `room` in link1 -- is never selected: rel counts real boundaries.)
     auto link3 = [&](float ev, int rel, float (&x)[8]) {
         const int ebits = __builtin_bit_cast(int, ev);
         const int addr = 4 * (rel * 6 + 1 - half);
@@ -515,16 +677,16 @@ __global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
 
     // prologue: first tile, unpipelined
     float f[8];
-    s_base = __builtin_amdgcn_readfirstlane(s_base);
+    int s_base = sc.start();
     {
         int64_t o[3];
         int rel, kid;
         float ev;
-        link0(s_base, o);
-        link1(tile0, s_base, o, rel, kid, f);
-        link2(kid, ev);
+        sc.link0(s_base, o);
+        sc.link1(tile0, s_base, o, rel, kid, f);
+        sc.link2(kid, ev);
         link3(ev, rel, f);
-        s_base += __builtin_amdgcn_readfirstlane(__shfl(rel, 31, 64));
+        s_base += sc.advance(rel);
     }
 
     BnPairs bnq;
@@ -535,48 +697,25 @@ __global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
         float fn[8], evn;
         int64_t o[3];
         int reln, kidn;
-        link0(s_base, o);
+        sc.link0(s_base, o);
         tile_body_priority();
 
-        f32x16 acc2, h1a, h1b;
-#pragma unroll
-        for (int q = 0; q < 16; q++) { acc2[q] = 0.0f; h1a[q] = 0.0f; }
-#pragma unroll
-        for (int st = 0; st < 8; st++)
-            h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < 5; m++) {
-            f32x16 &cur = (m & 1) ? h1b : h1a;
-            f32x16 &nxt = (m & 1) ? h1a : h1b;
-            if (m < 4) {
-#pragma unroll
-                for (int q = 0; q < 16; q++) nxt[q] = 0.0f;
-#pragma unroll
-                for (int st = 0; st < 8; st++)
-                    nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(m + 1) * 8 + st], f[st], nxt, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+        f32x16 acc2;
+        unit_tile_loop(acc2, w2, bnq, bn_half, [&](int m, f32x16 &acc) { layer1_16(m, acc, w1, f); }, [&](int m) {
             // where the three links of the next tile's input chain sit: behind the layer-1 MFMAs of unit tiles 2, 3 and 4 (round 6; rounds 2-6a: 1, 2 and 4 --
             // m = 0, 1, 3 here).  Measured over two runs of interleaved legs (profiles/r06_encoder_ab_schedule.json, r06_encoder_ab_links.json): -0.5 %;
             // 0/1/4, 2/3/4, 1/3/4: +-0.2 %; 0/2/3, 0/2/4, 0/3/4: +0.4 .. +1.3 %.
-            if (m == 1) link1(tn, s_base, o, reln, kidn, fn);
-            if (m == 2) link2(kidn, evn);
+            if (m == 1) sc.link1(tn, s_base, o, reln, kidn, fn);
+            if (m == 2) sc.link2(kidn, evn);
             if (m == 3) link3(evn, reln, fn);
-            if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
-            if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
-            if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
-            if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
-            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
-        }
+        });
         tile_epilogue_priority();
-        const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;
-        const float p = 1.0f / (1.0f + sleef_expf_u10(-z));
-        if (half == 0 && col <= (tile == n_tiles - 1 ? last_lim : 31)) (a.read_prob + (int64_t)tile * 32)[col] = p;
-        if (tn != tile) s_base += __builtin_amdgcn_readfirstlane(__shfl(reln, 31, 64));
+        store_prob_as_reference(acc2, w3, half, a.b3, col <= sc.lim(tile), a.read_prob + (int64_t)tile * 32 + col);
+        if (tn != tile) s_base += sc.advance(reln);
 #pragma unroll
         for (int i = 0; i < 8; i++) f[i] = fn[i];
     }
-    if (too_small && lane == 0) atomicExch(a.err, 2);
+    sc.raise_too_small();
     m6a_clk_stamp(a.clk, 1);
 }
 
@@ -599,106 +738,33 @@ __global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)
 // (x, y) pairs over the LDS crossbar with ds_bpermute (not a VALU instruction), and folded against
 // W1[:, 9..14] (kept in LDS, one row per lane) with 30 v_pk_fma_f32 -- two site vectors per FMA.
 // Lane halves: h=0 supplies slots x0,x2,x4,x6,x8,I(a+1); h=1 supplies x1,x3,x5,x7,I(a),I(a+2).
-// Everything else (layer 2, ReLU batching, ping-pong, epilogue, input prefetch chain) is as in
-// enc_kernel.  A tile that would need a fourth site raises the error flag (the host only
-// launches this kernel when the smallest bag has >= 16 reads).
+// Everything else (layer 2, ReLU batching, ping-pong, the scalar chain's links 0..2) is shared with the
+// kernels above; the 32 -> 1 sum is a plain one.
 // =====================================================================================
 __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
 {
     clamp_keeps_nan();
     m6a_clk_stamp(a.clk, 0);
-    __shared__ float s_emb[132];
+    __shared__ EncLds lds;
     __shared__ float s_w1e[35 * 32];             // [m*7 + e][col]: W1[u][9+e] (e<6), b1[u] (e=6), u = the unit of row col of tile m
-    for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
+    stage_lds(lds, a);
     for (int i = threadIdx.x; i < 35 * 32; i += 256) s_w1e[i] = a.w1e_tab[i];
-    __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
     // W3 in the order the layer-2 accumulator holds the 32 units: [half][q] (16 VGPRs the tile loop needs more)
     __shared__ float s_w3[32];
     if (threadIdx.x < 64) s_w3[(threadIdx.x >> 5) * 16 + (threadIdx.x & 15)] = a.wfrag[(120 + (threadIdx.x & 15)) * 64 + (threadIdx.x & 32)];
     __syncthreads();
 
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 31;
-    const int half = lane >> 5;
-    const float *bn_half = s_bn + half * 32;
-    // Tile and site indices are 32-bit here (the host sends jobs beyond 2^31 sites or tiles to enc_kernel)
-    // and wave-uniform: the SALU has 32-bit ordered compares but no 64-bit ones, so 64-bit indices would put
-    // every clamp and loop test on the VALU -- at half rate, on the datapath the MFMAs need.
-    const int wave = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int n_tiles = (int)a.n_tiles, tpw = (int)a.tiles_per_wave;
-    const int tile0 = wave * tpw;
-    if (tile0 >= n_tiles) return;
-    const int tile1 = (tile0 + tpw < n_tiles) ? tile0 + tpw : n_tiles;
-    const int n_sites = (int)a.n_sites;
-    const int last_lim = (int)(a.n_reads - 1 - (int64_t)(n_tiles - 1) * 32);   // last valid column of the last tile
+    ScalarChain sc(a, lds.emb);
+    const int lane = sc.lane, col = sc.col, half = sc.half, tile0 = sc.tile0, tile1 = sc.tile1;
+    const float *bn_half = lds.bn + half * 32;
+    if (tile0 >= sc.n_tiles) return;
 
     // static weight fragments: w1x[m*4+st] = W1[u][2st+half], w8[m] = W1[u][8], u = the unit of row col of tile m
     float w1x[20], w8[5], w2[80];
-#pragma unroll
-    for (int i = 0; i < 20; i++) w1x[i] = a.wfrag2[i * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 5; i++) w8[i] = a.wfrag2[(20 + i) * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 80; i++) w2[i] = a.wfrag[(40 + i) * 64 + lane];
+    load_frag(w1x, a.wfrag2, lane);
+    load_frag(w8, a.wfrag2 + 20 * 64, lane);
+    load_frag(w2, a.wfrag + 40 * 64, lane);
 
-    int s_base;
-    {
-        const int64_t r = (int64_t)tile0 * 32;
-        int lo = 0, hi = n_sites;                // invariant: off[lo] <= r < off[hi]
-        while (hi - lo > 1) {
-            const int mid = (int)(((int64_t)lo + hi) >> 1);
-            if (a.off[mid] <= r) lo = mid; else hi = mid;
-        }
-        s_base = lo;
-    }
-    const int last_site = n_sites - 1;
-
-    // ---- input chain of one tile ----------------------------------------------------------------
-    // link0: the three CSR offsets after the base site -- scalar loads (base is uniform)
-    // (through the constant address space: the kernel also stores to global memory, and without it the compiler issues
-    // these uniform loads as vector loads -- three more VMEM instructions in the MFMA stream per tile)
-    const __attribute__((address_space(4))) int64_t *off_c = (const __attribute__((address_space(4))) int64_t *)a.off;
-    auto link0 = [&](int base, int64_t (&o)[3]) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int si = base + 1 + i;
-            o[i] = off_c[si <= n_sites ? si : n_sites];
-        }
-    };
-    // link1: the lane's site relative to base; lanes 0..17 fetch the k-mer id their embedding
-    // float belongs to (float q of site base + q/6 is E[kmer (q%6)/2][q&1]); THEN the x loads
-    // (4 per lane, + x8 on half 0) -- vector loads retire in order, the k-mer ids must not queue
-    // behind the x stream
-    const int kq = lane < 18 ? lane : 17;                    // every lane loads a valid byte: no merge
-    const int kq_site = kq / 6, kq_byte = (kq % 6) / 2;
-    int too_small = 0;                                       // wave-uniform
-    auto link1 = [&](int tile, int base, const int64_t (&o)[3], int &rel, int &kid, float (&x)[5]) {
-        const int64_t rbase = (int64_t)tile * 32;                                 // uniform
-        const int lim = tile == n_tiles - 1 ? last_lim : 31;                      // last valid column of this tile
-        const int crel = col < lim ? col : lim;                                   // the lane's read, clamped into the job
-        // site boundaries relative to the tile: o[i] > rbase (base holds the tile's first read) and a bag is
-        // far smaller than 2^31 reads, so the low words are enough
-        const int d0 = (int)o[0] - (int)rbase, d1 = (int)o[1] - (int)rbase, d2 = (int)o[2] - (int)rbase;
-        rel = (crel >= d0 ? 1 : 0) + (crel >= d1 ? 1 : 0);
-        // a lane beyond the third site boundary would need a 4th site (precondition broken): the tile's last column is
-        // the largest crel, so the test is scalar; the flag is raised once, after the tile loop
-        too_small |= lim >= d2 ? 1 : 0;
-        const int room = last_site - base;                                        // sites after the base site
-        const int ksr = kq_site < room ? kq_site : room;
-        kid = (int)(a.site_kmers + (int64_t)base * 3)[__umul24((unsigned)ksr, 3u) + (unsigned)kq_byte];      // scalar base + unsigned 32-bit lane offset (see the x loads)
-        // K slot 2st+half holds feature 2st+half: the features enter the sum in the order the reference's dot product
-        // has them.  (One 16-byte load per lane -- half 0 x0..x3, half 1 x4..x7, weights permuted to match -- is the
-        // same speed and moves the summation order away from the reference's: the worst use of the rtol 1e-5 bar over
-        // 10 M reads rose from 0.81 to 0.89 on the arabidopsis weights, 0.936 to 0.951 on HEK293T.)
-        const float *xt = a.X + rbase * 9;                   // scalar base + unsigned 32-bit lane offset, as in enc_site16_kernel
-        const float *xp = (const float *)((const char *)xt + (unsigned)(4 * (crel * 9 + half)));
-#pragma unroll
-        for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
-        x[4] = *(const float *)((const char *)xt + (unsigned)(4 * (crel * 9 + (half ? 7 : 8))));      // x8 on half 0 (half 1: a valid dummy)
-    };
-    // link2: the embedding float itself
-    auto link2 = [&](int kid, float &ev) { ev = s_emb[2 * kid + (lane & 1)]; };
     // link3: c vectors -> A operands of the two indicator steps, indicator B operands
     // (x8 is the value loaded for slot 4 on half 0; in place: a4/a5/x[4..5] of the running tile are
     // dead once layer 1 of its last unit tile has issued)
@@ -737,18 +803,18 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
 
     // prologue: first tile, unpipelined
     float f[6], a4[5], a5[5];
-    s_base = __builtin_amdgcn_readfirstlane(s_base);
+    int s_base = sc.start();
     {
         int64_t o[3];
         int rel, kid;
         float ev, x5[5];
-        link0(s_base, o);
-        link1(tile0, s_base, o, rel, kid, x5);
+        sc.link0(s_base, o);
+        sc.link1(tile0, s_base, o, rel, kid, x5);
 #pragma unroll
         for (int i = 0; i < 4; i++) f[i] = x5[i];
-        link2(kid, ev);
+        sc.link2(kid, ev);
         link3(ev, rel, x5[4], f, a4, a5);
-        s_base += __builtin_amdgcn_readfirstlane(__shfl(rel, 31, 64));
+        s_base += sc.advance(rel);
     }
 
     BnPairs bnq;
@@ -759,9 +825,10 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
         float fn[5], evn;
         int64_t o[3];
         int reln, kidn;
-        link0(s_base, o);
+        sc.link0(s_base, o);
         tile_body_priority();
 
+        // the 6-step layer 1: four x steps, then the two steps link3 builds
         auto layer1 = [&](int m, f32x16 &acc) {
 #pragma unroll
             for (int q = 0; q < 16; q++) acc[q] = 0.0f;
@@ -771,26 +838,12 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m], f[4], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a5[m], f[5], acc, 0, 0, 0);
         };
-
-        f32x16 acc2, h1a, h1b;
-#pragma unroll
-        for (int q = 0; q < 16; q++) acc2[q] = 0.0f;
-        layer1(0, h1a);
-#pragma unroll
-        for (int m = 0; m < 5; m++) {
-            f32x16 &cur = (m & 1) ? h1b : h1a;
-            f32x16 &nxt = (m & 1) ? h1a : h1b;
-            if (m < 4) layer1(m + 1, nxt);
-            __builtin_amdgcn_sched_barrier(0);
-            if (m == 0) link1(tn, s_base, o, reln, kidn, fn);
-            if (m == 1) link2(kidn, evn);
+        f32x16 acc2;
+        unit_tile_loop(acc2, w2, bnq, bn_half, layer1, [&](int m) {
+            if (m == 0) sc.link1(tn, s_base, o, reln, kidn, fn);
+            if (m == 1) sc.link2(kidn, evn);
             if (m == 3) link3(evn, reln, fn[4], f, a4, a5);             // layer1(4) has issued: in place
-            if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
-            if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
-            if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
-            if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
-            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
-        }
+        });
         tile_epilogue_priority();
         float z = 0.0f;
 #pragma unroll
@@ -798,12 +851,12 @@ __global__ __launch_bounds__(256, 2) void enc_csite_kernel(EncArgs a)
         z += __shfl_xor(z, 32, 64);
         z += a.b3;
         const float p = 1.0f / (1.0f + expf(-z));
-        if (half == 0 && col <= (tile == n_tiles - 1 ? last_lim : 31)) (a.read_prob + (int64_t)tile * 32)[col] = p;
-        if (tn != tile) s_base += __builtin_amdgcn_readfirstlane(__shfl(reln, 31, 64));
+        if (half == 0 && col <= sc.lim(tile)) (a.read_prob + (int64_t)tile * 32)[col] = p;
+        if (tn != tile) s_base += sc.advance(reln);
 #pragma unroll
         for (int i = 0; i < 4; i++) f[i] = fn[i];
     }
-    if (too_small && lane == 0) atomicExch(a.err, 2);
+    sc.raise_too_small();
     m6a_clk_stamp(a.clk, 1);
 }
 
@@ -1584,210 +1637,6 @@ __global__ __launch_bounds__(256) void bag_verify_kernel(const unsigned long lon
         if (got[0] != mn || got[1] != mx || got[2] != reads || h != hash) atomicExch(err, 3);
     }
 }
-
-// =====================================================================================
-// Read representation: enc_kernel that also stores layer 2 after its ReLU, the 32 floats per read the reference's
-// MILModel.get_read_representation returns (m6anet/model/model.py:85-97).
-//
-// Every float32 operation up to the probability is enc_kernel's (same fragments, same K-slot wiring, layer2_with_bn, the
-// per-lane walk of off[] that takes every bag size, the same epilogue); the body below is enc_kernel's, line for line, so
-// that the shipped kernels stay as they are.  What is new sits between the tile body and the epilogue: the store.
-//
-// Where the 32 outputs of a read are: register q of lane half 0 holds output unit 2q + 1, register q of half 1 unit 2q + 2,
-// and register 15 of half 1 unit 0 (m6a_api.hip build_fragments out_unit: the wiring gemv32_as_mkl wants).  The two lanes
-// of a read (lane, lane ^ 32) swap eight values -- half 0 gives away units 17, 19, .., 31 (registers 8..15) and gets units
-// 0, 2, .., 14; half 1 gives away register 15 and registers 0..6 -- after which half 0 holds units 0..15 and half 1 units
-// 16..31 in order: four 16-byte stores per lane, 64 contiguous bytes, repr[r][16 half .. 16 half + 16).  The exchange is
-// executed by all lanes; only the stores are guarded (the last tile is partial, its spare lanes compute on a clamped read).
-// relu is the oracle's a < 0 ? 0 : a on the accumulator itself (keeps NaN, as torch's does), not relu2's doubled value.
-// read_prob may be null: the epilogue is then skipped (wave-uniform).
-//
-// The kernel is a template over the output type with two instantiations.  enc_repr_kernel<false> (float32) is the kernel as it was:
-// the same arithmetic, the same four stores.  enc_repr_kernel<true> stores IEEE binary16: after the same swap the lane's 16 values
-// are converted, each from the float32 value the other kernel stores, and leave as 32 contiguous bytes, two guarded 16-byte
-// stores, repr[r][16 half .. 16 half + 16) of a [R][32] binary16 array.  The conversion is v_cvt_f16_f32 under the mode the
-// build gives every kernel here: round to nearest even, float_denorm_mode_32 = 3 and float_denorm_mode_16_64 = 3 (the kernel
-// descriptor's defaults; clamp_keeps_nan touches DX10_CLAMP alone), so a float32 subnormal is read as it is and a result in
-// the binary16 subnormal range is produced, not flushed; FP16_OVFL is clear, so what rounds above 65504 is +inf; a NaN stays
-// a NaN with the top bits of its payload.  That is np.float32(v).astype(np.float16) on every value this kernel can produce.
-// =====================================================================================
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t f16_pair(float lo, float hi)
-{
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
-template <bool F16> __global__ __launch_bounds__(256, 2) void enc_repr_kernel(EncReprArgs ra)
-{
-    const EncArgs a = ra.enc;
-    clamp_keeps_nan();
-    __shared__ float s_emb[132];
-    __shared__ __attribute__((aligned(16))) float s_bn[M6A_BN_FLOATS];
-    for (int i = threadIdx.x; i < 132; i += 256) s_emb[i] = a.emb[i];
-    for (int i = threadIdx.x; i < M6A_BN_FLOATS; i += 256) s_bn[i] = a.bn[i];
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 31;
-    const int half = lane >> 5;
-    const float *bn_half = s_bn + half * 32;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t tile0 = wave * a.tiles_per_wave;
-    if (tile0 >= a.n_tiles) return;
-    const int64_t tile1 = (tile0 + a.tiles_per_wave < a.n_tiles) ? tile0 + a.tiles_per_wave : a.n_tiles;
-
-    float w1[40], w2[80], w3[16];
-#pragma unroll
-    for (int i = 0; i < 40; i++) w1[i] = a.wfrag[i * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 80; i++) w2[i] = a.wfrag[(40 + i) * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < 16; i++) w3[i] = a.wfrag[(120 + i) * 64 + lane];
-
-    int64_t s_base;
-    {
-        const int64_t r = tile0 * 32;
-        int64_t lo = 0, hi = a.n_sites;          // invariant: off[lo] <= r < off[hi]
-        while (hi - lo > 1) {
-            int64_t mid = (lo + hi) >> 1;
-            if (a.off[mid] <= r) lo = mid; else hi = mid;
-        }
-        s_base = lo;
-    }
-    const int64_t last_site = a.n_sites - 1;
-
-    // the three links of the input chain, as in enc_kernel
-    auto link0 = [&](int64_t base, int64_t (&o)[3]) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int64_t si = base + 1 + i;
-            o[i] = a.off[si <= a.n_sites ? si : a.n_sites];
-        }
-    };
-    auto link1 = [&](int64_t tile, int64_t base, const int64_t (&o)[3], int64_t &s, int (&km)[3], float (&x)[8]) {
-        const int64_t r = tile * 32 + col;
-        const int64_t rc = r < a.n_reads ? r : a.n_reads - 1;
-        s = base + (rc >= o[0] ? 1 : 0) + (rc >= o[1] ? 1 : 0);
-        if (__any(rc >= o[2])) {                 // bags smaller than 16 reads: walk
-            s = base;
-            while (a.off[s + 1] <= rc) ++s;
-        }
-        s = s < last_site ? s : last_site;
-        const uint8_t *kp = a.site_kmers + s * 3;
-        km[0] = kp[0]; km[1] = kp[1]; km[2] = kp[2];
-        const float *xp = a.X + rc * 9 + half;
-#pragma unroll
-        for (int i = 0; i < 4; i++) x[i] = xp[2 * i];
-        x[4] = xp[half ? 6 : 8];
-    };
-    auto link2 = [&](const int (&km)[3], float (&x)[8]) {
-        const float e0 = s_emb[2 * km[0] + 1 - half], e1 = s_emb[2 * km[1] + 1 - half], e2 = s_emb[2 * km[2] + 1 - half];
-        x[4] = half ? e0 : x[4];
-        x[5] = half ? e1 : e0;
-        x[6] = half ? e2 : e1;
-        x[7] = half ? 1.0f : e2;
-    };
-
-    float f[8];
-    s_base = uniform_i64(s_base);
-    {
-        int64_t o[3], s;
-        int km[3];
-        link0(s_base, o);
-        link1(tile0, s_base, o, s, km, f);
-        link2(km, f);
-        s_base = uniform_i64(__shfl(s, 31, 64));
-    }
-
-    BnPairs bnq;
-    bn_pairs_load(bnq, bn_half);
-    for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t tn = tile + 1 < tile1 ? tile + 1 : tile;
-        float fn[8];
-        int64_t o[3], sn;
-        int km[3];
-        link0(s_base, o);
-        tile_body_priority();
-
-        f32x16 acc2, h1a, h1b;
-#pragma unroll
-        for (int q = 0; q < 16; q++) { acc2[q] = 0.0f; h1a[q] = 0.0f; }
-#pragma unroll
-        for (int st = 0; st < 8; st++)
-            h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < 5; m++) {
-            f32x16 &cur = (m & 1) ? h1b : h1a;
-            f32x16 &nxt = (m & 1) ? h1a : h1b;
-            if (m < 4) {
-#pragma unroll
-                for (int q = 0; q < 16; q++) nxt[q] = 0.0f;
-#pragma unroll
-                for (int st = 0; st < 8; st++)
-                    nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(m + 1) * 8 + st], f[st], nxt, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (m == 0) link1(tn, s_base, o, sn, km, fn);
-            if (m == 2) link2(km, fn);
-            if (m == 0) layer2_with_bn<0>(acc2, cur, w2, bnq, bn_half);
-            if (m == 1) layer2_with_bn<1>(acc2, cur, w2, bnq, bn_half);
-            if (m == 2) layer2_with_bn<2>(acc2, cur, w2, bnq, bn_half);
-            if (m == 3) layer2_with_bn<3>(acc2, cur, w2, bnq, bn_half);
-            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);
-        }
-        tile_epilogue_priority();
-        const int64_t r = tile * 32 + col;
-        {
-            float h[16], got[8];
-#pragma unroll
-            for (int q = 0; q < 16; q++) h[q] = acc2[q] < 0.0f ? 0.0f : acc2[q];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                float give = half ? h[(i + 15) & 15] : h[8 + i];
-                got[i] = __shfl_xor(give, 32, 64);                    // all lanes: the guard is on the stores
-            }
-            float4 v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                v[j].x = half ? h[7 + 2 * j] : got[2 * j];
-                v[j].y = half ? got[2 * j] : h[2 * j];
-                v[j].z = half ? h[8 + 2 * j] : got[2 * j + 1];
-                v[j].w = half ? got[2 * j + 1] : h[2 * j + 1];
-            }
-            if constexpr (F16) {
-                uint4 w[2];
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    w[j].x = f16_pair(v[2 * j].x, v[2 * j].y);
-                    w[j].y = f16_pair(v[2 * j].z, v[2 * j].w);
-                    w[j].z = f16_pair(v[2 * j + 1].x, v[2 * j + 1].y);
-                    w[j].w = f16_pair(v[2 * j + 1].z, v[2 * j + 1].w);
-                }
-                if (r < a.n_reads) {
-                    uint4 *dst = (uint4 *)((uint16_t *)ra.repr + r * 32 + half * 16);
-                    dst[0] = w[0];
-                    dst[1] = w[1];
-                }
-            } else if (r < a.n_reads) {
-                float4 *dst = (float4 *)((float *)ra.repr + r * 32 + half * 16);
-#pragma unroll
-                for (int j = 0; j < 4; j++) dst[j] = v[j];
-            }
-        }
-        if (a.read_prob) {                                            // kernel argument: wave-uniform
-            const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;
-            const float p = 1.0f / (1.0f + sleef_expf_u10(-z));
-            if (half == 0 && r < a.n_reads) a.read_prob[r] = p;
-        }
-        if (tn != tile) s_base = uniform_i64(__shfl(sn, 31, 64));
-#pragma unroll
-        for (int i = 0; i < 8; i++) f[i] = fn[i];
-    }
-}
-
-template __global__ void enc_repr_kernel<false>(EncReprArgs ra);
-template __global__ void enc_repr_kernel<true>(EncReprArgs ra);
 
 // An empty kernel per translation unit: HIP maps a code object on the first launch of any kernel in it (0.3-1.2 ms, measured
 // in the first call's timeline, profiles/r03_first_call_timeline.txt); m6a_create's background set-up launches these instead.

@@ -35,17 +35,25 @@ import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from variant_build import KO, REPO, build, swap
+from variant_build import KO, REPO, build, swap, within
 
 sys.path.insert(0, REPO)
 
 
+SITE16 = "__global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)\n"
+
+
+def in_site16(s, fn):
+    """fn applied to the text of enc_site16_kernel alone: the pieces it shares with the other encoder kernels are out of reach."""
+    return within(s, SITE16, "\n}\n", fn)
+
+
 def links(a, b, c):
-    def f(s):
-        s = swap(s, "if (m == 1) link1(tn, s_base, o, reln, kidn, fn);", "if (m == %d) link1(tn, s_base, o, reln, kidn, fn);" % a)
-        s = swap(s, "if (m == 2) link2(kidn, evn);", "if (m == %d) link2(kidn, evn);" % b)
-        return swap(s, "if (m == 3) link3(evn, reln, fn);", "if (m == %d) link3(evn, reln, fn);" % c)
-    return f
+    def f(k):
+        k = swap(k, "if (m == 1) sc.link1(tn, s_base, o, reln, kidn, fn);", "if (m == %d) sc.link1(tn, s_base, o, reln, kidn, fn);" % a)
+        k = swap(k, "if (m == 2) sc.link2(kidn, evn);", "if (m == %d) sc.link2(kidn, evn);" % b)
+        return swap(k, "if (m == 3) link3(evn, reln, fn);", "if (m == %d) link3(evn, reln, fn);" % c)
+    return lambda s: in_site16(s, f)
 
 
 def prio(body, epi):
@@ -66,11 +74,11 @@ def bn_block(n):
 
 
 def no_epilogue(s):
-    """WRONG RESULTS by construction, timing only: enc_site16_kernel stores a sum of two accumulators instead of the probability."""
-    return swap(s, "        const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;\n        const float p = 1.0f / (1.0f + sleef_expf_u10(-z));\n"
-                   "        if (half == 0 && col <= (tile == n_tiles - 1 ? last_lim : 31)) (a.read_prob",
-                "        const float p = (acc2[0] + acc2[5]) + w3[0];      // knock-out: WRONG results\n"
-                "        if (half == 0 && col <= (tile == n_tiles - 1 ? last_lim : 31)) (a.read_prob")
+    """WRONG RESULTS by construction, timing only: enc_site16_kernel stores a sum of two accumulators instead of the probability
+    (its call of the shared epilogue is replaced; the epilogue itself, which enc_kernel and enc_repr_kernel use too, stays)."""
+    return in_site16(s, lambda k: swap(k, "        store_prob_as_reference(acc2, w3, half, a.b3, col <= sc.lim(tile), a.read_prob + (int64_t)tile * 32 + col);\n",
+                                       "        const float p = (acc2[0] + acc2[5]) + w3[0];      // knock-out: WRONG results\n"
+                                       "        if (half == 0 && col <= sc.lim(tile)) (a.read_prob + (int64_t)tile * 32)[col] = p;\n"))
 
 
 VARIANTS = {"base": lambda s: s, "no_prio": no_prio, "p01": prio(0, 1), "p13": prio(1, 3), "p23": prio(2, 3), "prio_body3_epi0": prio(3, 0),

@@ -2,7 +2,9 @@
 """Where a tile's wall time goes inside enc_site16_kernel, from the kernel's own clock: a diagnostic build (never the product) stamps
 s_memtime at ten points of 16 consecutive tiles of EVERY wave, with the wave's hardware slot, so the two waves that share a SIMD can
 be laid side by side.  The stamp buffer, its reader and the ten stamp points are not in m6a_kernels.hip: stamps() below inserts them
-into a copy (tools/variant_build.py), on top of encoder_ab.py's priority edits for stamps_noprio / stamps_body3_epi0.
+into a copy (tools/variant_build.py), on top of encoder_ab.py's priority edits for stamps_noprio / stamps_body3_epi0.  Six of the ten
+points lie inside unit_tile_loop and store_prob_as_reference, which enc_site16_kernel shares with the other encoder kernels: the copy
+gives those two a defaulted extra functor (a no-op for every other caller) and enc_site16_kernel passes the stamp.
 
     python tools/encoder_timeline.py --build     (here: cross-compiles tools/ko/libm6a_ab_stamps.so, which travels to the GPU box)
     python tools/encoder_timeline.py             (GPU box: one JSON object)
@@ -53,30 +55,41 @@ extern "C" int m6a_ab_read_stamps(unsigned long long *stamps, unsigned *hw)
 STAMP_STORE = """        M6A_STAMP(9);
         {
             const int k = tile - tile0 - %(FIRST)d;
-            if (k >= 0 && k < %(TILES)d && wave < %(MAXW)d && lane == 0) {
+            if (k >= 0 && k < %(TILES)d && sc.wave < %(MAXW)d && lane == 0) {
 #pragma unroll
-                for (int i = 0; i < %(POINTS)d; i++) m6a_ab_stamp_buf[wave][k][i] = ts[i];
+                for (int i = 0; i < %(POINTS)d; i++) m6a_ab_stamp_buf[sc.wave][k][i] = ts[i];
                 if (k == 0) {
-                    m6a_ab_stamp_hw[wave][0] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));       // HW_REG_HW_ID
-                    m6a_ab_stamp_hw[wave][1] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));      // HW_REG_XCC_ID
+                    m6a_ab_stamp_hw[sc.wave][0] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));       // HW_REG_HW_ID
+                    m6a_ab_stamp_hw[sc.wave][1] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));      // HW_REG_XCC_ID
                 }
             }
         }
 """ % {"TILES": TILES, "POINTS": POINTS, "FIRST": FIRST, "MAXW": MAXW}
 KERNEL = "__global__ __launch_bounds__(256, 2) void enc_site16_kernel(EncArgs a)\n"
+LOOP = "template <class Layer1, class Links>\n__device__ __forceinline__ void unit_tile_loop("
+EPILOGUE = "__device__ __forceinline__ void store_prob_as_reference("
+PASS_STAMP = ", [&](int k) { M6A_STAMP(k); });\n"
 
 
 def stamps(s):
     """The stamp buffer and its reader in front of enc_site16_kernel, the ten stamp points and the store into its tile loop."""
+    def hook(fn, *points):
+        """A shared piece calls stamp(k) behind each given line; stamp is a trailing functor that defaults to nothing."""
+        fn = swap(fn, ")\n{\n", ", Stamp &&stamp = Stamp())\n{\n")
+        for line, k in points:
+            fn = swap(fn, line, line + line[:len(line) - len(line.lstrip())] + "stamp(%s);\n" % k)
+        return fn
+    s = within(s, LOOP, "\n}\n", lambda fn: hook(fn, ("    layer1(0, h1a);\n", "1"), ("        if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);\n", "2 + m")))
+    s = swap(s, LOOP, "struct NoStamp { __device__ void operator()(int) const {} };\n" + LOOP.replace("class Links>", "class Links, class Stamp = NoStamp>"))
+    s = within(s, EPILOGUE, "\n}\n", lambda fn: hook(fn, ("    const float z = gemv32_as_mkl(acc2, w3, half) + b3;\n", "7")))
+    s = swap(s, EPILOGUE, "template <class Stamp = NoStamp> " + EPILOGUE)
+
     def tile_loop(k):
-        k = swap(k, "        int reln, kidn;\n        link0(s_base, o);\n", "        int reln, kidn;\n        unsigned long long ts[%d];\n        M6A_STAMP(0);\n        link0(s_base, o);\n" % POINTS)
-        for line, stamp in (("            h1a = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], f[st], h1a, 0, 0, 0);\n", "        M6A_STAMP(1);\n"),
-                            ("            if (m == 4) layer2_with_bn<4>(acc2, cur, w2, bnq, bn_half);\n", "            M6A_STAMP(2 + m);\n"),
-                            ("        const float z = gemv32_as_mkl(acc2, w3, half) + a.b3;\n", "        M6A_STAMP(7);\n"),
-                            ("(a.read_prob + (int64_t)tile * 32)[col] = p;\n", "        M6A_STAMP(8);\n"),
-                            ("        for (int i = 0; i < 8; i++) f[i] = fn[i];\n", STAMP_STORE)):
-            k = swap(k, line, line + stamp)
-        return k
+        k = swap(k, "        int reln, kidn;\n        sc.link0(s_base, o);\n", "        int reln, kidn;\n        unsigned long long ts[%d];\n        M6A_STAMP(0);\n        sc.link0(s_base, o);\n" % POINTS)
+        k = swap(k, "        });\n        tile_epilogue_priority();\n", "        }" + PASS_STAMP + "        tile_epilogue_priority();\n")          # stamps 1 .. 6
+        k = swap(k, "a.read_prob + (int64_t)tile * 32 + col);\n", "a.read_prob + (int64_t)tile * 32 + col" + PASS_STAMP + "        M6A_STAMP(8);\n")       # 7, 8
+        line = "        for (int i = 0; i < 8; i++) f[i] = fn[i];\n"
+        return swap(k, line, line + STAMP_STORE)
     s = within(s, KERNEL, "\n}\n", tile_loop)
     return swap(s, KERNEL, STAMP_STATE + KERNEL)
 

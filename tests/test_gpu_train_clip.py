@@ -60,13 +60,10 @@ def same_bits(a, b, keys=("loss", "grad", "blob")):
         assert a["state"]["m"].tobytes() == b["state"]["m"].tobytes() and a["state"]["v"].tobytes() == b["state"]["v"].tobytes()
 
 
-@pytest.mark.parametrize("weight_decay", [0.0, 1e-2])
-@pytest.mark.parametrize("B,bag", CT.SHAPES)
-def test_clipped_steps(eng, bundled, B, bag, weight_decay):
-    """Three steps at 0.25 T; with weight_decay, because clipping precedes the decay term."""
+def clipped_steps(eng, bundled, B, bag, weight_decay, seeds=CT.SEEDS):
     w = load_weights(HCT)
     e_ref, e_hip = [], []
-    for s in CT.SEEDS:
+    for s in seeds:
         batches = CT.case_batches(bundled, B, bag, s)
         max_norm = 0.25 * CT.first_norm(w, batches, weight_decay=weight_decay)
         CT.conditions(w, batches, max_norm, clipped=True, weight_decay=weight_decay)
@@ -78,6 +75,19 @@ def test_clipped_steps(eng, bundled, B, bag, weight_decay):
         e_ref.append(CT.errors(f32, f64))
         e_hip.append(CT.errors(got, f64))
     TT.hold("clipped %dx%d wd %g" % (B, bag, weight_decay), TT.pooled(e_ref), TT.pooled(e_hip))
+
+
+@pytest.mark.parametrize("weight_decay", [0.0, 1e-2])
+@pytest.mark.parametrize("B,bag", CT.SHAPES)
+def test_clipped_steps(eng, bundled, B, bag, weight_decay):
+    """Three steps at 0.25 T; with weight_decay, because clipping precedes the decay term."""
+    clipped_steps(eng, bundled, B, bag, weight_decay)
+
+
+def test_clipped_steps_beyond_one_tile_per_chunk(eng, bundled):
+    """8 240 reads: chunks of 64 reads, two tiles each, the last one a full tile and 16 reads (tests/train_regimes.py: chunking).
+    train_grad_kernel folds the same 129 parts train_adam_kernel folds with clipping off."""
+    clipped_steps(eng, bundled, 412, 20, 0.0)
 
 
 @pytest.mark.parametrize("B,bag", CT.SHAPES)

@@ -41,10 +41,13 @@ def trainable_mask():
     return m
 
 
-def step_gradient(w, X, kmers, y, bag, zero_sites=(), logits_only=False):
+def step_gradient(w, X, kmers, y, bag, zero_sites=(), logits_only=False, s_given=None):
     """-> (loss, y_pred [B], gradient in blob order with zeros in the running-statistic slots, the blob's new running statistics).
     zero_sites: sites whose dL/dlogit is set to zero (what a site with a saturated read contributes in float32).
-    logits_only: return the N logits instead."""
+    logits_only: return the N logits instead.
+    s_given [B]: the site probabilities a float32 subject produced.  The loss terms and dL/ds are evaluated at np.float64(s_given), so
+    1 - s is the exact float64 of the float32 value and the one rounding s = fl(1 - prod) is the subject's and the statement's alike;
+    p, the prefix and suffix products, the backward pass and the returned y_pred stay the statement's own."""
     p = unpack(np.asarray(w, np.float64))
     X = np.asarray(X, np.float64).reshape(-1, 9)
     kmers = np.asarray(kmers).reshape(-1, 3).astype(np.int64)
@@ -73,10 +76,11 @@ def step_gradient(w, X, kmers, y, bag, zero_sites=(), logits_only=False):
     for k in range(bag - 2, -1, -1):
         suf[:, k] = suf[:, k + 1] * q[:, k + 1]
     s = 1.0 - pre[:, -1] * q[:, -1]
+    sl = s if s_given is None else np.asarray(s_given).astype(np.float64).reshape(B)
     with np.errstate(divide="ignore"):
-        terms = -(y * np.maximum(np.log(s), -100.0) + (1.0 - y) * np.maximum(np.log(1.0 - s), -100.0))
+        terms = -(y * np.maximum(np.log(sl), -100.0) + (1.0 - y) * np.maximum(np.log(1.0 - sl), -100.0))
     loss = terms.mean()
-    dLds = (s - y) / np.maximum((1.0 - s) * s, 1e-12) / B
+    dLds = (sl - y) / np.maximum((1.0 - sl) * sl, 1e-12) / B
     dlogit = (dLds[:, None] * pre * suf).reshape(N) * pr * (1.0 - pr)
     for b in zero_sites:
         dlogit[b * bag:(b + 1) * bag] = 0.0
@@ -110,8 +114,8 @@ class Trainer:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.grad = np.zeros(N_FLOATS)
 
-    def step(self, X, kmers, y, bag, zero_sites=()):
-        loss, s, g, running = step_gradient(self.w, X, kmers, y, bag, zero_sites)
+    def step(self, X, kmers, y, bag, zero_sites=(), s_given=None):
+        loss, s, g, running = step_gradient(self.w, X, kmers, y, bag, zero_sites, s_given=s_given)
         self.grad = g
         for k, val in running.items():
             self.w[SLICES[k][0]] = val

@@ -966,6 +966,33 @@ int m6a_prep_sites_write_read_representation(m6a_prep_sites *p, m6a_ctx *ctx, co
  *   m6a_train_state_set  the inverse: on a trainer created from the blob m6a_train_weights gave, it makes the trainer that m, v and
  *                      t were taken from -- its next steps have that trainer's bits (the blob carries the running statistics).  The
  *                      running-statistic slots of m and v are stored as zeros.
+ *
+ * The step cut at s, for a caller that brings its own loss, sampler and optimizer (torch autograd: m6anet_amd/torch_model.py).
+ * train_fwd2_kernel needs one number per site from the loss, dL/ds_b; everything behind that number -- the head, layer 2, batch norm
+ * backward, the folds -- does not depend on which loss produced it.  So: forward returns s, backward takes dL/ds.
+ *   m6a_train_set_weights  blob: 7 997 floats, a host or a device pointer, copied into the trainer's own blob (the running statistics
+ *                      included); a device pointer is copied on the context's stream without a wait.  Adam's m, v and t are untouched.
+ *                      The trainer's copy is what forward AND backward read: a caller that changes its own parameters between the
+ *                      two still gets the gradient at the weights the forward ran on.  It ends the validity of an earlier ticket.
+ *   m6a_train_forward  the first half of m6a_train_step and nothing else: train_fwd1_kernel, train_stats_kernel, then layer 2, the
+ *                      head and the bag product (train_fwd2_kernel's forward instantiation).  s [n_bags] is m6a_train_step's y_pred
+ *                      on the same weights and batch bit for bit, and so are the running statistics left in the trainer's blob: the
+ *                      same arithmetic in the same order.  No loss, no gradient; Adam's state and n_steps do not move.  *ticket names
+ *                      the activations kept in the trainer's scratch (the site_kmers are copied with them: the caller's buffers are
+ *                      free again once the call's work has run); only the latest forward's are kept.  The argument checks and the
+ *                      single wait of m6a_train_step, minus the labels.  training = 0 is M6A_EINVAL: eval mode is m6a_bag_forward's.
+ *   m6a_train_running_stats  running_mean | running_var, 300 floats, out of the trainer's blob; a device pointer without a wait.
+ *   m6a_train_backward  grad_s [n_bags] = dL/ds; grads: 7 997 floats in blob order, zeros in the 300 running-statistic slots, as
+ *                      m6a_train_grads gives them (and m6a_train_grads gives these afterwards).  It queues the backward half: the head
+ *                      and layer-2 backward from the kept activations with dL/ds read from memory (p is recomputed from the kept
+ *                      layer-2 pre-activations, by the forward's operations: its bits), train_fold_kernel's two folds (its loss wave
+ *                      runs over 0 sites), train_bwd1_kernel, train_grad_kernel's folds.  Layer 1 and the statistics do not run again:
+ *                      the running statistics move once per forward, as in torch.  A ticket that is not the latest forward's is
+ *                      M6A_EINVAL, and the text says what overwrote those activations (a later forward, a step or an epoch, new
+ *                      weights, a larger batch).  The same ticket twice is allowed and gives the same bits (torch's retain_graph).
+ *                      With device pointers it is stream-ordered with no wait.  What it computes is
+ *                        dL/dlogit_bk = grad_s_b prod_{j != k} (1 - p_bj) (1 - p_bk) p_bk
+ *                      and from there on the step's backward; there is no gradient with respect to X.
  * Pointers are all host or all device, as everywhere; a host dataset is uploaded once per call, device-pointer calls are stream-ordered
  * after the one wait named above (m6a_sync before reading their outputs).
  * M6A_EINVAL: bag outside 1..M6A_MAX_SAMPLES; a batch of fewer than 2 reads (torch refuses a one-value batch norm) or of more than
@@ -989,6 +1016,11 @@ int m6a_train_set_clip(m6a_trainer *t, float max_norm);   /* 0 = off (the defaul
 int m6a_train_last_norm(m6a_trainer *t, float *total_norm);
 int m6a_train_state_get(m6a_trainer *t, float *m, float *v, int64_t *n_steps);
 int m6a_train_state_set(m6a_trainer *t, const float *m, const float *v, int64_t n_steps);
+int m6a_train_set_weights(m6a_trainer *t, const float *blob);
+int m6a_train_forward(m6a_trainer *t, const float *X, const uint8_t *site_kmers, int64_t n_bags, int bag, int training,
+                      float *s, int64_t *ticket);
+int m6a_train_running_stats(m6a_trainer *t, float *stats);
+int m6a_train_backward(m6a_trainer *t, int64_t ticket, const float *grad_s, float *grads);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,8 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
            "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_prep_sites_write_read_representation", "m6a_json_sites_build", "m6a_norm_factors_build", "m6a_repr_format", "m6a_prep_dataprep_write",
            "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats",
-           "m6a_train_set_clip", "m6a_train_last_norm", "m6a_train_state_get", "m6a_train_state_set"]
+           "m6a_train_set_clip", "m6a_train_last_norm", "m6a_train_state_get", "m6a_train_state_set",
+           "m6a_train_set_weights", "m6a_train_forward", "m6a_train_running_stats", "m6a_train_backward"]
 
 _lib = None
 
@@ -263,6 +264,10 @@ def load():
     L.m6a_train_last_norm.argtypes = [vp, vp]
     L.m6a_train_state_get.argtypes = [vp, vp, vp, pl]
     L.m6a_train_state_set.argtypes = [vp, vp, vp, i64]
+    L.m6a_train_set_weights.argtypes = [vp, vp]
+    L.m6a_train_forward.argtypes = [vp, vp, vp, i64, i32, i32, vp, pl]
+    L.m6a_train_running_stats.argtypes = [vp, vp]
+    L.m6a_train_backward.argtypes = [vp, i64, vp, vp]
     L.m6a_prep_last_error.argtypes = []
     L.m6a_prep_last_error.restype = C.c_char_p
     for name in SYMBOLS:

@@ -14,6 +14,9 @@
 //                        db2, dW3, db3; dL/dx of the six embedding inputs per read;
 //   train_adam_kernel    the chunks' parts in chunk order (the embedding: a wave per entry over the bags that carry the k-mer),
 //                        the gradient, Adam.
+// The same step cut at s for a caller with its own loss and optimizer (m6a_train_forward / m6a_train_backward): the forward half is
+// train_fwd1_kernel, train_stats_kernel and train_fwd2_kernel<kForward>; the backward half train_fwd2_kernel<kBackward> (dL/ds read
+// from memory), train_fold_kernel, train_bwd1_kernel and train_grad_kernel, on the activations the forward left in the scratch.
 // Sums run in a fixed order and there is no atomic on a float anywhere: the same state and batch give the same bits.
 #include "m6a_ctx.h"
 #include "m6a_train_draw.h"
@@ -49,6 +52,14 @@ __global__ void train_check_sites_kernel(const uint8_t *km, const int64_t *off, 
     if (km[s * 3] >= M6A_N_KMERS || km[s * 3 + 1] >= M6A_N_KMERS || km[s * 3 + 2] >= M6A_N_KMERS) report(err, s, kErrKmer);
     const float v = y[s];
     if (!(v == 0.f || v == 1.f)) report(err, s, kErrLabel);
+}
+
+// m6a_train_forward has no labels to check: the k-mer ids alone
+__global__ void train_check_kmers_kernel(const uint8_t *km, int64_t S, unsigned long long *err)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    if (km[s * 3] >= M6A_N_KMERS || km[s * 3 + 1] >= M6A_N_KMERS || km[s * 3 + 2] >= M6A_N_KMERS) report(err, s, kErrKmer);
 }
 
 // every position of an epoch's order: the site exists; its `bag` reads (m6a_train_draw.h) as global read indices
@@ -153,7 +164,17 @@ __device__ inline double wave_sum(double v)
     return v;
 }
 
+// train_fwd2_kernel is one body behind three kernels, the two halves m6a_train_forward / m6a_train_backward cut a step into among
+// them; the mode is a compile-time constant, so each instantiation holds its own half only:
+//   kFused     the step's kernel: everything below, dL/ds from BCELoss and the labels bt.y;
+//   kForward   up to s: h2buf and y_pred are written, nothing else (dlogit, dy1, wpart, loss_term may be null);
+//   kBackward  from the kept h2buf: the head and p again (the same operations on the same values: the forward's bits), the products,
+//              then dL/ds READ from bt.y [B] -- the place of the labels holds the upstream gradient -- and everything behind it.
+//              h2buf is only read; loss_term and y_pred may be null.
 // bags_per_wave = 64 / bag whole bags per wave, lane = read.  wpart [n_waves][300]: the wave's sums of dy1 (dbeta) and dy1 xhat (dgamma).
+enum { kFused = 0, kForward = 1, kBackward = 2 };
+
+template <int Mode>
 __global__ __launch_bounds__(256) void train_fwd2_kernel(Batch bt, int bags_per_wave, int64_t n_waves, float inv_B, const float *__restrict__ z1,
                                                          const double *__restrict__ stat, const float *__restrict__ P, float *__restrict__ h2buf,
                                                          float *__restrict__ dlogit, float *__restrict__ dy1, float *__restrict__ wpart,
@@ -178,19 +199,23 @@ __global__ __launch_bounds__(256) void train_fwd2_kernel(Batch bt, int bags_per_
     for (int i = 0; i < kH2; i++) acc[i] = P[oB2 + i];
     float p = 0.f;
     if (active) {
-        for (int j0 = 0; j0 < kH1; j0 += kRow) {                 // kRow values of the read's row of z1 loaded together
-            float z[kRow];
-            for (int u = 0; u < kRow; u++) z[u] = z1[n * kH1 + j0 + u];
-            for (int u = 0; u < kRow; u++) {
-                const int j = j0 + u;
-                const float xh = (float)(((double)z[u] - mus[j]) * iss[j]);
-                const float a = fmaxf(fmaf(gs[j], xh, bs[j]), 0.f);
-                for (int i = 0; i < kH2; i++) acc[i] = fmaf(w2t[j * kH2 + i], a, acc[i]);
+        if constexpr (Mode == kBackward) {
+            for (int i = 0; i < kH2; i++) acc[i] = h2buf[n * kH2 + i];
+        } else {
+            for (int j0 = 0; j0 < kH1; j0 += kRow) {             // kRow values of the read's row of z1 loaded together
+                float z[kRow];
+                for (int u = 0; u < kRow; u++) z[u] = z1[n * kH1 + j0 + u];
+                for (int u = 0; u < kRow; u++) {
+                    const int j = j0 + u;
+                    const float xh = (float)(((double)z[u] - mus[j]) * iss[j]);
+                    const float a = fmaxf(fmaf(gs[j], xh, bs[j]), 0.f);
+                    for (int i = 0; i < kH2; i++) acc[i] = fmaf(w2t[j * kH2 + i], a, acc[i]);
+                }
             }
         }
         float logit = P[oB3];
         for (int i = 0; i < kH2; i++) {
-            h2buf[n * kH2 + i] = acc[i];
+            if constexpr (Mode != kBackward) h2buf[n * kH2 + i] = acc[i];
             logit = fmaf(P[oW3 + i], fmaxf(acc[i], 0.f), logit);
         }
         p = 1.0f / (1.0f + expf(-logit));
@@ -208,17 +233,26 @@ __global__ __launch_bounds__(256) void train_fwd2_kernel(Batch bt, int bags_per_
         const float qk = __shfl(q, (base + k) & 63);
         if (k > pos) suf *= qk;
     }
+    if constexpr (Mode == kForward) {
+        if (active && pos == 0) y_pred[b] = 1.0f - prod;
+        return;
+    }
     float dl = 0.f;
     if (active) {
-        const float s = 1.0f - prod;
-        const float yb = bt.y[bt.sidx ? bt.sidx[b] : b];
-        const float dLds = (s - yb) / fmaxf((1.0f - s) * s, 1e-12f) * inv_B;
-        dl = dLds * (pre * suf) * ((1.0f - p) * p);
-        dlogit[n] = dl;
-        if (pos == 0) {
-            const float ls = fmaxf(logf(s), -100.0f), l1s = fmaxf(logf(1.0f - s), -100.0f);
-            loss_term[b] = -(yb * ls + (1.0f - yb) * l1s);
-            y_pred[b] = s;
+        if constexpr (Mode == kBackward) {
+            dl = bt.y[b] * (pre * suf) * ((1.0f - p) * p);
+            dlogit[n] = dl;
+        } else {
+            const float s = 1.0f - prod;
+            const float yb = bt.y[bt.sidx ? bt.sidx[b] : b];
+            const float dLds = (s - yb) / fmaxf((1.0f - s) * s, 1e-12f) * inv_B;
+            dl = dLds * (pre * suf) * ((1.0f - p) * p);
+            dlogit[n] = dl;
+            if (pos == 0) {
+                const float ls = fmaxf(logf(s), -100.0f), l1s = fmaxf(logf(1.0f - s), -100.0f);
+                loss_term[b] = -(yb * ls + (1.0f - yb) * l1s);
+                y_pred[b] = s;
+            }
         }
     }
     for (int i = 0; i < kH2; i++) acc[i] = acc[i] > 0.f ? dl * P[oW3 + i] : 0.f;          // dL/dh2
@@ -485,6 +519,11 @@ struct m6a_trainer {
     float clip = 0.f;                                                   // max_norm, 0 = no clipping
     bool have_norm = false;
     int64_t n_steps = 0, n_launches = 0, n_syncs = 0;
+    // m6a_train_forward / m6a_train_backward: the latest forward's activations live in z1, xbuf, h2 and stat, its k-mers in keptK
+    DevBuf keptK, sGradS;
+    int64_t n_forwards = 0, kept_ticket = 0, kept_B = 0;                // kept_ticket 0: nothing is kept
+    int kept_bag = 0;
+    const char *kept_lost = "no forward has been made on this trainer";
 };
 
 namespace {
@@ -494,6 +533,10 @@ int ensure_scratch(m6a_trainer *t, int64_t B, int bag)
     m6a_ctx *c = t->c;
     const size_t N = (size_t)B * bag;
     const size_t n_waves = (size_t)((B + 64 / bag - 1) / (64 / bag));
+    if (N * kH1 * 4 > t->z1.cap || N * kXs * 4 > t->xbuf.cap || N * kH2 * 4 > t->h2.cap) {      // what m6a_train_backward reads again
+        t->kept_ticket = 0;
+        t->kept_lost = "a larger batch on this trainer made it allocate its scratch anew";
+    }
     HIPCHK(c, t->z1.ensure(N * kH1 * 4));
     HIPCHK(c, t->dy1.ensure(N * kH1 * 4));
     HIPCHK(c, t->xbuf.ensure(N * kXs * 4));
@@ -529,20 +572,34 @@ int arm_check(m6a_trainer *t)
     return M6A_OK;
 }
 
+// how a batch is cut: chunks of whole 32-read tiles for layer 1 and its backward, 64 / bag whole bags per wave for train_fwd2_kernel
+struct Cut { int64_t chunk, n_waves; int n_chunks, per_wave; };
+
+Cut cut(const Batch &bt)
+{
+    Cut k;
+    k.chunk = (bt.N + kMaxChunks - 1) / kMaxChunks;
+    k.chunk = std::max<int64_t>(kTile, (k.chunk + kTile - 1) / kTile * kTile);
+    k.n_chunks = (int)((bt.N + k.chunk - 1) / k.chunk);
+    k.per_wave = 64 / bt.bag;
+    k.n_waves = (bt.B + k.per_wave - 1) / k.per_wave;
+    return k;
+}
+
 // queues one step; every pointer is a device pointer and the scratch is large enough
 int queue_step(m6a_trainer *t, const Batch &bt, float *loss, float *y_pred)
 {
     m6a_ctx *c = t->c;
     hipStream_t st = c->stream;
     const int64_t N = bt.N;
-    int64_t chunk = (N + kMaxChunks - 1) / kMaxChunks;
-    chunk = std::max<int64_t>(kTile, (chunk + kTile - 1) / kTile * kTile);
-    const int n_chunks = (int)((N + chunk - 1) / chunk);
-    const int per_wave = 64 / bt.bag;
-    const int64_t n_waves = (bt.B + per_wave - 1) / per_wave;
+    const Cut k = cut(bt);
+    const int64_t chunk = k.chunk, n_waves = k.n_waves;
+    const int n_chunks = k.n_chunks, per_wave = k.per_wave;
     float *z1 = (float *)t->z1.p, *dy1 = (float *)t->dy1.p, *xbuf = (float *)t->xbuf.p, *h2 = (float *)t->h2.p, *dl = (float *)t->dlogit.p,
           *dxe = (float *)t->dxe.p, *wpart = (float *)t->wpart.p, *lt = (float *)t->loss_term.p;
     t->n_steps++;
+    t->kept_ticket = 0;
+    t->kept_lost = "a step or an epoch on this trainer overwrote those activations";
     const double b1 = t->cfg.beta1, b2 = t->cfg.beta2;
     AdamArgs a;
     a.step_size = (float)((double)t->cfg.lr / (1.0 - std::pow(b1, (double)t->n_steps)));
@@ -553,7 +610,7 @@ int queue_step(m6a_trainer *t, const Batch &bt, float *loss, float *y_pred)
 
     hipLaunchKernelGGL(train_fwd1_kernel, dim3((unsigned)n_chunks), dim3(192), 0, st, bt, chunk, (const float *)t->P, xbuf, z1, t->part1);
     hipLaunchKernelGGL(train_stats_kernel, dim3(1), dim3(192), 0, st, (const double *)t->part1, n_chunks, N, t->P, t->stat);
-    hipLaunchKernelGGL(train_fwd2_kernel, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, bt, per_wave, n_waves, 1.0f / (float)bt.B,
+    hipLaunchKernelGGL(train_fwd2_kernel<kFused>, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, st, bt, per_wave, n_waves, 1.0f / (float)bt.B,
                        (const float *)z1, (const double *)t->stat, (const float *)t->P, h2, dl, dy1, wpart, lt, y_pred);
     hipLaunchKernelGGL(train_fold_kernel, dim3(1), dim3(256), 0, st, (const float *)wpart, n_waves, t->tot, (const float *)lt, bt.B, loss);
     hipLaunchKernelGGL(train_bwd1_kernel, dim3((unsigned)n_chunks), dim3(192), 0, st, N, chunk, (const float *)z1, (const float *)dy1,
@@ -639,7 +696,7 @@ void m6a_train_destroy(m6a_trainer *t)
     if (!t) return;
     if (t->c) { (void)hipSetDevice(t->c->device); (void)hipStreamSynchronize(t->c->stream); }
     for (DevBuf *b : {&t->z1, &t->dy1, &t->xbuf, &t->h2, &t->dlogit, &t->dxe, &t->wpart, &t->loss_term, &t->ridx, &t->sX, &t->sK, &t->sOff, &t->sY,
-                      &t->sOrder, &t->sLoss, &t->sPred})
+                      &t->sOrder, &t->sLoss, &t->sPred, &t->keptK, &t->sGradS})
         b->release();
     if (t->P) (void)hipFree(t->P);
     if (t->stat) (void)hipFree(t->stat);
@@ -762,6 +819,139 @@ int m6a_train_epoch(m6a_trainer *t, const float *X, const uint8_t *km, const int
     if (y_pred) HIPCHK(c, hipMemcpyAsync(y_pred, d_pred, (size_t)n_order * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     t->n_syncs++;
+    return M6A_OK;
+}
+
+// ---- the step cut at s: forward gives s, backward takes dL/ds (include/m6a.h) -------------------------------------------------------
+int m6a_train_set_weights(m6a_trainer *t, const float *blob)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    m6a_ctx *c = t->c;
+    if (!blob) return fail(c, M6A_EINVAL, "null pointer argument");
+    const bool dev = is_device_ptr(blob);
+    HIPCHK(c, hipMemcpyAsync(t->P, blob, (size_t)M6A_N_WEIGHTS * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    t->kept_ticket = 0;
+    t->kept_lost = "the weights were replaced since that forward (m6a_train_set_weights)";
+    if (dev) return M6A_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t->n_syncs++;
+    return M6A_OK;
+}
+
+int m6a_train_running_stats(m6a_trainer *t, float *stats)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    m6a_ctx *c = t->c;
+    if (!stats) return fail(c, M6A_EINVAL, "null pointer argument");
+    if (!is_device_ptr(stats)) return copy_out(t, stats, t->P + oMean, (size_t)2 * kH1 * 4);
+    HIPCHK(c, hipMemcpyAsync(stats, t->P + oMean, (size_t)2 * kH1 * 4, hipMemcpyDeviceToDevice, c->stream));
+    return M6A_OK;
+}
+
+int m6a_train_forward(m6a_trainer *t, const float *X, const uint8_t *km, int64_t B, int bag, int training, float *s, int64_t *ticket)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    m6a_ctx *c = t->c;
+    if (!training) return fail(c, M6A_EINVAL, "training = 0: the trainer runs batch norm on the batch's statistics only; eval mode is m6a_bag_forward's");
+    if (bag < 1 || bag > M6A_MAX_SAMPLES) return fail(c, M6A_EINVAL, "bag must be in 1..%d", M6A_MAX_SAMPLES);
+    if (B < 1 || B * bag < 2) return fail(c, M6A_EINVAL, "a forward needs n_bags * bag >= 2 reads (batch norm over one value is undefined)");
+    if (B > kMaxBatchReads || B * bag > kMaxBatchReads) return fail(c, M6A_EINVAL, "a batch holds at most 2^20 reads");
+    if (!X || !km || !s || !ticket) return fail(c, M6A_EINVAL, "null pointer argument");
+    const bool dev = is_device_ptr(X);
+    if (dev != is_device_ptr(km) || dev != is_device_ptr(s)) return fail(c, M6A_EINVAL, "X, site_kmers, s must be all host or all device pointers");
+    const int64_t N = B * bag;
+    const uint8_t *d_km = km;
+    if (!dev) {
+        HIPCHK(c, t->sK.ensure((size_t)B * 3));
+        HIPCHK(c, hipMemcpyAsync(t->sK.p, km, (size_t)B * 3, hipMemcpyHostToDevice, c->stream));
+        d_km = (const uint8_t *)t->sK.p;
+    }
+    rc = arm_check(t);
+    if (rc) return rc;
+    hipLaunchKernelGGL(train_check_kmers_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, d_km, B, t->d_err);
+    t->n_launches++;
+    HIPCHK(c, hipGetLastError());
+    rc = checked(t, "order");
+    if (rc) return rc;                                  // nothing is changed: an earlier forward's activations are still kept
+    t->kept_ticket = 0;
+    t->kept_lost = "a later forward on this trainer failed part-way";
+    rc = ensure_scratch(t, B, bag);
+    if (rc) return rc;
+    HIPCHK(c, t->keptK.ensure((size_t)B * 3));
+    HIPCHK(c, hipMemcpyAsync(t->keptK.p, d_km, (size_t)B * 3, hipMemcpyDeviceToDevice, c->stream));
+    Batch bt{X, nullptr, (const uint8_t *)t->keptK.p, nullptr, nullptr, B, N, bag};
+    float *d_s = s;
+    if (!dev) {
+        HIPCHK(c, t->sX.ensure((size_t)N * 9 * 4));
+        HIPCHK(c, t->sPred.ensure((size_t)B * 4));
+        HIPCHK(c, hipMemcpyAsync(t->sX.p, X, (size_t)N * 9 * 4, hipMemcpyHostToDevice, c->stream));
+        bt.X = (const float *)t->sX.p;
+        d_s = (float *)t->sPred.p;
+    }
+    const Cut k = cut(bt);
+    hipStream_t st = c->stream;
+    float *z1 = (float *)t->z1.p;
+    hipLaunchKernelGGL(train_fwd1_kernel, dim3((unsigned)k.n_chunks), dim3(192), 0, st, bt, k.chunk, (const float *)t->P, (float *)t->xbuf.p, z1,
+                       t->part1);
+    hipLaunchKernelGGL(train_stats_kernel, dim3(1), dim3(192), 0, st, (const double *)t->part1, k.n_chunks, N, t->P, t->stat);
+    hipLaunchKernelGGL(train_fwd2_kernel<kForward>, dim3((unsigned)((k.n_waves + 3) / 4)), dim3(256), 0, st, bt, k.per_wave, k.n_waves, 0.f,
+                       (const float *)z1, (const double *)t->stat, (const float *)t->P, (float *)t->h2.p, (float *)nullptr, (float *)nullptr,
+                       (float *)nullptr, (float *)nullptr, d_s);
+    t->n_launches += 3;
+    HIPCHK(c, hipGetLastError());
+    t->kept_ticket = ++t->n_forwards;
+    t->kept_B = B;
+    t->kept_bag = bag;
+    t->kept_lost = "a later forward on this trainer overwrote those activations";
+    *ticket = t->kept_ticket;
+    if (dev) return M6A_OK;
+    HIPCHK(c, hipMemcpyAsync(s, d_s, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t->n_syncs++;
+    return M6A_OK;
+}
+
+int m6a_train_backward(m6a_trainer *t, int64_t ticket, const float *grad_s, float *grads)
+{
+    int rc = enter(t);
+    if (rc) return rc;
+    m6a_ctx *c = t->c;
+    if (!grad_s || !grads) return fail(c, M6A_EINVAL, "null pointer argument");
+    if (ticket < 1 || ticket > t->n_forwards) return fail(c, M6A_EINVAL, "ticket %lld was not given by m6a_train_forward on this trainer", (long long)ticket);
+    if (ticket != t->kept_ticket) return fail(c, M6A_EINVAL, "the activations of ticket %lld are gone: %s", (long long)ticket, t->kept_lost);
+    const bool dev = is_device_ptr(grad_s);
+    if (dev != is_device_ptr(grads)) return fail(c, M6A_EINVAL, "grad_s, grads must be all host or all device pointers");
+    const int64_t B = t->kept_B;
+    const float *d_g = grad_s;
+    if (!dev) {
+        HIPCHK(c, t->sGradS.ensure((size_t)B * 4));
+        HIPCHK(c, hipMemcpyAsync(t->sGradS.p, grad_s, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
+        d_g = (const float *)t->sGradS.p;
+    }
+    HIPCHK(c, t->sLoss.ensure(4));
+    // the place of the labels holds dL/ds (train_fwd2_kernel<kBackward>); X is not read again: xbuf has the forward's gather
+    Batch bt{nullptr, nullptr, (const uint8_t *)t->keptK.p, nullptr, d_g, B, B * t->kept_bag, t->kept_bag};
+    const Cut k = cut(bt);
+    hipStream_t st = c->stream;
+    float *z1 = (float *)t->z1.p, *dy1 = (float *)t->dy1.p, *h2 = (float *)t->h2.p, *dl = (float *)t->dlogit.p, *dxe = (float *)t->dxe.p,
+          *wpart = (float *)t->wpart.p;
+    hipLaunchKernelGGL(train_fwd2_kernel<kBackward>, dim3((unsigned)((k.n_waves + 3) / 4)), dim3(256), 0, st, bt, k.per_wave, k.n_waves, 0.f,
+                       (const float *)z1, (const double *)t->stat, (const float *)t->P, h2, dl, dy1, wpart, (float *)nullptr, (float *)nullptr);
+    // B = 0 for the fold's loss wave: it adds nothing and its one store goes to scratch nobody reads -- the loss is the caller's
+    hipLaunchKernelGGL(train_fold_kernel, dim3(1), dim3(256), 0, st, (const float *)wpart, k.n_waves, t->tot, (const float *)nullptr, (int64_t)0,
+                       (float *)t->sLoss.p);
+    hipLaunchKernelGGL(train_bwd1_kernel, dim3((unsigned)k.n_chunks), dim3(192), 0, st, bt.N, k.chunk, (const float *)z1, (const float *)dy1,
+                       (const float *)t->xbuf.p, (const float *)h2, (const float *)dl, (const double *)t->stat, (const double *)t->tot,
+                       (const float *)t->P, t->part2, dxe);
+    hipLaunchKernelGGL(train_grad_kernel, dim3(kGradBlocks), dim3(64), 0, st, bt, (const float *)t->part2, k.n_chunks, (const double *)t->tot,
+                       (const float *)dxe, t->G, t->sq);
+    t->n_launches += 4;
+    HIPCHK(c, hipGetLastError());
+    if (!dev) return copy_out(t, grads, t->G, (size_t)M6A_N_WEIGHTS * 4);
+    HIPCHK(c, hipMemcpyAsync(grads, t->G, (size_t)M6A_N_WEIGHTS * 4, hipMemcpyDeviceToDevice, c->stream));
     return M6A_OK;
 }
 

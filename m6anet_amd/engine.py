@@ -674,6 +674,51 @@ class Trainer:
             raise ValueError("m and v must have %d floats" % N_WEIGHT_FLOATS)
         self._engine._chk(self._L.m6a_train_state_set(self._h, m.ctypes.data, v.ctypes.data, int(state["n_steps"])))
 
+    # -- the step cut at s (include/m6a.h): forward gives s, backward takes dL/ds; m6anet_amd/torch_model.py puts autograd on top --
+    def set_weights(self, blob):
+        """The trainer's blob <- blob (7 997 floats, running statistics included; numpy, or a tensor on the engine's GPU: copied on
+        the stream without a wait).  Adam's state is untouched."""
+        a = _Arg(blob, np.float32, "float32")
+        if a.size != N_WEIGHT_FLOATS:
+            raise ValueError("weights must have %d floats" % N_WEIGHT_FLOATS)
+        self._engine._chk(self._L.m6a_train_set_weights(self._h, a.ptr))
+
+    def forward(self, X, site_kmers, bag=N_SAMPLES):
+        """The first half of step(): X [B * bag, 9], site_kmers [B, 3] -> (s [B], ticket).  s and the running statistics are step()'s
+        bits; no loss, no gradient, Adam's state does not move.  The ticket names the activations kept for backward()."""
+        aX, aK = _Arg(X, np.float32, "float32"), _Arg(site_kmers, np.uint8, "uint8")
+        B = aK.size // 3
+        if aK.size != 3 * B or aX.size != B * int(bag) * 9:
+            raise ValueError("X must be [B * bag, 9] and site_kmers [B, 3]")
+        s, ticket = self._engine._out(aX.is_dev, B, np.float32, "float32"), C.c_int64()
+        aS = _Arg(s, np.float32, "float32")
+        self._engine._chk(self._L.m6a_train_forward(self._h, aX.ptr, aK.ptr, B, int(bag), 1, aS.ptr, C.byref(ticket)))
+        self._kept = (int(ticket.value), B)
+        return s, int(ticket.value)
+
+    def backward(self, ticket, grad_s, out=None):
+        """The backward half from the activations `ticket` names under grad_s [B] = dL/ds -> the gradient, 7 997 floats in blob order
+        (zeros in the running-statistic slots).  Only the latest forward's ticket is good; the same one may be used again."""
+        aG = _Arg(grad_s, np.float32, "float32")
+        kept = getattr(self, "_kept", None)
+        if kept and kept[0] == int(ticket) and aG.size != kept[1]:
+            raise ValueError("grad_s must have one value per site of that forward (%d), not %d" % (kept[1], aG.size))
+        g = self._engine._out(aG.is_dev, N_WEIGHT_FLOATS, np.float32, "float32") if out is None else out
+        aO = _Arg(g, np.float32, "float32")
+        if aO.size != N_WEIGHT_FLOATS:
+            raise ValueError("out must have %d floats" % N_WEIGHT_FLOATS)
+        self._engine._chk(self._L.m6a_train_backward(self._h, int(ticket), aG.ptr, aO.ptr))
+        return g
+
+    def running_stats(self, out=None):
+        """running_mean | running_var (300 floats) out of the trainer's blob, into `out` where given (a device tensor: no wait)."""
+        r = np.empty(300, np.float32) if out is None else out
+        a = _Arg(r, np.float32, "float32")
+        if a.size != 300:
+            raise ValueError("out must have 300 floats")
+        self._engine._chk(self._L.m6a_train_running_stats(self._h, a.ptr))
+        return r
+
     def state_dict(self):
         """The reference's state_dict keys -> NumPy arrays (state_dict_from_weights), num_batches_tracked = the steps taken."""
         return state_dict_from_weights(self.weights(), self.stats()["n_steps"])

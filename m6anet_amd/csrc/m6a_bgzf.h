@@ -390,7 +390,7 @@ template <class F> struct Walker {
 }  // namespace m6a_bgzf
 
 #ifdef M6A_BGZF_DEVICE_PART
-// ---- part 2: kernels and the upload (inside m6a_prep.hip: DevMem, Streams, PCHK, prep_fail, now_ms, g_d2h, kBlk are its own) ----
+// ---- part 2: kernels and the upload (inside m6a_prep.hip: DevMem, Streams, upload_range, PCHK, prep_fail, kBlk: m6a_prep_kit.h) ----
 namespace {
 
 struct BgzfBlock {                  // one block for the kernels: its deflate stream in the compressed buffer, its place in the text
@@ -470,7 +470,7 @@ struct BgzfUp {
 // The compressed file [0, n) of fd goes up through S.pin (chunks of `chunk` bytes) while the host walks the block chain in the pinned
 // bytes; the text buffer is allocated at the sum of ISIZE, every block inflated to its place and its CRC checked; the compressed
 // buffer is released before this returns.  S.s[0] runs the kernels, S.s[1] the copies, as in front_half.
-int bgzf_upload_inflate(const char *path, int fd, int64_t n, DevMem &m, Streams &S, int64_t chunk, BgzfUp &U)
+int bgzf_upload_inflate(int device_id, const char *path, int fd, int64_t n, DevMem &m, Streams &S, int64_t chunk, BgzfUp &U)
 {
     int rc;
     uint8_t *dcomp;
@@ -485,22 +485,13 @@ int bgzf_upload_inflate(const char *path, int fd, int64_t n, DevMem &m, Streams 
     };
     std::unique_ptr<m6a_bgzf::Walker<decltype(on_block)>> W(new m6a_bgzf::Walker<decltype(on_block)>(on_block));     // 64 KiB of carry
     const double t0 = now_ms();
-    for (int64_t k = 0, off = 0; off < n && !W->bad; k++, off += chunk) {
-        const int slot = (int)(k & 1);
-        PCHK(hipEventSynchronize(S.copied[slot]));
-        const int64_t len = std::min(chunk, n - off);
-        for (int64_t got = 0; got < len;) {
-            const ssize_t r = ::pread(fd, (char *)S.pin[slot] + got, (size_t)(len - got), (off_t)(off + got));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
-            got += r;
-        }
-        PCHK(hipMemcpyAsync(dcomp + off, S.pin[slot], (size_t)len, hipMemcpyHostToDevice, S.s[1]));
-        PCHK(hipEventRecord(S.copied[slot], S.s[1]));
-        W->feed((const uint8_t *)S.pin[slot], len);       // the chain is walked while the chunk is on its way
-    }
+    // the chain is walked while the chunk is on its way, and nothing goes up behind the first bad block; dcomp holds n bytes: no padding
+    rc = upload_range(device_id, fd, path, S, dcomp, 0, n, chunk, [&](int slot, int64_t, int64_t len) {
+        W->feed((const uint8_t *)S.pin[slot], len);
+        return W->bad ? kUploadStop : (int)M6A_OK;
+    }, false);
+    if (rc) return rc;
     W->finish();
-    PCHK(hipStreamSynchronize(S.s[1]));
     U.ms_upload = now_ms() - t0;
     if (W->bad && W->bad_at == 0 && W->bad == m6a_bgzf::BR_HEADER)
         return prep_fail(M6A_EFORMAT, "%s is gzip but not BGZF: its first member has no BGZF header (compress it with `bgzip`, or "
@@ -545,10 +536,10 @@ int bgzf_upload_inflate(const char *path, int fd, int64_t n, DevMem &m, Streams 
 }
 
 // front_half's BGZF branch: the text where the upload would have put it, and what the call reports
-int bgzf_front(const char *path, int fd, int64_t n_file, DevMem &m, Streams &S, int64_t chunk, uint8_t *&text, int64_t &n_text, Front &F, double *ms)
+int bgzf_front(int device_id, const char *path, int fd, int64_t n_file, DevMem &m, Streams &S, int64_t chunk, uint8_t *&text, int64_t &n_text, Front &F, double *ms)
 {
     BgzfUp U;
-    const int rc = bgzf_upload_inflate(path, fd, n_file, m, S, chunk, U);
+    const int rc = bgzf_upload_inflate(device_id, path, fd, n_file, m, S, chunk, U);
     if (rc) return rc;
     text = U.text;
     n_text = U.n_text;
@@ -567,7 +558,7 @@ extern "C" int m6a_bgzf_inflate(int device_id, const char *path, char *text, int
     if (!path || !n_bytes) return prep_fail(M6A_EINVAL, "null argument");
     *n_bytes = 0;
     if (stats) *stats = m6a_bgzf_stats{};
-    try {
+    return guarded([&]() -> int {
         Fd fd;
         fd.fd = ::open(path, O_RDONLY);
         if (fd.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", path);
@@ -594,31 +585,14 @@ extern "C" int m6a_bgzf_inflate(int device_id, const char *path, char *text, int
             *n_bytes = total;
             return M6A_OK;
         }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
-        if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
-        PCHK(hipSetDevice(device_id));
-        g_d2h = 0;
         DevMem m;
-        m.advice = "inflate it on the host";
-        size_t fr = 0, tot = 0;
-        PCHK(hipMemGetInfo(&fr, &tot));
-        m.budget = fr - std::min<size_t>(fr / 16, (size_t)4 << 30);
-        const char *bm = getenv("M6A_PREP_BUDGET_MB");
-        if (bm && atoll(bm) > 0) m.budget = std::min(m.budget, (size_t)atoll(bm) << 20);
-        Streams S;
-        for (int i = 0; i < 2; i++) {
-            PCHK(hipStreamCreateWithFlags(&S.s[i], hipStreamNonBlocking));
-            PCHK(hipEventCreateWithFlags(&S.copied[i], hipEventDisableTiming));
-        }
-        const char *ck = getenv("M6A_PREP_CHUNK_KB");
-        int64_t chunk = (ck && atoll(ck) > 0 ? atoll(ck) : 65536) << 10;
-        chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
-        chunk = std::min<int64_t>(chunk, (n + kScanBytes - 1) / kScanBytes * kScanBytes);
-        for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&S.pin[i], (size_t)chunk, hipHostMallocDefault));
-        BgzfUp U;
-        const int rc = bgzf_upload_inflate(path, fd.fd, n, m, S, chunk, U);
+        int rc = open_device(device_id, m, "inflate it on the host");
         if (rc) return rc;
+        g_d2h = 0;
+        Streams S;
+        int64_t chunk = 0;
+        BgzfUp U;
+        if ((rc = S.open((n + kScanBytes - 1) / kScanBytes * kScanBytes, chunk)) || (rc = bgzf_upload_inflate(device_id, path, fd.fd, n, m, S, chunk, U))) return rc;
         *n_bytes = U.n_text;
         if (cap < U.n_text) return prep_fail(M6A_EINVAL, "the text needs %lld bytes, the buffer holds %lld", (long long)U.n_text, (long long)cap);
         const double t0 = now_ms();
@@ -626,11 +600,7 @@ extern "C" int m6a_bgzf_inflate(int device_id, const char *path, char *text, int
         g_d2h += U.n_text;
         if (stats) *stats = m6a_bgzf_stats{U.n_blocks, U.comp_bytes, U.ms_upload, U.ms_inflate, U.ms_crc, now_ms() - t0, g_d2h};
         return M6A_OK;
-    } catch (const std::bad_alloc &) {
-        return prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        return prep_fail(M6A_EIO, "unexpected exception");
-    }
+    });
 }
 
 namespace {

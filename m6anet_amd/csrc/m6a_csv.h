@@ -1,6 +1,6 @@
 // m6a_csv.h -- data.site_proba.csv / data.indiv_proba.csv formatted on the device (include/m6a.h: m6a_csv_format,
-// m6a_prep_sites_write_csv).  Part of m6a_prep.hip's translation unit (it works on that file's m6a_prep_sites handle and uses its
-// DevMem, scan and error helpers); not a file to compile on its own.
+// m6a_prep_sites_write_csv).  Part of m6a_prep.hip's translation unit (it works on that file's m6a_prep_sites handle and uses
+// m6a_prep_kit.h's DevMem, scans, Rounds, run_rounds and error helpers); not a file to compile on its own.
 //
 // The bytes are the host writer's (m6a_io.cpp: format_rows, format_f16), i.e. the reference's '%s,%d,%s,%.16f,%s,%.16f' and
 // '%s,%d,%s,%.16f' (m6anet/utils/inference_utils.py:62,66):
@@ -345,23 +345,6 @@ __global__ __launch_bounds__(kCsvWave) void csv_site_kernel(CsvDev d, int64_t A,
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
-int csv_device(int device_id, DevMem &m)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
-    if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
-    PCHK(hipSetDevice(device_id));
-    size_t fr = 0, tot = 0;
-    PCHK(hipMemGetInfo(&fr, &tot));
-    const size_t margin = std::min<size_t>(fr / 16, (size_t)4 << 30);
-    m.budget = fr > margin ? fr - margin : 0;
-    m.budget_set = true;
-    const char *b = getenv("M6A_PREP_BUDGET_MB");
-    if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
-    m.advice = "write the CSV files on the host (--csv host)";
-    return M6A_OK;
-}
-
 // lengths and offsets of sites [A, B): the scanned arrays on the device (B - A + 1 entries, the last one the total) and on the host
 struct CsvPlan {
     int64_t *d_site = nullptr, *d_indiv = nullptr;
@@ -393,6 +376,12 @@ int csv_plan(DevMem &m, const CsvDev &d, int64_t A, int64_t B, hipStream_t s, Cs
     PCHK(hipStreamSynchronize(s));
     P.declined = (int64_t)hd;
     return M6A_OK;
+}
+
+int csv_declined(int64_t n)
+{
+    return prep_fail(M6A_EDECLINED, "%lld values are outside what the device formats (a probability or ratio that is negative or >= 2, "
+                     "a read index that is not an integer in [0, 10^15))", (long long)n);
 }
 
 // the text of sites [a, b) of a plan over [A, ...): the read rows from out[0] on, the site rows from out[site_at] on
@@ -439,149 +428,152 @@ bool csv_pwrite_threads(int fd, const char *p, int64_t n, int64_t at, int nw)
 const char kCsvSiteHeader[] = "transcript_id,transcript_position,n_reads,probability_modified,kmer,mod_ratio\n";
 const char kCsvIndivHeader[] = "transcript_id,transcript_position,read_index,probability_modified\n";
 
-struct CsvRound {                          // pinned buffer, device buffer, stream and events of one of the two rounds in flight
-    hipStream_t s = nullptr;
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};         // start, formatted, copied
-    char *pin = nullptr;
-    ~CsvRound()
+const char kCsvAdvice[] = "write the CSV files on the host (--csv host)";
+
+// whatever way a writer's call ends, what it copied and allocated is reported
+template <class Stats> struct Account {
+    m6a_prep_sites &P; DevMem &m; Stats &st;
+    ~Account()
     {
-        if (s) (void)hipStreamSynchronize(s);
-        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-        if (pin) (void)hipHostFree(pin);
-        if (s) (void)hipStreamDestroy(s);
+        st.d2h_bytes = g_d2h;
+        P.info.d2h_bytes += g_d2h;
+        P.info.peak_bytes = std::max<int64_t>(P.info.peak_bytes, (int64_t)(P.held + m.peak));
     }
 };
 
-int csv_write_impl(m6a_prep_sites &P, const char *out_dir, int write_header, int64_t n_limit, int n_threads, m6a_csv_stats &st)
-{
-    const m6a_prep_sites_info &I = P.info;
-    const int64_t S = n_limit >= 0 ? std::min<int64_t>(n_limit, I.n_sites) : I.n_sites;
-    if (I.n_sites && !P.csv_ids) return prep_fail(M6A_EINVAL, "the handle holds no read ids on the device");
-    const int nw = n_threads > 0 ? n_threads : m6a_usable_cpus();
+// What m6a_prep_sites_write_csv and its BGZF twin (m6a_deflate.h) do around their rounds.  begin: the device, the small uploads, the
+// lengths and offsets of the whole job, the refusal of a declined value, the rounds.  The writer then allocates every device and pinned
+// buffer, so that a call over the budget touches no file, and only then open_files; close_files after the last round.
+template <class Stats> struct CsvJob {
+    m6a_prep_sites &P;
+    Stats &st;
     DevMem m;
-    int rc = csv_device(P.device, m);
-    if (rc) return rc;
-    g_d2h = 0;
-    struct Account {                       // whatever way the call ends, what it copied and allocated is reported
-        m6a_prep_sites &P; DevMem &m; m6a_csv_stats &st;
-        ~Account()
-        {
-            st.d2h_bytes = g_d2h;
-            P.info.d2h_bytes += g_d2h;
-            P.info.peak_bytes = std::max<int64_t>(P.info.peak_bytes, (int64_t)(P.held + m.peak));
-        }
-    } account{P, m, st};
-    CsvRound rd[2];
-    for (CsvRound &r : rd) {
-        PCHK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-        for (hipEvent_t &x : r.e) PCHK(hipEventCreate(&x));
-    }
-    hipStream_t s = rd[0].s;
-
-    // ---- the small uploads, lengths and offsets of the whole job
-    uint8_t *blob;
-    int64_t *tx_off;
-    const size_t nblob = (size_t)(I.n_tx ? I.tx_off[I.n_tx] : 0);
-    if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)I.n_tx + 1, "transcript names"))) return rc;
-    if ((rc = h2d(blob, (const uint8_t *)I.tx_blob, nblob, s)) || (rc = h2d(tx_off, I.tx_off, I.n_tx ? (size_t)I.n_tx + 1 : 0, s))) return rc;
-    const CsvDev d{I.off, P.csv_tx, P.csv_pos, P.csv_k7, 7, 1, blob, tx_off, P.csv_ids, nullptr, I.n_rep > 1 ? P.csv_parts : nullptr,
-                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio, P.csv_names, P.csv_name_off};
-    double t0 = now_ms();
+    Account<Stats> account{P, m, st};
+    int64_t S = 0;
+    int nw = 0;
+    CsvDev d{};
     CsvPlan plan;
-    if ((rc = csv_plan(m, d, 0, S, s, plan))) return rc;
-    st.ms_format += now_ms() - t0;
-    st.n_declined = plan.declined;
-    st.site_bytes = plan.site[(size_t)S];
-    st.indiv_bytes = plan.indiv[(size_t)S];
-    if (plan.declined)
-        return prep_fail(M6A_EDECLINED, "%lld values are outside what the device formats (a probability or ratio that is negative or >= 2, "
-                         "a read index that is not an integer in [0, 10^15))", (long long)plan.declined);
-
-    // ---- rounds of whole sites: [cut[k], cut[k + 1])
-    const char *rk = getenv("M6A_CSV_ROUND_KB");
-    const int64_t round_bytes = (rk && atoll(rk) > 0 ? atoll(rk) : kCsvRoundKB) << 10;
-    std::vector<int64_t> cut{0};
-    int64_t cap = 0;
-    auto text = [&](int64_t a, int64_t b) { return plan.site[(size_t)b] - plan.site[(size_t)a] + plan.indiv[(size_t)b] - plan.indiv[(size_t)a]; };
-    auto span = [&](int64_t a, int64_t b) { return csv_align(plan.indiv[(size_t)b] - plan.indiv[(size_t)a]) + plan.site[(size_t)b] - plan.site[(size_t)a]; };
-    while (cut.back() < S) {
-        const int64_t a = cut.back();
-        int64_t lo = a + 1, hi = S;                          // the last b with text(a, b) <= round_bytes, at least a + 1
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) / 2;
-            if (text(a, mid) <= round_bytes) lo = mid; else hi = mid - 1;
-        }
-        cut.push_back(lo);
-        cap = std::max(cap, span(a, lo));
-    }
-    const int64_t n_rounds = (int64_t)cut.size() - 1;
-    st.n_rounds = n_rounds;
-
-    // ---- the files
-    const std::string fs = std::string(out_dir) + "/data.site_proba.csv", fi = std::string(out_dir) + "/data.indiv_proba.csv";
-    const int flags = O_WRONLY | O_CREAT | (write_header ? O_TRUNC : 0);
+    std::vector<int64_t> cut{0};            // round k is sites [cut[k], cut[k + 1])
+    std::string fs, fi;
     Fd f, g;
-    f.fd = ::open(fs.c_str(), flags, 0644);
-    if (f.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fs.c_str());
-    g.fd = ::open(fi.c_str(), flags, 0644);
-    if (g.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fi.c_str());
-    int64_t at_site = 0, at_indiv = 0;
-    if (write_header) {
-        at_site = (int64_t)sizeof(kCsvSiteHeader) - 1;
-        at_indiv = (int64_t)sizeof(kCsvIndivHeader) - 1;
-        if (!csv_pwrite_all(f.fd, kCsvSiteHeader, at_site, 0)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
-        if (!csv_pwrite_all(g.fd, kCsvIndivHeader, at_indiv, 0)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
-    } else {                                                // append: behind whatever the files hold
+    int64_t at_site = 0, at_indiv = 0;      // where the rows begin in either file
+    CsvJob(m6a_prep_sites &P_, Stats &st_) : P(P_), st(st_) {}
+    int64_t ni(int64_t a, int64_t b) const { return plan.indiv[(size_t)b] - plan.indiv[(size_t)a]; }
+    int64_t ns(int64_t a, int64_t b) const { return plan.site[(size_t)b] - plan.site[(size_t)a]; }
+    int64_t n_rounds() const { return (int64_t)cut.size() - 1; }
+
+    // on_round(ni, ns) sees the read and site text of every round: the writer sizes its buffers from them
+    template <class OnRound> int begin(int64_t n_limit, int n_threads, Rounds &rd, int n_events, OnRound on_round)
+    {
+        g_d2h = 0;
+        const m6a_prep_sites_info &I = P.info;
+        S = n_limit >= 0 ? std::min<int64_t>(n_limit, I.n_sites) : I.n_sites;
+        if (I.n_sites && !P.csv_ids) return prep_fail(M6A_EINVAL, "the handle holds no read ids on the device");
+        nw = n_threads > 0 ? n_threads : m6a_usable_cpus();
+        int rc;
+        if ((rc = open_device(P.device, m, kCsvAdvice)) || (rc = rd.open(n_events))) return rc;
+        hipStream_t s = rd.s[0];
+        uint8_t *blob;
+        int64_t *tx_off;
+        const size_t nblob = (size_t)(I.n_tx ? I.tx_off[I.n_tx] : 0);
+        if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)I.n_tx + 1, "transcript names"))) return rc;
+        if ((rc = h2d(blob, (const uint8_t *)I.tx_blob, nblob, s)) || (rc = h2d(tx_off, I.tx_off, I.n_tx ? (size_t)I.n_tx + 1 : 0, s))) return rc;
+        d = CsvDev{I.off, P.csv_tx, P.csv_pos, P.csv_k7, 7, 1, blob, tx_off, P.csv_ids, nullptr, I.n_rep > 1 ? P.csv_parts : nullptr,
+                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio, P.csv_names, P.csv_name_off};
+        const double t0 = now_ms();
+        if ((rc = csv_plan(m, d, 0, S, s, plan))) return rc;
+        st.ms_format += now_ms() - t0;
+        st.n_declined = plan.declined;
+        st.site_bytes = plan.site[(size_t)S];
+        st.indiv_bytes = plan.indiv[(size_t)S];
+        if (plan.declined) return csv_declined(plan.declined);
+        m6a_rounds::cut_rounds(S, round_kb("M6A_CSV_ROUND_KB", kCsvRoundKB) << 10, [&](int64_t a, int64_t b) { return ni(a, b) + ns(a, b); },
+                               [&](int64_t a, int64_t b) { cut.push_back(b); on_round(ni(a, b), ns(a, b)); });
+        st.n_rounds = n_rounds();
+        return M6A_OK;
+    }
+
+    // both files of out_dir; header(line, n) gives the bytes that stand for a header line.  write_header = 0 appends: nothing is
+    // truncated and the rows go behind whatever the files hold
+    template <class Header> int open_files(const char *out_dir, const char *suffix, int write_header, Header header)
+    {
+        fs = std::string(out_dir) + "/data.site_proba.csv" + suffix;
+        fi = std::string(out_dir) + "/data.indiv_proba.csv" + suffix;
+        const int flags = O_WRONLY | O_CREAT | (write_header ? O_TRUNC : 0);
+        f.fd = ::open(fs.c_str(), flags, 0644);
+        if (f.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fs.c_str());
+        g.fd = ::open(fi.c_str(), flags, 0644);
+        if (g.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fi.c_str());
+        if (write_header) {
+            const std::string hs = header(kCsvSiteHeader, (int32_t)sizeof(kCsvSiteHeader) - 1), hi = header(kCsvIndivHeader, (int32_t)sizeof(kCsvIndivHeader) - 1);
+            at_site = (int64_t)hs.size();
+            at_indiv = (int64_t)hi.size();
+            if (!csv_pwrite_all(f.fd, hs.data(), at_site, 0)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
+            if (!csv_pwrite_all(g.fd, hi.data(), at_indiv, 0)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
+            return M6A_OK;
+        }
         struct stat sb;
         if (fstat(f.fd, &sb) != 0) return prep_fail(M6A_EIO, "cannot stat %s", fs.c_str());
         at_site = (int64_t)sb.st_size;
         if (fstat(g.fd, &sb) != 0) return prep_fail(M6A_EIO, "cannot stat %s", fi.c_str());
         at_indiv = (int64_t)sb.st_size;
+        return M6A_OK;
     }
 
-    // ---- round k + 1 is formatted and copied while round k is written
-    char *dbuf[2] = {nullptr, nullptr};
-    if (n_rounds) {
-        for (int i = 0; i < (n_rounds > 1 ? 2 : 1); i++) {
-            if ((rc = m.alloc(dbuf[i], (size_t)cap, "CSV text"))) return rc;
-            PCHK(hipHostMalloc((void **)&rd[i].pin, (size_t)std::max<int64_t>(cap, 16), hipHostMallocDefault));
-        }
+    int close_files()
+    {
+        const int cf = ::close(f.fd), cg = ::close(g.fd);
+        f.fd = g.fd = -1;
+        if (cf != 0) return prep_fail(M6A_EIO, "cannot close %s", fs.c_str());
+        if (cg != 0) return prep_fail(M6A_EIO, "cannot close %s", fi.c_str());
+        return M6A_OK;
     }
-    auto enqueue = [&](int64_t k) -> int {
-        CsvRound &r = rd[k & 1];
-        const int64_t a = cut[(size_t)k], b = cut[(size_t)k + 1];
-        PCHK(hipEventRecord(r.e[0], r.s));
-        int rc2 = csv_launch(d, plan, 0, a, b, dbuf[k & 1], csv_align(plan.indiv[(size_t)b] - plan.indiv[(size_t)a]), r.s);
+};
+
+int csv_write_impl(m6a_prep_sites &P, const char *out_dir, int write_header, int64_t n_limit, int n_threads, m6a_csv_stats &st)
+{
+    CsvJob<m6a_csv_stats> J(P, st);
+    Rounds rd;                                              // events: start, formatted, copied
+    int64_t cap = 0;
+    int rc = J.begin(n_limit, n_threads, rd, 3, [&](int64_t ni, int64_t ns) { cap = std::max(cap, csv_align(ni) + ns); });
+    if (rc) return rc;
+    const int64_t n_rounds = J.n_rounds();
+    char *dbuf[2] = {nullptr, nullptr};
+    for (int i = 0; i < (n_rounds > 1 ? 2 : n_rounds ? 1 : 0); i++)
+        if ((rc = J.m.alloc(dbuf[i], (size_t)cap, "CSV text")) || (rc = rd.pinned(i, cap))) return rc;
+    if ((rc = J.open_files(out_dir, "", write_header, [](const char *line, int32_t n) { return std::string(line, (size_t)n); }))) return rc;
+
+    // ---- round k + 1 is formatted and copied while round k is written
+    auto queue = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        const int64_t a = J.cut[(size_t)k], b = J.cut[(size_t)k + 1], ni = J.ni(a, b);
+        PCHK(hipEventRecord(rd.e[i][0], rd.s[i]));
+        const int rc2 = csv_launch(J.d, J.plan, 0, a, b, dbuf[i], csv_align(ni), rd.s[i]);
         if (rc2) return rc2;
-        PCHK(hipEventRecord(r.e[1], r.s));
-        const int64_t n = span(a, b);
-        PCHK(hipMemcpyAsync(r.pin, dbuf[k & 1], (size_t)n, hipMemcpyDeviceToHost, r.s));
+        PCHK(hipEventRecord(rd.e[i][1], rd.s[i]));
+        const int64_t n = csv_align(ni) + J.ns(a, b);
+        PCHK(hipMemcpyAsync(rd.pin[i], dbuf[i], (size_t)n, hipMemcpyDeviceToHost, rd.s[i]));
         g_d2h += n;
-        PCHK(hipEventRecord(r.e[2], r.s));
+        PCHK(hipEventRecord(rd.e[i][2], rd.s[i]));
         return M6A_OK;
     };
-    if (n_rounds && (rc = enqueue(0))) return rc;
-    for (int64_t k = 0; k < n_rounds; k++) {
-        if (k + 1 < n_rounds && (rc = enqueue(k + 1))) return rc;
-        CsvRound &r = rd[k & 1];
-        PCHK(hipEventSynchronize(r.e[2]));
+    auto finish = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        PCHK(hipEventSynchronize(rd.e[i][2]));
         float fm = 0, cm = 0;
-        PCHK(hipEventElapsedTime(&fm, r.e[0], r.e[1]));
-        PCHK(hipEventElapsedTime(&cm, r.e[1], r.e[2]));
+        PCHK(hipEventElapsedTime(&fm, rd.e[i][0], rd.e[i][1]));
+        PCHK(hipEventElapsedTime(&cm, rd.e[i][1], rd.e[i][2]));
         st.ms_format += fm;
         st.ms_copy += cm;
-        const int64_t a = cut[(size_t)k], b = cut[(size_t)k + 1];
-        const int64_t ni = plan.indiv[(size_t)b] - plan.indiv[(size_t)a], ns = plan.site[(size_t)b] - plan.site[(size_t)a];
-        t0 = now_ms();
-        if (!csv_pwrite_threads(g.fd, r.pin, ni, at_indiv + plan.indiv[(size_t)a], nw)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
-        if (!csv_pwrite_all(f.fd, r.pin + csv_align(ni), ns, at_site + plan.site[(size_t)a])) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
+        const int64_t a = J.cut[(size_t)k], b = J.cut[(size_t)k + 1], ni = J.ni(a, b);
+        const double t0 = now_ms();
+        if (!csv_pwrite_threads(J.g.fd, rd.pin[i], ni, J.at_indiv + J.plan.indiv[(size_t)a], J.nw)) return prep_fail(M6A_EIO, "cannot write %s", J.fi.c_str());
+        if (!csv_pwrite_all(J.f.fd, rd.pin[i] + csv_align(ni), J.ns(a, b), J.at_site + J.plan.site[(size_t)a])) return prep_fail(M6A_EIO, "cannot write %s", J.fs.c_str());
         st.ms_write += now_ms() - t0;
-    }
-    const int cf = ::close(f.fd), cg = ::close(g.fd);
-    f.fd = g.fd = -1;
-    if (cf != 0) return prep_fail(M6A_EIO, "cannot close %s", fs.c_str());
-    if (cg != 0) return prep_fail(M6A_EIO, "cannot close %s", fi.c_str());
-    return M6A_OK;
+        return M6A_OK;
+    };
+    if ((rc = run_rounds(n_rounds, queue, finish))) return rc;
+    return J.close_files();
 }
 
 int csv_format_impl(int device_id, const m6a_csv_arrays &a, int64_t A, int64_t B, char *site_text, int64_t site_cap, char *indiv_text,
@@ -607,9 +599,8 @@ int csv_format_impl(int device_id, const m6a_csv_arrays &a, int64_t A, int64_t B
     if (!site_bytes || !indiv_bytes || !n_declined) return prep_fail(M6A_EINVAL, "null argument");
 
     DevMem m;
-    int rc = csv_device(device_id, m);
+    int rc = open_device(device_id, m, "format fewer sites per call");
     if (rc) return rc;
-    m.advice = "format fewer sites per call";
     Streams st;
     PCHK(hipStreamCreateWithFlags(&st.s[0], hipStreamNonBlocking));
     hipStream_t s = st.s[0];
@@ -638,9 +629,7 @@ int csv_format_impl(int device_id, const m6a_csv_arrays &a, int64_t A, int64_t B
     *site_bytes = ns;
     *indiv_bytes = ni;
     *n_declined = plan.declined;
-    if (plan.declined)
-        return prep_fail(M6A_EDECLINED, "%lld values are outside what the device formats (a probability or ratio that is negative or >= 2, "
-                         "a read index that is not an integer in [0, 10^15))", (long long)plan.declined);
+    if (plan.declined) return csv_declined(plan.declined);
     if (!site_text && !indiv_text) return M6A_OK;          // the sizing call
     if (!site_text || !indiv_text || site_cap < ns || indiv_cap < ni)
         return prep_fail(M6A_EINVAL, "the texts take %lld and %lld bytes, the buffers hold %lld and %lld", (long long)ns, (long long)ni,
@@ -659,13 +648,9 @@ extern "C" int m6a_csv_format(int device_id, const m6a_csv_arrays *a, int64_t si
                               char *indiv_text, int64_t indiv_cap, int64_t *site_bytes, int64_t *indiv_bytes, int64_t *n_declined)
 {
     if (!a) return prep_fail(M6A_EINVAL, "null argument");
-    try {
+    return guarded([&] {
         return csv_format_impl(device_id, *a, site_begin, site_end, site_text, site_cap, indiv_text, indiv_cap, site_bytes, indiv_bytes, n_declined);
-    } catch (const std::bad_alloc &) {
-        return prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        return prep_fail(M6A_EIO, "unexpected exception");
-    }
+    });
 }
 
 extern "C" int m6a_prep_sites_write_csv(m6a_prep_sites *p, const char *out_dir, int write_header, int64_t n_sites_limit, int n_threads,
@@ -673,14 +658,7 @@ extern "C" int m6a_prep_sites_write_csv(m6a_prep_sites *p, const char *out_dir, 
 {
     if (!p || !out_dir) return prep_fail(M6A_EINVAL, "null argument");
     m6a_csv_stats st{};
-    int rc;
-    try {
-        rc = csv_write_impl(*p, out_dir, write_header, n_sites_limit, n_threads, st);
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+    const int rc = guarded([&] { return csv_write_impl(*p, out_dir, write_header, n_sites_limit, n_threads, st); });
     if (stats) *stats = st;
     return rc;
 }

@@ -1,6 +1,6 @@
 // m6a_dataprep.h -- eventalign.index, data.json, data.info and data.log written from the device (include/m6a.h: m6a_repr_format,
-// m6a_prep_dataprep_write).  Part of m6a_prep.hip's translation unit, behind m6a_csv.h (it uses that file's csv_emit, rounds and
-// pwrite helpers, and m6a_prep.hip's DevMem, scans, RowSrc and RunDev); not a file to compile on its own.
+// m6a_prep_dataprep_write).  Part of m6a_prep.hip's translation unit, behind m6a_csv.h (it uses that file's csv_emit and pwrite
+// helpers, m6a_prep_kit.h's DevMem, scans, Rounds and run_rounds, and m6a_prep.hip's RowSrc and RunDev); not a file to compile on its own.
 //
 // The bytes are the host writer's (m6a_io.cpp: emit_transcript, dataprep_impl); the numbers are m6a_repr.h's.
 //   record     {"<tx>":{"<pos>":{"<7-mer>":[[f,f,f,f,f,f,f,f,f,<read>.0],[...]]}}}\n  per kept site; as rows for csv_emit a site is its
@@ -257,52 +257,39 @@ struct TextRounds {
     }
 };
 
-// round k + 1 is formatted and copied while round k is written at file offset base + at[k]
+// round k + 1 is formatted and copied while round k is written at file offset base + at[k]; events: start, formatted, copied
 template <class Launch>
-int text_rounds_write(const TextRounds &T, CsvRound rd[2], char *const dbuf[2], Launch launch, int fd, int64_t base, int nw, const char *path,
+int text_rounds_write(const TextRounds &T, Rounds &rd, char *const dbuf[2], Launch launch, int fd, int64_t base, int nw, const char *path,
                       m6a_dataprep_stats &st)
 {
-    const int64_t n_rounds = T.n();
-    auto enqueue = [&](int64_t k) -> int {
-        CsvRound &r = rd[k & 1];
-        PCHK(hipEventRecord(r.e[0], r.s));
-        const int rc = launch(T.cut[(size_t)k], T.cut[(size_t)k + 1], dbuf[k & 1], r.s);
+    auto queue = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        PCHK(hipEventRecord(rd.e[i][0], rd.s[i]));
+        const int rc = launch(T.cut[(size_t)k], T.cut[(size_t)k + 1], dbuf[i], rd.s[i]);
         if (rc) return rc;
-        PCHK(hipEventRecord(r.e[1], r.s));
+        PCHK(hipEventRecord(rd.e[i][1], rd.s[i]));
         const int64_t n = T.at[(size_t)k + 1] - T.at[(size_t)k];
-        if (n) PCHK(hipMemcpyAsync(r.pin, dbuf[k & 1], (size_t)n, hipMemcpyDeviceToHost, r.s));
+        if (n) PCHK(hipMemcpyAsync(rd.pin[i], dbuf[i], (size_t)n, hipMemcpyDeviceToHost, rd.s[i]));
         g_d2h += n;
-        PCHK(hipEventRecord(r.e[2], r.s));
+        PCHK(hipEventRecord(rd.e[i][2], rd.s[i]));
         return M6A_OK;
     };
-    int rc;
-    if (n_rounds && (rc = enqueue(0))) return rc;
-    for (int64_t k = 0; k < n_rounds; k++) {
-        if (k + 1 < n_rounds && (rc = enqueue(k + 1))) return rc;
-        CsvRound &r = rd[k & 1];
-        PCHK(hipEventSynchronize(r.e[2]));
+    auto finish = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        PCHK(hipEventSynchronize(rd.e[i][2]));
         float fm = 0, cm = 0;
-        PCHK(hipEventElapsedTime(&fm, r.e[0], r.e[1]));
-        PCHK(hipEventElapsedTime(&cm, r.e[1], r.e[2]));
+        PCHK(hipEventElapsedTime(&fm, rd.e[i][0], rd.e[i][1]));
+        PCHK(hipEventElapsedTime(&cm, rd.e[i][1], rd.e[i][2]));
         st.ms_format += fm;
         st.ms_copy += cm;
         const double t0 = now_ms();
-        if (!csv_pwrite_threads(fd, r.pin, T.at[(size_t)k + 1] - T.at[(size_t)k], base + T.at[(size_t)k], nw)) return prep_fail(M6A_EIO, "cannot write %s", path);
+        if (!csv_pwrite_threads(fd, rd.pin[i], T.at[(size_t)k + 1] - T.at[(size_t)k], base + T.at[(size_t)k], nw)) return prep_fail(M6A_EIO, "cannot write %s", path);
         st.ms_write += now_ms() - t0;
-    }
-    st.n_rounds += n_rounds;
-    return M6A_OK;
-}
-
-bool write_all(int fd, const std::string &s)
-{
-    for (size_t got = 0; got < s.size();) {
-        const ssize_t k = ::write(fd, s.data() + got, s.size() - got);
-        if (k < 0 && errno == EINTR) continue;
-        if (k <= 0) return false;
-        got += (size_t)k;
-    }
-    return true;
+        return M6A_OK;
+    };
+    const int rc = run_rounds(T.n(), queue, finish);
+    if (!rc) st.n_rounds += T.n();
+    return rc;
 }
 
 const char kIndexHeader[] = "transcript_id,read_index,pos_start,pos_end\n";
@@ -316,13 +303,11 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
     if (NS > 0x7fffffffll) return prep_fail(M6A_EINVAL, "more than 2^31 sites");
     st.n_sites = NS;
     st.n_runs = NR;
-    CsvRound rd[2];
-    for (CsvRound &r : rd) {
-        PCHK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-        for (hipEvent_t &x : r.e) PCHK(hipEventCreate(&x));
-    }
+    Rounds rd;
+    int rc = rd.open(3);
+    if (rc) return rc;
     PCHK(hipStreamSynchronize(s0));                         // the back half's arrays are complete
-    hipStream_t s = rd[0].s;
+    hipStream_t s = rd.s[0];
     double t0 = now_ms();
 
     // ---- the small uploads, lengths and offsets of the whole job
@@ -330,7 +315,6 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
     int64_t *tx_off, *joff, *xoff, *xcut;
     unsigned long long *dd, hd = 0;
     const size_t nblob = src.blob->size();
-    int rc;
     if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)NT + 1, "transcript names")) ||
         (rc = m.alloc(logged, (size_t)NT + 1, "transcripts")) || (rc = m.alloc(joff, (size_t)NS + 1, "data.json offsets")) ||
         (rc = m.alloc(xoff, (size_t)NR + 1, "index offsets")) || (rc = m.alloc(dd, 1, "flags")))
@@ -358,8 +342,7 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
         PCHK(hipGetLastError());
     }
     if ((rc = scan_excl(m, joff, NS + 1, s)) || (rc = scan_excl(m, xoff, NR + 1, s))) return rc;
-    const char *rk = getenv("M6A_JSON_ROUND_KB");
-    const int64_t round_bytes = (rk && atoll(rk) > 0 ? atoll(rk) : kJsonRoundKB) << 10;
+    const int64_t round_bytes = round_kb("M6A_JSON_ROUND_KB", kJsonRoundKB) << 10;
     // index rows come back as one offset per block of q rows (q rows are about a sixteenth of a round)
     const int64_t q = std::max<int64_t>(kCsvWave, round_bytes / 1024), nc = (NR + q - 1) / q + 1;
     if ((rc = m.alloc(xcut, (size_t)nc, "index offsets"))) return rc;
@@ -383,15 +366,8 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
 
     // ---- rounds of whole sites, and of whole blocks of index rows
     TextRounds J, X;
-    while (J.cut.back() < NS) {
-        const int64_t a = J.cut.back();
-        int64_t lo = a + 1, hi = NS;                        // the last b with text(a, b) <= round_bytes, at least a + 1
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) / 2;
-            if (hj[(size_t)mid] - hj[(size_t)a] <= round_bytes) lo = mid; else hi = mid - 1;
-        }
-        J.add(lo, hj[(size_t)lo]);
-    }
+    m6a_rounds::cut_rounds(NS, round_bytes, [&](int64_t a, int64_t b) { return hj[(size_t)b] - hj[(size_t)a]; },
+                           [&](int64_t, int64_t b) { J.add(b, hj[(size_t)b]); });
     for (int64_t c = 0; c + 1 < nc;) {
         int64_t e = c + 1;
         while (e + 1 < nc && hcut[(size_t)e + 1] - hcut[(size_t)c] <= round_bytes) ++e;
@@ -401,8 +377,7 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
     const int64_t cap = std::max<int64_t>(std::max(J.cap, X.cap), 16);
     char *dbuf[2] = {nullptr, nullptr};
     for (int i = 0; i < (J.n() > 1 || X.n() > 1 ? 2 : 1); i++) {
-        if ((rc = m.alloc(dbuf[i], (size_t)cap, "text"))) return rc;
-        PCHK(hipHostMalloc((void **)&rd[i].pin, (size_t)cap, hipHostMallocDefault));
+        if ((rc = m.alloc(dbuf[i], (size_t)cap, "text")) || (rc = rd.pinned(i, cap))) return rc;
     }
 
     // ---- the files
@@ -437,18 +412,18 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
                                (long long)(hoff[(size_t)i + 1] - hoff[(size_t)i]));
         text.append(num, (size_t)k);
         if (text.size() >= ((size_t)4 << 20) || i == NS - 1) {
-            if (!write_all(F.fd[2], text)) return prep_fail(M6A_EIO, "cannot write %s", F.path[2].c_str());
+            if ((rc = write_fully(F.fd[2], text.data(), text.size(), F.path[2].c_str()))) return rc;
             text.clear();
         }
     }
-    if (!text.empty() && !write_all(F.fd[2], text)) return prep_fail(M6A_EIO, "cannot write %s", F.path[2].c_str());
+    if (!text.empty() && (rc = write_fully(F.fd[2], text.data(), text.size(), F.path[2].c_str()))) return rc;
     text.clear();
     for (int64_t t = 0; t < NT; t++) {
         if (!hlog[(size_t)t]) continue;
         text.append(names, (size_t)to[(size_t)t], (size_t)(to[(size_t)t + 1] - to[(size_t)t]));
         text += ": Data preparation ... Done.\n";
     }
-    if (!write_all(F.fd[3], text)) return prep_fail(M6A_EIO, "cannot write %s", F.path[3].c_str());
+    if ((rc = write_fully(F.fd[3], text.data(), text.size(), F.path[3].c_str()))) return rc;
     if ((rc = F.close_all(job.out_dir))) return rc;
     st.ms_write += now_ms() - t0;
     F.keep = true;
@@ -460,9 +435,8 @@ int repr_format_impl(int device_id, const double *v, int64_t n, int round3, char
     if (n < 0 || (n && !v) || !off || !n_declined) return prep_fail(M6A_EINVAL, "null argument");
     if (n > 0x7fffffffll * kCsvWave) return prep_fail(M6A_EINVAL, "more than 2^37 values");
     DevMem m;
-    int rc = csv_device(device_id, m);
+    int rc = open_device(device_id, m, "format fewer values per call");
     if (rc) return rc;
-    m.advice = "format fewer values per call";
     Streams st;
     PCHK(hipStreamCreateWithFlags(&st.s[0], hipStreamNonBlocking));
     hipStream_t s = st.s[0];
@@ -498,13 +472,7 @@ int repr_format_impl(int device_id, const double *v, int64_t n, int round3, char
 
 extern "C" int m6a_repr_format(int device_id, const double *v, int64_t n, int round3, char *text, int64_t cap, int64_t *off, int64_t *n_declined)
 {
-    try {
-        return repr_format_impl(device_id, v, n, round3, text, cap, off, n_declined);
-    } catch (const std::bad_alloc &) {
-        return prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        return prep_fail(M6A_EIO, "unexpected exception");
-    }
+    return guarded([&] { return repr_format_impl(device_id, v, n, round3, text, cap, off, n_declined); });
 }
 
 extern "C" int m6a_prep_dataprep_write(int device_id, const char *path, const char *out_dir, int readcount_min, int readcount_max,
@@ -514,24 +482,20 @@ extern "C" int m6a_prep_dataprep_write(int device_id, const char *path, const ch
     m6a_dataprep_stats st{};
     int rc;
     if (!path || !out_dir) rc = prep_fail(M6A_EINVAL, "null argument");
-    else {
-        try {
+    else
+        rc = guarded([&] {
             g_d2h = 0;
             DevMem m;                                       // its advice is the budget error's `use --device cpu`
             m6a_prep_sites P;
             P.device = device_id;
             const DataprepJob job{out_dir, compress, n_threads, &st};
             double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            rc = sites_impl(device_id, path, readcount_min, readcount_max, min_segment_count, nullptr, nullptr, nullptr, 0, host, n_threads,
-                            window_from_env(), P, m, ms, nullptr, &job);
+            const int rc2 = sites_impl(device_id, path, readcount_min, readcount_max, min_segment_count, nullptr, nullptr, nullptr, 0, host,
+                                       n_threads, window_from_env(), P, m, ms, nullptr, &job);
             st.d2h_bytes = g_d2h;
             st.peak_bytes = (int64_t)m.peak;
-        } catch (const std::bad_alloc &) {
-            rc = prep_fail(M6A_ENOMEM, "out of host memory");
-        } catch (...) {
-            rc = prep_fail(M6A_EIO, "unexpected exception");
-        }
-    }
+            return rc2;
+        });
     if (stats) *stats = st;
     return rc;
 }

@@ -655,8 +655,8 @@ inline int64_t blocks_host(const uint8_t *text, int64_t n, int level, uint8_t *o
 }  // namespace m6a_deflate
 
 #ifdef M6A_DEFLATE_DEVICE_PART
-// ---- part 2: kernels and the two entry points (inside m6a_prep.hip, behind m6a_csv.h: DevMem, PCHK, prep_fail, now_ms, g_d2h, Fd and
-// the CSV writer's plan, launch and pwrite helpers are theirs) ----
+// ---- part 2: kernels and the two entry points (inside m6a_prep.hip, behind m6a_csv.h: DevMem, PCHK, prep_fail, now_ms, g_d2h, Rounds
+// and run_rounds are m6a_prep_kit.h's; CsvJob and the CSV writer's plan, launch and pwrite helpers are m6a_csv.h's) ----
 namespace m6a_deflate {
 namespace {
 
@@ -851,9 +851,8 @@ int deflate_impl(int device_id, const uint8_t *text, int64_t n, int level, uint8
                  int64_t *n_by_type)
 {
     DevMem m;
-    int rc = csv_device(device_id, m);
+    int rc = open_device(device_id, m, "deflate it on the host, or in pieces");
     if (rc) return rc;
-    m.advice = "deflate it on the host, or in pieces";
     g_d2h = 0;
     Streams S;
     PCHK(hipStreamCreateWithFlags(&S.s[0], hipStreamNonBlocking));
@@ -891,195 +890,112 @@ int deflate_impl(int device_id, const uint8_t *text, int64_t n, int level, uint8
     return M6A_OK;
 }
 
-struct DeflRound {                         // stream, events, device and pinned buffers of one of the two rounds in flight
-    hipStream_t s = nullptr;
-    hipEvent_t e[6] = {};                  // start, formatted, deflated, status copied, copy begins, copied
-    uint8_t *text = nullptr, *slots = nullptr, *pin = nullptr;
+struct DeflBufs {                          // beside a round's stream, events and pinned buffer (Rounds): its device buffers and status words
+    uint8_t *text = nullptr, *slots = nullptr;
     int64_t *size = nullptr;
-    unsigned long long *status = nullptr, *hstatus = nullptr;
-    ~DeflRound()
-    {
-        if (s) (void)hipStreamSynchronize(s);
-        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-        if (pin) (void)hipHostFree(pin);
-        if (hstatus) (void)hipHostFree(hstatus);
-        if (s) (void)hipStreamDestroy(s);
-    }
+    unsigned long long *status = nullptr, *hstatus = nullptr;          // hstatus is pinned
+    ~DeflBufs() { if (hstatus) (void)hipHostFree(hstatus); }
 };
 
 // the header line of a file as a BGZF block of its own, made by the host core at the writer's level
-std::vector<uint8_t> header_block(const char *line, int32_t n, int level, int64_t *n_by_type)
+std::string header_block(const char *line, int32_t n, int level, int64_t *n_by_type)
 {
-    std::vector<uint8_t> blk((size_t)kSlot);
-    blk.resize((size_t)blocks_host((const uint8_t *)line, n, level, blk.data(), n_by_type));
+    std::string blk((size_t)kSlot, '\0');
+    blk.resize((size_t)blocks_host((const uint8_t *)line, n, level, (uint8_t *)&blk[0], n_by_type));
     return blk;
 }
 
 int csv_write_bgzf_impl(m6a_prep_sites &P, const char *out_dir, int write_header, int64_t n_limit, int n_threads, int level, m6a_csv_bgzf_stats &st,
                         int64_t *by_type)
 {
-    const m6a_prep_sites_info &I = P.info;
-    const int64_t S = n_limit >= 0 ? std::min<int64_t>(n_limit, I.n_sites) : I.n_sites;
-    if (I.n_sites && !P.csv_ids) return prep_fail(M6A_EINVAL, "the handle holds no read ids on the device");
-    const int nw = n_threads > 0 ? n_threads : m6a_usable_cpus();
-    DevMem m;
-    int rc = csv_device(P.device, m);
-    if (rc) return rc;
-    g_d2h = 0;
-    struct Account {                       // whatever way the call ends, what it copied and allocated is reported
-        m6a_prep_sites &P; DevMem &m; m6a_csv_bgzf_stats &st;
-        ~Account()
-        {
-            st.d2h_bytes = g_d2h;
-            P.info.d2h_bytes += g_d2h;
-            P.info.peak_bytes = std::max<int64_t>(P.info.peak_bytes, (int64_t)(P.held + m.peak));
-        }
-    } account{P, m, st};
     const int words = status_words(level);
     int64_t none[3], *const n_by_type = by_type ? by_type : none;
     n_by_type[0] = n_by_type[1] = n_by_type[2] = 0;
-    DeflRound rd[2];
-    for (DeflRound &r : rd) {
-        PCHK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-        for (hipEvent_t &x : r.e) PCHK(hipEventCreate(&x));
-    }
-    hipStream_t s = rd[0].s;
-
-    // ---- the small uploads, lengths and offsets of the whole job, and the rounds: as the plain writer's
-    uint8_t *blob;
-    int64_t *tx_off;
-    const size_t nblob = (size_t)(I.n_tx ? I.tx_off[I.n_tx] : 0);
-    if ((rc = m.alloc(blob, nblob + 1, "transcript names")) || (rc = m.alloc(tx_off, (size_t)I.n_tx + 1, "transcript names"))) return rc;
-    if ((rc = h2d(blob, (const uint8_t *)I.tx_blob, nblob, s)) || (rc = h2d(tx_off, I.tx_off, I.n_tx ? (size_t)I.n_tx + 1 : 0, s))) return rc;
-    const CsvDev d{I.off, P.csv_tx, P.csv_pos, P.csv_k7, 7, 1, blob, tx_off, P.csv_ids, nullptr, I.n_rep > 1 ? P.csv_parts : nullptr,
-                   I.n_rep > 1 ? I.n_rep : 1, I.read_prob, I.site_prob, I.mod_ratio, P.csv_names, P.csv_name_off};
-    double t0 = now_ms();
-    CsvPlan plan;
-    if ((rc = csv_plan(m, d, 0, S, s, plan))) return rc;
-    st.ms_format += now_ms() - t0;
-    st.n_declined = plan.declined;
-    st.site_bytes = plan.site[(size_t)S];
-    st.indiv_bytes = plan.indiv[(size_t)S];
-    if (plan.declined)
-        return prep_fail(M6A_EDECLINED, "%lld values are outside what the device formats (a probability or ratio that is negative or >= 2, "
-                         "a read index that is not an integer in [0, 10^15))", (long long)plan.declined);
-    const char *rk = getenv("M6A_CSV_ROUND_KB");
-    const int64_t round_bytes = (rk && atoll(rk) > 0 ? atoll(rk) : kCsvRoundKB) << 10;
-    std::vector<int64_t> cut{0};
+    CsvJob<m6a_csv_bgzf_stats> J(P, st);
+    DeflBufs bufs[2];                                       // outlive the streams of rd
+    Rounds rd;                                              // events: start, formatted, deflated, status copied, copy begins, copied
     int64_t cap_text = 0, cap_blocks = 0;
-    auto ni_of = [&](int64_t a, int64_t b) { return plan.indiv[(size_t)b] - plan.indiv[(size_t)a]; };
-    auto ns_of = [&](int64_t a, int64_t b) { return plan.site[(size_t)b] - plan.site[(size_t)a]; };
-    while (cut.back() < S) {
-        const int64_t a = cut.back();
-        int64_t lo = a + 1, hi = S;                          // the last b with the text of [a, b) <= round_bytes, at least a + 1
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) / 2;
-            if (ni_of(a, mid) + ns_of(a, mid) <= round_bytes) lo = mid; else hi = mid - 1;
-        }
-        cut.push_back(lo);
-        const int64_t ni = ni_of(a, lo), ns = ns_of(a, lo);
+    int rc = J.begin(n_limit, n_threads, rd, 6, [&](int64_t ni, int64_t ns) {
         cap_text = std::max(cap_text, std::max(csv_align(ni) + ns, packed_room(ni, ns)));
         cap_blocks = std::max(cap_blocks, n_blocks(ni) + n_blocks(ns));
-    }
-    const int64_t n_rounds = (int64_t)cut.size() - 1;
-    st.n_rounds = n_rounds;
-
-    // ---- every buffer before a file is opened: over the budget nothing is touched
+    });
+    if (rc) return rc;
+    const int64_t n_rounds = J.n_rounds();
     for (int i = 0; i < (n_rounds > 1 ? 2 : n_rounds ? 1 : 0); i++) {
-        DeflRound &r = rd[i];
-        if ((rc = m.alloc(r.text, (size_t)cap_text, "CSV text")) || (rc = m.alloc(r.slots, (size_t)(cap_blocks * kSlot), "BGZF slots")) ||
-            (rc = m.alloc(r.size, (size_t)cap_blocks + 1, "BGZF sizes")) || (rc = m.alloc(r.status, (size_t)words, "flags")))
+        DeflBufs &r = bufs[i];
+        if ((rc = J.m.alloc(r.text, (size_t)cap_text, "CSV text")) || (rc = J.m.alloc(r.slots, (size_t)(cap_blocks * kSlot), "BGZF slots")) ||
+            (rc = J.m.alloc(r.size, (size_t)cap_blocks + 1, "BGZF sizes")) || (rc = J.m.alloc(r.status, (size_t)words, "flags")) ||
+            (rc = rd.pinned(i, cap_text)))
             return rc;
-        PCHK(hipHostMalloc((void **)&r.pin, (size_t)std::max<int64_t>(cap_text, 16), hipHostMallocDefault));
         PCHK(hipHostMalloc((void **)&r.hstatus, (size_t)words * sizeof *r.hstatus, hipHostMallocDefault));
     }
-
-    // ---- the files: the header line is a block of its own
-    const std::string fs = std::string(out_dir) + "/data.site_proba.csv.gz", fi = std::string(out_dir) + "/data.indiv_proba.csv.gz";
-    const int flags = O_WRONLY | O_CREAT | (write_header ? O_TRUNC : 0);
-    Fd f, g;
-    f.fd = ::open(fs.c_str(), flags, 0644);
-    if (f.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fs.c_str());
-    g.fd = ::open(fi.c_str(), flags, 0644);
-    if (g.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", fi.c_str());
-    int64_t at_site = 0, at_indiv = 0;
-    if (write_header) {
-        const std::vector<uint8_t> hs = header_block(kCsvSiteHeader, (int32_t)sizeof(kCsvSiteHeader) - 1, level, n_by_type),
-                                   hi = header_block(kCsvIndivHeader, (int32_t)sizeof(kCsvIndivHeader) - 1, level, n_by_type);
-        at_site = (int64_t)hs.size();
-        at_indiv = (int64_t)hi.size();
-        st.n_blocks += 2;
-        if (!csv_pwrite_all(f.fd, (const char *)hs.data(), at_site, 0)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
-        if (!csv_pwrite_all(g.fd, (const char *)hi.data(), at_indiv, 0)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
-    } else {                                                // append: behind whatever the files hold (an earlier marker is an empty block)
-        struct stat sb;
-        if (fstat(f.fd, &sb) != 0) return prep_fail(M6A_EIO, "cannot stat %s", fs.c_str());
-        at_site = (int64_t)sb.st_size;
-        if (fstat(g.fd, &sb) != 0) return prep_fail(M6A_EIO, "cannot stat %s", fi.c_str());
-        at_indiv = (int64_t)sb.st_size;
-    }
-    const int64_t site0 = at_site, indiv0 = at_indiv;
+    // the header line is a block of its own; appended to, an earlier end marker stays in the middle as an empty block
+    if ((rc = J.open_files(out_dir, ".gz", write_header, [&](const char *line, int32_t n) { ++st.n_blocks; return header_block(line, n, level, n_by_type); })))
+        return rc;
+    const int64_t site0 = J.at_site, indiv0 = J.at_indiv;
+    int64_t at_site = site0, at_indiv = indiv0;
 
     // ---- round k + 1 is formatted and deflated while round k is copied and written
-    auto enqueue = [&](int64_t k) -> int {
-        DeflRound &r = rd[k & 1];
-        const int64_t a = cut[(size_t)k], b = cut[(size_t)k + 1], ni = ni_of(a, b), ns = ns_of(a, b);
-        PCHK(hipEventRecord(r.e[0], r.s));
-        int rc2 = csv_launch(d, plan, 0, a, b, (char *)r.text, csv_align(ni), r.s);
+    auto queue = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        DeflBufs &r = bufs[i];
+        hipStream_t s = rd.s[i];
+        const int64_t a = J.cut[(size_t)k], b = J.cut[(size_t)k + 1], ni = J.ni(a, b), ns = J.ns(a, b);
+        PCHK(hipEventRecord(rd.e[i][0], s));
+        int rc2 = csv_launch(J.d, J.plan, 0, a, b, (char *)r.text, csv_align(ni), s);
         if (rc2) return rc2;
-        PCHK(hipEventRecord(r.e[1], r.s));
-        if ((rc2 = deflate_launch(DeflText{r.text, ni, csv_align(ni), ns}, r.slots, r.size, r.status, r.text, r.s, level))) return rc2;
-        PCHK(hipEventRecord(r.e[2], r.s));
-        PCHK(hipMemcpyAsync(r.hstatus, r.status, (size_t)words * sizeof *r.status, hipMemcpyDeviceToHost, r.s));
+        PCHK(hipEventRecord(rd.e[i][1], s));
+        if ((rc2 = deflate_launch(DeflText{r.text, ni, csv_align(ni), ns}, r.slots, r.size, r.status, r.text, s, level))) return rc2;
+        PCHK(hipEventRecord(rd.e[i][2], s));
+        PCHK(hipMemcpyAsync(r.hstatus, r.status, (size_t)words * sizeof *r.status, hipMemcpyDeviceToHost, s));
         g_d2h += (int64_t)((size_t)words * sizeof *r.status);
-        PCHK(hipEventRecord(r.e[3], r.s));
+        PCHK(hipEventRecord(rd.e[i][3], s));
         st.n_blocks += n_blocks(ni) + n_blocks(ns);
         return M6A_OK;
     };
-    if (n_rounds && (rc = enqueue(0))) return rc;
-    for (int64_t k = 0; k < n_rounds; k++) {
-        DeflRound &r = rd[k & 1];
-        PCHK(hipEventSynchronize(r.e[3]));
-        const int64_t ci = (int64_t)r.hstatus[0], ct = (int64_t)r.hstatus[1];
-        st.n_stored += (int64_t)r.hstatus[2];
-        {
-            const int64_t a = cut[(size_t)k], b = cut[(size_t)k + 1], nb = n_blocks(ni_of(a, b)) + n_blocks(ns_of(a, b));
-            const int64_t dyn = level == 2 ? (int64_t)r.hstatus[3] : 0;
-            n_by_type[0] += (int64_t)r.hstatus[2];
-            n_by_type[2] += dyn;
-            n_by_type[1] += nb - (int64_t)r.hstatus[2] - dyn;
-        }
-        PCHK(hipEventRecord(r.e[4], r.s));
-        if (ct) PCHK(hipMemcpyAsync(r.pin, r.text, (size_t)ct, hipMemcpyDeviceToHost, r.s));
+    auto settle = [&](int64_t k) -> int {                   // the status words say how many bytes the payload copy takes
+        const int i = (int)(k & 1);
+        DeflBufs &r = bufs[i];
+        PCHK(hipEventSynchronize(rd.e[i][3]));
+        const int64_t a = J.cut[(size_t)k], b = J.cut[(size_t)k + 1], nb = n_blocks(J.ni(a, b)) + n_blocks(J.ns(a, b));
+        const int64_t ct = (int64_t)r.hstatus[1], stored = (int64_t)r.hstatus[2], dyn = level == 2 ? (int64_t)r.hstatus[3] : 0;
+        st.n_stored += stored;
+        n_by_type[0] += stored;
+        n_by_type[2] += dyn;
+        n_by_type[1] += nb - stored - dyn;
+        PCHK(hipEventRecord(rd.e[i][4], rd.s[i]));
+        if (ct) PCHK(hipMemcpyAsync(rd.pin[i], r.text, (size_t)ct, hipMemcpyDeviceToHost, rd.s[i]));
         g_d2h += ct;
-        PCHK(hipEventRecord(r.e[5], r.s));
-        if (k + 1 < n_rounds && (rc = enqueue(k + 1))) return rc;
-        PCHK(hipEventSynchronize(r.e[5]));
+        PCHK(hipEventRecord(rd.e[i][5], rd.s[i]));
+        return M6A_OK;
+    };
+    auto finish = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        PCHK(hipEventSynchronize(rd.e[i][5]));
         float fm = 0, dm = 0, cm = 0;
-        PCHK(hipEventElapsedTime(&fm, r.e[0], r.e[1]));
-        PCHK(hipEventElapsedTime(&dm, r.e[1], r.e[2]));
-        PCHK(hipEventElapsedTime(&cm, r.e[4], r.e[5]));
+        PCHK(hipEventElapsedTime(&fm, rd.e[i][0], rd.e[i][1]));
+        PCHK(hipEventElapsedTime(&dm, rd.e[i][1], rd.e[i][2]));
+        PCHK(hipEventElapsedTime(&cm, rd.e[i][4], rd.e[i][5]));
         st.ms_format += fm;
         st.ms_deflate += dm;
         st.ms_copy += cm;
-        t0 = now_ms();
-        if (!csv_pwrite_threads(g.fd, (const char *)r.pin, ci, at_indiv, nw)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
-        if (!csv_pwrite_all(f.fd, (const char *)r.pin + ci, ct - ci, at_site)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
+        const int64_t ci = (int64_t)bufs[i].hstatus[0], ct = (int64_t)bufs[i].hstatus[1];
+        const double t0 = now_ms();
+        if (!csv_pwrite_threads(J.g.fd, rd.pin[i], ci, at_indiv, J.nw)) return prep_fail(M6A_EIO, "cannot write %s", J.fi.c_str());
+        if (!csv_pwrite_all(J.f.fd, rd.pin[i] + ci, ct - ci, at_site)) return prep_fail(M6A_EIO, "cannot write %s", J.fs.c_str());
         st.ms_write += now_ms() - t0;
         at_indiv += ci;
         at_site += ct - ci;
-    }
+        return M6A_OK;
+    };
+    if ((rc = run_rounds(n_rounds, queue, settle, finish))) return rc;
     char eof[kEofBytes];
     for (int i = 0; i < kEofBytes; i++) eof[i] = (char)eof_byte(i);
-    if (!csv_pwrite_all(f.fd, eof, kEofBytes, at_site)) return prep_fail(M6A_EIO, "cannot write %s", fs.c_str());
-    if (!csv_pwrite_all(g.fd, eof, kEofBytes, at_indiv)) return prep_fail(M6A_EIO, "cannot write %s", fi.c_str());
+    if (!csv_pwrite_all(J.f.fd, eof, kEofBytes, at_site)) return prep_fail(M6A_EIO, "cannot write %s", J.fs.c_str());
+    if (!csv_pwrite_all(J.g.fd, eof, kEofBytes, at_indiv)) return prep_fail(M6A_EIO, "cannot write %s", J.fi.c_str());
     st.site_compressed = at_site + kEofBytes - (write_header ? 0 : site0);
     st.indiv_compressed = at_indiv + kEofBytes - (write_header ? 0 : indiv0);
-    const int cf = ::close(f.fd), cg = ::close(g.fd);
-    f.fd = g.fd = -1;
-    if (cf != 0) return prep_fail(M6A_EIO, "cannot close %s", fs.c_str());
-    if (cg != 0) return prep_fail(M6A_EIO, "cannot close %s", fi.c_str());
-    return M6A_OK;
+    return J.close_files();
 }
 
 }  // namespace
@@ -1095,14 +1011,7 @@ extern "C" int m6a_bgzf_deflate_level(int device_id, const char *text, int64_t n
     if (n_by_type) n_by_type[0] = n_by_type[1] = n_by_type[2] = 0;
     if (!out) return M6A_OK;                               // the sizing call
     m6a_deflate_stats st{};
-    int rc;
-    try {
-        rc = m6a_deflate::deflate_impl(device_id, (const uint8_t *)text, n, level, (uint8_t *)out, cap, n_bytes, st, n_by_type);
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+    const int rc = guarded([&] { return m6a_deflate::deflate_impl(device_id, (const uint8_t *)text, n, level, (uint8_t *)out, cap, n_bytes, st, n_by_type); });
     if (stats) *stats = st;
     return rc;
 }
@@ -1119,14 +1028,7 @@ extern "C" int m6a_prep_sites_write_csv_bgzf_level(m6a_prep_sites *p, const char
     if (level != 1 && level != 2) return prep_fail(M6A_EINVAL, "level %d: the BGZF writer has levels 1 and 2", level);
     if (n_by_type) n_by_type[0] = n_by_type[1] = n_by_type[2] = 0;
     m6a_csv_bgzf_stats st{};
-    int rc;
-    try {
-        rc = m6a_deflate::csv_write_bgzf_impl(*p, out_dir, write_header, n_sites_limit, n_threads, level, st, n_by_type);
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+    const int rc = guarded([&] { return m6a_deflate::csv_write_bgzf_impl(*p, out_dir, write_header, n_sites_limit, n_threads, level, st, n_by_type); });
     if (stats) *stats = st;
     return rc;
 }

@@ -303,7 +303,7 @@ M6A_HD inline int walk(const uint8_t *p, const uint8_t *e, const uint8_t *tx, in
 
 #if defined(M6A_JSON_DEVICE_PART) && !defined(M6A_JSON_DEVICE_PART_DONE)
 #define M6A_JSON_DEVICE_PART_DONE
-// ---- part 2: the kernels and m6a_json_sites_build; at the end of m6a_prep.hip, whose DevMem, Streams and helpers it uses ----------
+// ---- part 2: the kernels and m6a_json_sites_build; at the end of m6a_prep.hip; DevMem, Streams, upload_range: m6a_prep_kit.h ----
 namespace {
 
 using namespace m6a_json;
@@ -518,35 +518,12 @@ int json_impl(int device_id, const char *dir, int min_reads, const char *norm_km
     double host_ms = now_ms() - t1;
 
     // ---- device memory: the file, the table and everything the handle keeps, all under the budget before a byte goes up
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
-    if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
-    PCHK(hipSetDevice(device_id));
     DevMem m;
-    m.advice = "run `inference --loader host` (the default), which streams X from host memory";
-    {
-        m.budget_set = true;
-        size_t fr = 0, tot = 0;
-        PCHK(hipMemGetInfo(&fr, &tot));
-        const size_t margin = std::min<size_t>(fr / 16, (size_t)4 << 30);
-        m.budget = fr > margin ? fr - margin : 0;
-        const char *b = getenv("M6A_PREP_BUDGET_MB");
-        if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
-    }
+    if ((rc = open_device(device_id, m, "run `inference --loader host` (the default), which streams X from host memory"))) return rc;
     const int64_t nb = std::max<int64_t>(1, (n + kScanBytes - 1) / kScanBytes);
     std::vector<uint64_t> nk, voc = vocab_keys();
     std::vector<int32_t> nix;
-    {
-        std::vector<std::pair<uint64_t, int32_t>> norm;
-        for (int i = 0; i < n_norm; i++) {
-            uint64_t x = 0;
-            for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)norm_kmers[5 * i + j];
-            norm.emplace_back(x, i);
-        }
-        std::sort(norm.begin(), norm.end());                   // a repeated 5-mer: the loader's map keeps the first
-        for (size_t i = 0; i < norm.size(); i++)
-            if (i == 0 || norm[i].first != norm[i - 1].first) { nk.push_back(norm[i].first); nix.push_back(norm[i].second); }
-    }
+    norm_keys(norm_kmers, n_norm, nk, nix);
     uint8_t *df, *dblob, *site_kmers, *site_k7, *dstatus;
     JsonSite *dsites;
     int64_t *doff, *dtx_off, *site_pos;
@@ -570,18 +547,10 @@ int json_impl(int device_id, const char *dir, int min_reads, const char *norm_km
 
     // ---- upload: data.json whole through the pinned pair; the table goes up beside it
     Streams St;
-    for (int i = 0; i < 2; i++) {
-        PCHK(hipStreamCreateWithFlags(&St.s[i], hipStreamNonBlocking));
-        PCHK(hipEventCreateWithFlags(&St.copied[i], hipEventDisableTiming));
-    }
+    int64_t chunk = 0;
+    if ((rc = St.open(nb * kScanBytes, chunk))) return rc;
     hipStream_t s = St.s[0];
-    const char *ck = getenv("M6A_PREP_CHUNK_KB");
-    int64_t chunk = (ck && atoll(ck) > 0 ? atoll(ck) : 65536) << 10;
-    chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
-    chunk = std::min<int64_t>(chunk, nb * kScanBytes);
-    for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&St.pin[i], (size_t)chunk, hipHostMallocDefault));
     const double t_up = now_ms();
-    PCHK(hipMemsetAsync(df + (nb - 1) * kScanBytes, 0, (size_t)kScanBytes, St.s[1]));         // the zero padding of the last block
     if ((rc = h2d(dsites, hs.data(), (size_t)S, s)) || (rc = h2d(doff, P.off.data(), (size_t)S + 1, s)) ||
         (rc = h2d(dblob, (const uint8_t *)P.blob.data(), P.blob.size(), s)) || (rc = h2d(dtx_off, P.tx_off.data(), P.tx_off.size(), s)) ||
         (rc = h2d(site_tx, P.tx.data(), (size_t)S, s)) || (rc = h2d(site_pos, P.pos.data(), (size_t)S, s)) ||
@@ -592,19 +561,8 @@ int json_impl(int device_id, const char *dir, int min_reads, const char *norm_km
     // in the pinned chunk that holds its first byte, under that chunk's copy, with the core the kernels compile.
     size_t nxt = 0;
     std::vector<uint8_t> edge;
-    for (int64_t k = 0, at = 0; at < n; k++, at += chunk) {
-        const int slot = (int)(k & 1);
-        PCHK(hipEventSynchronize(St.copied[slot]));
-        const int64_t len = std::min(chunk, n - at);
-        uint8_t *const pin = (uint8_t *)St.pin[slot];
-        for (int64_t got = 0; got < len;) {
-            const ssize_t r = ::pread(fd.fd, pin + got, (size_t)(len - got), (off_t)(at + got));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path.c_str());
-            got += r;
-        }
-        PCHK(hipMemcpyAsync(df + at, pin, (size_t)len, hipMemcpyHostToDevice, St.s[1]));
-        PCHK(hipEventRecord(St.copied[slot], St.s[1]));
+    rc = upload_range(device_id, fd.fd, path.c_str(), St, df, 0, n, chunk, [&](int slot, int64_t at, int64_t len) -> int {
+        const uint8_t *const pin = (const uint8_t *)St.pin[slot];
         for (; nxt < order.size() && hs[order[nxt]].start < at + len; nxt++) {
             const uint32_t i = order[nxt];
             const JsonSite &h = hs[i];
@@ -614,13 +572,8 @@ int json_impl(int device_id, const char *dir, int min_reads, const char *norm_km
             int r = header(pin + (h.start - at), pin + (std::min(h.end, at + len) - at), tx, tx_len, h.pos, &k7, &body);
             if (r && h.end > at + len) {                    // the header may straddle the chunk's end: its bytes from the file
                 edge.resize((size_t)std::min<int64_t>(h.end - h.start, tx_len + 4096));
-                size_t got = 0;
-                while (got < edge.size()) {
-                    const ssize_t q = ::pread(fd.fd, edge.data() + got, edge.size() - got, (off_t)(h.start + (int64_t)got));
-                    if (q < 0 && errno == EINTR) continue;
-                    if (q <= 0) return prep_fail(M6A_EIO, "cannot read %s", path.c_str());
-                    got += (size_t)q;
-                }
+                const int rc2 = read_fully(fd.fd, edge.data(), (int64_t)edge.size(), h.start, path.c_str());
+                if (rc2) return rc2;
                 r = header(edge.data(), edge.data() + edge.size(), tx, tx_len, h.pos, &k7, &body);
             }
             if (!r) {
@@ -628,8 +581,9 @@ int json_impl(int device_id, const char *dir, int min_reads, const char *norm_km
                 take[i] = 1;
             }
         }
-    }
-    PCHK(hipStreamSynchronize(St.s[1]));
+        return M6A_OK;
+    });
+    if (rc) return rc;
     PCHK(hipStreamSynchronize(s));
     ms[0] = now_ms() - t_up;
     ms[6] = ms[0] > 0 ? (double)n / (ms[0] * 1e6) : 0;
@@ -723,14 +677,7 @@ extern "C" int m6a_json_sites_build(int device_id, const char *const *dirs, int 
     m6a_prep_sites *p = new (std::nothrow) m6a_prep_sites;
     if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
     p->device = device_id;
-    int rc;
-    try {
-        rc = json_impl(device_id, dirs[0], min_reads, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, *p);
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+    const int rc = guarded([&] { return json_impl(device_id, dirs[0], min_reads, norm_kmers, norm_mean, norm_std, n_norm, host, n_threads, *p); });
     if (rc) { delete p; return rc; }
     *out = p;
     return M6A_OK;

@@ -276,21 +276,8 @@ int norm_impl(int device_id, const char *json_path, int64_t S, const char *tx_bl
     const int64_t R = off[(size_t)S], E = 3 * S, blob_len = tx_off[S];
 
     // ---- device memory, all of it under the budget before a byte goes up
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
-    if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
-    PCHK(hipSetDevice(device_id));
     DevMem m;
-    m.advice = "run `compute_norm_factors --device cpu`, which sums on the host";
-    {
-        m.budget_set = true;
-        size_t fr = 0, tot = 0;
-        PCHK(hipMemGetInfo(&fr, &tot));
-        const size_t margin = std::min<size_t>(fr / 16, (size_t)4 << 30);
-        m.budget = fr > margin ? fr - margin : 0;
-        const char *b = getenv("M6A_PREP_BUDGET_MB");
-        if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
-    }
+    if ((rc = open_device(device_id, m, "run `compute_norm_factors --device cpu`, which sums on the host"))) return rc;
     uint8_t *df, *dblob, *dstatus;
     JsonSite *dsites;
     int64_t *doff, *dtx_off, *flag;
@@ -310,16 +297,9 @@ int norm_impl(int device_id, const char *json_path, int64_t S, const char *tx_bl
 
     // ---- upload: data.json whole through the pinned pair; the table goes up beside it
     Streams St;
-    for (int i = 0; i < 2; i++) {
-        PCHK(hipStreamCreateWithFlags(&St.s[i], hipStreamNonBlocking));
-        PCHK(hipEventCreateWithFlags(&St.copied[i], hipEventDisableTiming));
-    }
+    int64_t chunk = 0;
+    if ((rc = St.open(padded(n), chunk))) return rc;
     hipStream_t s = St.s[0];
-    const char *ck = getenv("M6A_PREP_CHUNK_KB");
-    int64_t chunk = (ck && atoll(ck) > 0 ? atoll(ck) : 65536) << 10;
-    chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
-    chunk = std::min<int64_t>(chunk, padded(n));
-    for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&St.pin[i], (size_t)chunk, hipHostMallocDefault));
     double t1 = now_ms();
     if ((rc = h2d(dsites, hs.data(), (size_t)S, s)) || (rc = h2d(doff, off.data(), (size_t)S + 1, s)) ||
         (rc = h2d(dblob, (const uint8_t *)tx_blob, (size_t)blob_len, s)) || (rc = h2d(dtx_off, tx_off, (size_t)S + 1, s)) ||
@@ -408,28 +388,23 @@ extern "C" int m6a_norm_factors_build(int device_id, const char *json_path, int6
         return prep_fail(M6A_EINVAL, "null argument");
     m6a_norm_stats I{};
     if (!n_sites) { if (stats) *stats = I; return M6A_OK; }
-    int rc;
-    try {
+    const int rc = guarded([&] {
         std::vector<NormRec> recs;
-        rc = norm_impl(device_id, json_path, n_sites, tx_blob, tx_off, pos, start, end, n_reads, host, n_threads, recs, status, kmer7, I);
-        if (!rc) {
-            for (size_t k = 0; k < recs.size(); k++) {             // the radix passes leave the 5-mers in bytewise order
-                const NormRec &r = recs[k];
-                for (int j = 0; j < 5; j++) kmers[5 * k + (size_t)j] = (char)(r.key >> (8 * (4 - j)));
-                N[k] = r.N;
-                for (int j = 0; j < 3; j++) {
-                    S[3 * k + (size_t)j] = r.S[j];
-                    S2[3 * k + (size_t)j] = r.S2[j];
-                    m6a_norm::finish(r.S[j], r.S2[j], r.N, mean + 3 * k + (size_t)j, sd + 3 * k + (size_t)j);
-                }
+        const int rc2 = norm_impl(device_id, json_path, n_sites, tx_blob, tx_off, pos, start, end, n_reads, host, n_threads, recs, status, kmer7, I);
+        if (rc2) return rc2;
+        for (size_t k = 0; k < recs.size(); k++) {                 // the radix passes leave the 5-mers in bytewise order
+            const NormRec &r = recs[k];
+            for (int j = 0; j < 5; j++) kmers[5 * k + (size_t)j] = (char)(r.key >> (8 * (4 - j)));
+            N[k] = r.N;
+            for (int j = 0; j < 3; j++) {
+                S[3 * k + (size_t)j] = r.S[j];
+                S2[3 * k + (size_t)j] = r.S2[j];
+                m6a_norm::finish(r.S[j], r.S2[j], r.N, mean + 3 * k + (size_t)j, sd + 3 * k + (size_t)j);
             }
-            *n_kmers = (int64_t)recs.size();
         }
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+        *n_kmers = (int64_t)recs.size();
+        return (int)M6A_OK;
+    });
     if (stats) *stats = I;
     return rc;
 }

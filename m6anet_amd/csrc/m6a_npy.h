@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+#include "m6a_rounds.h"
+
 namespace m6a_npy {
 
 constexpr int kCols = 32;                    // M6A_N_REPR
@@ -59,16 +61,10 @@ inline int64_t cut_rounds(const int64_t *off, int64_t S, int64_t round_bytes, in
     const int64_t per = round_bytes / row_bytes(dtype) > 1 ? round_bytes / row_bytes(dtype) : 1;
     int64_t widest = 0;
     cut.assign(1, 0);
-    while (cut.back() < S) {
-        const int64_t a = cut.back();
-        int64_t lo = a + 1, hi = S;          // the last b with off[b] - off[a] <= per, at least a + 1
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo + 1) / 2;
-            if (off[mid] - off[a] <= per) lo = mid; else hi = mid - 1;
-        }
-        cut.push_back(lo);
-        if (off[lo] - off[a] > widest) widest = off[lo] - off[a];
-    }
+    m6a_rounds::cut_rounds(S, per, [&](int64_t a, int64_t b) { return off[b] - off[a]; }, [&](int64_t a, int64_t b) {
+        cut.push_back(b);
+        if (off[b] - off[a] > widest) widest = off[b] - off[a];
+    });
     return widest;
 }
 

@@ -1,6 +1,6 @@
 // m6a_npy_write.h -- m6a_prep_sites_write_read_representation (include/m6a.h): data.read_representation.npy from the handle's
-// device arrays, in rounds.  Included at the end of m6a_prep.hip (DevMem, PCHK, prep_fail, Fd, now_ms, g_d2h, and the pwrite
-// helpers of m6a_csv.h); the header's bytes and the round rule are m6a_npy.h.
+// device arrays, in rounds.  Included at the end of m6a_prep.hip, behind m6a_csv.h: it uses m6a_prep_kit.h (DevMem, Rounds,
+// run_rounds, guarded) and the pwrite helpers and Account of m6a_csv.h; the header's bytes and the round rule are m6a_npy.h.
 //
 // Round k is whole sites [cut[k], cut[k + 1]) (m6a_npy::cut_rounds over the handle's host copy of off[]).  Two device buffers and
 // two pinned buffers of the largest round are allocated before the first round and nothing after it.  Round k's kernels run on
@@ -19,16 +19,6 @@ int repr_writer_round(m6a_ctx *c, const float *X, const uint8_t *km, const int64
 
 namespace {
 
-struct ReprRound {                           // what one of the two rounds in flight owns
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};      // kernel start, kernel end (context's stream); copy start, copy end
-    char *pin = nullptr;
-    ~ReprRound()
-    {
-        for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-        if (pin) (void)hipHostFree(pin);
-    }
-};
-
 int repr_write_impl(m6a_prep_sites &P, m6a_ctx *ctx, const char *path, int dtype, int64_t n_limit, m6a_repr_write_stats &st)
 {
     const m6a_prep_sites_info &I = P.info;
@@ -39,49 +29,40 @@ int repr_write_impl(m6a_prep_sites &P, m6a_ctx *ctx, const char *path, int dtype
     const int64_t n_rows = off[S], rb = m6a_npy::row_bytes(dtype);
 
     DevMem m;
-    int rc = csv_device(P.device, m);
+    int rc = open_device(P.device, m, nullptr);             // the advice is made below, when the rounds are known
     if (rc) return rc;
     hipStream_t s_ctx = nullptr;
     if ((rc = m6a_detail::repr_writer_begin(ctx, P.device, &s_ctx))) return prep_fail(rc, "%s", m6a_last_error(ctx));
     g_d2h = 0;
-    struct Account {                         // whatever way the call ends, what it copied and allocated is reported
-        m6a_prep_sites &P; DevMem &m; m6a_repr_write_stats &st;
-        ~Account()
-        {
-            st.d2h_bytes = g_d2h;
-            P.info.d2h_bytes += g_d2h;
-            P.info.peak_bytes = std::max<int64_t>(P.info.peak_bytes, (int64_t)(P.held + m.peak));
-        }
-    } account{P, m, st};
+    Account<m6a_repr_write_stats> account{P, m, st};
 
     // ---- the rounds, and the four buffers of the largest one (the pinned pair counts against the budget like the device pair)
-    const char *rk = getenv("M6A_REPR_ROUND_KB");
-    const int64_t round_kb = rk && atoll(rk) > 0 ? atoll(rk) : m6a_npy::kRoundKB;
+    const int64_t kb = round_kb("M6A_REPR_ROUND_KB", m6a_npy::kRoundKB);
     std::vector<int64_t> cut;
-    const int64_t widest = m6a_npy::cut_rounds(off, S, round_kb << 10, dtype, cut);
+    const int64_t widest = m6a_npy::cut_rounds(off, S, kb << 10, dtype, cut);
     const int64_t n_rounds = (int64_t)cut.size() - 1, cap = std::max<int64_t>(widest * rb, 16);
     int64_t most_sites = 0;
     for (int64_t k = 0; k < n_rounds; k++) most_sites = std::max(most_sites, cut[(size_t)k + 1] - cut[(size_t)k]);
     char advice[160];
     snprintf(advice, sizeof advice, "set M6A_REPR_ROUND_KB below %lld (the largest round is %lld KB, and four buffers of it are held)",
-             (long long)round_kb, (long long)((cap + 1023) >> 10));
+             (long long)kb, (long long)((cap + 1023) >> 10));
     m.advice = advice;
     const int n_buf = n_rounds > 1 ? 2 : 1;
-    ReprRound rd[2];
-    Streams copy;                            // s[0]: the copy stream
+    Rounds rd;                               // s[0]: the copy stream of both rounds.  Events: kernel start, kernel end (the context's
+                                             // stream); copy start, copy end
     char *dbuf[2] = {nullptr, nullptr};
     int64_t *doff[2] = {nullptr, nullptr};
     if (n_rows) {
         if (m.used + (size_t)(2 * n_buf) * (size_t)cap > m.budget)
             return prep_fail(M6A_ENOMEM, "the read representation's %d buffers of %lld KB need more than the budget of %zu MB: %s", 2 * n_buf,
                              (long long)((cap + 1023) >> 10), m.budget >> 20, advice);
-        PCHK(hipStreamCreateWithFlags(&copy.s[0], hipStreamNonBlocking));
+        if ((rc = rd.open(4, 1))) return rc;
         for (int i = 0; i < n_buf; i++) {
-            if ((rc = m.alloc(dbuf[i], (size_t)cap, "read representation")) || (rc = m.alloc(doff[i], (size_t)most_sites + 1, "round offsets"))) return rc;
-            PCHK(hipHostMalloc((void **)&rd[i].pin, (size_t)cap, hipHostMallocDefault));
+            if ((rc = m.alloc(dbuf[i], (size_t)cap, "read representation")) || (rc = m.alloc(doff[i], (size_t)most_sites + 1, "round offsets")) ||
+                (rc = rd.pinned(i, cap)))
+                return rc;
             m.used += (size_t)cap;
             m.peak = std::max(m.peak, m.used);
-            for (hipEvent_t &x : rd[i].e) PCHK(hipEventCreate(&x));
         }
     }
 
@@ -100,37 +81,36 @@ int repr_write_impl(m6a_prep_sites &P, m6a_ctx *ctx, const char *path, int dtype
     if (!csv_pwrite_all(f.fd, head.data(), at0, 0)) return prep_fail(M6A_EIO, "cannot write %s", path);
     const int nw = std::min(m6a_usable_cpus(), 8);
 
-    auto enqueue = [&](int64_t k) -> int {
-        ReprRound &r = rd[k & 1];
+    hipStream_t copy = rd.s[0];
+    auto queue = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
         const int64_t a = cut[(size_t)k], b = cut[(size_t)k + 1], r0 = off[a], nr = off[b] - r0;
-        PCHK(hipEventRecord(r.e[0], s_ctx));
-        int rc2 = m6a_detail::repr_writer_round(ctx, I.X, I.site_kmers, I.off, doff[k & 1], a, b, r0, nr, dbuf[k & 1], dtype);
+        PCHK(hipEventRecord(rd.e[i][0], s_ctx));
+        const int rc2 = m6a_detail::repr_writer_round(ctx, I.X, I.site_kmers, I.off, doff[i], a, b, r0, nr, dbuf[i], dtype);
         if (rc2) return prep_fail(rc2, "%s", m6a_last_error(ctx));
-        PCHK(hipEventRecord(r.e[1], s_ctx));
-        PCHK(hipStreamWaitEvent(copy.s[0], r.e[1], 0));
-        PCHK(hipEventRecord(r.e[2], copy.s[0]));
-        if (nr) PCHK(hipMemcpyAsync(r.pin, dbuf[k & 1], (size_t)(nr * rb), hipMemcpyDeviceToHost, copy.s[0]));
+        PCHK(hipEventRecord(rd.e[i][1], s_ctx));
+        PCHK(hipStreamWaitEvent(copy, rd.e[i][1], 0));
+        PCHK(hipEventRecord(rd.e[i][2], copy));
+        if (nr) PCHK(hipMemcpyAsync(rd.pin[i], dbuf[i], (size_t)(nr * rb), hipMemcpyDeviceToHost, copy));
         g_d2h += nr * rb;
-        PCHK(hipEventRecord(r.e[3], copy.s[0]));
+        PCHK(hipEventRecord(rd.e[i][3], copy));
         return M6A_OK;
     };
-    if (n_rows) {
-        if ((rc = enqueue(0))) return rc;
-        for (int64_t k = 0; k < n_rounds; k++) {
-            if (k + 1 < n_rounds && (rc = enqueue(k + 1))) return rc;
-            ReprRound &r = rd[k & 1];
-            PCHK(hipEventSynchronize(r.e[3]));
-            float km = 0, cm = 0;
-            PCHK(hipEventElapsedTime(&km, r.e[0], r.e[1]));
-            PCHK(hipEventElapsedTime(&cm, r.e[2], r.e[3]));
-            st.ms_kernel += km;
-            st.ms_copy += cm;
-            const int64_t r0 = off[cut[(size_t)k]], nr = off[cut[(size_t)k + 1]] - r0;
-            const double t0 = now_ms();
-            if (!csv_pwrite_threads(f.fd, r.pin, nr * rb, at0 + r0 * rb, nw)) return prep_fail(M6A_EIO, "cannot write %s", path);
-            st.ms_write += now_ms() - t0;
-        }
-    }
+    auto finish = [&](int64_t k) -> int {
+        const int i = (int)(k & 1);
+        PCHK(hipEventSynchronize(rd.e[i][3]));
+        float km = 0, cm = 0;
+        PCHK(hipEventElapsedTime(&km, rd.e[i][0], rd.e[i][1]));
+        PCHK(hipEventElapsedTime(&cm, rd.e[i][2], rd.e[i][3]));
+        st.ms_kernel += km;
+        st.ms_copy += cm;
+        const int64_t r0 = off[cut[(size_t)k]], nr = off[cut[(size_t)k + 1]] - r0;
+        const double t0 = now_ms();
+        if (!csv_pwrite_threads(f.fd, rd.pin[i], nr * rb, at0 + r0 * rb, nw)) return prep_fail(M6A_EIO, "cannot write %s", path);
+        st.ms_write += now_ms() - t0;
+        return M6A_OK;
+    };
+    if (n_rows && (rc = run_rounds(n_rounds, queue, finish))) return rc;
     st.n_rounds = n_rows ? n_rounds : 0;
     st.n_rows = n_rows;
     st.bytes = at0 + n_rows * rb;
@@ -152,13 +132,7 @@ extern "C" int m6a_prep_sites_write_read_representation(m6a_prep_sites *p, m6a_c
     if (!p || !ctx || !path) {
         rc = prep_fail(M6A_EINVAL, "null argument");
     } else {
-        try {
-            rc = repr_write_impl(*p, ctx, path, dtype, n_sites_limit, st);
-        } catch (const std::bad_alloc &) {
-            rc = prep_fail(M6A_ENOMEM, "out of host memory");
-        } catch (...) {
-            rc = prep_fail(M6A_EIO, "unexpected exception");
-        }
+        rc = guarded([&] { return repr_write_impl(*p, ctx, path, dtype, n_sites_limit, st); });
     }
     if (stats) *stats = st;
     return rc;

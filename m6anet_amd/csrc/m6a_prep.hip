@@ -41,27 +41,11 @@
 
 #include "m6a.h"
 #include "m6a_io.h"
+#include "m6a_prep_kit.h"
 #include "m6a_stream.h"
 #include "m6a_uuid.h"
 
 namespace {
-
-thread_local std::string g_prep_err;
-thread_local int64_t g_d2h = 0;          // bytes copied device -> host by this thread's current call (m6a_prep_sites reports them)
-
-int prep_fail(int code, const char *fmt, ...)
-{
-    char buf[768];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_prep_err = buf;
-    return code;
-}
-
-constexpr int kBlk = 256;                 // threads per block everywhere
-constexpr int64_t kScanBytes = 4096;      // bytes per block of the newline scan: 256 lanes x 16 bytes
 
 // per-line event flags
 enum : uint8_t { L_TAB = 1, L_EMPTY = 2, L_HOST = 4, L_MATCH = 8, L_K5 = 16 };
@@ -122,42 +106,6 @@ __global__ void nl_write_kernel(const uint4 *__restrict__ f, int64_t nb, const i
     const int64_t at = b * kScanBytes + threadIdx.x * 16;
     for (int k = 0; k < 16; k++)
         if (((w[k >> 2] >> ((k & 3) * 8)) & 0xff) == '\n') nl[o++] = at + k;
-}
-
-// ---- exclusive scan of int64 (in place; a[n] receives the total) --------------------------------------------------
-__global__ void scan_block_kernel(int64_t *__restrict__ a, int64_t n, int64_t *__restrict__ sums)
-{
-    const int64_t base = (int64_t)blockIdx.x * (kBlk * 4);
-    int64_t v[4], t = 0;
-    for (int k = 0; k < 4; k++) {
-        const int64_t i = base + threadIdx.x * 4 + k;
-        v[k] = i < n ? a[i] : 0;
-        t += v[k];
-    }
-    __shared__ int64_t s[kBlk];
-    s[threadIdx.x] = t;
-    __syncthreads();
-    for (int o = 1; o < kBlk; o <<= 1) {
-        const int64_t x = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-        __syncthreads();
-        s[threadIdx.x] += x;
-        __syncthreads();
-    }
-    int64_t run = s[threadIdx.x] - t;
-    for (int k = 0; k < 4; k++) {
-        const int64_t i = base + threadIdx.x * 4 + k;
-        if (i < n) a[i] = run;
-        run += v[k];
-    }
-    if (threadIdx.x == kBlk - 1) sums[blockIdx.x] = s[kBlk - 1];
-}
-
-__global__ void scan_add_kernel(int64_t *__restrict__ a, int64_t n, const int64_t *__restrict__ sums)
-{
-    const int64_t i = (int64_t)blockIdx.x * (kBlk * 4) + threadIdx.x * 4;
-    const int64_t add = sums[blockIdx.x];
-    for (int k = 0; k < 4; k++)
-        if (i + k < n) a[i + k] += add;
 }
 
 // ---- lines ---------------------------------------------------------------------------------------------------------
@@ -508,13 +456,6 @@ __global__ void run_cols_kernel(const RunDev *__restrict__ runs, int64_t NR, int
     if (r < NR) npos[r] = runs[r].status == M6A_PREP_RUN_OK ? runs[r].npos : 0;
 }
 
-inline unsigned grid(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlk - 1) / kBlk); }
-
-double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 // ---- the handle ----------------------------------------------------------------------------------------------------
@@ -530,191 +471,6 @@ struct m6a_prep {
 };
 
 namespace {
-
-#define PCHK(x)                                                                                                            \
-    do {                                                                                                                   \
-        hipError_t e_ = (x);                                                                                               \
-        if (e_ != hipSuccess) return prep_fail(M6A_EHIP, "%s: %s", #x, hipGetErrorString(e_));                             \
-    } while (0)
-
-// scratch of the window loop: one allocation (counted like any other) that every window bump-allocates from the start, so that no
-// hipMalloc or hipFree runs between the kernels of a window; a window that needs more says how much and is done again
-struct Arena {
-    uint8_t *base = nullptr;
-    size_t cap = 0, off = 0, need = 0;
-};
-constexpr int kArenaFull = 1;               // DevMem::alloc's answer then; never leaves front_windows
-
-// device memory of one call, every allocation counted against the budget (free memory minus a margin, or M6A_PREP_BUDGET_MB)
-struct DevMem {
-    std::vector<std::pair<void *, size_t>> ptrs;
-    size_t used = 0, budget = 0, peak = 0;
-    bool budget_set = false;                     // the first file of a job sets it; what stays of earlier files counts against it
-    const char *advice = "use --device cpu";     // what the budget error tells the user to do instead
-    Arena *arena = nullptr;                      // set: alloc() takes from it (release() of such a pointer does nothing)
-    ~DevMem() { for (auto &p : ptrs) (void)hipFree(p.first); }
-    template <class T> int alloc(T *&p, size_t count, const char *what)
-    {
-        const size_t bytes = std::max<size_t>(16, count * sizeof(T));
-        if (arena) {
-            const size_t a = (bytes + 255) & ~(size_t)255;
-            if (arena->off + a > arena->cap) { arena->need = std::max(arena->need, arena->off + a); return kArenaFull; }
-            p = (T *)(arena->base + arena->off);
-            arena->off += a;
-            return M6A_OK;
-        }
-        if (used + bytes > budget)
-            return prep_fail(M6A_ENOMEM, "dataprep on the device needs more than its budget of %zu MB (%s: %zu MB used, %zu MB more); "
-                             "this file does not fit: %s", budget >> 20, what, used >> 20, bytes >> 20, advice);
-        void *q = nullptr;
-        if (hipMalloc(&q, bytes) != hipSuccess) return prep_fail(M6A_ENOMEM, "hipMalloc of %zu MB failed (%s); %s", bytes >> 20, what, advice);
-        ptrs.emplace_back(q, bytes);
-        used += bytes;
-        peak = std::max(peak, used);
-        p = (T *)q;
-        return M6A_OK;
-    }
-    // hipFree everything allocated from entry `mark` of ptrs on, but `keep`
-    void release_since(size_t mark, std::initializer_list<const void *> keep)
-    {
-        std::vector<std::pair<void *, size_t>> left(ptrs.begin(), ptrs.begin() + (ptrdiff_t)std::min(mark, ptrs.size()));
-        for (size_t i = mark; i < ptrs.size(); i++) {
-            if (std::find(keep.begin(), keep.end(), (const void *)ptrs[i].first) != keep.end()) { left.push_back(ptrs[i]); continue; }
-            (void)hipFree(ptrs[i].first);
-            used -= ptrs[i].second;
-        }
-        ptrs.swap(left);
-    }
-    // hipFree now (release) or never (detach: the caller owns it from here on)
-    void drop(const void *p, bool free_it)
-    {
-        for (size_t i = 0; i < ptrs.size(); i++)
-            if (ptrs[i].first == p) {
-                if (free_it) { (void)hipFree(ptrs[i].first); used -= ptrs[i].second; }
-                ptrs.erase(ptrs.begin() + (ptrdiff_t)i);
-                return;
-            }
-    }
-    void release(const void *p) { drop(p, true); }
-    void release(std::initializer_list<const void *> ps) { for (const void *p : ps) drop(p, true); }
-    void detach(const void *p) { drop(p, false); }
-    size_t size_of(const void *p) const
-    {
-        for (const auto &q : ptrs)
-            if (q.first == p) return q.second;
-        return 0;
-    }
-};
-
-struct Streams {
-    hipStream_t s[2] = {nullptr, nullptr};
-    hipEvent_t copied[2] = {nullptr, nullptr};
-    void *pin[2] = {nullptr, nullptr};
-    ~Streams()
-    {
-        for (int i = 0; i < 2; i++) {
-            if (s[i]) (void)hipStreamSynchronize(s[i]);
-        }
-        for (int i = 0; i < 2; i++) {
-            if (copied[i]) (void)hipEventDestroy(copied[i]);
-            if (pin[i]) (void)hipHostFree(pin[i]);
-            if (s[i]) (void)hipStreamDestroy(s[i]);
-        }
-    }
-};
-
-struct Fd {
-    int fd = -1;
-    bool own = true;                        // false: descriptor 0 for `-`, which stays the process's
-    ~Fd() { if (own && fd >= 0) ::close(fd); }
-};
-
-// one lane per item: grid(n) blocks of kBlk on s, and nothing at n <= 0
-template <class... P, class... A> int launch(void (*kernel)(P...), int64_t n, hipStream_t s, A... args)
-{
-    if (n <= 0) return M6A_OK;
-    kernel<<<grid(n), kBlk, 0, s>>>(args...);
-    PCHK(hipGetLastError());
-    return M6A_OK;
-}
-
-// len rounded up to whole scan blocks, one at the least: what a text buffer holds, zeros behind the text
-inline int64_t padded(int64_t len) { return std::max<int64_t>(1, (len + kScanBytes - 1) / kScanBytes) * kScanBytes; }
-
-// one value device -> host, there when this returns
-template <class T> int fetch(T &host, const T *dev, hipStream_t s)
-{
-    PCHK(hipMemcpyAsync(&host, dev, sizeof(T), hipMemcpyDeviceToHost, s));
-    g_d2h += (int64_t)sizeof(T);
-    PCHK(hipStreamSynchronize(s));
-    return M6A_OK;
-}
-
-// file bytes [off, off + len) -> dst, all of them
-int read_fully(int fd, void *dst, int64_t len, int64_t off, const char *path)
-{
-    for (int64_t got = 0; got < len;) {
-        const ssize_t r = ::pread(fd, (char *)dst + got, (size_t)(len - got), (off_t)(off + got));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return prep_fail(M6A_EIO, "cannot read %s", path);
-        got += r;
-    }
-    return M6A_OK;
-}
-
-int write_fully(int fd, const void *src, size_t len, const char *path)
-{
-    for (size_t got = 0; got < len;) {
-        const ssize_t k = ::write(fd, (const char *)src + got, len - got);
-        if (k < 0 && errno == EINTR) continue;
-        if (k <= 0) return prep_fail(M6A_EIO, "cannot write %s", path);
-        got += (size_t)k;
-    }
-    return M6A_OK;
-}
-
-// names -> ids in order of first appearance; a new name goes behind blob, where tx_off says it starts (the caller closes tx_off)
-struct Interner {
-    std::string &blob;
-    std::vector<int64_t> &tx_off;
-    std::unordered_map<std::string, uint32_t> ids;
-    Interner(std::string &b, std::vector<int64_t> &o) : blob(b), tx_off(o) {}
-    uint32_t id(const std::string &nm)
-    {
-        auto it = ids.find(nm);
-        if (it != ids.end()) return it->second;
-        const uint32_t t = (uint32_t)ids.size();
-        ids.emplace(nm, t);
-        tx_off.push_back((int64_t)blob.size());
-        blob += nm;
-        return t;
-    }
-};
-
-int scan_excl(DevMem &m, int64_t *a, int64_t n, hipStream_t s)
-{
-    const int64_t per = kBlk * 4, nb = (n + per - 1) / per;
-    if (n <= 0) return M6A_OK;
-    int64_t *sums;
-    int rc = m.alloc(sums, (size_t)nb + 1, "scan");
-    if (rc) return rc;
-    scan_block_kernel<<<(unsigned)nb, kBlk, 0, s>>>(a, n, sums);
-    PCHK(hipGetLastError());
-    if (nb > 1) {
-        if ((rc = scan_excl(m, sums, nb, s))) return rc;
-        scan_add_kernel<<<(unsigned)nb, kBlk, 0, s>>>(a, n, sums);
-        PCHK(hipGetLastError());
-    }
-    return M6A_OK;
-}
-
-// a[n] = sum of a[0..n) after the scan: the array holds n + 1 elements, the last one 0 before it
-int scan_total(DevMem &m, int64_t *a, int64_t n, hipStream_t s, int64_t &total)
-{
-    PCHK(hipMemsetAsync(a + n, 0, sizeof(int64_t), s));
-    int rc = scan_excl(m, a, n + 1, s);
-    return rc ? rc : fetch(total, a + n, s);
-}
 
 // the rows of an existing eventalign.index, as m6a_io.cpp's read_index_file reads them
 int read_index(const char *path, std::vector<std::string> &names, std::vector<uint32_t> &tx, std::vector<int64_t> &read,
@@ -816,9 +572,8 @@ struct Front {
 };
 
 // m6a_bgzf.h, included at the end of this file
-struct BgzfUp;
 bool bgzf_is_gzip(int fd, int64_t n);
-int bgzf_front(const char *path, int fd, int64_t n_file, DevMem &m, Streams &S, int64_t chunk, uint8_t *&text, int64_t &n_text, Front &F, double *ms);
+int bgzf_front(int device_id, const char *path, int fd, int64_t n_file, DevMem &m, Streams &S, int64_t chunk, uint8_t *&text, int64_t &n_text, Front &F, double *ms);
 int bgzf_gather(DevMem &m, hipStream_t s, const uint8_t *text, int64_t n_text, const std::vector<int64_t> &src, const std::vector<int64_t> &len,
                 std::vector<uint8_t> &out);
 
@@ -843,33 +598,6 @@ int64_t window_from_env()
 {
     const char *e = getenv("M6A_PREP_WINDOW_KB");
     return e && atoll(e) > 0 ? atoll(e) << 10 : 0;
-}
-
-// file bytes [off, off + len) -> dst on the copy stream, zeros behind them to a whole scan block; returns when they have arrived.
-// per_chunk(slot, done, part) is called when the copy of bytes [done, done + part) has been recorded as S.copied[slot]: the resident
-// file counts the chunk's newlines behind that event while the next chunk is read (the zeros go first, so the last block is whole then)
-template <class Hook>
-int upload_range(int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk, Hook per_chunk)
-{
-    int rc;
-    PCHK(hipSetDevice(device_id));
-    if (padded(len) > len) PCHK(hipMemsetAsync(dst + len, 0, (size_t)(padded(len) - len), S.s[1]));
-    for (int64_t k = 0, done = 0; done < len; k++, done += chunk) {
-        const int slot = (int)(k & 1);
-        PCHK(hipEventSynchronize(S.copied[slot]));          // the copy that last used this buffer is done
-        const int64_t part = std::min(chunk, len - done);
-        if ((rc = read_fully(fd, S.pin[slot], part, off + done, path))) return rc;
-        PCHK(hipMemcpyAsync(dst + done, S.pin[slot], (size_t)part, hipMemcpyHostToDevice, S.s[1]));
-        PCHK(hipEventRecord(S.copied[slot], S.s[1]));
-        if ((rc = per_chunk(slot, done, part))) return rc;
-    }
-    PCHK(hipStreamSynchronize(S.s[1]));
-    return M6A_OK;
-}
-
-int upload_range(int device_id, int fd, const char *path, Streams &S, uint8_t *dst, int64_t off, int64_t len, int64_t chunk)
-{
-    return upload_range(device_id, fd, path, S, dst, off, len, chunk, [](int, int64_t, int64_t) { return M6A_OK; });
 }
 
 // One window: file bytes [b, b + n); `len` bytes from b are in df, zeros behind them.  A resident file is the one window that starts
@@ -1420,10 +1148,8 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
                DevMem &m, Streams &S, Fd &fd, Front &F, double *ms)
 {
     const bool index_path = istart != nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(M6A_ENODEV, "no HIP device");
-    if (device_id < 0 || device_id >= ndev) return prep_fail(M6A_EINVAL, "device %d of %d", device_id, ndev);
-    PCHK(hipSetDevice(device_id));
+    int rc = open_device(device_id, m, nullptr);             // the first file of a job sets the budget
+    if (rc) return rc;
     if (is_stdin(path)) { fd.fd = 0; fd.own = false; }
     else fd.fd = ::open(path, O_RDONLY);
     if (fd.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", path);
@@ -1442,37 +1168,20 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         return prep_fail(M6A_EINVAL, "%s: windows over compressed input are not implemented (--window_mb, M6A_PREP_WINDOW_KB); a BGZF file "
                          "must fit resident: run it without a window", path);
     F.n = n;
-    if (!m.budget_set) {
-        m.budget_set = true;
-        size_t fr = 0, tot = 0;
-        PCHK(hipMemGetInfo(&fr, &tot));
-        const size_t margin = std::min<size_t>(fr / 16, (size_t)4 << 30);
-        m.budget = fr > margin ? fr - margin : 0;
-        const char *b = getenv("M6A_PREP_BUDGET_MB");
-        if (b && atoll(b) > 0) m.budget = std::min(m.budget, (size_t)atoll(b) << 20);
-    }
     int64_t nb = padded(n) / kScanBytes;                                        // 4 KB scan blocks; the buffer is padded to them
     if (stream && window <= 0) window = M6A_PREP_STREAM_WINDOW_BYTES;           // a stream is always parsed in windows
     const int64_t W = index_path || window <= 0 ? 0 : (window + kScanBytes - 1) / kScanBytes * kScanBytes;
     uint8_t *df = nullptr;
     int64_t *bcnt = nullptr;
-    int rc = M6A_OK;
     if (!W && !gz) {
         rc = m.alloc(df, (size_t)(nb * kScanBytes), "the file");
         if (!rc) rc = m.alloc(bcnt, (size_t)nb + 1, "newline counts");
         if (rc) return rc;
     }
 
-    for (int i = 0; i < 2; i++) {
-        PCHK(hipStreamCreateWithFlags(&S.s[i], hipStreamNonBlocking));
-        PCHK(hipEventCreateWithFlags(&S.copied[i], hipEventDisableTiming));
-    }
+    int64_t chunk = 0;
+    if ((rc = S.open(W ? W : nb * kScanBytes, chunk))) return rc;
     hipStream_t s = S.s[0];                                  // kernels; S.s[1] copies
-    const char *ck = getenv("M6A_PREP_CHUNK_KB");
-    int64_t chunk = (ck && atoll(ck) > 0 ? atoll(ck) : 65536) << 10;
-    chunk = std::max<int64_t>(kScanBytes, (chunk + kScanBytes - 1) / kScanBytes * kScanBytes);
-    chunk = std::min<int64_t>(chunk, W ? W : nb * kScanBytes);
-    for (int i = 0; i < 2; i++) PCHK(hipHostMalloc(&S.pin[i], (size_t)chunk, hipHostMallocDefault));
     if (W) {
         Windows C(device_id, path, W, chunk, m, S);
         if (stream) { StreamSource src(C, fd.fd); return front_windows(C, src, w, F, ms); }
@@ -1480,7 +1189,7 @@ int front_half(int device_id, const char *path, int w, const std::vector<int64_t
         return front_windows(C, src, w, F, ms);
     }
     if (gz) {                                                // the compressed bytes go up, the text is inflated where the upload would have put it
-        if ((rc = bgzf_front(path, fd.fd, n, m, S, chunk, df, n, F, ms))) return rc;
+        if ((rc = bgzf_front(device_id, path, fd.fd, n, m, S, chunk, df, n, F, ms))) return rc;
         F.n = n;
         nb = padded(n) / kScanBytes;
         const double t_nl = now_ms();
@@ -1652,57 +1361,6 @@ int prep_impl(int device_id, const char *path, int w, const char *index_path, m6
 //   sites      cut where (transcript, position) changes; 7-mers must agree; kept with >= min_segment_count and >= 20 reads
 //   X          (float)((v - mean) / std) in f64 per feature, as m6a_io_load_sites computes it
 namespace {
-
-constexpr int kRadixItems = 16, kRadixTile = kBlk * kRadixItems;     // 4096 keys per block
-static_assert(kBlk == 256, "radix_scatter_kernel scans 16 digits x 16 chunks of 16 lanes: one lane per (digit, chunk)");
-
-__global__ void radix_hist_kernel(const uint64_t *__restrict__ key, int64_t n, int shift, int64_t nblk, int64_t *__restrict__ hist)
-{
-    __shared__ int c[16];
-    if (threadIdx.x < 16) c[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * kRadixTile;
-    for (int k = 0; k < kRadixItems; k++) {
-        const int64_t i = base + (int64_t)k * kBlk + threadIdx.x;
-        if (i < n) atomicAdd(&c[(key[i] >> shift) & 15], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) hist[threadIdx.x * nblk + blockIdx.x] = c[threadIdx.x];
-}
-
-// stable: lane t owns keys [16 t, 16 t + 16) of the block's tile, in order; hist = exclusive scan, digit-major then block
-__global__ void radix_scatter_kernel(const uint64_t *__restrict__ key, const uint32_t *__restrict__ val, int64_t n, int shift, int64_t nblk,
-                                     const int64_t *__restrict__ hist, uint64_t *__restrict__ key2, uint32_t *__restrict__ val2)
-{
-    __shared__ int cnt[16][kBlk];
-    __shared__ int part[16][16];
-    const int t = threadIdx.x;
-    for (int d = 0; d < 16; d++) cnt[d][t] = 0;
-    const int64_t i0 = (int64_t)blockIdx.x * kRadixTile + (int64_t)t * kRadixItems;
-    for (int k = 0; k < kRadixItems; k++)
-        if (i0 + k < n) cnt[(key[i0 + k] >> shift) & 15][t]++;
-    __syncthreads();
-    const int d = t >> 4, c = t & 15;                  // per digit, the exclusive scan over the lanes: 16 chunks of 16 lanes
-    int sum = 0;
-    for (int k = 0; k < 16; k++) sum += cnt[d][c * 16 + k];
-    part[d][c] = sum;
-    __syncthreads();
-    if (t < 16) {
-        int run = 0;
-        for (int k = 0; k < 16; k++) { const int v = part[t][k]; part[t][k] = run; run += v; }
-    }
-    __syncthreads();
-    int run = part[d][c];
-    for (int k = 0; k < 16; k++) { const int v = cnt[d][c * 16 + k]; cnt[d][c * 16 + k] = run; run += v; }
-    __syncthreads();
-    for (int k = 0; k < kRadixItems && i0 + k < n; k++) {
-        const uint64_t x = key[i0 + k];
-        const int g = (int)((x >> shift) & 15);
-        const int64_t o = hist[g * nblk + blockIdx.x] + cnt[g][t]++;
-        key2[o] = x;
-        val2[o] = val[i0 + k];
-    }
-}
 
 // flag[i] -> list of the flagged i (after the exclusive scan of the flags: ex[i + 1] != ex[i])
 __global__ void compact_u32_kernel(const int64_t *__restrict__ ex, int64_t n, uint32_t *__restrict__ out)
@@ -2021,84 +1679,6 @@ int dataprep_emit(DevMem &m, hipStream_t s0, const DataprepJob &job, const Datap
 
 int bits_for(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 
-// stable sort of (key, val) by the low `bits` bits of key; key / val end up pointing at the sorted pair (swapped with key2 / val2)
-int radix_sort(DevMem &m, uint64_t *&key, uint32_t *&val, uint64_t *&key2, uint32_t *&val2, int64_t n, int bits, hipStream_t s)
-{
-    if (n <= 1 || bits <= 0) return M6A_OK;
-    const int64_t nblk = (n + kRadixTile - 1) / kRadixTile;
-    int64_t *hist;
-    int rc = m.alloc(hist, (size_t)(16 * nblk) + 1, "sort");
-    if (rc) return rc;
-    for (int sh = 0; sh < bits; sh += 4) {
-        radix_hist_kernel<<<(unsigned)nblk, kBlk, 0, s>>>(key, n, sh, nblk, hist);
-        PCHK(hipGetLastError());
-        if ((rc = scan_excl(m, hist, 16 * nblk, s))) return rc;
-        radix_scatter_kernel<<<(unsigned)nblk, kBlk, 0, s>>>(key, val, n, sh, nblk, hist, key2, val2);
-        PCHK(hipGetLastError());
-        std::swap(key, key2);
-        std::swap(val, val2);
-    }
-    PCHK(hipStreamSynchronize(s));
-    m.release(hist);
-    return M6A_OK;
-}
-
-// stable sort of (key, val) by up to three fields, given by their bit widths, least significant first.  As many fields as fit into
-// 64 bits go into one key: make_key(use, shift) launches the caller's key kernel for the fields whose bit is set in `use`, field f at
-// bit shift[f], and radix_sort sorts by what was packed; the fields that are left follow in further passes (LSD, stable).
-template <class MakeKey>
-int sort_by_fields(DevMem &m, hipStream_t s, const int *bits, int n_fields, uint64_t *&key, uint32_t *&val, uint64_t *&key2, uint32_t *&val2, int64_t n,
-                   MakeKey make_key)
-{
-    int rc, shift[3] = {0, 0, 0}, at = 0;
-    unsigned use = 0;
-    for (int f = 0; f <= n_fields; f++) {
-        if (f == n_fields || (bits[f] && at + bits[f] > 64)) {          // sort by what is packed so far
-            if (use && ((rc = make_key(use, shift)) || (rc = radix_sort(m, key, val, key2, val2, n, at, s)))) return rc;
-            use = 0;
-            at = 0;
-        }
-        if (f == n_fields || !bits[f]) continue;
-        shift[f] = at;
-        use |= 1u << f;
-        at += bits[f];
-    }
-    return M6A_OK;
-}
-
-template <class T> int d2h(T *dst, const T *src, size_t count, hipStream_t s)
-{
-    if (!count) return M6A_OK;
-    PCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, s));
-    g_d2h += (int64_t)(count * sizeof(T));
-    return M6A_OK;
-}
-
-template <class T> int h2d(T *dst, const T *src, size_t count, hipStream_t s)
-{
-    if (!count) return M6A_OK;
-    PCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-    return M6A_OK;
-}
-
-// the 66-word vocabulary of m6a_io.cpp (sorted unique 5-mers of all N-DRACH-N 7-mers), packed like pack5
-std::vector<uint64_t> vocab_keys()
-{
-    std::vector<uint64_t> v;
-    const std::string N = "ACGT", D = "AGT", R = "GA", H = "ACT";
-    for (char a : N) for (char d : D) for (char r : R) for (char h : H) for (char b : N) {
-        const char k7[7] = {a, d, r, 'A', 'C', h, b};
-        for (int i = 0; i < 3; i++) {
-            uint64_t x = 0;
-            for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)k7[i + j];
-            v.push_back(x);
-        }
-    }
-    std::sort(v.begin(), v.end());
-    v.erase(std::unique(v.begin(), v.end()), v.end());
-    return v;
-}
-
 // ---- read names interned (m6a_prep_sites_build_names) -------------------------------------------------------------------------------
 // After the last window of a file and before anything reads RunDev.read, every run's 128-bit name becomes the dense index of the
 // name in order of first appearance -- the read index the twin file (names replaced by 0, 1, ...) carries in field 4:
@@ -2255,21 +1835,6 @@ struct m6a_prep_sites {
 };
 
 namespace {
-
-// the normalisation 5-mers packed like pack5, sorted, each once: keys, and per key the index of the first of equal 5-mers (the
-// loader's map keeps the first)
-void norm_keys(const char *norm_kmers, int n_norm, std::vector<uint64_t> &keys, std::vector<int32_t> &first)
-{
-    std::vector<std::pair<uint64_t, int32_t>> norm;
-    for (int i = 0; i < n_norm; i++) {
-        uint64_t x = 0;
-        for (int j = 0; j < 5; j++) x = x << 8 | (uint8_t)norm_kmers[5 * i + j];
-        norm.emplace_back(x, i);
-    }
-    std::sort(norm.begin(), norm.end());
-    for (size_t i = 0; i < norm.size(); i++)
-        if (i == 0 || norm[i].first != norm[i - 1].first) { keys.push_back(norm[i].first); first.push_back(norm[i].second); }
-}
 
 // the error of the lowest bad site (8 site + what) that site_info_kernel or, pooled, pool_site_kernel found; the sites are in P
 int bad_site(const m6a_prep_sites &P, unsigned long long bad, bool pooled)
@@ -3191,14 +2756,7 @@ extern "C" int m6a_prep_eventalign(int device_id, const char *path, int n_neighb
     *out = nullptr;
     m6a_prep *p = new (std::nothrow) m6a_prep;
     if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
-    int rc;
-    try {
-        rc = prep_impl(device_id, path, n_neighbors, index_path, *p);
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+    const int rc = guarded([&] { return prep_impl(device_id, path, n_neighbors, index_path, *p); });
     if (rc) { delete p; return rc; }
     *out = p;
     return M6A_OK;
@@ -3256,15 +2814,10 @@ extern "C" int m6a_prep_sites_build_names(int device_id, const char *const *path
     if (!p) return prep_fail(M6A_ENOMEM, "out of host memory");
     p->device = device_id;
     p->read_names = read_names != 0;
-    int rc;
-    try {
-        rc = sites_multi(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm,
-                         host, n_threads, window_bytes, *p);
-    } catch (const std::bad_alloc &) {
-        rc = prep_fail(M6A_ENOMEM, "out of host memory");
-    } catch (...) {
-        rc = prep_fail(M6A_EIO, "unexpected exception");
-    }
+    const int rc = guarded([&] {
+        return sites_multi(device_id, paths, n_paths, readcount_min, readcount_max, min_segment_count, norm_kmers, norm_mean, norm_std, n_norm, host,
+                           n_threads, window_bytes, *p);
+    });
     if (rc) { delete p; return rc; }
     *out = p;
     return M6A_OK;

@@ -5,12 +5,17 @@
                                                            range what _io.csv_format returned
     python csv_device_child.py declined EVENTALIGN OUT_DIR OUT.pkl
                                                            prep_sites(EVENTALIGN).write_csv(OUT_DIR) without inference: OUT holds the
-                                                           exception's class name, code and n_declined (or "written")"""
+                                                           exception's class name, code and n_declined (or "written")
+    python csv_device_child.py append EVENTALIGN HOST_DIR PLAIN_DIR GZ1_DIR GZ2_DIR OUT.pkl
+                                                           prep_sites + inference; the host writer into HOST_DIR, then on the one handle
+                                                           write_csv(write_header=True) and write_csv(write_header=False) into PLAIN_DIR,
+                                                           with compress=True into GZ1_DIR and at level 2 into GZ2_DIR; OUT: the statistics"""
 import os
 import pickle
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
@@ -34,6 +39,16 @@ def main():
                 res.update(what=type(e).__name__, code=e.code, n_declined=getattr(e, "n_declined", None), text=str(e))
             res["d2h_after"] = p.times()[1]
         pickle.dump(res, open(sys.argv[4], "wb"))
+    elif mode == "append":
+        from deflate_device_child import sites_with_outputs
+        p, eng = sites_with_outputs([sys.argv[2]])
+        res = {"n_sites": p.n_sites}
+        p.writer().write_csv(sys.argv[3], *p.fetch(), write_header=True, n_threads=2)
+        for key, out, kw in (("plain", sys.argv[4], {}), ("gz1", sys.argv[5], {"compress": True}), ("gz2", sys.argv[6], {"compress": True, "level": 2})):
+            res[key] = [p.write_csv(out, write_header=h, n_threads=2, **kw) for h in (True, False)]
+        p.close()
+        eng.close()
+        pickle.dump(res, open(sys.argv[7], "wb"))
     else:
         raise SystemExit("unknown mode %r" % mode)
 

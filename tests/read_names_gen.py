@@ -30,7 +30,7 @@ import eventalign_gen as G
 import eventalign_statement as S
 import read_names_statement as RS
 
-PREP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "m6anet_amd", "csrc", "m6a_prep.hip")
+PREP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "m6anet_amd", "csrc", "m6a_prep_kit.h")
 
 
 def radix_tile():

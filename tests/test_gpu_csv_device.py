@@ -5,6 +5,7 @@ held to tests/csv_statement.py and to the host writer, byte for byte.  Every GPU
 Rounds: m6a_prep_sites_write_csv cuts the job at SITE boundaries (a site with more text than M6A_CSV_ROUND_KB is a round of its own),
 so every round ends on a site's last byte; the sweep below checks that the bytes do not depend on where the cuts fall."""
 import filecmp
+import gzip
 import json
 import os
 import pickle
@@ -18,6 +19,7 @@ import csv_edges as E
 import csv_statement as ST
 import eventalign_gen as G
 import replicate_fixtures as F
+from m6anet_amd import _io, bgzf
 from test_csv_statement import host_texts, statement_texts
 from test_dataprep_rows import unpack
 
@@ -28,8 +30,8 @@ CSVS = ("data.site_proba.csv", "data.indiv_proba.csv")
 HEADERS = (len(ST.SITE_HEADER), len(ST.INDIV_HEADER))
 
 
-def child(args, limit=300):
-    p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, CHILD] + [str(a) for a in args], cwd=REPO, stdout=subprocess.PIPE,
+def child(args, limit=300, env=None):
+    p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, CHILD] + [str(a) for a in args], cwd=REPO, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE)
     assert p.returncode == 0, (p.returncode, p.stderr.decode()[-3000:])
     return p
@@ -186,6 +188,39 @@ def test_a_file_without_a_kept_site_leaves_the_header_lines(tmp_path):
         assert p.returncode not in (0, 124, 137) and b"no site with at least 20 reads" in p.stderr
         outs.append([open(os.path.join(out, fn), "rb").read() for fn in CSVS])
     assert outs[0] == outs[1] == [ST.SITE_HEADER, ST.INDIV_HEADER]
+
+
+# ---- 4b. append ------------------------------------------------------------------------------------------------------------------
+def test_write_header_0_appends_behind_what_the_files_hold(tmp_path):
+    """write_csv(write_header=True) then write_csv(write_header=False) on one handle, plain and compressed at both levels, two sites in
+    rounds of 1 KB: every file holds the host writer's bytes and then the same rows again without the header line.  The second call
+    opens without O_TRUNC and starts at the size fstat gives; the BGZF files keep the first call's end marker as an empty block in
+    the middle."""
+    rng = np.random.default_rng(6)
+    f = G.File(rng)
+    tx = G.Tx(rng, "APP", 30, (3, 14))
+    G.site_reads(f, tx, 3, list(range(60)), mismatch=0)
+    G.site_reads(f, tx, 14, list(range(100, 160)), mismatch=0)      # 60 read rows of 12 bytes or more: a site fills most of a round
+    ev = tmp_path / "two.txt"
+    ev.write_bytes(f.bytes())
+    dirs = [tmp_path / n for n in ("host", "plain", "gz1", "gz2")]
+    for d in dirs:
+        d.mkdir()
+    child(["append", ev] + dirs + [tmp_path / "res.pkl"], env=dict(os.environ, M6A_CSV_ROUND_KB="1"))
+    r = pickle.load(open(tmp_path / "res.pkl", "rb"))
+    assert r["n_sites"] == 2
+    for key in ("plain", "gz1", "gz2"):
+        assert [st["n_rounds"] for st in r[key]] == [2, 2], (key, r[key])
+    for fn, header in zip(CSVS, (ST.SITE_HEADER, ST.INDIV_HEADER)):
+        once = (dirs[0] / fn).read_bytes()
+        assert once.startswith(header) and len(once) > len(header), fn
+        want = once + once[len(header):]
+        assert (dirs[1] / fn).read_bytes() == want, fn
+        for d in dirs[2:]:
+            data = (d / (fn + ".gz")).read_bytes()
+            assert data[-28:] == bgzf.EOF_MARKER and data.count(bgzf.EOF_MARKER) == 2, (d.name, fn)
+            assert gzip.decompress(data) == want, (d.name, fn)
+            assert _io.bgzf_inflate_host(str(d / (fn + ".gz"))) == want, (d.name, fn)
 
 
 # ---- 5. fallback -----------------------------------------------------------------------------------------------------------------

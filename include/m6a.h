@@ -10,7 +10,9 @@
  *   - every function returns M6A_OK (0) or a negative M6A_E* code; m6a_last_error(ctx) gives text;
  *   - the caller owns every buffer; the library keeps no input pointer after a call returns (one exception, stated
  *     there: DEVICE batches of a streaming job are read in place until m6a_job_end / m6a_job_abort);
- *   - data pointers may be HOST or DEVICE pointers (detected with hipPointerGetAttributes):
+ *   - DATA POINTERS of one call are all HOST or all DEVICE pointers (detected with hipPointerGetAttributes; an optional pointer
+ *     that is NULL takes no side).  A mixture, a required pointer that is NULL, and a host off[] that does not start at 0 or
+ *     decreases are M6A_EINVAL before anything is queued.  Where an argument is always a host array, its entry says so:
  *       all-host   -> the library stages through its own device buffers and the call is
  *                     synchronous (results are in the host buffers on return);
  *       all-device -> kernels are enqueued on the context's stream (m6a_set_stream); the
@@ -291,7 +293,7 @@ int m6a_bag_forward(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, int
  * pairwise mean of its n_iters values.  Every bag needs >= n_samples reads (NumPy raises otherwise: M6A_EINVAL).  The sampler
  * is a sequential walk over one random stream and runs on the host; gathers, products and the
  * mean run on the GPU.  m6a_validate_pool starts from read probabilities, m6a_validate encodes
- * first (read_prob [R] or NULL).  Pointers: all host or all device, as everywhere. */
+ * first (read_prob [R] or NULL).  Pointers: see DATA POINTERS at the top. */
 int m6a_validate_pool(m6a_ctx *ctx, const float *read_prob, const int64_t *off, int64_t n_sites,
                       int n_iters, int n_samples, uint32_t seed, float *y_pred, float *y_pred_avg);
 int m6a_validate(m6a_ctx *ctx, const float *X, const uint8_t *site_kmers, const int64_t *off,
@@ -329,7 +331,7 @@ int m6a_shard_plan(const int64_t *off, int64_t n_sites, int64_t batch_size, int6
  *                        site_all / mod_all [shard_site_off[world]] are written on rank dst only (may be NULL
  *                        elsewhere).  ONE grouped send/recv exchange on the context's stream, ragged shards land at
  *                        their offsets without padding.  Data pointers all device (stream-ordered, the caller
- *                        synchronises with m6a_sync) or all host (staged through the context, synchronous), as everywhere;
+ *                        synchronises with m6a_sync) or all host (staged through the context, synchronous): DATA POINTERS at the top;
  *   m6a_gather_reads     the same exchange for the per-read output (data.indiv_proba.csv needs it on the rank that
  *                        writes): read_prob holds this rank's shard_read_off[rank+1] - shard_read_off[rank] reads
  *                        (shard_read_off[r] = off[shard_site_off[r]] of the job's CSR offsets), read_all on dst;
@@ -944,7 +946,7 @@ int m6a_prep_sites_write_read_representation(m6a_prep_sites *p, m6a_ctx *ctx, co
  *                      honoured) and must be destroyed before its context.
  *   m6a_train_step     X [n_bags * bag][9], site_kmers [n_bags][3], y [n_bags] (0 or 1), loss [1], y_pred [n_bags] = s (either may be
  *                      NULL).
- *   m6a_train_epoch    X / site_kmers / off / y describe n_sites sites as everywhere.  Step k takes order[k * batch_size :
+ *   m6a_train_epoch    X / site_kmers / off / y describe n_sites sites as in m6a_infer.  Step k takes order[k * batch_size :
  *                      (k + 1) * batch_size]; the last batch may be short (DataLoader's drop_last=False).  Position i of `order`
  *                      draws its `bag` reads by the rule of m6anet_amd/csrc/m6a_train_draw.h and the kernels read X in place through
  *                      those indices: no batch is materialised.  loss [ceil(n_order / batch_size)], y_pred [n_order].  All steps
@@ -993,7 +995,7 @@ int m6a_prep_sites_write_read_representation(m6a_prep_sites *p, m6a_ctx *ctx, co
  *                      With device pointers it is stream-ordered with no wait.  What it computes is
  *                        dL/dlogit_bk = grad_s_b prod_{j != k} (1 - p_bj) (1 - p_bk) p_bk
  *                      and from there on the step's backward; there is no gradient with respect to X.
- * Pointers are all host or all device, as everywhere; a host dataset is uploaded once per call, device-pointer calls are stream-ordered
+ * Pointers follow DATA POINTERS at the top; a host dataset is uploaded once per call, device-pointer calls are stream-ordered
  * after the one wait named above (m6a_sync before reading their outputs).
  * M6A_EINVAL: bag outside 1..M6A_MAX_SAMPLES; a batch of fewer than 2 reads (torch refuses a one-value batch norm) or of more than
  * 2^20; a site with fewer than `bag` reads; a k-mer id outside 0..65; an `order` entry outside [0, n_sites); a label that is not 0 or

@@ -1290,8 +1290,6 @@ void m6a_destroy(m6a_ctx *c)
         for (auto e : c->prof.start[k]) (void)hipEventDestroy(e);
         for (auto e : c->prof.stop[k]) (void)hipEventDestroy(e);
     }
-    for (DevBuf *b : {&c->raw, &c->tab, &c->goff, &c->rp_scratch, &c->off_scratch, &c->start_pos, &c->plan_dev, &c->tab_reg, &c->val_idx, &c->val_y, &c->val_avg, &c->sX, &c->sK, &c->sOff,
-                      &c->sP, &c->sSite, &c->sMod}) b->release();
     if (c->prof.d_clk) (void)hipFree(c->prof.d_clk);
     if (c->d_wfrag) (void)hipFree(c->d_wfrag);
     if (c->d_wfrag2) (void)hipFree(c->d_wfrag2);
@@ -1307,7 +1305,6 @@ void m6a_destroy(m6a_ctx *c)
     for (void *p : c->graveyard) (void)hipFree(p);
     if (c->rt.C) (void)hipFree(c->rt.C);
     if (c->rt.RS) (void)hipFree(c->rt.RS);
-    for (DevBuf *b : {&c->ctl_dev, &c->rt_rank, &c->rt_order, &c->sOffChunk, &c->jX, &c->jP, &c->jOff, &c->gSite, &c->gMod, &c->gP, &c->mt_scratch, &c->sSigma, &c->sRepr}) b->release();
     for (auto e : c->job.ev_h2d) (void)hipEventDestroy(e);
     for (auto e : c->job.ev_enc) (void)hipEventDestroy(e);
     release_staging(c);
@@ -1317,7 +1314,7 @@ void m6a_destroy(m6a_ctx *c)
     if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
     if (c->ev_ctl) (void)hipEventDestroy(c->ev_ctl);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                                                  // every DevBuf of the context goes here, on the device selected above
 }
 
 int m6a_set_stream(m6a_ctx *c, void *hip_stream)
@@ -1412,31 +1409,29 @@ int m6a_host_free(void *p)
 
 int m6a_encode_reads(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, float *rp)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    if (!c) return M6A_EINVAL;
+    int rc = enter(c);
+    if (rc) return rc;
     if (S < 0) return fail(c, M6A_EINVAL, "n_sites < 0");
     if (S == 0) return M6A_OK;
     if (!X || !km || !off || !rp) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(off) || dev != is_device_ptr(rp))
-        return fail(c, M6A_EINVAL, "X, site_kmers, off, read_prob must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, off, rp}, "X, site_kmers, off, read_prob must be all host or all device pointers");
+    if (dev < 0) return dev;
     if (!dev) {
-        if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-        for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+        rc = csr_check(c, off, S);
+        if (rc) return rc;
         const int64_t R = off[S];
         if (R == 0) return M6A_OK;
         host_bag_range(c, off, S);
         Prefault pf_rp;
         pf_rp.start(rp, (size_t)R * 4, 2);
-        int rc = staged_encode(c, X, km, off, S, R, rp);
+        rc = staged_encode(c, X, km, off, S, R, rp);
         if (rc) return rc;
         return sync_and_check(c);
     }
     // device pointers: total reads (grid size) and smallest bag (kernel choice): one read-back
-    int rc = bag_stats(c, off, S);
+    rc = bag_stats(c, off, S);
     if (rc) return rc;
     return launch_encode(c, X, km, off, S, c->n_reads, rp);
 }
@@ -1448,10 +1443,9 @@ int m6a_read_representation(m6a_ctx *c, const float *X, const uint8_t *km, const
 
 int m6a_read_representation_dtype(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, void *repr, int dtype, float *rp)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    if (!c) return M6A_EINVAL;
+    int rc = enter(c);
+    if (rc) return rc;
     if (dtype != M6A_REPR_F32 && dtype != M6A_REPR_F16) return fail(c, M6A_EINVAL, "dtype %d is neither M6A_REPR_F32 nor M6A_REPR_F16", dtype);
     const size_t row_bytes = dtype == M6A_REPR_F16 ? M6A_N_REPR * 2 : M6A_N_REPR * 4;
     if (S < 0) return fail(c, M6A_EINVAL, "n_sites < 0");
@@ -1459,20 +1453,19 @@ int m6a_read_representation_dtype(m6a_ctx *c, const float *X, const uint8_t *km,
     if (S == 0) return M6A_OK;
     if (!X || !km || !off) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(off) || dev != is_device_ptr(repr) || (rp && dev != is_device_ptr(rp)))
-        return fail(c, M6A_EINVAL, "X, site_kmers, off, repr, read_prob must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, off, repr, rp}, "X, site_kmers, off, repr, read_prob must be all host or all device pointers");
+    if (dev < 0) return dev;
     if (dev) {
         if ((uintptr_t)repr & 15) return fail(c, M6A_EINVAL, "repr must be 16-byte aligned in device memory");
-        int rc = bag_stats(c, off, S);
+        rc = bag_stats(c, off, S);
         if (rc) return rc;
         return launch_repr(c, X, km, off, S, c->n_reads, repr, dtype, rp);
     }
     // Host pointers: chunks cut at site boundaries -- upload the chunk's rows of X, launch, copy its representation (and
     // probabilities) back, in order, all on the context's stream.  128 B per read (64 in binary16) come back for 36 B that went: the return
     // copy is the whole cost, and the pinned ring of m6a_encode_reads (sized for 4 B per read) is left as it is.
-    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+    rc = csr_check(c, off, S);
+    if (rc) return rc;
     const int64_t R = off[S];
     if (R == 0) return M6A_OK;
     const int64_t chunk_reads = (int64_t)1 << 20;             // 128 MB of representation per chunk (a larger bag is its own chunk)
@@ -1487,13 +1480,11 @@ int m6a_read_representation_dtype(m6a_ctx *c, const float *X, const uint8_t *km,
     }
     const int64_t nchunk = (int64_t)cs.size() - 1;
     HIPCHK(c, c->sX.ensure((size_t)widest * 9 * 4));
-    HIPCHK(c, c->sK.ensure((size_t)S * 3));
-    HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
     HIPCHK(c, c->sOffChunk.ensure((size_t)(S + nchunk) * 8));
     HIPCHK(c, c->sRepr.ensure((size_t)widest * row_bytes));
     if (rp) HIPCHK(c, c->sP.ensure((size_t)widest * 4));
-    HIPCHK(c, hipMemcpyAsync(c->sK.p, km, (size_t)S * 3, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, stage_in(c, c->sK, km, (size_t)S * 3));
+    HIPCHK(c, stage_in(c, c->sOff, off, (size_t)(S + 1) * 8));
     for (int64_t k = 0; k < nchunk; k++) {
         const int64_t s0 = cs[k], s1 = cs[k + 1], r0 = off[s0], nr = off[s1] - r0;
         if (nr == 0) continue;
@@ -1501,51 +1492,63 @@ int m6a_read_representation_dtype(m6a_ctx *c, const float *X, const uint8_t *km,
         int64_t *d_off = (int64_t *)c->sOffChunk.p + s0 + k;   // the chunk's own CSR row, starting at 0
         hipLaunchKernelGGL(rebase_off_kernel, dim3((unsigned)((s1 - s0 + 1 + 255) / 256)), dim3(256), 0, c->stream,
                            (const int64_t *)c->sOff.p + s0, s1 - s0 + 1, d_off);
-        int rc = launch_repr(c, (const float *)c->sX.p, (const uint8_t *)c->sK.p + s0 * 3, d_off, s1 - s0, nr, c->sRepr.p, dtype,
-                             rp ? (float *)c->sP.p : nullptr);
+        rc = launch_repr(c, (const float *)c->sX.p, (const uint8_t *)c->sK.p + s0 * 3, d_off, s1 - s0, nr, c->sRepr.p, dtype,
+                         rp ? (float *)c->sP.p : nullptr);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync((char *)repr + (size_t)r0 * row_bytes, c->sRepr.p, (size_t)nr * row_bytes, hipMemcpyDeviceToHost, c->stream));
-        if (rp) HIPCHK(c, hipMemcpyAsync(rp + r0, c->sP.p, (size_t)nr * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, stage_out(c, (char *)repr + (size_t)r0 * row_bytes, c->sRepr, (size_t)nr * row_bytes));
+        if (rp) HIPCHK(c, stage_out(c, rp + r0, c->sP, (size_t)nr * 4));
         HIPCHK(c, hipStreamSynchronize(c->stream));           // the chunk's buffers are reused by the next one
     }
+    return sync_and_check(c);
+}
+
+// The host-pointer body that m6a_site_pool and m6a_site_expectation share, around their launches: read_prob and off staged into sP
+// and sOff with the bag statistics taken on the way, room for the results in sSite / sMod (/ sSigma); then the results back.
+static int pool_stage_in(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, bool sigma)
+{
+    int rc = csr_check(c, off, S);
+    if (rc) return rc;
+    HIPCHK(c, c->sSite.ensure((size_t)S * 4));
+    HIPCHK(c, c->sMod.ensure((size_t)S * 8));
+    if (sigma) HIPCHK(c, c->sSigma.ensure((size_t)S * 8));
+    HIPCHK(c, stage_in(c, c->sP, rp, (size_t)off[S] * 4));
+    HIPCHK(c, stage_in(c, c->sOff, off, (size_t)(S + 1) * 8));
+    host_bag_range(c, off, S);
+    return M6A_OK;
+}
+
+static int pool_stage_out(m6a_ctx *c, int64_t S, float *site, double *mod, double *sigma)
+{
+    HIPCHK(c, stage_out(c, site, c->sSite, (size_t)S * 4));
+    HIPCHK(c, stage_out(c, mod, c->sMod, (size_t)S * 8));
+    if (sigma) HIPCHK(c, stage_out(c, sigma, c->sSigma, (size_t)S * 8));
     return sync_and_check(c);
 }
 
 int m6a_site_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, float thr,
                   uint32_t seed, int rng_mode, int64_t bs, int64_t spb, float *site, double *mod)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    int rc = check_pool_args(c, S, T, K, rng_mode, bs, spb);
+    int rc = enter(c);
+    if (rc) return rc;
+    rc = check_pool_args(c, S, T, K, rng_mode, bs, spb);
     if (rc) return rc;
     if (S == 0) return M6A_OK;
     if (!rp || !off || !site || !mod) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(rp);
-    if (dev != is_device_ptr(off) || dev != is_device_ptr(site) || dev != is_device_ptr(mod))
-        return fail(c, M6A_EINVAL, "read_prob, off, site_prob, mod_ratio must be all host or all device pointers");
+    const int dev = same_side(c, rp, {off, site, mod}, "read_prob, off, site_prob, mod_ratio must be all host or all device pointers");
+    if (dev < 0) return dev;
     if (dev) {
         rc = bag_stats(c, off, S);
         if (rc) return rc;
         return launch_pool(c, rp, off, S, T, K, thr, seed, bs, spb, site, mod);
     }
-    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
-    const int64_t R = off[S];
-    HIPCHK(c, c->sP.ensure((size_t)std::max<int64_t>(R, 1) * 4));
-    HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
-    HIPCHK(c, c->sSite.ensure((size_t)S * 4));
-    HIPCHK(c, c->sMod.ensure((size_t)S * 8));
-    HIPCHK(c, hipMemcpyAsync(c->sP.p, rp, (size_t)R * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    host_bag_range(c, off, S);
+    rc = pool_stage_in(c, rp, off, S, false);
+    if (rc) return rc;
     rc = launch_pool(c, (const float *)c->sP.p, (const int64_t *)c->sOff.p, S, T, K, thr, seed, bs, spb,
                      (float *)c->sSite.p, (double *)c->sMod.p);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(site, c->sSite.p, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(mod, c->sMod.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
-    return sync_and_check(c);
+    return pool_stage_out(c, S, site, mod, nullptr);
 }
 
 int m6a_set_site_mode(m6a_ctx *c, int mode)
@@ -1565,59 +1568,44 @@ int m6a_set_site_mode(m6a_ctx *c, int mode)
 int m6a_site_expectation(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int K, float thr,
                          float *site, double *mod, double *sigma)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    int rc = check_pool_args(c, S, 1, K, M6A_RNG_NUMPY, 1, 1);
+    int rc = enter(c);
+    if (rc) return rc;
+    rc = check_pool_args(c, S, 1, K, M6A_RNG_NUMPY, 1, 1);
     if (rc) return rc;
     if (S == 0) return M6A_OK;
     if (!rp || !off || !site || !mod) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(rp);
-    if (dev != is_device_ptr(off) || dev != is_device_ptr(site) || dev != is_device_ptr(mod) || (sigma && dev != is_device_ptr(sigma)))
-        return fail(c, M6A_EINVAL, "read_prob, off, site_prob, mod_ratio, mc_sigma must be all host or all device pointers");
+    const int dev = same_side(c, rp, {off, site, mod, sigma}, "read_prob, off, site_prob, mod_ratio, mc_sigma must be all host or all device pointers");
+    if (dev < 0) return dev;
     if (dev) {
         rc = bag_stats(c, off, S);
         if (rc) return rc;
         if (c->bag_min < 0 || c->bag_max > 0x7fffffff) return fail(c, M6A_EINVAL, "off[] is not a non-decreasing CSR array");
         return launch_expect(c, rp, off, S, K, thr, c->bag_min, c->bag_max, site, mod, sigma);
     }
-    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
-    const int64_t R = off[S];
-    HIPCHK(c, c->sP.ensure((size_t)std::max<int64_t>(R, 1) * 4));
-    HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
-    HIPCHK(c, c->sSite.ensure((size_t)S * 4));
-    HIPCHK(c, c->sMod.ensure((size_t)S * 8));
-    if (sigma) HIPCHK(c, c->sSigma.ensure((size_t)S * 8));
-    HIPCHK(c, hipMemcpyAsync(c->sP.p, rp, (size_t)R * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    host_bag_range(c, off, S);
+    rc = pool_stage_in(c, rp, off, S, sigma != nullptr);
+    if (rc) return rc;
     if (c->bag_max > 0x7fffffff) return fail(c, M6A_EINVAL, "a bag of more than 2^31 reads");
     rc = launch_expect(c, (const float *)c->sP.p, (const int64_t *)c->sOff.p, S, K, thr, c->bag_min, c->bag_max,
                        (float *)c->sSite.p, (double *)c->sMod.p, sigma ? (double *)c->sSigma.p : nullptr);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(site, c->sSite.p, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(mod, c->sMod.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sigma) HIPCHK(c, hipMemcpyAsync(sigma, c->sSigma.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
-    return sync_and_check(c);
+    return pool_stage_out(c, S, site, mod, sigma);
 }
 
 int m6a_infer(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int T, int K,
               float thr, uint32_t seed, int rng_mode, int64_t bs, int64_t spb, float *rp, float *site, double *mod)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    int rc = check_pool_args(c, S, T, K, rng_mode, bs, spb);
+    int rc = enter(c);
+    if (rc) return rc;
+    rc = check_pool_args(c, S, T, K, rng_mode, bs, spb);
     if (rc) return rc;
     if (S == 0) return M6A_OK;
     if (!X || !km || !off || !site || !mod) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(off) || dev != is_device_ptr(site) ||
-        dev != is_device_ptr(mod) || (rp && dev != is_device_ptr(rp)))
-        return fail(c, M6A_EINVAL, "all data pointers must be host pointers or all device pointers");
+    const int dev = same_side(c, X, {km, off, site, mod, rp}, "all data pointers must be host pointers or all device pointers");
+    if (dev < 0) return dev;
     if (dev) {
         rc = bag_stats(c, off, S);
         if (rc) return rc;
@@ -1642,8 +1630,8 @@ int m6a_infer(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off,
         }
         return pool_run(c, plan, p, thr, site, mod);
     }
-    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+    rc = csr_check(c, off, S);
+    if (rc) return rc;
     const int64_t R = off[S];
     HIPCHK(c, c->sSite.ensure((size_t)S * 4));
     HIPCHK(c, c->sMod.ensure((size_t)S * 8));
@@ -1662,17 +1650,15 @@ int m6a_infer(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off,
 
 int m6a_bag_forward(m6a_ctx *c, const float *X, const uint8_t *km, int64_t B, int bag, float *site)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    if (!c) return M6A_EINVAL;
+    int rc = enter(c);
+    if (rc) return rc;
     if (B < 0 || bag < 1) return fail(c, M6A_EINVAL, "n_bags must be >= 0 and bag >= 1");
     if (B == 0) return M6A_OK;
     if (!X || !km || !site) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(site))
-        return fail(c, M6A_EINVAL, "X, site_kmers, site_prob must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, site}, "X, site_kmers, site_prob must be all host or all device pointers");
+    if (dev < 0) return dev;
     const int64_t R = B * bag;
     HIPCHK(c, c->off_scratch.ensure((size_t)(B + 1) * 8));
     HIPCHK(c, c->rp_scratch.ensure((size_t)R * 4));
@@ -1682,20 +1668,18 @@ int m6a_bag_forward(m6a_ctx *c, const float *X, const uint8_t *km, int64_t B, in
     HIPCHK(c, hipGetLastError());
     const float *dX = X; const uint8_t *dK = km; float *dS = site;
     if (!dev) {
-        HIPCHK(c, c->sX.ensure((size_t)R * 9 * 4));
-        HIPCHK(c, c->sK.ensure((size_t)B * 3));
         HIPCHK(c, c->sSite.ensure((size_t)B * 4));
-        HIPCHK(c, hipMemcpyAsync(c->sX.p, X, (size_t)R * 9 * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->sK.p, km, (size_t)B * 3, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, stage_in(c, c->sX, X, (size_t)R * 9 * 4));
+        HIPCHK(c, stage_in(c, c->sK, km, (size_t)B * 3));
         dX = (const float *)c->sX.p; dK = (const uint8_t *)c->sK.p; dS = (float *)c->sSite.p;
     }
     c->bag_min = c->bag_max = bag; c->n_reads = R;
-    int rc = launch_encode(c, dX, dK, d_off, B, R, d_p);
+    rc = launch_encode(c, dX, dK, d_off, B, R, d_p);
     if (rc) return rc;
     hipLaunchKernelGGL(bag_noisy_or_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, d_p, B, bag, dS);
     HIPCHK(c, hipGetLastError());
     if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(site, dS, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, stage_out(c, site, c->sSite, (size_t)B * 4));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return M6A_OK;

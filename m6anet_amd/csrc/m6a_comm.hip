@@ -170,7 +170,7 @@ int m6a_device_link(int dev_a, int dev_b, int *link_type, int *hops, int *peer_a
 
 namespace {
 
-struct GatherArray { const void *src; void *out; int dtype; size_t esz; const char *name; };
+struct GatherArray { const void *src; void *out; int dtype; size_t esz; const char *name; DevBuf m6a_ctx::*up, m6a_ctx::*down; };
 
 // ONE grouped exchange on the context's stream: every rank (dst included) sends its slice of each array, dst posts the
 // matching receives at the shards' offsets -- direct peer-to-peer writes over xGMI, no ring, no padding.  A failing
@@ -211,9 +211,10 @@ int check_gather_args(m6a_ctx *c, const int64_t *cuts, int dst)
     return M6A_OK;
 }
 
-}  // namespace
-
-int m6a_gather(m6a_ctx *c, const float *site, const double *mod, const int64_t *cuts, int dst, float *site_all, double *mod_all)
+// m6a_gather and m6a_gather_reads: the arguments held to the pointer convention (the arrays that take part are this rank's slices
+// when it has sites and the receive arrays on dst), then the exchange -- in place for device pointers; for host pointers staged
+// through the context's buffers (`up` to send from, `down` to receive into) and synchronous.
+static int gather_call(m6a_ctx *c, GatherArray *arr, int n_arr, const int64_t *cuts, int dst, const char *dst_needs, const char *sentence)
 {
     settle(c);
     if (!c) return M6A_EINVAL;
@@ -222,66 +223,44 @@ int m6a_gather(m6a_ctx *c, const float *site, const double *mod, const int64_t *
     if (c->job.open) return job_busy(c);
     const int W = c->comm_world, me = c->comm_rank;
     const int64_t mine = cuts[me + 1] - cuts[me], total = cuts[W] - cuts[0];
-    if (mine > 0 && (!site || !mod)) return fail(c, M6A_EINVAL, "null pointer argument");
-    if (me == dst && total > 0 && (!site_all || !mod_all)) return fail(c, M6A_EINVAL, "rank dst needs site_all and mod_all");
-    HIPCHK(c, hipSetDevice(c->device));
     const bool recv = me == dst && total > 0;
-    const bool dev = mine > 0 ? is_device_ptr(site) : recv ? is_device_ptr(site_all) : true;
-    if ((mine > 0 && dev != is_device_ptr(mod)) || (recv && (dev != is_device_ptr(site_all) || dev != is_device_ptr(mod_all))))
-        return fail(c, M6A_EINVAL, "site_prob, mod_ratio, site_all, mod_all must be all host or all device pointers");
-    GatherArray arr[2] = {{site, site_all, 7 /* ncclFloat32 */, 4, "site_prob"}, {mod, mod_all, 8 /* ncclFloat64 */, 8, "mod_ratio"}};
-    if (dev) return gather_group(c, arr, 2, cuts, dst);
-    // host arrays: staged through the context's device buffers, synchronous
-    if (mine > 0) {
-        HIPCHK(c, c->sSite.ensure((size_t)mine * 4));
-        HIPCHK(c, c->sMod.ensure((size_t)mine * 8));
-        HIPCHK(c, hipMemcpyAsync(c->sSite.p, site, (size_t)mine * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->sMod.p, mod, (size_t)mine * 8, hipMemcpyHostToDevice, c->stream));
-        arr[0].src = c->sSite.p; arr[1].src = c->sMod.p;
+    for (int a = 0; a < n_arr; a++) if (mine > 0 && !arr[a].src) return fail(c, M6A_EINVAL, "null pointer argument");
+    for (int a = 0; a < n_arr; a++) if (recv && !arr[a].out) return fail(c, M6A_EINVAL, "%s", dst_needs);
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev = mine > 0 ? is_device_ptr(arr[0].src) : recv ? is_device_ptr(arr[0].out) : true;
+    for (int a = 0; a < n_arr; a++)
+        if ((mine > 0 && dev != is_device_ptr(arr[a].src)) || (recv && dev != is_device_ptr(arr[a].out))) return fail(c, M6A_EINVAL, "%s", sentence);
+    if (dev) return gather_group(c, arr, n_arr, cuts, dst);
+    void *host_out[2] = {nullptr, nullptr};
+    for (int a = 0; a < n_arr; a++) {
+        DevBuf &up = c->*arr[a].up, &down = c->*arr[a].down;
+        if (mine > 0) { HIPCHK(c, stage_in(c, up, arr[a].src, (size_t)mine * arr[a].esz)); arr[a].src = up.p; }
+        host_out[a] = arr[a].out;
+        if (recv) { HIPCHK(c, down.ensure((size_t)total * arr[a].esz)); arr[a].out = down.p; }
     }
-    if (recv) {
-        HIPCHK(c, c->gSite.ensure((size_t)total * 4));
-        HIPCHK(c, c->gMod.ensure((size_t)total * 8));
-        arr[0].out = c->gSite.p; arr[1].out = c->gMod.p;
-    }
-    rc = gather_group(c, arr, 2, cuts, dst);
+    rc = gather_group(c, arr, n_arr, cuts, dst);
     if (rc) return rc;
-    if (recv) {
-        rc = d2h_through_ring(c, site_all, c->gSite.p, (size_t)total * 4);
-        if (rc) return rc;
-        rc = d2h_through_ring(c, mod_all, c->gMod.p, (size_t)total * 8);
+    for (int a = 0; a < n_arr && recv; a++) {
+        rc = d2h_through_ring(c, host_out[a], arr[a].out, (size_t)total * arr[a].esz);
         if (rc) return rc;
     }
     return sync_and_check(c);
 }
 
+}  // namespace
+
+int m6a_gather(m6a_ctx *c, const float *site, const double *mod, const int64_t *cuts, int dst, float *site_all, double *mod_all)
+{
+    GatherArray arr[2] = {{site, site_all, 7 /* ncclFloat32 */, 4, "site_prob", &m6a_ctx::sSite, &m6a_ctx::gSite},
+                          {mod, mod_all, 8 /* ncclFloat64 */, 8, "mod_ratio", &m6a_ctx::sMod, &m6a_ctx::gMod}};
+    return gather_call(c, arr, 2, cuts, dst, "rank dst needs site_all and mod_all",
+                       "site_prob, mod_ratio, site_all, mod_all must be all host or all device pointers");
+}
+
 int m6a_gather_reads(m6a_ctx *c, const float *rp, const int64_t *cuts, int dst, float *rp_all)
 {
-    settle(c);
-    if (!c) return M6A_EINVAL;
-    int rc = check_gather_args(c, cuts, dst);
-    if (rc) return rc;
-    if (c->job.open) return job_busy(c);
-    const int W = c->comm_world, me = c->comm_rank;
-    const int64_t mine = cuts[me + 1] - cuts[me], total = cuts[W] - cuts[0];
-    if (mine > 0 && !rp) return fail(c, M6A_EINVAL, "null pointer argument");
-    if (me == dst && total > 0 && !rp_all) return fail(c, M6A_EINVAL, "rank dst needs read_all");
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool recv = me == dst && total > 0;
-    const bool dev = mine > 0 ? is_device_ptr(rp) : recv ? is_device_ptr(rp_all) : true;
-    if (mine > 0 && recv && dev != is_device_ptr(rp_all)) return fail(c, M6A_EINVAL, "read_prob and read_all must be both host or both device pointers");
-    GatherArray arr[1] = {{rp, rp_all, 7 /* ncclFloat32 */, 4, "read_prob"}};
-    if (dev) return gather_group(c, arr, 1, cuts, dst);
-    if (mine > 0) {
-        HIPCHK(c, c->sP.ensure((size_t)mine * 4));
-        HIPCHK(c, hipMemcpyAsync(c->sP.p, rp, (size_t)mine * 4, hipMemcpyHostToDevice, c->stream));
-        arr[0].src = c->sP.p;
-    }
-    if (recv) { HIPCHK(c, c->gP.ensure((size_t)total * 4)); arr[0].out = c->gP.p; }
-    rc = gather_group(c, arr, 1, cuts, dst);
-    if (rc) return rc;
-    if (recv) { rc = d2h_through_ring(c, rp_all, c->gP.p, (size_t)total * 4); if (rc) return rc; }
-    return sync_and_check(c);
+    GatherArray arr[1] = {{rp, rp_all, 7 /* ncclFloat32 */, 4, "read_prob", &m6a_ctx::sP, &m6a_ctx::gP}};
+    return gather_call(c, arr, 1, cuts, dst, "rank dst needs read_all", "read_prob and read_all must be both host or both device pointers");
 }
 
 

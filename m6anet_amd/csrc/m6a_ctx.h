@@ -5,6 +5,9 @@
 //   m6a_comm.hip       RCCL bound at run time, m6a_comm_*, m6a_gather, m6a_gather_reads, m6a_device_link
 //   m6a_expect.hip     the closed-form site probability: site_expect_kernel (its launches are in m6a_api.hip)
 //   m6a_validate.hip   validation forward: the without-replacement sampler on host threads, m6a_validate / m6a_validate_pool
+//   m6a_train.hip      the trainer (m6a_train_*): its kernels, its scratch and the calls around them
+// What every entry point with data pointers obeys -- all host or all device -- is stated once, below: enter, same_side, csr_check,
+// stage_in / stage_out.  DevBuf frees itself, so neither destroy keeps a list of buffers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -47,6 +50,12 @@ struct DevBuf {
         return e;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // A buffer goes with the struct that holds it: m6a_destroy and m6a_train_destroy select the device and delete, and no list of
+    // names has to be kept for them (sSigma, sRepr and sGradS were each appended to one by hand).
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
 };
 
 constexpr int kMaxProfiled = 8192;
@@ -310,6 +319,55 @@ struct HintScope {
     explicit HintScope(m6a_ctx *ctx) : c(ctx) {}
     ~HintScope() { if (c) c->hint_off = nullptr; }
 };
+
+// ---- the pointer convention of include/m6a.h (DATA POINTERS), once --------------------------------------------------------------
+// An entry point that takes data pointers opens with `HintScope hint_scope(c); int rc = enter(c);` (the trainer's calls, the setters
+// and m6a_random_stream have no hint scope: they leave an armed hint to the call it was meant for), checks its scalar arguments and
+// its required pointers, selects the device and asks same_side whether this is a host or a device call.  hipSetDevice stays behind
+// the argument checks: a refused call, or one that has nothing to do, leaves the thread's current device alone.  A host call holds
+// its off[] to csr_check, stages its inputs in with stage_in, launches on the staged arrays, stages the results out with stage_out
+// and closes with one synchronise.  The pinned ring (m6a_host_ring.hip) is the other way in and out, for the calls whose transfer is
+// worth overlapping.
+
+// The prologue: the background set-up has ended, there is a context, and no streaming job owns it.
+static inline int enter(m6a_ctx *c)
+{
+    settle(c);
+    if (!c) return M6A_EINVAL;
+    return job_busy(c);
+}
+
+// The side check: 1 for a device call, 0 for a host call, or the refusal (every M6A_E* code is negative).  `first` decides the
+// side and every other pointer must be on it, or the call is refused with the caller's sentence.  NULL among `rest` is an optional
+// argument left out: the required ones were refused before.
+static inline int same_side(m6a_ctx *c, const void *first, std::initializer_list<const void *> rest, const char *sentence)
+{
+    const bool dev = is_device_ptr(first);
+    for (const void *p : rest)
+        if (p && dev != is_device_ptr(p)) return fail(c, M6A_EINVAL, "%s", sentence);
+    return dev;
+}
+
+// A host CSR array before anything is read through it: S + 1 offsets from 0, none below the one before.
+static inline int csr_check(m6a_ctx *c, const int64_t *off, int64_t S)
+{
+    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
+    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+    return M6A_OK;
+}
+
+// Staging in: room in `b`, then the upload, queued on the context's stream; b.p is the device copy.  An empty array still gets a
+// block, so no kernel is handed NULL.  Staging out is the copy back; the caller's closing synchronise makes it the caller's.
+static inline hipError_t stage_in(m6a_ctx *c, DevBuf &b, const void *host, size_t bytes)
+{
+    const hipError_t e = b.ensure(bytes ? bytes : 1);
+    return e != hipSuccess ? e : hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, c->stream);
+}
+static inline hipError_t stage_out(m6a_ctx *c, void *host, const DevBuf &b, size_t bytes)
+{
+    return hipMemcpyAsync(host, b.p, bytes, hipMemcpyDeviceToHost, c->stream);
+}
+
 // m6a_api.hip
 int launch_encode(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, float *rp);
 int launch_repr(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int64_t R, void *repr, int dtype, float *rp);

@@ -136,9 +136,8 @@ void job_append_offsets(m6a_ctx *c, char *pin, const int64_t *off, int64_t i, in
 int job_feed_impl(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t n, bool dev)
 {
     auto &j = c->job;
-    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < n; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
-    int rc;
+    int rc = csr_check(c, off, n);
+    if (rc) return rc;
     if (dev) {
         // features already on the device: every piece of <= cap_sites sites is a chunk of its own, read in place
         rc = job_flush(c);
@@ -335,9 +334,9 @@ int m6a_job_end(m6a_ctx *c, float *rp, float *site, double *mod)
     const int64_t S = j.S, R = j.R;
     if (S == 0) return M6A_OK;
     if (!site || !mod) return fail(c, M6A_EINVAL, "null pointer argument");
-    const bool dev = is_device_ptr(site);
-    if (dev != is_device_ptr(mod) || (rp && R > 0 && dev != is_device_ptr(rp)))
-        return fail(c, M6A_EINVAL, "read_prob, site_prob, mod_ratio must be all host or all device pointers");
+    // without reads read_prob has nothing to point at (an empty tensor's pointer may be anything): it is left out of the check
+    const int dev = same_side(c, site, {mod, R > 0 ? rp : nullptr}, "read_prob, site_prob, mod_ratio must be all host or all device pointers");
+    if (dev < 0) return dev;
     host_bag_range(c, j.off.data(), S);
     float *d_site = site; double *d_mod = mod;
     if (!dev) {

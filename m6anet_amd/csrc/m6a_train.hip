@@ -505,7 +505,7 @@ __global__ __launch_bounds__(kClipThreads) void train_clip_adam_kernel(const dou
 
 }  // namespace
 
-struct m6a_trainer {
+struct __attribute__((visibility("hidden"))) m6a_trainer {                 // its destructor (the DevBufs') is no symbol of the library
     m6a_ctx *c = nullptr;
     m6a_train_config cfg{};
     float *P = nullptr, *M = nullptr, *V = nullptr, *G = nullptr;       // [M6A_N_WEIGHTS] each, blob order
@@ -548,10 +548,11 @@ int ensure_scratch(m6a_trainer *t, int64_t B, int bag)
     return M6A_OK;
 }
 
-// reads the lowest (index, kind) the check kernels reported; one wait for the stream
-int checked(m6a_trainer *t, const char *index_name)
+// after the check kernels' launches: reads the lowest (index, kind) they reported; one wait for the stream
+int checked(m6a_trainer *t)
 {
     m6a_ctx *c = t->c;
+    HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(t->h_err, t->d_err, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     t->n_syncs++;
@@ -562,14 +563,8 @@ int checked(m6a_trainer *t, const char *index_name)
     case kErrReads: return fail(c, M6A_EINVAL, "site %lld has fewer reads than bag (or more than 2^32 - 1)", at);
     case kErrKmer: return fail(c, M6A_EINVAL, "site %lld: k-mer id outside 0..%d", at, M6A_N_KMERS - 1);
     case kErrLabel: return fail(c, M6A_EINVAL, "site %lld: the label is not 0 or 1", at);
-    default: return fail(c, M6A_EINVAL, "%s[%lld] is outside [0, n_sites)", index_name, at);
+    default: return fail(c, M6A_EINVAL, "order[%lld] is outside [0, n_sites)", at);
     }
-}
-
-int arm_check(m6a_trainer *t)
-{
-    HIPCHK(t->c, hipMemsetAsync(t->d_err, 0xff, 8, t->c->stream));
-    return M6A_OK;
 }
 
 // how a batch is cut: chunks of whole 32-read tiles for layer 1 and its backward, 64 / bag whole bags per wave for train_fwd2_kernel
@@ -632,22 +627,28 @@ int queue_step(m6a_trainer *t, const Batch &bt, float *loss, float *y_pred)
     return M6A_OK;
 }
 
+// the context's prologue (m6a_ctx.h) behind a trainer; the device is selected at once: every trainer call works on it
 int enter(m6a_trainer *t)
 {
-    if (!t || !t->c) return M6A_EINVAL;
-    settle(t->c);
-    if (t->c->job.open) return job_busy(t->c);
+    if (!t) return M6A_EINVAL;
+    int rc = m6a_detail::enter(t->c);
+    if (rc) return rc;
     HIPCHK(t->c, hipSetDevice(t->c->device));
+    return M6A_OK;
+}
+
+// the closing synchronise of a call that hands results to the host, counted for m6a_train_stats
+int sync_counted(m6a_trainer *t)
+{
+    HIPCHK(t->c, hipStreamSynchronize(t->c->stream));
+    t->n_syncs++;
     return M6A_OK;
 }
 
 int copy_out(m6a_trainer *t, void *dst, const void *src, size_t bytes)
 {
-    m6a_ctx *c = t->c;
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    t->n_syncs++;
-    return M6A_OK;
+    HIPCHK(t->c, hipMemcpyAsync(dst, src, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, t->c->stream));
+    return sync_counted(t);
 }
 
 }  // namespace
@@ -695,15 +696,12 @@ void m6a_train_destroy(m6a_trainer *t)
 {
     if (!t) return;
     if (t->c) { (void)hipSetDevice(t->c->device); (void)hipStreamSynchronize(t->c->stream); }
-    for (DevBuf *b : {&t->z1, &t->dy1, &t->xbuf, &t->h2, &t->dlogit, &t->dxe, &t->wpart, &t->loss_term, &t->ridx, &t->sX, &t->sK, &t->sOff, &t->sY,
-                      &t->sOrder, &t->sLoss, &t->sPred, &t->keptK, &t->sGradS})
-        b->release();
     if (t->P) (void)hipFree(t->P);
     if (t->stat) (void)hipFree(t->stat);
     if (t->part2) (void)hipFree(t->part2);
     if (t->d_err) (void)hipFree(t->d_err);
     if (t->h_err) (void)hipHostFree(t->h_err);
-    delete t;
+    delete t;                                           // with every DevBuf it holds
 }
 
 int m6a_train_step(m6a_trainer *t, const float *X, const uint8_t *km, const float *y, int64_t B, int bag, float *loss, float *y_pred)
@@ -715,9 +713,8 @@ int m6a_train_step(m6a_trainer *t, const float *X, const uint8_t *km, const floa
     if (B < 1 || B * bag < 2) return fail(c, M6A_EINVAL, "a step needs n_bags * bag >= 2 reads (batch norm over one value is undefined)");
     if (B > kMaxBatchReads || B * bag > kMaxBatchReads) return fail(c, M6A_EINVAL, "a batch holds at most 2^20 reads");
     if (!X || !km || !y) return fail(c, M6A_EINVAL, "null pointer argument");
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(y) || (loss && dev != is_device_ptr(loss)) || (y_pred && dev != is_device_ptr(y_pred)))
-        return fail(c, M6A_EINVAL, "X, site_kmers, y, loss, y_pred must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, y, loss, y_pred}, "X, site_kmers, y, loss, y_pred must be all host or all device pointers");
+    if (dev < 0) return dev;
     const int64_t N = B * bag;
     rc = ensure_scratch(t, B, bag);
     if (rc) return rc;
@@ -725,30 +722,23 @@ int m6a_train_step(m6a_trainer *t, const float *X, const uint8_t *km, const floa
     HIPCHK(c, t->sPred.ensure((size_t)B * 4));
     Batch bt{X, nullptr, km, nullptr, y, B, N, bag};
     if (!dev) {
-        HIPCHK(c, t->sX.ensure((size_t)N * 9 * 4));
-        HIPCHK(c, t->sK.ensure((size_t)B * 3));
-        HIPCHK(c, t->sY.ensure((size_t)B * 4));
-        HIPCHK(c, hipMemcpyAsync(t->sX.p, X, (size_t)N * 9 * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(t->sK.p, km, (size_t)B * 3, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(t->sY.p, y, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, stage_in(c, t->sX, X, (size_t)N * 9 * 4));
+        HIPCHK(c, stage_in(c, t->sK, km, (size_t)B * 3));
+        HIPCHK(c, stage_in(c, t->sY, y, (size_t)B * 4));
         bt.X = (const float *)t->sX.p; bt.km = (const uint8_t *)t->sK.p; bt.y = (const float *)t->sY.p;
     }
-    rc = arm_check(t);
-    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(t->d_err, 0xff, 8, c->stream));       // nothing reported yet (checked)
     hipLaunchKernelGGL(train_check_sites_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, bt.km, (const int64_t *)nullptr, bt.y,
                        B, bag, t->d_err);
     t->n_launches++;
-    HIPCHK(c, hipGetLastError());
-    rc = checked(t, "order");
+    rc = checked(t);
     if (rc) return rc;
     float *d_loss = dev && loss ? loss : (float *)t->sLoss.p, *d_pred = dev && y_pred ? y_pred : (float *)t->sPred.p;
     rc = queue_step(t, bt, d_loss, d_pred);
     if (rc || dev) return rc;
-    if (loss) HIPCHK(c, hipMemcpyAsync(loss, d_loss, 4, hipMemcpyDeviceToHost, c->stream));
-    if (y_pred) HIPCHK(c, hipMemcpyAsync(y_pred, d_pred, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    t->n_syncs++;
-    return M6A_OK;
+    if (loss) HIPCHK(c, stage_out(c, loss, t->sLoss, 4));
+    if (y_pred) HIPCHK(c, stage_out(c, y_pred, t->sPred, (size_t)B * 4));
+    return sync_counted(t);
 }
 
 int m6a_train_epoch(m6a_trainer *t, const float *X, const uint8_t *km, const int64_t *off, const float *y, int64_t S, const int64_t *order,
@@ -765,10 +755,9 @@ int m6a_train_epoch(m6a_trainer *t, const float *X, const uint8_t *km, const int
     if (last * bag < 2) return fail(c, M6A_EINVAL, "a batch of this epoch has fewer than 2 reads (batch norm over one value is undefined)");
     if (n_order > INT64_MAX / 8 / bag) return fail(c, M6A_EINVAL, "n_order * bag too large");
     if (!X || !km || !off || !y || !order) return fail(c, M6A_EINVAL, "null pointer argument");
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(off) || dev != is_device_ptr(y) || dev != is_device_ptr(order) ||
-        (loss && dev != is_device_ptr(loss)) || (y_pred && dev != is_device_ptr(y_pred)))
-        return fail(c, M6A_EINVAL, "X, site_kmers, off, y, order, loss, y_pred must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, off, y, order, loss, y_pred},
+                              "X, site_kmers, off, y, order, loss, y_pred must be all host or all device pointers");
+    if (dev < 0) return dev;
     const int64_t n_steps = (n_order + bs - 1) / bs;
     rc = ensure_scratch(t, largest, bag);
     if (rc) return rc;
@@ -779,31 +768,23 @@ int m6a_train_epoch(m6a_trainer *t, const float *X, const uint8_t *km, const int
     Batch bt{X, nullptr, km, nullptr, y, 0, 0, bag};
     if (!dev) {
         // a host dataset goes up once per call
-        if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-        for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
-        const int64_t R = off[S];
-        HIPCHK(c, t->sX.ensure((size_t)std::max<int64_t>(R, 1) * 9 * 4));
-        HIPCHK(c, t->sK.ensure((size_t)S * 3));
-        HIPCHK(c, t->sOff.ensure((size_t)(S + 1) * 8));
-        HIPCHK(c, t->sY.ensure((size_t)S * 4));
-        HIPCHK(c, t->sOrder.ensure((size_t)n_order * 8));
-        HIPCHK(c, hipMemcpyAsync(t->sX.p, X, (size_t)R * 9 * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(t->sK.p, km, (size_t)S * 3, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(t->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(t->sY.p, y, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(t->sOrder.p, order, (size_t)n_order * 8, hipMemcpyHostToDevice, c->stream));
+        rc = csr_check(c, off, S);
+        if (rc) return rc;
+        HIPCHK(c, stage_in(c, t->sX, X, (size_t)off[S] * 9 * 4));
+        HIPCHK(c, stage_in(c, t->sK, km, (size_t)S * 3));
+        HIPCHK(c, stage_in(c, t->sOff, off, (size_t)(S + 1) * 8));
+        HIPCHK(c, stage_in(c, t->sY, y, (size_t)S * 4));
+        HIPCHK(c, stage_in(c, t->sOrder, order, (size_t)n_order * 8));
         bt.X = (const float *)t->sX.p; bt.km = (const uint8_t *)t->sK.p; bt.y = (const float *)t->sY.p;
         d_off = (const int64_t *)t->sOff.p; d_order = (const int64_t *)t->sOrder.p;
     }
     int64_t *ridx = (int64_t *)t->ridx.p;
-    rc = arm_check(t);
-    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(t->d_err, 0xff, 8, c->stream));       // nothing reported yet (checked)
     hipLaunchKernelGGL(train_check_sites_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, bt.km, d_off, bt.y, S, bag, t->d_err);
     hipLaunchKernelGGL(train_draw_kernel, dim3((unsigned)((n_order + 63) / 64)), dim3(64), 0, c->stream, d_off, d_order, n_order, S, bag, seed, ridx,
                        t->d_err);
     t->n_launches += 2;
-    HIPCHK(c, hipGetLastError());
-    rc = checked(t, "order");
+    rc = checked(t);
     if (rc) return rc;
     float *d_loss = dev && loss ? loss : (float *)t->sLoss.p, *d_pred = dev && y_pred ? y_pred : (float *)t->sPred.p;
     for (int64_t k = 0; k < n_steps; k++) {             // queued back to back: nothing below waits for the device
@@ -815,11 +796,9 @@ int m6a_train_epoch(m6a_trainer *t, const float *X, const uint8_t *km, const int
         if (rc) return rc;
     }
     if (dev) return M6A_OK;
-    if (loss) HIPCHK(c, hipMemcpyAsync(loss, d_loss, (size_t)n_steps * 4, hipMemcpyDeviceToHost, c->stream));
-    if (y_pred) HIPCHK(c, hipMemcpyAsync(y_pred, d_pred, (size_t)n_order * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    t->n_syncs++;
-    return M6A_OK;
+    if (loss) HIPCHK(c, stage_out(c, loss, t->sLoss, (size_t)n_steps * 4));
+    if (y_pred) HIPCHK(c, stage_out(c, y_pred, t->sPred, (size_t)n_order * 4));
+    return sync_counted(t);
 }
 
 // ---- the step cut at s: forward gives s, backward takes dL/ds (include/m6a.h) -------------------------------------------------------
@@ -833,10 +812,7 @@ int m6a_train_set_weights(m6a_trainer *t, const float *blob)
     HIPCHK(c, hipMemcpyAsync(t->P, blob, (size_t)M6A_N_WEIGHTS * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     t->kept_ticket = 0;
     t->kept_lost = "the weights were replaced since that forward (m6a_train_set_weights)";
-    if (dev) return M6A_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    t->n_syncs++;
-    return M6A_OK;
+    return dev ? M6A_OK : sync_counted(t);
 }
 
 int m6a_train_running_stats(m6a_trainer *t, float *stats)
@@ -860,21 +836,18 @@ int m6a_train_forward(m6a_trainer *t, const float *X, const uint8_t *km, int64_t
     if (B < 1 || B * bag < 2) return fail(c, M6A_EINVAL, "a forward needs n_bags * bag >= 2 reads (batch norm over one value is undefined)");
     if (B > kMaxBatchReads || B * bag > kMaxBatchReads) return fail(c, M6A_EINVAL, "a batch holds at most 2^20 reads");
     if (!X || !km || !s || !ticket) return fail(c, M6A_EINVAL, "null pointer argument");
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(s)) return fail(c, M6A_EINVAL, "X, site_kmers, s must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, s}, "X, site_kmers, s must be all host or all device pointers");
+    if (dev < 0) return dev;
     const int64_t N = B * bag;
     const uint8_t *d_km = km;
     if (!dev) {
-        HIPCHK(c, t->sK.ensure((size_t)B * 3));
-        HIPCHK(c, hipMemcpyAsync(t->sK.p, km, (size_t)B * 3, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, stage_in(c, t->sK, km, (size_t)B * 3));
         d_km = (const uint8_t *)t->sK.p;
     }
-    rc = arm_check(t);
-    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(t->d_err, 0xff, 8, c->stream));       // nothing reported yet (checked)
     hipLaunchKernelGGL(train_check_kmers_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, d_km, B, t->d_err);
     t->n_launches++;
-    HIPCHK(c, hipGetLastError());
-    rc = checked(t, "order");
+    rc = checked(t);
     if (rc) return rc;                                  // nothing is changed: an earlier forward's activations are still kept
     t->kept_ticket = 0;
     t->kept_lost = "a later forward on this trainer failed part-way";
@@ -885,9 +858,8 @@ int m6a_train_forward(m6a_trainer *t, const float *X, const uint8_t *km, int64_t
     Batch bt{X, nullptr, (const uint8_t *)t->keptK.p, nullptr, nullptr, B, N, bag};
     float *d_s = s;
     if (!dev) {
-        HIPCHK(c, t->sX.ensure((size_t)N * 9 * 4));
         HIPCHK(c, t->sPred.ensure((size_t)B * 4));
-        HIPCHK(c, hipMemcpyAsync(t->sX.p, X, (size_t)N * 9 * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, stage_in(c, t->sX, X, (size_t)N * 9 * 4));
         bt.X = (const float *)t->sX.p;
         d_s = (float *)t->sPred.p;
     }
@@ -908,10 +880,8 @@ int m6a_train_forward(m6a_trainer *t, const float *X, const uint8_t *km, int64_t
     t->kept_lost = "a later forward on this trainer overwrote those activations";
     *ticket = t->kept_ticket;
     if (dev) return M6A_OK;
-    HIPCHK(c, hipMemcpyAsync(s, d_s, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    t->n_syncs++;
-    return M6A_OK;
+    HIPCHK(c, stage_out(c, s, t->sPred, (size_t)B * 4));
+    return sync_counted(t);
 }
 
 int m6a_train_backward(m6a_trainer *t, int64_t ticket, const float *grad_s, float *grads)
@@ -922,13 +892,12 @@ int m6a_train_backward(m6a_trainer *t, int64_t ticket, const float *grad_s, floa
     if (!grad_s || !grads) return fail(c, M6A_EINVAL, "null pointer argument");
     if (ticket < 1 || ticket > t->n_forwards) return fail(c, M6A_EINVAL, "ticket %lld was not given by m6a_train_forward on this trainer", (long long)ticket);
     if (ticket != t->kept_ticket) return fail(c, M6A_EINVAL, "the activations of ticket %lld are gone: %s", (long long)ticket, t->kept_lost);
-    const bool dev = is_device_ptr(grad_s);
-    if (dev != is_device_ptr(grads)) return fail(c, M6A_EINVAL, "grad_s, grads must be all host or all device pointers");
+    const int dev = same_side(c, grad_s, {grads}, "grad_s, grads must be all host or all device pointers");
+    if (dev < 0) return dev;
     const int64_t B = t->kept_B;
     const float *d_g = grad_s;
     if (!dev) {
-        HIPCHK(c, t->sGradS.ensure((size_t)B * 4));
-        HIPCHK(c, hipMemcpyAsync(t->sGradS.p, grad_s, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, stage_in(c, t->sGradS, grad_s, (size_t)B * 4));
         d_g = (const float *)t->sGradS.p;
     }
     HIPCHK(c, t->sLoss.ensure(4));

@@ -299,6 +299,19 @@ int check_validate_args(m6a_ctx *c, int64_t S, int T, int K)
     return M6A_OK;
 }
 
+// The tail of both host-pointer calls: the read probabilities are in sP.  Pools them and stages y_pred out, with read_prob and
+// y_pred_avg where the caller asked for them.
+static int validate_staged(m6a_ctx *c, const int64_t *off, int64_t S, int T, int K, uint32_t seed, float *rp, float *y, float *avg)
+{
+    HIPCHK(c, c->val_y.ensure((size_t)T * S * 4));
+    HIPCHK(c, c->val_avg.ensure((size_t)S * 4));
+    int rc = launch_validate_pool(c, (const float *)c->sP.p, off, S, T, K, seed, (float *)c->val_y.p, avg ? (float *)c->val_avg.p : nullptr);
+    if (rc) return rc;
+    if (rp) HIPCHK(c, stage_out(c, rp, c->sP, (size_t)off[S] * 4));
+    HIPCHK(c, stage_out(c, y, c->val_y, (size_t)T * S * 4));
+    if (avg) HIPCHK(c, stage_out(c, avg, c->val_avg, (size_t)S * 4));
+    return sync_and_check(c);
+}
 
 }  // namespace m6a_detail
 
@@ -308,17 +321,16 @@ extern "C" {
 int m6a_validate_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S, int T, int K, uint32_t seed,
                       float *y, float *avg)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    int rc = check_validate_args(c, S, T, K);
+    int rc = enter(c);
+    if (rc) return rc;
+    rc = check_validate_args(c, S, T, K);
     if (rc) return rc;
     if (S == 0) return M6A_OK;
     if (!rp || !off || !y) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(rp);
-    if (dev != is_device_ptr(off) || dev != is_device_ptr(y) || (avg && dev != is_device_ptr(avg)))
-        return fail(c, M6A_EINVAL, "read_prob, off, y_pred, y_pred_avg must be all host or all device pointers");
+    const int dev = same_side(c, rp, {off, y, avg}, "read_prob, off, y_pred, y_pred_avg must be all host or all device pointers");
+    if (dev < 0) return dev;
     std::vector<int64_t> h_off;
     const int64_t *ho = off;
     if (dev) {
@@ -327,36 +339,26 @@ int m6a_validate_pool(m6a_ctx *c, const float *rp, const int64_t *off, int64_t S
         HIPCHK(c, hipStreamSynchronize(c->stream));
         ho = h_off.data();
     }
-    if (ho[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < S; s++) if (ho[s + 1] < ho[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
-    if (dev) return launch_validate_pool(c, rp, ho, S, T, K, seed, y, avg);
-    const int64_t R = ho[S];
-    HIPCHK(c, c->sP.ensure((size_t)std::max<int64_t>(R, 1) * 4));
-    HIPCHK(c, c->val_y.ensure((size_t)T * S * 4));
-    HIPCHK(c, c->val_avg.ensure((size_t)S * 4));
-    HIPCHK(c, hipMemcpyAsync(c->sP.p, rp, (size_t)R * 4, hipMemcpyHostToDevice, c->stream));
-    rc = launch_validate_pool(c, (const float *)c->sP.p, ho, S, T, K, seed, (float *)c->val_y.p, avg ? (float *)c->val_avg.p : nullptr);
+    rc = csr_check(c, ho, S);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(y, c->val_y.p, (size_t)T * S * 4, hipMemcpyDeviceToHost, c->stream));
-    if (avg) HIPCHK(c, hipMemcpyAsync(avg, c->val_avg.p, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_and_check(c);
+    if (dev) return launch_validate_pool(c, rp, ho, S, T, K, seed, y, avg);
+    HIPCHK(c, stage_in(c, c->sP, rp, (size_t)ho[S] * 4));
+    return validate_staged(c, ho, S, T, K, seed, nullptr, y, avg);
 }
 
 int m6a_validate(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *off, int64_t S, int T, int K,
                  uint32_t seed, float *rp, float *y, float *avg)
 {
-    settle(c);
     HintScope hint_scope(c);
-    if (c && c->job.open) return job_busy(c);
-    int rc = check_validate_args(c, S, T, K);
+    int rc = enter(c);
+    if (rc) return rc;
+    rc = check_validate_args(c, S, T, K);
     if (rc) return rc;
     if (S == 0) return M6A_OK;
     if (!X || !km || !off || !y) return fail(c, M6A_EINVAL, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = is_device_ptr(X);
-    if (dev != is_device_ptr(km) || dev != is_device_ptr(off) || dev != is_device_ptr(y) || (rp && dev != is_device_ptr(rp)) ||
-        (avg && dev != is_device_ptr(avg)))
-        return fail(c, M6A_EINVAL, "X, site_kmers, off and the outputs must be all host or all device pointers");
+    const int dev = same_side(c, X, {km, off, y, rp, avg}, "X, site_kmers, off and the outputs must be all host or all device pointers");
+    if (dev < 0) return dev;
     if (dev) {
         float *d_rp = rp;
         rc = bag_stats(c, off, S);
@@ -367,28 +369,18 @@ int m6a_validate(m6a_ctx *c, const float *X, const uint8_t *km, const int64_t *o
         return m6a_validate_pool(c, d_rp, off, S, T, K, seed, y, avg);
     }
     // host pointers: encode through the staging buffers, pool from the staged read probabilities
-    if (off[0] != 0) return fail(c, M6A_EINVAL, "off[0] must be 0");
-    for (int64_t s = 0; s < S; s++) if (off[s + 1] < off[s]) return fail(c, M6A_EINVAL, "off[] must be non-decreasing");
+    rc = csr_check(c, off, S);
+    if (rc) return rc;
     const int64_t R = off[S];
     if (R == 0) return fail(c, M6A_EINVAL, "no reads");
-    HIPCHK(c, c->sX.ensure((size_t)R * 9 * 4));
-    HIPCHK(c, c->sK.ensure((size_t)S * 3));
-    HIPCHK(c, c->sOff.ensure((size_t)(S + 1) * 8));
     HIPCHK(c, c->sP.ensure((size_t)R * 4));
-    HIPCHK(c, c->val_y.ensure((size_t)T * S * 4));
-    HIPCHK(c, c->val_avg.ensure((size_t)S * 4));
-    HIPCHK(c, hipMemcpyAsync(c->sX.p, X, (size_t)R * 9 * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->sK.p, km, (size_t)S * 3, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->sOff.p, off, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, stage_in(c, c->sX, X, (size_t)R * 9 * 4));
+    HIPCHK(c, stage_in(c, c->sK, km, (size_t)S * 3));
+    HIPCHK(c, stage_in(c, c->sOff, off, (size_t)(S + 1) * 8));
     host_bag_range(c, off, S);
     rc = launch_encode(c, (const float *)c->sX.p, (const uint8_t *)c->sK.p, (const int64_t *)c->sOff.p, S, R, (float *)c->sP.p);
     if (rc) return rc;
-    rc = launch_validate_pool(c, (const float *)c->sP.p, off, S, T, K, seed, (float *)c->val_y.p, avg ? (float *)c->val_avg.p : nullptr);
-    if (rc) return rc;
-    if (rp) HIPCHK(c, hipMemcpyAsync(rp, c->sP.p, (size_t)R * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(y, c->val_y.p, (size_t)T * S * 4, hipMemcpyDeviceToHost, c->stream));
-    if (avg) HIPCHK(c, hipMemcpyAsync(avg, c->val_avg.p, (size_t)S * 4, hipMemcpyDeviceToHost, c->stream));
-    return sync_and_check(c);
+    return validate_staged(c, off, S, T, K, seed, rp, y, avg);
 }
 
 

@@ -597,6 +597,52 @@ int m6a_prep_sites_fetch(m6a_prep_sites *p, float *read_prob, float *site_prob, 
 int m6a_prep_sites_inputs(m6a_prep_sites *p, float *X, uint8_t *site_kmers, int64_t *off);
 void m6a_prep_sites_free(m6a_prep_sites *p);
 
+/* Grouped input (`eventalign_inference --grouped`): nanopolish and f5c walk a coordinate-sorted BAM, so every transcript's lines come
+ * in one stretch, and every rule of the back half is per transcript.  m6a_prep_group delivers the sites of one file in batches, as
+ * transcripts complete, and what it keeps on the device follows the window and the group size, not the file.
+ *   grouped  Take the file's runs in file order, as m6a_prep_sites_build forms them (lines without a tab belong to no run).  The
+ *            input is grouped when no contig name heads a run after a run with a different contig has followed an earlier run of that
+ *            name.  Otherwise the offender is the first run in file order that breaks the rule, and the call that meets it returns
+ *            M6A_EFORMAT "<path>: transcript <name> appears again at byte <start of that run> after other transcripts: the input is
+ *            not grouped by transcript (run without --grouped)" -- the same at every window size and group size, a reappearance
+ *            inside one batch included: the host sees every segment's name and keeps the set of closed names.
+ *            tests/grouped_statement.py states the rule in plain Python.
+ *   promise  On grouped input the batches' arrays, one after the other, are m6a_prep_sites_build's on the same file, X bit for bit
+ *            (every batch numbers its transcripts itself: compare by name).  On any other input the error above; never other rows.
+ *   windows  The text is always parsed in windows: window_bytes > 0, else M6A_PREP_WINDOW_KB, else M6A_PREP_STREAM_WINDOW_BYTES, for
+ *            regular files too; a file, `-`, a FIFO.  BGZF content is M6A_EINVAL (windows over compressed input).
+ *   batches  After each window the kept runs in front of the last contig stretch -- the maximal tail of segments with one name,
+ *            compared by name since segments break at window edges -- are closed.  When the runs and rows of the closed part reach
+ *            group_bytes (<= 0: M6A_PREP_GROUP_KB, default M6A_PREP_GROUP_KB_DEFAULT; profiles/r30_grouped_input.json), or the input
+ *            ends, the back half's stages run on the closed part alone (declined runs through `host` as ever), and the closed runs and
+ *            rows leave the kept arrays.
+ *   flush    Every delivered batch but the last ends on a boundary m6a_flush_groups(n, batch_size, save_per_batch, ...) gives for a
+ *            longer job (the boundaries depend on the batch index alone), so m6a_set_job_offset(first_site) holds for every batch.
+ *            The sites behind the last such boundary -- fewer than one flush group -- stay on the device and head the next batch.  A
+ *            batch with no deliverable site is not delivered; parsing goes on.
+ *   errors   With one defect in the file, the code and text are m6a_prep_sites_build's.  With several, the one met first in batch
+ *            order is reported: a window's format error before the batch its runs would have joined, a batch's site error before
+ *            anything of a later window.  After an error every later call repeats it.
+ * m6a_prep_group_next: *batch is an ordinary m6a_prep_sites handle (m6a_prep_sites_get, _fetch, _inputs, the CSV writers and _free
+ * work on it as they are), NULL at the end.  Only one batch may be alive at a time: asking for the next with a live batch is
+ * M6A_EINVAL.  m6a_prep_group_info: n_sites, n_reads and first_site are the last batch's (first_site = the sites of all batches
+ * before it); max_kept_runs / max_kept_rows the high-water marks of the kept arrays; total_runs / total_rows what the back halves
+ * have taken so far; peak_bytes, d2h_bytes, n_windows, window_bytes, stream_bytes as m6a_prep_sites_info's, over the whole group. */
+#define M6A_PREP_GROUP_KB_DEFAULT ((int64_t)262144)
+typedef struct m6a_prep_group m6a_prep_group;
+typedef struct m6a_prep_group_counts {
+    int64_t n_batches, n_sites, n_reads, first_site;
+    int64_t max_kept_runs, max_kept_rows, total_runs, total_rows;
+    int64_t peak_bytes, d2h_bytes, n_windows, window_bytes, stream_bytes, group_bytes;
+} m6a_prep_group_counts;
+int m6a_prep_group_open(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
+                        const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                        const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, int64_t group_bytes, int64_t batch_size,
+                        int64_t save_per_batch, m6a_prep_group **out);
+int m6a_prep_group_next(m6a_prep_group *g, m6a_prep_sites **batch);
+int m6a_prep_group_info(const m6a_prep_group *g, m6a_prep_group_counts *counts);
+void m6a_prep_group_close(m6a_prep_group *g);
+
 /* `inference --loader device`: one directory of data.info + data.json -> the handle m6a_prep_sites_build returns, with the arrays
  * m6a_io_load_sites makes of that directory (include/m6a_io.h) -- X bit for bit -- and X, site_kmers and off left in HBM for m6a_infer.
  * Format: data.info is the loader's (a header line, then <transcript>,<position>,<start>,<end>,<n_reads>; rows with fewer than

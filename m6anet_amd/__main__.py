@@ -18,7 +18,7 @@ def main(argv=None):
     sub.add_parser("inference", parents=[inference.full_parser()], help="run the MI355X inference hot path")
     sub.add_parser("dataprep", parents=[dataprep.argparser()], help="eventalign.txt -> data.json / data.info (native, host-only)")
     sub.add_parser("pack", parents=[pack.argparser()], help="data.json / data.info -> one binary site store that later runs map")
-    sub.add_parser("eventalign_inference", parents=[eventalign_inference.full_parser()],
+    sub.add_parser("eventalign_inference", parents=[eventalign_inference.grouped_parser()],
                    help="eventalign.txt -> the two CSVs in one process, the features kept in HBM (= dataprep, then inference)")
     sub.add_parser("bgzip", parents=[bgzip.argparser()], help="FILE -> FILE.gz in BGZF, which eventalign_inference reads directly")
     sub.add_parser("train", parents=[train.argparser()], description=train.DESCRIPTION,

@@ -548,6 +548,86 @@ class prep_sites:
             pass
 
 
+class prep_sites_grouped:
+    """m6a_prep_group (libm6a_hip.so, include/m6a.h: grouped input): one eventalign file -- a path, `-`, a FIFO -- whose transcripts
+    each form one stretch, delivered as an iterator of prep_sites handles, batch after batch as transcripts complete; their arrays, one
+    after the other, are prep_sites(eventalign, ...)'s (every batch numbers its transcripts itself: compare through `names`).  The
+    text is always parsed in windows (window_kb, else M6A_PREP_WINDOW_KB, else 256 MB); a batch is taken when the closed runs and rows
+    reach group_kb (None: M6A_PREP_GROUP_KB, default 262144); every batch but the last ends on a flush boundary of (batch_size,
+    save_per_batch), and first_site -- the sites of the batches before the one at hand -- is what engine.set_job_offset takes.
+    Only one batch is alive at a time: the iterator closes the batch at hand before it asks for the next.  Input that is not grouped
+    raises M6AIOError (M6A_EFORMAT) with the statement's text when the offending run is met.  counts() is m6a_prep_group_counts."""
+    _CODES = prep_on_device._CODES
+
+    def __init__(self, eventalign, readcount_min=1, readcount_max=1000, min_segment_count=20, norm=None, n_threads=0, device_id=0,
+                 window_kb=None, group_kb=None, batch_size=16, save_per_batch=2):
+        from . import _lib
+        L, io = _lib.load(), load()
+        self._L, self._g, self._batch, self.first_site = L, C.c_void_p(), None, 0
+        blob, mean, std, n = norm_arrays(norm)
+        host = _lib.HostHalf(C.cast(io.m6a_io_runs_rows, C.c_void_p), C.cast(io.m6a_io_rows_table, C.c_void_p),
+                             C.cast(io.m6a_io_rows_free, C.c_void_p), C.cast(io.m6a_io_last_error, C.c_void_p))
+        rc = L.m6a_prep_group_open(int(device_id), os.fsencode(eventalign), int(readcount_min), int(readcount_max), int(min_segment_count), blob,
+                                   None if mean is None else mean.ctypes.data, None if std is None else std.ctypes.data, n, C.byref(host),
+                                   int(n_threads), -1 if not window_kb else int(window_kb) << 10, -1 if not group_kb else int(group_kb) << 10,
+                                   int(batch_size), int(save_per_batch), C.byref(self._g))
+        if rc != 0:
+            self._g = None
+            self._fail(rc)
+
+    def _fail(self, rc):
+        raise M6AIOError("m6a_prep error %d: %s" % (rc, self._L.m6a_prep_last_error().decode()), self._CODES.get(rc, rc))
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._batch is not None:
+            self._batch.close()
+            self._batch = None
+        if not self._g:
+            raise StopIteration
+        h = C.c_void_p()
+        rc = self._L.m6a_prep_group_next(self._g, C.byref(h))
+        if rc != 0:
+            self._fail(rc)
+        if not h:
+            raise StopIteration
+        p = prep_sites.__new__(prep_sites)
+        p._L, p._h = self._L, h
+        p._adopt()
+        self._batch, self.first_site = p, self.counts()["first_site"]
+        return p
+
+    def counts(self):
+        from . import _lib
+        c = _lib.PrepGroupCounts()
+        rc = self._L.m6a_prep_group_info(self._g, C.byref(c))
+        if rc != 0:
+            self._fail(rc)
+        return {k: int(getattr(c, k)) for k, _ in c._fields_}
+
+    def close(self):
+        if getattr(self, "_batch", None) is not None:
+            self._batch.close()
+            self._batch = None
+        if getattr(self, "_g", None):
+            self._L.m6a_prep_group_close(self._g)
+            self._g = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def json_sites(input_dir, min_reads=20, norm=None, n_threads=0, device=0):
     """m6a_json_sites_build (libm6a_hip.so): one directory of data.info + data.json -> the arrays NativeSites([input_dir], ...) holds,
     parsed by HIP kernels, with X, site_kmers and off left on the device -- a prep_sites, as prep_sites() returns for eventalign.txt

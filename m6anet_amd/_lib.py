@@ -20,6 +20,7 @@ SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
            "m6a_prep_sites_build", "m6a_prep_sites_build_multi", "m6a_prep_sites_build_windows", "m6a_prep_sites_build_names", "m6a_prep_sites_read_names", "m6a_prep_sites_intern_ms", "m6a_prep_sites_stream_bytes", "m6a_prep_sites_n_streams", "m6a_prep_sites_get", "m6a_prep_sites_fetch", "m6a_prep_sites_inputs", "m6a_prep_sites_free",
+           "m6a_prep_group_open", "m6a_prep_group_next", "m6a_prep_group_info", "m6a_prep_group_close",
            "m6a_csv_format", "m6a_prep_sites_write_csv", "m6a_bgzf_inflate", "m6a_bgzf_deflate", "m6a_prep_sites_write_csv_bgzf",
            "m6a_bgzf_deflate_level", "m6a_prep_sites_write_csv_bgzf_level", "m6a_prep_sites_write_read_representation", "m6a_json_sites_build", "m6a_norm_factors_build", "m6a_repr_format", "m6a_prep_dataprep_write",
            "m6a_train_create", "m6a_train_destroy", "m6a_train_step", "m6a_train_epoch", "m6a_train_sample", "m6a_train_grads", "m6a_train_weights", "m6a_train_stats",
@@ -61,6 +62,12 @@ class PrepSitesInfo(C.Structure):
                 ("n_windows", C.c_int64), ("window_bytes", C.c_int64),
                 ("n_bgzf_blocks", C.c_int64), ("compressed_bytes", C.c_int64), ("ms_inflate", C.c_double),
                 ("n_declined_sites", C.c_int64)]
+
+
+class PrepGroupCounts(C.Structure):
+    """m6a_prep_group_counts (include/m6a.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("n_batches", "n_sites", "n_reads", "first_site", "max_kept_runs", "max_kept_rows", "total_runs",
+                                         "total_rows", "peak_bytes", "d2h_bytes", "n_windows", "window_bytes", "stream_bytes", "group_bytes")]
 
 
 class BgzfStats(C.Structure):
@@ -240,6 +247,12 @@ def load():
     L.m6a_prep_sites_inputs.argtypes = [vp, vp, vp, vp]
     L.m6a_prep_sites_free.argtypes = [vp]
     L.m6a_prep_sites_free.restype = None
+    L.m6a_prep_group_open.argtypes = [i32, C.c_char_p, i32, i32, i32, C.c_char_p, vp, vp, i32, C.POINTER(HostHalf), i32, i64, i64, i64, i64,
+                                      C.POINTER(vp)]
+    L.m6a_prep_group_next.argtypes = [vp, C.POINTER(vp)]
+    L.m6a_prep_group_info.argtypes = [vp, C.POINTER(PrepGroupCounts)]
+    L.m6a_prep_group_close.argtypes = [vp]
+    L.m6a_prep_group_close.restype = None
     pl = C.POINTER(i64)
     L.m6a_csv_format.argtypes = [i32, C.POINTER(CsvArrays), i64, i64, vp, i64, vp, i64, pl, pl, pl]
     L.m6a_prep_sites_write_csv.argtypes = [vp, C.c_char_p, i32, i64, i32, C.POINTER(CsvStats)]

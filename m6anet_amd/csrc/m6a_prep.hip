@@ -19,6 +19,8 @@
 // With a window size (M6A_PREP_WINDOW_KB, m6a_prep_sites_build_windows) the same kernels run on one window of the file after the other
 // and only runs and rows stay on the device: front_windows, below, over a FileSource.  Text from a pipe (`-`, a FIFO) goes through the
 // same windows as it arrives, and what the back half would read again is saved from every window: the same loop over a StreamSource.
+// Input grouped by transcript (m6a_prep_group) stops that loop between two windows: the back half runs on the transcripts that are
+// complete, their runs and rows leave the device, and the sites come out in batches cut on flush boundaries.
 // Everything is built with -ffp-contract=off (build.py): no multiply-add is fused, and the f64 divisions are IEEE `/`.
 #include <hip/hip_runtime.h>
 
@@ -425,6 +427,56 @@ __global__ void keep_runs_kernel(const RunDev *__restrict__ runs, int64_t NR, in
     R.start += b; R.end += b; R.contig += b;
     kept[r] = R;
     row_cnt[r] = row_off[r + 1] - row_off[r];
+}
+
+// ---- grouped input (m6a_prep_group, include/m6a.h): what is kept of the windows is cut between two of them ------------------------
+// The closed prefix: one lane per segment of the kept runs (seg_first: its first run; seg_rank: its contig's number in order of first
+// appearance, which the host interned from the segment's name).  The last contig stretch is the tail of segments that carry the last
+// segment's rank, so the kept runs in front of it end at the first run of the highest segment g whose predecessor has another rank --
+// a maximum over the segment heads, 0 where the kept runs are one stretch.
+__global__ void closed_prefix_kernel(const int64_t *__restrict__ seg_first, const uint32_t *__restrict__ seg_rank, int64_t NSEG,
+                                     unsigned long long *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    unsigned long long v = 0;
+    if (g >= 1 && g < NSEG && seg_rank[g - 1] != seg_rank[NSEG - 1]) v = (unsigned long long)seg_first[g];
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long a = __shfl_xor(v, o);
+        v = a > v ? a : v;
+    }
+    if ((threadIdx.x & 63) == 0 && v) atomicMax(out, v);
+}
+
+// the candidate rows of the kept runs [0, n): the sum of their row counts
+__global__ void rows_before_kernel(const int64_t *__restrict__ cnt, int64_t n, unsigned long long *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    unsigned long long v = r < n ? (unsigned long long)cnt[r] : 0;
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
+}
+
+// The removal of the closed runs and rows: what stays of a kept array, its bytes from the first open run or row on, moves to the start
+// of a new array (8 bytes a lane where the source allows it, the ragged end and the 7-byte k-mers byte by byte) and the old one is
+// released.  The kept arrays hold file offsets and row counts, not offsets into each other, so nothing in them is rebased: the run
+// numbers of the segments the host keeps are, there.
+__global__ void keep_tail_kernel(const uint8_t *__restrict__ src, int64_t n, uint8_t *__restrict__ dst)
+{
+    const int64_t at = ((int64_t)blockIdx.x * kBlk + threadIdx.x) * 8;
+    if (at >= n) return;
+    if (((uintptr_t)src & 7) == 0 && at + 8 <= n) *(uint64_t *)(dst + at) = *(const uint64_t *)(src + at);
+    else
+        for (int k = 0; k < 8 && at + k < n; k++) dst[at + k] = src[at + k];
+}
+
+// The carried sites in front of a batch's: element j of the new array is element from + j of a's na elements followed by b's
+template <class T>
+__global__ void splice_kernel(const T *__restrict__ a, int64_t na, const T *__restrict__ b, int64_t from, int64_t n, T *__restrict__ dst)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (j >= n) return;
+    const int64_t i = from + j;
+    dst[j] = i < na ? a[i] : b[i - na];
 }
 
 // ---- a stream's windows: what the back half will ask for is saved while the window's text is there -------------------------------
@@ -1054,16 +1106,25 @@ struct StreamSource : Source {
     }
 };
 
-int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
-{
-    DevMem &m = C.m;
-    hipStream_t s = C.S.s[0];
-    int rc;
-    // window 0 arrives before anything can run; from then on window k + 1 arrives under window k's combine and windows
-    if ((rc = src.first(C.text[0]))) return rc;
+// The window loop, one window a step, so that a caller can stop between two windows (m6a_prep_group takes a batch there); front_windows
+// runs it to the end.
+struct WindowLoop {
+    Windows &C;
+    Source &src;
+    const int w;
+    const bool read_names;
     Kept kept;
-    int64_t b = 0, n_windows = 0, w_max = 0;
-    for (int64_t k = 0;; k++) {
+    int64_t b = 0, k = 0, n_windows = 0, w_max = 0;
+    bool done = false;                      // the last window has been kept
+    double ahead_fixed = 0;                 // > 0: Kept::append's projection, where the kept arrays do not grow with the file (m6a_prep_group)
+    WindowLoop(Windows &c, Source &s, int w_, bool names) : C(c), src(s), w(w_), read_names(names) {}
+    // window 0 arrives before anything can run; from then on window k + 1 arrives under window k's combine and windows
+    int start() { return src.first(C.text[0]); }
+    int step(double *ms)
+    {
+        DevMem &m = C.m;
+        hipStream_t s = C.S.s[0];
+        int rc;
         Text &T = C.text[k & 1], &T2 = C.text[(k + 1) & 1];
         Upload up;                                           // of window k + 1
         bool started = false;
@@ -1072,7 +1133,7 @@ int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
         for (;;) {                                           // until the arena holds the window and the window holds a cut
             V = Win();
             V.df = T.p; V.b = b; V.first = b == 0 ? 1 : 0;
-            V.read_names = F.read_names;
+            V.read_names = read_names;
             src.extent(V, Wk);
             C.arena.off = 0;
             m.arena = &C.arena;
@@ -1104,7 +1165,7 @@ int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
                 continue;
             }
             const double t1 = now_ms();
-            if ((rc = kept.append(m, s, V, w, src.ahead(V), pos_off, ps, row_off, nrow, src.saves() ? &sv : nullptr))) return rc;
+            if ((rc = kept.append(m, s, V, w, ahead_fixed > 0 ? ahead_fixed : src.ahead(V), pos_off, ps, row_off, nrow, src.saves() ? &sv : nullptr))) return rc;
             ms[2] += now_ms() - t1;
             break;
         }
@@ -1116,11 +1177,24 @@ int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
             C.wait_ms += now_ms() - t0; C.copy_ms += up.ms; C.copied += (double)up.got;
             if (up.rc) { g_prep_err = up.err; return up.rc; }
         }
-        if (V.last) break;
+        if (V.last) { done = true; return M6A_OK; }
         b = V.next;
         src.advance(up);
+        ++k;
+        return M6A_OK;
     }
-    if ((rc = src.finish(b, F))) return rc;
+};
+
+int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
+{
+    DevMem &m = C.m;
+    hipStream_t s = C.S.s[0];
+    WindowLoop L(C, src, w, F.read_names);
+    Kept &kept = L.kept;
+    int rc = L.start();
+    while (!rc && !L.done) rc = L.step(ms);
+    if (rc) return rc;
+    if ((rc = src.finish(L.b, F))) return rc;
     // the scratch goes before the back half: X needs the room
     for (Text &T : C.text)
         if (T.p) m.release(T.p);
@@ -1133,7 +1207,7 @@ int front_windows(Windows &C, Source &src, int w, Front &F, double *ms)
     ms[2] += now_ms() - t1;
     ms[0] = C.wait_ms;
     ms[5] = C.copy_ms > 0 ? C.copied / (C.copy_ms * 1e6) : 0;
-    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = n_windows; F.window_bytes = w_max;
+    F.NR = kept.NR; F.NROW = kept.NROW; F.n_windows = L.n_windows; F.window_bytes = L.w_max;
     F.runs = (RunDev *)kept.runs.p; F.row_off = (int64_t *)kept.cnt.p; F.rnames = (Name *)kept.names.p;
     F.row_pos = (int64_t *)kept.pos.p; F.row_kmer = kept.kmer.p; F.row_feat = (double *)kept.feat.p;
     F.heads = kept.heads.p; F.n_heads = (int64_t)kept.heads.used;
@@ -1831,7 +1905,14 @@ struct m6a_prep_sites {
     const int64_t *csv_name_off = nullptr;   // [n_rep + 1]
     double ms_intern = 0;
     int64_t stream_bytes = 0, n_streams = 0; // bytes read from streams, and how many of the files were streams
-    ~m6a_prep_sites() { for (void *p : dev) (void)hipFree(p); }
+    // a batch of m6a_prep_group: the group counts the handle's device bytes against its budget until the handle is freed
+    void (*on_free)(void *owner, size_t bytes) = nullptr;
+    void *owner = nullptr;
+    ~m6a_prep_sites()
+    {
+        for (void *p : dev) (void)hipFree(p);
+        if (on_free) on_free(owner, held);
+    }
 };
 
 namespace {
@@ -2089,11 +2170,12 @@ int host_half_rows(Back &B)
 }
 
 // ---- the host: transcript names, ranks, the readcount verdict, declined runs
-int host_part(Back &B)
+// (saved_stay: the saved bytes are the caller's -- a batch of m6a_prep_group, whose later batches read on in them)
+int host_part(Back &B, bool saved_stay = false)
 {
     int rc;
     if ((rc = name_segments(B)) || (rc = host_half_rows(B))) return rc;
-    B.m.release({B.F.text, B.F.heads, B.F.declined});       // names and declined runs are on the host: X needs the room
+    if (!saved_stay) B.m.release({B.F.text, B.F.heads, B.F.declined});       // names and declined runs are on the host: X needs the room
     B.NH = (int64_t)B.hpos.size();
     if (B.NROW + B.NH > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 candidate rows");
     return M6A_OK;
@@ -2749,6 +2831,453 @@ int sites_multi(int device_id, const char *const *paths, int n_paths, int rmin, 
 }
 
 }  // namespace
+
+// ---- grouped input (m6a_prep_group, include/m6a.h): sites as transcripts complete ---------------------------------------------------------
+// The window loop stops between two windows.  After every window the host sees the names of the new segments (group_absorb: the
+// grouped rule, the closed names) and the device says where the last contig stretch begins (group_closed); once the closed runs and
+// rows reach the group size, the back half's stages run on them alone (group_batch), the closed part leaves the kept arrays
+// (keep_tail) and the batch is cut on a flush boundary, the sites behind it carried in front of the next batch's (splice_sites).
+namespace {
+struct GroupSeg { int64_t first; int32_t len; uint32_t name; };    // a segment of the kept runs: its first run, the length and the number of its name
+}
+
+struct m6a_prep_group {
+    int device = 0;
+    std::string path, norm_kmers;
+    std::vector<double> norm_mean, norm_std;
+    int rmin = 0, rmax = 0, min_seg = 0, n_norm = 0, n_threads = 0;
+    m6a_prep_host_half host{};
+    bool has_host = false, stream = false, ended = false;
+    int64_t group_bytes = 0, bs = 0, spb = 0;
+    int failed = 0;                         // an error ends the group: every later call repeats it
+    std::string failed_text;
+    DevMem m;
+    Streams S;
+    Fd fd;
+    std::unique_ptr<Windows> C;
+    std::unique_ptr<Source> src;
+    std::unique_ptr<WindowLoop> L;
+    double fms[6] = {0, 0, 0, 0, 0, 0};
+    std::string name_blob;                  // every contig name met so far, and whether another name has followed it
+    std::vector<int64_t> name_off;
+    Interner names{name_blob, name_off};
+    std::vector<uint8_t> closed;
+    int64_t cur = -1;
+    std::vector<GroupSeg> segs;             // of the kept runs
+    int64_t heads_seen = 0;                 // a stream: the saved contig bytes in front of this offset have been named
+    int64_t closed_runs = 0, closed_rows = 0;
+    m6a_prep_sites *carry = nullptr, *live = nullptr;
+    int64_t written = 0;
+    m6a_prep_group_counts n{};
+    ~m6a_prep_group()
+    {
+        if (live) live->on_free = nullptr;
+        delete carry;
+        L.reset();
+        src.reset();
+        C.reset();
+    }
+};
+
+namespace {
+
+void group_batch_freed(void *owner, size_t bytes)
+{
+    m6a_prep_group *G = (m6a_prep_group *)owner;
+    G->m.used -= std::min(bytes, G->m.used);
+    G->live = nullptr;
+}
+
+// a handle the group made and no caller has seen
+void group_drop(m6a_prep_group &G, m6a_prep_sites *&p)
+{
+    if (!p) return;
+    G.m.used -= std::min(p->held, G.m.used);
+    delete p;
+    p = nullptr;
+}
+
+int group_open(m6a_prep_group &G, int64_t window)
+{
+    g_d2h = 0;
+    G.m.advice = "run `dataprep` and then `inference` instead (the two-step path), or give a smaller --window_mb or M6A_PREP_GROUP_KB";
+    int rc = open_device(G.device, G.m, nullptr);
+    if (rc) return rc;
+    const char *path = G.path.c_str();
+    if (is_stdin(path)) { G.fd.fd = 0; G.fd.own = false; }
+    else G.fd.fd = ::open(path, O_RDONLY);
+    if (G.fd.fd < 0) return prep_fail(M6A_EIO, "cannot open %s", path);
+    struct stat st;
+    if (fstat(G.fd.fd, &st) != 0) return prep_fail(M6A_EIO, "cannot stat %s", path);
+    G.stream = !S_ISREG(st.st_mode);
+    const int64_t n = G.stream ? 0 : (int64_t)st.st_size;
+    if (!G.stream && bgzf_is_gzip(G.fd.fd, n))
+        return prep_fail(M6A_EINVAL, "%s: windows over compressed input are not implemented (--window_mb, M6A_PREP_WINDOW_KB); a BGZF file "
+                         "must fit resident: run it without a window", path);
+    if (window <= 0) window = window_from_env();
+    if (window <= 0) window = M6A_PREP_STREAM_WINDOW_BYTES;
+    const int64_t W = (window + kScanBytes - 1) / kScanBytes * kScanBytes;
+    int64_t chunk = 0;
+    if ((rc = G.S.open(W, chunk))) return rc;
+    G.C.reset(new Windows(G.device, path, W, chunk, G.m, G.S));
+    if (G.stream) G.src.reset(new StreamSource(*G.C, G.fd.fd));
+    else G.src.reset(new FileSource(*G.C, G.fd.fd, n));
+    G.L.reset(new WindowLoop(*G.C, *G.src, 1, false));
+    G.L->ahead_fixed = 2.0;                                  // what is kept follows the group size, not the file's
+    rc = G.L->start();
+    G.n.d2h_bytes += g_d2h;
+    return rc;
+}
+
+// the segments of the kept runs [NR0, NR): their names to the host, the grouped rule, the closed names
+int group_absorb(m6a_prep_group &G, int64_t NR0)
+{
+    Kept &K = G.L->kept;
+    DevMem &m = G.m;
+    hipStream_t s = G.S.s[0];
+    const int64_t n = K.NR - NR0;
+    if (n <= 0) return M6A_OK;
+    const RunDev *runs = (const RunDev *)K.runs.p + NR0;
+    int rc;
+    int64_t *sx, *dx, NSEG = 0, ND = 0;
+    SegDev *seg;
+    DeclDev *decl;
+    if ((rc = m.alloc(sx, (size_t)n + 1, "segments")) || (rc = m.alloc(dx, (size_t)n + 1, "declined runs"))) return rc;
+    if ((rc = launch(run_flags_kernel, n, s, runs, n, sx, dx))) return rc;
+    if ((rc = scan_total(m, sx, n, s, NSEG)) || (rc = scan_total(m, dx, n, s, ND))) return rc;
+    if ((rc = m.alloc(seg, (size_t)NSEG + 1, "segments")) || (rc = m.alloc(decl, (size_t)ND + 1, "declined runs"))) return rc;
+    if ((rc = launch(run_lists_kernel, n, s, runs, n, sx, dx, seg, decl))) return rc;
+    std::vector<SegDev> hseg((size_t)NSEG);
+    if ((rc = d2h(hseg.data(), seg, (size_t)NSEG, s))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    m.release({sx, dx, seg, decl});
+    int64_t total = 0;
+    for (const SegDev &g : hseg) total += g.len;
+    std::vector<char> bytes((size_t)total + 1);
+    if (G.stream) {                                          // saved in run order: the new segments' names lie end to end
+        if (G.heads_seen + total > (int64_t)K.heads.used) return prep_fail(M6A_EHIP, "the saved contig names of %s do not add up", G.path.c_str());
+        if ((rc = d2h((uint8_t *)bytes.data(), K.heads.p + G.heads_seen, (size_t)total, s))) return rc;
+        PCHK(hipStreamSynchronize(s));
+        G.heads_seen += total;
+    }
+    std::string nm;
+    int64_t at = 0;
+    for (const SegDev &g : hseg) {
+        if (G.stream) nm.assign(bytes.data() + at, (size_t)g.len);
+        else {
+            nm.resize((size_t)g.len);
+            if ((rc = read_fully(G.fd.fd, &nm[0], g.len, g.contig, G.path.c_str()))) return rc;
+        }
+        at += g.len;
+        const uint32_t id = G.names.id(nm);
+        if (id == G.closed.size()) G.closed.push_back(0);
+        if ((int64_t)id != G.cur) {
+            if (G.cur >= 0) G.closed[(size_t)G.cur] = 1;
+            if (G.closed[id])
+                return prep_fail(M6A_EFORMAT, "%s: transcript %.*s appears again at byte %lld after other transcripts: the input is not grouped by "
+                                 "transcript (run without --grouped)", G.path.c_str(), (int)std::min<size_t>(nm.size(), 256), nm.c_str(), (long long)g.contig);
+            G.cur = id;
+        }
+        G.segs.push_back(GroupSeg{NR0 + g.first, g.len, id});
+    }
+    return M6A_OK;
+}
+
+// where the last contig stretch of the kept runs begins, and the rows in front of it
+int group_closed(m6a_prep_group &G)
+{
+    Kept &K = G.L->kept;
+    DevMem &m = G.m;
+    hipStream_t s = G.S.s[0];
+    const int64_t NSEG = (int64_t)G.segs.size();
+    G.closed_runs = G.closed_rows = 0;
+    if (NSEG < 2) return M6A_OK;
+    std::vector<int64_t> first((size_t)NSEG);
+    std::vector<uint32_t> rank((size_t)NSEG);
+    for (int64_t g = 0; g < NSEG; g++) { first[(size_t)g] = G.segs[(size_t)g].first; rank[(size_t)g] = G.segs[(size_t)g].name; }
+    int rc;
+    int64_t *dfirst;
+    uint32_t *drank;
+    unsigned long long *out, h[2] = {0, 0};
+    if ((rc = m.alloc(dfirst, (size_t)NSEG, "segments")) || (rc = m.alloc(drank, (size_t)NSEG, "segments")) || (rc = m.alloc(out, 2, "flags"))) return rc;
+    if ((rc = h2d(dfirst, first.data(), (size_t)NSEG, s)) || (rc = h2d(drank, rank.data(), (size_t)NSEG, s))) return rc;
+    PCHK(hipMemsetAsync(out, 0, 2 * sizeof(unsigned long long), s));
+    if ((rc = launch(closed_prefix_kernel, NSEG, s, dfirst, drank, NSEG, out)) || (rc = fetch(h[0], out, s))) return rc;   // first and rank may go now
+    const int64_t upto = (int64_t)h[0];
+    if (upto < 0 || upto > K.NR) return prep_fail(M6A_EHIP, "the closed runs of %s do not add up", G.path.c_str());
+    if ((rc = launch(rows_before_kernel, upto, s, (const int64_t *)K.cnt.p, upto, out + 1)) || (rc = fetch(h[1], out + 1, s))) return rc;
+    m.release({dfirst, drank, out});
+    if ((int64_t)h[1] > K.NROW) return prep_fail(M6A_EHIP, "the closed rows of %s do not add up", G.path.c_str());
+    G.closed_runs = upto;
+    G.closed_rows = (int64_t)h[1];
+    return M6A_OK;
+}
+
+// what stays of a kept array when its first `from` bytes leave
+int keep_tail(DevMem &m, hipStream_t s, DevVec &v, size_t from, const char *what)
+{
+    if (!v.p) return M6A_OK;
+    if (from > v.used) return prep_fail(M6A_EHIP, "the kept %s do not add up", what);
+    const size_t tail = v.used - from;
+    uint8_t *q = nullptr;
+    int rc = m.alloc(q, tail, what);
+    if (rc) return rc;
+    if ((rc = launch(keep_tail_kernel, (int64_t)((tail + 7) / 8), s, (const uint8_t *)v.p + from, (int64_t)tail, q))) return rc;
+    PCHK(hipStreamSynchronize(s));
+    m.release(v.p);
+    v.p = q;
+    v.cap = std::max<size_t>(16, tail);
+    v.used = tail;
+    return M6A_OK;
+}
+
+// sites [from, to) of A's followed by B's (either may be null) as a handle of their own: the carried sites go in front of a batch's
+int splice_sites(m6a_prep_group &G, const m6a_prep_sites *A, const m6a_prep_sites *B, int64_t from, int64_t to, m6a_prep_sites *&out)
+{
+    DevMem &m = G.m;
+    hipStream_t s = G.S.s[0];
+    const int64_t NA = A ? A->info.n_sites : 0, RA = A ? A->info.n_reads : 0, NB = B ? B->info.n_sites : 0;
+    if (from < 0 || to < from || to > NA + NB) return prep_fail(M6A_EHIP, "sites [%lld, %lld) of %lld", (long long)from, (long long)to, (long long)(NA + NB));
+    auto reads_before = [&](int64_t i) { return i < NA ? A->off[(size_t)i] : RA + (B ? B->off[(size_t)(i - NA)] : 0); };
+    const int64_t n = to - from, r0 = reads_before(from), R = reads_before(to) - r0;
+    std::unique_ptr<m6a_prep_sites> P(new m6a_prep_sites);
+    P->device = G.device;
+    P->off.resize((size_t)n + 1); P->tx.resize((size_t)n); P->pos.resize((size_t)n); P->k7.resize((size_t)n * 7); P->ids.resize((size_t)R);
+    Interner tx(P->blob, P->tx_off);
+    std::vector<int64_t> map_a(A ? (size_t)A->info.n_tx : 0, -1), map_b(B ? (size_t)B->info.n_tx : 0, -1);
+    for (int64_t j = 0; j < n; j++) {
+        const int64_t i = from + j, k = i < NA ? i : i - NA;
+        const m6a_prep_sites &Q = i < NA ? *A : *B;
+        std::vector<int64_t> &map = i < NA ? map_a : map_b;
+        const uint32_t t = Q.tx[(size_t)k];
+        if (map[t] < 0) map[t] = tx.id(std::string(Q.blob.data() + Q.tx_off[t], (size_t)(Q.tx_off[t + 1] - Q.tx_off[t])));
+        P->tx[(size_t)j] = (uint32_t)map[t];
+        P->pos[(size_t)j] = Q.pos[(size_t)k];
+        memcpy(P->k7.data() + j * 7, Q.k7.data() + k * 7, 7);
+        P->off[(size_t)j] = reads_before(i) - r0;
+    }
+    P->off[(size_t)n] = R;
+    P->tx_off.push_back((int64_t)P->blob.size());
+    for (int64_t r = 0; r < R; r++) P->ids[(size_t)r] = r0 + r < RA ? A->ids[(size_t)(r0 + r)] : B->ids[(size_t)(r0 + r - RA)];
+    P->rep.assign((size_t)R, 0);
+    int rc;
+    uint32_t *X, *stx;
+    uint8_t *kmers, *sk7;
+    int64_t *off, *spos;
+    uint64_t *ids;
+    float *rp, *sp;
+    double *mr;
+    if ((rc = m.alloc(X, (size_t)R * 9, "X")) || (rc = m.alloc(ids, (size_t)R + 1, "read ids")) || (rc = m.alloc(kmers, (size_t)n * 3 + 1, "site k-mers")) ||
+        (rc = m.alloc(off, (size_t)n + 1, "the offsets")) || (rc = m.alloc(stx, (size_t)n + 1, "sites")) || (rc = m.alloc(spos, (size_t)n + 1, "sites")) ||
+        (rc = m.alloc(sk7, (size_t)n * 7 + 1, "sites")) || (rc = m.alloc(rp, (size_t)R, "read probabilities")) ||
+        (rc = m.alloc(sp, (size_t)n, "site probabilities")) || (rc = m.alloc(mr, (size_t)n, "mod ratios")))
+        return rc;
+    const m6a_prep_sites_info *IA = A ? &A->info : nullptr, *IB = B ? &B->info : nullptr;
+    if ((rc = launch(splice_kernel<uint32_t>, R * 9, s, (const uint32_t *)(IA ? IA->X : nullptr), RA * 9, (const uint32_t *)(IB ? IB->X : nullptr), r0 * 9,
+                     R * 9, X)) ||
+        (rc = launch(splice_kernel<uint64_t>, R, s, (const uint64_t *)(A ? A->csv_ids : nullptr), RA, (const uint64_t *)(B ? B->csv_ids : nullptr), r0, R, ids)) ||
+        (rc = launch(splice_kernel<uint8_t>, n * 3, s, IA ? IA->site_kmers : nullptr, NA * 3, IB ? IB->site_kmers : nullptr, from * 3, n * 3, kmers)) ||
+        (rc = launch(splice_kernel<uint8_t>, n * 7, s, A ? A->csv_k7 : nullptr, NA * 7, B ? B->csv_k7 : nullptr, from * 7, n * 7, sk7)) ||
+        (rc = launch(splice_kernel<int64_t>, n, s, A ? A->csv_pos : nullptr, NA, B ? B->csv_pos : nullptr, from, n, spos)) ||
+        (rc = h2d(off, P->off.data(), (size_t)n + 1, s)) || (rc = h2d(stx, P->tx.data(), (size_t)n, s)))
+        return rc;
+    PCHK(hipStreamSynchronize(s));
+    publish(*P, m, Result{n, R, (int64_t)tx.ids.size(), 1, (float *)X, kmers, off, rp, sp, mr, stx, spos, sk7, (const double *)ids, nullptr, nullptr, nullptr});
+    out = P.release();
+    return M6A_OK;
+}
+
+// The back half on the kept runs [0, NRc) alone, their removal, and the cut of the batch on a flush boundary.  *out stays null where no
+// site can be delivered yet.
+int group_batch(m6a_prep_group &G, int64_t NRc, bool final, m6a_prep_sites **out)
+{
+    Kept &K = G.L->kept;
+    DevMem &m = G.m;
+    hipStream_t s = G.S.s[0];
+    int rc;
+    m6a_prep_sites *raw = nullptr;
+    struct Drop { m6a_prep_group &G; m6a_prep_sites *&p; ~Drop() { group_drop(G, p); } } drop_raw{G, raw};
+    if (NRc > 0) {
+        if (NRc > 0xffffffffll) return prep_fail(M6A_EINVAL, "more than 2^32 runs");
+        const double t_all = now_ms();
+        raw = new m6a_prep_sites;
+        raw->device = G.device;
+        const size_t mark = m.ptrs.size();
+        int64_t rows = 0, heads_c = 0, decl_c = 0;
+        {
+            Back B(G.path.c_str(), G.rmin, G.rmax, G.has_host ? &G.host : nullptr, G.n_threads, *raw, m);
+            B.fd.fd = G.fd.fd; B.fd.own = false;
+            B.s = s;
+            Front &F = B.F;
+            int64_t *row_off;
+            if ((rc = m.alloc(row_off, (size_t)NRc + 1, "rows"))) return rc;
+            PCHK(hipMemcpyAsync(row_off, K.cnt.p, (size_t)NRc * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+            if ((rc = scan_total(m, row_off, NRc, s, rows))) return rc;
+            for (const GroupSeg &g : G.segs)
+                if (g.first < NRc) heads_c += g.len;
+            if (rows > K.NROW || (G.stream && heads_c > (int64_t)K.heads.used)) return prep_fail(M6A_EHIP, "the closed rows of %s do not add up", G.path.c_str());
+            F.NR = NRc; F.NROW = rows;
+            F.runs = (RunDev *)K.runs.p; F.row_off = row_off;
+            F.row_pos = (int64_t *)K.pos.p; F.row_kmer = K.kmer.p; F.row_feat = (double *)K.feat.p;
+            F.stream = G.stream;
+            F.heads = K.heads.p; F.n_heads = heads_c;
+            F.declined = K.declined.p;
+            B.NR = NRc; B.NROW = rows;
+            B.t1 = now_ms();
+            if ((rc = segments_to_host(B))) return rc;
+            for (const DeclDev &d : B.hdecl) decl_c += d.end - d.start;
+            if (G.stream && decl_c > (int64_t)K.declined.used) return prep_fail(M6A_EHIP, "the saved declined runs of %s do not add up", G.path.c_str());
+            F.n_declined = decl_c;
+            B.dev_ms += now_ms() - B.t1;
+            B.t1 = now_ms();
+            if ((rc = host_part(B, true))) return rc;
+            B.host_ms += now_ms() - B.t1;
+            B.t1 = now_ms();
+            if ((rc = place_runs(B)) || (rc = sort_rows(B)) || (rc = cut_sites(B, std::max<int64_t>(G.min_seg, 20)))) return rc;
+            if ((rc = finish_single(B, G.n_norm ? G.norm_kmers.data() : nullptr, G.n_norm ? G.norm_mean.data() : nullptr,
+                                    G.n_norm ? G.norm_std.data() : nullptr, G.n_norm, raw->info.ms)))
+                return rc;
+            raw->info.ms[3] = B.dev_ms; raw->info.ms[4] = B.host_ms; raw->info.ms[7] = now_ms() - t_all;
+        }
+        PCHK(hipStreamSynchronize(s));
+        m.release_since(mark, {});                           // the batch's own arrays are the handle's already
+        // ---- the closed runs and rows leave the kept arrays
+        if ((rc = keep_tail(m, s, K.runs, (size_t)NRc * sizeof(RunDev), "runs")) || (rc = keep_tail(m, s, K.cnt, (size_t)NRc * 8, "rows")) ||
+            (rc = keep_tail(m, s, K.pos, (size_t)rows * 8, "rows")) || (rc = keep_tail(m, s, K.kmer, (size_t)rows * 7, "rows")) ||
+            (rc = keep_tail(m, s, K.feat, (size_t)rows * 72, "rows")) || (rc = keep_tail(m, s, K.heads, (size_t)heads_c, "saved names")) ||
+            (rc = keep_tail(m, s, K.declined, (size_t)decl_c, "saved runs")))
+            return rc;
+        K.NR -= NRc; K.NROW -= rows;
+        size_t at = 0;
+        for (const GroupSeg &g : G.segs)
+            if (g.first >= NRc) { G.segs[at] = g; G.segs[at++].first -= NRc; }
+        G.segs.resize(at);
+        G.heads_seen -= heads_c;
+        G.closed_runs = G.closed_rows = 0;
+        G.n.total_runs += NRc; G.n.total_rows += rows;
+    }
+    // ---- the cut: every batch but the last ends on a flush boundary of the job, and what lies behind it heads the next
+    const int64_t NC = G.carry ? G.carry->info.n_sites : 0, T = NC + (raw ? raw->info.n_sites : 0);
+    int64_t cut = T;
+    if (!final) {
+        int64_t k = (G.written + T) / G.bs;
+        while (k > 0 && k % G.spb == 0) --k;
+        cut = std::max<int64_t>(k * G.bs - G.written, 0);
+    }
+    m6a_prep_sites *batch = nullptr, *rest = nullptr;
+    if (cut == T && !NC) { batch = raw; raw = nullptr; }
+    else if (cut == 0 && !NC) { rest = raw; raw = nullptr; }
+    else {
+        if (cut > 0 && (rc = splice_sites(G, G.carry, raw, 0, cut, batch))) return rc;
+        if (cut < T && (rc = splice_sites(G, G.carry, raw, cut, T, rest))) { group_drop(G, batch); return rc; }
+    }
+    group_drop(G, G.carry);
+    G.carry = rest;
+    if (batch && batch->info.n_sites == 0) group_drop(G, batch);
+    if (!batch) return M6A_OK;
+    m6a_prep_sites_info &I = batch->info;
+    I.n_windows = G.L->n_windows; I.window_bytes = G.L->w_max;
+    I.peak_bytes = (int64_t)m.peak;
+    I.d2h_bytes = G.n.d2h_bytes + g_d2h;
+    batch->stream_bytes = G.n.stream_bytes; batch->n_streams = G.stream ? 1 : 0;
+    batch->on_free = group_batch_freed;
+    batch->owner = &G;
+    G.live = batch;
+    G.n.n_batches += 1; G.n.n_sites = I.n_sites; G.n.n_reads = I.n_reads; G.n.first_site = G.written;
+    G.written += I.n_sites;
+    *out = batch;
+    return M6A_OK;
+}
+
+int group_next(m6a_prep_group &G, m6a_prep_sites **batch)
+{
+    g_d2h = 0;
+    PCHK(hipSetDevice(G.device));
+    Kept &K = G.L->kept;
+    int rc = M6A_OK;
+    for (;;) {
+        const bool final = G.L->done;
+        const int64_t bytes = G.closed_runs * (int64_t)(sizeof(RunDev) + 8) + G.closed_rows * (8 + 7 + 72);
+        if (final || (G.closed_runs > 0 && bytes >= G.group_bytes)) {
+            if ((rc = group_batch(G, final ? K.NR : G.closed_runs, final, batch))) break;
+            if (final) G.ended = true;
+            if (*batch || final) break;
+            continue;
+        }
+        const int64_t NR0 = K.NR;
+        if ((rc = G.L->step(G.fms))) break;
+        G.n.n_windows = G.L->n_windows; G.n.window_bytes = G.L->w_max;
+        G.n.max_kept_runs = std::max(G.n.max_kept_runs, K.NR); G.n.max_kept_rows = std::max(G.n.max_kept_rows, K.NROW);
+        if ((rc = group_absorb(G, NR0))) break;
+        if (G.L->done) {
+            Front F;
+            if ((rc = G.src->finish(G.L->b, F))) break;
+            G.n.stream_bytes = F.stream ? F.n : 0;
+        } else if ((rc = group_closed(G)))
+            break;
+    }
+    G.n.d2h_bytes += g_d2h;
+    G.n.peak_bytes = (int64_t)G.m.peak;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int m6a_prep_group_open(int device_id, const char *path, int readcount_min, int readcount_max, int min_segment_count,
+                                   const char *norm_kmers, const double *norm_mean, const double *norm_std, int n_norm,
+                                   const m6a_prep_host_half *host, int n_threads, int64_t window_bytes, int64_t group_bytes, int64_t batch_size,
+                                   int64_t save_per_batch, m6a_prep_group **out)
+{
+    if (!path || !out) return prep_fail(M6A_EINVAL, "null argument");
+    *out = nullptr;
+    if (n_norm < 0 || (n_norm > 0 && (!norm_kmers || !norm_mean || !norm_std))) return prep_fail(M6A_EINVAL, "bad normalisation arguments");
+    if (batch_size < 1 || save_per_batch < 1) return prep_fail(M6A_EINVAL, "batch_size and save_per_batch must be 1 or more");
+    return guarded([&]() -> int {
+        std::unique_ptr<m6a_prep_group> G(new m6a_prep_group);
+        G->device = device_id;
+        G->path = path;
+        G->rmin = readcount_min; G->rmax = readcount_max; G->min_seg = min_segment_count;
+        G->n_norm = n_norm;
+        if (n_norm) {
+            G->norm_kmers.assign(norm_kmers, (size_t)n_norm * 5);
+            G->norm_mean.assign(norm_mean, norm_mean + (size_t)n_norm * 3);
+            G->norm_std.assign(norm_std, norm_std + (size_t)n_norm * 3);
+        }
+        if (host) { G->host = *host; G->has_host = true; }
+        G->n_threads = n_threads;
+        G->bs = batch_size; G->spb = save_per_batch;
+        if (group_bytes <= 0) {
+            const char *e = getenv("M6A_PREP_GROUP_KB");
+            group_bytes = (e && atoll(e) > 0 ? atoll(e) : M6A_PREP_GROUP_KB_DEFAULT) << 10;
+        }
+        G->group_bytes = G->n.group_bytes = group_bytes;
+        const int rc = group_open(*G, window_bytes);
+        if (rc) return rc;
+        *out = G.release();
+        return M6A_OK;
+    });
+}
+
+extern "C" int m6a_prep_group_next(m6a_prep_group *g, m6a_prep_sites **batch)
+{
+    if (!g || !batch) return prep_fail(M6A_EINVAL, "null argument");
+    *batch = nullptr;
+    if (g->failed) { g_prep_err = g->failed_text; return g->failed; }
+    if (g->live) return prep_fail(M6A_EINVAL, "the batch before this one is still alive: free it before asking for the next");
+    if (g->ended) return M6A_OK;
+    const int rc = guarded([&] { return group_next(*g, batch); });
+    if (rc) { g->failed = rc; g->failed_text = g_prep_err; }
+    return rc;
+}
+
+extern "C" int m6a_prep_group_info(const m6a_prep_group *g, m6a_prep_group_counts *counts)
+{
+    if (!g || !counts) return prep_fail(M6A_EINVAL, "null argument");
+    *counts = g->n;
+    return M6A_OK;
+}
+
+extern "C" void m6a_prep_group_close(m6a_prep_group *g) { delete g; }
 
 extern "C" int m6a_prep_eventalign(int device_id, const char *path, int n_neighbors, const char *index_path, m6a_prep **out)
 {

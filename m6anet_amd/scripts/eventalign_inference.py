@@ -1,7 +1,8 @@
 """`eventalign_inference` sub-command: eventalign.txt -> data.site_proba.csv / data.indiv_proba.csv in one process, byte-identical
 to `dataprep --device cpu` followed by `inference` with the same flags.  The file is parsed, combined and windowed in HBM
 (m6a_prep_sites_build, include/m6a.h), the sites' features go from there to X without leaving the device, and only ids and
-probabilities come back to the host; no data.json is written or parsed."""
+probabilities come back to the host; no data.json is written or parsed.  With --grouped (m6a_prep_group) the sites come in batches as
+transcripts complete, each scored and appended to the two files while the input still arrives (main_grouped)."""
 import os
 import pathlib
 import time
@@ -97,6 +98,34 @@ def full_parser():
     return inference.add_representation_dtype(parser)
 
 
+def grouped_parser():
+    """full_parser() and --grouped: the parser of the `eventalign_inference` command"""
+    parser = full_parser()
+    parser.add_argument("--grouped", action="store_true",
+                        help="the file's transcripts each form one stretch, as nanopolish and f5c write them from a coordinate-sorted BAM: "
+                             "the sites of a transcript are built, scored and written once another contig follows it, and its runs and rows "
+                             "are released, so device memory follows the window (--window_mb; 256 MB with neither the flag nor "
+                             "M6A_PREP_WINDOW_KB set, for regular files too) and the group size (M6A_PREP_GROUP_KB, default 262144), not the "
+                             "file, and the CSV files grow while the input -- a file, `-`, a FIFO -- still arrives.  Both CSV files are byte "
+                             "for byte those of the command without the flag.  Input that is not grouped is an error that names the "
+                             "transcript and the byte where it appears again, and leaves no CSV file.  One plain-text file; not with "
+                             "--read_names, --compress or --read_representation.")
+    return parser
+
+
+# what --grouped does not take, each refused as an argument error (exit status 2) before anything is opened
+GROUPED_REFUSALS = (
+    (lambda a: not isinstance(a.eventalign, (str, bytes, os.PathLike)),
+     "--grouped takes one --eventalign file: replicates are pooled over whole files, which a batch of transcripts is not"),
+    (lambda a: getattr(a, "read_names", False),
+     "--grouped with --read_names is not built: read names are interned over the whole file after its last window"),
+    (lambda a: getattr(a, "compress", False),
+     "--grouped with --compress is not built: a BGZF file cannot be appended to behind its end-of-file block"),
+    (lambda a: getattr(a, "read_representation", False),
+     "--grouped with --read_representation is not built: the .npy header states the number of rows, which is known at the end"),
+)
+
+
 GZ = ("data.site_proba.csv", "data.indiv_proba.csv")
 
 
@@ -132,6 +161,115 @@ def write_on_device(sites, out_dir, n_threads, n_sites, compress=False, level=1)
         return None
 
 
+def main_grouped(args, weights, device, csv_on, window_mb):
+    """--grouped: the loop over the batches of _io.prep_sites_grouped.  Every batch starts on a flush-group boundary of the job, so the
+    engine scores it under set_job_offset(first_site) as it scores those sites in the whole job, and the chosen writer appends its
+    rows; the header goes with the first batch.  An error that comes once rows were written removes both CSV files: a CSV that
+    exists is complete."""
+    import sys
+    import threading
+
+    import numpy as np
+
+    from .. import _io
+    from ..constants import DEFAULT_MIN_READS, N_SAMPLES
+    from ..data_utils import load_norm_factors
+    from ..engine import reference_written_sites
+
+    t_start = time.perf_counter()
+    made = {}
+
+    def make_engine():                       # the GPU context comes up while the first windows are parsed
+        try:
+            made["engine"] = inference.make_engine_for(args, weights, device)
+        except BaseException as exc:        # re-raised on the main thread below
+            made["error"] = exc
+
+    starter = threading.Thread(target=make_engine)
+    starter.start()
+    try:
+        group = _io.prep_sites_grouped(args.eventalign, args.readcount_min, args.readcount_max, args.min_segment_count,
+                                       load_norm_factors(args.norm_path), args.n_processes, device,
+                                       window_kb=window_mb * 1024 if window_mb else None, batch_size=args.batch_size,
+                                       save_per_batch=args.save_per_batch)
+    finally:
+        starter.join()
+    if "error" in made:
+        group.close()
+        raise made["error"]
+    engine = made["engine"]
+    wrote = False
+    ms = {"infer": 0.0, "csv_write": 0.0, "first_csv_byte": None}
+    n_sites = n_reads = 0
+    try:
+        pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
+        for sites in group:
+            i = sites.info
+            t0 = time.perf_counter()
+            engine.set_job_offset(group.first_site)
+            engine.set_host_offsets(sites.off)
+            engine.infer_ptrs(i.X, i.site_kmers, i.off, sites.n_sites, args.num_iterations, N_SAMPLES, args.read_proba_threshold, args.seed,
+                              args.batch_size, args.save_per_batch, i.read_prob, i.site_prob, i.mod_ratio)
+            engine.sync()
+            t1 = time.perf_counter()
+            n_write = None
+            if args.drop_unflushed_tail:     # the reference's row set of the job so far, less what the batches before have written
+                n_write = reference_written_sites(group.first_site + sites.n_sites, args.batch_size, args.save_per_batch) - group.first_site
+            done = False
+            if csv_on == "device":
+                try:
+                    sites.write_csv(args.out_dir, write_header=not wrote, n_threads=args.n_processes, n_sites=n_write)
+                    done = True
+                except _io.CsvDeclined as e:
+                    print("eventalign_inference: --csv device declined %d values (%s); writing the batch's rows on the host"
+                          % (e.n_declined, str(e).split(": ", 1)[1]), file=sys.stderr, flush=True)
+            if not done:
+                read_prob, site_prob, mod_ratio = sites.fetch()
+                writer = sites.writer()
+                try:
+                    writer.write_csv(args.out_dir, read_prob, site_prob, mod_ratio, write_header=not wrote, n_threads=args.n_processes,
+                                     n_sites=n_write)
+                finally:
+                    writer.close()
+            wrote = True
+            t2 = time.perf_counter()
+            if ms["first_csv_byte"] is None:
+                ms["first_csv_byte"] = (t2 - t_start) * 1e3
+            ms["infer"] += (t1 - t0) * 1e3
+            ms["csv_write"] += (t2 - t1) * 1e3
+            n_sites += sites.n_sites
+            n_reads += sites.n_reads
+        if not wrote:                        # what the default leaves behind: the two header lines, then the loader's error
+            empty = _io.NativeSites.from_arrays(np.zeros(1, np.int64), np.zeros(0, np.int64), b"", np.zeros(1, np.int64), np.zeros(0, np.uint32),
+                                                np.zeros((0, 5), np.uint8), np.zeros(0))
+            try:
+                empty.write_csv(args.out_dir, [], [], [], write_header=True, n_threads=args.n_processes)
+            finally:
+                empty.close()
+            raise _io.M6AIOError("m6a_io error -4: no site with at least %d reads" % DEFAULT_MIN_READS, -4)
+        if os.environ.get("M6A_EVENTALIGN_TIMES"):      # for tools/measure_eventalign_inference.py
+            import json
+            c = group.counts()
+            ms["total"] = (time.perf_counter() - t_start) * 1e3
+            print("M6A_TIMES " + json.dumps({"ms": ms, "d2h_bytes": c["d2h_bytes"], "n_sites": n_sites, "n_reads": n_reads, "csv_writer": csv_on,
+                                                "n_windows": c["n_windows"], "window_bytes": c["window_bytes"], "peak_bytes": c["peak_bytes"],
+                                                "stream_bytes": c["stream_bytes"], "n_streams": 1 if c["stream_bytes"] else 0,
+                                                "n_batches": c["n_batches"], "max_kept_rows": c["max_kept_rows"],
+                                                "max_kept_runs": c["max_kept_runs"], "group_bytes": c["group_bytes"],
+                                                "total_rows": c["total_rows"], "total_runs": c["total_runs"]}), flush=True)
+    except BaseException:
+        if wrote:
+            for fn in GZ:
+                try:
+                    os.remove(os.path.join(args.out_dir, fn))
+                except OSError:
+                    pass
+        raise
+    finally:
+        group.close()
+        engine.close()
+
+
 def main(args):
     import threading
 
@@ -144,6 +282,12 @@ def main(args):
         import sys
         print("m6anet_amd eventalign_inference: error: --compress_level %d needs --compress" % args.compress_level, file=sys.stderr)
         raise SystemExit(2)
+    if getattr(args, "grouped", False):
+        import sys
+        for refused, text in GROUPED_REFUSALS:
+            if refused(args):
+                print("m6anet_amd eventalign_inference: error: " + text, file=sys.stderr)
+                raise SystemExit(2)
     inference.check_representation_dtype(args, "eventalign_inference")
     weights = inference.resolve_model(args)
     device = inference._device_index(args.device)
@@ -155,6 +299,8 @@ def main(args):
     want_repr = getattr(args, "read_representation", False)
     if window_mb < 0:
         raise ValueError("--window_mb must be 0 or more, not %d" % window_mb)
+    if getattr(args, "grouped", False):
+        return main_grouped(args, weights, device, csv_on, window_mb)
     made = {}
 
     def make_engine():                       # the GPU context comes up while the file is parsed

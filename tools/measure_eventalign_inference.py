@@ -75,7 +75,17 @@ The shape's file read as a file and as a stream, interleaved legs of the one-fil
 ended when it has).  Medians, the phase table of every leg with stream_bytes and n_streams, the stream's bytes per second of its
 upload wait, peak and device-to-host bytes, and the CSV files of the two compared.  The stream leg carries no bar: a pipe moves its
 bytes through read() and may be slower than pread from the page cache; which is faster is reported.  With --parent_tree the default
-command (no window, a file) against the parent's, the bar of mode (b)."""
+command (no window, a file) against the parent's, the bar of mode (b).
+
+    python tools/measure_eventalign_inference.py --grouped [--shapes 3.1GB] [--legs 5] [--window_mb 256]
+                                                 [--group_kb 65536,262144,1048576] [--parent_tree DIR] [--out profiles/r30_grouped_input.json]
+
+The shape's file, checked to be grouped by transcript, as interleaved legs of the whole command, each in its own process: the default;
+--window_mb W; --grouped --window_mb W at every group size (M6A_PREP_GROUP_KB); the same from `cat FILE |`.  Per leg the wall time, the
+time at which data.site_proba.csv first held a row (polled from outside), peak_bytes, max_kept_rows and n_batches, and the CSV files
+compared with the default's.  Then one leg with M6A_PREP_BUDGET_MB just under what the windowed leg needed: windowed refused and
+grouped completed as yes / no, CSVs identical as yes / no.  The grouped legs carry no bar (they add a back half per batch); with
+--parent_tree the default command against the parent's, the bar of mode (b)."""
 import filecmp
 import gzip
 import json
@@ -521,6 +531,126 @@ def stream_legs(tag, legs, window_mb, parent, ev_dir, limit):
     return res
 
 
+def check_grouped(path):
+    """every contig of the file forms one stretch (lines without a tab belong to no run): what --grouped needs of a shape"""
+    closed, current = set(), None
+    with open(path, "rb") as f:
+        f.readline()
+        for line in f:
+            tab = line.find(b"\t")
+            if tab < 0:
+                continue
+            name = line[:tab]
+            if name != current:
+                if current is not None:
+                    closed.add(current)
+                if name in closed:
+                    raise SystemExit("%s is not grouped by transcript: %s appears again" % (path, name.decode()))
+                current = name
+
+
+def timed_watching(cmd, out_dir, limit, env=None, pipe_from=None):
+    """timed() or timed_from_pipe() with the time at which data.site_proba.csv first holds a row: polled every 10 ms from outside"""
+    import threading
+    site = os.path.join(out_dir, CSVS[0])
+    seen, stop = [None], threading.Event()
+    t0 = time.perf_counter()
+
+    def watch():
+        while not stop.is_set():
+            try:
+                if os.path.getsize(site) > 100:              # the header line is 78 bytes
+                    seen[0] = time.perf_counter() - t0
+                    return
+            except OSError:
+                pass
+            stop.wait(0.01)
+    w = threading.Thread(target=watch, daemon=True)
+    w.start()
+    try:
+        s, p = timed_from_pipe(pipe_from, cmd, limit, env=env) if pipe_from else timed(cmd, limit, env=env)
+    finally:
+        stop.set()
+        w.join()
+    return s, p, seen[0]
+
+
+def grouped_legs(tag, legs, window_mb, group_kbs, parent, ev_dir, limit):
+    """--grouped: interleaved legs, each the whole command in its own process -- the default; --window_mb W; --grouped --window_mb W at
+    every group size; the same from `cat FILE |`.  Per leg the wall time, when the first CSV row was there, peak_bytes, and for the
+    grouped legs max_kept_rows and n_batches.  Then one leg with M6A_PREP_BUDGET_MB just under what the windowed leg needed: windowed
+    refused, grouped completed, CSVs identical.  The grouped legs carry no bar; with --parent_tree the default command against the parent's."""
+    path, n = write_shape(tag, ev_dir)
+    check_grouped(path)
+    res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs, "window_mb": window_mb, "group_kb": group_kbs, "grouped_input": True}
+    modes = {"default": ([], None, False), "windows": (["--window_mb", str(window_mb)], None, False)}
+    for kb in group_kbs:
+        modes["grouped_%d" % kb] = (["--grouped", "--window_mb", str(window_mb)], kb, False)
+        modes["grouped_%d_pipe" % kb] = (["--grouped", "--window_mb", str(window_mb)], kb, True)
+    runs = {m: [] for m in modes}
+    one, par = [], []
+    base = dict(os.environ, M6A_EVENTALIGN_TIMES="1")
+    for k in ("M6A_PREP_WINDOW_KB", "M6A_PREP_GROUP_KB", "M6A_PREP_BUDGET_MB"):
+        base.pop(k, None)
+    ref = os.path.join(ev_dir, "default")
+
+    def leg(mode, out, env_more=None):
+        flags, kb, piped = modes[mode]
+        env = dict(base, **(env_more or {}), **({"M6A_PREP_GROUP_KB": str(kb)} if kb else {}))
+        cmd = ["eventalign_inference", "--eventalign", "-" if piped else path, "--out_dir", out] + flags + THREADS
+        subprocess.run(["rm", "-rf", out], check=False)       # the watcher must not see an earlier leg's file
+        return timed_watching(cmd, out, limit, env=env, pipe_from=path if piped else None)
+    try:
+        for k in range(legs):
+            same = {}
+            for mode in modes:
+                out = os.path.join(ev_dir, mode)
+                s, p, first = leg(mode, out)
+                must(s, p, mode)
+                t = json.loads(p.stdout.split("M6A_TIMES ", 1)[1].splitlines()[0])
+                runs[mode].append(dict(t, s=s, first_csv_row_s=first))
+                if mode != "default":
+                    same[mode] = all(filecmp.cmp(os.path.join(ref, f), os.path.join(out, f), shallow=False) for f in CSVS)
+                    subprocess.run(["rm", "-rf", out], check=False)
+            res["csvs_identical"] = same
+            if parent:
+                cmd = ["eventalign_inference", "--eventalign", path, "--out_dir", os.path.join(ev_dir, "one")] + THREADS
+                one.append(must(*timed(cmd, limit), "default command, this tree"))
+                cmd[4] = os.path.join(ev_dir, "one_parent")
+                par.append(must(*timed(cmd, limit, tree=parent), "default command, parent tree"))
+                res["one_file_csvs_identical"] = all(filecmp.cmp(os.path.join(ev_dir, "one", f), os.path.join(ev_dir, "one_parent", f),
+                                                                 shallow=False) for f in CSVS)
+                for d in ("one", "one_parent"):
+                    subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+            print("%s: leg %d of %d: %s" % (tag, k + 1, legs, ", ".join("%s %.2f s" % (m, runs[m][-1]["s"]) for m in modes)), file=sys.stderr, flush=True)
+        for mode, v in runs.items():
+            res[mode] = {"median_s": median([x["s"] for x in v]),
+                         "first_csv_row_s": median([x["first_csv_row_s"] for x in v]) if all(x["first_csv_row_s"] is not None for x in v) else None,
+                         "peak_bytes": v[-1]["peak_bytes"], "n_windows": v[-1]["n_windows"], "max_kept_rows": v[-1].get("max_kept_rows"),
+                         "max_kept_runs": v[-1].get("max_kept_runs"), "n_batches": v[-1].get("n_batches"), "group_bytes": v[-1].get("group_bytes"),
+                         "legs": v}
+        # ---- the wall: a budget just under what the windowed leg needed
+        budget_mb = max(1, (res["windows"]["peak_bytes"] >> 20) - 1)
+        first_grouped = "grouped_%d" % group_kbs[0]
+        _, pw, _ = leg("windows", os.path.join(ev_dir, "w_budget"), {"M6A_PREP_BUDGET_MB": str(budget_mb)})
+        _, pg, _ = leg(first_grouped, os.path.join(ev_dir, "g_budget"), {"M6A_PREP_BUDGET_MB": str(budget_mb)})
+        res["budget"] = {"budget_mb": budget_mb, "windowed_refused": "yes" if pw.returncode != 0 else "no",
+                         "grouped_completed": "yes" if pg.returncode == 0 else "no", "grouped_mode": first_grouped,
+                         "csvs_identical": "yes" if pg.returncode == 0 and all(
+                             filecmp.cmp(os.path.join(ref, f), os.path.join(ev_dir, "g_budget", f), shallow=False) for f in CSVS) else "no"}
+        if parent:
+            res["default_command"] = {"this_s": one, "parent_s": par, "this_median_s": median(one), "parent_median_s": median(par),
+                                      "parent_spread_s": max(par) - min(par), "bar_s": median(par) + max(par) - min(par),
+                                      "within_bar": median(one) <= median(par) + max(par) - min(par)}
+    except StepFailed as e:
+        res["failed"] = e.args[0]
+        res["legs_done"] = runs
+    for d in list(modes) + ["w_budget", "g_budget"]:
+        subprocess.run(["rm", "-rf", os.path.join(ev_dir, d)], check=False)
+    os.remove(path)
+    return res
+
+
 def compress_legs(tag, legs, parent, ev_dir, limit):
     path, n = write_shape(tag, ev_dir)
     res = {"copies": n, "eventalign_GB": os.path.getsize(path) / 1e9, "legs": legs}
@@ -680,6 +810,25 @@ def main():
         with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
             for tag in shapes:
                 res[tag] = bgzf_legs(tag, legs, parent, d, limit)
+                print(json.dumps({tag: res[tag]}), flush=True)
+                os.makedirs(os.path.dirname(dest), exist_ok=True)
+                with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured
+                    json.dump(res, f, indent=1)
+                if "failed" in res[tag]:
+                    break                                   # a failed step: nothing more is started
+        return
+    if "--grouped" in sys.argv:
+        shapes = sys.argv[sys.argv.index("--shapes") + 1].split(",") if "--shapes" in sys.argv else ["3.1GB"]
+        dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(REPO, "profiles", "r30_grouped_input.json")
+        legs = int(sys.argv[sys.argv.index("--legs") + 1]) if "--legs" in sys.argv else 5
+        window_mb = int(sys.argv[sys.argv.index("--window_mb") + 1]) if "--window_mb" in sys.argv else 256
+        group_kbs = [int(x) for x in (sys.argv[sys.argv.index("--group_kb") + 1] if "--group_kb" in sys.argv else "65536,262144,1048576").split(",")]
+        parent = os.path.abspath(sys.argv[sys.argv.index("--parent_tree") + 1]) if "--parent_tree" in sys.argv else None
+        if os.path.exists(dest):                            # one shape per call is allowed: the shapes share the file
+            res = json.load(open(dest))
+        with tempfile.TemporaryDirectory(dir=os.environ.get("M6A_MEASURE_TMP")) as d:
+            for tag in shapes:
+                res[tag] = grouped_legs(tag, legs, window_mb, group_kbs, parent, d, limit)
                 print(json.dumps({tag: res[tag]}), flush=True)
                 os.makedirs(os.path.dirname(dest), exist_ok=True)
                 with open(dest, "w") as f:                  # after every shape: a later failure keeps what was measured

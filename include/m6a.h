@@ -240,6 +240,46 @@ int m6a_site_expectation(m6a_ctx *ctx, const float *read_prob, const int64_t *of
 enum { M6A_SITE_SAMPLED = 0, M6A_SITE_EXPECTED = 1 };
 int m6a_set_site_mode(m6a_ctx *ctx, int mode);
 
+/* The rank-sum test between two conditions, per site: is a site's bag of read probabilities in one set shifted against its bag in
+ * another?  Two sets of sites are given as m6a_encode_reads leaves them (prob [off[n_sites]] float32 and CSR offsets off [n_sites + 1],
+ * for instance the read_prob and off of two m6a_prep_sites handles); pair k compares site pair_a[k] of the first set with site
+ * pair_b[k] of the second.  The test is the two-sided Mann-Whitney U test with midranks for ties, the tie-corrected variance, the
+ * continuity correction and the normal approximation: scipy.stats.mannwhitneyu(a, b, use_continuity=True, alternative="two-sided",
+ * method="asymptotic").  The operation (tests/ranksum_statement.py states it in NumPy; host and device give the same bits), for a
+ * pair with bag a (n reads) and bag b (m reads); every comparison is the IEEE float32 comparison, so -0.0 == 0.0:
+ *   gt  = #{(i, j) : a_i > b_j}                                              int64
+ *   eq  = #{(i, j) : a_i == b_j}                                             int64; 2 gt + eq is twice scipy's U1
+ *   tie = sum over the distinct values v of the pooled sample of t_v^3 - t_v, t_v = how often v occurs in it -- the same number is
+ *         the sum over the pooled elements x of c_x^2 - 1, c_x = the pooled elements equal to x                  int64
+ *   z   one double; every line is one IEEE double operation per operator, evaluated as written (no fma, no reassociation; division
+ *       and sqrt round correctly on both sides):
+ *           nm  = (double)n * (double)m;         N = (double)(n + m)
+ *           U   = (double)(2*gt + eq) * 0.5;     d = U - nm * 0.5
+ *           tc  = (double)tie / (N * (N - 1.0))
+ *           var = nm / 12.0 * ((N + 1.0) - tc);  s = sqrt(var)
+ *           num = max(fabs(d) - 0.5, 0.0)
+ *           z   = num > 0 ? copysign(num, d) / s : copysign(0.0, d)
+ *       z > 0: the reads of a score higher.  The two-sided p-value is erfc(|z| / sqrt(2)) and U / nm is the AUC (the host's business:
+ *       m6anet_amd/ranksum.py).  All pooled values equal: d = 0 and z = 0, where scipy reports p = 1.
+ *   undefined pairs  either bag empty, a NaN in either bag, or n + m > 2^20 (the bound keeps tie <= (n + m)^3 inside int64): gt = eq =
+ *       tie = -1 and z = NaN.  Not an error.  Infinite values are ordinary values.
+ * The counts are integers, so they do not depend on how they are counted; no float is added anywhere before z.  The kernel
+ * (site_ranksum_kernel, a wavefront per pair) compares all pairs: about (n + m)^2 comparisons per pair, made for bags of tens to a few
+ * thousand reads; the largest defined pair occupies one wavefront for about a minute.
+ *   pair_a, pair_b  [n_pairs] int64, or NULL: the identity, which needs n_pairs == n_sites_a == n_sites_b (else M6A_EINVAL).  A site
+ *       may appear in any number of pairs, in any order
+ *   gt, eq, tie     [n_pairs] int64 out, each may be NULL;  z [n_pairs] float64 out, required
+ * Pointers all host (staged, synchronous) or all device (queued on the context's stream), as stated under DATA POINTERS.  With host
+ * arrays a pair index outside its set and offsets that do not start at 0 or that decrease are M6A_EINVAL before anything is queued
+ * and the outputs are untouched.  With device arrays the kernel reads nothing through an index or an offset it has not checked: a
+ * pair whose index is outside its set, or whose offsets are negative, decrease or exceed off[n_sites], gets the undefined pair's
+ * values and raises a deferred M6A_EINVAL that the next m6a_sync returns; every other pair of the call is computed.  n_pairs == 0 is
+ * M6A_OK and touches nothing.  No reference counterpart: the reference scores one condition at a time. */
+int m6a_site_ranksum(m6a_ctx *ctx, const float *prob_a, const int64_t *off_a, int64_t n_sites_a,
+                     const float *prob_b, const int64_t *off_b, int64_t n_sites_b,
+                     const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
+                     int64_t *gt, int64_t *eq, int64_t *tie, double *z);
+
 /* Streaming form of m6a_infer: the batch loop of run_inference (m6anet/utils/inference_utils.py:33-54) fed as the
  * DataLoader produces it, so a reference-side binding keeps its loader and its loop.
  *   m6a_job_begin   the arguments calculate_site_proba / the flush test get per job (inference_utils.py:47,54);

@@ -266,6 +266,16 @@ int m6a_io_norm_partials(const char *json_path, int64_t n_sites, const char *tx_
                          const int64_t *start, const int64_t *end, const int64_t *n_reads, const int64_t *sites, int64_t n, int n_threads,
                          double *s, double *s2, char *kmer7);
 
+/* m6a_site_ranksum (include/m6a.h states the operation) on the host: the same arguments without the context, every array a host
+ * array, the pairs spread over n_threads threads (0: the usable CPUs).  The counts and z are the kernel's, bit for bit: both compile
+ * m6anet_amd/csrc/m6a_ranksum.h.  A pair is counted from sorted copies of its two bags, so the cost is O((n + m) log(n + m)).
+ * pair_a and pair_b may be NULL (the identity: n_pairs == n_sites_a == n_sites_b); gt, eq and tie may each be NULL; z is required.
+ * M6A_IO_EINVAL, with the outputs untouched, for a null required pointer, a negative count, offsets that do not start at 0 or that
+ * decrease, and a pair index outside its set.  n_pairs == 0 is M6A_IO_OK. */
+int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,
+                        int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
+                        int64_t *tie, double *z, int n_threads);
+
 #ifdef __cplusplus
 }
 #endif

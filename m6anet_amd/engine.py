@@ -425,6 +425,36 @@ class M6ANetEngine:
                                                aS.ptr, aM.ptr, aG.ptr if aG else None))
         return (site, mod, sigma) if want_sigma else (site, mod)
 
+    def site_ranksum(self, read_probs_a, off_a, read_probs_b, off_b, pair_a=None, pair_b=None):
+        """The rank-sum test between two sets of sites (include/m6a.h: m6a_site_ranksum): pair k compares the reads of site pair_a[k]
+        of the first set with those of site pair_b[k] of the second; without the two index arrays site k is compared with site k.
+        NumPy arrays (synchronous) or torch tensors on the GPU (queued: `sync()` before reading), all of one kind.  Returns
+        (gt, eq, tie int64 [P], z float64 [P]); an undefined pair -- an empty bag, a NaN, more than 2^20 pooled reads -- is
+        (-1, -1, -1, NaN).  m6anet_amd/ranksum.py turns them into p, q and the AUC."""
+        if (pair_a is None) != (pair_b is None):
+            raise ValueError("pair_a and pair_b are given together or not at all")
+        aPa, aOa = _Arg(read_probs_a, np.float32, "float32"), _Arg(off_a, np.int64, "int64")
+        aPb, aOb = _Arg(read_probs_b, np.float32, "float32"), _Arg(off_b, np.int64, "int64")
+        Sa, Sb = aOa.size - 1, aOb.size - 1
+        aIa = _Arg(pair_a, np.int64, "int64") if pair_a is not None else None
+        aIb = _Arg(pair_b, np.int64, "int64") if pair_b is not None else None
+        if aIa is not None and aIa.size != aIb.size:
+            raise ValueError("pair_a and pair_b must have one entry per pair")
+        if aIa is None and Sa != Sb:
+            raise ValueError("without pair_a / pair_b the two sets must have the same number of sites")
+        P = aIa.size if aIa is not None else Sa
+        out = [self._out(aPa.is_dev, P, np.int64, "int64") for _ in range(3)] + [self._out(aPa.is_dev, P, np.float64, "float64")]
+        ptrs = [_Arg(o, dt, name).ptr for o, dt, name in zip(out, (np.int64,) * 3 + (np.float64,), ("int64",) * 3 + ("float64",))]
+        self.site_ranksum_ptrs(aPa.ptr, aOa.ptr, Sa, aPb.ptr, aOb.ptr, Sb, aIa.ptr if aIa else None, aIb.ptr if aIb else None, P, *ptrs)
+        return tuple(out)
+
+    def site_ranksum_ptrs(self, prob_a, off_a, n_sites_a, prob_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, gt, eq, tie, z):
+        """m6a_site_ranksum on raw addresses (ints) the caller owns, as infer_ptrs is m6a_infer on them -- e.g. the read_prob and off
+        of two m6a_prep_sites handles after infer_ptrs has filled them: all host or all device; pair_a / pair_b and gt / eq / tie may
+        be None.  With device pointers the call is queued on the context's stream: `sync()` before the outputs are read."""
+        self._chk(self._L.m6a_site_ranksum(self._h, prob_a, off_a, int(n_sites_a), prob_b, off_b, int(n_sites_b), pair_a, pair_b,
+                                           int(n_pairs), gt, eq, tie, z))
+
     def infer(self, X, site_kmers, off, n_iters, n_samples=N_SAMPLES,
               read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16, save_per_batch=2,
               want_read_probs=True, out=None):

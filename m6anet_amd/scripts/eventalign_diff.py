@@ -1,0 +1,150 @@
+"""`eventalign_diff` sub-command: two conditions' eventalign files -> each condition's two CSV files and OUT/data.diff.csv, the per-site
+rank-sum test between them (include/m6a.h: m6a_site_ranksum).  Each condition is built and scored as `eventalign_inference` builds
+and scores it (several files are pooled as replicates; BGZF, `-` and FIFOs are what the handle takes), as a job of its own with the
+same --seed, and both handles stay open: the two site tables are joined on the host, the pair indices go up, the kernel compares the
+two read_prob arrays where they lie, and 24 bytes per pair come back (gt, eq, z).  OUT/a and OUT/b hold what `eventalign_inference`
+writes for the condition, byte for byte."""
+import os
+import pathlib
+import sys
+from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
+
+from . import dataprep, eventalign_inference, inference
+
+# eventalign_inference.argparser()'s flags without --eventalign: a condition is scored whole, so --drop_unflushed_tail has no place
+INFERENCE_FLAGS = tuple(f for f in eventalign_inference.INFERENCE_FLAGS if f != "--drop_unflushed_tail")
+
+
+def argparser():
+    parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter, add_help=False)
+    for side, what in (("a", "first"), ("b", "second")):
+        parser.add_argument("--eventalign_" + side, required=True, nargs="+",
+                            help="eventalign file(s) of the %s condition, each as `eventalign_inference --eventalign` takes it (plain text or "
+                                 "BGZF, `-` for the standard input, a FIFO); several files are replicates and are pooled." % what)
+    parser.add_argument("--out_dir", required=True,
+                        help="directory for the results: a/ and b/ (the two CSV files of each condition) and data.diff.csv.")
+    eventalign_inference._copy(dataprep.argparser(), parser, eventalign_inference.DATAPREP_FLAGS)
+    eventalign_inference._copy(inference.argparser(), parser, INFERENCE_FLAGS)
+    parser.add_argument("--window_mb", type=int, default=0,
+                        help="parse each eventalign file in windows of this many MB, as `eventalign_inference --window_mb` does (0: resident).")
+    return inference.add_site_proba(parser)
+
+
+def argument_error(args):
+    """the sentence for what is refused before anything is opened or a GPU is touched, or None"""
+    a, b = list(args.eventalign_a), list(args.eventalign_b)
+    if (a + b).count("-") > 1:
+        return "`-` is the standard input and can be read once: it is given %d times" % (a + b).count("-")
+    if args.num_iterations < 1:
+        return "--num_iterations must be 1 or more, not %d" % args.num_iterations
+    if args.batch_size < 1 or args.save_per_batch < 1:
+        return "--batch_size and --save_per_batch must be 1 or more"
+    if args.window_mb < 0:
+        return "--window_mb must be 0 or more, not %d" % args.window_mb
+    if not 0 <= int(args.seed) <= 0xffffffff:
+        return "--seed must be between 0 and 2**32 - 1"
+    if args.readcount_min < 1 or args.readcount_max < args.readcount_min:
+        return "--readcount_min must be 1 or more and at most --readcount_max"
+    if str(args.device).lower().startswith("cpu"):
+        return "--device cpu: this build runs the hot path on an MI355X only (no CPU fallback)"
+    return None
+
+
+def score(engine, sites, out_dir, args):
+    """One condition as `eventalign_inference` scores and writes it (host writer); returns (site_prob, mod_ratio) of its sites."""
+    from .. import _io
+    from ..constants import DEFAULT_MIN_READS, N_SAMPLES
+    pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
+    writer = sites.writer()
+    try:
+        if sites.n_sites == 0:               # what `eventalign_inference` leaves behind: the two header lines, then the loader's error
+            writer.write_csv(out_dir, [], [], [], write_header=True, n_threads=args.n_processes)
+            raise _io.M6AIOError("m6a_io error -4: no site with at least %d reads" % DEFAULT_MIN_READS, -4)
+        i = sites.info
+        engine.set_host_offsets(sites.off)
+        engine.infer_ptrs(i.X, i.site_kmers, i.off, sites.n_sites, args.num_iterations, N_SAMPLES, args.read_proba_threshold, args.seed,
+                          args.batch_size, args.save_per_batch, i.read_prob, i.site_prob, i.mod_ratio)
+        engine.sync()
+        read_prob, site_prob, mod_ratio = sites.fetch()
+        writer.write_csv(out_dir, read_prob, site_prob, mod_ratio, write_header=True, n_threads=args.n_processes)
+    finally:
+        writer.close()
+    return site_prob, mod_ratio
+
+
+def compare(engine, sites_a, sites_b, pair_a, pair_b):
+    """m6a_site_ranksum on the two handles' device arrays: the pair indices go up, (gt, eq, z) come back"""
+    import numpy as np
+    import torch
+    P = int(pair_a.size)
+    if P == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)
+    dev = "cuda:%d" % engine.device
+    ia, ib = torch.from_numpy(pair_a).to(dev), torch.from_numpy(pair_b).to(dev)      # pageable memory: the copies are done on return
+    gt, eq = torch.empty(P, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.int64, device=dev)
+    z = torch.empty(P, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(engine.device)
+    a, b = sites_a.info, sites_b.info
+    engine.site_ranksum_ptrs(a.read_prob, a.off, sites_a.n_sites, b.read_prob, b.off, sites_b.n_sites, ia.data_ptr(), ib.data_ptr(), P,
+                             gt.data_ptr(), eq.data_ptr(), None, z.data_ptr())
+    engine.sync()
+    return gt.cpu().numpy(), eq.cpu().numpy(), z.cpu().numpy()
+
+
+def main(args):
+    import threading
+
+    import numpy as np
+
+    from .. import _io, ranksum
+    from ..data_utils import load_norm_factors
+
+    text = argument_error(args)
+    if text:
+        print("m6anet_amd eventalign_diff: error: " + text, file=sys.stderr)
+        raise SystemExit(2)
+    weights = inference.resolve_model(args)
+    device = inference._device_index(args.device)
+    made = {}
+
+    def make_engine():                       # the GPU context comes up while the first condition is parsed
+        try:
+            made["engine"] = inference.make_engine_for(args, weights, device)
+        except BaseException as exc:        # re-raised on the main thread below
+            made["error"] = exc
+
+    def build(paths):                        # one file is a path, several are replicates: as --eventalign has them
+        return _io.prep_sites(paths[0] if len(paths) == 1 else list(paths), args.readcount_min, args.readcount_max, args.min_segment_count,
+                              load_norm_factors(args.norm_path), args.n_processes, device,
+                              window_kb=args.window_mb * 1024 if args.window_mb else None)
+
+    starter = threading.Thread(target=make_engine)
+    starter.start()
+    sites = []
+    try:
+        try:
+            sites.append(build(args.eventalign_a))
+        finally:
+            starter.join()
+        if "error" in made:
+            raise made["error"]
+        sites.append(build(args.eventalign_b))
+        engine = made["engine"]
+        sa, sb = sites
+        site_a, mod_a = score(engine, sa, os.path.join(args.out_dir, "a"), args)
+        site_b, mod_b = score(engine, sb, os.path.join(args.out_dir, "b"), args)
+        names_a, names_b = np.asarray(sa.names, object), np.asarray(sb.names, object)
+        pair_a, pair_b = ranksum.join(names_a[sa.site_tx], sa.tx_pos, names_b[sb.site_tx], sb.tx_pos)
+        gt, eq, z = compare(engine, sa, sb, pair_a, pair_b)
+        kmer = [bytes(k).decode() for k in sa.kmer7[pair_a, 1:6]]
+        text = ranksum.diff_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b],
+                                 site_a[pair_a], site_b[pair_b], mod_a[pair_a], mod_b[pair_b], gt, eq, z)
+        with open(os.path.join(args.out_dir, ranksum.DIFF_FILE), "w") as f:
+            f.write(text)
+        print("eventalign_diff: %d sites in both conditions, %d only in A, %d only in B"
+              % (pair_a.size, sa.n_sites - pair_a.size, sb.n_sites - np.unique(pair_b).size), flush=True)
+    finally:
+        for s in sites:
+            s.close()
+        if "engine" in made:
+            made["engine"].close()

@@ -279,6 +279,29 @@ int m6a_site_ranksum(m6a_ctx *ctx, const float *prob_a, const int64_t *off_a, in
                      const float *prob_b, const int64_t *off_b, int64_t n_sites_b,
                      const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
                      int64_t *gt, int64_t *eq, int64_t *tie, double *z);
+/* The same test on the signal itself: m6a_site_ranksum on each of the M6A_N_FEATURES columns of two sets' X, the model-free comparison
+ * beside the one on read probabilities.  X_* is [off_*[n_sites_*]][9] float32 as m6a_encode_reads takes it (for instance the X and off of
+ * two m6a_prep_sites handles), so per read dwell_time, norm_std, norm_mean at position -1, then at 0, then at +1 (M6A_N_FEATURES above);
+ * off_* counts rows.  A site has the same 7-mer in both sets, so its normalisation is one increasing affine map per column and ranks on X
+ * are ranks on the raw signal.  For pair k and column c the result, at [k * 9 + c] of each output, is exactly m6a_site_ranksum's result
+ * on two bags: column c of the rows of site pair_a[k] and column c of the rows of site pair_b[k] -- gt, eq and tie as defined above, z by
+ * the lines above (one header, m6anet_amd/csrc/m6a_ranksum.h, computes it for both kernels and the host), the float32 comparisons as above.
+ * tests/signal_ranksum_statement.py states it by calling the statement above per column.
+ *   undefined  either bag empty or n + m > 2^20: all nine columns.  A NaN in column c of either bag: column c alone (-1, -1, -1, NaN),
+ *       the other eight are computed.  Not an error.
+ *   gt, eq, tie  [n_pairs][9] int64 out, row-major, each may be NULL;  z [n_pairs][9] float64 out, required
+ * Pair arrays, pointers (all host: staged, synchronous, checked before anything is queued and the outputs untouched on M6A_EINVAL; or all
+ * device: queued on the context's stream) and n_pairs == 0 are m6a_site_ranksum's rules.  With device arrays nothing is read through an
+ * index or an offset that has not been checked: a bad pair gets the undefined values in all nine columns and raises the deferred
+ * M6A_EINVAL of the next m6a_sync; every other pair is computed.  The kernel (site_signal_ranksum_kernel, a wavefront per pair) makes the
+ * same (n + m)^2 comparisons per column and fetches each tile of rows once for all nine.  The nine p-values of a site are nine tests:
+ * `eventalign_diff --signal` corrects them as one Benjamini-Hochberg family over every row of data.diff_signal.csv (nine per shared
+ * site).  Not built: a sort-based path for very large bags, a lane-per-pair variant, a Kolmogorov-Smirnov statistic, effect sizes in pA.
+ * No reference counterpart. */
+int m6a_site_signal_ranksum(m6a_ctx *ctx, const float *X_a, const int64_t *off_a, int64_t n_sites_a,
+                            const float *X_b, const int64_t *off_b, int64_t n_sites_b,
+                            const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
+                            int64_t *gt, int64_t *eq, int64_t *tie, double *z);
 
 /* Streaming form of m6a_infer: the batch loop of run_inference (m6anet/utils/inference_utils.py:33-54) fed as the
  * DataLoader produces it, so a reference-side binding keeps its loader and its loop.

@@ -275,6 +275,12 @@ int m6a_io_norm_partials(const char *json_path, int64_t n_sites, const char *tx_
 int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,
                         int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
                         int64_t *tie, double *z, int n_threads);
+/* m6a_site_signal_ranksum (include/m6a.h) on the host: X_* [off_*[n_sites_*]][9], outputs [n_pairs][9].  Per pair and column, the column
+ * of either bag is gathered into scratch and counted by m6a_ranksum.h's count(), so a NaN leaves its own column undefined and no other;
+ * arguments, errors and threading are m6a_io_site_ranksum's. */
+int m6a_io_site_signal_ranksum(const float *X_a, const int64_t *off_a, int64_t n_sites_a, const float *X_b, const int64_t *off_b,
+                               int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
+                               int64_t *tie, double *z, int n_threads);
 
 #ifdef __cplusplus
 }

@@ -455,6 +455,38 @@ class M6ANetEngine:
         self._chk(self._L.m6a_site_ranksum(self._h, prob_a, off_a, int(n_sites_a), prob_b, off_b, int(n_sites_b), pair_a, pair_b,
                                            int(n_pairs), gt, eq, tie, z))
 
+    def site_signal_ranksum(self, X_a, off_a, X_b, off_b, pair_a=None, pair_b=None):
+        """The rank-sum test on each of the nine signal features (include/m6a.h: m6a_site_signal_ranksum): site_ranksum on every
+        column of X_a [Ra, 9] and X_b [Rb, 9] -- dwell_time, norm_std, norm_mean at positions -1, 0, +1 -- with off_* in rows.  NumPy
+        arrays (synchronous) or torch tensors on the GPU (queued: `sync()` before reading), all of one kind.  Returns (gt, eq, tie
+        int64 [P, 9], z float64 [P, 9]); a NaN leaves its own column of the pair undefined, an empty bag or more than 2^20 pooled
+        reads all nine.  m6anet_amd/ranksum.py (signal_rows) turns them into p, q and the AUC."""
+        if (pair_a is None) != (pair_b is None):
+            raise ValueError("pair_a and pair_b are given together or not at all")
+        aXa, aOa = _Arg(X_a, np.float32, "float32"), _Arg(off_a, np.int64, "int64")
+        aXb, aOb = _Arg(X_b, np.float32, "float32"), _Arg(off_b, np.int64, "int64")
+        if aXa.size % 9 or aXb.size % 9:
+            raise ValueError("X_a and X_b hold nine float32 per read")
+        Sa, Sb = aOa.size - 1, aOb.size - 1
+        aIa = _Arg(pair_a, np.int64, "int64") if pair_a is not None else None
+        aIb = _Arg(pair_b, np.int64, "int64") if pair_b is not None else None
+        if aIa is not None and aIa.size != aIb.size:
+            raise ValueError("pair_a and pair_b must have one entry per pair")
+        if aIa is None and Sa != Sb:
+            raise ValueError("without pair_a / pair_b the two sets must have the same number of sites")
+        P = aIa.size if aIa is not None else Sa
+        out = [self._out(aXa.is_dev, P * 9, np.int64, "int64") for _ in range(3)] + [self._out(aXa.is_dev, P * 9, np.float64, "float64")]
+        ptrs = [_Arg(o, dt, name).ptr for o, dt, name in zip(out, (np.int64,) * 3 + (np.float64,), ("int64",) * 3 + ("float64",))]
+        self.site_signal_ranksum_ptrs(aXa.ptr, aOa.ptr, Sa, aXb.ptr, aOb.ptr, Sb, aIa.ptr if aIa else None, aIb.ptr if aIb else None, P, *ptrs)
+        return tuple(o.reshape(P, 9) for o in out)
+
+    def site_signal_ranksum_ptrs(self, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, gt, eq, tie, z):
+        """m6a_site_signal_ranksum on raw addresses (ints) the caller owns, as site_ranksum_ptrs is m6a_site_ranksum on them -- e.g. the
+        X and off of two m6a_prep_sites handles: all host or all device; pair_a / pair_b and gt / eq / tie may be None; the outputs
+        hold nine values per pair.  With device pointers the call is queued on the context's stream: `sync()` before they are read."""
+        self._chk(self._L.m6a_site_signal_ranksum(self._h, X_a, off_a, int(n_sites_a), X_b, off_b, int(n_sites_b), pair_a, pair_b,
+                                                  int(n_pairs), gt, eq, tie, z))
+
     def infer(self, X, site_kmers, off, n_iters, n_samples=N_SAMPLES,
               read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16, save_per_batch=2,
               want_read_probs=True, out=None):

@@ -6,7 +6,8 @@ only.
               (ties count half); NaN for an undefined pair
   bh          Benjamini-Hochberg q over the rows whose p is not NaN: stable order by p, q_(i) = min(1, min_{j >= i} p_(j) M / j)
   join        the inner join of two site tables on (transcript_id, transcript_position), in the order of the first table
-  diff_rows   the lines of data.diff.csv"""
+  diff_rows   the lines of data.diff.csv
+  signal_rows the lines of data.diff_signal.csv (`eventalign_diff --signal`; m6a_site_signal_ranksum): nine per pair, one BH family"""
 import math
 
 import numpy as np
@@ -14,6 +15,12 @@ import numpy as np
 DIFF_HEADER = ("transcript_id,transcript_position,kmer,n_reads_a,n_reads_b,probability_modified_a,probability_modified_b,"
                "mod_ratio_a,mod_ratio_b,auc,z,p_value,q_value")
 DIFF_FILE = "data.diff.csv"
+SIGNAL_HEADER = "transcript_id,transcript_position,kmer,n_reads_a,n_reads_b,position_offset,feature,auc,z,p_value,q_value"
+SIGNAL_FILE = "data.diff_signal.csv"
+# the columns of X [R][9] as (position_offset, feature): the reference's order, dwell_time, norm_std, norm_mean per position
+# (m6anet/utils/dataprep_utils.py:132) and positions -1, 0, +1 (the loader's left, centre and right indices)
+SIGNAL_COLUMNS = tuple((o, f) for o in (-1, 0, 1) for f in ("dwell_time", "norm_std", "norm_mean"))
+N_SIGNAL = len(SIGNAL_COLUMNS)
 _SQRT2 = math.sqrt(2.0)
 
 
@@ -80,3 +87,23 @@ def diff_rows(tx, pos, kmer, n_a, n_b, site_a, site_b, mod_a, mod_b, gt, eq, z):
 
 def diff_text(*columns):
     return DIFF_HEADER + "\n" + "".join(diff_rows(*columns))
+
+
+def signal_rows(tx, pos, kmer, n_a, n_b, gt, eq, z):
+    """The data lines of data.diff_signal.csv (no header, each with its newline) for P pairs: tx, pos, kmer, n_a, n_b as diff_rows takes
+    them and gt, eq, z [P, 9] of m6a_site_signal_ranksum.  Nine lines per pair in column order, SIGNAL_COLUMNS naming the column;
+    q_value is Benjamini-Hochberg over all 9 P rows whose p is not NaN, one family; auc, z, p_value and q_value are repr(float)."""
+    z = np.asarray(z, np.float64).reshape(-1, N_SIGNAL)
+    P = z.shape[0]
+    gt, eq = np.asarray(gt, np.int64).reshape(P, N_SIGNAL), np.asarray(eq, np.int64).reshape(P, N_SIGNAL)
+    p = p_value(z)
+    q = bh(p.ravel()).reshape(P, N_SIGNAL)
+    n_a, n_b = np.asarray(n_a, np.int64).reshape(P), np.asarray(n_b, np.int64).reshape(P)
+    a = auc(gt, eq, np.repeat(n_a[:, None], N_SIGNAL, axis=1), np.repeat(n_b[:, None], N_SIGNAL, axis=1))
+    return ["%s,%d,%s,%d,%d,%d,%s,%s,%s,%s,%s\n"
+            % (tx[k], pos[k], kmer[k], n_a[k], n_b[k], SIGNAL_COLUMNS[c][0], SIGNAL_COLUMNS[c][1], _repr(float(a[k, c])), _repr(float(z[k, c])),
+               _repr(float(p[k, c])), _repr(float(q[k, c]))) for k in range(P) for c in range(N_SIGNAL)]
+
+
+def signal_text(*columns):
+    return SIGNAL_HEADER + "\n" + "".join(signal_rows(*columns))

@@ -3,7 +3,11 @@ rank-sum test between them (include/m6a.h: m6a_site_ranksum).  Each condition is
 and scores it (several files are pooled as replicates; BGZF, `-` and FIFOs are what the handle takes), as a job of its own with the
 same --seed, and both handles stay open: the two site tables are joined on the host, the pair indices go up, the kernel compares the
 two read_prob arrays where they lie, and 24 bytes per pair come back (gt, eq, z).  OUT/a and OUT/b hold what `eventalign_inference`
-writes for the condition, byte for byte."""
+writes for the condition, byte for byte.
+With --signal one more launch follows (include/m6a.h: m6a_site_signal_ranksum): the same test on each of the nine columns of the two
+handles' X -- dwell_time, norm_std and norm_mean at positions -1, 0, +1 -- with the same pair indices, 288 bytes per pair come back,
+and OUT/data.diff_signal.csv holds nine rows per shared site, in data.diff.csv's order of sites and X's order of columns.  Its q_value is
+Benjamini-Hochberg over all rows of that file, nine tests per site in one family.  Every other file keeps its bytes."""
 import os
 import pathlib
 import sys
@@ -27,6 +31,10 @@ def argparser():
     eventalign_inference._copy(inference.argparser(), parser, INFERENCE_FLAGS)
     parser.add_argument("--window_mb", type=int, default=0,
                         help="parse each eventalign file in windows of this many MB, as `eventalign_inference --window_mb` does (0: resident).")
+    parser.add_argument("--signal", action="store_true",
+                        help="also write data.diff_signal.csv: the rank-sum test on each of the nine signal features of a shared site "
+                             "(dwell_time, norm_std, norm_mean at positions -1, 0, +1), the model-free comparison.  Nine rows per site; "
+                             "q_value is Benjamini-Hochberg over all rows of that file, nine tests per site in one family.")
     return inference.add_site_proba(parser)
 
 
@@ -91,6 +99,25 @@ def compare(engine, sites_a, sites_b, pair_a, pair_b):
     return gt.cpu().numpy(), eq.cpu().numpy(), z.cpu().numpy()
 
 
+def compare_signal(engine, sites_a, sites_b, pair_a, pair_b):
+    """m6a_site_signal_ranksum on the two handles' X where they lie: the pair indices go up, (gt, eq, z) [P, 9] come back"""
+    import numpy as np
+    import torch
+    P = int(pair_a.size)
+    if P == 0:
+        return np.zeros((0, 9), np.int64), np.zeros((0, 9), np.int64), np.zeros((0, 9), np.float64)
+    dev = "cuda:%d" % engine.device
+    ia, ib = torch.from_numpy(pair_a).to(dev), torch.from_numpy(pair_b).to(dev)      # pageable memory: the copies are done on return
+    gt, eq = torch.empty((P, 9), dtype=torch.int64, device=dev), torch.empty((P, 9), dtype=torch.int64, device=dev)
+    z = torch.empty((P, 9), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(engine.device)
+    a, b = sites_a.info, sites_b.info
+    engine.site_signal_ranksum_ptrs(a.X, a.off, sites_a.n_sites, b.X, b.off, sites_b.n_sites, ia.data_ptr(), ib.data_ptr(), P,
+                                    gt.data_ptr(), eq.data_ptr(), None, z.data_ptr())
+    engine.sync()
+    return gt.cpu().numpy(), eq.cpu().numpy(), z.cpu().numpy()
+
+
 def main(args):
     import threading
 
@@ -141,6 +168,12 @@ def main(args):
                                  site_a[pair_a], site_b[pair_b], mod_a[pair_a], mod_b[pair_b], gt, eq, z)
         with open(os.path.join(args.out_dir, ranksum.DIFF_FILE), "w") as f:
             f.write(text)
+        if args.signal:
+            gt, eq, z = compare_signal(engine, sa, sb, pair_a, pair_b)
+            text = ranksum.signal_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b],
+                                       gt, eq, z)
+            with open(os.path.join(args.out_dir, ranksum.SIGNAL_FILE), "w") as f:
+                f.write(text)
         print("eventalign_diff: %d sites in both conditions, %d only in A, %d only in B"
               % (pair_a.size, sa.n_sites - pair_a.size, sb.n_sites - np.unique(pair_b).size), flush=True)
     finally:

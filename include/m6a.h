@@ -296,12 +296,58 @@ int m6a_site_ranksum(m6a_ctx *ctx, const float *prob_a, const int64_t *off_a, in
  * M6A_EINVAL of the next m6a_sync; every other pair is computed.  The kernel (site_signal_ranksum_kernel, a wavefront per pair) makes the
  * same (n + m)^2 comparisons per column and fetches each tile of rows once for all nine.  The nine p-values of a site are nine tests:
  * `eventalign_diff --signal` corrects them as one Benjamini-Hochberg family over every row of data.diff_signal.csv (nine per shared
- * site).  Not built: a sort-based path for very large bags, a lane-per-pair variant, a Kolmogorov-Smirnov statistic, effect sizes in pA.
+ * site).  Not built: a sort-based path for very large bags, a lane-per-pair variant, effect sizes in pA (m6a_site_signal_ks below gives
+ * the Kolmogorov-Smirnov statistic and the medians in X's units).
  * No reference counterpart. */
 int m6a_site_signal_ranksum(m6a_ctx *ctx, const float *X_a, const int64_t *off_a, int64_t n_sites_a,
                             const float *X_b, const int64_t *off_b, int64_t n_sites_b,
                             const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
                             int64_t *gt, int64_t *eq, int64_t *tie, double *z);
+
+/* The two-sample Kolmogorov-Smirnov statistic and the two medians, per pair of sites: the test that sees more than a shift of location
+ * (a bag that became a mixture of two populations can keep its rank-sum near zero), and the effect size beside it.  Sets, pairs and
+ * pointers are m6a_site_ranksum's.  The operation (tests/ks_statement.py states it in NumPy; host and device give the same bits), for a
+ * pair with bag a (n reads) and bag b (m reads), the float32 comparisons as above (-0.0 == 0.0, infinities are ordinary values):
+ *   with A(v) = #{a_i <= v} and B(v) = #{b_j <= v} for a pooled value v,
+ *   d_pos = max over the pooled v of (m A(v) - n B(v))                        int64
+ *   d_neg = max over the pooled v of (n B(v) - m A(v))                        int64; both >= 0 (the expression is 0 at the largest v),
+ *                                                                             both <= 2^40
+ *   med_a = (double)lo * 0.5 + (double)hi * 0.5 with lo = a_((n-1)/2) and hi = a_(n/2) of sorted(a), 0-based, integer division: two
+ *           float32 order statistics and one line of IEEE double operations, np.median(a.astype(float64)) wherever that is finite.  A
+ *           result that compares equal to zero is +0.0 (which of -0.0 and 0.0 a selection meets is not defined); +inf and -inf as the
+ *           two middles give NaN, as np.median does.  med_b likewise.
+ *   undefined pairs  m6a_site_ranksum's rule as it is: either bag empty, a NaN in either bag, or n + m > 2^20: d_pos = d_neg = -1 and
+ *       med_a = med_b = NaN.  Not an error.
+ * Derived on the host (m6anet_amd/ranksum.py): D = max(d_pos, d_neg) / (n m) in double, scipy.stats.ks_2samp's statistic; ks_sign = +1
+ * where d_pos >= d_neg, else -1 (+1: a's empirical CDF lies above b's at the widest gap, so a's values tend lower); and the p-value
+ * p = Q(lambda), lambda = sqrt(n m / (n + m)) D, Q the Kolmogorov limit distribution 2 sum_{k>=1} (-1)^(k-1) exp(-2 k^2 lambda^2) --
+ * scipy.stats.kstwobign.sf(lambda).  That is NOT what scipy.stats.ks_2samp returns (exact for small bags, kstwo at round(en) under
+ * method="asymp"); the limit is conservative for small bags (one 20 + 20 pair: 0.0047 against the exact 0.0040).  The exact
+ * small-sample p-value is not built.
+ *   d_pos, d_neg   [n_pairs] int64 out, required;  med_a, med_b [n_pairs] float64 out, each may be NULL
+ * Pointers all host (staged, synchronous, checked before anything is queued and the outputs untouched on M6A_EINVAL) or all device
+ * (queued on the context's stream), pair arrays and n_pairs == 0 as for m6a_site_ranksum.  With device arrays nothing is read through an
+ * index or an offset that has not been checked: a bad pair gets the undefined values and raises the deferred M6A_EINVAL of the next
+ * m6a_sync; every other pair is computed.  The kernel (site_ks_kernel, a wavefront per pair) makes about 1.5 (n + m)^2 comparisons per
+ * pair and adds no float before the median's line.  No reference counterpart. */
+int m6a_site_ks(m6a_ctx *ctx, const float *prob_a, const int64_t *off_a, int64_t n_sites_a,
+                const float *prob_b, const int64_t *off_b, int64_t n_sites_b,
+                const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
+                int64_t *d_pos, int64_t *d_neg, double *med_a, double *med_b);
+/* m6a_site_ks on each of the M6A_N_FEATURES columns of two sets' X [off_*[n_sites_*]][9], as m6a_site_signal_ranksum is m6a_site_ranksum
+ * on them: for pair k and column c the result, at [k * 9 + c] of each output, is m6a_site_ks's result on column c of the rows of the two
+ * sites (tests/ks_statement.py calls its own pair statement per column).  The medians are in the normalised units of X; their
+ * conversion to pA is not built.
+ *   undefined  either bag empty or n + m > 2^20: all nine columns.  A NaN in column c of either bag: column c alone, the other eight
+ *       are computed.  Not an error.
+ *   d_pos, d_neg  [n_pairs][9] int64 out, row-major, required;  med_a, med_b [n_pairs][9] float64 out, each may be NULL
+ * Everything else is m6a_site_ks's.  The kernel (site_signal_ks_kernel, a wavefront per pair) fetches each tile of rows once for all nine
+ * columns.  `eventalign_diff --signal --ks` corrects the nine p-values of a site as one Benjamini-Hochberg family over every row of
+ * data.diff_signal_ks.csv.  No reference counterpart. */
+int m6a_site_signal_ks(m6a_ctx *ctx, const float *X_a, const int64_t *off_a, int64_t n_sites_a,
+                       const float *X_b, const int64_t *off_b, int64_t n_sites_b,
+                       const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
+                       int64_t *d_pos, int64_t *d_neg, double *med_a, double *med_b);
 
 /* Streaming form of m6a_infer: the batch loop of run_inference (m6anet/utils/inference_utils.py:33-54) fed as the
  * DataLoader produces it, so a reference-side binding keeps its loader and its loop.

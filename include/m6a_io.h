@@ -281,6 +281,16 @@ int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, int64_t n_sit
 int m6a_io_site_signal_ranksum(const float *X_a, const int64_t *off_a, int64_t n_sites_a, const float *X_b, const int64_t *off_b,
                                int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
                                int64_t *tie, double *z, int n_threads);
+/* m6a_site_ks and m6a_site_signal_ks (include/m6a.h state the operation) on the host: the two Kolmogorov-Smirnov integers and the two
+ * medians per pair (per pair and column: X_* [off_*[n_sites_*]][9], outputs [n_pairs][9]), the kernels' bits -- both sides compile
+ * m6anet_amd/csrc/m6a_ks.h, which counts a pair from sorted copies of its two bags.  d_pos and d_neg are required, med_a and med_b may
+ * each be NULL; everything else -- arguments, errors with the outputs untouched, threading -- is m6a_io_site_ranksum's. */
+int m6a_io_site_ks(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,
+                   int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *d_pos, int64_t *d_neg,
+                   double *med_a, double *med_b, int n_threads);
+int m6a_io_site_signal_ks(const float *X_a, const int64_t *off_a, int64_t n_sites_a, const float *X_b, const int64_t *off_b,
+                          int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *d_pos, int64_t *d_neg,
+                          double *med_a, double *med_b, int n_threads);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,8 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_save_store", "m6a_io_open_store", "m6a_io_store_tag", "m6a_io_dataprep", "m6a_io_dataprep_rows", "m6a_io_rows_table",
            "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_sites_set_read_names", "m6a_io_uuid_parse", "m6a_io_uuid_format", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
            "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk",
-           "m6a_io_norm_factors", "m6a_io_norm_partials", "m6a_io_site_ranksum", "m6a_io_site_signal_ranksum"]
+           "m6a_io_norm_factors", "m6a_io_norm_partials", "m6a_io_site_ranksum", "m6a_io_site_signal_ranksum", "m6a_io_site_ks",
+           "m6a_io_site_signal_ks"]
 _lib = None
 
 
@@ -120,6 +121,8 @@ def load():
     L.m6a_io_norm_partials.argtypes = [C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
     L.m6a_io_site_ranksum.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
     L.m6a_io_site_signal_ranksum.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
+    L.m6a_io_site_ks.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
+    L.m6a_io_site_signal_ks.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
     _lib = L
     return L
 

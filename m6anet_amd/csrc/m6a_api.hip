@@ -1103,6 +1103,8 @@ int deferred_error(m6a_ctx *c)
         if (e == 4) return fail(c, M6A_EHIP, "pool_rtab_kernel: the dynamic LDS block does not start at offset 0");
         if (e == 5) return fail(c, M6A_EINVAL, "m6a_site_ranksum: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
         if (e == 6) return fail(c, M6A_EINVAL, "m6a_site_signal_ranksum: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
+        if (e == 7) return fail(c, M6A_EINVAL, "m6a_site_ks: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
+        if (e == 8) return fail(c, M6A_EINVAL, "m6a_site_signal_ks: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
         if (e == 3) return fail(c, M6A_EINVAL, "the host offsets given to m6a_set_host_offsets differ from the device off[] of the call");
         return fail(c, M6A_ESTREAM, "MT19937 stream too short for a flush group");
     }

@@ -5,6 +5,7 @@
 #include "m6a_repr.h"
 #include "m6a_uuid.h"
 #include "m6a_ranksum.h"
+#include "m6a_ks.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -2748,4 +2749,71 @@ extern "C" int m6a_io_site_signal_ranksum(const float *X_a, const int64_t *off_a
     } catch (const std::bad_alloc &) {
         return fail(M6A_IO_ENOMEM, "out of memory");
     }
+}
+
+// ---- m6a_io_site_ks, m6a_io_site_signal_ks: include/m6a.h's m6a_site_ks and m6a_site_signal_ks on the host (the core is m6a_ks.h, which
+// the kernels' unit compiles too); a bag's element is C float32 (1: a value, 9: a row of X) and a pair's output C values
+static int site_ks_on_host(int C, const float *v_a, const int64_t *off_a, int64_t n_sites_a, const float *v_b, const int64_t *off_b,
+                           int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *d_pos, int64_t *d_neg,
+                           double *med_a, double *med_b, int n_threads)
+{
+    if (n_sites_a < 0 || n_sites_b < 0 || n_pairs < 0) return fail(M6A_IO_EINVAL, "n_sites_a, n_sites_b and n_pairs must be >= 0");
+    if (!n_pairs) return M6A_IO_OK;
+    if ((!pair_a || !pair_b) && (n_pairs != n_sites_a || n_pairs != n_sites_b))
+        return fail(M6A_IO_EINVAL, "a NULL pair array is the identity and needs n_pairs == n_sites_a == n_sites_b");
+    if (!v_a || !off_a || !v_b || !off_b || !d_pos || !d_neg) return fail(M6A_IO_EINVAL, "null argument");
+    const int64_t *offs[2] = {off_a, off_b};
+    const int64_t ns[2] = {n_sites_a, n_sites_b};
+    for (int side = 0; side < 2; side++) {
+        if (offs[side][0] != 0) return fail(M6A_IO_EINVAL, "off[0] must be 0");
+        for (int64_t s = 0; s < ns[side]; s++)
+            if (offs[side][s + 1] < offs[side][s]) return fail(M6A_IO_EINVAL, "off[] must be non-decreasing");
+    }
+    for (int64_t k = 0; k < n_pairs; k++)
+        if ((pair_a && (pair_a[k] < 0 || pair_a[k] >= n_sites_a)) || (pair_b && (pair_b[k] < 0 || pair_b[k] >= n_sites_b)))
+            return fail(M6A_IO_EINVAL, "pair %lld names a site outside its set", (long long)k);
+    try {
+        const int nw = n_workers(n_threads, n_pairs);
+        std::atomic<bool> no_mem{false};
+        auto work = [&](int w) {
+            try {
+                std::vector<float> ga, gb, sa, sb;
+                for (int64_t k = n_pairs * w / nw; k < n_pairs * (w + 1) / nw; k++) {
+                    const int64_t ia = pair_a ? pair_a[k] : k, ib = pair_b ? pair_b[k] : k;
+                    for (int c = 0; c < C; c++) {
+                        const m6a_ks::Result r = m6a_ks::count_column(v_a + off_a[ia] * C, off_a[ia + 1] - off_a[ia], v_b + off_b[ib] * C,
+                                                                      off_b[ib + 1] - off_b[ib], c, C, ga, gb, sa, sb);
+                        d_pos[k * C + c] = r.d_pos;
+                        d_neg[k * C + c] = r.d_neg;
+                        if (med_a) med_a[k * C + c] = r.med_a;
+                        if (med_b) med_b[k * C + c] = r.med_b;
+                    }
+                }
+            } catch (const std::bad_alloc &) {
+                no_mem = true;
+            }
+        };
+        std::vector<std::thread> th;
+        for (int w = 1; w < nw; w++) th.emplace_back(work, w);
+        work(0);
+        for (auto &t : th) t.join();
+        if (no_mem) return fail(M6A_IO_ENOMEM, "out of memory");
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory");
+    }
+}
+
+extern "C" int m6a_io_site_ks(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,
+                              int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *d_pos,
+                              int64_t *d_neg, double *med_a, double *med_b, int n_threads)
+{
+    return site_ks_on_host(1, prob_a, off_a, n_sites_a, prob_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b, n_threads);
+}
+
+extern "C" int m6a_io_site_signal_ks(const float *X_a, const int64_t *off_a, int64_t n_sites_a, const float *X_b, const int64_t *off_b,
+                                     int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *d_pos,
+                                     int64_t *d_neg, double *med_a, double *med_b, int n_threads)
+{
+    return site_ks_on_host(9, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b, n_threads);   // M6A_N_FEATURES: the row of X
 }

@@ -487,6 +487,54 @@ class M6ANetEngine:
         self._chk(self._L.m6a_site_signal_ranksum(self._h, X_a, off_a, int(n_sites_a), X_b, off_b, int(n_sites_b), pair_a, pair_b,
                                                   int(n_pairs), gt, eq, tie, z))
 
+    def _site_ks(self, cols, v_a, off_a, v_b, off_b, pair_a, pair_b):
+        if (pair_a is None) != (pair_b is None):
+            raise ValueError("pair_a and pair_b are given together or not at all")
+        aVa, aOa = _Arg(v_a, np.float32, "float32"), _Arg(off_a, np.int64, "int64")
+        aVb, aOb = _Arg(v_b, np.float32, "float32"), _Arg(off_b, np.int64, "int64")
+        if aVa.size % cols or aVb.size % cols:                   # (cols is 1 or 9)
+            raise ValueError("X_a and X_b hold nine float32 per read")
+        Sa, Sb = aOa.size - 1, aOb.size - 1
+        aIa = _Arg(pair_a, np.int64, "int64") if pair_a is not None else None
+        aIb = _Arg(pair_b, np.int64, "int64") if pair_b is not None else None
+        if aIa is not None and aIa.size != aIb.size:
+            raise ValueError("pair_a and pair_b must have one entry per pair")
+        if aIa is None and Sa != Sb:
+            raise ValueError("without pair_a / pair_b the two sets must have the same number of sites")
+        P = aIa.size if aIa is not None else Sa
+        out = [self._out(aVa.is_dev, P * cols, np.int64, "int64") for _ in range(2)] + \
+              [self._out(aVa.is_dev, P * cols, np.float64, "float64") for _ in range(2)]
+        ptrs = [_Arg(o, dt, name).ptr for o, dt, name in zip(out, (np.int64,) * 2 + (np.float64,) * 2, ("int64",) * 2 + ("float64",) * 2)]
+        call = self.site_ks_ptrs if cols == 1 else self.site_signal_ks_ptrs
+        call(aVa.ptr, aOa.ptr, Sa, aVb.ptr, aOb.ptr, Sb, aIa.ptr if aIa else None, aIb.ptr if aIb else None, P, *ptrs)
+        return tuple(out) if cols == 1 else tuple(o.reshape(P, cols) for o in out)
+
+    def site_ks(self, read_probs_a, off_a, read_probs_b, off_b, pair_a=None, pair_b=None):
+        """The Kolmogorov-Smirnov integers and the medians of pairs of sites (include/m6a.h: m6a_site_ks), shaped like site_ranksum:
+        NumPy arrays (synchronous) or torch tensors on the GPU (queued: `sync()` before reading), all of one kind.  Returns (d_pos,
+        d_neg int64 [P], med_a, med_b float64 [P]); an undefined pair -- an empty bag, a NaN, more than 2^20 pooled reads -- is
+        (-1, -1, NaN, NaN).  m6anet_amd/ranksum.py turns them into D, its sign, p and q."""
+        return self._site_ks(1, read_probs_a, off_a, read_probs_b, off_b, pair_a, pair_b)
+
+    def site_ks_ptrs(self, prob_a, off_a, n_sites_a, prob_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b):
+        """m6a_site_ks on raw addresses (ints) the caller owns, as site_ranksum_ptrs is m6a_site_ranksum on them: all host or all device;
+        pair_a / pair_b and med_a / med_b may be None.  With device pointers the call is queued on the context's stream: `sync()`
+        before the outputs are read."""
+        self._chk(self._L.m6a_site_ks(self._h, prob_a, off_a, int(n_sites_a), prob_b, off_b, int(n_sites_b), pair_a, pair_b,
+                                      int(n_pairs), d_pos, d_neg, med_a, med_b))
+
+    def site_signal_ks(self, X_a, off_a, X_b, off_b, pair_a=None, pair_b=None):
+        """site_ks on each of the nine signal features (include/m6a.h: m6a_site_signal_ks), shaped like site_signal_ranksum: X_a [Ra, 9]
+        and X_b [Rb, 9] with off_* in rows.  Returns (d_pos, d_neg int64 [P, 9], med_a, med_b float64 [P, 9]), the medians in the
+        normalised units of X; a NaN leaves its own column of the pair undefined, an empty bag or more than 2^20 pooled reads all nine."""
+        return self._site_ks(9, X_a, off_a, X_b, off_b, pair_a, pair_b)
+
+    def site_signal_ks_ptrs(self, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b):
+        """m6a_site_signal_ks on raw addresses (ints) the caller owns, as site_ks_ptrs is m6a_site_ks on them; the outputs hold nine
+        values per pair."""
+        self._chk(self._L.m6a_site_signal_ks(self._h, X_a, off_a, int(n_sites_a), X_b, off_b, int(n_sites_b), pair_a, pair_b,
+                                             int(n_pairs), d_pos, d_neg, med_a, med_b))
+
     def infer(self, X, site_kmers, off, n_iters, n_samples=N_SAMPLES,
               read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16, save_per_batch=2,
               want_read_probs=True, out=None):

@@ -7,7 +7,13 @@ only.
   bh          Benjamini-Hochberg q over the rows whose p is not NaN: stable order by p, q_(i) = min(1, min_{j >= i} p_(j) M / j)
   join        the inner join of two site tables on (transcript_id, transcript_position), in the order of the first table
   diff_rows   the lines of data.diff.csv
-  signal_rows the lines of data.diff_signal.csv (`eventalign_diff --signal`; m6a_site_signal_ranksum): nine per pair, one BH family"""
+  signal_rows the lines of data.diff_signal.csv (`eventalign_diff --signal`; m6a_site_signal_ranksum): nine per pair, one BH family
+What follows from the Kolmogorov-Smirnov integers and the medians of m6a_site_ks / m6a_site_signal_ks (`eventalign_diff --ks`):
+  ks_d        D = max(d_pos, d_neg) / (n m), scipy.stats.ks_2samp's statistic; NaN for an undefined pair
+  ks_sign     +1 where d_pos >= d_neg (the first bag's CDF lies above at the widest gap: its values tend lower), else -1; 0: undefined
+  ks_p_value  Q(lambda), lambda = sqrt(n m / (n + m)) D, Q the Kolmogorov limit distribution: scipy.stats.kstwobign.sf(lambda), NOT
+              ks_2samp's p (exact for small bags); the limit is conservative for small bags.  The exact small-sample p is not built.
+  ks_rows     the lines of data.diff_ks.csv;  signal_ks_rows  those of data.diff_signal_ks.csv, nine per pair, one BH family"""
 import math
 
 import numpy as np
@@ -21,6 +27,12 @@ SIGNAL_FILE = "data.diff_signal.csv"
 # (m6anet/utils/dataprep_utils.py:132) and positions -1, 0, +1 (the loader's left, centre and right indices)
 SIGNAL_COLUMNS = tuple((o, f) for o in (-1, 0, 1) for f in ("dwell_time", "norm_std", "norm_mean"))
 N_SIGNAL = len(SIGNAL_COLUMNS)
+KS_HEADER = "transcript_id,transcript_position,kmer,n_reads_a,n_reads_b,median_a,median_b,median_shift,ks_d,ks_sign,p_value,q_value"
+KS_FILE = "data.diff_ks.csv"
+SIGNAL_KS_HEADER = ("transcript_id,transcript_position,kmer,n_reads_a,n_reads_b,position_offset,feature,median_a,median_b,median_shift,"
+                    "ks_d,ks_sign,p_value,q_value")
+SIGNAL_KS_FILE = "data.diff_signal_ks.csv"
+KS_SWITCH = 1.18                        # lambda below it: the theta-function form of Q; seven terms of either series
 _SQRT2 = math.sqrt(2.0)
 
 
@@ -107,3 +119,85 @@ def signal_rows(tx, pos, kmer, n_a, n_b, gt, eq, z):
 
 def signal_text(*columns):
     return SIGNAL_HEADER + "\n" + "".join(signal_rows(*columns))
+
+
+def ks_d(d_pos, d_neg, n, m):
+    d_pos, d_neg = np.asarray(d_pos, np.int64), np.asarray(d_neg, np.int64)
+    nm = np.asarray(n, np.float64) * np.asarray(m, np.float64)
+    out = np.full(d_pos.shape, np.nan)
+    ok = d_pos >= 0
+    out[ok] = np.maximum(d_pos, d_neg)[ok].astype(np.float64) / nm[ok]
+    return out
+
+
+def ks_sign(d_pos, d_neg):
+    d_pos, d_neg = np.asarray(d_pos, np.int64), np.asarray(d_neg, np.int64)
+    return np.where(d_pos < 0, 0, np.where(d_pos >= d_neg, 1, -1)).astype(np.int64)
+
+
+def kolmogorov_sf(lam):
+    """Q(lambda) = 2 sum_{k>=1} (-1)^(k-1) exp(-2 k^2 lambda^2); below KS_SWITCH its theta-function form
+    1 - sqrt(2 pi) / lambda sum_{k>=1} exp(-(2k-1)^2 pi^2 / (8 lambda^2)), whose terms fall off as fast there.  Seven terms of either."""
+    if math.isnan(lam):
+        return lam
+    if lam <= 0.0:
+        return 1.0
+    if lam < KS_SWITCH:
+        c = math.pi * math.pi / (8.0 * lam * lam)
+        return 1.0 - math.sqrt(2.0 * math.pi) / lam * sum(math.exp(-float((2 * k - 1) ** 2) * c) for k in range(1, 8))
+    return 2.0 * sum((1.0 if k % 2 else -1.0) * math.exp(-2.0 * float(k * k) * lam * lam) for k in range(1, 8))
+
+
+def ks_lambda(d, n, m):
+    return math.sqrt(float(n) * float(m) / float(n + m)) * d
+
+
+def ks_p_value(d, n, m):
+    """d = ks_d(...), n and m the bag sizes, arrays of one shape -> p, NaN where d is NaN"""
+    d = np.asarray(d, np.float64)
+    n, m = np.broadcast_to(np.asarray(n, np.int64), d.shape), np.broadcast_to(np.asarray(m, np.int64), d.shape)
+    return np.array([float("nan") if math.isnan(v) else kolmogorov_sf(ks_lambda(v, int(i), int(j)))
+                     for v, i, j in zip(d.ravel().tolist(), n.ravel().tolist(), m.ravel().tolist())], np.float64).reshape(d.shape)
+
+
+def _ks_fields(d_pos, d_neg, med_a, med_b, n_a, n_b):
+    """per test, flat: the seven strings median_a .. q_value; one BH family over all of them"""
+    d_pos, d_neg = np.asarray(d_pos, np.int64).ravel(), np.asarray(d_neg, np.int64).ravel()
+    med_a, med_b = np.asarray(med_a, np.float64).ravel(), np.asarray(med_b, np.float64).ravel()
+    d = ks_d(d_pos, d_neg, n_a, n_b)
+    sign = ks_sign(d_pos, d_neg)
+    p = ks_p_value(d, n_a, n_b)
+    q = bh(p)
+    with np.errstate(invalid="ignore"):
+        shift = med_a - med_b                                    # inf - inf: NaN
+    return [(_repr(float(med_a[k])), _repr(float(med_b[k])), _repr(float(shift[k])), _repr(float(d[k])), "%d" % sign[k] if sign[k] else "nan",
+             _repr(float(p[k])), _repr(float(q[k]))) for k in range(d.size)]
+
+
+def ks_rows(tx, pos, kmer, n_a, n_b, d_pos, d_neg, med_a, med_b):
+    """The data lines of data.diff_ks.csv (no header, each with its newline) for P pairs: tx, pos, kmer, n_a, n_b as diff_rows takes them
+    and the four outputs [P] of m6a_site_ks.  median_shift = median_a - median_b; floats are repr(float), ks_sign is 1 or -1, and an
+    undefined pair is `nan` in all seven; q_value is Benjamini-Hochberg over the rows whose p is not NaN."""
+    n_a, n_b = np.asarray(n_a, np.int64).ravel(), np.asarray(n_b, np.int64).ravel()
+    f = _ks_fields(d_pos, d_neg, med_a, med_b, n_a, n_b)
+    return ["%s,%d,%s,%d,%d,%s\n" % (tx[k], pos[k], kmer[k], n_a[k], n_b[k], ",".join(f[k])) for k in range(len(f))]
+
+
+def ks_text(*columns):
+    return KS_HEADER + "\n" + "".join(ks_rows(*columns))
+
+
+def signal_ks_rows(tx, pos, kmer, n_a, n_b, d_pos, d_neg, med_a, med_b):
+    """The data lines of data.diff_signal_ks.csv for P pairs and the four outputs [P, 9] of m6a_site_signal_ks: nine lines per pair in
+    column order, SIGNAL_COLUMNS naming the column, the medians in the normalised units of X; q_value is Benjamini-Hochberg over all
+    9 P rows whose p is not NaN, one family."""
+    n_a, n_b = np.asarray(n_a, np.int64).ravel(), np.asarray(n_b, np.int64).ravel()
+    P = n_a.size
+    f = _ks_fields(d_pos, d_neg, med_a, med_b, np.repeat(n_a, N_SIGNAL), np.repeat(n_b, N_SIGNAL))
+    assert len(f) == P * N_SIGNAL
+    return ["%s,%d,%s,%d,%d,%d,%s,%s\n" % (tx[k], pos[k], kmer[k], n_a[k], n_b[k], SIGNAL_COLUMNS[c][0], SIGNAL_COLUMNS[c][1],
+                                          ",".join(f[k * N_SIGNAL + c])) for k in range(P) for c in range(N_SIGNAL)]
+
+
+def signal_ks_text(*columns):
+    return SIGNAL_KS_HEADER + "\n" + "".join(signal_ks_rows(*columns))

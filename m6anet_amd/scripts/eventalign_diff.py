@@ -7,7 +7,13 @@ writes for the condition, byte for byte.
 With --signal one more launch follows (include/m6a.h: m6a_site_signal_ranksum): the same test on each of the nine columns of the two
 handles' X -- dwell_time, norm_std and norm_mean at positions -1, 0, +1 -- with the same pair indices, 288 bytes per pair come back,
 and OUT/data.diff_signal.csv holds nine rows per shared site, in data.diff.csv's order of sites and X's order of columns.  Its q_value is
-Benjamini-Hochberg over all rows of that file, nine tests per site in one family.  Every other file keeps its bytes."""
+Benjamini-Hochberg over all rows of that file, nine tests per site in one family.  Every other file keeps its bytes.
+With --ks the two-sample Kolmogorov-Smirnov test and the medians follow the rank-sum launch (include/m6a.h: m6a_site_ks) with the same
+pair indices on the two read_prob arrays: 32 bytes per pair come back (d_pos, d_neg, med_a, med_b) and OUT/data.diff_ks.csv holds
+median_a, median_b, median_shift = median_a - median_b, ks_d, ks_sign, p_value and q_value per shared site.  p_value is the Kolmogorov
+limit distribution at sqrt(n m / (n + m)) D, conservative for small bags; the exact small-sample p-value is not built.  With --signal
+--ks m6a_site_signal_ks also runs on the two X and OUT/data.diff_signal_ks.csv holds nine rows per site, one Benjamini-Hochberg
+family, its medians in the normalised units of X (their conversion to pA is not built).  Every other file keeps its bytes."""
 import os
 import pathlib
 import sys
@@ -35,6 +41,12 @@ def argparser():
                         help="also write data.diff_signal.csv: the rank-sum test on each of the nine signal features of a shared site "
                              "(dwell_time, norm_std, norm_mean at positions -1, 0, +1), the model-free comparison.  Nine rows per site; "
                              "q_value is Benjamini-Hochberg over all rows of that file, nine tests per site in one family.")
+    parser.add_argument("--ks", action="store_true",
+                        help="also write data.diff_ks.csv: per shared site the medians of the two conditions' read probabilities, their "
+                             "difference median_a - median_b, and the two-sample Kolmogorov-Smirnov statistic with its sign, the p-value of "
+                             "the Kolmogorov limit distribution (conservative for small bags; not scipy.stats.ks_2samp's exact p) and its "
+                             "Benjamini-Hochberg q_value.  With --signal also data.diff_signal_ks.csv: the same on each of the nine signal "
+                             "features, medians in normalised units, nine rows per site in one family.")
     return inference.add_site_proba(parser)
 
 
@@ -118,6 +130,30 @@ def compare_signal(engine, sites_a, sites_b, pair_a, pair_b):
     return gt.cpu().numpy(), eq.cpu().numpy(), z.cpu().numpy()
 
 
+def compare_ks(engine, sites_a, sites_b, pair_a, pair_b, signal=False):
+    """m6a_site_ks on the two handles' read_prob (signal: m6a_site_signal_ks on their X) where they lie: the pair indices go up,
+    (d_pos, d_neg, med_a, med_b), each [P] or [P, 9], come back"""
+    import numpy as np
+    import torch
+    P = int(pair_a.size)
+    shape = (P, 9) if signal else (P,)
+    if P == 0:
+        return (np.zeros(shape, np.int64),) * 2 + (np.zeros(shape, np.float64),) * 2
+    dev = "cuda:%d" % engine.device
+    ia, ib = torch.from_numpy(pair_a).to(dev), torch.from_numpy(pair_b).to(dev)      # pageable memory: the copies are done on return
+    out = [torch.empty(shape, dtype=dt, device=dev) for dt in (torch.int64, torch.int64, torch.float64, torch.float64)]
+    torch.cuda.synchronize(engine.device)
+    a, b = sites_a.info, sites_b.info
+    if signal:
+        engine.site_signal_ks_ptrs(a.X, a.off, sites_a.n_sites, b.X, b.off, sites_b.n_sites, ia.data_ptr(), ib.data_ptr(), P,
+                                   *[o.data_ptr() for o in out])
+    else:
+        engine.site_ks_ptrs(a.read_prob, a.off, sites_a.n_sites, b.read_prob, b.off, sites_b.n_sites, ia.data_ptr(), ib.data_ptr(), P,
+                            *[o.data_ptr() for o in out])
+    engine.sync()
+    return tuple(o.cpu().numpy() for o in out)
+
+
 def main(args):
     import threading
 
@@ -168,12 +204,22 @@ def main(args):
                                  site_a[pair_a], site_b[pair_b], mod_a[pair_a], mod_b[pair_b], gt, eq, z)
         with open(os.path.join(args.out_dir, ranksum.DIFF_FILE), "w") as f:
             f.write(text)
+        if args.ks:
+            text = ranksum.ks_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b],
+                                   *compare_ks(engine, sa, sb, pair_a, pair_b))
+            with open(os.path.join(args.out_dir, ranksum.KS_FILE), "w") as f:
+                f.write(text)
         if args.signal:
             gt, eq, z = compare_signal(engine, sa, sb, pair_a, pair_b)
             text = ranksum.signal_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b],
                                        gt, eq, z)
             with open(os.path.join(args.out_dir, ranksum.SIGNAL_FILE), "w") as f:
                 f.write(text)
+            if args.ks:
+                text = ranksum.signal_ks_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a],
+                                              np.diff(sb.off)[pair_b], *compare_ks(engine, sa, sb, pair_a, pair_b, signal=True))
+                with open(os.path.join(args.out_dir, ranksum.SIGNAL_KS_FILE), "w") as f:
+                    f.write(text)
         print("eventalign_diff: %d sites in both conditions, %d only in A, %d only in B"
               % (pair_a.size, sa.n_sites - pair_a.size, sb.n_sites - np.unique(pair_b).size), flush=True)
     finally:

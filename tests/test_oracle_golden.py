@@ -38,7 +38,7 @@ def test_choice_known_answers(golden):
     assert np.array_equal(np.concatenate(seq), g["choice_seed42_seq_20_33_1_64_21"])
 
 
-@pytest.mark.parametrize("n", [2, 7, 20, 31, 32, 33, 100, 257, 999])
+@pytest.mark.parametrize("n", [2, 7, 20, 31, 32, 33, 100, 257, 999, 65535, 65536, 65537, 70000, 131073])
 def test_choice_against_live_numpy(n):
     np.random.seed(123)
     want = np.random.choice(np.arange(n), 5000, replace=True)

@@ -1101,10 +1101,10 @@ int deferred_error(m6a_ctx *c)
         *c->h_err = 0;
         if (e == 2) return fail(c, M6A_EINVAL, "encoder: a 32-read tile spans more than 3 sites (bag < 16 reads) in the 12-slot kernel");
         if (e == 4) return fail(c, M6A_EHIP, "pool_rtab_kernel: the dynamic LDS block does not start at offset 0");
-        if (e == 5) return fail(c, M6A_EINVAL, "m6a_site_ranksum: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
-        if (e == 6) return fail(c, M6A_EINVAL, "m6a_site_signal_ranksum: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
-        if (e == 7) return fail(c, M6A_EINVAL, "m6a_site_ks: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
-        if (e == 8) return fail(c, M6A_EINVAL, "m6a_site_signal_ks: a pair index outside its set, or offsets that decrease or leave their set, in device arrays");
+        if (e >= 5 && e <= 8) {                                 // the four pair kernels (m6a_pairs.h), each with a code of its own
+            static const char *const entry[4] = {"m6a_site_ranksum", "m6a_site_signal_ranksum", "m6a_site_ks", "m6a_site_signal_ks"};
+            return fail(c, M6A_EINVAL, "%s: a pair index outside its set, or offsets that decrease or leave their set, in device arrays", entry[e - 5]);
+        }
         if (e == 3) return fail(c, M6A_EINVAL, "the host offsets given to m6a_set_host_offsets differ from the device off[] of the call");
         return fail(c, M6A_ESTREAM, "MT19937 stream too short for a flush group");
     }

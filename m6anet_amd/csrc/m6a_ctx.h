@@ -4,8 +4,9 @@
 //   m6a_job.hip        the streaming job (m6a_job_begin / feed / end): the reference's batch loop fed as the loader produces it
 //   m6a_comm.hip       RCCL bound at run time, m6a_comm_*, m6a_gather, m6a_gather_reads, m6a_device_link
 //   m6a_expect.hip     the closed-form site probability: site_expect_kernel (its launches are in m6a_api.hip)
-//   m6a_ranksum.hip    m6a_site_ranksum: the rank-sum test between two sets of sites, its kernel and its launch
-//   m6a_ks.hip         m6a_site_ks, m6a_site_signal_ks: the Kolmogorov-Smirnov integers and the medians of pairs of sites, kernels and launch
+//   m6a_ranksum.hip    m6a_site_ranksum, m6a_site_signal_ranksum: the rank-sum test between two sets of sites, its kernels
+//   m6a_ks.hip         m6a_site_ks, m6a_site_signal_ks: the Kolmogorov-Smirnov integers and the medians of pairs of sites, its kernels
+//                      (m6a_pairs.h: what the two units share -- the pair header, the tile fills, the launch and the entry point)
 //   m6a_validate.hip   validation forward: the without-replacement sampler on host threads, m6a_validate / m6a_validate_pool
 //   m6a_train.hip      the trainer (m6a_train_*): its kernels, its scratch and the calls around them
 // What every entry point with data pointers obeys -- all host or all device -- is stated once, below: enter, same_side, csr_check,
@@ -288,7 +289,7 @@ struct m6a_ctx {
     int site_mode = M6A_SITE_SAMPLED;         // m6a_set_site_mode: what site_prob means in pool / infer / job_end
     std::atomic<bool> warm_cancel{false};     // the background set-up stops at its next step (the mode went to M6A_SITE_EXPECTED)
     DevBuf sSigma;                            // host-pointer m6a_site_expectation: mc_sigma [S]
-    DevBuf sRank[10];                         // host-pointer m6a_site_ranksum: its six inputs and four outputs (m6a_ranksum.hip; m6a_ks.hip stages in them too)
+    DevBuf sRank[10];                         // the host-pointer calls on pairs of sites: their six inputs and four outputs (pair_call, m6a_pairs.h)
     DevBuf sRepr;                             // host-pointer m6a_read_representation: one chunk of repr [chunk reads][32]
 };
 

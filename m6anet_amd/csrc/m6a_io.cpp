@@ -2648,16 +2648,23 @@ extern "C" int m6a_io_norm_factors(const char *json_path, int64_t n_sites, const
     }
 }
 
-// ---- m6a_io_site_ranksum: include/m6a.h's m6a_site_ranksum on the host (the core is m6a_ranksum.h, which the kernels' unit compiles too)
-extern "C" int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,
-                                   int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
-                                   int64_t *tie, double *z, int n_threads)
+// ---- m6a_io_site_ranksum, m6a_io_site_signal_ranksum, m6a_io_site_ks, m6a_io_site_signal_ks: include/m6a.h's four calls on pairs of
+// sites on the host (the cores are m6a_ranksum.h and m6a_ks.h, which the kernels' units compile too).  A bag's element is C float32 (1: a
+// value, 9: a row of X) and a pair's output C values.  What the four share is here: the refusals, the split of the pairs over the
+// workers and the out-of-memory handling; count(at, a, n, b, m, c, scratch) counts column c of one pair's bags a [n][C] and b [m][C]
+// and stores the result at [at]
+namespace { struct PairScratch { std::vector<float> ga, gb, sa, sb; }; }
+
+template <class Count>
+static int site_pairs_on_host(int C, const float *v_a, const int64_t *off_a, int64_t n_sites_a, const float *v_b, const int64_t *off_b,
+                              int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, bool outputs_given, int n_threads,
+                              Count count)
 {
     if (n_sites_a < 0 || n_sites_b < 0 || n_pairs < 0) return fail(M6A_IO_EINVAL, "n_sites_a, n_sites_b and n_pairs must be >= 0");
     if (!n_pairs) return M6A_IO_OK;
     if ((!pair_a || !pair_b) && (n_pairs != n_sites_a || n_pairs != n_sites_b))
         return fail(M6A_IO_EINVAL, "a NULL pair array is the identity and needs n_pairs == n_sites_a == n_sites_b");
-    if (!prob_a || !off_a || !prob_b || !off_b || !z) return fail(M6A_IO_EINVAL, "null argument");
+    if (!v_a || !off_a || !v_b || !off_b || !outputs_given) return fail(M6A_IO_EINVAL, "null argument");
     const int64_t *offs[2] = {off_a, off_b};
     const int64_t ns[2] = {n_sites_a, n_sites_b};
     for (int side = 0; side < 2; side++) {
@@ -2673,15 +2680,11 @@ extern "C" int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, in
         std::atomic<bool> no_mem{false};
         auto work = [&](int w) {
             try {
-                std::vector<float> sa, sb;
+                PairScratch scratch;
                 for (int64_t k = n_pairs * w / nw; k < n_pairs * (w + 1) / nw; k++) {
                     const int64_t ia = pair_a ? pair_a[k] : k, ib = pair_b ? pair_b[k] : k;
-                    const m6a_ranksum::Result r = m6a_ranksum::count(prob_a + off_a[ia], off_a[ia + 1] - off_a[ia], prob_b + off_b[ib],
-                                                                     off_b[ib + 1] - off_b[ib], sa, sb);
-                    if (gt) gt[k] = r.gt;
-                    if (eq) eq[k] = r.eq;
-                    if (tie) tie[k] = r.tie;
-                    z[k] = r.z;
+                    for (int c = 0; c < C; c++)
+                        count(k * C + c, v_a + off_a[ia] * C, off_a[ia + 1] - off_a[ia], v_b + off_b[ib] * C, off_b[ib + 1] - off_b[ib], c, scratch);
                 }
             } catch (const std::bad_alloc &) {
                 no_mem = true;
@@ -2698,110 +2701,49 @@ extern "C" int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, in
     }
 }
 
-// ---- m6a_io_site_signal_ranksum: include/m6a.h's m6a_site_signal_ranksum on the host, a column of either bag gathered and counted at a time
-extern "C" int m6a_io_site_signal_ranksum(const float *X_a, const int64_t *off_a, int64_t n_sites_a, const float *X_b, const int64_t *off_b,
-                                          int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt,
-                                          int64_t *eq, int64_t *tie, double *z, int n_threads)
+// the rank-sum calls: z is required; C == 1 counts the bags where they lie, C == 9 a gathered column of either at a time
+static int site_ranksum_on_host(int C, const float *v_a, const int64_t *off_a, int64_t n_sites_a, const float *v_b, const int64_t *off_b,
+                                int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
+                                int64_t *tie, double *z, int n_threads)
 {
-    constexpr int C = 9;                                      // M6A_N_FEATURES: the row of X
-    if (n_sites_a < 0 || n_sites_b < 0 || n_pairs < 0) return fail(M6A_IO_EINVAL, "n_sites_a, n_sites_b and n_pairs must be >= 0");
-    if (!n_pairs) return M6A_IO_OK;
-    if ((!pair_a || !pair_b) && (n_pairs != n_sites_a || n_pairs != n_sites_b))
-        return fail(M6A_IO_EINVAL, "a NULL pair array is the identity and needs n_pairs == n_sites_a == n_sites_b");
-    if (!X_a || !off_a || !X_b || !off_b || !z) return fail(M6A_IO_EINVAL, "null argument");
-    const int64_t *offs[2] = {off_a, off_b};
-    const int64_t ns[2] = {n_sites_a, n_sites_b};
-    for (int side = 0; side < 2; side++) {
-        if (offs[side][0] != 0) return fail(M6A_IO_EINVAL, "off[0] must be 0");
-        for (int64_t s = 0; s < ns[side]; s++)
-            if (offs[side][s + 1] < offs[side][s]) return fail(M6A_IO_EINVAL, "off[] must be non-decreasing");
-    }
-    for (int64_t k = 0; k < n_pairs; k++)
-        if ((pair_a && (pair_a[k] < 0 || pair_a[k] >= n_sites_a)) || (pair_b && (pair_b[k] < 0 || pair_b[k] >= n_sites_b)))
-            return fail(M6A_IO_EINVAL, "pair %lld names a site outside its set", (long long)k);
-    try {
-        const int nw = n_workers(n_threads, n_pairs);
-        std::atomic<bool> no_mem{false};
-        auto work = [&](int w) {
-            try {
-                std::vector<float> ga, gb, sa, sb;
-                for (int64_t k = n_pairs * w / nw; k < n_pairs * (w + 1) / nw; k++) {
-                    const int64_t ia = pair_a ? pair_a[k] : k, ib = pair_b ? pair_b[k] : k;
-                    for (int c = 0; c < C; c++) {
-                        const m6a_ranksum::Result r = m6a_ranksum::count_column(X_a + off_a[ia] * C, off_a[ia + 1] - off_a[ia], X_b + off_b[ib] * C,
-                                                                                off_b[ib + 1] - off_b[ib], c, C, ga, gb, sa, sb);
-                        if (gt) gt[k * C + c] = r.gt;
-                        if (eq) eq[k * C + c] = r.eq;
-                        if (tie) tie[k * C + c] = r.tie;
-                        z[k * C + c] = r.z;
-                    }
-                }
-            } catch (const std::bad_alloc &) {
-                no_mem = true;
-            }
-        };
-        std::vector<std::thread> th;
-        for (int w = 1; w < nw; w++) th.emplace_back(work, w);
-        work(0);
-        for (auto &t : th) t.join();
-        if (no_mem) return fail(M6A_IO_ENOMEM, "out of memory");
-        return M6A_IO_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(M6A_IO_ENOMEM, "out of memory");
-    }
+    return site_pairs_on_host(C, v_a, off_a, n_sites_a, v_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, z != nullptr, n_threads,
+                              [=](int64_t at, const float *a, int64_t n, const float *b, int64_t m, int c, PairScratch &s) {
+                                  const m6a_ranksum::Result r = C == 1 ? m6a_ranksum::count(a, n, b, m, s.sa, s.sb)
+                                                                       : m6a_ranksum::count_column(a, n, b, m, c, C, s.ga, s.gb, s.sa, s.sb);
+                                  if (gt) gt[at] = r.gt;
+                                  if (eq) eq[at] = r.eq;
+                                  if (tie) tie[at] = r.tie;
+                                  z[at] = r.z;
+                              });
 }
 
-// ---- m6a_io_site_ks, m6a_io_site_signal_ks: include/m6a.h's m6a_site_ks and m6a_site_signal_ks on the host (the core is m6a_ks.h, which
-// the kernels' unit compiles too); a bag's element is C float32 (1: a value, 9: a row of X) and a pair's output C values
+// the Kolmogorov-Smirnov calls: d_pos and d_neg are required
 static int site_ks_on_host(int C, const float *v_a, const int64_t *off_a, int64_t n_sites_a, const float *v_b, const int64_t *off_b,
                            int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *d_pos, int64_t *d_neg,
                            double *med_a, double *med_b, int n_threads)
 {
-    if (n_sites_a < 0 || n_sites_b < 0 || n_pairs < 0) return fail(M6A_IO_EINVAL, "n_sites_a, n_sites_b and n_pairs must be >= 0");
-    if (!n_pairs) return M6A_IO_OK;
-    if ((!pair_a || !pair_b) && (n_pairs != n_sites_a || n_pairs != n_sites_b))
-        return fail(M6A_IO_EINVAL, "a NULL pair array is the identity and needs n_pairs == n_sites_a == n_sites_b");
-    if (!v_a || !off_a || !v_b || !off_b || !d_pos || !d_neg) return fail(M6A_IO_EINVAL, "null argument");
-    const int64_t *offs[2] = {off_a, off_b};
-    const int64_t ns[2] = {n_sites_a, n_sites_b};
-    for (int side = 0; side < 2; side++) {
-        if (offs[side][0] != 0) return fail(M6A_IO_EINVAL, "off[0] must be 0");
-        for (int64_t s = 0; s < ns[side]; s++)
-            if (offs[side][s + 1] < offs[side][s]) return fail(M6A_IO_EINVAL, "off[] must be non-decreasing");
-    }
-    for (int64_t k = 0; k < n_pairs; k++)
-        if ((pair_a && (pair_a[k] < 0 || pair_a[k] >= n_sites_a)) || (pair_b && (pair_b[k] < 0 || pair_b[k] >= n_sites_b)))
-            return fail(M6A_IO_EINVAL, "pair %lld names a site outside its set", (long long)k);
-    try {
-        const int nw = n_workers(n_threads, n_pairs);
-        std::atomic<bool> no_mem{false};
-        auto work = [&](int w) {
-            try {
-                std::vector<float> ga, gb, sa, sb;
-                for (int64_t k = n_pairs * w / nw; k < n_pairs * (w + 1) / nw; k++) {
-                    const int64_t ia = pair_a ? pair_a[k] : k, ib = pair_b ? pair_b[k] : k;
-                    for (int c = 0; c < C; c++) {
-                        const m6a_ks::Result r = m6a_ks::count_column(v_a + off_a[ia] * C, off_a[ia + 1] - off_a[ia], v_b + off_b[ib] * C,
-                                                                      off_b[ib + 1] - off_b[ib], c, C, ga, gb, sa, sb);
-                        d_pos[k * C + c] = r.d_pos;
-                        d_neg[k * C + c] = r.d_neg;
-                        if (med_a) med_a[k * C + c] = r.med_a;
-                        if (med_b) med_b[k * C + c] = r.med_b;
-                    }
-                }
-            } catch (const std::bad_alloc &) {
-                no_mem = true;
-            }
-        };
-        std::vector<std::thread> th;
-        for (int w = 1; w < nw; w++) th.emplace_back(work, w);
-        work(0);
-        for (auto &t : th) t.join();
-        if (no_mem) return fail(M6A_IO_ENOMEM, "out of memory");
-        return M6A_IO_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(M6A_IO_ENOMEM, "out of memory");
-    }
+    return site_pairs_on_host(C, v_a, off_a, n_sites_a, v_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos && d_neg, n_threads,
+                              [=](int64_t at, const float *a, int64_t n, const float *b, int64_t m, int c, PairScratch &s) {
+                                  const m6a_ks::Result r = m6a_ks::count_column(a, n, b, m, c, C, s.ga, s.gb, s.sa, s.sb);
+                                  d_pos[at] = r.d_pos;
+                                  d_neg[at] = r.d_neg;
+                                  if (med_a) med_a[at] = r.med_a;
+                                  if (med_b) med_b[at] = r.med_b;
+                              });
+}
+
+extern "C" int m6a_io_site_ranksum(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,
+                                   int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt, int64_t *eq,
+                                   int64_t *tie, double *z, int n_threads)
+{
+    return site_ranksum_on_host(1, prob_a, off_a, n_sites_a, prob_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, gt, eq, tie, z, n_threads);
+}
+
+extern "C" int m6a_io_site_signal_ranksum(const float *X_a, const int64_t *off_a, int64_t n_sites_a, const float *X_b, const int64_t *off_b,
+                                          int64_t n_sites_b, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, int64_t *gt,
+                                          int64_t *eq, int64_t *tie, double *z, int n_threads)
+{
+    return site_ranksum_on_host(9, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, gt, eq, tie, z, n_threads);   // M6A_N_FEATURES: the row of X
 }
 
 extern "C" int m6a_io_site_ks(const float *prob_a, const int64_t *off_a, int64_t n_sites_a, const float *prob_b, const int64_t *off_b,

@@ -59,16 +59,12 @@ inline Result count(const float *a, int64_t n, const float *b, int64_t m, std::v
 }
 
 // One pair and one column of m6a_site_signal_ks on the host: column c of the rows Xa [n][width] and Xb [m][width], gathered into the
-// caller's scratch ga and gb and counted as above.  Reads Xa[i * width + c] and Xb[j * width + c] and nothing else.
+// caller's scratch ga and gb (m6a_ranksum::gather_column) and counted as above.
 inline Result count_column(const float *Xa, int64_t n, const float *Xb, int64_t m, int c, int width, std::vector<float> &ga,
                            std::vector<float> &gb, std::vector<float> &sa, std::vector<float> &sb)
 {
     if (m6a_ranksum::undefined_sizes(n, m)) return undefined();
-    ga.resize((size_t)n);
-    gb.resize((size_t)m);
-    for (int64_t i = 0; i < n; i++) ga[(size_t)i] = Xa[i * width + c];
-    for (int64_t j = 0; j < m; j++) gb[(size_t)j] = Xb[j * width + c];
-    return count(ga.data(), n, gb.data(), m, sa, sb);
+    return count(m6a_ranksum::gather_column(Xa, n, c, width, ga), n, m6a_ranksum::gather_column(Xb, m, c, width, gb), m, sa, sb);
 }
 
 }  // namespace m6a_ks

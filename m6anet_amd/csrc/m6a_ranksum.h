@@ -89,17 +89,22 @@ inline Result count(const float *a, int64_t n, const float *b, int64_t m, std::v
     return {gt, eq, tie, finish(n, m, gt, eq, tie)};
 }
 
+// Column c of the rows X [n][width], gathered into the caller's scratch g (m6a_ks.h gathers with it too).  Reads X[i * width + c] and
+// nothing else.
+inline const float *gather_column(const float *X, int64_t n, int c, int width, std::vector<float> &g)
+{
+    g.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) g[(size_t)i] = X[i * width + c];
+    return g.data();
+}
+
 // One pair and one column of m6a_site_signal_ranksum on the host: column c of the rows Xa [n][width] and Xb [m][width], gathered into
-// the caller's scratch ga and gb and counted as above.  Reads Xa[i * width + c] and Xb[j * width + c] and nothing else.
+// the caller's scratch ga and gb and counted as above.
 inline Result count_column(const float *Xa, int64_t n, const float *Xb, int64_t m, int c, int width, std::vector<float> &ga,
                            std::vector<float> &gb, std::vector<float> &sa, std::vector<float> &sb)
 {
     if (undefined_sizes(n, m)) return undefined();
-    ga.resize((size_t)n);
-    gb.resize((size_t)m);
-    for (int64_t i = 0; i < n; i++) ga[(size_t)i] = Xa[i * width + c];
-    for (int64_t j = 0; j < m; j++) gb[(size_t)j] = Xb[j * width + c];
-    return count(ga.data(), n, gb.data(), m, sa, sb);
+    return count(gather_column(Xa, n, c, width, ga), n, gather_column(Xb, m, c, width, gb), m, sa, sb);
 }
 
 }  // namespace m6a_ranksum

@@ -152,6 +152,11 @@ class _Arg:
             self.size = a.size
 
 
+# the four outputs of the calls on pairs of sites (_site_pairs): gt, eq, tie, z and d_pos, d_neg, med_a, med_b
+_RANKSUM_OUT = ((np.int64, "int64"),) * 3 + ((np.float64, "float64"),)
+_KS_OUT = ((np.int64, "int64"),) * 2 + ((np.float64, "float64"),) * 2
+
+
 class M6ANetEngine:
     def __init__(self, weights=None, pretrained_model=DEFAULT_PRETRAINED_MODEL, device=0):
         self._L = _lib.load()
@@ -431,22 +436,7 @@ class M6ANetEngine:
         NumPy arrays (synchronous) or torch tensors on the GPU (queued: `sync()` before reading), all of one kind.  Returns
         (gt, eq, tie int64 [P], z float64 [P]); an undefined pair -- an empty bag, a NaN, more than 2^20 pooled reads -- is
         (-1, -1, -1, NaN).  m6anet_amd/ranksum.py turns them into p, q and the AUC."""
-        if (pair_a is None) != (pair_b is None):
-            raise ValueError("pair_a and pair_b are given together or not at all")
-        aPa, aOa = _Arg(read_probs_a, np.float32, "float32"), _Arg(off_a, np.int64, "int64")
-        aPb, aOb = _Arg(read_probs_b, np.float32, "float32"), _Arg(off_b, np.int64, "int64")
-        Sa, Sb = aOa.size - 1, aOb.size - 1
-        aIa = _Arg(pair_a, np.int64, "int64") if pair_a is not None else None
-        aIb = _Arg(pair_b, np.int64, "int64") if pair_b is not None else None
-        if aIa is not None and aIa.size != aIb.size:
-            raise ValueError("pair_a and pair_b must have one entry per pair")
-        if aIa is None and Sa != Sb:
-            raise ValueError("without pair_a / pair_b the two sets must have the same number of sites")
-        P = aIa.size if aIa is not None else Sa
-        out = [self._out(aPa.is_dev, P, np.int64, "int64") for _ in range(3)] + [self._out(aPa.is_dev, P, np.float64, "float64")]
-        ptrs = [_Arg(o, dt, name).ptr for o, dt, name in zip(out, (np.int64,) * 3 + (np.float64,), ("int64",) * 3 + ("float64",))]
-        self.site_ranksum_ptrs(aPa.ptr, aOa.ptr, Sa, aPb.ptr, aOb.ptr, Sb, aIa.ptr if aIa else None, aIb.ptr if aIb else None, P, *ptrs)
-        return tuple(out)
+        return self._site_pairs(1, self.site_ranksum_ptrs, _RANKSUM_OUT, read_probs_a, off_a, read_probs_b, off_b, pair_a, pair_b)
 
     def site_ranksum_ptrs(self, prob_a, off_a, n_sites_a, prob_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, gt, eq, tie, z):
         """m6a_site_ranksum on raw addresses (ints) the caller owns, as infer_ptrs is m6a_infer on them -- e.g. the read_prob and off
@@ -461,24 +451,7 @@ class M6ANetEngine:
         arrays (synchronous) or torch tensors on the GPU (queued: `sync()` before reading), all of one kind.  Returns (gt, eq, tie
         int64 [P, 9], z float64 [P, 9]); a NaN leaves its own column of the pair undefined, an empty bag or more than 2^20 pooled
         reads all nine.  m6anet_amd/ranksum.py (signal_rows) turns them into p, q and the AUC."""
-        if (pair_a is None) != (pair_b is None):
-            raise ValueError("pair_a and pair_b are given together or not at all")
-        aXa, aOa = _Arg(X_a, np.float32, "float32"), _Arg(off_a, np.int64, "int64")
-        aXb, aOb = _Arg(X_b, np.float32, "float32"), _Arg(off_b, np.int64, "int64")
-        if aXa.size % 9 or aXb.size % 9:
-            raise ValueError("X_a and X_b hold nine float32 per read")
-        Sa, Sb = aOa.size - 1, aOb.size - 1
-        aIa = _Arg(pair_a, np.int64, "int64") if pair_a is not None else None
-        aIb = _Arg(pair_b, np.int64, "int64") if pair_b is not None else None
-        if aIa is not None and aIa.size != aIb.size:
-            raise ValueError("pair_a and pair_b must have one entry per pair")
-        if aIa is None and Sa != Sb:
-            raise ValueError("without pair_a / pair_b the two sets must have the same number of sites")
-        P = aIa.size if aIa is not None else Sa
-        out = [self._out(aXa.is_dev, P * 9, np.int64, "int64") for _ in range(3)] + [self._out(aXa.is_dev, P * 9, np.float64, "float64")]
-        ptrs = [_Arg(o, dt, name).ptr for o, dt, name in zip(out, (np.int64,) * 3 + (np.float64,), ("int64",) * 3 + ("float64",))]
-        self.site_signal_ranksum_ptrs(aXa.ptr, aOa.ptr, Sa, aXb.ptr, aOb.ptr, Sb, aIa.ptr if aIa else None, aIb.ptr if aIb else None, P, *ptrs)
-        return tuple(o.reshape(P, 9) for o in out)
+        return self._site_pairs(9, self.site_signal_ranksum_ptrs, _RANKSUM_OUT, X_a, off_a, X_b, off_b, pair_a, pair_b)
 
     def site_signal_ranksum_ptrs(self, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, gt, eq, tie, z):
         """m6a_site_signal_ranksum on raw addresses (ints) the caller owns, as site_ranksum_ptrs is m6a_site_ranksum on them -- e.g. the
@@ -487,7 +460,9 @@ class M6ANetEngine:
         self._chk(self._L.m6a_site_signal_ranksum(self._h, X_a, off_a, int(n_sites_a), X_b, off_b, int(n_sites_b), pair_a, pair_b,
                                                   int(n_pairs), gt, eq, tie, z))
 
-    def _site_ks(self, cols, v_a, off_a, v_b, off_b, pair_a, pair_b):
+    def _site_pairs(self, cols, call, out_dtypes, v_a, off_a, v_b, off_b, pair_a, pair_b):
+        """The four calls on pairs of sites: a bag's element is `cols` float32 (1: a value, 9: a row of X), `call` the *_ptrs method and
+        out_dtypes its four outputs' (NumPy dtype, name); [P] for cols == 1, [P, cols] otherwise."""
         if (pair_a is None) != (pair_b is None):
             raise ValueError("pair_a and pair_b are given together or not at all")
         aVa, aOa = _Arg(v_a, np.float32, "float32"), _Arg(off_a, np.int64, "int64")
@@ -502,10 +477,8 @@ class M6ANetEngine:
         if aIa is None and Sa != Sb:
             raise ValueError("without pair_a / pair_b the two sets must have the same number of sites")
         P = aIa.size if aIa is not None else Sa
-        out = [self._out(aVa.is_dev, P * cols, np.int64, "int64") for _ in range(2)] + \
-              [self._out(aVa.is_dev, P * cols, np.float64, "float64") for _ in range(2)]
-        ptrs = [_Arg(o, dt, name).ptr for o, dt, name in zip(out, (np.int64,) * 2 + (np.float64,) * 2, ("int64",) * 2 + ("float64",) * 2)]
-        call = self.site_ks_ptrs if cols == 1 else self.site_signal_ks_ptrs
+        out = [self._out(aVa.is_dev, P * cols, dt, name) for dt, name in out_dtypes]
+        ptrs = [_Arg(o, dt, name).ptr for o, (dt, name) in zip(out, out_dtypes)]
         call(aVa.ptr, aOa.ptr, Sa, aVb.ptr, aOb.ptr, Sb, aIa.ptr if aIa else None, aIb.ptr if aIb else None, P, *ptrs)
         return tuple(out) if cols == 1 else tuple(o.reshape(P, cols) for o in out)
 
@@ -514,7 +487,7 @@ class M6ANetEngine:
         NumPy arrays (synchronous) or torch tensors on the GPU (queued: `sync()` before reading), all of one kind.  Returns (d_pos,
         d_neg int64 [P], med_a, med_b float64 [P]); an undefined pair -- an empty bag, a NaN, more than 2^20 pooled reads -- is
         (-1, -1, NaN, NaN).  m6anet_amd/ranksum.py turns them into D, its sign, p and q."""
-        return self._site_ks(1, read_probs_a, off_a, read_probs_b, off_b, pair_a, pair_b)
+        return self._site_pairs(1, self.site_ks_ptrs, _KS_OUT, read_probs_a, off_a, read_probs_b, off_b, pair_a, pair_b)
 
     def site_ks_ptrs(self, prob_a, off_a, n_sites_a, prob_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b):
         """m6a_site_ks on raw addresses (ints) the caller owns, as site_ranksum_ptrs is m6a_site_ranksum on them: all host or all device;
@@ -527,7 +500,7 @@ class M6ANetEngine:
         """site_ks on each of the nine signal features (include/m6a.h: m6a_site_signal_ks), shaped like site_signal_ranksum: X_a [Ra, 9]
         and X_b [Rb, 9] with off_* in rows.  Returns (d_pos, d_neg int64 [P, 9], med_a, med_b float64 [P, 9]), the medians in the
         normalised units of X; a NaN leaves its own column of the pair undefined, an empty bag or more than 2^20 pooled reads all nine."""
-        return self._site_ks(9, X_a, off_a, X_b, off_b, pair_a, pair_b)
+        return self._site_pairs(9, self.site_signal_ks_ptrs, _KS_OUT, X_a, off_a, X_b, off_b, pair_a, pair_b)
 
     def site_signal_ks_ptrs(self, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b):
         """m6a_site_signal_ks on raw addresses (ints) the caller owns, as site_ks_ptrs is m6a_site_ks on them; the outputs hold nine

@@ -3,7 +3,7 @@ what tests/ranksum_statement.py says of them, computed once per (site of A, site
 
 Two sets of sites with the same number of sites, so that the identity pairing is a legal call.  Sites 0..10 of either set are bags
 of SIZES reads; the sites behind them are the two sides of the special pairs below, in order.  TILE is the kernel's LDS tile
-(M6A_RANKSUM_TILE in m6anet_amd/csrc/m6a_ranksum.hip); its wavefront owns the pooled sample in chunks of 64."""
+(M6A_PAIR_TILE in m6anet_amd/csrc/m6a_pairs.h); its wavefront owns the pooled sample in chunks of 64."""
 import functools
 
 import numpy as np

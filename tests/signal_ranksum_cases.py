@@ -2,8 +2,8 @@
 m6a_site_signal_ranksum on, and what tests/signal_ranksum_statement.py says of them, computed once per (site of A, site of B) and shared.
 
 Two sets of sites with the same number of sites, so that the identity pairing is a legal call.  Sites 0..15 of either set are bags of
-SIZES rows: the sizes around the wavefront's chunk of 64 and around TILE, the kernel's LDS tile in rows (M6A_SIGNAL_TILE in
-m6anet_amd/csrc/m6a_ranksum.hip).  The sites behind them are the two sides of the special pairs, in order.  Every column of X has a
+SIZES rows: the sizes around the wavefront's chunk of 64 and around TILE, the kernel's LDS tile in rows (M6A_PAIR_TILE in
+m6anet_amd/csrc/m6a_pairs.h).  The sites behind them are the two sides of the special pairs, in order.  Every column of X has a
 value family of its own (COLUMNS), so a result that took another column's values, or its neighbour's, is another number."""
 import functools
 

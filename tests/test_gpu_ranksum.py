@@ -1,6 +1,6 @@
 """m6a_site_ranksum on the GPU (include/m6a.h): site_ranksum_kernel gives the integers and the bits of z that tests/ranksum_statement.py
 states, with device pointers and with host pointers, on every shape of tests/ranksum_cases.py -- bag sizes around the wavefront's
-chunk of 64 crossed, lopsided pairs, pairs around the LDS tile of 256 floats (ranksum_cases.TILE = M6A_RANKSUM_TILE), a 3000 x 2500
+chunk of 64 crossed, lopsided pairs, pairs around the LDS tile of 256 floats (ranksum_cases.TILE = M6A_PAIR_TILE), a 3000 x 2500
 pair, empty bags, ties, signed zeros, infinities, NaN -- for pair lists that repeat sites, run backwards and hold 0, 1, 65 and 4097
 pairs, with the index arrays and the optional outputs left out, and with sentinels around all four outputs.  A bad index is refused on
 the host and contained on the device."""

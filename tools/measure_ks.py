@@ -10,9 +10,8 @@ the calls which existed before them did not move:
            rank-sum twin.  Before anything is timed the new calls' outputs are held bit for bit to the host core (m6a_io_site_ks on
            every pair; m6a_io_site_signal_ks on the first --check_pairs pairs).  Shapes: 1 M pairs of 20 + 20 reads and 125 k pairs of
            50..500 reads a side.  The new kernels carry no speed bar.
-  parent   --parent_root DIR (a built tree of the parent commit): m6a_site_ranksum and m6a_site_signal_ranksum themselves, in
-           alternating processes of this tree and that one, on both shapes; bar: this tree's median within the parent's median plus the
-           parent's own spread.
+  parent   --parent_root DIR (a built tree of the parent commit): the four calls themselves, in alternating processes of this tree and
+           that one, on both shapes; bar: this tree's median within the parent's median plus the parent's own spread.
   bench    with --parent_root: plain `bench.py --gpus 1` in alternating processes of the two trees, with --dump-outputs; bar as above on
            ms_per_step, and the dumped arrays byte-identical.
 
@@ -29,6 +28,8 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = {"uniform": (1_000_000, 20), "ragged": (125_000, (50, 500))}
 MODEL = "HCT116_RNA002"
+CALLS = {"site_ranksum": ("prob", 1, 3), "site_signal_ranksum": ("X", 9, 3), "site_ks": ("prob", 1, 2),
+         "site_signal_ks": ("X", 9, 2)}     # the engine's *_ptrs method: (input, values per pair, how many of the four outputs are int64)
 
 
 def offsets(shape, seed):
@@ -156,16 +157,17 @@ def measure_legs(shape, steps, warmup, legs, check_pairs):
 
 
 def child(root, steps, warmup):
-    """m6a_site_ranksum and m6a_site_signal_ranksum alone, from the tree at `root`: one JSON line {call: {shape: [ms, ...]}}"""
+    """the four calls alone, from the tree at `root`: one JSON line {call: {shape: [ms, ...]}}"""
     import torch
     eng = engine(root)
     dev = torch.device("cuda:0")
-    out = {"site_ranksum": {}, "site_signal_ranksum": {}}
+    out = {c: {} for c in CALLS}
     for shape, (S, _) in SHAPES.items():
         a, b = conditions(shape, dev)
         pair = torch.arange(S, dtype=torch.int64, device=dev)
-        for name, method, key, W in (("site_ranksum", eng.site_ranksum_ptrs, "prob", 1), ("site_signal_ranksum", eng.site_signal_ranksum_ptrs, "X", 9)):
-            res = [torch.empty(S * W, dtype=torch.int64, device=dev) for _ in range(3)] + [torch.empty(S * W, dtype=torch.float64, device=dev)]
+        for name, (key, W, n_int) in CALLS.items():
+            method = getattr(eng, name + "_ptrs")
+            res = [torch.empty(S * W, dtype=torch.int64 if i < n_int else torch.float64, device=dev) for i in range(4)]
 
             def run():
                 method(a[key].data_ptr(), a["off"].data_ptr(), S, b[key].data_ptr(), b["off"].data_ptr(), S, pair.data_ptr(), pair.data_ptr(), S,
@@ -188,8 +190,7 @@ def against(per):
 
 
 def measure_parent(parent_root, steps, warmup, rounds, limit):
-    calls = ("site_ranksum", "site_signal_ranksum")
-    per = {c: {s: {"parent": [], "this": []} for s in SHAPES} for c in calls}
+    per = {c: {s: {"parent": [], "this": []} for s in SHAPES} for c in CALLS}
     for _ in range(rounds):
         for name, root in (("parent", os.path.abspath(parent_root)), ("this", REPO)):
             p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", root, "--steps", str(steps),
@@ -197,10 +198,10 @@ def measure_parent(parent_root, steps, warmup, rounds, limit):
             if p.returncode != 0:
                 raise RuntimeError("the %s process failed (%d): %s" % (name, p.returncode, p.stderr[-2000:]))
             got = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("CHILD ")][-1][6:])
-            for c in calls:
+            for c in CALLS:
                 for s in SHAPES:
                     per[c][s][name].append(got[c][s])
-    return {c: {s: against(per[c][s]) for s in SHAPES} for c in calls}
+    return {c: {s: against(per[c][s]) for s in SHAPES} for c in CALLS}
 
 
 def measure_bench(parent_root, steps, warmup, rounds, limit):
@@ -255,7 +256,7 @@ def main():
             json.dump(res, f, indent=1)
             f.write("\n")
 
-    for part in list(SHAPES) + ["ranksum_calls_against_parent", "bench_against_parent"]:
+    for part in list(SHAPES) + ["calls_against_parent", "bench_against_parent"]:
         res[part] = "not measured"
     for shape in SHAPES:
         if shape in a.shapes.split(","):
@@ -263,8 +264,8 @@ def main():
         print(shape, json.dumps(res[shape]), flush=True)
         write()
     if a.parent_root:
-        res["ranksum_calls_against_parent"] = measure_parent(a.parent_root, a.steps, a.warmup, a.legs, a.timeout)
-    print("ranksum_calls_against_parent", json.dumps(res["ranksum_calls_against_parent"]), flush=True)
+        res["calls_against_parent"] = measure_parent(a.parent_root, a.steps, a.warmup, a.legs, a.timeout)
+    print("calls_against_parent", json.dumps(res["calls_against_parent"]), flush=True)
     write()
     if a.parent_root and not a.no_bench:
         res["bench_against_parent"] = measure_bench(a.parent_root, a.bench_steps, a.bench_warmup, a.legs, a.timeout)

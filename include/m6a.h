@@ -323,7 +323,7 @@ int m6a_site_signal_ranksum(m6a_ctx *ctx, const float *X_a, const int64_t *off_a
  * p = Q(lambda), lambda = sqrt(n m / (n + m)) D, Q the Kolmogorov limit distribution 2 sum_{k>=1} (-1)^(k-1) exp(-2 k^2 lambda^2) --
  * scipy.stats.kstwobign.sf(lambda).  That is NOT what scipy.stats.ks_2samp returns (exact for small bags, kstwo at round(en) under
  * method="asymp"); the limit is conservative for small bags (one 20 + 20 pair: 0.0047 against the exact 0.0040).  The exact
- * small-sample p-value is not built.
+ * finite-sample p-value, ks_2samp's, is m6a_ks_exact below, from h = max(d_pos, d_neg) as it stands.
  *   d_pos, d_neg   [n_pairs] int64 out, required;  med_a, med_b [n_pairs] float64 out, each may be NULL
  * Pointers all host (staged, synchronous, checked before anything is queued and the outputs untouched on M6A_EINVAL) or all device
  * (queued on the context's stream), pair arrays and n_pairs == 0 as for m6a_site_ranksum.  With device arrays nothing is read through an
@@ -348,6 +348,36 @@ int m6a_site_signal_ks(m6a_ctx *ctx, const float *X_a, const int64_t *off_a, int
                        const float *X_b, const int64_t *off_b, int64_t n_sites_b,
                        const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
                        int64_t *d_pos, int64_t *d_neg, double *med_a, double *med_b);
+
+#define M6A_KS_EXACT_SHORT 2047                               /* min(n, m) above this: the item is undefined */
+#define M6A_KS_EXACT_CELLS 100000000                          /* n m above this: the item is undefined */
+/* The exact two-sided p-value of the two-sample Kolmogorov-Smirnov statistic, P(D_{n,m} >= d), per item: what
+ * scipy.stats.ks_2samp(a, b, method="exact") returns, from the integers m6a_site_ks and m6a_site_signal_ks deliver -- n and m the two
+ * bag sizes and h = max(d_pos, d_neg), the statistic in units of 1 / (n m), so no float comes between the counting and the p-value.
+ * The operation (tests/ks_exact_statement.py states it in NumPy; host and device give the same bits), for n >= 1, m >= 1:
+ *   a cell (i, j), 0 <= i <= n, 0 <= j <= m, is OUTSIDE when |m i - n j| >= h, compared in int64.  v[i][j] is the probability that a
+ *   uniformly drawn monotone path from (i, j) to (n, m) meets an outside cell, (i, j) included:
+ *     v[i][j] = 1.0 when (i, j) is outside;  v[n][m] = 0.0 when it is inside;  otherwise
+ *     v[i][j] = ((double)(n - i) * v[i+1][j] + (double)(m - j) * v[i][j+1]) / (double)(n + m - i - j),
+ *   a neighbour beyond the grid being 0.0: each product rounded on its own, then the sum, then one correctly rounded division -- no fused
+ *   multiply-add, no reciprocal.  p = v[0][0].
+ *   h == 0 gives 1.0 and an h above every attainable value (h > n m) gives 0.0, both by the recurrence.  Every term is positive, so
+ *   nothing cancels: the relative error is about 3 (n + m) roundings down to the subnormal range (measured against exact path counts
+ *   for n, m <= 12: at most 0.29 (n + m) 2^-53), and a result below the smallest subnormal is 0.0, as scipy's is.  The recurrence is
+ *   symmetric under swapping the two bags, to the bit.
+ *   undefined items  n < 1 or m < 1; h < 0 (the undefined pair of m6a_site_ks has d_pos = d_neg = -1); min(n, m) > M6A_KS_EXACT_SHORT
+ *       (2047) or n m > M6A_KS_EXACT_CELLS (10^8, scipy's own 10 000 x 10 000): p = NaN.  Not an error.  `eventalign_diff --ks_exact`
+ *       writes the limit distribution's p for such an item and says so in its p_method column.
+ *   n, m, h [count] int64 in;  p [count] float64 out
+ * Pointers all host (staged, synchronous) or all device (queued on the context's stream); count == 0 is M6A_OK; a null pointer, a
+ * negative count or a mixture of host and device pointers is M6A_EINVAL with p untouched.  Nothing is read through n, m or h, so no
+ * value of them is an error.  The kernel (ks_exact_kernel, m6anet_amd/csrc/m6a_ks_exact.hip) gives an item to a wavefront: the shorter
+ * bag on j, rows i in stripes of 64 with lane l on row i0 + l one step behind lane l + 1, so that every step has all lanes on one
+ * anti-diagonal; v[i][j+1] is the lane's own last result, v[i+1][j] one cross-lane move of a double, and the row between two stripes
+ * (min(n, m) + 1 doubles, the reason for the first cap) stays in LDS.  Only the j at which some row of a stripe is inside the band
+ * are walked.  An item costs about its inside cells plus 64 steps per stripe; the largest defined item is 10^8 divisions on one
+ * wavefront.  Not built: one-sided exact p-values.  No reference counterpart. */
+int m6a_ks_exact(m6a_ctx *ctx, const int64_t *n, const int64_t *m, const int64_t *h, int64_t count, double *p);
 
 /* Streaming form of m6a_infer: the batch loop of run_inference (m6anet/utils/inference_utils.py:33-54) fed as the
  * DataLoader produces it, so a reference-side binding keeps its loader and its loop.

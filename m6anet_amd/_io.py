@@ -13,7 +13,7 @@ SYMBOLS = ["m6a_io_last_error", "m6a_io_load_sites", "m6a_io_free", "m6a_io_n_si
            "m6a_io_rows_free", "m6a_io_dataprep_write", "m6a_io_runs_rows", "m6a_io_sites_from_arrays", "m6a_io_sites_from_arrays_rep", "m6a_io_sites_set_read_names", "m6a_io_uuid_parse", "m6a_io_uuid_format", "m6a_io_bgzf_inflate", "m6a_io_bgzf_deflate", "m6a_io_bgzf_deflate_level",
            "m6a_io_info_open", "m6a_io_info_get", "m6a_io_info_free", "m6a_io_info_rows", "m6a_io_json_walk",
            "m6a_io_norm_factors", "m6a_io_norm_partials", "m6a_io_site_ranksum", "m6a_io_site_signal_ranksum", "m6a_io_site_ks",
-           "m6a_io_site_signal_ks"]
+           "m6a_io_site_signal_ks", "m6a_io_ks_exact"]
 _lib = None
 
 
@@ -123,6 +123,7 @@ def load():
     L.m6a_io_site_signal_ranksum.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
     L.m6a_io_site_ks.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
     L.m6a_io_site_signal_ks.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32]
+    L.m6a_io_ks_exact.argtypes = [vp, vp, vp, i64, vp]
     _lib = L
     return L
 
@@ -145,6 +146,18 @@ def usable_cpus():
 def _chk(rc):
     if rc != 0:
         raise M6AIOError("m6a_io error %d: %s" % (rc, load().m6a_io_last_error().decode()), rc)
+
+
+def ks_exact(n, m, h):
+    """m6a_io_ks_exact: the exact two-sided Kolmogorov-Smirnov p-value of every item (n, m, h) on the host, the bits m6a_ks_exact gives
+    on a device (include/m6a.h states the recurrence and what is undefined, NaN).  Integer arrays of one size -> float64 of their shape."""
+    shape = np.shape(n)
+    n, m, h = (np.ascontiguousarray(np.asarray(x).ravel(), np.int64) for x in (n, m, h))
+    if not n.size == m.size == h.size:
+        raise ValueError("n, m and h must have one entry per item")
+    p = np.empty(n.size, np.float64)
+    _chk(load().m6a_io_ks_exact(n.ctypes.data, m.ctypes.data, h.ctypes.data, n.size, p.ctypes.data))
+    return p.reshape(shape)
 
 
 def dataprep(eventalign, out_dir, n_threads=0, readcount_min=1, readcount_max=1000, min_segment_count=20,

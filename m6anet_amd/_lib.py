@@ -15,7 +15,7 @@ REPR_DTYPES = {"float32": 0, "float16": 1}           # M6A_REPR_F32, M6A_REPR_F1
 
 # every symbol include/m6a.h declares (tests check the .so exports exactly these)
 SYMBOLS = ["m6a_create", "m6a_destroy", "m6a_last_error", "m6a_set_stream", "m6a_set_job_offset", "m6a_set_scan_driver", "m6a_set_table_variant", "m6a_set_encoder_variant", "m6a_last_encoder_variant", "m6a_last_encoder_kernel", "m6a_sync", "m6a_set_host_offsets", "m6a_prepare_host_io", "m6a_host_alloc", "m6a_host_free", "m6a_host_is_pinned",
-           "m6a_encode_reads", "m6a_read_representation", "m6a_read_representation_dtype", "m6a_site_pool", "m6a_site_expectation", "m6a_site_ranksum", "m6a_site_signal_ranksum", "m6a_site_ks", "m6a_site_signal_ks", "m6a_set_site_mode", "m6a_infer", "m6a_job_begin", "m6a_job_feed", "m6a_job_feed_collated", "m6a_job_size", "m6a_job_end", "m6a_job_abort", "m6a_bag_forward", "m6a_validate_pool", "m6a_validate", "m6a_flush_groups",
+           "m6a_encode_reads", "m6a_read_representation", "m6a_read_representation_dtype", "m6a_site_pool", "m6a_site_expectation", "m6a_site_ranksum", "m6a_site_signal_ranksum", "m6a_site_ks", "m6a_site_signal_ks", "m6a_ks_exact", "m6a_set_site_mode", "m6a_infer", "m6a_job_begin", "m6a_job_feed", "m6a_job_feed_collated", "m6a_job_size", "m6a_job_end", "m6a_job_abort", "m6a_bag_forward", "m6a_validate_pool", "m6a_validate", "m6a_flush_groups",
            "m6a_reference_written_sites",
            "m6a_shard_plan", "m6a_comm_unique_id", "m6a_comm_init", "m6a_gather", "m6a_gather_reads", "m6a_device_count", "m6a_random_stream", "m6a_comm_destroy", "m6a_comm_count", "m6a_comm_info", "m6a_device_link", "m6a_profile_enable", "m6a_profile_read", "m6a_profile_clock", "m6a_last_pool_variant",
            "m6a_version", "m6a_prep_eventalign", "m6a_prep_table", "m6a_prep_times", "m6a_prep_free", "m6a_prep_last_error",
@@ -190,6 +190,7 @@ def load():
     L.m6a_site_signal_ranksum.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
     L.m6a_site_ks.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
     L.m6a_site_signal_ks.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
+    L.m6a_ks_exact.argtypes = [vp, vp, vp, vp, i64, vp]
     L.m6a_set_site_mode.argtypes = [vp, i32]
     L.m6a_infer.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, u32, i32, i64, i64, vp, vp, vp]
     L.m6a_job_begin.argtypes = [vp, i32, i32, f32, u32, i32, i64, i64, i64, i64]

@@ -8,9 +8,9 @@ CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 LIB = os.path.join(PKG, "libm6a_hip.so")
 IO_LIB = os.path.join(PKG, "libm6a_io.so")
-SOURCES = ["m6a_kernels.hip", "m6a_pool_reg.hip", "m6a_pool_rtab.hip", "m6a_expect.hip", "m6a_ranksum.hip", "m6a_ks.hip", "m6a_api.hip", "m6a_host_ring.hip", "m6a_job.hip", "m6a_comm.hip",
+SOURCES = ["m6a_kernels.hip", "m6a_pool_reg.hip", "m6a_pool_rtab.hip", "m6a_expect.hip", "m6a_ranksum.hip", "m6a_ks.hip", "m6a_ks_exact.hip", "m6a_api.hip", "m6a_host_ring.hip", "m6a_job.hip", "m6a_comm.hip",
            "m6a_validate.hip", "m6a_prep.hip", "m6a_train.hip"]
-DEPS = SOURCES + [os.path.join(INCLUDE, "m6a_io.h"), "m6a_kernels.h", "m6a_ctx.h", "m6a_prep_kit.h", "m6a_rounds.h", "m6a_host_cpus.h", "m6a_csv.h", "m6a_npy.h", "m6a_npy_write.h", "m6a_repr.h", "m6a_dataprep.h", "m6a_bgzf.h", "m6a_deflate.h", "m6a_json.h", "m6a_norm.h", "m6a_uuid.h", "m6a_ranksum.h", "m6a_ks.h", "m6a_pairs.h", "m6a_stream.h", "m6a_train_draw.h", os.path.join(INCLUDE, "m6a.h"), os.path.join(PKG, "assets", "mt19937_jump.bin")]
+DEPS = SOURCES + [os.path.join(INCLUDE, "m6a_io.h"), "m6a_kernels.h", "m6a_ctx.h", "m6a_prep_kit.h", "m6a_rounds.h", "m6a_host_cpus.h", "m6a_csv.h", "m6a_npy.h", "m6a_npy_write.h", "m6a_repr.h", "m6a_dataprep.h", "m6a_bgzf.h", "m6a_deflate.h", "m6a_json.h", "m6a_norm.h", "m6a_uuid.h", "m6a_ranksum.h", "m6a_ks.h", "m6a_ks_exact.h", "m6a_pairs.h", "m6a_stream.h", "m6a_train_draw.h", os.path.join(INCLUDE, "m6a.h"), os.path.join(PKG, "assets", "mt19937_jump.bin")]
 
 
 def needs_build():
@@ -40,7 +40,7 @@ def build_io(force=False, verbose=False):
     src = os.path.join(CSRC, "m6a_io.cpp")
     hdr = os.path.join(INCLUDE, "m6a_io.h")
     deps = [src, hdr, os.path.join(CSRC, "m6a_host_cpus.h"), os.path.join(CSRC, "m6a_bgzf.h"), os.path.join(CSRC, "m6a_deflate.h"),
-            os.path.join(CSRC, "m6a_json.h"), os.path.join(CSRC, "m6a_norm.h"), os.path.join(CSRC, "m6a_uuid.h"), os.path.join(CSRC, "m6a_repr.h"), os.path.join(CSRC, "m6a_ranksum.h"), os.path.join(CSRC, "m6a_ks.h")]
+            os.path.join(CSRC, "m6a_json.h"), os.path.join(CSRC, "m6a_norm.h"), os.path.join(CSRC, "m6a_uuid.h"), os.path.join(CSRC, "m6a_repr.h"), os.path.join(CSRC, "m6a_ranksum.h"), os.path.join(CSRC, "m6a_ks.h"), os.path.join(CSRC, "m6a_ks_exact.h")]
     if not force and os.path.exists(IO_LIB) and os.path.getmtime(IO_LIB) >= max(os.path.getmtime(d) for d in deps):
         return IO_LIB
     # -ffp-contract=off: m6a_norm.h's sums round every product on its own, as the kernels' build does

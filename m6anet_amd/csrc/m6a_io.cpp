@@ -6,6 +6,7 @@
 #include "m6a_uuid.h"
 #include "m6a_ranksum.h"
 #include "m6a_ks.h"
+#include "m6a_ks_exact.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -2758,4 +2759,19 @@ extern "C" int m6a_io_site_signal_ks(const float *X_a, const int64_t *off_a, int
                                      int64_t *d_neg, double *med_a, double *med_b, int n_threads)
 {
     return site_ks_on_host(9, X_a, off_a, n_sites_a, X_b, off_b, n_sites_b, pair_a, pair_b, n_pairs, d_pos, d_neg, med_a, med_b, n_threads);   // M6A_N_FEATURES: the row of X
+}
+
+// ---- m6a_io_ks_exact: include/m6a.h's m6a_ks_exact on the host (the core is m6a_ks_exact.h, which the kernel's unit compiles too) ----
+extern "C" int m6a_io_ks_exact(const int64_t *n, const int64_t *m, const int64_t *h, int64_t count, double *p)
+{
+    if (count < 0) return fail(M6A_IO_EINVAL, "count must be >= 0");
+    if (!count) return M6A_IO_OK;
+    if (!n || !m || !h || !p) return fail(M6A_IO_EINVAL, "null argument");
+    try {
+        std::vector<double> row;
+        for (int64_t k = 0; k < count; k++) p[k] = m6a_kse::p_value(n[k], m[k], h[k], row);
+        return M6A_IO_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(M6A_IO_ENOMEM, "out of memory");
+    }
 }

@@ -508,6 +508,24 @@ class M6ANetEngine:
         self._chk(self._L.m6a_site_signal_ks(self._h, X_a, off_a, int(n_sites_a), X_b, off_b, int(n_sites_b), pair_a, pair_b,
                                              int(n_pairs), d_pos, d_neg, med_a, med_b))
 
+    def ks_exact(self, n, m, h):
+        """The exact two-sided Kolmogorov-Smirnov p-value of every item (include/m6a.h: m6a_ks_exact): n and m the two bag sizes and
+        h = max(d_pos, d_neg) of site_ks / site_signal_ks (m6anet_amd/ranksum.py: ks_h), the statistic in units of 1 / (n m) -- what
+        scipy.stats.ks_2samp(method="exact") returns.  int64 NumPy arrays (synchronous) or torch tensors on the GPU (queued: `sync()`
+        before reading), all of one kind and one size.  Returns p float64 of n's shape; NaN where the item is undefined: an empty bag,
+        h < 0 (the undefined pair of site_ks), min(n, m) > 2047 or n m > 10^8."""
+        aN, aM, aH = (_Arg(x, np.int64, "int64") for x in (n, m, h))
+        if not aN.size == aM.size == aH.size:
+            raise ValueError("n, m and h must have one entry per item")
+        p = self._out(aN.is_dev, aN.size, np.float64, "float64")
+        self.ks_exact_ptrs(aN.ptr, aM.ptr, aH.ptr, aN.size, _Arg(p, np.float64, "float64").ptr)
+        return p.reshape(tuple(aN.keep.shape))
+
+    def ks_exact_ptrs(self, n, m, h, count, p):
+        """m6a_ks_exact on raw addresses (ints) the caller owns: all host or all device.  With device pointers the call is queued on
+        the context's stream: `sync()` before p is read."""
+        self._chk(self._L.m6a_ks_exact(self._h, n, m, h, int(count), p))
+
     def infer(self, X, site_kmers, off, n_iters, n_samples=N_SAMPLES,
               read_proba_threshold=DEFAULT_READ_THRESHOLD, seed=0, batch_size=16, save_per_batch=2,
               want_read_probs=True, out=None):

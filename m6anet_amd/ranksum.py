@@ -12,8 +12,11 @@ What follows from the Kolmogorov-Smirnov integers and the medians of m6a_site_ks
   ks_d        D = max(d_pos, d_neg) / (n m), scipy.stats.ks_2samp's statistic; NaN for an undefined pair
   ks_sign     +1 where d_pos >= d_neg (the first bag's CDF lies above at the widest gap: its values tend lower), else -1; 0: undefined
   ks_p_value  Q(lambda), lambda = sqrt(n m / (n + m)) D, Q the Kolmogorov limit distribution: scipy.stats.kstwobign.sf(lambda), NOT
-              ks_2samp's p (exact for small bags); the limit is conservative for small bags.  The exact small-sample p is not built.
-  ks_rows     the lines of data.diff_ks.csv;  signal_ks_rows  those of data.diff_signal_ks.csv, nine per pair, one BH family"""
+              ks_2samp's p (exact for small bags); the limit is conservative for small bags
+  ks_h        h = max(d_pos, d_neg), the statistic in units of 1 / (n m) as m6a_ks_exact takes it (include/m6a.h); -1: undefined
+  ks_rows     the lines of data.diff_ks.csv;  signal_ks_rows  those of data.diff_signal_ks.csv, nine per pair, one BH family.  Given
+              p_exact, m6a_ks_exact's p-values of the same tests (`eventalign_diff --ks_exact`), p_value is the exact one wherever it
+              is not NaN and Q(lambda) elsewhere, q_value corrects p_value as written, and a last column p_method says which it is"""
 import math
 
 import numpy as np
@@ -32,6 +35,8 @@ KS_FILE = "data.diff_ks.csv"
 SIGNAL_KS_HEADER = ("transcript_id,transcript_position,kmer,n_reads_a,n_reads_b,position_offset,feature,median_a,median_b,median_shift,"
                     "ks_d,ks_sign,p_value,q_value")
 SIGNAL_KS_FILE = "data.diff_signal_ks.csv"
+P_METHOD_COLUMN = ",p_method"            # behind either KS header when the exact p-values are given
+P_METHODS = ("asymptotic", "exact")
 KS_SWITCH = 1.18                        # lambda below it: the theta-function form of Q; seven terms of either series
 _SQRT2 = math.sqrt(2.0)
 
@@ -130,6 +135,10 @@ def ks_d(d_pos, d_neg, n, m):
     return out
 
 
+def ks_h(d_pos, d_neg):
+    return np.maximum(np.asarray(d_pos, np.int64), np.asarray(d_neg, np.int64))
+
+
 def ks_sign(d_pos, d_neg):
     d_pos, d_neg = np.asarray(d_pos, np.int64), np.asarray(d_neg, np.int64)
     return np.where(d_pos < 0, 0, np.where(d_pos >= d_neg, 1, -1)).astype(np.int64)
@@ -160,44 +169,52 @@ def ks_p_value(d, n, m):
                      for v, i, j in zip(d.ravel().tolist(), n.ravel().tolist(), m.ravel().tolist())], np.float64).reshape(d.shape)
 
 
-def _ks_fields(d_pos, d_neg, med_a, med_b, n_a, n_b):
-    """per test, flat: the seven strings median_a .. q_value; one BH family over all of them"""
+def _ks_fields(d_pos, d_neg, med_a, med_b, n_a, n_b, p_exact=None):
+    """per test, flat: the seven strings median_a .. q_value, and p_method behind them where p_exact is given; one BH family over all
+    of them"""
     d_pos, d_neg = np.asarray(d_pos, np.int64).ravel(), np.asarray(d_neg, np.int64).ravel()
     med_a, med_b = np.asarray(med_a, np.float64).ravel(), np.asarray(med_b, np.float64).ravel()
     d = ks_d(d_pos, d_neg, n_a, n_b)
     sign = ks_sign(d_pos, d_neg)
     p = ks_p_value(d, n_a, n_b)
+    method = ()
+    if p_exact is not None:
+        p_exact = np.asarray(p_exact, np.float64).ravel()
+        assert p_exact.size == d.size
+        exact = ~np.isnan(p_exact)
+        p = np.where(exact, p_exact, p)                          # an item m6a_ks_exact leaves undefined keeps the limit's p (NaN: stays NaN)
+        method = [(P_METHODS[int(e)],) for e in exact]
     q = bh(p)
     with np.errstate(invalid="ignore"):
         shift = med_a - med_b                                    # inf - inf: NaN
     return [(_repr(float(med_a[k])), _repr(float(med_b[k])), _repr(float(shift[k])), _repr(float(d[k])), "%d" % sign[k] if sign[k] else "nan",
-             _repr(float(p[k])), _repr(float(q[k]))) for k in range(d.size)]
+             _repr(float(p[k])), _repr(float(q[k]))) + (method[k] if method else ()) for k in range(d.size)]
 
 
-def ks_rows(tx, pos, kmer, n_a, n_b, d_pos, d_neg, med_a, med_b):
+def ks_rows(tx, pos, kmer, n_a, n_b, d_pos, d_neg, med_a, med_b, p_exact=None):
     """The data lines of data.diff_ks.csv (no header, each with its newline) for P pairs: tx, pos, kmer, n_a, n_b as diff_rows takes them
     and the four outputs [P] of m6a_site_ks.  median_shift = median_a - median_b; floats are repr(float), ks_sign is 1 or -1, and an
-    undefined pair is `nan` in all seven; q_value is Benjamini-Hochberg over the rows whose p is not NaN."""
+    undefined pair is `nan` in all seven; q_value is Benjamini-Hochberg over the rows whose p is not NaN.  p_exact [P]: see above."""
     n_a, n_b = np.asarray(n_a, np.int64).ravel(), np.asarray(n_b, np.int64).ravel()
-    f = _ks_fields(d_pos, d_neg, med_a, med_b, n_a, n_b)
+    f = _ks_fields(d_pos, d_neg, med_a, med_b, n_a, n_b, p_exact)
     return ["%s,%d,%s,%d,%d,%s\n" % (tx[k], pos[k], kmer[k], n_a[k], n_b[k], ",".join(f[k])) for k in range(len(f))]
 
 
-def ks_text(*columns):
-    return KS_HEADER + "\n" + "".join(ks_rows(*columns))
+def ks_text(*columns, p_exact=None):
+    return KS_HEADER + (P_METHOD_COLUMN if p_exact is not None else "") + "\n" + "".join(ks_rows(*columns, p_exact=p_exact))
 
 
-def signal_ks_rows(tx, pos, kmer, n_a, n_b, d_pos, d_neg, med_a, med_b):
+def signal_ks_rows(tx, pos, kmer, n_a, n_b, d_pos, d_neg, med_a, med_b, p_exact=None):
     """The data lines of data.diff_signal_ks.csv for P pairs and the four outputs [P, 9] of m6a_site_signal_ks: nine lines per pair in
     column order, SIGNAL_COLUMNS naming the column, the medians in the normalised units of X; q_value is Benjamini-Hochberg over all
-    9 P rows whose p is not NaN, one family."""
+    9 P rows whose p is not NaN, one family.  p_exact [P, 9]: see above."""
     n_a, n_b = np.asarray(n_a, np.int64).ravel(), np.asarray(n_b, np.int64).ravel()
     P = n_a.size
-    f = _ks_fields(d_pos, d_neg, med_a, med_b, np.repeat(n_a, N_SIGNAL), np.repeat(n_b, N_SIGNAL))
+    f = _ks_fields(d_pos, d_neg, med_a, med_b, np.repeat(n_a, N_SIGNAL), np.repeat(n_b, N_SIGNAL), p_exact)
     assert len(f) == P * N_SIGNAL
     return ["%s,%d,%s,%d,%d,%d,%s,%s\n" % (tx[k], pos[k], kmer[k], n_a[k], n_b[k], SIGNAL_COLUMNS[c][0], SIGNAL_COLUMNS[c][1],
                                           ",".join(f[k * N_SIGNAL + c])) for k in range(P) for c in range(N_SIGNAL)]
 
 
-def signal_ks_text(*columns):
-    return SIGNAL_KS_HEADER + "\n" + "".join(signal_ks_rows(*columns))
+def signal_ks_text(*columns, p_exact=None):
+    return SIGNAL_KS_HEADER + (P_METHOD_COLUMN if p_exact is not None else "") + "\n" + "".join(signal_ks_rows(*columns, p_exact=p_exact))

@@ -11,9 +11,15 @@ Benjamini-Hochberg over all rows of that file, nine tests per site in one family
 With --ks the two-sample Kolmogorov-Smirnov test and the medians follow the rank-sum launch (include/m6a.h: m6a_site_ks) with the same
 pair indices on the two read_prob arrays: 32 bytes per pair come back (d_pos, d_neg, med_a, med_b) and OUT/data.diff_ks.csv holds
 median_a, median_b, median_shift = median_a - median_b, ks_d, ks_sign, p_value and q_value per shared site.  p_value is the Kolmogorov
-limit distribution at sqrt(n m / (n + m)) D, conservative for small bags; the exact small-sample p-value is not built.  With --signal
---ks m6a_site_signal_ks also runs on the two X and OUT/data.diff_signal_ks.csv holds nine rows per site, one Benjamini-Hochberg
-family, its medians in the normalised units of X (their conversion to pA is not built).  Every other file keeps its bytes."""
+limit distribution at sqrt(n m / (n + m)) D, conservative for small bags.  With --signal --ks m6a_site_signal_ks also runs on the two
+X and OUT/data.diff_signal_ks.csv holds nine rows per site, one Benjamini-Hochberg family, its medians in the normalised units of X
+(their conversion to pA is not built).  Every other file keeps its bytes.
+With --ks --ks_exact one more launch follows each of the two (include/m6a.h: m6a_ks_exact): the host forms h = max(d_pos, d_neg) from
+what has come back, (n, m, h) go up -- 24 bytes per test, nine tests per site under --signal -- and the exact finite-sample p-value,
+scipy.stats.ks_2samp's, comes back, 8 bytes per test.  In both KS files p_value is then the exact value wherever the test is defined
+(both bags non-empty and without NaN, the shorter at most 2047 reads, n m at most 10^8) and the limit's value elsewhere, q_value is
+Benjamini-Hochberg over p_value as written, and a last column p_method says `exact` or `asymptotic`.  Every other file keeps its bytes,
+and without --ks_exact so do these two."""
 import os
 import pathlib
 import sys
@@ -44,9 +50,14 @@ def argparser():
     parser.add_argument("--ks", action="store_true",
                         help="also write data.diff_ks.csv: per shared site the medians of the two conditions' read probabilities, their "
                              "difference median_a - median_b, and the two-sample Kolmogorov-Smirnov statistic with its sign, the p-value of "
-                             "the Kolmogorov limit distribution (conservative for small bags; not scipy.stats.ks_2samp's exact p) and its "
-                             "Benjamini-Hochberg q_value.  With --signal also data.diff_signal_ks.csv: the same on each of the nine signal "
-                             "features, medians in normalised units, nine rows per site in one family.")
+                             "the Kolmogorov limit distribution (conservative for small bags; --ks_exact gives scipy.stats.ks_2samp's exact p "
+                             "instead) and its Benjamini-Hochberg q_value.  With --signal also data.diff_signal_ks.csv: the same on each of the "
+                             "nine signal features, medians in normalised units, nine rows per site in one family.")
+    parser.add_argument("--ks_exact", action="store_true",
+                        help="with --ks: p_value in data.diff_ks.csv and data.diff_signal_ks.csv is the exact finite-sample p-value of the "
+                             "Kolmogorov-Smirnov statistic, what scipy.stats.ks_2samp(method='exact') returns, wherever the shorter bag has at "
+                             "most 2047 reads and the product of the two sizes is at most 10^8, and the limit distribution's elsewhere; "
+                             "q_value corrects p_value as written and a last column p_method says `exact` or `asymptotic`.")
     return inference.add_site_proba(parser)
 
 
@@ -65,6 +76,8 @@ def argument_error(args):
         return "--seed must be between 0 and 2**32 - 1"
     if args.readcount_min < 1 or args.readcount_max < args.readcount_min:
         return "--readcount_min must be 1 or more and at most --readcount_max"
+    if args.ks_exact and not args.ks:
+        return "--ks_exact chooses the p-value of --ks and needs it"
     if str(args.device).lower().startswith("cpu"):
         return "--device cpu: this build runs the hot path on an MI355X only (no CPU fallback)"
     return None
@@ -154,6 +167,27 @@ def compare_ks(engine, sites_a, sites_b, pair_a, pair_b, signal=False):
     return tuple(o.cpu().numpy() for o in out)
 
 
+def exact_p(engine, n_a, n_b, d_pos, d_neg):
+    """m6a_ks_exact on what compare_ks brought back: the host forms h = max(d_pos, d_neg), (n, m, h) go up -- 24 bytes per test, the
+    bag sizes repeated for the nine columns of a signal pair -- and p, of d_pos's shape, comes back; NaN where the test is undefined"""
+    import numpy as np
+    import torch
+
+    from .. import ranksum
+    h = ranksum.ks_h(d_pos, d_neg)
+    if h.size == 0:
+        return np.zeros(h.shape, np.float64)
+    per_pair = h.size // int(np.size(n_a))                          # 1, or the nine columns
+    dev = "cuda:%d" % engine.device
+    up = [torch.from_numpy(np.ascontiguousarray(x, np.int64)).to(dev)
+          for x in (np.repeat(np.asarray(n_a).ravel(), per_pair), np.repeat(np.asarray(n_b).ravel(), per_pair), h.ravel())]
+    p = torch.empty(h.size, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(engine.device)
+    engine.ks_exact_ptrs(*[x.data_ptr() for x in up], h.size, p.data_ptr())
+    engine.sync()
+    return p.cpu().numpy().reshape(h.shape)
+
+
 def main(args):
     import threading
 
@@ -205,8 +239,10 @@ def main(args):
         with open(os.path.join(args.out_dir, ranksum.DIFF_FILE), "w") as f:
             f.write(text)
         if args.ks:
+            ks = compare_ks(engine, sa, sb, pair_a, pair_b)
+            exact = {"p_exact": exact_p(engine, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b], ks[0], ks[1])} if args.ks_exact else {}
             text = ranksum.ks_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b],
-                                   *compare_ks(engine, sa, sb, pair_a, pair_b))
+                                   *ks, **exact)
             with open(os.path.join(args.out_dir, ranksum.KS_FILE), "w") as f:
                 f.write(text)
         if args.signal:
@@ -216,8 +252,10 @@ def main(args):
             with open(os.path.join(args.out_dir, ranksum.SIGNAL_FILE), "w") as f:
                 f.write(text)
             if args.ks:
+                ks = compare_ks(engine, sa, sb, pair_a, pair_b, signal=True)
+                exact = {"p_exact": exact_p(engine, np.diff(sa.off)[pair_a], np.diff(sb.off)[pair_b], ks[0], ks[1])} if args.ks_exact else {}
                 text = ranksum.signal_ks_text(names_a[sa.site_tx[pair_a]], sa.tx_pos[pair_a], kmer, np.diff(sa.off)[pair_a],
-                                              np.diff(sb.off)[pair_b], *compare_ks(engine, sa, sb, pair_a, pair_b, signal=True))
+                                              np.diff(sb.off)[pair_b], *ks, **exact)
                 with open(os.path.join(args.out_dir, ranksum.SIGNAL_KS_FILE), "w") as f:
                     f.write(text)
         print("eventalign_diff: %d sites in both conditions, %d only in A, %d only in B"
